@@ -10,6 +10,17 @@ ones inside the same solve (max_iter = W+K), the split being taken from the
 per-iteration host clock the library stamps after each iteration's final stream
 synchronisation.  The whole call is bracketed by barrier + cuda.synchronize.
 The problem is uploaded before the loop starts (inputs resident in HBM).
+The headline solve runs all of its iterations whatever --steps is: min_iter =
+max_iter keeps the tol-1e-4 stop (met after ~1050 iterations) from ending it
+early, so windows beyond that point time the solver's post-convergence
+iterations (where its rank rule may raise the target rank).
+
+--dump-outputs DIR (headline workload): after the timed steps, what the headline
+solve returned after its last step -- primal, dual_cone, dual_eq, dual_in,
+slack_eq, slack_in, objective scalars, the last window's trace without its clock
+column -- as float64 DIR/<name>.npy, outputs with no entries left out; the two n(n+1)/2 vectors as a fixed,
+seeded sample of 2^20 entries (~17 MB in all).  The instance is seeded, so two
+builds run with the same arguments can be compared file by file.
 
 N > 1: the single-PSD-block path does not shard (SURVEY.md section 8e,
 DESIGN.md section 8) -> N independent replicas (seed = rank), no data-path
@@ -57,6 +68,12 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec
+
+
+DUMP_SAMPLE = 1 << 20         # --dump-outputs: longer outputs are written as this many entries at seeded indices
+DUMP_SEED = 0
+DUMP_TRACE_ROWS = 1 << 16
+DUMP_MAX_BYTES = 64 << 20
 
 
 def main():
@@ -126,6 +143,9 @@ def main():
     ap.add_argument("--no-config-legs", action="store_true",
                     help="skip the compact legs of BASELINE configs 3 / 4 / 5 (config_randsdp, config_mimo_x8, config_sdplib) "
                          "that ride in the default line")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline solve returned after its last step to DIR/<name>.npy "
+                         "(float64; outputs longer than %d entries as a fixed, seeded sample)" % DUMP_SAMPLE)
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -157,6 +177,8 @@ def main():
     if binding.device_count() <= 0:
         raise SystemExit("bench.py needs a HIP device (no CPU fallback)")
     if args.workload != "maxcut":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs is implemented for the headline workload (maxcut) only")
         leg = {"mimo": bench_mimo, "randsdp": bench_randsdp, "sdplib": bench_sdplib}[args.workload]
         line = leg(args, torch, dist, rank, world, dev_id, backend)
         if rank == 0:
@@ -190,7 +212,9 @@ def main():
     # by max_target_rank_krylov_eigs (prox_operators.jl:46-49); where --steps/--warmup land does not
     # change the regime.
     NWIN = max(1, args.windows)
-    opt = Optimizer(max_iter=W + NWIN * K, device_id=dev_id, profile_symv_every=args.profile_every,
+    # min_iter = max_iter: the optimality stop cannot end the solve before the last timed step (the pinned solve meets
+    # tol 1e-4 after ~1050 iterations); until the iteration where it would have stopped, the iterates are the same
+    opt = Optimizer(max_iter=W + NWIN * K, min_iter=W + NWIN * K, device_id=dev_id, profile_symv_every=args.profile_every,
                     support_path=args.support_path, lanczos_operator=args.lanczos_operator,
                     initial_target_rank=r0, max_target_rank_krylov_eigs=kry, **extra_opts(args))
     sync()
@@ -232,6 +256,8 @@ def main():
         "roofline": step_roofline(st, n, N, r0, krylovdim, mv_step, 1e3 * t_steps / K),
         "solve_wall_s": wall, "init_s": st["init_time"], "exit_s": st["exit_time"],
     }
+    if args.dump_outputs and rank == 0:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, sol, opt, K)
 
     if W > W0 and len(sol.trace) >= W0 + K:
         # the same solve's cold-start window (what --settle 0 would have timed): first projections of a
@@ -244,7 +270,7 @@ def main():
     if solo and not args.no_early_leg:
         # the first iterations of a solve with reference default options (target rank 2..5): the
         # cheapest regime, 25-46 mat-vecs per iteration -- side figure only
-        o4 = Optimizer(max_iter=W0 + K, device_id=dev_id, profile_symv_every=args.profile_every,
+        o4 = Optimizer(max_iter=W0 + K, min_iter=W0 + K, device_id=dev_id, profile_symv_every=args.profile_every,
                        support_path=args.support_path, lanczos_operator=args.lanczos_operator, **extra_opts(args))
         s4 = o4.optimize(pr, trace_capacity=W0 + K)
         t4, mv4, tr4, rk4 = window(s4, W0, K)
@@ -256,7 +282,7 @@ def main():
     if solo and not args.no_packed_leg:
         # HBM evidence: the same early window with the reference's operator -- every mat-vec streams
         # the packed triangle through the tile kernel (8N + 16n bytes per launch, what dsymv('U') reads)
-        o1 = Optimizer(max_iter=W0 + K, device_id=dev_id, profile_symv_every=args.profile_every,
+        o1 = Optimizer(max_iter=W0 + K, min_iter=W0 + K, device_id=dev_id, profile_symv_every=args.profile_every,
                        support_path=args.support_path, lanczos_operator=0)
         s1 = o1.optimize(pr, trace_capacity=W0 + K)
         t1 = window(s1, W0, K)[0]
@@ -519,6 +545,47 @@ def medium_blocks_leg(dev_id):
     rows["round5_us_per_iteration"] = {"sensorloc_n100": 1025, "sensorloc_n200": 1715, "mcp124-1": 368, "mcp250-1": 336,
                                        "source": "profiles/r05_cycle_medium.md, profiles/r05_runbench.md"}
     return rows
+
+
+def dump_outputs(path, sol, opt, k):
+    """--dump-outputs: what a caller of the headline solve receives after its last step, one float64 .npy per output.
+    The inputs are fixed by the arguments (seeded instance), so two builds can be compared file by file.  An output with
+    more than DUMP_SAMPLE entries (primal and dual_cone: n(n+1)/2 = 8 002 000 at n = 4000) is written as the entries at a
+    fixed, seeded, sorted sample of its indices; "trace" is the last timed window's per-iteration record without its
+    wall-clock column.  An output with no entries (dual_in and slack_in of a model without inequality rows, as Max-Cut)
+    gets no file and is named in "omitted_empty"."""
+    from proxsdp_jl_amd.binding import TRACE_NAMES
+    os.makedirs(path, exist_ok=True)
+    outs = {"primal": sol.primal, "dual_cone": sol.dual_cone, "dual_eq": sol.dual_eq, "dual_in": sol.dual_in,
+            "slack_eq": sol.slack_eq, "slack_in": sol.slack_in,
+            "objective": [opt.objective_value(), opt.dual_objective_value(), sol.gap, sol.primal_residual,
+                          sol.dual_residual, sol.iter, sol.final_rank, sol.status]}
+    clock = TRACE_NAMES.index("elapsed")
+    outs["trace"] = np.delete(sol.trace[-min(k, DUMP_TRACE_ROWS):], clock, axis=1)
+    sampled, empty = {}, []
+    for name in list(outs):
+        a = np.asarray(outs[name], dtype=np.float64)
+        if a.size == 0:                       # e.g. dual_in / slack_in of a model without inequality rows
+            empty.append(name)
+            del outs[name]
+            continue
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.ravel()[idx]
+            sampled[name] = "%d of %d entries (seed %d)" % (DUMP_SAMPLE, len(outs[name]), DUMP_SEED)
+        outs[name] = a
+    total = sum(a.nbytes for a in outs.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES))
+    for name in empty:                        # no stale file of an earlier run under the name of an omitted output
+        if os.path.exists(os.path.join(path, name + ".npy")):
+            os.remove(os.path.join(path, name + ".npy"))
+    for name, a in outs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": sorted(outs), "bytes": total, "sampled": sampled, "omitted_empty": empty,
+            "objective_fields": ["objective", "dual_objective", "gap", "primal_residual", "dual_residual", "iterations",
+                                 "final_rank", "status"],
+            "trace_columns": [c for c in TRACE_NAMES if c != "elapsed"]}
 
 
 def compact(line):
