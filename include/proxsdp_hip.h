@@ -47,7 +47,9 @@ extern "C" {
  * new reserved slots -- offsets of every earlier member unchanged, struct_size larger), proxsdp_stats grew at its end
  * (proxsdp_result with it: it is the LAST member); a Krylov dimension beyond 255 is served by the dense eigensolver
  * instead of PROXSDP_E_INVALID; new proxsdp_state and
- * proxsdp_hip_solve_ex (capture / resume of the solver state at an iteration boundary); PROXSDP_E_COMM_ABORTED */
+ * proxsdp_hip_solve_ex (capture / resume of the solver state at an iteration boundary); PROXSDP_E_COMM_ABORTED;
+ * later: proxsdp_options gained lanczos_wide_krylov (from reserved_i2[0]), proxsdp_stats wide_krylov_projections
+ * (from reserved_s[0]): same struct sizes and offsets, version unchanged */
 #define PROXSDP_HIP_ABI_VERSION 9
 
 /* error codes (negative return values) */
@@ -362,7 +364,13 @@ typedef struct proxsdp_options {
                                   * 1 / 2 / 4 groups): a cycle is bound by its chain of dependent launches on the GPU (135 us of
                                   * the 200), kernels of different streams do not overlap enough to pay for twice the launches --
                                   * kept as an opt-in for models with many more blocks */
-    int32_t reserved_i2[8];      /* zero */
+    int32_t lanczos_wide_krylov; /* Krylov dimensions 256..511 (target rank up to 255, eigsolver_min_lanczos up to 511): 0 (default) =
+                                  * the dense eigensolver serves those projections (dense_truncated_projections); 1 = the
+                                  * wide Lanczos kernels run them on the device (KrylovKit's thick restart, as for the narrow
+                                  * dimensions; wide_krylov_projections counts them).  Larger dimensions stay dense either way.
+                                  * The workspace is wide only for a block whose max(2 max_target_rank_krylov_eigs + 1,
+                                  * eigsolver_min_lanczos) exceeds 255.  Other values: PROXSDP_E_INVALID */
+    int32_t reserved_i2[7];      /* zero */
     double  full_eig_lanczos_warm_pow; /* start vector of a Lanczos-served full_eig! (positive-part run, the library's own engine): the
                                   * previous projection's Ritz vectors are summed with weights (lam_0 / lam_c)^p -- the pairs with the SMALL
                                   * eigenvalues are the ones such a run converges last, so they get the larger share.  Default 1.0
@@ -441,7 +449,9 @@ typedef struct proxsdp_stats {
     int64_t dense_truncated_projections;  /* Krylov-branch projections whose krylovdim = max(2 target_rank + 1, eigsolver_min_lanczos)
                                            * exceeds the step kernels' 255 columns: served by the dense eigensolver (top target_rank
                                            * pairs of dsyevd, the same truncated projection and min_eig); status_string says so */
-    int64_t reserved_s[7];                /* zero */
+    int64_t wide_krylov_projections;      /* Krylov-branch projections with a Krylov dimension of 256..511 run by the wide Lanczos
+                                           * kernels (lanczos_wide_krylov = 1) */
+    int64_t reserved_s[6];                /* zero */
 } proxsdp_stats;
 
 /* Result (structs.jl:60-81).  Arrays are caller-allocated with the stated

@@ -117,7 +117,8 @@ struct Stats                     # proxsdp_stats
     full_eigs_lanczos_cert_failed::Int64
     cert_matvecs::Int64
     dense_truncated_projections::Int64
-    reserved_s::NTuple{7,Int64}
+    wide_krylov_projections::Int64
+    reserved_s::NTuple{6,Int64}
 end
 
 mutable struct CResult           # proxsdp_result

@@ -113,7 +113,7 @@ def _opt_fields():
     a("sign_start_row", i32); a("general_batch", i32); a("full_eig_lanczos_certify", i32); a("host_merge_threads", i32); a("reserved_i", i32 * 1)
     a("full_eig_lanczos_tol", f64); a("reserved_d", f64 * 1)
     a("equilibration_reference_aliasing", i32); a("reserved_i3", i32 * 2)
-    a("block_batch_groups", i32); a("reserved_i2", i32 * 8); a("full_eig_lanczos_warm_pow", f64); a("reserved_d2", f64 * 3)
+    a("block_batch_groups", i32); a("lanczos_wide_krylov", i32); a("reserved_i2", i32 * 7); a("full_eig_lanczos_warm_pow", f64); a("reserved_d2", f64 * 3)
     return F
 
 
@@ -140,7 +140,7 @@ class Stats(C.Structure):
                 ("batched_profiled_blocks", i64), ("host_eig_merges", i64),
                 ("host_eig_overlap_time", f64), ("sign_short_pass", i64), ("sign_short_fail", i64),
                 ("full_eigs_lanczos_certified", i64), ("full_eigs_lanczos_cert_failed", i64), ("cert_matvecs", i64),
-                ("dense_truncated_projections", i64), ("reserved_s", i64 * 7)]
+                ("dense_truncated_projections", i64), ("wide_krylov_projections", i64), ("reserved_s", i64 * 6)]
 
 
 class Result(C.Structure):

@@ -168,6 +168,8 @@ inline void Solver::project_block(int idx, const double* xin, double* xout, bool
     // zero off the support) and the update is the sparse support update of this iteration
     W.use_fop = !lanczos_done && fuse && use_support && opt.lanczos_operator != 0 && W.fop_ok && krylov &&
                 (W.have_factors || W.x_prev_sparse) && !(opt.krylovkit_eager && opt.eigsolver != 1);
+    // (a Krylov dimension beyond the step kernels -- the wide kernels or the dense stand-in -- takes the packed-tile mat-vec)
+    if (std::max(2 * (int)target_rank[idx] + 1, (int)opt.eigsolver_min_lanczos) > dev::MAXK - 1) W.use_fop = false;
     if (W.use_fop) {
         if (!W.have_factors) { W.F_r = 0; W.F_first = 0; }
         W.esv = esv_d.p + (W.have_factors ? 0 : ns);
@@ -349,7 +351,8 @@ inline bool Solver::full_eig_by_lanczos(int idx, const double* xp, double* xo, b
     if (opt.full_eig_lanczos == 0 || opt.eigsolver == 1 || W.n <= opt.min_size_krylov_eigs) return false;
     if (W.last_npos < 0) return false;                       // no estimate yet: dense eigensolver first
     if (W.fel_disabled) return false;                        // a verification failed earlier in this solve
-    const int maxnev = std::min((W.cap - 2) / 2, W.n - 1);   // krylovdim = 2 nev + 1 <= cap - 1
+    // krylovdim = 2 nev + 1 <= cap - 1, and never beyond the step kernels' 255 columns (a wide workspace included)
+    const int maxnev = std::min((std::min(W.cap, dev::MAXK - 4) - 2) / 2, W.n - 1);
     int g = W.last_npos + std::max(3, W.last_npos / 8);
     if (8 * W.last_npos > W.n) return false;                 // many positive pairs: the dense solver is the cheaper tool
     const bool used_fop = W.use_fop;

@@ -33,6 +33,7 @@
 #include "kernels.hip.hpp"
 #include "lanczos_cycle.hip.hpp"
 #include "lanczos_block1.hip.hpp"
+#include "lanczos_wide.hip.hpp"
 #include "small_sign.hip.hpp"
 #include "sign_project.hip.hpp"
 #include "rccl_dl.hpp"
@@ -152,6 +153,11 @@ struct LzRun {
     int howmany = 0, numiter = 1, converged = 0, K = 0, kfirst = 0, pos_count = -1, m_arrow = 0;
     bool pos_fail = false, presymv = false;
     double betaK = 0.0;
+    // where the cycle's read-back lands: alphas at rec[0..), betas at rec[rec_ld..), LanczosCtl at rec[2 rec_ld]
+    // (the narrow record, or the wide one of Solver::lanczos_wide)
+    const double* rec = nullptr;
+    int rec_ld = 0;
+    bool wide = false;                // run of the wide kernels (lanczos_wide.hip.hpp): no arrow part, wide rotation
     // split + rank-one merge (host_eig_merge.hpp): first part solved under the GPU's cycle.  The solver object lives
     // in the block's workspace (its ~0.5 MB of tables are reused across projections, not re-allocated per call)
     SplitEig* splitp = nullptr;
@@ -177,6 +183,14 @@ struct EigWork {
     double* rec_host = nullptr;
     static constexpr size_t REC_DOUBLES = 2 * dev::MAXK + sizeof(dev::LanczosCtl) / sizeof(double);
     static constexpr size_t USTAGE_DOUBLES = (size_t)dev::MAXK * dev::MAXK + 2 * dev::MAXK;
+    size_t ustage_doubles = USTAGE_DOUBLES;   // U / Ustage capacity of THIS workspace (wide: LZW_MAXK^2 + 2 LZW_MAXK)
+    // wide Lanczos (options.lanczos_wide_krylov = 1, Krylov dimension 256..511): own records, sized only when the block's
+    // largest Krylov dimension exceeds 255 (the narrow buffers above are kept: the positive-part engine uses them)
+    bool wide = false;
+    DevBuf<double> hpw1, hpw2, hsw1, hsw2, recw;   // partial dots [pld x KW] + |w'|^2 records [pld], their sums [KW + 1], alphas | betas | ctl
+    PinnedBuf recw_pinned;
+    dev::LanczosCtl* ctlw_p = nullptr;
+    static constexpr size_t RECW_DOUBLES = 2 * dev::LZW_MAXK + sizeof(dev::LanczosCtl) / sizeof(double);
     // full-eig fallback
     DevBuf<double> A, D, E;
     DevBuf<rocblas_int> info;
@@ -358,6 +372,8 @@ public:
     bool lz_after_cycle(EigWork& W, struct LzRun& R, bool speculated);
     void lz_finish_run(EigWork& W, struct LzRun& R);
     void lanczos_eager(EigWork& W, const double* xp, int nev);
+    void lanczos_wide(EigWork& W, const double* xp, int nev);
+    void lzw_step(EigWork& W, const double* xp, int k, int kfirst, double step_tol, bool& presymv);
     void lz_merge_vectors(EigWork& W, struct LzRun& R, int ncols);
     bool lz_split_first(EigWork& W, struct LzRun& R, int k1);
     void full_eig_values(EigWork& W, const double* xp, double offscale, bool vectors, std::vector<double>& Dhost);
@@ -371,7 +387,7 @@ public:
     void launch_block1(EigWork& W, const double* xp, int kfirst, int krylovdim, double tol);
     bool sg48_ok = false;                         // 72 KiB of dynamic LDS granted to k_sym_gemm48 (setup_device)
     DevBuf<long long> cy_dbg;                     // PROXSDP_HIP_DEBUG_CYCLE: per-phase tick sums
-    void launch_symv(EigWork& W, const double* xp, const double* v, bool use_ctl);
+    void launch_symv(EigWork& W, const double* xp, const double* v, bool use_ctl, dev::LanczosCtl* ctl = nullptr);
     void launch_symv_finish(EigWork& W, const double* xp, int kclose, double tol, bool use_carry);
     void launch_reconstruct(EigWork& W, const double* Z, int ldz, const double* lam, int r, double* xp_out,
                             const double* xp_old = nullptr, int blk = -1);
@@ -611,7 +627,13 @@ private:
         const double tmin = std::min({opt.tol_gap, opt.tol_feasibility, opt.tol_primal, opt.tol_dual});
         return tmin > 0.0 ? std::min(base, 1e-2 * tmin) : base;
     }
-    bool krylovdim_fits(int nev) const { return std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos) <= dev::MAXK - 1; }
+    // the step kernels run Krylov dimensions up to 255; with lanczos_wide_krylov = 1 the wide kernels up to 511 (not under
+    // krylovkit_eager, whose driver is written on the step kernels)
+    bool krylovdim_fits(int nev) const {
+        const int kd = std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos);
+        if (kd <= dev::MAXK - 1) return true;
+        return opt.lanczos_wide_krylov == 1 && kd <= dev::LZW_MAXK - 1 && !(opt.krylovkit_eager && opt.eigsolver != 1);
+    }
     bool exact_projection_by_sign(int idx, const double* xp, double* xo, bool fuse, int nev);
     void verify_sign_engine(int idx, const double* xo);
     template <int EPI, bool FUSE>
@@ -668,7 +690,10 @@ inline void Solver::alloc_eigwork(EigWork& W, int n, int max_nev) {
     // the step kernels hold up to dev::MAXK - 1 = 255 basis columns; a projection whose Krylov dimension
     // max(2 target_rank + 1, eigsolver_min_lanczos) is larger (options.jl:76,88 accept any value) is served by the dense
     // eigensolver instead (Solver::truncated_project_dense): the workspace is sized for what the kernels can run
-    int kd = std::min(std::max(2 * max_nev + 1, (int)opt.eigsolver_min_lanczos), dev::MAXK - 1);
+    // (with lanczos_wide_krylov = 1 up to 511 columns: the wide kernels, lanczos_wide.hip.hpp)
+    const int kd_want = std::max(2 * max_nev + 1, (int)opt.eigsolver_min_lanczos);
+    W.wide = opt.lanczos_wide_krylov == 1 && kd_want > dev::MAXK - 1;
+    int kd = std::min(kd_want, W.wide ? dev::LZW_MAXK - 1 : dev::MAXK - 1);
     W.cap = kd + 1;
     W.V.alloc((size_t)W.npad * W.cap);
     W.Z.alloc((size_t)W.npad * W.cap);
@@ -689,8 +714,22 @@ inline void Solver::alloc_eigwork(EigWork& W, int n, int max_nev) {
     W.ctl_p = reinterpret_cast<dev::LanczosCtl*>(W.rec.p + 2 * dev::MAXK);
     W.rec_pinned.alloc(EigWork::REC_DOUBLES);
     W.rec_host = W.rec_pinned.p;
-    W.U.alloc(EigWork::USTAGE_DOUBLES);
-    W.Ustage[0].alloc(EigWork::USTAGE_DOUBLES); W.Ustage[1].alloc(EigWork::USTAGE_DOUBLES);
+    W.ustage_doubles = W.wide ? (size_t)dev::LZW_MAXK * dev::LZW_MAXK + 2 * dev::LZW_MAXK : EigWork::USTAGE_DOUBLES;
+    W.U.alloc(W.ustage_doubles);
+    W.Ustage[0].alloc(W.ustage_doubles); W.Ustage[1].alloc(W.ustage_doubles);
+    if (W.wide) {
+        // records of the nt producers: V'w at [g * KW, g * KW + KW), |w'|^2 at pld * KW + g (g < nt <= pld; nt reaches 725 at
+        // side 46340, beyond KW: the norm records get a row of their own, sized by pld)
+        if (W.nt > W.pld) throw std::logic_error("wide Lanczos: more producers than partial-dot records");
+        const size_t hpw_doubles = dev::lzw_hpart_doubles(W.pld);
+        W.hpw1.alloc(hpw_doubles); W.hpw2.alloc(hpw_doubles);
+        W.hpw1.zero(stream); W.hpw2.zero(stream);
+        W.hsw1.alloc(dev::KW + 1); W.hsw2.alloc(dev::KW + 1);
+        W.hsw1.zero(stream); W.hsw2.zero(stream);
+        W.recw.alloc(EigWork::RECW_DOUBLES); W.recw.zero(stream);
+        W.ctlw_p = reinterpret_cast<dev::LanczosCtl*>(W.recw.p + 2 * dev::LZW_MAXK);
+        W.recw_pinned.alloc(EigWork::RECW_DOUBLES);
+    }
     W.arrow_p = W.arrow.p;
     W.lam.alloc(std::max(n, dev::MAXK));
     W.resid.alloc(W.npad);
@@ -704,6 +743,7 @@ inline void Solver::setup_device() {
     PX_HIP(hipGetDeviceCount(&ndev));
     if (ndev <= 0) throw HipError("no HIP device available");
     if (opt.device_id < 0 || opt.device_id >= ndev) throw std::invalid_argument("device_id out of range");
+    if (opt.lanczos_wide_krylov != 0 && opt.lanczos_wide_krylov != 1) throw std::invalid_argument("lanczos_wide_krylov must be 0 or 1");
     PX_HIP(hipSetDevice(opt.device_id));
     PX_HIP(hipStreamCreate(&stream.main));
     // gfx950: 160 KiB of LDS per CU.  The restart rotation at K = 127, keep = 78 needs 145 KiB (U tile + V tile): with 144 KiB
@@ -922,7 +962,7 @@ static inline void launch_prof(bool prof, hipEvent_t e0, hipEvent_t e1, K kern, 
     else hipLaunchKernelGGL(kern, grid, dim3(dev::TPB), 0, stream, args...);
 }
 
-inline void Solver::launch_symv(EigWork& W, const double* xp, const double* v, bool use_ctl) {
+inline void Solver::launch_symv(EigWork& W, const double* xp, const double* v, bool use_ctl, dev::LanczosCtl* ctl) {
     const int ntile = 8 * ceil_div(W.nt * (W.nt + 1) / 2, 8);     // one workgroup per 64x64 tile, padded to 8 XCDs
     bool prof = opt.profile_symv_every > 0 && (W.lst.symv_launches % opt.profile_symv_every) == 0;
     size_t slot = 0;
@@ -945,7 +985,7 @@ inline void Solver::launch_symv(EigWork& W, const double* xp, const double* v, b
                     W.ebuf.p, W.apartf.p, (const dev::LanczosCtl*)(use_ctl ? W.ctl_p : nullptr), W.ov);
     } else {
         launch_prof(prof, e0, e1, dev::k_symv_packed, dim3(ntile), stream,
-                    xp, W.n, W.nt, W.npad, v, W.Ppart.p, (const dev::LanczosCtl*)(use_ctl ? W.ctl_p : nullptr), W.Apart.p);
+                    xp, W.n, W.nt, W.npad, v, W.Ppart.p, (const dev::LanczosCtl*)(use_ctl ? (ctl ? ctl : W.ctl_p) : nullptr), W.Apart.p);
     }
     W.lst.symv_launches++;
     W.lst.symv_bytes += 8.0 * (double)W.N + 16.0 * (double)W.n;
@@ -1040,7 +1080,7 @@ inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int 
     W.ustage_next ^= 1;
     // `extra` (the arrow part f | D of the restarted Rayleigh quotient) rides behind U in the same
     // host-to-device copy; the kernels find it at W.arrow_p
-    if ((size_t)K * std::max(ncols, 1) + (size_t)std::max(nextra, 0) > EigWork::USTAGE_DOUBLES)
+    if ((size_t)K * std::max(ncols, 1) + (size_t)std::max(nextra, 0) > W.ustage_doubles)
         throw std::logic_error("rotation staging buffer too small");
     for (int c = 0; c < ncols; ++c)
         for (int j = 0; j < K; ++j) tmp[(size_t)c * K + j] = U[(size_t)c * ldu + j];
@@ -1053,6 +1093,12 @@ inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int 
     }
     W.U.upload(tmp, (size_t)K * ncols + (size_t)std::max(nextra, 0), stream);
     if (nextra > 0) W.arrow_p = W.U.p + (size_t)K * ncols;
+    if (W.lzrun.wide) {                                  // wide run: LDS-tiled over K (neither form below fits at K > 255)
+        if (ncols > 0 || copy_src >= 0)
+            hipLaunchKernelGGL(dev::k_lzw_rotate, dim3(W.nt, std::max(1, ceil_div(ncols, dev::LZW_RC))), dim3(dev::TPB), 0, stream,
+                               (const double*)W.V.p, W.npad, K, (const double*)W.U.p, ncols, out, W.npad, copy_src, copy_dst);
+        return;
+    }
     // fp64 MFMA form from K = 32 / 16 columns on (skinny GEMM); grid = row tiles x groups of 16 columns; LDS: V tile + one U group
     {
         const int Kp = (K + 3) & ~3;
@@ -1100,13 +1146,15 @@ inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int 
 // parameters of the run and the per-call reset of W; false = the call ends at once (dsaupd argument errors)
 inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     R.nev = nev; R.positive_part = positive_part;
+    R.wide = false;
     R.arpack = (opt.eigsolver == 1);
     int krylovdim = std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos);
     // positive-part mode is the library's own algorithm (not KrylovKit's call): a larger Krylov space
     // resolves the bulk-edge pairs that decide it with fewer restarts (options.full_eig_lanczos_kdim10)
     if (positive_part) {
         const int mult10 = opt.full_eig_lanczos_kdim10 > 0 ? opt.full_eig_lanczos_kdim10 : 30;
-        krylovdim = std::min(W.cap - 1, std::max(krylovdim, nev * mult10 / 10 + 8));
+        // (the engine keeps the step kernels' 255 columns in a wide workspace too)
+        krylovdim = std::min(std::min(W.cap, dev::MAXK - 4) - 1, std::max(krylovdim, nev * mult10 / 10 + 8));
     }
     if (krylovdim + 1 > W.cap) throw std::invalid_argument("Lanczos workspace too small for the requested rank");
     R.krylovdim = krylovdim;
@@ -1124,6 +1172,7 @@ inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     R.pos_fail = false; R.presymv = false; R.betaK = 0.0;
     R.split_ready = false; R.merge_active = false;
     R.splitp = &W.split;
+    R.rec = W.rec_host; R.rec_ld = dev::MAXK; R.wide = false;
     return true;
 }
 
@@ -1164,9 +1213,9 @@ inline bool Solver::lz_after_cycle(EigWork& W, LzRun& R, bool speculated) {
     std::vector<double>& T = R.T; std::vector<double>& D = R.D; std::vector<double>& U = R.U;
     std::vector<double>& f = R.f; std::vector<double>& al = R.al; std::vector<double>& be = R.be;
     dev::LanczosCtl hctl{};
-    std::copy(W.rec_host, W.rec_host + krylovdim, al.begin());
-    std::copy(W.rec_host + dev::MAXK, W.rec_host + dev::MAXK + krylovdim, be.begin());
-    std::memcpy(&hctl, W.rec_host + 2 * dev::MAXK, sizeof(hctl));
+    std::copy(R.rec, R.rec + krylovdim, al.begin());
+    std::copy(R.rec + R.rec_ld, R.rec + R.rec_ld + krylovdim, be.begin());
+    std::memcpy(&hctl, R.rec + 2 * R.rec_ld, sizeof(hctl));
     const int Kend = hctl.stop ? hctl.kstop : krylovdim;
     // launches after the stop flag are no-ops; count the mat-vecs that did work
     {
@@ -1266,9 +1315,10 @@ inline bool Solver::lz_after_cycle(EigWork& W, LzRun& R, bool speculated) {
                               : (3 * krylovdim + 2 * converged) / 5;
     // arrow part of the restarted T for k_lz_orth: f (couplings of v_K with the kept Ritz
     // vectors) and D (their Ritz values)
-    for (int j = 0; j < keep; ++j) { W.arrow_host.p[j] = f[j]; W.arrow_host.p[dev::MAXK + j] = D[j]; }
+    // (the wide kernels measure both passes: no arrow part)
+    if (!R.wide) for (int j = 0; j < keep; ++j) { W.arrow_host.p[j] = f[j]; W.arrow_host.p[dev::MAXK + j] = D[j]; }
     if (R.merge_active) lz_merge_vectors(W, R, keep);
-    rotate(W, K, U, K, keep, W.Z.p, K, keep, W.arrow_host.p, 2 * dev::MAXK);   // Z[:, :keep] = V U[:, :keep]; Z[:, keep] = V[:, K]
+    rotate(W, K, U, K, keep, W.Z.p, K, keep, W.arrow_host.p, R.wide ? 0 : 2 * dev::MAXK);   // Z[:, :keep] = V U[:, :keep]; Z[:, keep] = V[:, K]
     std::swap(W.V.p, W.Z.p);
     std::fill(T.begin(), T.end(), 0.0);
     for (int j = 0; j < keep; ++j) {
@@ -1584,6 +1634,14 @@ inline bool Solver::lanczos_certificate(EigWork& W, const double* xp, int npos, 
 }
 
 inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive_part) {
+    // Krylov dimension beyond the step kernels: the wide driver (never the cycle kernels, the one-workgroup kernel, the
+    // batched driver, the operator form or the eager driver -- all of them are written for at most 255 columns)
+    if (!positive_part && std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos) > dev::MAXK - 1) {
+        if (opt.krylovkit_eager && opt.eigsolver != 1)
+            throw std::invalid_argument("krylovkit_eager: Krylov dimension > 255 is not supported");
+        lanczos_wide(W, xp, nev);
+        return;
+    }
     if (opt.krylovkit_eager && opt.eigsolver != 1 && !positive_part) { lanczos_eager(W, xp, nev); return; }
     LzRun& R = W.lzrun;
     if (!lz_init(W, R, nev, positive_part)) return;
@@ -1725,6 +1783,65 @@ inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive
     const double tdbg2 = debug ? now_s() : 0.0;
     lz_finish_run(W, R);
     if (debug) dbg_lz[3] += now_s() - tdbg2;
+}
+
+// One step of the wide recurrence (lanczos_wide.hip.hpp): mat-vec, two measured Gram-Schmidt passes, closing.
+inline void Solver::lzw_step(EigWork& W, const double* xp, int k, int kfirst, double step_tol, bool& presymv) {
+    if (k == kfirst && presymv) {                  // after a restart the mat-vec of v_keep is already in Ppart
+        W.lst.symv_launches++; W.lst.symv_bytes += 8.0 * (double)W.N + 16.0 * (double)W.n;
+    } else {
+        launch_symv(W, xp, W.V.p + (size_t)k * W.npad, true, W.ctlw_p);
+    }
+    presymv = false;
+    const dev::LanczosCtl* ctl = W.ctlw_p;
+    const int nred = ceil_div(k + 2, dev::TPB);
+    hipLaunchKernelGGL(dev::k_lzw_dots, dim3(W.nt), dim3(dev::TPB), 0, stream,
+                       (const double*)W.Ppart.p, W.nt, W.npad, (const double*)W.V.p, W.npad, k, W.w.p, W.hpw1.p, ctl);
+    hipLaunchKernelGGL(dev::k_lzw_reduce, dim3(nred), dim3(dev::TPB), 0, stream,
+                       (const double*)W.hpw1.p, W.pld, W.nt, k, W.hsw1.p, ctl, 0);
+    hipLaunchKernelGGL(dev::k_lzw_update, dim3(W.nt), dim3(dev::TPB), 0, stream,
+                       W.w.p, (const double*)W.V.p, W.npad, k, (const double*)W.hsw1.p, W.hpw2.p, W.pld, ctl);
+    hipLaunchKernelGGL(dev::k_lzw_reduce, dim3(nred), dim3(dev::TPB), 0, stream,
+                       (const double*)W.hpw2.p, W.pld, W.nt, k, W.hsw2.p, ctl, 1);
+    hipLaunchKernelGGL(dev::k_lzw_close, dim3(W.nt), dim3(dev::TPB), 0, stream,
+                       (const double*)W.w.p, W.V.p, W.npad, k, (const double*)W.hsw1.p, (const double*)W.hsw2.p,
+                       W.recw.p, W.recw.p + dev::LZW_MAXK, W.ctlw_p, step_tol);
+}
+
+// KrylovKit's eigsolve for Krylov dimensions 256..511 (options.lanczos_wide_krylov = 1): the restart logic, the K x K
+// eigensolves, the convergence rules and the results are those of Solver::lanczos (lz_init / lz_after_cycle /
+// lz_finish_run); the recurrence runs on the wide kernels and the rotations on k_lzw_rotate.  Packed-tile mat-vec only.
+inline void Solver::lanczos_wide(EigWork& W, const double* xp, int nev) {
+    LzRun& R = W.lzrun;
+    if (!lz_init(W, R, nev, false)) return;
+    if (!W.wide) throw std::logic_error("lanczos_wide: workspace has no wide records");
+    R.rec = W.recw_pinned.p; R.rec_ld = dev::LZW_MAXK; R.wide = true;
+    const int krylovdim = R.krylovdim;
+    QlPool::get().arm();                              // host eigensolve helpers wake up under the first cycle
+    W.lst.wide_krylov_projections++;
+    hipLaunchKernelGGL(dev::k_lz_begin, dim3(ceil_div(W.npad, dev::TPB)), dim3(dev::TPB), 0, stream,
+                       W.V.p, (const double*)W.resid.p, W.npad, W.ctlw_p);
+    while (true) {
+        for (int k = R.kfirst; k < krylovdim; ++k) lzw_step(W, xp, k, R.kfirst, R.step_tol, R.presymv);
+        // the first mat-vec of a possible next cycle (v_K is final): as in Solver::lanczos
+        const bool speculate = W.prev_numiter > 1 || R.numiter > 1;
+        if (speculate) {
+            launch_symv(W, xp, W.V.p + (size_t)krylovdim * W.npad, true, W.ctlw_p);
+            W.lst.symv_launches--; W.lst.symv_bytes -= 8.0 * (double)W.N + 16.0 * (double)W.n;   // counted when used
+        }
+        PX_HIP(hipMemcpyAsync(W.recw_pinned.p, W.recw.p, EigWork::RECW_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
+        lz_prepare_arrow(R);                          // (host work under the GPU's cycle)
+        wait_stream();
+        if (W.ev.used) {                              // harvest profiled symv launches
+            for (size_t s = 0; s < W.ev.used; ++s) {
+                float ms = 0.f;
+                if (hipEventElapsedTime(&ms, W.ev.e0[s], W.ev.e1[s]) == hipSuccess) { W.lst.symv_profiled_ms += ms; W.lst.symv_profiled++; }
+            }
+            W.ev.used = 0;
+        }
+        if (!lz_after_cycle(W, R, speculate)) break;
+    }
+    lz_finish_run(W, R);
 }
 
 inline void Solver::flush_rotations(RotSink& S, BatchCtx& C) {
@@ -2287,7 +2404,7 @@ inline void Solver::merge_block_stats() {
         PX_MERGE(full_eig_solver_ms); PX_MERGE(full_eig_recon_ms);
         PX_MERGE(full_eigs_lanczos); PX_MERGE(full_eigs_lanczos_checks); PX_MERGE(full_eigs_lanczos_mismatches);
         PX_MERGE(full_eigs_lanczos_certified); PX_MERGE(full_eigs_lanczos_cert_failed); PX_MERGE(cert_matvecs);
-        PX_MERGE(dense_truncated_projections);
+        PX_MERGE(dense_truncated_projections); PX_MERGE(wide_krylov_projections);
         PX_MERGE(full_eigs_sign); PX_MERGE(sign_products); PX_MERGE(sign_short_pass); PX_MERGE(sign_short_fail);
         PX_MERGE(sign_engine_projections); PX_MERGE(sign_engine_rejected);
         PX_MERGE(sign_engine_checks); PX_MERGE(sign_engine_mismatches);
