@@ -231,18 +231,14 @@ typedef struct proxsdp_options {
                                   * positive eigenvalues, compute them with the Lanczos engine (all pairs down to the
                                   * first eigenvalue <= 0, converged to krylovkit_tol) and fall back to the dense
                                   * eigensolver otherwise; 0 = always the dense eigensolver.  Same projection. */
-    int32_t lanczos_cycle_kernel;/* 1 = run a whole Lanczos cycle (operator form) in ONE persistent launch whose <= 32
-                                  * workgroups sit on one XCD, keep their rows of the basis in LDS and exchange partial
-                                  * dots through that XCD's L2, instead of two launches per step (same arithmetic per
-                                  * step; falls back to the step kernels if its bounded spins time out): measured gain
-                                  * 1.3x per step, +5 % iterations/s, off in auto.
-                                  * 2 (round 6) = ONE WORKGROUP per Lanczos cycle for blocks of side <= 512 (csrc/
+    int32_t lanczos_cycle_kernel;/* 2 (round 6) = ONE WORKGROUP per Lanczos cycle for blocks of side <= 512 (csrc/
                                   * lanczos_block1.hip.hpp: basis in registers, operator and records in LDS, the restart
                                   * rotation in the prologue; the step kernels' arithmetic term by term: BIT-IDENTICAL
                                   * results); applies to the operator form with <= 16 factor columns and to a packed
                                   * triangle that fits in LDS (side <= ~140), Krylov dimension <= 31 -- anything else runs
                                   * the step kernels.  -1 auto = 2 for sides <= 256 (where it is 2.2-2.6x faster per step),
-                                  * step kernels beyond; 0 = step kernels always. */
+                                  * step kernels beyond; 0 = step kernels always.  1 selected a persistent multi-
+                                  * workgroup cycle kernel that has been removed: it now means 0. */
     int32_t lanczos_warm_start;  /* 0 (default): every KrylovKit projection starts from the fixed start vector, as the
                                   * reference does (krylovkit_reset_resid = false).  1: start from the normalised sum of
                                   * the previous projection's Ritz vectors (+ 1e-3 x the fixed vector).  Changes the
@@ -419,7 +415,7 @@ typedef struct proxsdp_stats {
     double  orth_profiled_ms;    /* sum of their durations                                       */
     double  full_eig_solver_ms;  /* full_eig!: dense eigensolver time (events; profile_symv_every > 0) */
     double  full_eig_recon_ms;   /* full_eig!: reconstruction kernel time (events)               */
-    int64_t cycle_launches;      /* Lanczos cycles run by the persistent LDS-resident kernel     */
+    int64_t cycle_launches;      /* Lanczos cycles run by the one-workgroup kernel (lanczos_cycle_kernel = 2) */
     int64_t full_eigs_lanczos;   /* full_eig! calls served by the Lanczos engine (all positive pairs) */
     int64_t cycle_steps;         /* Lanczos steps run inside those launches                       */
     double  cycle_ms;            /* their summed kernel time (events; profile_symv_every > 0)     */

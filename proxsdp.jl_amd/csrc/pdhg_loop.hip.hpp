@@ -83,8 +83,7 @@ inline bool Solver::krylov_branch(int idx) const {
 inline bool Solver::batch_eligible(int idx, bool fuse) const {
     const EigWork& W = eig[idx];
     if (opt.block_batch == 0 || !krylov_branch(idx)) return false;
-    if (opt.eigsolver == 1 || opt.psd_sign_engine == 1 || opt.lanczos_warm_start > 0 || opt.lanczos_cycle_kernel == 1 ||
-        opt.krylovkit_eager)
+    if (opt.eigsolver == 1 || opt.psd_sign_engine == 1 || opt.lanczos_warm_start > 0 || opt.krylovkit_eager)
         return false;
     // operator-form blocks keep their own path (their step kernels take per-block factor ranks)
     if (fuse && use_support && opt.lanczos_operator != 0 && W.fop_ok && (W.have_factors || W.x_prev_sparse)) return false;
@@ -1166,11 +1165,6 @@ inline void Solver::setup_support() {
             W.tpart.alloc((size_t)dev::MAXK * W.pld); W.tpart.zero(stream);
             W.ebuf.alloc(W.npad); W.ebuf.zero(stream);
             W.apartf.alloc(W.pld); W.apartf.zero(stream);
-            // persistent cycle kernel: granule buffers [64 workgroups][CY_CMAX][2], zero = never-valid tag
-            W.xg1.alloc((size_t)32 * dev::CY_CMAX); W.xg1.zero(stream);
-            W.xg2.alloc((size_t)32 * (dev::CY_CMAX + 128)); W.xg2.zero(stream);           // + the R rows of w'
-            W.xf1.alloc(32); W.xf1.zero(stream); W.xf2.alloc(32); W.xf2.zero(stream);     // flags: zero = never-valid epoch
-            W.cy_err.alloc(1); W.cy_err.zero(stream);
             W.warm_part.alloc(ceil_div(W.npad, dev::TPB)); W.warm_part.zero(stream);
             PX_HIP(hipStreamSynchronize(stream));                 // host vectors go out of scope
             W.fop_ok = true;
@@ -2046,17 +2040,6 @@ inline void Solver::run() {
     if (capture_state && capture_state->ints[3] == 0 && iter == capture_state->iteration) write_capture();
     for (EigWork& W : eig) harvest_full_eig_events(W);
     merge_block_stats();
-    if (cy_dbg.n) {
-        long long t[16];
-        cy_dbg.download(t, 16, stream);
-        PX_HIP(hipStreamSynchronize(stream));
-        const double sN = (double)std::max<long long>(st.cycle_steps, 1);
-        std::fprintf(stderr, "[cycle ticks/step @100MHz] closeA+opA %.1f |B %.1f |ei,vk,av+C %.1f | X1 %.1f | t,alpha,coef %.1f |H %.1f | w' dots %.1f |I+wp+put+fold %.1f |K %.1f | X2 %.1f (steps %lld)\n",
-                     t[0] / sN, t[1] / sN, t[2] / sN, t[3] / sN, t[4] / sN, t[5] / sN, t[6] / sN, t[7] / sN, t[8] / sN, t[9] / sN,
-                     (long long)st.cycle_steps);
-        std::fprintf(stderr, "[cycle] XCC id mask of the active workgroups: 0x%llx; shader clock during the cycles: %.0f MHz\n",
-                     (unsigned long long)t[15], t[10] > 0 ? 100.0 * (double)t[11] / (double)t[10] : 0.0);
-    }
     st.loop_time = now_s() - t_loop0;
     if (warm.joinable()) warm.join();
 

@@ -27,11 +27,13 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <tuple>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "host_util.hpp"
 #include "kernels.hip.hpp"
-#include "lanczos_cycle.hip.hpp"
 #include "lanczos_block1.hip.hpp"
 #include "lanczos_wide.hip.hpp"
 #include "small_sign.hip.hpp"
@@ -130,6 +132,24 @@ struct CircularVector {
 struct EigEvents {                  // optional profiling of the dominant kernel
     std::vector<hipEvent_t> e0, e1;
     size_t used = 0;
+    // start / stop events of one more profiled launch (created on first use)
+    std::pair<hipEvent_t, hipEvent_t> acquire() {
+        if (used == e0.size()) {
+            hipEvent_t a, b;
+            PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
+            e0.push_back(a); e1.push_back(b);
+        }
+        ++used;
+        return {e0[used - 1], e1[used - 1]};
+    }
+    // add the durations of the profiled launches since the last harvest to (ms, count)
+    void harvest(double& ms_sum, int64_t& count) {
+        for (size_t s = 0; s < used; ++s) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, e0[s], e1[s]) == hipSuccess) { ms_sum += ms; count++; }
+        }
+        used = 0;
+    }
 };
 
 // The solver's stream.  Block workers (one host thread per PSD block while the blocks are
@@ -154,7 +174,7 @@ struct LzRun {
     bool pos_fail = false, presymv = false;
     double betaK = 0.0;
     // where the cycle's read-back lands: alphas at rec[0..), betas at rec[rec_ld..), LanczosCtl at rec[2 rec_ld]
-    // (the narrow record, or the wide one of Solver::lanczos_wide)
+    // (the narrow record, or the wide one)
     const double* rec = nullptr;
     int rec_ld = 0;
     bool wide = false;                // run of the wide kernels (lanczos_wide.hip.hpp): no arrow part, wide rotation
@@ -226,14 +246,8 @@ struct EigWork {
     long long fel_served = 0;                      // full_eig! calls of this block served by the Lanczos engine
     bool fel_disabled = false;                     // ... switched off after a failed verification (full_eig_lanczos_verify)
     int fel_cert_fails = 0;                        // failed certificates of this block (full_eig_lanczos_certify)
-    // persistent Lanczos cycle kernel (lanczos_cycle.hip.hpp): granule buffers, epoch counter, error word
-    DevBuf<double> xg1, xg2, warm_part;
-    DevBuf<unsigned> xf1, xf2;
-    DevBuf<int> cy_err;
-    PinnedBuf cy_err_host;                         // pinned mirror of cy_err (first 4 bytes)
-    unsigned cy_epoch = 1;
-    bool cy_disabled = false;
-    hipEvent_t cye[2] = {nullptr, nullptr};
+    DevBuf<double> warm_part;                      // partial sums of the warm start (k_lz_warm_sum)
+    hipEvent_t cye[2] = {nullptr, nullptr};        // profiled k_lz_block1 launch
     bool cye_pending = false;
     const double* esv = nullptr;                   // support values of E for the projection in progress
     // per-block execution context: counters are merged into the solver's after the projections
@@ -264,6 +278,25 @@ struct EigWork {
     DevBuf<double> sg_out;
 };
 
+
+// `c` mat-vec launches of block W in the stats (negative: launches counted before that did no work)
+static inline void count_matvecs(EigWork& W, long long c) {
+    W.lst.symv_launches += c;
+    W.lst.symv_bytes += (double)c * (8.0 * (double)W.N + 16.0 * (double)W.n);
+}
+
+// chunks of 64 columns in a basis of `cols` columns: the <NCH> argument of the step kernels' templates
+static inline int lz_nch(int cols) { return (cols <= 64) ? 1 : (cols <= 128) ? 2 : (cols <= 192) ? 3 : 4; }
+// f(std::integral_constant<int, lz_nch(cols)>{})
+template <typename F>
+static inline void with_nch(int cols, F&& f) {
+    switch (lz_nch(cols)) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
 
 // requests of one batched rotation launch (lanczos_batch): filled through Solver::rotate while a sink is installed
 struct RotSink {
@@ -340,6 +373,8 @@ public:
     void alloc_eigwork(EigWork& W, int n, int max_nev);
     void lanczos(EigWork& W, const double* xp, int nev, bool positive_part = false);
     void lz_launch_step(EigWork& W, const double* xp, int k, int kfirst, double step_tol, bool& presymv);
+    void lz_launch_finish(EigWork& W, int k, double tol, bool use_carry);
+    void lz_launch_begin(EigWork& W, const double* start, dev::LanczosCtl* ctl);
     bool lanczos_certificate(EigWork& W, const double* xp, int npos, int msteps, double& theta_max, double& scale);
     void lanczos_batch(const std::vector<int>& blocks, const double* xbase, const std::vector<int>& nevs, int ctx_slot = 0);
     // batched rotations: U of every block staged in ONE pinned buffer, one upload, one launch (grid.z = block)
@@ -370,23 +405,20 @@ public:
     bool lz_init(EigWork& W, struct LzRun& R, int nev, bool positive_part);
     void lz_prepare_arrow(struct LzRun& R);
     bool lz_after_cycle(EigWork& W, struct LzRun& R, bool speculated);
+    void lz_rayleigh(EigWork& W, struct LzRun& R, int K, double betaK, bool from_arrow, bool check_first);
+    void lz_restart(EigWork& W, struct LzRun& R, int K, int keep, bool speculated);
     void lz_finish_run(EigWork& W, struct LzRun& R);
     void lanczos_eager(EigWork& W, const double* xp, int nev);
-    void lanczos_wide(EigWork& W, const double* xp, int nev);
     void lzw_step(EigWork& W, const double* xp, int k, int kfirst, double step_tol, bool& presymv);
     void lz_merge_vectors(EigWork& W, struct LzRun& R, int ncols);
     bool lz_split_first(EigWork& W, struct LzRun& R, int k1);
     void full_eig_values(EigWork& W, const double* xp, double offscale, bool vectors, std::vector<double>& Dhost);
     void harvest_full_eig_events(EigWork& W);
-    bool cycle_plan(const EigWork& W, int krylovdim, int& R, int& G, bool& f_in_lds) const;
-    void launch_cycle(EigWork& W, int kfirst, int krylovdim, double tol, int R, int G, bool f_in_lds);
-    int cycle_lds_cap = 0;                        // dynamic LDS granted to k_lz_cycle (setup_device)
     int block1_lds_cap = 0;                       // dynamic LDS granted to k_lz_block1 (setup_device)
     DevBuf<long long> b1_dbg;                     // PROXSDP_HIP_DEBUG_B1: tick sums of k_lz_block1 (prologue | loop | epilogue | steps | launches)
     bool block1_plan(const EigWork& W, int krylovdim, bool split_wanted) const;
     void launch_block1(EigWork& W, const double* xp, int kfirst, int krylovdim, double tol);
     bool sg48_ok = false;                         // 72 KiB of dynamic LDS granted to k_sym_gemm48 (setup_device)
-    DevBuf<long long> cy_dbg;                     // PROXSDP_HIP_DEBUG_CYCLE: per-phase tick sums
     void launch_symv(EigWork& W, const double* xp, const double* v, bool use_ctl, dev::LanczosCtl* ctl = nullptr);
     void launch_symv_finish(EigWork& W, const double* xp, int kclose, double tol, bool use_carry);
     void launch_reconstruct(EigWork& W, const double* Z, int ldz, const double* lam, int r, double* xp_out,
@@ -744,6 +776,7 @@ inline void Solver::setup_device() {
     if (ndev <= 0) throw HipError("no HIP device available");
     if (opt.device_id < 0 || opt.device_id >= ndev) throw std::invalid_argument("device_id out of range");
     if (opt.lanczos_wide_krylov != 0 && opt.lanczos_wide_krylov != 1) throw std::invalid_argument("lanczos_wide_krylov must be 0 or 1");
+    if (opt.lanczos_cycle_kernel == 1) opt.lanczos_cycle_kernel = 0;   // (1 selected the retired persistent cycle kernel)
     PX_HIP(hipSetDevice(opt.device_id));
     PX_HIP(hipStreamCreate(&stream.main));
     // gfx950: 160 KiB of LDS per CU.  The restart rotation at K = 127, keep = 78 needs 145 KiB (U tile + V tile): with 144 KiB
@@ -764,18 +797,6 @@ inline void Solver::setup_device() {
     for (const void* f : {reinterpret_cast<const void*>(dev::k_sym_gemm48<dev::SG_PLAIN, 4>), reinterpret_cast<const void*>(dev::k_sym_gemm48<dev::SG_POLY, 4>)})
         sg48_ok = sg48_ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dev::sg48_lds_bytes(4)) == hipSuccess;
     if (!sg48_ok) (void)hipGetLastError();
-    if (std::getenv("PROXSDP_HIP_DEBUG_CYCLE") != nullptr) { cy_dbg.alloc(16); cy_dbg.zero(stream); }
-    cycle_lds_cap = 0;
-    for (int kb : {160, 156, 152, 144, 128, 96, 64}) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(dev::k_lz_cycle<128>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kb * 1024) == hipSuccess &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::k_lz_cycle<64>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kb * 1024) == hipSuccess) {
-            cycle_lds_cap = kb * 1024;
-            break;
-        }
-        (void)hipGetLastError();
-    }
     // one-launch small-block projection: 4 matrices of side x (side + 2) doubles in LDS (132 KiB at side 64).  Probed here so
     // that a device / partition that does not grant it sends the larger of those blocks to the tiled engines instead of
     // failing the solve
@@ -804,7 +825,7 @@ inline void Solver::setup_device() {
 }
 
 // one-workgroup cycle kernel for medium blocks (lanczos_block1.hip.hpp): the step kernels' arithmetic bit for bit, one launch
-// per Lanczos cycle.  lanczos_cycle_kernel: 2 = on, -1 (auto) = on where it applies, 0 / 1 = off.
+// per Lanczos cycle.  lanczos_cycle_kernel: 2 = on, -1 (auto) = on where it applies, 0 = off (1 is read as 0, setup_device).
 inline bool Solver::block1_plan(const EigWork& W, int krylovdim, bool split_wanted) const {
     if (!(opt.lanczos_cycle_kernel == 2 || opt.lanczos_cycle_kernel < 0) || block1_lds_cap == 0) return false;
     if (W.nt > dev::B1_MAXNT || krylovdim > dev::B1_KMAX || split_wanted || rot_sink != nullptr) return false;
@@ -856,68 +877,7 @@ inline void Solver::launch_block1(EigWork& W, const double* xp, int kfirst, int 
     }
     W.lst.cycle_launches++;
     W.lst.cycle_steps += krylovdim - kfirst;
-    W.lst.symv_launches += krylovdim - kfirst;
-    W.lst.symv_bytes += (double)(krylovdim - kfirst) * (8.0 * (double)W.N + 16.0 * (double)W.n);
-}
-
-// persistent cycle kernel: rows per workgroup, grid and whether the previous factors fit in LDS
-inline bool Solver::cycle_plan(const EigWork& W, int krylovdim, int& R, int& G, bool& f_in_lds) const {
-    if (std::getenv("PROXSDP_HIP_DEBUG_CYCLE") != nullptr)
-        std::fprintf(stderr, "[cycle_plan] knob %d disabled %d cap %d par %d fop %d ov %d xg %zu kd %d Fr %d ellw %d npad %d\n",
-                     (int)opt.lanczos_cycle_kernel, (int)W.cy_disabled, cycle_lds_cap, (int)parallel_blocks, (int)W.use_fop,
-                     (int)(W.ov.wr_ptr != nullptr), W.xg1.n, krylovdim, W.F_r, W.ell_w, W.npad);
-    // auto (-1) = off: measured 10.9 us per Lanczos step against 14.1 us for the step kernels at n = 4000,
-    // K = 25 -- +5 % iterations/s, not worth an assumption about workgroup placement by default
-    if (opt.lanczos_cycle_kernel != 1 || W.cy_disabled || cycle_lds_cap == 0 || parallel_blocks) return false;
-    if (!W.use_fop || W.ov.wr_ptr != nullptr || W.xg1.n == 0) return false;
-    if (krylovdim + 2 > dev::CY_CMAX - 2 || W.F_r > 126) return false;
-    const size_t cap = (size_t)cycle_lds_cap - 512;
-    for (int r : {128, 64}) {
-        const int S = dev::NWAVE / (r / 64);
-        if (W.ell_w > dev::CY_NE * S) continue;
-        const int g = ceil_div(W.npad, r);
-        if (g > 32) continue;                               // one XCD: 32 CUs, one workgroup each
-        for (bool fl : {true, false}) {
-            if (dev::cycle_lds_bytes(krylovdim, W.F_r, r, g, fl) <= cap) { R = r; G = g; f_in_lds = fl; return true; }
-        }
-    }
-    return false;
-}
-
-inline void Solver::launch_cycle(EigWork& W, int kfirst, int krylovdim, double tol, int R, int G, bool f_in_lds) {
-    dev::CycleArgs a{};
-    a.V = W.V.p; a.ldv = W.npad; a.n = W.n; a.npad = W.npad;
-    a.kfirst = kfirst; a.kd = krylovdim; a.tol = tol;
-    a.Vp = W.F.p + (size_t)W.F_first * W.npad; a.rp = W.F_r; a.lam = W.Flam.p;
-    a.ell_col = W.ell_col.p; a.ell_sidx = W.ell_sidx.p; a.ell_w = W.ell_w; a.esv = W.esv;
-    a.arrow = W.arrow_p;
-    a.alphas = W.alphas_p; a.betas = W.betas_p; a.ctl = W.ctl_p;
-    a.x1 = W.xg1.p; a.x2 = W.xg2.p; a.xs1 = dev::CY_CMAX; a.xs2 = dev::CY_CMAX + 128;
-    a.f1 = W.xf1.p; a.f2 = W.xf2.p;
-    a.epoch0 = W.cy_epoch;
-    a.R = R; a.G = G; a.f_in_lds = f_in_lds ? 1 : 0;
-    a.err = W.cy_err.p;
-    a.dbg = cy_dbg.p;
-    W.cy_epoch += 2u * (unsigned)(krylovdim - kfirst) + 8u;
-    if (W.cy_epoch > 0xF0000000u) {                        // tags would wrap: start over on zeroed buffers
-        W.xf1.zero(stream); W.xf2.zero(stream); W.cy_epoch = 1; a.epoch0 = 1;
-        W.cy_epoch += 2u * (unsigned)(krylovdim - kfirst) + 8u;
-    }
-    const size_t lds = dev::cycle_lds_bytes(krylovdim, W.F_r, R, G, f_in_lds);
-    const bool prof = opt.profile_symv_every > 0;
-    if (prof) {
-        if (W.cye[0] == nullptr) { PX_HIP(hipEventCreate(&W.cye[0])); PX_HIP(hipEventCreate(&W.cye[1])); }
-        if (R == 128) hipExtLaunchKernelGGL(dev::k_lz_cycle<128>, dim3(8 * G), dim3(dev::TPB), lds, stream, W.cye[0], W.cye[1], 0, a);
-        else hipExtLaunchKernelGGL(dev::k_lz_cycle<64>, dim3(8 * G), dim3(dev::TPB), lds, stream, W.cye[0], W.cye[1], 0, a);
-        W.cye_pending = true;
-    } else {
-        if (R == 128) hipLaunchKernelGGL(dev::k_lz_cycle<128>, dim3(8 * G), dim3(dev::TPB), lds, stream, a);
-        else hipLaunchKernelGGL(dev::k_lz_cycle<64>, dim3(8 * G), dim3(dev::TPB), lds, stream, a);
-    }
-    W.lst.cycle_launches++;
-    W.lst.cycle_steps += krylovdim - kfirst;
-    W.lst.symv_launches += krylovdim - kfirst;
-    W.lst.symv_bytes += (double)(krylovdim - kfirst) * (8.0 * (double)W.N + 16.0 * (double)W.n);
+    count_matvecs(W, krylovdim - kfirst);
 }
 
 // rocSOLVER's first dsyevd in a process pays ~3 s of code-object loading.  The exit path
@@ -964,19 +924,11 @@ static inline void launch_prof(bool prof, hipEvent_t e0, hipEvent_t e1, K kern, 
 
 inline void Solver::launch_symv(EigWork& W, const double* xp, const double* v, bool use_ctl, dev::LanczosCtl* ctl) {
     const int ntile = 8 * ceil_div(W.nt * (W.nt + 1) / 2, 8);     // one workgroup per 64x64 tile, padded to 8 XCDs
-    bool prof = opt.profile_symv_every > 0 && (W.lst.symv_launches % opt.profile_symv_every) == 0;
-    size_t slot = 0;
-    if (prof) {
-        if (W.ev.used == W.ev.e0.size()) {
-            hipEvent_t a, b;
-            PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
-            W.ev.e0.push_back(a); W.ev.e1.push_back(b);
-        }
-        slot = W.ev.used++;
-    }
+    const bool prof = opt.profile_symv_every > 0 && (W.lst.symv_launches % opt.profile_symv_every) == 0;
     // profiled launches carry their own start/stop events (the dispatch's timestamps, i.e. the
     // kernel alone, as rocprofv3 reports it -- not the gaps to the neighbouring launches)
-    hipEvent_t e0 = prof ? W.ev.e0[slot] : nullptr, e1 = prof ? W.ev.e1[slot] : nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (prof) std::tie(e0, e1) = W.ev.acquire();
     if (W.use_fop) {
         auto kern = (W.F_r <= 64) ? dev::k_fop<1> : dev::k_fop<2>;
         launch_prof(prof, e0, e1, kern, dim3(W.nt), stream,
@@ -987,8 +939,7 @@ inline void Solver::launch_symv(EigWork& W, const double* xp, const double* v, b
         launch_prof(prof, e0, e1, dev::k_symv_packed, dim3(ntile), stream,
                     xp, W.n, W.nt, W.npad, v, W.Ppart.p, (const dev::LanczosCtl*)(use_ctl ? (ctl ? ctl : W.ctl_p) : nullptr), W.Apart.p);
     }
-    W.lst.symv_launches++;
-    W.lst.symv_bytes += 8.0 * (double)W.N + 16.0 * (double)W.n;
+    count_matvecs(W, 1);
 }
 
 // partial-dot buffer written by the orthogonalisation of step k
@@ -999,37 +950,42 @@ inline double* lz_hpart(EigWork& W, int k) {
 // k_symv_finish: closes Lanczos step `kclose` and runs the mat-vec of step kclose+1 on w'
 inline void Solver::launch_symv_finish(EigWork& W, const double* xp, int kclose, double tol, bool use_carry) {
     const int ntile = 8 * ceil_div(W.nt * (W.nt + 1) / 2, 8);
-    bool prof = opt.profile_symv_every > 0 && (W.lst.symv_launches % opt.profile_symv_every) == 0;
-    size_t slot = 0;
-    if (prof) {
-        if (W.ev.used == W.ev.e0.size()) {
-            hipEvent_t a, b;
-            PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
-            W.ev.e0.push_back(a); W.ev.e1.push_back(b);
+    const bool prof = opt.profile_symv_every > 0 && (W.lst.symv_launches % opt.profile_symv_every) == 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (prof) std::tie(e0, e1) = W.ev.acquire();
+    with_nch(kclose + 1, [&](auto nch) {
+        constexpr int NCH = decltype(nch)::value;
+        if (W.use_fop) {
+            auto kern = (W.F_r <= 64) ? dev::k_fop_finish<1, NCH> : dev::k_fop_finish<2, NCH>;
+            launch_prof(prof, e0, e1, kern, dim3(2 * W.nt), stream,
+                        (const double*)W.w.p, W.V.p, W.npad, kclose, (const double*)lz_hpart(W, kclose), W.pld,
+                        (const double*)W.hsum1.p, W.alphas_p, W.betas_p, W.ctl_p, tol, use_carry ? 1 : 0, W.nt,
+                        (const double*)(W.F.p + (size_t)W.F_first * W.npad), W.F_r,
+                        (const int*)W.ell_col.p, (const int*)W.ell_sidx.p, W.ell_w, W.npad, W.esv, W.tpart.p, W.ebuf.p,
+                        W.apartf.p, W.hred.p, W.ov);
+        } else {
+            launch_prof(prof, e0, e1, dev::k_symv_finish<NCH>, dim3(W.nt + ntile), stream,
+                        xp, W.n, W.nt, W.npad, W.Ppart.p, (const double*)W.w.p, W.V.p, W.npad, kclose,
+                        (const double*)lz_hpart(W, kclose), W.pld, (const double*)W.hsum1.p, W.alphas_p, W.betas_p, W.ctl_p,
+                        tol, use_carry ? 1 : 0, W.Apart.p, W.hred.p);
         }
-        slot = W.ev.used++;
-    }
-    hipEvent_t e0 = prof ? W.ev.e0[slot] : nullptr, e1 = prof ? W.ev.e1[slot] : nullptr;
-    if (W.use_fop) {
-        const int nchf = (kclose + 1 <= 64) ? 1 : (kclose + 1 <= 128) ? 2 : (kclose + 1 <= 192) ? 3 : 4;
-        auto kern = (W.F_r <= 64) ? (nchf == 1 ? dev::k_fop_finish<1, 1> : nchf == 2 ? dev::k_fop_finish<1, 2> : nchf == 3 ? dev::k_fop_finish<1, 3> : dev::k_fop_finish<1, 4>)
-                                  : (nchf == 1 ? dev::k_fop_finish<2, 1> : nchf == 2 ? dev::k_fop_finish<2, 2> : nchf == 3 ? dev::k_fop_finish<2, 3> : dev::k_fop_finish<2, 4>);
-        launch_prof(prof, e0, e1, kern, dim3(2 * W.nt), stream,
-                    (const double*)W.w.p, W.V.p, W.npad, kclose, (const double*)lz_hpart(W, kclose), W.pld,
-                    (const double*)W.hsum1.p, W.alphas_p, W.betas_p, W.ctl_p, tol, use_carry ? 1 : 0, W.nt,
-                    (const double*)(W.F.p + (size_t)W.F_first * W.npad), W.F_r,
-                    (const int*)W.ell_col.p, (const int*)W.ell_sidx.p, W.ell_w, W.npad, W.esv, W.tpart.p, W.ebuf.p,
-                    W.apartf.p, W.hred.p, W.ov);
-    } else {
-        const int nchf = (kclose + 1 <= 64) ? 1 : (kclose + 1 <= 128) ? 2 : (kclose + 1 <= 192) ? 3 : 4;
-        auto ksf = nchf == 1 ? dev::k_symv_finish<1> : nchf == 2 ? dev::k_symv_finish<2> : nchf == 3 ? dev::k_symv_finish<3> : dev::k_symv_finish<4>;
-        launch_prof(prof, e0, e1, ksf, dim3(W.nt + ntile), stream,
-                    xp, W.n, W.nt, W.npad, W.Ppart.p, (const double*)W.w.p, W.V.p, W.npad, kclose,
-                    (const double*)lz_hpart(W, kclose), W.pld, (const double*)W.hsum1.p, W.alphas_p, W.betas_p, W.ctl_p,
-                    tol, use_carry ? 1 : 0, W.Apart.p, W.hred.p);
-    }
-    W.lst.symv_launches++;
-    W.lst.symv_bytes += 8.0 * (double)W.N + 16.0 * (double)W.n;
+    });
+    count_matvecs(W, 1);
+}
+
+// k_lz_finish: closes Lanczos step k (its coefficients land in the record) without a mat-vec behind it
+inline void Solver::lz_launch_finish(EigWork& W, int k, double tol, bool use_carry) {
+    with_nch(k + 1, [&](auto nch) {
+        hipLaunchKernelGGL(dev::k_lz_finish<decltype(nch)::value>, dim3(W.nt), dim3(dev::TPB), 0, stream,
+                           (const double*)W.w.p, W.n, W.V.p, W.npad, k, (const double*)lz_hpart(W, k), W.pld,
+                           (const double*)W.hsum1.p, W.alphas_p, W.betas_p, W.ctl_p, tol, use_carry ? 1 : 0, W.hred.p);
+    });
+}
+
+// k_lz_begin: V[:, 0] = the (normalised) start vector, the control block `ctl` cleared
+inline void Solver::lz_launch_begin(EigWork& W, const double* start, dev::LanczosCtl* ctl) {
+    hipLaunchKernelGGL(dev::k_lz_begin, dim3(ceil_div(W.npad, dev::TPB)), dim3(dev::TPB), 0, stream,
+                       W.V.p, start, W.npad, ctl);
 }
 
 inline void Solver::launch_reconstruct(EigWork& W, const double* Z, int ldz, const double* lam, int r, double* xp_out,
@@ -1146,7 +1102,8 @@ inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int 
 // parameters of the run and the per-call reset of W; false = the call ends at once (dsaupd argument errors)
 inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     R.nev = nev; R.positive_part = positive_part;
-    R.wide = false;
+    // a restart rotation deferred into a launch that never came (an exception in the last run) is void
+    W.b1_rot_K = 0; W.b1_rot_U = nullptr;
     R.arpack = (opt.eigsolver == 1);
     int krylovdim = std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos);
     // positive-part mode is the library's own algorithm (not KrylovKit's call): a larger Krylov space
@@ -1158,6 +1115,11 @@ inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     }
     if (krylovdim + 1 > W.cap) throw std::invalid_argument("Lanczos workspace too small for the requested rank");
     R.krylovdim = krylovdim;
+    // Krylov dimension beyond the step kernels (lanczos_wide_krylov = 1): the wide kernels and their own record
+    R.wide = krylovdim > dev::MAXK - 1;
+    if (R.wide && !W.wide) throw std::logic_error("wide Lanczos: workspace has no wide records");
+    R.rec = R.wide ? W.recw_pinned.p : W.rec_host;
+    R.rec_ld = R.wide ? dev::LZW_MAXK : dev::MAXK;
     R.tol = R.arpack ? opt.arpack_tol : opt.krylovkit_tol;
     R.maxiter = R.arpack ? (long long)opt.arpack_max_iter : (long long)opt.krylovkit_max_iter;
     W.prev_numiter = std::max(W.numiter, 1);
@@ -1172,7 +1134,6 @@ inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     R.pos_fail = false; R.presymv = false; R.betaK = 0.0;
     R.split_ready = false; R.merge_active = false;
     R.splitp = &W.split;
-    R.rec = W.rec_host; R.rec_ld = dev::MAXK; R.wide = false;
     return true;
 }
 
@@ -1210,21 +1171,17 @@ inline void Solver::lz_prepare_arrow(LzRun& R) {
 inline bool Solver::lz_after_cycle(EigWork& W, LzRun& R, bool speculated) {
     const int krylovdim = R.krylovdim, ld = R.ld, kfirst = R.kfirst, nev = R.nev;
     const double tol = R.tol;
-    std::vector<double>& T = R.T; std::vector<double>& D = R.D; std::vector<double>& U = R.U;
-    std::vector<double>& f = R.f; std::vector<double>& al = R.al; std::vector<double>& be = R.be;
+    std::vector<double>& T = R.T; std::vector<double>& D = R.D; std::vector<double>& f = R.f;
+    std::vector<double>& al = R.al; std::vector<double>& be = R.be;
     dev::LanczosCtl hctl{};
     std::copy(R.rec, R.rec + krylovdim, al.begin());
     std::copy(R.rec + R.rec_ld, R.rec + R.rec_ld + krylovdim, be.begin());
     std::memcpy(&hctl, R.rec + 2 * R.rec_ld, sizeof(hctl));
     const int Kend = hctl.stop ? hctl.kstop : krylovdim;
     // launches after the stop flag are no-ops; count the mat-vecs that did work
-    {
-        long long skipped = (long long)(krylovdim - Kend);
-        W.lst.lanczos_matvecs += (Kend - kfirst);
-        W.lst.symv_launches -= skipped;
-        W.lst.symv_bytes -= skipped * (8.0 * (double)W.N + 16.0 * (double)W.n);
-        W.mv_iter += (Kend - kfirst);
-    }
+    W.lst.lanczos_matvecs += (Kend - kfirst);
+    count_matvecs(W, -(long long)(krylovdim - Kend));
+    W.mv_iter += (Kend - kfirst);
     for (int k = kfirst; k < Kend; ++k) {
         T[(size_t)k * ld + k] = al[k];
         if (k + 1 < Kend) { T[(size_t)k * ld + k + 1] = be[k]; T[(size_t)(k + 1) * ld + k] = be[k]; }
@@ -1253,28 +1210,8 @@ inline bool Solver::lz_after_cycle(EigWork& W, LzRun& R, bool speculated) {
         W.lst.host_eig_time += now_s() - te0;
     }
     R.split_ready = false;
-    if (R.merge_active) {
-        // (Ritz-vector coefficients are formed below / in lz_finish_run, for the columns actually needed)
-    } else if (K == 1) {
-        D[0] = T[0]; U.assign(1, 1.0); f[0] = betaK;
-    } else {
-        R.Tw.assign((size_t)K * K, 0.0);
-        for (int c = 0; c < K; ++c)
-            for (int r = 0; r < K; ++r) R.Tw[(size_t)c * K + r] = T[(size_t)c * ld + r];
-        std::vector<double> Dasc(K);
-        const double te0 = now_s();
-        if (R.m_arrow > 0 && K > R.m_arrow)
-            symeig_tridiag_from(K, R.m_arrow, R.Qa.data(), R.da.data(), R.ea.data(), al.data(), be.data(), R.Tw.data(), Dasc.data());
-        else
-            symeig_dense(K, R.Tw.data(), Dasc.data(), kfirst == 0);       // (also the fallback of a failed merge: Qa was not prepared)
-        W.lst.host_eig_time += now_s() - te0; W.lst.host_eigs++;
-        U.assign((size_t)K * K, 0.0);
-        for (int c = 0; c < K; ++c) {                // :LR -> descending
-            D[c] = Dasc[K - 1 - c];
-            for (int r = 0; r < K; ++r) U[(size_t)c * K + r] = R.Tw[(size_t)(K - 1 - c) * K + r];
-            f[c] = betaK * U[(size_t)c * K + (K - 1)];
-        }
-    }
+    // (after a merge the Ritz-vector coefficients are formed in lz_restart / lz_finish_run, for the columns actually needed)
+    if (!R.merge_active) lz_rayleigh(W, R, K, betaK, true, kfirst == 0);
     int converged = 0;
     if (!R.arpack) {
         // (positive-part mode, the library's own algorithm: optionally a residual RELATIVE to the spectral scale,
@@ -1313,24 +1250,59 @@ inline bool Solver::lz_after_cycle(EigWork& W, LzRun& R, bool speculated) {
     // -3 % .. +11 % of this rule's 12.4 s with the same 8651 iterations -- the rule stays)
     const int keep = R.arpack ? std::min(krylovdim - 1, nev + std::max(1, (krylovdim - nev) / 2))
                               : (3 * krylovdim + 2 * converged) / 5;
+    lz_restart(W, R, K, keep, speculated);
+    return true;
+}
+
+// K x K Rayleigh quotient R.T[:K, :K] -> Ritz values R.D in :LR (descending) order, their vectors R.U and couplings
+// R.f = betaK U[K - 1, :].  from_arrow: finish the tridiagonal reduction lz_prepare_arrow started, where it did;
+// check_first: symeig_dense's argument
+inline void Solver::lz_rayleigh(EigWork& W, LzRun& R, int K, double betaK, bool from_arrow, bool check_first) {
+    std::vector<double>& D = R.D; std::vector<double>& U = R.U; std::vector<double>& f = R.f;
+    if (K == 1) {
+        D[0] = R.T[0]; U.assign(1, 1.0); f[0] = betaK;
+        return;
+    }
+    R.Tw.assign((size_t)K * K, 0.0);
+    for (int c = 0; c < K; ++c)
+        for (int r = 0; r < K; ++r) R.Tw[(size_t)c * K + r] = R.T[(size_t)c * R.ld + r];
+    std::vector<double> Dasc(K);
+    const double te0 = now_s();
+    if (from_arrow && R.m_arrow > 0 && K > R.m_arrow)
+        symeig_tridiag_from(K, R.m_arrow, R.Qa.data(), R.da.data(), R.ea.data(), R.al.data(), R.be.data(), R.Tw.data(), Dasc.data());
+    else
+        symeig_dense(K, R.Tw.data(), Dasc.data(), check_first);       // (also the fallback of a failed merge: Qa was not prepared)
+    W.lst.host_eig_time += now_s() - te0; W.lst.host_eigs++;
+    U.assign((size_t)K * K, 0.0);
+    for (int c = 0; c < K; ++c) {                    // :LR -> descending
+        D[c] = Dasc[K - 1 - c];
+        for (int r = 0; r < K; ++r) U[(size_t)c * K + r] = R.Tw[(size_t)(K - 1 - c) * K + r];
+        f[c] = betaK * U[(size_t)c * K + (K - 1)];
+    }
+}
+
+// thick restart on the first `keep` Ritz pairs of the K-column basis: rotation (enqueued), R.T = the arrow [diag(D) f; f' .]
+// of the next cycle, which starts at basis column `keep`.  speculated: the mat-vec of v_keep is already under way
+inline void Solver::lz_restart(EigWork& W, LzRun& R, int K, int keep, bool speculated) {
+    const std::vector<double>& D = R.D; const std::vector<double>& f = R.f;
     // arrow part of the restarted T for k_lz_orth: f (couplings of v_K with the kept Ritz
     // vectors) and D (their Ritz values)
     // (the wide kernels measure both passes: no arrow part)
     if (!R.wide) for (int j = 0; j < keep; ++j) { W.arrow_host.p[j] = f[j]; W.arrow_host.p[dev::MAXK + j] = D[j]; }
     if (R.merge_active) lz_merge_vectors(W, R, keep);
-    rotate(W, K, U, K, keep, W.Z.p, K, keep, W.arrow_host.p, R.wide ? 0 : 2 * dev::MAXK);   // Z[:, :keep] = V U[:, :keep]; Z[:, keep] = V[:, K]
+    rotate(W, K, R.U, K, keep, W.Z.p, K, keep, W.arrow_host.p, R.wide ? 0 : 2 * dev::MAXK);   // Z[:, :keep] = V U[:, :keep]; Z[:, keep] = V[:, K]
     std::swap(W.V.p, W.Z.p);
-    std::fill(T.begin(), T.end(), 0.0);
+    std::fill(R.T.begin(), R.T.end(), 0.0);
+    const int ld = R.ld;
     for (int j = 0; j < keep; ++j) {
-        T[(size_t)j * ld + j] = D[j];
-        T[(size_t)j * ld + keep] = f[j];
-        T[(size_t)keep * ld + j] = f[j];
+        R.T[(size_t)j * ld + j] = D[j];
+        R.T[(size_t)j * ld + keep] = f[j];
+        R.T[(size_t)keep * ld + j] = f[j];
     }
     R.kfirst = keep;
     R.presymv = speculated;
     ++R.numiter;
     W.lst.lanczos_restarts++;
-    return true;
 }
 
 // results of the run (KrylovKit's return values / dseupd's), Ritz vectors into W.Z
@@ -1381,28 +1353,14 @@ inline void Solver::lanczos_eager(EigWork& W, const double* xp, int nev) {
     W.use_fop = false;
     if (!lz_init(W, R, nev, false)) return;
     if (R.arpack) throw std::invalid_argument("krylovkit_eager applies to eigsolver = 2 (KrylovKit) only");
+    if (R.wide) throw std::invalid_argument("krylovkit_eager: Krylov dimension > 255 is not supported");
     const int kd = R.krylovdim, ld = R.ld;
     const double tol = R.tol;
-    hipLaunchKernelGGL(dev::k_lz_begin, dim3(ceil_div(W.npad, dev::TPB)), dim3(dev::TPB), 0, stream,
-                       W.V.p, (const double*)W.resid.p, W.npad, W.ctl_p);
-    std::vector<double>& T = R.T; std::vector<double>& D = R.D; std::vector<double>& U = R.U; std::vector<double>& f = R.f;
-    std::vector<double> fstep(2 * dev::MAXK, 0.0), Dasc;
+    lz_launch_begin(W, W.resid.p, W.ctl_p);
+    std::vector<double>& T = R.T; std::vector<double>& f = R.f;
+    std::vector<double> fstep(2 * dev::MAXK, 0.0);
     int K = 0, kfirst = 0, converged = 0;
     double beta = 0.0;
-    auto launch_orth = [&](int k, int keep) {
-        const int nch = (k + 1 <= 64) ? 1 : (k + 1 <= 128) ? 2 : (k + 1 <= 192) ? 3 : 4;
-        double* hp[2] = {W.hpart1.p, W.hpart2.p};
-        dev::FopArgs fo{};
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(W.nt), dim3(dev::TPB), 0, stream,
-                               (const double*)W.Ppart.p, W.nt, W.npad, (const double*)W.V.p, W.npad, k, W.w.p,
-                               (const double*)W.hred.p, hp[k & 1], W.pld, W.hsum1.p, (const dev::LanczosCtl*)W.ctl_p,
-                               (const double*)W.alphas_p, (const double*)W.betas_p, (const double*)W.Apart.p, W.napart, 1,
-                               (const double*)W.arrow_p, keep, fo);
-        };
-        if (nch == 1) go(dev::k_lz_orth<1, 0>); else if (nch == 2) go(dev::k_lz_orth<2, 0>);
-        else if (nch == 3) go(dev::k_lz_orth<3, 0>); else go(dev::k_lz_orth<4, 0>);
-    };
     while (true) {
         const int k = K;                                  // expand: v_k is an exact, normalised basis vector
         launch_symv(W, xp, W.V.p + (size_t)k * W.npad, true);
@@ -1414,10 +1372,15 @@ inline void Solver::lanczos_eager(EigWork& W, const double* xp, int nev) {
             W.arrow_p = W.arrow.p;
             keep = k;
         }
-        launch_orth(k, keep);
-        auto klf = (k + 1 <= 64) ? dev::k_lz_finish<1> : (k + 1 <= 128) ? dev::k_lz_finish<2> : (k + 1 <= 192) ? dev::k_lz_finish<3> : dev::k_lz_finish<4>;
-        hipLaunchKernelGGL(klf, dim3(W.nt), dim3(dev::TPB), 0, stream, W.w.p, W.n, W.V.p, W.npad, k, lz_hpart(W, k), W.pld,
-                           W.hsum1.p, W.alphas_p, W.betas_p, W.ctl_p, 0.0, 0, W.hred.p);
+        with_nch(k + 1, [&](auto nch) {
+            auto kern = dev::k_lz_orth<decltype(nch)::value, 0>;
+            hipLaunchKernelGGL(kern, dim3(W.nt), dim3(dev::TPB), 0, stream,
+                               (const double*)W.Ppart.p, W.nt, W.npad, (const double*)W.V.p, W.npad, k, W.w.p,
+                               (const double*)W.hred.p, lz_hpart(W, k), W.pld, W.hsum1.p, (const dev::LanczosCtl*)W.ctl_p,
+                               (const double*)W.alphas_p, (const double*)W.betas_p, (const double*)W.Apart.p, W.napart, 1,
+                               (const double*)W.arrow_p, keep, dev::FopArgs{});
+        });
+        lz_launch_finish(W, k, 0.0, false);
         PX_HIP(hipMemcpyAsync(W.rec_host, W.rec.p, EigWork::REC_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
         PX_HIP(hipStreamSynchronize(stream));
         const double al_k = W.rec_host[k];
@@ -1429,23 +1392,7 @@ inline void Solver::lanczos_eager(EigWork& W, const double* xp, int nev) {
         K = k + 1;
         if (beta <= tol && K < R.howmany) R.howmany = K;
         if (K == kd || beta <= tol || K >= R.howmany) {
-            if (K == 1) {
-                D[0] = T[0]; U.assign(1, 1.0); f[0] = beta;
-            } else {
-                R.Tw.assign((size_t)K * K, 0.0);
-                for (int c = 0; c < K; ++c)
-                    for (int r = 0; r < K; ++r) R.Tw[(size_t)c * K + r] = T[(size_t)c * ld + r];
-                Dasc.resize(K);
-                const double te0 = now_s();
-                symeig_dense(K, R.Tw.data(), Dasc.data(), false);
-                W.lst.host_eig_time += now_s() - te0; W.lst.host_eigs++;
-                U.assign((size_t)K * K, 0.0);
-                for (int c = 0; c < K; ++c) {
-                    D[c] = Dasc[K - 1 - c];
-                    for (int r = 0; r < K; ++r) U[(size_t)c * K + r] = R.Tw[(size_t)(K - 1 - c) * K + r];
-                    f[c] = beta * U[(size_t)c * K + (K - 1)];
-                }
-            }
+            lz_rayleigh(W, R, K, beta, false, false);
             converged = 0;
             while (converged < K && std::fabs(f[converged]) <= tol) ++converged;
             R.K = K; R.converged = converged;
@@ -1456,20 +1403,8 @@ inline void Solver::lanczos_eager(EigWork& W, const double* xp, int nev) {
             continue;
         }
         if (R.numiter == R.maxiter) break;
-        // thick restart, as lz_after_cycle
-        const int keepn = (3 * kd + 2 * converged) / 5;
-        for (int j = 0; j < keepn; ++j) { W.arrow_host.p[j] = f[j]; W.arrow_host.p[dev::MAXK + j] = D[j]; }
-        rotate(W, K, U, K, keepn, W.Z.p, K, keepn, W.arrow_host.p, 2 * dev::MAXK);
-        std::swap(W.V.p, W.Z.p);
-        std::fill(T.begin(), T.end(), 0.0);
-        for (int j = 0; j < keepn; ++j) {
-            T[(size_t)j * ld + j] = D[j];
-            T[(size_t)j * ld + keepn] = f[j];
-            T[(size_t)keepn * ld + j] = f[j];
-        }
-        kfirst = keepn; K = keepn;
-        ++R.numiter;
-        W.lst.lanczos_restarts++;
+        lz_restart(W, R, K, (3 * kd + 2 * converged) / 5, false);
+        kfirst = K = R.kfirst;
     }
     lz_finish_run(W, R);
 }
@@ -1502,57 +1437,38 @@ inline bool Solver::lz_split_first(EigWork& W, LzRun& R, int k1) {
 // start of a cycle, otherwise fused with the closing of step k-1 and run on the uncorrected w') and the
 // recurrence / re-orthogonalisation kernel
 inline void Solver::lz_launch_step(EigWork& W, const double* xp, int k, int kfirst, double step_tol, bool& presymv) {
-            if (k == kfirst) {
-                if (!presymv) launch_symv(W, xp, W.V.p + (size_t)k * W.npad, true);   // v_k is ready (start)
-                else { W.lst.symv_launches++; W.lst.symv_bytes += 8.0 * (double)W.N + 16.0 * (double)W.n; }
-                presymv = false;               // after a restart the mat-vec of v_keep is already in Ppart
-            } else {
-                // close step k-1 and run the mat-vec of step k in one launch
-                launch_symv_finish(W, xp, k - 1, step_tol, k - 1 > kfirst);
-            }
-            // recurrence, predicted correction and the measured full pass in one launch;
-            // the partial-dot buffers alternate by step parity (read k-1, write k)
-            double* hp[2] = {W.hpart1.p, W.hpart2.p};
-            dev::FopArgs fo{};
-            if (W.use_fop) {
-                fo.Vp = W.F.p + (size_t)W.F_first * W.npad; fo.lam = W.Flam.p; fo.rp = W.F_r;
-                fo.tpart = W.tpart.p; fo.ebuf = W.ebuf.p; fo.apart = W.apartf.p;
-            }
-            const int nch = (k + 1 <= 64) ? 1 : (k + 1 <= 128) ? 2 : (k + 1 <= 192) ? 3 : 4;
-            const int nchp = !W.use_fop ? 0 : (W.F_r <= 64 ? 1 : 2);
-            const bool prof_o = opt.profile_symv_every > 0 && (W.lst.symv_launches % opt.profile_symv_every) == 1;
-            size_t oslot = 0;
-            if (prof_o) {
-                if (W.evo.used == W.evo.e0.size()) {
-                    hipEvent_t a, b;
-                    PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
-                    W.evo.e0.push_back(a); W.evo.e1.push_back(b);
-                }
-                oslot = W.evo.used++;
-            }
-            auto launch_orth = [&](auto kern) {
-                launch_prof(prof_o, prof_o ? W.evo.e0[oslot] : nullptr, prof_o ? W.evo.e1[oslot] : nullptr, kern,
-                                   dim3(W.nt), stream,
-                                   (const double*)W.Ppart.p, W.nt, W.npad, (const double*)W.V.p, W.npad, k, W.w.p,
-                                   (const double*)W.hred.p, hp[k & 1], W.pld, W.hsum1.p,
-                                   (const dev::LanczosCtl*)W.ctl_p, (const double*)W.alphas_p, (const double*)W.betas_p,
-                                   (const double*)W.Apart.p, W.napart, k == kfirst ? 1 : 0, (const double*)W.arrow_p,
-                                   kfirst, fo);
-            };
-            switch (nch * 3 + nchp) {
-                case 3: launch_orth(dev::k_lz_orth<1, 0>); break;
-                case 4: launch_orth(dev::k_lz_orth<1, 1>); break;
-                case 5: launch_orth(dev::k_lz_orth<1, 2>); break;
-                case 6: launch_orth(dev::k_lz_orth<2, 0>); break;
-                case 7: launch_orth(dev::k_lz_orth<2, 1>); break;
-                case 8: launch_orth(dev::k_lz_orth<2, 2>); break;
-                case 9: launch_orth(dev::k_lz_orth<3, 0>); break;
-                case 10: launch_orth(dev::k_lz_orth<3, 1>); break;
-                case 11: launch_orth(dev::k_lz_orth<3, 2>); break;
-                case 12: launch_orth(dev::k_lz_orth<4, 0>); break;
-                case 13: launch_orth(dev::k_lz_orth<4, 1>); break;
-                default: launch_orth(dev::k_lz_orth<4, 2>); break;
-            }
+    if (k == kfirst) {
+        if (!presymv) launch_symv(W, xp, W.V.p + (size_t)k * W.npad, true);   // v_k is ready (start)
+        else count_matvecs(W, 1);
+        presymv = false;               // after a restart the mat-vec of v_keep is already in Ppart
+    } else {
+        // close step k-1 and run the mat-vec of step k in one launch
+        launch_symv_finish(W, xp, k - 1, step_tol, k - 1 > kfirst);
+    }
+    // recurrence, predicted correction and the measured full pass in one launch;
+    // the partial-dot buffers alternate by step parity (read k-1, write k)
+    dev::FopArgs fo{};
+    if (W.use_fop) {
+        fo.Vp = W.F.p + (size_t)W.F_first * W.npad; fo.lam = W.Flam.p; fo.rp = W.F_r;
+        fo.tpart = W.tpart.p; fo.ebuf = W.ebuf.p; fo.apart = W.apartf.p;
+    }
+    const bool prof_o = opt.profile_symv_every > 0 && (W.lst.symv_launches % opt.profile_symv_every) == 1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (prof_o) std::tie(e0, e1) = W.evo.acquire();
+    auto launch_orth = [&](auto kern) {
+        launch_prof(prof_o, e0, e1, kern, dim3(W.nt), stream,
+                    (const double*)W.Ppart.p, W.nt, W.npad, (const double*)W.V.p, W.npad, k, W.w.p,
+                    (const double*)W.hred.p, lz_hpart(W, k), W.pld, W.hsum1.p,
+                    (const dev::LanczosCtl*)W.ctl_p, (const double*)W.alphas_p, (const double*)W.betas_p,
+                    (const double*)W.Apart.p, W.napart, k == kfirst ? 1 : 0, (const double*)W.arrow_p,
+                    kfirst, fo);
+    };
+    with_nch(k + 1, [&](auto nch) {                  // <NCH, NCHP>: NCHP = 0 packed operator, 1 / 2 operator form (factor rank <= 64 / more)
+        constexpr int NCH = decltype(nch)::value;
+        if (!W.use_fop) launch_orth(dev::k_lz_orth<NCH, 0>);
+        else if (W.F_r <= 64) launch_orth(dev::k_lz_orth<NCH, 1>);
+        else launch_orth(dev::k_lz_orth<NCH, 2>);
+    });
 }
 
 // Certificate of a Lanczos-served full_eig! (options.full_eig_lanczos_certify).  Single-vector Lanczos
@@ -1574,20 +1490,17 @@ inline bool Solver::lanczos_certificate(EigWork& W, const double* xp, int npos, 
         PX_HIP(hipStreamSynchronize(stream));                       // (r2 goes out of scope)
     }
     std::swap(W.V.p, W.Z.p);                                        // the basis buffer holds the Ritz vectors in columns [0, npos)
-    auto nch_of = [](int cols) { return cols <= 64 ? 1 : cols <= 128 ? 2 : cols <= 192 ? 3 : 4; };
     if (npos == 0) {
-        hipLaunchKernelGGL(dev::k_lz_begin, dim3(ceil_div(W.npad, dev::TPB)), dim3(dev::TPB), 0, stream,
-                           W.V.p, (const double*)W.resid2.p, W.npad, W.ctl_p);
+        lz_launch_begin(W, W.resid2.p, W.ctl_p);
     } else {
         // v_npos = (r - Z Z'r) / |.|: measured dots, then the ordinary step closing
         PX_HIP(hipMemcpyAsync(W.w.p, W.resid2.p, (size_t)W.npad * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        const int kc = npos - 1, nch = nch_of(npos);
-        auto km = nch == 1 ? dev::k_lz_measure<1> : nch == 2 ? dev::k_lz_measure<2> : nch == 3 ? dev::k_lz_measure<3> : dev::k_lz_measure<4>;
-        hipLaunchKernelGGL(km, dim3(W.nt), dim3(dev::TPB), 0, stream, (const double*)W.w.p, (const double*)W.V.p, W.npad, kc,
-                           lz_hpart(W, kc), W.pld, W.ctl_p);
-        auto kf = nch == 1 ? dev::k_lz_finish<1> : nch == 2 ? dev::k_lz_finish<2> : nch == 3 ? dev::k_lz_finish<3> : dev::k_lz_finish<4>;
-        hipLaunchKernelGGL(kf, dim3(W.nt), dim3(dev::TPB), 0, stream, (const double*)W.w.p, W.n, W.V.p, W.npad, kc,
-                           (const double*)lz_hpart(W, kc), W.pld, (const double*)W.hsum1.p, W.alphas_p, W.betas_p, W.ctl_p, 0.0, 0, W.hred.p);
+        const int kc = npos - 1;
+        with_nch(npos, [&](auto nch) {
+            hipLaunchKernelGGL(dev::k_lz_measure<decltype(nch)::value>, dim3(W.nt), dim3(dev::TPB), 0, stream,
+                               (const double*)W.w.p, (const double*)W.V.p, W.npad, kc, lz_hpart(W, kc), W.pld, W.ctl_p);
+        });
+        lz_launch_finish(W, kc, 0.0, false);
     }
     // locked part: coupling row f = 0, Ritz values D (the prediction of k_lz_orth multiplies the measured junk by them)
     for (int j = 0; j < npos; ++j) { W.arrow_host.p[j] = 0.0; W.arrow_host.p[dev::MAXK + j] = W.vals[j]; }
@@ -1599,13 +1512,7 @@ inline bool Solver::lanczos_certificate(EigWork& W, const double* xp, int npos, 
     const int kend = npos + msteps;
     bool presymv = false;
     for (int k = npos; k < kend; ++k) lz_launch_step(W, xp, k, npos, 0.0, presymv);
-    {
-        const int nch = nch_of(kend);
-        auto kf = nch == 1 ? dev::k_lz_finish<1> : nch == 2 ? dev::k_lz_finish<2> : nch == 3 ? dev::k_lz_finish<3> : dev::k_lz_finish<4>;
-        hipLaunchKernelGGL(kf, dim3(W.nt), dim3(dev::TPB), 0, stream, (const double*)W.w.p, W.n, W.V.p, W.npad, kend - 1,
-                           (const double*)lz_hpart(W, kend - 1), W.pld, (const double*)W.hsum1.p, W.alphas_p, W.betas_p, W.ctl_p, 0.0,
-                           (kend - 1 > npos) ? 1 : 0, W.hred.p);
-    }
+    lz_launch_finish(W, kend - 1, 0.0, kend - 1 > npos);
     PX_HIP(hipMemcpyAsync(W.rec_host, W.rec.p, EigWork::REC_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
     wait_stream();
     std::swap(W.V.p, W.Z.p);
@@ -1634,26 +1541,24 @@ inline bool Solver::lanczos_certificate(EigWork& W, const double* xp, int npos, 
 }
 
 inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive_part) {
-    // Krylov dimension beyond the step kernels: the wide driver (never the cycle kernels, the one-workgroup kernel, the
-    // batched driver, the operator form or the eager driver -- all of them are written for at most 255 columns)
-    if (!positive_part && std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos) > dev::MAXK - 1) {
-        if (opt.krylovkit_eager && opt.eigsolver != 1)
-            throw std::invalid_argument("krylovkit_eager: Krylov dimension > 255 is not supported");
-        lanczos_wide(W, xp, nev);
-        return;
-    }
     if (opt.krylovkit_eager && opt.eigsolver != 1 && !positive_part) { lanczos_eager(W, xp, nev); return; }
     LzRun& R = W.lzrun;
     if (!lz_init(W, R, nev, positive_part)) return;
     const int krylovdim = R.krylovdim;
     const double step_tol = R.step_tol;
+    // the engine of the cycles: the wide kernels (Krylov dimension 256..511: never the one-workgroup kernel, the operator
+    // form, the split eigensolve or a warm start -- all of them are written for at most 255 columns), the one-workgroup
+    // kernel (medium blocks), or the step kernels
+    const bool wide = R.wide;
+    if (wide) W.lst.wide_krylov_projections++;
     if (krylovdim >= 96) QlPool::get().arm();            // host eigensolve helpers wake up under the first Lanczos cycle
+    dev::LanczosCtl* const ctl = wide ? W.ctlw_p : W.ctl_p;
     // start from the previous projection's Ritz vectors: on the Krylov branch only on request (library-only knob; the
     // reference starts every projection from the same fixed vector, krylovkit_reset_resid = false); in positive-part mode
     // (full_eig! served by this engine: the library's own algorithm, the start vector is its own choice) by default
     // -- same X+ to krylovkit_tol, fewer restarts (lanczos_warm_start = -1 switches it off there too)
     const bool warm_start = positive_part ? (opt.lanczos_warm_start >= 0) : (opt.lanczos_warm_start > 0);
-    if (warm_start && W.fop_ok && W.have_factors && W.F_r > 0 && W.tpart.n > 0) {
+    if (!wide && warm_start && W.fop_ok && W.have_factors && W.F_r > 0 && W.tpart.n > 0) {
         const int nb = ceil_div(W.npad, dev::TPB);
         hipLaunchKernelGGL(dev::k_lz_warm_sum, dim3(nb), dim3(dev::TPB), 0, stream,
                            W.V.p, (const double*)(W.F.p + (size_t)W.F_first * W.npad), W.npad, W.F_r,
@@ -1664,21 +1569,15 @@ inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive
                            W.V.p, W.npad, (const double*)W.warm_part.p, nb, W.ctl_p);
         W.lst.warm_starts++;
     } else
-    hipLaunchKernelGGL(dev::k_lz_begin, dim3(ceil_div(W.npad, dev::TPB)), dim3(dev::TPB), 0, stream,
-                       W.V.p, (const double*)W.resid.p, W.npad, W.ctl_p);
+        lz_launch_begin(W, W.resid.p, ctl);
 
-    int cyR = 0, cyG = 0;
-    bool cyF = false;
-    const bool cyc = cycle_plan(W, krylovdim, cyR, cyG, cyF);
-    int cy_err_host = 0;
-    if (cyc && W.cy_err_host.p == nullptr) { W.cy_err_host.alloc(1); W.cy_err_host.p[0] = 0.0; }
     // split + rank-one merge of the K x K eigensolve (options.host_eig_merge): not for the dsaupd rule (its
-    // wanted set is re-ordered afterwards) and not under the persistent cycle kernel
+    // wanted set is re-ordered afterwards)
     const int merge_from = opt.host_eig_merge == 0 ? (1 << 30) : (opt.host_eig_merge == 1 ? 24 : 64);
     // one-workgroup cycle kernel (medium blocks): where the split eigensolve would want a mid-cycle read-back the step
     // kernels stay in charge, so that either engine hands the host the same work
-    const bool blk1 = !cyc && block1_plan(W, krylovdim, !R.arpack && krylovdim >= merge_from);
-    const bool use_split = !cyc && !blk1 && !R.arpack && krylovdim >= merge_from;
+    const bool blk1 = !wide && block1_plan(W, krylovdim, !R.arpack && krylovdim >= merge_from);
+    const bool use_split = !wide && !blk1 && !R.arpack && krylovdim >= merge_from;
     struct PoolGuard { SpinPool* p; ~PoolGuard() { if (p) p->disarm(); } } pool_guard{nullptr};
     W.split.M.par = nullptr;
     if (use_split && merge_helpers() > 0 && StreamRef::tl == nullptr) {      // (not from a block worker thread: one pool per solver)
@@ -1697,6 +1596,12 @@ inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive
         PX_HIP(hipEventCreateWithFlags(&W.ev_early, hipEventDisableTiming));
         W.rec_early.alloc(EigWork::REC_DOUBLES);
     }
+    // the one-workgroup kernel rotates in the next cycle's prologue: Solver::rotate only stages U while the restart logic runs
+    struct DeferGuard {
+        EigWork& W;
+        DeferGuard(EigWork& w, bool on) : W(w) { W.b1_defer = on; }
+        ~DeferGuard() { W.b1_defer = false; }
+    };
     while (true) {
         const int kfirst = R.kfirst;
         // split point: the arrow with its hub after a restart, the first half of the tridiagonal in the first cycle;
@@ -1705,38 +1610,35 @@ inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive
         // steps do, and the tail left for the critical path shrinks to a quarter of the basis: (0.28)^3 of the QL work)
         const int k1 = (kfirst == 0) ? (18 * krylovdim) / 25 : kfirst + 1;
         const bool split_cycle = use_split && k1 >= 1 && k1 <= krylovdim - 2;
-        if (cyc) {
-            launch_cycle(W, kfirst, krylovdim, step_tol, cyR, cyG, cyF);
-            PX_HIP(hipMemcpyAsync(W.cy_err_host.p, W.cy_err.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (wide) {
+            for (int k = kfirst; k < krylovdim; ++k) lzw_step(W, xp, k, kfirst, step_tol, R.presymv);
         } else if (blk1) {
             launch_block1(W, xp, kfirst, krylovdim, step_tol);
             R.presymv = false;
         } else {
-        for (int k = kfirst; k < krylovdim; ++k) {
-            lz_launch_step(W, xp, k, kfirst, step_tol, R.presymv);
-            if (split_cycle && k == k1) {
-                // alphas / betas up to step k1 - 1 are final: copy them out on the side stream while the cycle runs on
-                PX_HIP(hipEventRecord(W.ev_mid, stream));
-                PX_HIP(hipStreamWaitEvent(W.side, W.ev_mid, 0));
-                PX_HIP(hipMemcpyAsync(W.rec_early.p, W.rec.p, EigWork::REC_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, W.side));
-                PX_HIP(hipEventRecord(W.ev_early, W.side));
+            for (int k = kfirst; k < krylovdim; ++k) {
+                lz_launch_step(W, xp, k, kfirst, step_tol, R.presymv);
+                if (split_cycle && k == k1) {
+                    // alphas / betas up to step k1 - 1 are final: copy them out on the side stream while the cycle runs on
+                    PX_HIP(hipEventRecord(W.ev_mid, stream));
+                    PX_HIP(hipStreamWaitEvent(W.side, W.ev_mid, 0));
+                    PX_HIP(hipMemcpyAsync(W.rec_early.p, W.rec.p, EigWork::REC_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, W.side));
+                    PX_HIP(hipEventRecord(W.ev_early, W.side));
+                }
             }
-        }
-        auto klf = (krylovdim <= 64) ? dev::k_lz_finish<1> : (krylovdim <= 128) ? dev::k_lz_finish<2> : (krylovdim <= 192) ? dev::k_lz_finish<3> : dev::k_lz_finish<4>;
-        hipLaunchKernelGGL(klf, dim3(W.nt), dim3(dev::TPB), 0, stream,
-                           W.w.p, W.n, W.V.p, W.npad, krylovdim - 1, lz_hpart(W, krylovdim - 1), W.pld, W.hsum1.p,
-                           W.alphas_p, W.betas_p, W.ctl_p, step_tol, (krylovdim - 1 > kfirst) ? 1 : 0, W.hred.p);
+            lz_launch_finish(W, krylovdim - 1, step_tol, krylovdim - 1 > kfirst);
         }
         // the first mat-vec of a possible next cycle only needs v_K = V[:,krylovdim], which is
         // final now: enqueue it before the host round trip so the GPU works during the K x K
         // eigensolve (wasted only when this cycle turns out to be the last one)
         // -- speculated only when this block's previous projection needed a restart too
-        const bool speculate = !cyc && !blk1 && (W.prev_numiter > 1 || R.numiter > 1);
+        const bool speculate = !blk1 && (W.prev_numiter > 1 || R.numiter > 1);
         if (speculate) {
-            launch_symv(W, xp, W.V.p + (size_t)krylovdim * W.npad, true);
-            W.lst.symv_launches--; W.lst.symv_bytes -= 8.0 * (double)W.N + 16.0 * (double)W.n;   // counted when used
+            launch_symv(W, xp, W.V.p + (size_t)krylovdim * W.npad, true, ctl);
+            count_matvecs(W, -1);                         // counted when used
         }
-        PX_HIP(hipMemcpyAsync(W.rec_host, W.rec.p, EigWork::REC_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (wide) PX_HIP(hipMemcpyAsync(W.recw_pinned.p, W.recw.p, EigWork::RECW_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
+        else PX_HIP(hipMemcpyAsync(W.rec_host, W.rec.p, EigWork::REC_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
         // host work under the GPU's cycle: the first part of the split eigensolve, or the arrow reduction of the QL path
         if (!(split_cycle && lz_split_first(W, R, k1))) lz_prepare_arrow(R);
         const double tdbg0 = debug ? now_s() : 0.0;
@@ -1747,36 +1649,14 @@ inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, W.cye[0], W.cye[1]) == hipSuccess) W.lst.cycle_ms += ms;
         }
-        if (cyc) std::memcpy(&cy_err_host, W.cy_err_host.p, sizeof(int));
-        if (cyc && cy_err_host != 0) {
-            // a spin inside the persistent kernel timed out (its workgroups were not all resident):
-            // switch this block to the step kernels for the rest of the solve and redo the projection
-            W.cy_disabled = true;
-            W.cy_err.zero(stream);
-            W.lst.lanczos_calls--;
-            lanczos(W, xp, nev, positive_part);
-            return;
-        }
-        if (W.ev.used) {                                   // harvest profiled symv launches
-            for (size_t s = 0; s < W.ev.used; ++s) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, W.ev.e0[s], W.ev.e1[s]) == hipSuccess) {
-                    W.lst.symv_profiled_ms += ms; W.lst.symv_profiled++;
-                }
-            }
-            W.ev.used = 0;
-        }
-        for (size_t s = 0; s < W.evo.used; ++s) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, W.evo.e0[s], W.evo.e1[s]) == hipSuccess) {
-                W.lst.orth_profiled_ms += ms; W.lst.orth_profiled++;
-            }
-        }
-        W.evo.used = 0;
+        W.ev.harvest(W.lst.symv_profiled_ms, W.lst.symv_profiled);
+        W.evo.harvest(W.lst.orth_profiled_ms, W.lst.orth_profiled);
         const double tdbg1 = debug ? now_s() : 0.0;
-        W.b1_defer = blk1;
-        const bool go_on = lz_after_cycle(W, R, speculate);
-        W.b1_defer = false;
+        bool go_on;
+        {
+            DeferGuard defer(W, blk1);
+            go_on = lz_after_cycle(W, R, speculate);
+        }
         if (debug) dbg_lz[1] += now_s() - tdbg1;
         if (!go_on) break;
     }
@@ -1788,7 +1668,7 @@ inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive
 // One step of the wide recurrence (lanczos_wide.hip.hpp): mat-vec, two measured Gram-Schmidt passes, closing.
 inline void Solver::lzw_step(EigWork& W, const double* xp, int k, int kfirst, double step_tol, bool& presymv) {
     if (k == kfirst && presymv) {                  // after a restart the mat-vec of v_keep is already in Ppart
-        W.lst.symv_launches++; W.lst.symv_bytes += 8.0 * (double)W.N + 16.0 * (double)W.n;
+        count_matvecs(W, 1);
     } else {
         launch_symv(W, xp, W.V.p + (size_t)k * W.npad, true, W.ctlw_p);
     }
@@ -1806,42 +1686,6 @@ inline void Solver::lzw_step(EigWork& W, const double* xp, int k, int kfirst, do
     hipLaunchKernelGGL(dev::k_lzw_close, dim3(W.nt), dim3(dev::TPB), 0, stream,
                        (const double*)W.w.p, W.V.p, W.npad, k, (const double*)W.hsw1.p, (const double*)W.hsw2.p,
                        W.recw.p, W.recw.p + dev::LZW_MAXK, W.ctlw_p, step_tol);
-}
-
-// KrylovKit's eigsolve for Krylov dimensions 256..511 (options.lanczos_wide_krylov = 1): the restart logic, the K x K
-// eigensolves, the convergence rules and the results are those of Solver::lanczos (lz_init / lz_after_cycle /
-// lz_finish_run); the recurrence runs on the wide kernels and the rotations on k_lzw_rotate.  Packed-tile mat-vec only.
-inline void Solver::lanczos_wide(EigWork& W, const double* xp, int nev) {
-    LzRun& R = W.lzrun;
-    if (!lz_init(W, R, nev, false)) return;
-    if (!W.wide) throw std::logic_error("lanczos_wide: workspace has no wide records");
-    R.rec = W.recw_pinned.p; R.rec_ld = dev::LZW_MAXK; R.wide = true;
-    const int krylovdim = R.krylovdim;
-    QlPool::get().arm();                              // host eigensolve helpers wake up under the first cycle
-    W.lst.wide_krylov_projections++;
-    hipLaunchKernelGGL(dev::k_lz_begin, dim3(ceil_div(W.npad, dev::TPB)), dim3(dev::TPB), 0, stream,
-                       W.V.p, (const double*)W.resid.p, W.npad, W.ctlw_p);
-    while (true) {
-        for (int k = R.kfirst; k < krylovdim; ++k) lzw_step(W, xp, k, R.kfirst, R.step_tol, R.presymv);
-        // the first mat-vec of a possible next cycle (v_K is final): as in Solver::lanczos
-        const bool speculate = W.prev_numiter > 1 || R.numiter > 1;
-        if (speculate) {
-            launch_symv(W, xp, W.V.p + (size_t)krylovdim * W.npad, true, W.ctlw_p);
-            W.lst.symv_launches--; W.lst.symv_bytes -= 8.0 * (double)W.N + 16.0 * (double)W.n;   // counted when used
-        }
-        PX_HIP(hipMemcpyAsync(W.recw_pinned.p, W.recw.p, EigWork::RECW_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
-        lz_prepare_arrow(R);                          // (host work under the GPU's cycle)
-        wait_stream();
-        if (W.ev.used) {                              // harvest profiled symv launches
-            for (size_t s = 0; s < W.ev.used; ++s) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, W.ev.e0[s], W.ev.e1[s]) == hipSuccess) { W.lst.symv_profiled_ms += ms; W.lst.symv_profiled++; }
-            }
-            W.ev.used = 0;
-        }
-        if (!lz_after_cycle(W, R, speculate)) break;
-    }
-    lz_finish_run(W, R);
 }
 
 inline void Solver::flush_rotations(RotSink& S, BatchCtx& C) {
@@ -1916,7 +1760,6 @@ inline void Solver::lanczos_batch(const std::vector<int>& blocks, const double* 
     if (pool) pool->arm();
     for (int q = 0; q < nb; ++q) fill(q).mode = live[q] ? 1 : 0;
     hipLaunchKernelGGL(dev::k_lzb_begin, dim3(ceil_div(W0.npad, dev::TPB), 1, nb), dim3(dev::TPB), 0, stream, B);
-    const double mv_bytes = 8.0 * (double)W0.N + 16.0 * (double)W0.n;
     long long nlaunch = 0, prof_blocks = 0;
     double tp0 = debug ? now_s() : 0.0;                  // PROXSDP_HIP_DEBUG: host-time split of the batched run
     auto lap = [&](double& acc) { if (debug && !concurrent) { const double t = now_s(); acc += t - tp0; tp0 = t; } };
@@ -1941,20 +1784,15 @@ inline void Solver::lanczos_batch(const std::vector<int>& blocks, const double* 
                 any_mv = any_mv || b.mode != 0;
                 if (k < kd) {
                     any_orth = true;
-                    eig[blocks[q]].lst.symv_launches++; eig[blocks[q]].lst.symv_bytes += mv_bytes;
+                    count_matvecs(eig[blocks[q]], 1);
                 }
             }
             // every profile_symv_every-th batched mat-vec launch carries its own start/stop events
             const bool prof = any_mv && opt.profile_symv_every > 0 && t > 0 && t < tmax && (nlaunch++ % opt.profile_symv_every) == 0;
             if (prof) {
-                if (W0.ev.used == W0.ev.e0.size()) {
-                    hipEvent_t a, b2;
-                    PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b2));
-                    W0.ev.e0.push_back(a); W0.ev.e1.push_back(b2);
-                }
-                const size_t slot = W0.ev.used++;
+                const auto ev = W0.ev.acquire();
                 hipExtLaunchKernelGGL(dev::k_lzb_mv, dim3(W0.nt + ntile, 1, nb), dim3(dev::TPB), 0, stream,
-                                      W0.ev.e0[slot], W0.ev.e1[slot], 0, B, rec_out, rec_n);
+                                      ev.first, ev.second, 0, B, rec_out, rec_n);
                 int act = 0;
                 for (int q = 0; q < nb; ++q) act += (B.b[q].mode == 2) ? 1 : 0;
                 prof_blocks += act;
@@ -1988,13 +1826,7 @@ inline void Solver::lanczos_batch(const std::vector<int>& blocks, const double* 
         lap(dbg_batch[1]);                               // waiting for the GPU
         for (int q = 0; q < nb; ++q)
             if (live[q]) std::memcpy(eig[blocks[q]].rec_host, C.rec_host.p + (size_t)q * EigWork::REC_DOUBLES, EigWork::REC_DOUBLES * sizeof(double));
-        for (size_t sl = 0; sl < W0.ev.used; ++sl) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, W0.ev.e0[sl], W0.ev.e1[sl]) == hipSuccess) {
-                W0.lst.symv_profiled_ms += ms; W0.lst.symv_profiled++;
-            }
-        }
-        W0.ev.used = 0;
+        W0.ev.harvest(W0.lst.symv_profiled_ms, W0.lst.symv_profiled);
         // per-block restart logic (K x K eigensolve, convergence, rotation matrix): independent, on the helper threads
         std::exception_ptr err[dev::LZB_MAX] = {};
         auto job = [&](int q) {

@@ -1486,25 +1486,20 @@ def test_batched_small_block_projection_against_lapack(n):
 
 
 @pytest.mark.parametrize("n,maxrank,rank0", [(700, 16, 2), (1500, 40, 30)])
-def test_persistent_cycle_kernel_matches_the_step_kernels(n, maxrank, rank0):
-    """lanczos_cycle_kernel = 1: one persistent launch per Lanczos cycle (workgroups of one XCD keep their
-    rows of the basis in LDS, partial dots exchanged through that XCD's L2).  Same arithmetic per step as
-    the two step kernels, only the grouping of partial sums differs: same mat-vec / restart counts, traces
-    to 1e-9.  (If the placement assumption failed, the bounded spins would time out and the library would
-    fall back to the step kernels: cycle_launches would still be counted but the test's equality holds
-    either way; the second assertion checks that cycles really ran.)"""
+def test_cycle_kernel_option_1_is_the_step_kernels(n, maxrank, rank0):
+    """lanczos_cycle_kernel = 1 selected a persistent multi-workgroup cycle kernel that has been removed; the value is kept in
+    the ABI and now means 0, the step kernels.  Operator-form Max-Cut with thick restarts: no cycle launches, and the traces
+    (all but the wall clock, column 12), iteration counts and mat-vec / restart counts are EQUAL, bit for bit."""
     pr = P.maxcut(n, seed=5)
     kw = dict(max_iter=160, support_path=1, max_target_rank_krylov_eigs=maxrank, initial_target_rank=rank0)
     a = Optimizer(lanczos_cycle_kernel=0, **kw).optimize(pr, trace_capacity=160)
     b = Optimizer(lanczos_cycle_kernel=1, **kw).optimize(pr, trace_capacity=160)
-    assert a.stats["cycle_launches"] == 0 and b.stats["cycle_launches"] > 100
-    assert b.stats["cycle_steps"] >= 0.9 * b.stats["lanczos_matvecs"]
+    assert a.stats["cycle_launches"] == 0 == b.stats["cycle_launches"]
     assert a.iter == b.iter and a.status == b.status
-    assert np.array_equal(a.trace[:, 13], b.trace[:, 13])                         # mat-vecs per iteration
-    assert np.array_equal(a.trace[:, 11], b.trace[:, 11])                         # linesearch trials
-    assert a.stats["lanczos_restarts"] == b.stats["lanczos_restarts"]
-    for col in (1, 2, 7):
-        assert np.allclose(a.trace[:, col], b.trace[:, col], rtol=1e-9, atol=1e-12), col
+    assert a.stats["lanczos_matvecs"] == b.stats["lanczos_matvecs"] > 0
+    assert a.stats["lanczos_restarts"] == b.stats["lanczos_restarts"] > 0
+    cols = [c for c in range(a.trace.shape[1]) if c != 12]                       # (column 12 is the wall clock)
+    assert np.array_equal(a.trace[:, cols], b.trace[:, cols]), np.abs(a.trace - b.trace).max(axis=0)
 
 
 @pytest.mark.parametrize("name", ["maxcut150", "maxcut300", "maxcut500", "sensorloc100", "sensorloc200", "mcp124-1", "mcp250-1", "gpp124-2"])
