@@ -40,8 +40,11 @@ whatever --steps/--warmup are ("cold_start_window" reports the --settle 0 window
 Extra objects on the JSON line: "roofline" for the two launches of a Lanczos
 step (HIP events recorded by the library on its own stream around every 16th
 launch inside the timed solve; bytes actually moved, so frac <= 1) and
-"cpu_baseline" (the NumPy/SciPy oracle -- a restatement, NOT the Julia
-reference, which cannot run here -- on a bounded sample of the same instance at
+"cold_start_window", both read from the headline solve itself.  Everything else
+takes runs of its own and is left out unless --full is given (N = 1 only; the
+--no-* options still drop single legs): "cpu_baseline" (the NumPy/SciPy
+oracle -- a restatement, NOT the Julia reference, which cannot run here -- on
+a bounded sample of the same instance at
 the same pinned rank, rank 0, N = 1 only), plus "early_iterations" (first
 iterations at rank 2..5), "packed_operator" (the reference's mat-vec operator:
 the HBM-bound kernel, with an n = 16000 HBM-resident leg), "time_to_tol"
@@ -142,7 +145,12 @@ def main():
     ap.add_argument("--mimo-n", type=int, default=512)
     ap.add_argument("--no-config-legs", action="store_true",
                     help="skip the compact legs of BASELINE configs 3 / 4 / 5 (config_randsdp, config_mimo_x8, config_sdplib) "
-                         "that ride in the default line")
+                         "that ride in the --full line")
+    ap.add_argument("--full", action="store_true",
+                    help="maxcut workload, N = 1: after the headline solve, also run the side legs that take runs of their own "
+                         "(early_iterations, packed_operator, time_to_tol*, full_eig_regime_n4000, cpu_baseline, "
+                         "config_maxcut_n1000, config_sdplib / config_mimo_x8 / config_randsdp, medium_blocks).  Without it "
+                         "the line carries what the headline solve yields: value, its roofline, cold_start_window")
     ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the headline solve returned after its last step to DIR/<name>.npy "
                          "(float64; outputs longer than %d entries as a fixed, seeded sample)" % DUMP_SAMPLE)
@@ -266,7 +274,7 @@ def main():
         out["cold_start_window"] = {"value": K / tc_, "unit": "iterations/s", "ms_per_step": 1e3 * tc_ / K,
                                     "timed_iterations": [W0 + 1, W0 + K], "lanczos_matvecs_per_step": mvc_}
         out["config"]["cold_start_it_per_s"] = K / tc_
-    solo = rank == 0 and world == 1
+    solo = rank == 0 and world == 1 and args.full        # the side legs below: --full, one rank
     if solo and not args.no_early_leg:
         # the first iterations of a solve with reference default options (target rank 2..5): the
         # cheapest regime, 25-46 mat-vecs per iteration -- side figure only

@@ -72,6 +72,14 @@ def test_bench_refuses_a_world_size_that_is_not_gpus():
     assert r.returncode == 0 and '"n_gpus": 1' in r.stdout
 
 
+def test_bench_full_is_an_option():
+    """`--full` (the side legs of the maxcut line) is parsed on every path, the dry run included"""
+    r = _run_bench({"PROXSDP_BENCH_DRYRUN": "1"}, "--gpus", "1", "--steps", "3", "--full")
+    assert r.returncode == 0 and '"n_gpus": 1' in r.stdout, r.stderr[-2000:]
+    r = _run_bench({}, "--help")
+    assert r.returncode == 0 and "--full" in r.stdout
+
+
 def test_block_assignment():
     assert replicas.assign_blocks(8, 8) == list(range(8))
     assert replicas.assign_blocks(8, 2) == [0, 1, 0, 1, 0, 1, 0, 1]

@@ -4,8 +4,8 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r02prof; rm -rf $O; mkdir -p $O
 rocprofv3 -L 2>/dev/null | grep -i -E "mfma|FETCH_SIZE|WRITE_SIZE|GRBM_GUI_ACTIVE|SQ_BUSY_CYCLES|SQ_WAVE_CYCLES" | head -40 > $O/counters_available.txt
-rocprofv3 --kernel-trace --stats -d $O/kt -- python bench.py --no-cpu --no-time-to-tol --hbm-n 0 > $O/bench_under_rocprof.json 2> $O/kt.err
-python tools/prof_summary.py $O/kt profiles_r02_kernel_stats.md "Kernel stats, round 2: bench.py windows (rank-63 headline, early iterations, packed operator)" "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu --no-time-to-tol --hbm-n 0" > /dev/null
+rocprofv3 --kernel-trace --stats -d $O/kt -- python bench.py --full --no-cpu --no-time-to-tol --hbm-n 0 > $O/bench_under_rocprof.json 2> $O/kt.err
+python tools/prof_summary.py $O/kt profiles_r02_kernel_stats.md "Kernel stats, round 2: bench.py windows (rank-63 headline, early iterations, packed operator)" "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu --no-time-to-tol --hbm-n 0" > /dev/null
 mv profiles_r02_kernel_stats.md $O/
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch -- python tools/gpurun_pmc5.py > $O/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write -- python tools/gpurun_pmc5.py > $O/pmc_write.log 2>&1
