@@ -344,6 +344,7 @@ k_symv_packed(const double* __restrict__ xp, int n, int nt, int npad,
 constexpr int MAXK = 260;           // capacity of the Krylov basis (krylovdim + 1 <= 256: the step kernels hold
                                     // 16*NCH <= 64 basis columns per wave in registers, 4 waves, and map
                                     // thread j <-> basis column j) => target rank <= 127
+constexpr int LZ_KMAX = 255;        // largest Krylov dimension of the step kernels (the wide kernels take 256..511)
 constexpr int LZ_ROWS = TILE;       // rows per workgroup in the Lanczos vector kernels
 constexpr int NRM_SLOT = MAXK - 1;  // slot of a partial-dots row that carries |w'|^2
 

@@ -168,7 +168,7 @@ inline void Solver::project_block(int idx, const double* xin, double* xout, bool
     W.use_fop = !lanczos_done && fuse && use_support && opt.lanczos_operator != 0 && W.fop_ok && krylov &&
                 (W.have_factors || W.x_prev_sparse) && !(opt.krylovkit_eager && opt.eigsolver != 1);
     // (a Krylov dimension beyond the step kernels -- the wide kernels or the dense stand-in -- takes the packed-tile mat-vec)
-    if (std::max(2 * (int)target_rank[idx] + 1, (int)opt.eigsolver_min_lanczos) > dev::MAXK - 1) W.use_fop = false;
+    if (std::max(2 * (int)target_rank[idx] + 1, (int)opt.eigsolver_min_lanczos) > dev::LZ_KMAX) W.use_fop = false;
     if (W.use_fop) {
         if (!W.have_factors) { W.F_r = 0; W.F_first = 0; }
         W.esv = esv_d.p + (W.have_factors ? 0 : ns);

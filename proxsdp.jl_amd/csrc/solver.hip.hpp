@@ -663,7 +663,7 @@ private:
     // krylovkit_eager, whose driver is written on the step kernels)
     bool krylovdim_fits(int nev) const {
         const int kd = std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos);
-        if (kd <= dev::MAXK - 1) return true;
+        if (kd <= dev::LZ_KMAX) return true;
         return opt.lanczos_wide_krylov == 1 && kd <= dev::LZW_MAXK - 1 && !(opt.krylovkit_eager && opt.eigsolver != 1);
     }
     bool exact_projection_by_sign(int idx, const double* xp, double* xo, bool fuse, int nev);
@@ -719,13 +719,13 @@ inline void Solver::alloc_eigwork(EigWork& W, int n, int max_nev) {
     W.nt = ceil_div(n, dev::TILE);
     W.npad = W.nt * dev::TILE;
     W.nwg = ceil_div(n, dev::TPB);
-    // the step kernels hold up to dev::MAXK - 1 = 255 basis columns; a projection whose Krylov dimension
+    // the step kernels run Krylov dimensions up to dev::LZ_KMAX = 255; a projection whose Krylov dimension
     // max(2 target_rank + 1, eigsolver_min_lanczos) is larger (options.jl:76,88 accept any value) is served by the dense
     // eigensolver instead (Solver::truncated_project_dense): the workspace is sized for what the kernels can run
     // (with lanczos_wide_krylov = 1 up to 511 columns: the wide kernels, lanczos_wide.hip.hpp)
     const int kd_want = std::max(2 * max_nev + 1, (int)opt.eigsolver_min_lanczos);
-    W.wide = opt.lanczos_wide_krylov == 1 && kd_want > dev::MAXK - 1;
-    int kd = std::min(kd_want, W.wide ? dev::LZW_MAXK - 1 : dev::MAXK - 1);
+    W.wide = opt.lanczos_wide_krylov == 1 && kd_want > dev::LZ_KMAX;
+    int kd = std::min(kd_want, W.wide ? dev::LZW_MAXK - 1 : dev::LZ_KMAX);
     W.cap = kd + 1;
     W.V.alloc((size_t)W.npad * W.cap);
     W.Z.alloc((size_t)W.npad * W.cap);
@@ -1116,7 +1116,7 @@ inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     if (krylovdim + 1 > W.cap) throw std::invalid_argument("Lanczos workspace too small for the requested rank");
     R.krylovdim = krylovdim;
     // Krylov dimension beyond the step kernels (lanczos_wide_krylov = 1): the wide kernels and their own record
-    R.wide = krylovdim > dev::MAXK - 1;
+    R.wide = krylovdim > dev::LZ_KMAX;
     if (R.wide && !W.wide) throw std::logic_error("wide Lanczos: workspace has no wide records");
     R.rec = R.wide ? W.recw_pinned.p : W.rec_host;
     R.rec_ld = R.wide ? dev::LZW_MAXK : dev::MAXK;

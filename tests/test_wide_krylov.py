@@ -9,7 +9,7 @@ from proxsdp_jl_amd import binding as B
 from proxsdp_jl_amd import problems as P
 from proxsdp_jl_amd.optimizer import Optimizer
 
-from helpers import planted_packed, smat
+from helpers import oracle_project, planted_packed, smat, svec
 
 pytestmark = pytest.mark.gpu
 
@@ -161,3 +161,94 @@ def test_wide_two_block_model_with_and_without_block_workers():
         assert sol.stats["wide_krylov_projections"] == 15 and sol.stats["dense_truncated_projections"] == 0
         assert sol.stats["lanczos_calls"] == 30
     assert np.array_equal(sols[0].trace[:, NOT_TIME], sols[1].trace[:, NOT_TIME])
+
+
+# ----------------------------------------------------------------- edge cases of the wide engine (as test_lanczos_edge_cases
+# for the step kernels)
+@pytest.mark.parametrize("n", [576, 1024])
+def test_wide_eigsolve_sides_multiple_of_64(n):
+    """no padding rows: the last row group is full"""
+    _check_eigsolve(n, 130, 261, list(np.linspace(80.0, 5.0, 150)), (-3.0, 0.5), 40 + n)
+
+
+@pytest.mark.parametrize("n,nev", [(260, 130), (300, 150)])
+def test_wide_eigsolve_krylov_dimension_beyond_n(n, nev):
+    """Krylov dimension 2 nev + 1 > n: the Krylov space runs out inside the first cycle"""
+    _check_eigsolve(n, nev, 2 * nev + 1, list(np.linspace(50.0, 10.0, nev + 10)), (-2.0, 1.0), 60 + n)
+
+
+def test_wide_eigsolve_zero_matrix():
+    """invariant subspace at K = 1, howmany reduced -- the step kernels' case in test_lanczos_edge_cases"""
+    vals, vecs, info = B.eigsolve(np.zeros(300 * 301 // 2), 300, 130, options=_wide())
+    assert list(vals) == [0.0] and info["converged"] == 1 and info["nmatvec"] == 1
+
+
+def test_wide_eigsolve_exact_low_rank_stops_mid_cycle():
+    """a rank-5 PSD matrix: the Krylov space has dimension 6, so the engine stops at step 6 of a 261-step cycle; values,
+    vectors and counts as the oracle's"""
+    n, nev = 600, 130
+    rng = np.random.default_rng(21)
+    Z, _ = np.linalg.qr(rng.standard_normal((n, 5)))
+    lam = np.array([9.0, 7.0, 4.0, 2.5, 1.0])
+    X = (Z * lam) @ Z.T
+    X = (X + X.T) / 2
+    x = svec(X)
+    vals, vecs, info = B.eigsolve(x, n, nev, options=_wide(), cap=262)
+    ovals, ovecs, oconv, onumiter, onumops = oeig.krylovkit_eigsolve(lambda v: X @ v, oeig.start_vector(n), nev, 261,
+                                                                     100, 1e-12)
+    assert info["numiter"] == onumiter and info["nmatvec"] == onumops, (info, onumiter, onumops)
+    assert onumops < 261
+    assert len(vals) == len(ovals) and info["converged"] == oconv
+    assert np.abs(vals - ovals).max() <= 1e-12 * 9.0
+    assert np.abs(vals[:5] - lam).max() <= 1e-12 * 9.0
+    assert np.abs(X @ vecs - vecs * vals).max() <= 1e-10 * 9.0
+    assert np.abs(vecs.T @ vecs - np.eye(len(vals))).max() <= 1e-10
+
+
+def test_wide_eigsolve_explicit_start_vector_and_determinism():
+    n, nev = 700, 130
+    x = planted_packed(n, 23, list(np.linspace(60.0, 5.0, nev + 10)), bulk=(-3.0, 0.5))
+    r = np.random.default_rng(5).standard_normal(n)
+    v1, z1, i1 = B.eigsolve(x, n, nev, options=_wide(), resid=r)
+    v2, z2, i2 = B.eigsolve(x, n, nev, options=_wide(), resid=3.0 * r)   # normalised inside, as KrylovKit does
+    assert np.allclose(v1[:nev], v2[:nev], rtol=0, atol=1e-12 * 60.0) and i1["nmatvec"] == i2["nmatvec"]
+    X = smat(x, n)
+    ovals, _, _, onumiter, onumops = oeig.krylovkit_eigsolve(lambda v: X @ v, r / np.linalg.norm(r), nev, 261, 100, 1e-12)
+    assert i1["nmatvec"] == onumops and i1["numiter"] == onumiter
+    assert np.abs(v1[:nev] - ovals[:nev]).max() <= 1e-11 * 60.0
+    # fixed-order sums: two identical calls give the same bits
+    v3, z3, i3 = B.eigsolve(x, n, nev, options=_wide(), resid=r)
+    assert np.array_equal(v1, v3) and np.array_equal(z1, z3) and i1 == i3
+
+
+def test_wide_psd_project_rank130_against_oracle():
+    n, tr = 600, 130
+    x = planted_packed(n, 29, list(np.linspace(70.0, 3.0, tr + 15)), bulk=(-4.0, 0.5))
+    out, info = B.psd_project(x, n, tr, mode=0, options=_wide())
+    o_out, o_rank, o_min, arc = oracle_project(x, n, tr, False)
+    scale = np.abs(x).max()
+    assert np.allclose(out, o_out, rtol=0, atol=2e-9 * scale), np.abs(out - o_out).max()
+    assert info["rank"] == o_rank and info["fell_back"] == 0
+    assert abs(info["min_eig"] - o_min) <= 1e-9 * scale
+    assert info["nmatvec"] == arc.matvecs
+
+
+@pytest.mark.parametrize("min_lanczos", [255, 256, 259])
+def test_wide_engine_boundary_min_lanczos(min_lanczos):
+    """Krylov dimension max(2 nev + 1, eigsolver_min_lanczos): 255 stays on the step kernels (their 4 waves x 64 basis
+    columns), 256 is the first wide one, and 259 (the last that fits the step kernels' record stride) is wide too"""
+    pr = P.maxcut(300, seed=3)
+    iters = 15
+    sol = Optimizer(lanczos_wide_krylov=1, eigsolver_min_lanczos=min_lanczos, max_iter=iters).optimize(
+        pr, trace_capacity=iters)
+    o = Options()
+    o.max_iter, o.eigsolver_min_lanczos = iters, min_lanczos
+    omv = []
+    ref = oracle.solve(pr, o, trace=True, proj_callback=lambda it, xi, xo, p_, arc: omv.append(int(arc[0].matvecs)))
+    assert sol.status == ref.status and sol.iter == ref.iter == iters
+    per_it = np.diff(np.array([0] + omv))
+    assert _counts_match(sol.trace[:, 13], per_it), (sol.trace[:, 13], per_it)
+    G = _trace_cols(ref.trace)
+    assert np.allclose(sol.trace[:, COLS], G, rtol=1e-8, atol=1e-10 * np.abs(G).max())
+    assert sol.stats["wide_krylov_projections"] == (0 if min_lanczos == 255 else iters)
+    assert sol.stats["dense_truncated_projections"] == 0
