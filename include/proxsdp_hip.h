@@ -321,11 +321,11 @@ typedef struct proxsdp_options {
                                   * sends the next 8 projections two rows down, a second one soon after lowers the row for good); 0 = the full table, no test
                                   * (round-2 behaviour); k > 0 = always start at row k (capped where the test stops
                                   * resolving 1e-10) */
-    int32_t general_batch;       /* models without a support set (full-vector passes, sparse M): linesearch candidates,
-                                  * residual and gap in one batch of launches and ONE read-back per iteration (up to 3
-                                  * candidates evaluated side by side, the first the reference's loop would accept wins;
-                                  * per candidate the same arithmetic): -1 auto = 1 = on, 0 = one trial per
-                                  * synchronisation (round-2 path) */
+    int32_t general_batch;       /* linesearch candidates per read-back on every vector path (support set, full vectors,
+                                  * dense M): -1 auto = 1 = up to 3 candidates, their residual and gap reductions in one
+                                  * batch of launches and ONE read-back per iteration (the first the reference's loop would
+                                  * accept wins); 0 = one candidate per read-back.  Per candidate the same arithmetic: the
+                                  * same bits either way */
     int32_t full_eig_lanczos_certify; /* PER-CALL certificate of a Lanczos-served full_eig! (single-vector Lanczos shows one
                                   * eigenvector per distinct eigenvalue the start vector sees: a repeated positive eigenvalue
                                   * or a deficient start vector would drop positive pairs from X+): after convergence a
@@ -399,8 +399,8 @@ typedef struct proxsdp_stats {
     double  loop_time;           /* s: the PDHG loop ("CP loop")                     */
     double  exit_time;           /* s: cache_solution                                */
     double  t_primal, t_psd, t_linesearch, t_residual;   /* s, host wall incl. syncs: the reference's TimerOutputs sections (pdhg.jl:150-164).
-                                  * t_primal = primal_step! incl. the projection (t_psd); on the fused paths the residual / gap REDUCTIONS
-                                  * ride in the linesearch candidates' batch and its one read-back (counted in t_linesearch), t_residual is
+                                  * t_primal = primal_step! incl. the projection (t_psd); on every path the residual / gap REDUCTIONS
+                                  * ride in the linesearch candidates' batch and its read-back (counted in t_linesearch), t_residual is
                                   * what is left of compute_residual! / compute_gap!: the host scalars */
     int64_t dense_passes;        /* passes over a dense A (A x or batched A' y), 8*p*n bytes each */
     double  dense_ms;            /* their summed durations (HIP events on the solve stream)    */

@@ -442,9 +442,11 @@ int proxsdp_hip_dual_trial(const double* y, const double* Mx, const double* Mx_o
         proxsdp::DevBuf<double> dy(Q), d1(Q), d0(Q), dbh(Q), dout(Q), part(proxsdp::PSTRIDE), sc(2);
         dy.upload(y, Q, st); d1.upload(Mx, Q, st); d0.upload(Mx_old, Q, st); dbh.upload(bh, Q, st);
         part.zero(st);
-        hipLaunchKernelGGL(proxsdp::dev::k_dual_trial, dim3(g), dim3(proxsdp::dev::TPB), 0, st,
+        proxsdp::dev::TrialBatch tb{};               // one linesearch candidate
+        tb.nc = 1; tb.bt[0] = bt; tb.theta[0] = theta;
+        hipLaunchKernelGGL(proxsdp::dev::k_dual_trial_batch, dim3(g, 1), dim3(proxsdp::dev::TPB), 0, st,
                            (const double*)dy.p, (const double*)d1.p, (const double*)d0.p, (const double*)dbh.p,
-                           (int)p, (int)Q, bt, theta, dout.p, part.p, 1);
+                           (int)p, (int)Q, tb, dout.p, (long long)Q, part.p, 0LL);
         hipLaunchKernelGGL(proxsdp::dev::k_combine, dim3(1), dim3(proxsdp::dev::TPB), 0, st,
                            (const double*)part.p, proxsdp::PSTRIDE, g, 1, 0u, sc.p);
         dout.download(y_out, Q, st);
@@ -468,21 +470,22 @@ int proxsdp_hip_residuals(const double* x, const double* x_old, const double* Mt
         using proxsdp::DevBuf;
         const int gx = std::min(proxsdp::PSTRIDE, proxsdp::grid_for(n)), gq = std::min(proxsdp::PSTRIDE, proxsdp::grid_for(Q));
         DevBuf<double> dx(n), dxo(n), dm(n), dmo(n), dc(n), dy(Q), dyo(Q), d1(Q), d0(Q), dbh(Q);
-        DevBuf<double> part((size_t)9 * proxsdp::PSTRIDE), sc(9);
+        DevBuf<double> part((size_t)11 * proxsdp::PSTRIDE), sc(9);
         dx.upload(x, n, st); dxo.upload(x_old, n, st); dm.upload(Mty, n, st); dmo.upload(Mty_old, n, st); dc.upload(c, n, st);
         dy.upload(y, Q, st); dyo.upload(y_old, Q, st); d1.upload(Mx, Q, st); d0.upload(Mx_old, Q, st); dbh.upload(bh, Q, st);
         part.zero(st);
-        // the kernels lay their quantities out with stride gridDim.x: run both with PSTRIDE-strided combines
-        hipLaunchKernelGGL(proxsdp::dev::k_residual_x, dim3(gx), dim3(proxsdp::dev::TPB), 0, st,
-                           (const double*)dx.p, (const double*)dxo.p, 1.0, (const double*)dm.p, (const double*)dmo.p,
-                           (const double*)dc.p, tau, (long long)n, part.p);
+        // one candidate of the linesearch's residual batch: the x part lands in quantities 2..4, the y part in 5..10
+        proxsdp::dev::TrialBatch tb{};
+        tb.nc = 1; tb.tau[0] = tau; tb.sigma[0] = sigma;
+        hipLaunchKernelGGL(proxsdp::dev::k_residual_xy_full_batch, dim3(std::max(gx, gq), 1, 2), dim3(proxsdp::dev::TPB), 0, st,
+                           (const double*)dx.p, (const double*)dxo.p, 1.0, (const double*)dm.p, (long long)n,
+                           (const double*)dmo.p, (const double*)dc.p, (long long)n, gx,
+                           (const double*)dy.p, (long long)Q, (const double*)dyo.p, (const double*)d1.p, (const double*)d0.p,
+                           (const double*)dbh.p, (int)p, (int)Q, gq, tb, part.p, proxsdp::PSTRIDE, 0LL);
         hipLaunchKernelGGL(proxsdp::dev::k_combine, dim3(1), dim3(proxsdp::dev::TPB), 0, st,
-                           (const double*)part.p, gx, gx, 3, 0x3u, sc.p);
-        hipLaunchKernelGGL(proxsdp::dev::k_residual_y, dim3(gq), dim3(proxsdp::dev::TPB), 0, st,
-                           (const double*)dy.p, (const double*)dyo.p, (const double*)d1.p, (const double*)d0.p,
-                           (const double*)dbh.p, (int)p, (int)Q, sigma, part.p + (size_t)3 * proxsdp::PSTRIDE);
+                           (const double*)(part.p + (size_t)2 * proxsdp::PSTRIDE), proxsdp::PSTRIDE, gx, 3, 0x3u, sc.p);
         hipLaunchKernelGGL(proxsdp::dev::k_combine, dim3(1), dim3(proxsdp::dev::TPB), 0, st,
-                           (const double*)(part.p + (size_t)3 * proxsdp::PSTRIDE), gq, gq, 6, 0xFu, sc.p + 3);
+                           (const double*)(part.p + (size_t)5 * proxsdp::PSTRIDE), proxsdp::PSTRIDE, gq, 6, 0xFu, sc.p + 3);
         sc.download(out, 9, st);
         PX_HIP(hipStreamSynchronize(st));
         return 0;

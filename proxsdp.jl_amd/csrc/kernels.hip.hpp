@@ -1765,32 +1765,6 @@ k_spmv_csr_wave(const int* __restrict__ rowptr, const int* __restrict__ col, con
     if (lane == 0) y[r] = acc;
 }
 
-// y+ = ybar - bt*box(ybar/bt),  ybar = y + bt((1+theta)Mx - theta Mx_old)
-// pdhg.jl:547-553 + box_projection! (prox_operators.jl:160-170), fused with the
-// partial of |y+ - y_old|^2 (pdhg.jl:561-562; y_old == y at this point).
-__global__ void __launch_bounds__(TPB)
-k_dual_trial(const double* __restrict__ y, const double* __restrict__ Mx, const double* __restrict__ Mx_old,
-             const double* __restrict__ bh, int p, int Q, double bt, double theta,
-             double* __restrict__ yout, double* __restrict__ part, int addback) {
-    __shared__ double sm[NWAVE];
-    double ss = 0.0;
-    for (int i = blockIdx.x * TPB + threadIdx.x; i < Q; i += gridDim.x * TPB) {
-        const double yi = y[i];
-        const double ybar = yi + bt * ((1.0 + theta) * Mx[i] - theta * Mx_old[i]);
-        const double proj = (i < p) ? bh[i] : fmin(ybar / bt, bh[i]);
-        const double yn = ybar - bt * proj;
-        const double d = yn - yi;
-        // linesearch! takes its norms "in place" (y_temp .-= y_old ... y_temp .+= y_old, pdhg.jl:560-575):
-        // the y it keeps is fl(fl(y+ - y_old) + y_old); dual_step! (addback = 0) keeps y+ itself
-        yout[i] = addback ? d + yi : yn;
-        ss += d * d;
-    }
-    double tot = block_sum(ss, sm);
-    if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-// no-linesearch variant (dual_step!, pdhg.jl:584-609): ybar = y + sigma(2Mx - Mx_old)
-// is the same kernel with theta = 1, bt = sigma.
-
 // ---- long columns of M (round 6).  The transposed products below give every column to ONE thread, which walks its entries
 // with two dependent memory round trips per entry (row index, then y[row]): ~250 ns per entry.  Sensor localisation has three
 // columns -- the entries of the identity block, present in every anchor constraint -- with thousands of entries: ONE launch of
@@ -1903,28 +1877,6 @@ __device__ __forceinline__ double col_dot(const LongCols& L, int col, const int*
     return acc;
 }
 
-// Mty = M' y (M in CSC: one dot per column) fused with |Mty - Mty_old|^2
-// pdhg.jl:556-563.  Thread per column; columns are mostly empty or short.
-__global__ void __launch_bounds__(TPB)
-k_spmv_csc_norm(const int* __restrict__ colptr, const int* __restrict__ row, const double* __restrict__ val,
-                const double* __restrict__ y, double* __restrict__ Mty, const double* __restrict__ Mty_old,
-                long long ncols, double* __restrict__ part, int addback) {
-    __shared__ double sm[NWAVE];
-    __shared__ LongCols lc;
-    double ss = 0.0;
-    long long j = (long long)blockIdx.x * TPB + threadIdx.x;
-    const long long stride = (long long)gridDim.x * TPB;
-    long_cols_collect(lc, colptr, row, val, y, j, stride, ncols, [](long long s) { return (int)s; });
-    for (; j < ncols; j += stride) {
-        const double acc = col_dot(lc, (int)j, colptr, row, val, y);
-        const double o = Mty_old[j];
-        const double d = acc - o;
-        Mty[j] = addback ? d + o : acc;       // pdhg.jl:560,574 (a.Mty .-= a.Mty_old ... a.Mty .+= a.Mty_old)
-        ss += d * d;
-    }
-    double tot = block_sum(ss, sm);
-    if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
 // plain transposed product (test entry point)
 __global__ void __launch_bounds__(TPB)
 k_spmv_csc(const int* __restrict__ colptr, const int* __restrict__ row, const double* __restrict__ val,
@@ -1935,61 +1887,6 @@ k_spmv_csc(const int* __restrict__ colptr, const int* __restrict__ row, const do
         double acc = 0.0;
         for (int k = colptr[j]; k < colptr[j + 1]; ++k) acc += val[k] * y[row[k]];
         out[j] = acc;
-    }
-}
-
-// compute_residual! (x part, residuals.jl:41-48) + prim_obj = c.x (residuals.jl:22)
-// in ONE pass over (x, x_old, Mty, Mty_old, c).  part layout: [3][grid]:
-//   0: max |(x - tau Mty) - (x_old - tau Mty_old)|   1: max |x_old - tau Mty_old|   2: sum c*x
-__global__ void __launch_bounds__(TPB)
-k_residual_x(const double* __restrict__ x, const double* __restrict__ xold, double xold_coef,
-             const double* __restrict__ Mty, const double* __restrict__ Mty_old, const double* __restrict__ c,
-             double tau, long long N, double* __restrict__ part) {
-    __shared__ double sm[NWAVE];
-    double m0 = 0.0, m1 = 0.0, s2 = 0.0;
-    long long i = (long long)blockIdx.x * TPB + threadIdx.x;
-    const long long stride = (long long)gridDim.x * TPB;
-    for (; i < N; i += stride) {
-        const double xi = x[i];
-        const double pold = xold_coef * xold[i] - tau * Mty_old[i];
-        const double pnew = xi - tau * Mty[i];
-        m0 = fmax(m0, fabs(pnew - pold));
-        m1 = fmax(m1, fabs(pold));
-        s2 += c[i] * xi;
-    }
-    double r0 = block_max(m0, sm);
-    double r1 = block_max(m1, sm);
-    double r2 = block_sum(s2, sm);
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = r0;
-        part[gridDim.x + blockIdx.x] = r1;
-        part[2 * gridDim.x + blockIdx.x] = r2;
-    }
-}
-// y part of compute_residual! (residuals.jl:51-58) + compute_gap! (residuals.jl:2-35)
-// part layout [6][grid]: 0 max|dPy| 1 max|Py_old| 2 max|Mx-b| (eq) 3 max(Mx-h) (ineq, >=0)
-//                        4 sum b*y_eq 5 sum h*y_in
-__global__ void __launch_bounds__(TPB)
-k_residual_y(const double* __restrict__ y, const double* __restrict__ yold,
-             const double* __restrict__ Mx, const double* __restrict__ Mx_old,
-             const double* __restrict__ bh, int p, int Q, double sigma, double* __restrict__ part) {
-    __shared__ double sm[NWAVE];
-    double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0, s4 = 0.0, s5 = 0.0;
-    for (int i = blockIdx.x * TPB + threadIdx.x; i < Q; i += gridDim.x * TPB) {
-        const double yi = y[i], mx = Mx[i], rhs = bh[i];
-        const double pold = yold[i] - sigma * Mx_old[i];
-        const double pnew = yi - sigma * mx;
-        m0 = fmax(m0, fabs(pnew - pold));
-        m1 = fmax(m1, fabs(pold));
-        if (i < p) { m2 = fmax(m2, fabs(mx - rhs)); s4 += rhs * yi; }
-        else       { m3 = fmax(m3, mx - rhs);       s5 += rhs * yi; }
-    }
-    double r0 = block_max(m0, sm), r1 = block_max(m1, sm), r2 = block_max(m2, sm), r3 = block_max(m3, sm);
-    double r4 = block_sum(s4, sm), r5 = block_sum(s5, sm);
-    if (threadIdx.x == 0) {
-        const int g = gridDim.x, b = blockIdx.x;
-        part[b] = r0; part[g + b] = r1; part[2 * g + b] = r2; part[3 * g + b] = r3;
-        part[4 * g + b] = r4; part[5 * g + b] = r5;
     }
 }
 
@@ -2026,7 +1923,9 @@ struct TrialBatch {                 // up to 4 linesearch candidates per launch
                                     // through linesearch!'s in-place norm + revert
 };
 
-// candidates of y+ (pdhg.jl:547-553): grid.y = candidate; part[c][0][wg] = |y+ - y|^2 partials
+// candidates of y+ = ybar - bt*box(ybar/bt),  ybar = y + bt((1+theta)Mx - theta Mx_old)  (pdhg.jl:547-553 + box_projection!,
+// prox_operators.jl:160-170; dual_step!, pdhg.jl:584-609, is theta = 1, bt = sigma): grid.y = candidate;
+// part[c][0][wg] = |y+ - y|^2 partials (pdhg.jl:561-562; y_old == y at this point)
 __global__ void __launch_bounds__(TPB)
 k_dual_trial_batch(const double* __restrict__ y, const double* __restrict__ Mx, const double* __restrict__ Mx_old,
                    const double* __restrict__ bh, int p, int Q, TrialBatch tb,
@@ -2105,7 +2004,8 @@ residual_xS_body(const double* __restrict__ xnew, const int* __restrict__ supp, 
     }
 }
 
-// y part of compute_residual! + compute_gap! per candidate; part[c][q][wg], q as in k_residual_y
+// y part of compute_residual! (residuals.jl:51-58) + compute_gap! (residuals.jl:2-35) per candidate; part[c][q][wg], q = 0: max |dPy|
+// 1: max |Py_old|  2: max |Mx - b| (eq)  3: max(Mx - h) (ineq, >= 0)  4: sum b*y_eq  5: sum h*y_in
 __device__ __forceinline__ void
 residual_y_body(const double* __restrict__ ycand, long long ystride, const double* __restrict__ yold,
                 const double* __restrict__ Mx, const double* __restrict__ Mx_old,
@@ -2158,12 +2058,13 @@ k_residual_xy_batch(const double* __restrict__ xnew, const int* __restrict__ sup
                         part + 5 * (long long)pstride, pstride, cstride, gq, sm, roww);
 }
 
-// The same batch on the GENERAL path (no support set: full-vector passes).  Mty_c = M' y_c for every candidate
-// + |Mty_c - Mty_old|^2 partials: per candidate the arithmetic of k_spmv_csc_norm (addback form).
+// The same batch on the GENERAL path (no support set: full-vector passes).  Mty_c = M' y_c for every candidate (M in CSC: one
+// dot per column, thread per column; columns are mostly empty or short) + |Mty_c - Mty_old|^2 partials (pdhg.jl:556-563)
 __global__ void __launch_bounds__(TPB)
 k_spmv_csc_norm_batch(const int* __restrict__ colptr, const int* __restrict__ row, const double* __restrict__ val,
                       const double* __restrict__ ycand, long long ystride, double* __restrict__ Mtycand, long long mstride,
-                      const double* __restrict__ Mty_old, long long ncols, double* __restrict__ part, long long cstride) {
+                      const double* __restrict__ Mty_old, long long ncols, double* __restrict__ part, long long cstride,
+                      int plain) {
     __shared__ double sm[NWAVE];
     const int c = blockIdx.y;
     const double* y = ycand + (long long)c * ystride;
@@ -2177,14 +2078,14 @@ k_spmv_csc_norm_batch(const int* __restrict__ colptr, const int* __restrict__ ro
         const double acc = col_dot(lc, (int)j, colptr, row, val, y);
         const double o = Mty_old[j];
         const double d = acc - o;
-        out[j] = d + o;                        // pdhg.jl:560,574
+        out[j] = plain ? acc : d + o;          // pdhg.jl:560,574 (plain: dual_step!'s mul!(Mty, Mt, y), pdhg.jl:606)
         ss += d * d;
     }
     const double tot = block_sum(ss, sm);
     if (threadIdx.x == 0) part[(long long)c * cstride + blockIdx.x] = tot;
 }
-// x part of compute_residual! + c.x over the whole vector, per candidate (the arithmetic of k_residual_x);
-// part[c][q][wg], q = 0: max |dPx|  1: max |Px_old|  2: sum c*x
+// x part of compute_residual! (residuals.jl:41-48) + c.x (residuals.jl:22) over the whole vector, per candidate;
+// part[c][q][wg], q = 0: max |(x - tau Mty) - (x_old - tau Mty_old)|  1: max |x_old - tau Mty_old|  2: sum c*x
 __device__ __forceinline__ void
 residual_x_full_body(const double* __restrict__ x, const double* __restrict__ xold, double xold_coef,
                      const double* __restrict__ Mtycand, long long mstride, const double* __restrict__ Mty_old,

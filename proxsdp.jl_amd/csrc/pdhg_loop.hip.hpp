@@ -542,7 +542,7 @@ inline void Solver::primal_step_dev() {
         double t0 = now_s();
         // block-sharded solve: a shard whose projection fails (e.g. non-finite input) must still join this
         // iteration's collectives, or its peers wait in them for ever: the error is kept, a flag travels with the
-        // iteration's scalar record (linesearch_residual_support), and every shard aborts after that reduce
+        // iteration's scalar record (reduce_candidates), and every shard aborts after that reduce
         if (sharded()) {
             try {
                 if (opt.debug_fail_iteration > 0 && iter == opt.debug_fail_iteration)
@@ -576,115 +576,216 @@ inline void Solver::primal_step_dev() {
     spmv(xo, Mxbuf[1 - mxc].p);
 }
 
-// linesearch! (pdhg.jl:532-582)
-inline int Solver::linesearch() {
-    primal_step = primal_step * std::sqrt(1.0 + theta);
-    const int gq = std::min(PSTRIDE, grid_for(std::max<int64_t>(P.Q, 1)));
-    const int gx = std::min(PSTRIDE, grid_for(P.n));
-    int trials = 0;
-    for (int i = 0; i < opt.max_linsearch_steps; ++i) {
-        ++trials;
-        theta = primal_step / primal_step_old;
-        const double bt = beta * primal_step;
-        hipLaunchKernelGGL(dev::k_dual_trial, dim3(gq), dim3(dev::TPB), 0, stream,
-                           ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, bt, theta,
-                           ybuf[1 - yc].p, part.p, 1);
-        hipLaunchKernelGGL(dev::k_spmv_csc_norm, dim3(gx), dim3(dev::TPB), 0, stream,
-                           csc_ptr.p, csc_row.p, csc_val.p, ybuf[1 - yc].p, Mtybuf[1 - mtyc].p, Mtybuf[mtyc].p,
-                           (long long)P.n, part.p + PSTRIDE, 1);
-        hipLaunchKernelGGL(dev::k_combine, dim3(1), dim3(dev::TPB), 0, stream,
-                           part.p, PSTRIDE, PSTRIDE, 2, 0u, scal.p);
-        // the residual / gap reductions of THIS candidate ride behind its trial (pure reductions over the candidate's
-        // y and M'y): when it is the accepted one -- the common case -- residual_and_gap finds its nine scalars in the
-        // same read-back and the iteration has one synchronisation less; a rejected candidate's are ignored
-        enqueue_residual(primal_step, beta * primal_step);
-        if (hscal_pin.p == nullptr) hscal_pin.alloc(64);
-        PX_HIP(hipMemcpyAsync(hscal_pin.p, scal.p, 11 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        wait_stream();
-        std::copy(hscal_pin.p, hscal_pin.p + 11, hscal.begin());
-        residual_ready = true;
-        const double y_norm = std::sqrt(hscal[0]), Mty_norm = std::sqrt(hscal[1]);
-        if (debug && iter <= 5 && trials <= 6)
-            std::fprintf(stderr, "[dbg] it %lld trial %d tau %.6e theta %.6e y_norm %.6e Mty_norm %.6e\n",
-                         iter, trials, primal_step, theta, y_norm, Mty_norm);
-        if (std::sqrt(beta) * primal_step * Mty_norm <= opt.delta * y_norm) break;
-        primal_step *= opt.linsearch_decay;
-        residual_ready = false;                  // (also when the loop ends on its trial limit: the reference then
-                                                 //  continues with the DECAYED step and the last candidate's y)
+// ---- linesearch! / dual_step! (pdhg.jl:532-609) + compute_residual! + compute_gap! (residuals.jl:2-71) on every vector path
+constexpr int NCAND = 3;    // candidates per batch (options.general_batch = 0: one); the scalar record always holds NCAND
+constexpr int NSCAL = 11;   // scalars per candidate: q0,q1 sums | q2,q3 max, q4 sum | q5..q8 max, q9,q10 sum
+
+// the candidates' buffers: y_c, M'y_c (on the support, or every column), their partials and the scalar record
+inline void Solver::alloc_candidates() {
+    ycand_d.alloc((size_t)NCAND * std::max<int64_t>(P.Q, 1)); ycand_d.zero(stream);
+    Mtycand_d.alloc((size_t)NCAND * (use_support ? std::max<int64_t>(ns, 1) : P.n)); Mtycand_d.zero(stream);
+    bpart.alloc((size_t)NCAND * NSCAL * PSTRIDE); bpart.zero(stream);
+    bscal.alloc(64); bscal.zero(stream);
+    hbscal.assign(64, 0.0);
+    hscal_pin.alloc(64);
+    PX_HIP(hipStreamSynchronize(stream));
+}
+
+// block-sharded solve: every shard evaluated the same candidates on its own blocks / rows: combine their scalar records
+// (always NCAND of them, whatever the batch width: the collective's message keeps one size)
+inline void Solver::reduce_candidates(int nc) {
+    if (!sharded()) return;
+    std::vector<double> sums, maxs;
+    for (int c = 0; c < NCAND; ++c) {
+        const double* sc = hbscal.data() + NSCAL * c;
+        for (int q : {0, 1, 4, 9, 10}) sums.push_back(c < nc ? sc[q] : 0.0);
+        for (int q : {2, 3, 5, 6, 7, 8}) maxs.push_back(c < nc ? sc[q] : 0.0);
     }
-    primal_step_old = primal_step;
-    dual_step = beta * primal_step;
-    st.linesearch_trials += trials;
-    return trials;
+    maxs.push_back(hbscal[NCAND * NSCAL]); maxs.push_back(hbscal[NCAND * NSCAL + 1]);
+    maxs.push_back(convergedrank() ? 0.0 : 1.0);          // any shard not rank-converged
+    bool below = false;
+    for (size_t idx = 0; idx < P.blocks.size(); ++idx) below = below || target_rank[idx] < P.blocks[idx].n;
+    maxs.push_back(below ? 1.0 : 0.0);                    // any block with target_rank < side
+    maxs.push_back(now_s() - time0);                      // one clock for the limits
+    maxs.push_back(shard_error ? 1.0 : 0.0);              // a shard failed in this iteration's projection
+    if (shard_error)                                      // (its own partials may be garbage: keep them finite)
+        for (double& v : sums) if (!(v == v)) v = 0.0;
+    reduce(sums, maxs);
+    if (maxs.back() > 0.5) {
+        if (shard_error) { std::exception_ptr e = shard_error; shard_error = nullptr; std::rethrow_exception(e); }
+        throw std::runtime_error("another shard of the block-sharded solve failed in this iteration");
+    }
+    size_t si = 0, mi = 0;
+    for (int c = 0; c < NCAND; ++c) {
+        double* sc = hbscal.data() + NSCAL * c;
+        for (int q : {0, 1, 4, 9, 10}) sc[q] = sums[si++];
+        for (int q : {2, 3, 5, 6, 7, 8}) sc[q] = maxs[mi++];
+    }
+    hbscal[NCAND * NSCAL] = maxs[mi++]; hbscal[NCAND * NSCAL + 1] = maxs[mi++];
+    g_not_converged_rank = maxs[mi++] > 0.5;
+    g_any_below_full = maxs[mi++] > 0.5;
+    g_elapsed = maxs[mi++];
 }
 
-// dual_step! (pdhg.jl:584-609): the same kernels with theta = 1, bt = dual_step
-inline void Solver::dual_step_plain() {
+// Up to NCAND consecutive step-size candidates tau, 0.75 tau, 0.75^2 tau are evaluated by ONE batch of launches -- y+, M'y+ and
+// their norms, then the residual / gap reductions, pure reductions over each candidate's y and M'y -- and ONE read-back; the host
+// takes the first candidate the reference's loop would have accepted.  Per candidate the arithmetic is that of a batch of one, so
+// the batch width changes no bit.  line_search_flag = false: ONE plain candidate, dual_step! (pdhg.jl:584-609) -- y+ = y +
+// sigma (2 Mx - Mx_old) with the solver's own dual_step, taken as it is; primal_step, dual_step and theta are left alone.
+// Returns the accepted candidate's scalar record.
+inline const double* Solver::linesearch_and_residuals() {
+    const int ncmax = opt.general_batch != 0 ? NCAND : 1;
     const int gq = std::min(PSTRIDE, grid_for(std::max<int64_t>(P.Q, 1)));
-    const int gx = std::min(PSTRIDE, grid_for(P.n));
-    hipLaunchKernelGGL(dev::k_dual_trial, dim3(gq), dim3(dev::TPB), 0, stream,
-                       ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, dual_step, 1.0,
-                       ybuf[1 - yc].p, part.p, 0);
-    if (P.dense())
-        dense_mtv(1, ybuf[1 - yc].p, 0, true, Mtybuf[1 - mtyc].p, 0, Mtybuf[mtyc].p, nullptr, part.p + PSTRIDE, 0, false);
-    else
-    hipLaunchKernelGGL(dev::k_spmv_csc_norm, dim3(gx), dim3(dev::TPB), 0, stream,
-                       csc_ptr.p, csc_row.p, csc_val.p, ybuf[1 - yc].p, Mtybuf[1 - mtyc].p, Mtybuf[mtyc].p,
-                       (long long)P.n, part.p + PSTRIDE, 0);
-    primal_step_old = primal_step;
-    st.linesearch_trials += 1;
-}
-
-// compute_residual! + compute_gap! (residuals.jl:2-71), then the *_old rotation
-// (:65-68) as index flips instead of four vector copies
-inline void Solver::enqueue_residual(double pstep, double dstep) {
-    const int gq = std::min(PSTRIDE, grid_for(std::max<int64_t>(P.Q, 1)));
-    const int gx = std::min(PSTRIDE, grid_for(P.n));
+    const int gx = std::min(PSTRIDE, grid_for(use_support ? std::max<int64_t>(ns, 1) : P.n));   // the support, or every column
+    const long long cstride = (long long)NSCAL * PSTRIDE;
+    const long long ystride = std::max<int64_t>(P.Q, 1), mstride = use_support ? std::max<int64_t>(ns, 1) : P.n;
     const double xold_coef = (iter == 1 && opt.advanced_initialization) ? 0.0 : 1.0;   // x_old = 0 at k = 1
-    hipLaunchKernelGGL(dev::k_residual_x, dim3(gx), dim3(dev::TPB), 0, stream,
-                       xbuf[1 - xc].p, xbuf[xc].p, xold_coef, Mtybuf[1 - mtyc].p, Mtybuf[mtyc].p, c_d.p,
-                       pstep, (long long)P.n, part.p + 2 * PSTRIDE);
-    // k_residual_x writes 3 quantities with stride gridDim; re-stride into the common layout
-    // by launching with exactly PSTRIDE-strided output: handled by passing gridDim == gx and
-    // combining with stride gx (see k_combine call below).
-    hipLaunchKernelGGL(dev::k_residual_y, dim3(gq), dim3(dev::TPB), 0, stream,
-                       ybuf[1 - yc].p, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q,
-                       dstep, part.p + 5 * PSTRIDE);
-    hipLaunchKernelGGL(dev::k_combine, dim3(1), dim3(dev::TPB), 0, stream,
-                       part.p + 2 * PSTRIDE, gx, gx, 3, 0x3u, scal.p + 2);
-    hipLaunchKernelGGL(dev::k_combine, dim3(1), dim3(dev::TPB), 0, stream,
-                       part.p + 5 * PSTRIDE, gq, gq, 6, 0xFu, scal.p + 5);
+    double* mty_cur = use_support ? MtyS_cur.p : Mtybuf[mtyc].p;
+    const double* roww = roww_d.p;
+    auto residuals = [&](const dev::TrialBatch& tb, int nc, int c0) {        // candidates c0 .. c0 + nc - 1
+        const double* yc0 = ycand_d.p + (size_t)c0 * ystride;
+        const double* mc0 = Mtycand_d.p + (size_t)c0 * mstride;
+        if (use_support)
+            hipLaunchKernelGGL(dev::k_residual_xy_batch, dim3(std::max(gx, gq), nc, 2), dim3(dev::TPB), 0, stream,
+                               xbuf[1 - xc].p, supp_d.p, ns, xsave_d.p, xold_coef, mc0, mstride, mty_cur, cS_d.p, gx,
+                               yc0, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, gq,
+                               tb, bpart.p, PSTRIDE, cstride, roww);
+        else
+            hipLaunchKernelGGL(dev::k_residual_xy_full_batch, dim3(std::max(gx, gq), nc, 2), dim3(dev::TPB), 0, stream,
+                               xbuf[1 - xc].p, xbuf[xc].p, xold_coef, mc0, mstride, mty_cur, c_d.p, (long long)P.n, gx,
+                               yc0, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, gq,
+                               tb, bpart.p, PSTRIDE, cstride);
+    };
+    // (the vector paths differ only in the launches that compute M'y+ and the residuals)
+    auto evaluate = [&](const dev::TrialBatch& tb, int nc) {
+        hipLaunchKernelGGL(dev::k_dual_trial_batch, dim3(gq, nc), dim3(dev::TPB), 0, stream,
+                           ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, tb,
+                           ycand_d.p, ystride, bpart.p, cstride, roww);
+        if (use_support)
+            hipLaunchKernelGGL(dev::k_spmvT_S_batch, dim3(gx, nc), dim3(dev::TPB), 0, stream,
+                               csc_ptr.p, csc_row.p, csc_val.p, supp_d.p, ns, ycand_d.p, ystride,
+                               Mtycand_d.p, mstride, mty_cur, bpart.p + PSTRIDE, cstride, tb.plain);
+        else if (P.dense())
+            dense_mtv(nc, ycand_d.p, ystride, true, Mtycand_d.p, mstride, mty_cur, nullptr, bpart.p + PSTRIDE, cstride, !tb.plain);
+        else
+            hipLaunchKernelGGL(dev::k_spmv_csc_norm_batch, dim3(gx, nc), dim3(dev::TPB), 0, stream,
+                               csc_ptr.p, csc_row.p, csc_val.p, ycand_d.p, ystride, Mtycand_d.p, mstride, mty_cur,
+                               (long long)P.n, bpart.p + PSTRIDE, cstride, tb.plain);
+        residuals(tb, nc, 0);
+    };
+    // the scalar record: NSCAL per candidate, then (support path) the two off-support residual maxima that the fused
+    // reconstruction reduced -- independent of the candidate, combined by two extra workgroups
+    const double* rec = use_support ? hbscal.data() : hscal_pin.p;
+    auto read_back = [&](int nc) {
+        unsigned long long ismax = 0;
+        for (int c = 0; c < nc; ++c) ismax |= 0x1ECull << (NSCAL * c);      // bits 2,3,5,6,7,8 of every candidate
+        if (use_support) {
+            // (measured, tools/_ab in round 5: letting this kernel write its scalars straight into pinned host memory -- as the
+            // small-model path does -- costs the rank-63 iteration 3 %: a kernel that stores to host memory ends with a system-scope
+            // release, and behind the reconstruction that means writing 64 MB of dirty L2 lines back first)
+            hipLaunchKernelGGL(dev::k_combine_multi, dim3(nc * NSCAL + 2), dim3(dev::TPB), 0, stream,
+                               (const double*)bpart.p, PSTRIDE, std::max(gq, gx), ismax, bscal.p, nc * NSCAL,
+                               (const double*)respart_d.p, rstride, n_res_wg, bscal.p + NCAND * NSCAL);
+            PX_HIP(hipMemcpyAsync(hbscal.data(), bscal.p, (NCAND * NSCAL + 2) * sizeof(double), hipMemcpyDeviceToHost, stream));
+            wait_stream();
+            reduce_candidates(nc);
+            return;
+        }
+        // small models: the scalars go STRAIGHT into pinned host memory (no copy launch: 6 us of a 60 us iteration); larger ones keep
+        // the copy (a kernel that stores to host memory ends with a system-scope release of everything the iteration left dirty)
+        const bool zc = zero_copy_small();
+        hipLaunchKernelGGL(dev::k_combine_multi, dim3(nc * NSCAL), dim3(dev::TPB), 0, stream,
+                           (const double*)bpart.p, PSTRIDE, std::max(gq, gx), ismax, zc ? hscal_pin.p : bscal.p, nc * NSCAL,
+                           (const double*)nullptr, 0, 0, (double*)nullptr);
+        if (!zc) PX_HIP(hipMemcpyAsync(hscal_pin.p, bscal.p, NCAND * NSCAL * sizeof(double), hipMemcpyDeviceToHost, stream));
+        wait_stream();
+    };
+    auto commit = [&](int c) {                           // y <- y_c, M'y <- M'y_c (one launch)
+        const long long nm = use_support ? ns : P.n;
+        hipLaunchKernelGGL(dev::k_copy2, dim3(grid_for((long long)P.Q + nm)), dim3(dev::TPB), 0, stream,
+                           ybuf[1 - yc].p, (const double*)(ycand_d.p + (size_t)c * ystride), (long long)P.Q,
+                           use_support ? MtyS_cur.p : Mtybuf[1 - mtyc].p, (const double*)(Mtycand_d.p + (size_t)c * mstride), nm);
+    };
+    const bool ls = opt.line_search_flag;
+    if (ls) primal_step = primal_step * std::sqrt(1.0 + theta);
+    int trials = 0;
+    const double* s_acc = nullptr;
+    while (s_acc == nullptr) {
+        dev::TrialBatch tb{};
+        double tau_c = primal_step;
+        int nc = 0;
+        for (; ls && nc < ncmax && trials + nc < opt.max_linsearch_steps; ++nc) {
+            tb.tau[nc] = tau_c;
+            tb.theta[nc] = tau_c / primal_step_old;
+            tb.bt[nc] = beta * tau_c;
+            tb.sigma[nc] = beta * tau_c;
+            tau_c *= opt.linsearch_decay;
+        }
+        if (!ls) { nc = 1; tb.tau[0] = primal_step; tb.theta[0] = 1.0; tb.bt[0] = dual_step; tb.sigma[0] = dual_step; tb.plain = 1; }
+        tb.nc = nc;
+        evaluate(tb, nc);
+        read_back(nc);
+        for (int c = 0; c < nc && s_acc == nullptr; ++c) {
+            ++trials;
+            const double* sc = rec + NSCAL * c;
+            if (ls) {
+                primal_step = tb.tau[c];
+                theta = tb.theta[c];
+                const double y_norm = std::sqrt(sc[0]), Mty_norm = std::sqrt(sc[1]);
+                if (debug && iter <= 5 && trials <= 6)
+                    std::fprintf(stderr, "[dbg] it %lld trial %d tau %.6e theta %.6e y_norm %.6e Mty_norm %.6e\n",
+                                 iter, trials, primal_step, theta, y_norm, Mty_norm);
+                const bool ok = std::sqrt(beta) * primal_step * Mty_norm <= opt.delta * y_norm;
+                if (!ok && trials < opt.max_linsearch_steps) { primal_step = tb.tau[c] * opt.linsearch_decay; continue; }
+                if (!ok) {
+                    // reference quirk (pdhg.jl:545-569): max_linsearch_steps exhausted -> the step is decayed once more while
+                    // the last trial's y / M'y are kept, and compute_residual! / compute_gap! then run with THAT primal_step and
+                    // dual_step: candidate c's residual scalars are evaluated again with the final steps (rare: one more batch)
+                    primal_step *= opt.linsearch_decay;
+                    dev::TrialBatch t1{};
+                    t1.nc = 1; t1.tau[0] = primal_step; t1.theta[0] = theta; t1.bt[0] = beta * primal_step;
+                    t1.sigma[0] = beta * primal_step;
+                    residuals(t1, 1, c);
+                    read_back(1);
+                    sc = rec;                            // (its two norms, slots 0 and 1, are not read any more)
+                }
+            }
+            s_acc = sc;
+            commit(c);
+        }
+    }
+    primal_step_old = primal_step;
+    if (ls) dual_step = beta * primal_step;
+    st.linesearch_trials += trials;
+    last_trials = trials;
+    return s_acc;
 }
 
-inline void Solver::residual_and_gap() {
-    if (!residual_ready) {
-        enqueue_residual(primal_step, dual_step);
-        if (hscal_pin.p == nullptr) hscal_pin.alloc(64);
-        PX_HIP(hipMemcpyAsync(hscal_pin.p + 2, scal.p + 2, 9 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        wait_stream();
-        std::copy(hscal_pin.p + 2, hscal_pin.p + 11, hscal.begin() + 2);
-    }
-    residual_ready = false;
-    const double* s = hscal.data() + 2;
+// compute_residual! + compute_gap! (residuals.jl:2-71) from the accepted candidate's scalar record, then the *_old rotation
+// (:65-68) as index flips instead of four vector copies
+inline void Solver::record_residuals(const double* s) {
     if (debug && iter <= 5)
         std::fprintf(stderr, "[dbg] it %lld res: %.6e %.6e cx %.6e | %.6e %.6e eq %.6e in %.6e by %.6e hy %.6e\n",
-                     iter, s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8]);
-    const double pres = std::sqrt(g_n) * s[0] / std::max({s[1], g_norm_b, g_norm_h, 1.0});
-    const double dres = std::sqrt(g_Q) * s[3] / std::max({s[4], g_norm_c, 1.0});
+                     iter, s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10]);
+    const double m0 = use_support ? std::max(s[2], hbscal[NCAND * NSCAL]) : s[2];          // (+ the off-support maxima)
+    const double m1 = use_support ? std::max(s[3], hbscal[NCAND * NSCAL + 1]) : s[3];
+    const double pres = std::sqrt(g_n) * m0 / std::max({m1, g_norm_b, g_norm_h, 1.0});
+    const double dres = std::sqrt(g_Q) * s[5] / std::max({s[6], g_norm_c, 1.0});
     h_pres.at(iter) = pres;
     h_dres.at(iter) = dres;
     h_comb.at(iter) = std::max(pres, dres);
-    if (P.p > 0) equa_feasibility = s[5] / (1.0 + g_norm_b);
-    if (P.m > 0) ineq_feasibility = s[6] / (1.0 + g_norm_h);
+    if (g_p > 0) equa_feasibility = s[7] / (1.0 + g_norm_b);
+    if (g_m > 0) ineq_feasibility = s[8] / (1.0 + g_norm_h);
     h_feas.at(iter) = std::max(equa_feasibility, ineq_feasibility);
-    const double po = s[2];
+    const double po = s[4];
     double d_o = 0.0;
-    if (P.p > 0) d_o -= s[7];
-    if (P.m > 0) d_o -= s[8];
+    if (g_p > 0) d_o -= s[9];
+    if (g_m > 0) d_o -= s[10];
     h_pobj.at(iter) = po;
     h_dobj.at(iter) = d_o;
     h_gap.at(iter) = std::fabs(po - d_o) / (1.0 + std::fabs(po) + std::fabs(d_o));
-    xc = 1 - xc; mtyc = 1 - mtyc; yc = 1 - yc; mxc = 1 - mxc;
+    xc = 1 - xc; yc = 1 - yc; mxc = 1 - mxc;
+    if (!use_support) mtyc = 1 - mtyc;                   // (the support path keeps M'y on S in one buffer, updated by commit)
 }
 
 // convergedrank (residuals.jl:88-101)
@@ -922,11 +1023,6 @@ inline void Solver::setup_dense() {
     dmv_slices = (int)std::min<long long>(dmv_slices, std::max<long long>(chunks, 1));
     dmv_qpad = (int)std::max<int64_t>(P.p, 1);
     dmv_part.alloc((size_t)dmv_slices * dmv_qpad);
-    Mtycand_d.alloc((size_t)3 * P.n);
-    ycand_d.alloc((size_t)4 * std::max<int64_t>(P.Q, 1));
-    bpart.alloc((size_t)4 * 2 * PSTRIDE); bpart.zero(stream);
-    bscal.alloc(64); bscal.zero(stream);
-    hbscal.assign(64, 0.0);
     // ||M||_F of the column-scaled matrix (pdhg.jl:121 after norm_scaling)
     const int gx = std::min(PSTRIDE, grid_for(P.n));
     hipLaunchKernelGGL(dev::k_dense_frob, dim3(gx), dim3(dev::TPB), 0, stream,
@@ -999,66 +1095,7 @@ inline void Solver::dense_mtv(int nc, const double* Y, long long ystride, bool s
     st.dense_passes += 1;
 }
 
-// linesearch! (pdhg.jl:532-582) with a dense M: the candidates tau, 3/4 tau, (3/4)^2 tau are
-// evaluated by ONE pass over M (8 Q n bytes) and one synchronisation; the host takes the first
-// candidate the reference's loop would have accepted.
-inline int Solver::linesearch_dense() {
-    constexpr int NC = 3;
-    const int gq = std::min(PSTRIDE, grid_for(std::max<int64_t>(P.Q, 1)));
-    const int gx = std::min(PSTRIDE, grid_for(P.n));
-    const long long cstride = 2LL * PSTRIDE;
-    const long long ystride = std::max<int64_t>(P.Q, 1);
-    primal_step = primal_step * std::sqrt(1.0 + theta);
-    int trials = 0;
-    bool accepted = false;
-    while (!accepted && trials < opt.max_linsearch_steps) {
-        dev::TrialBatch tb{};
-        double tau_c = primal_step;
-        int nc = 0;
-        for (; nc < NC && trials + nc < opt.max_linsearch_steps; ++nc) {
-            tb.tau[nc] = tau_c;
-            tb.theta[nc] = tau_c / primal_step_old;
-            tb.bt[nc] = beta * tau_c;
-            tb.sigma[nc] = beta * tau_c;
-            tau_c *= opt.linsearch_decay;
-        }
-        tb.nc = nc;
-        hipLaunchKernelGGL(dev::k_dual_trial_batch, dim3(gq, nc), dim3(dev::TPB), 0, stream,
-                           ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, tb,
-                           ycand_d.p, ystride, bpart.p, cstride);
-        dense_mtv(nc, ycand_d.p, ystride, true, Mtycand_d.p, (long long)P.n, Mtybuf[mtyc].p, nullptr,
-                  bpart.p + PSTRIDE, cstride, true);
-        hipLaunchKernelGGL(dev::k_combine_multi, dim3(nc * 2), dim3(dev::TPB), 0, stream,
-                           (const double*)bpart.p, PSTRIDE, std::max(gq, gx), 0ull, bscal.p, nc * 2,
-                           (const double*)nullptr, 0, 0, (double*)nullptr);
-        PX_HIP(hipMemcpyAsync(hbscal.data(), bscal.p, NC * 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        PX_HIP(hipStreamSynchronize(stream));
-        for (int c = 0; c < nc; ++c) {
-            ++trials;
-            primal_step = tb.tau[c];
-            theta = tb.theta[c];
-            const double y_norm = std::sqrt(hbscal[2 * c]), Mty_norm = std::sqrt(hbscal[2 * c + 1]);
-            const bool ok = std::sqrt(beta) * primal_step * Mty_norm <= opt.delta * y_norm;
-            const bool last = trials >= opt.max_linsearch_steps;
-            if (ok || last) {
-                if (!ok) primal_step *= opt.linsearch_decay;     // reference quirk: decayed once more, trial kept
-                accepted = true;
-                PX_HIP(hipMemcpyAsync(ybuf[1 - yc].p, ycand_d.p + (size_t)c * ystride, (size_t)P.Q * 8,
-                                      hipMemcpyDeviceToDevice, stream));
-                PX_HIP(hipMemcpyAsync(Mtybuf[1 - mtyc].p, Mtycand_d.p + (size_t)c * P.n, (size_t)P.n * 8,
-                                      hipMemcpyDeviceToDevice, stream));
-                break;
-            }
-            primal_step = tb.tau[c] * opt.linsearch_decay;
-        }
-    }
-    primal_step_old = primal_step;
-    dual_step = beta * primal_step;
-    st.linesearch_trials += trials;
-    return trials;
-}
-
-// ---- support-aware path: setup and the batched linesearch + residual
+// ---- support-aware path
 inline void Solver::setup_support() {
     use_support = false;
     // (without linesearch the support path runs on request -- support_path = 1 -- and inside a block-sharded solve, which is built on it)
@@ -1073,11 +1110,10 @@ inline void Solver::setup_support() {
     std::vector<double> cS(std::max(ns, 1), 0.0);
     for (int s = 0; s < ns; ++s) { mask[supp[s] >> 5] |= 1u << (supp[s] & 31); cS[s] = P.c[supp[s]]; }
     supp_d.alloc(std::max(ns, 1)); mask_d.alloc(mask.size()); cS_d.alloc(std::max(ns, 1));
-    xsave_d.alloc(std::max(ns, 1)); MtyS_cur.alloc(std::max(ns, 1)); MtyS_cand.alloc((size_t)4 * std::max(ns, 1));
-    ycand_d.alloc((size_t)4 * std::max<int64_t>(P.Q, 1));
+    xsave_d.alloc(std::max(ns, 1)); MtyS_cur.alloc(std::max(ns, 1));
     supp_d.upload(supp.data(), ns, stream); mask_d.upload(mask.data(), mask.size(), stream);
     cS_d.upload(cS.data(), ns, stream);
-    MtyS_cur.zero(stream); MtyS_cand.zero(stream); xsave_d.zero(stream); ycand_d.zero(stream);
+    MtyS_cur.zero(stream); xsave_d.zero(stream);
     // residual partial slots: one per reconstruction tile of every block + the tail workgroups
     tile_base.clear();
     int base = 0;
@@ -1091,9 +1127,6 @@ inline void Solver::setup_support() {
     n_res_wg = base;
     rstride = base;
     respart_d.alloc((size_t)2 * std::max(base, 1)); respart_d.zero(stream);
-    bpart.alloc((size_t)4 * 11 * PSTRIDE); bpart.zero(stream);
-    bscal.alloc(64); bscal.zero(stream);
-    hbscal.assign(64, 0.0);
     // operator-form mat-vec: the support update as a symmetric sparse matrix per block (ELL)
     esv_d.alloc((size_t)2 * std::max(ns, 1)); esv_d.zero(stream);
     if (opt.lanczos_operator != 0) {
@@ -1172,298 +1205,6 @@ inline void Solver::setup_support() {
     }
     PX_HIP(hipStreamSynchronize(stream));
     use_support = true;
-}
-
-// linesearch! (pdhg.jl:532-582) + compute_residual! + compute_gap! (residuals.jl) on the
-// support path: up to 3 consecutive step-size candidates tau, 0.75 tau, 0.75^2 tau are
-// evaluated by one batch of small kernels (the dense terms were produced by the fused
-// reconstruction), the host reads all scalars with ONE synchronisation and takes the first
-// candidate the reference's loop would have accepted.
-inline int Solver::linesearch_residual_support() {
-    constexpr int NC = 3;
-    const int gq = std::min(PSTRIDE, grid_for(std::max<int64_t>(P.Q, 1)));
-    const int gs = std::min(PSTRIDE, grid_for(std::max(ns, 1)));
-    const long long cstride = 11LL * PSTRIDE;
-    const long long ystride = std::max<int64_t>(P.Q, 1), mstride = std::max(ns, 1);
-    const double xold_coef = (iter == 1 && opt.advanced_initialization) ? 0.0 : 1.0;
-    // line_search_flag = false (round 6; the sharded loop needs this path): ONE candidate, dual_step! (pdhg.jl:584-609) -- y+ = y +
-    // sigma (2 Mx - Mx_old) with the solver's own dual_step, accepted as it is; primal_step, dual_step and theta are left alone
-    const bool ls = opt.line_search_flag;
-    if (ls) primal_step = primal_step * std::sqrt(1.0 + theta);
-    int trials = 0;
-    bool accepted = false;
-    const double* s_acc = nullptr;
-    // (the off-support residual maxima of this iteration, independent of the candidate, are
-    // reduced by the two extra workgroups of the batch's final combine)
-    // block-sharded solve: every shard evaluated the same candidates on its own blocks/rows: combine
-    auto reduce_candidates = [&](int nc) {
-        if (!sharded()) return;
-        std::vector<double> sums, maxs;
-        for (int c = 0; c < NC; ++c) {
-            const double* sc = hbscal.data() + 11 * c;
-            for (int q : {0, 1, 4, 9, 10}) sums.push_back(c < nc ? sc[q] : 0.0);
-            for (int q : {2, 3, 5, 6, 7, 8}) maxs.push_back(c < nc ? sc[q] : 0.0);
-        }
-        maxs.push_back(hbscal[NC * 11]); maxs.push_back(hbscal[NC * 11 + 1]);
-        maxs.push_back(convergedrank() ? 0.0 : 1.0);          // any shard not rank-converged
-        bool below = false;
-        for (size_t idx = 0; idx < P.blocks.size(); ++idx) below = below || target_rank[idx] < P.blocks[idx].n;
-        maxs.push_back(below ? 1.0 : 0.0);                    // any block with target_rank < side
-        maxs.push_back(now_s() - time0);                      // one clock for the limits
-        maxs.push_back(shard_error ? 1.0 : 0.0);              // a shard failed in this iteration's projection
-        if (shard_error)                                      // (its own partials may be garbage: keep them finite)
-            for (double& v : sums) if (!(v == v)) v = 0.0;
-        reduce(sums, maxs);
-        if (maxs.back() > 0.5) {
-            if (shard_error) { std::exception_ptr e = shard_error; shard_error = nullptr; std::rethrow_exception(e); }
-            throw std::runtime_error("another shard of the block-sharded solve failed in this iteration");
-        }
-        size_t si = 0, mi = 0;
-        for (int c = 0; c < NC; ++c) {
-            double* sc = hbscal.data() + 11 * c;
-            for (int q : {0, 1, 4, 9, 10}) sc[q] = sums[si++];
-            for (int q : {2, 3, 5, 6, 7, 8}) sc[q] = maxs[mi++];
-        }
-        hbscal[NC * 11] = maxs[mi++]; hbscal[NC * 11 + 1] = maxs[mi++];
-        g_not_converged_rank = maxs[mi++] > 0.5;
-        g_any_below_full = maxs[mi++] > 0.5;
-        g_elapsed = maxs[mi++];
-    };
-    while (!accepted && (!ls || trials < opt.max_linsearch_steps)) {
-        dev::TrialBatch tb{};
-        double tau_c = primal_step;
-        int nc = 0;
-        for (; ls && nc < NC && trials + nc < opt.max_linsearch_steps; ++nc) {
-            tb.tau[nc] = tau_c;
-            tb.theta[nc] = tau_c / primal_step_old;
-            tb.bt[nc] = beta * tau_c;
-            tb.sigma[nc] = beta * tau_c;
-            tau_c *= opt.linsearch_decay;
-        }
-        if (!ls) { nc = 1; tb.tau[0] = primal_step; tb.theta[0] = 1.0; tb.bt[0] = dual_step; tb.sigma[0] = dual_step; tb.plain = 1; }
-        tb.nc = nc;
-        hipLaunchKernelGGL(dev::k_dual_trial_batch, dim3(gq, nc), dim3(dev::TPB), 0, stream,
-                           ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, tb,
-                           ycand_d.p, ystride, bpart.p, cstride, (const double*)roww_d.p);
-        hipLaunchKernelGGL(dev::k_spmvT_S_batch, dim3(gs, nc), dim3(dev::TPB), 0, stream,
-                           csc_ptr.p, csc_row.p, csc_val.p, supp_d.p, ns, ycand_d.p, ystride,
-                           MtyS_cand.p, mstride, MtyS_cur.p, bpart.p + PSTRIDE, cstride, tb.plain);
-        hipLaunchKernelGGL(dev::k_residual_xy_batch, dim3(std::max(gs, gq), nc, 2), dim3(dev::TPB), 0, stream,
-                           xbuf[1 - xc].p, supp_d.p, ns, xsave_d.p, xold_coef, MtyS_cand.p, mstride, MtyS_cur.p,
-                           cS_d.p, gs,
-                           ycand_d.p, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, gq,
-                           tb, bpart.p, PSTRIDE, cstride, (const double*)roww_d.p);
-        // per candidate: q0,q1 sums | q2,q3 max, q4 sum | q5..q8 max, q9,q10 sum
-        unsigned long long ismax = 0;
-        for (int c = 0; c < nc; ++c) ismax |= 0x1ECull << (11 * c);      // bits 2,3,5,6,7,8
-        // (measured, tools/_ab in round 5: letting this kernel write its scalars straight into pinned host memory -- as the small-model
-        // path does -- costs the rank-63 iteration 3 %: a kernel that stores to host memory ends with a system-scope release, and
-        // behind the reconstruction that means writing 64 MB of dirty L2 lines back first)
-        hipLaunchKernelGGL(dev::k_combine_multi, dim3(nc * 11 + 2), dim3(dev::TPB), 0, stream,
-                           (const double*)bpart.p, PSTRIDE, std::max(gq, gs), ismax, bscal.p, nc * 11,
-                           (const double*)respart_d.p, rstride, n_res_wg, bscal.p + NC * 11);
-        PX_HIP(hipMemcpyAsync(hbscal.data(), bscal.p, (NC * 11 + 2) * sizeof(double), hipMemcpyDeviceToHost, stream));
-        wait_stream();
-        reduce_candidates(nc);
-        if (!ls) {
-            trials = 1; accepted = true; s_acc = hbscal.data();
-            hipLaunchKernelGGL(dev::k_copy2, dim3(grid_for((long long)P.Q + ns)), dim3(dev::TPB), 0, stream,
-                               ybuf[1 - yc].p, (const double*)ycand_d.p, (long long)P.Q,
-                               MtyS_cur.p, (const double*)MtyS_cand.p, (long long)ns);
-            break;
-        }
-        for (int c = 0; c < nc; ++c) {
-            ++trials;
-            const double* sc = hbscal.data() + 11 * c;
-            primal_step = tb.tau[c];
-            theta = tb.theta[c];
-            const double y_norm = std::sqrt(sc[0]), Mty_norm = std::sqrt(sc[1]);
-            const bool ok = std::sqrt(beta) * primal_step * Mty_norm <= opt.delta * y_norm;
-            const bool last = trials >= opt.max_linsearch_steps;
-            if (ok || last) {
-                accepted = true;
-                s_acc = sc;
-                if (!ok) {
-                    // reference quirk (pdhg.jl:545-569): max_linsearch_steps exhausted -> the step is
-                    // decayed once more while the last trial's y / Mty are kept, and compute_residual!
-                    // / compute_gap! then run with THAT primal_step and dual_step.  Re-evaluate the
-                    // residual scalars of candidate c with the final steps (rare path: one more batch).
-                    primal_step *= opt.linsearch_decay;
-                    dev::TrialBatch t1{};
-                    t1.nc = 1; t1.tau[0] = primal_step; t1.theta[0] = theta; t1.bt[0] = beta * primal_step;
-                    t1.sigma[0] = beta * primal_step;
-                    hipLaunchKernelGGL(dev::k_residual_xy_batch, dim3(std::max(gs, gq), 1, 2), dim3(dev::TPB), 0, stream,
-                                       xbuf[1 - xc].p, supp_d.p, ns, xsave_d.p, xold_coef,
-                                       MtyS_cand.p + (size_t)c * mstride, mstride, MtyS_cur.p, cS_d.p, gs,
-                                       ycand_d.p + (size_t)c * ystride, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p,
-                                       bh_d.p, (int)P.p, (int)P.Q, gq, t1, bpart.p, PSTRIDE, cstride, (const double*)roww_d.p);
-                    hipLaunchKernelGGL(dev::k_combine_multi, dim3(11 + 2), dim3(dev::TPB), 0, stream,
-                                       (const double*)bpart.p, PSTRIDE, std::max(gq, gs), 0x1ECull, bscal.p, 11,
-                                       (const double*)respart_d.p, rstride, n_res_wg, bscal.p + NC * 11);
-                    PX_HIP(hipMemcpyAsync(hbscal.data(), bscal.p, (NC * 11 + 2) * sizeof(double), hipMemcpyDeviceToHost, stream));
-                    PX_HIP(hipStreamSynchronize(stream));
-                    reduce_candidates(1);
-                    s_acc = hbscal.data();
-                }
-                // y <- y_c, Mty <- Mty_c  (one launch)
-                hipLaunchKernelGGL(dev::k_copy2, dim3(grid_for((long long)P.Q + ns)), dim3(dev::TPB), 0, stream,
-                                   ybuf[1 - yc].p, (const double*)(ycand_d.p + (size_t)c * ystride), (long long)P.Q,
-                                   MtyS_cur.p, (const double*)(MtyS_cand.p + (size_t)c * mstride), (long long)ns);
-                break;
-            }
-            primal_step = tb.tau[c] * opt.linsearch_decay;
-        }
-    }
-    primal_step_old = primal_step;
-    if (ls) dual_step = beta * primal_step;
-    st.linesearch_trials += trials;
-    // ---- residuals and gap from the accepted candidate's scalars
-    const double tr0 = now_s();
-    const double m0 = std::max(s_acc[2], hbscal[NC * 11]);
-    const double m1 = std::max(s_acc[3], hbscal[NC * 11 + 1]);
-    const double pres = std::sqrt(g_n) * m0 / std::max({m1, g_norm_b, g_norm_h, 1.0});
-    const double dres = std::sqrt(g_Q) * s_acc[5] / std::max({s_acc[6], g_norm_c, 1.0});
-    h_pres.at(iter) = pres;
-    h_dres.at(iter) = dres;
-    h_comb.at(iter) = std::max(pres, dres);
-    if (g_p > 0) equa_feasibility = s_acc[7] / (1.0 + g_norm_b);
-    if (g_m > 0) ineq_feasibility = s_acc[8] / (1.0 + g_norm_h);
-    h_feas.at(iter) = std::max(equa_feasibility, ineq_feasibility);
-    const double po = s_acc[4];
-    double d_o = 0.0;
-    if (g_p > 0) d_o -= s_acc[9];
-    if (g_m > 0) d_o -= s_acc[10];
-    h_pobj.at(iter) = po;
-    h_dobj.at(iter) = d_o;
-    h_gap.at(iter) = std::fabs(po - d_o) / (1.0 + std::fabs(po) + std::fabs(d_o));
-    xc = 1 - xc; yc = 1 - yc; mxc = 1 - mxc;
-    last_resid_s = now_s() - tr0;
-    return trials;
-}
-
-// linesearch! + compute_residual! + compute_gap! on the GENERAL path (no support set, sparse M): the structure of
-// linesearch_residual_support with full-vector kernels -- up to 3 consecutive candidates per batch, ONE read-back,
-// the first candidate the reference's loop would have accepted wins.  Per candidate the arithmetic is that of
-// linesearch() / residual_and_gap() (same kernels' bodies, same partial layout and combine order): identical scalars.
-inline int Solver::linesearch_residual_general() {
-    constexpr int NC = 3;
-    const int gq = std::min(PSTRIDE, grid_for(std::max<int64_t>(P.Q, 1)));
-    const int gx = std::min(PSTRIDE, grid_for(P.n));
-    const long long cstride = 11LL * PSTRIDE;
-    const long long ystride = std::max<int64_t>(P.Q, 1), mstride = P.n;
-    const double xold_coef = (iter == 1 && opt.advanced_initialization) ? 0.0 : 1.0;
-    if (Mtycand_d.n < (size_t)NC * P.n) {
-        Mtycand_d.alloc((size_t)NC * P.n);
-        ycand_d.alloc((size_t)4 * std::max<int64_t>(P.Q, 1));
-        bpart.alloc((size_t)4 * 11 * PSTRIDE); bpart.zero(stream);
-        bscal.alloc(64); bscal.zero(stream);
-        hbscal.assign(64, 0.0);
-        if (hscal_pin.p == nullptr) hscal_pin.alloc(64);
-    }
-    primal_step = primal_step * std::sqrt(1.0 + theta);
-    int trials = 0;
-    bool accepted = false;
-    const double* s_acc = nullptr;
-    auto residual_batch = [&](const dev::TrialBatch& tb, int nc, int c0) {
-        hipLaunchKernelGGL(dev::k_residual_xy_full_batch, dim3(std::max(gx, gq), nc, 2), dim3(dev::TPB), 0, stream,
-                           xbuf[1 - xc].p, xbuf[xc].p, xold_coef, Mtycand_d.p + (size_t)c0 * mstride, mstride, Mtybuf[mtyc].p,
-                           c_d.p, (long long)P.n, gx,
-                           ycand_d.p + (size_t)c0 * ystride, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p,
-                           bh_d.p, (int)P.p, (int)P.Q, gq, tb, bpart.p, PSTRIDE, cstride);
-    };
-    auto read_back = [&](int nc) {
-        unsigned long long ismax = 0;
-        for (int c = 0; c < nc; ++c) ismax |= 0x1ECull << (11 * c);      // bits 2,3,5,6,7,8 of every candidate
-        // small models: the scalars go STRAIGHT into pinned host memory (no copy launch: 6 us of a 60 us iteration); larger ones keep
-        // the copy (a kernel that stores to host memory ends with a system-scope release of everything the iteration left dirty)
-        hipLaunchKernelGGL(dev::k_combine_multi, dim3(nc * 11), dim3(dev::TPB), 0, stream,
-                           (const double*)bpart.p, PSTRIDE, std::max(gq, gx), ismax, zero_copy_small() ? hscal_pin.p : bscal.p, nc * 11,
-                           (const double*)nullptr, 0, 0, (double*)nullptr);
-        if (!zero_copy_small()) PX_HIP(hipMemcpyAsync(hscal_pin.p, bscal.p, NC * 11 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        wait_stream();
-        std::copy(hscal_pin.p, hscal_pin.p + NC * 11, hbscal.begin());
-    };
-    while (!accepted && trials < opt.max_linsearch_steps) {
-        dev::TrialBatch tb{};
-        double tau_c = primal_step;
-        int nc = 0;
-        for (; nc < NC && trials + nc < opt.max_linsearch_steps; ++nc) {
-            tb.tau[nc] = tau_c;
-            tb.theta[nc] = tau_c / primal_step_old;
-            tb.bt[nc] = beta * tau_c;
-            tb.sigma[nc] = beta * tau_c;
-            tau_c *= opt.linsearch_decay;
-        }
-        tb.nc = nc;
-        hipLaunchKernelGGL(dev::k_dual_trial_batch, dim3(gq, nc), dim3(dev::TPB), 0, stream,
-                           ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, tb,
-                           ycand_d.p, ystride, bpart.p, cstride, (const double*)nullptr);
-        hipLaunchKernelGGL(dev::k_spmv_csc_norm_batch, dim3(gx, nc), dim3(dev::TPB), 0, stream,
-                           csc_ptr.p, csc_row.p, csc_val.p, ycand_d.p, ystride, Mtycand_d.p, mstride, Mtybuf[mtyc].p,
-                           (long long)P.n, bpart.p + PSTRIDE, cstride);
-        residual_batch(tb, nc, 0);
-        read_back(nc);
-        for (int c = 0; c < nc; ++c) {
-            ++trials;
-            const double* sc = hbscal.data() + 11 * c;
-            primal_step = tb.tau[c];
-            theta = tb.theta[c];
-            const double y_norm = std::sqrt(sc[0]), Mty_norm = std::sqrt(sc[1]);
-            if (debug && iter <= 5 && trials <= 6)
-                std::fprintf(stderr, "[dbg] it %lld trial %d tau %.6e theta %.6e y_norm %.6e Mty_norm %.6e\n",
-                             iter, trials, primal_step, theta, y_norm, Mty_norm);
-            const bool ok = std::sqrt(beta) * primal_step * Mty_norm <= opt.delta * y_norm;
-            const bool last = trials >= opt.max_linsearch_steps;
-            if (ok || last) {
-                accepted = true;
-                s_acc = sc;
-                if (!ok) {
-                    // reference quirk (pdhg.jl:545-569): trial limit reached -> the step is decayed once more while the
-                    // last trial's y / Mty are kept; the residual scalars are re-evaluated with THAT step (rare path)
-                    primal_step *= opt.linsearch_decay;
-                    dev::TrialBatch t1{};
-                    t1.nc = 1; t1.tau[0] = primal_step; t1.theta[0] = theta; t1.bt[0] = beta * primal_step;
-                    t1.sigma[0] = beta * primal_step;
-                    residual_batch(t1, 1, c);
-                    read_back(1);
-                    // (candidate c's two norms, slots 0 and 1, are not needed any more)
-                    s_acc = hbscal.data();
-                }
-                hipLaunchKernelGGL(dev::k_copy2, dim3(grid_for((long long)P.Q + P.n)), dim3(dev::TPB), 0, stream,
-                                   ybuf[1 - yc].p, (const double*)(ycand_d.p + (size_t)c * ystride), (long long)P.Q,
-                                   Mtybuf[1 - mtyc].p, (const double*)(Mtycand_d.p + (size_t)c * mstride), (long long)P.n);
-                break;
-            }
-            primal_step = tb.tau[c] * opt.linsearch_decay;
-        }
-    }
-    primal_step_old = primal_step;
-    dual_step = beta * primal_step;
-    st.linesearch_trials += trials;
-    // ---- residuals and gap from the accepted candidate's scalars (residual_and_gap)
-    const double tr0 = now_s();
-    const double* s = s_acc + 2;
-    if (debug && iter <= 5)
-        std::fprintf(stderr, "[dbg] it %lld res: %.6e %.6e cx %.6e | %.6e %.6e eq %.6e in %.6e by %.6e hy %.6e\n",
-                     iter, s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8]);
-    const double pres = std::sqrt(g_n) * s[0] / std::max({s[1], g_norm_b, g_norm_h, 1.0});
-    const double dres = std::sqrt(g_Q) * s[3] / std::max({s[4], g_norm_c, 1.0});
-    h_pres.at(iter) = pres;
-    h_dres.at(iter) = dres;
-    h_comb.at(iter) = std::max(pres, dres);
-    if (P.p > 0) equa_feasibility = s[5] / (1.0 + g_norm_b);
-    if (P.m > 0) ineq_feasibility = s[6] / (1.0 + g_norm_h);
-    h_feas.at(iter) = std::max(equa_feasibility, ineq_feasibility);
-    const double po = s[2];
-    double d_o = 0.0;
-    if (P.p > 0) d_o -= s[7];
-    if (P.m > 0) d_o -= s[8];
-    h_pobj.at(iter) = po;
-    h_dobj.at(iter) = d_o;
-    h_gap.at(iter) = std::fabs(po - d_o) / (1.0 + std::fabs(po) + std::fabs(d_o));
-    xc = 1 - xc; mtyc = 1 - mtyc; yc = 1 - yc; mxc = 1 - mxc;
-    last_resid_s = now_s() - tr0;
-    return trials;
 }
 
 // ---- hooks for the kernel-level test entry points
@@ -1664,7 +1405,6 @@ inline void Solver::run() {
     }
     part.alloc((size_t)NQ * PSTRIDE); part.zero(stream);
     scal.alloc(NQ); scal.zero(stream);
-    hscal.assign(NQ, 0.0);
     {   // sparse operator, both orientations, int32 indices
         std::vector<int> rp(P.Q + 1), cp(P.n + 1);
         // (prepare() guarantees n, Q, nnz < 2^31: the casts below cannot truncate)
@@ -1777,6 +1517,7 @@ inline void Solver::run() {
     if (P.dense()) opt.support_path = 0;                 // every column of a dense M is in the support
     setup_support();
     setup_dense();
+    alloc_candidates();
     if (sharded() && !use_support)
         throw std::domain_error("block-sharded solve needs the support-aware path (no SOC / 1x1 cones)");
     double spectral_norm = g_frob;                       // LinearAlgebra.norm(M), pdhg.jl:121
@@ -1823,25 +1564,14 @@ inline void Solver::run() {
         const double tp0 = now_s();
         primal_step_dev();
         st.t_primal += now_s() - tp0;                    // "primal" section of pdhg.jl:150 (includes t_psd)
+        // (the residual / gap REDUCTIONS ride in the candidates' batch and its read-back -- they are part of t_linesearch;
+        // t_residual counts what is left of compute_residual! / compute_gap!: the host scalars)
         const double tl0 = now_s();
-        if (use_support) {
-            // (fused paths: the residual / gap REDUCTIONS ride in the candidates' batch and its one read-back -- they are
-            // part of t_linesearch; t_residual counts what is left of compute_residual! / compute_gap!: the host scalars)
-            last_trials = linesearch_residual_support();
-            st.t_linesearch += now_s() - tl0 - last_resid_s; st.t_residual += last_resid_s;
-        } else {
-            if (opt.line_search_flag && !P.dense() && !sharded() && opt.general_batch != 0) {
-                last_trials = linesearch_residual_general();       // trials + residual + gap in one batch and one read-back
-                st.t_linesearch += now_s() - tl0 - last_resid_s; st.t_residual += last_resid_s;
-            } else {
-            if (opt.line_search_flag) last_trials = P.dense() ? linesearch_dense() : linesearch();
-            else { dual_step_plain(); last_trials = 1; }
-            const double tl1 = now_s();
-            residual_and_gap();
-            st.t_linesearch += tl1 - tl0;
-            st.t_residual += now_s() - tl1;
-            }
-        }
+        const double* s_acc = linesearch_and_residuals();
+        const double tl1 = now_s();
+        record_residuals(s_acc);
+        st.t_linesearch += tl1 - tl0;
+        st.t_residual += now_s() - tl1;
         {   // algorithmic bytes of this iteration
             const double t = (double)last_trials;
             double bb = 8.0 * (double)P.n * (11.0 + 3.0 * t) + 12.0 * (double)P.nnz * (1.0 + t) +

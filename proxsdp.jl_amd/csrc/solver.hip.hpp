@@ -521,7 +521,6 @@ public:
     void apply_resume();
     void write_capture();
     int ada_count = 0;                    // pdhg.jl:306-332 (a local of chambolle_pock)
-    double last_resid_s = 0.0;            // host part of compute_residual! / compute_gap! of the last fused linesearch call
     void wait_event(hipEvent_t ev) {
         if (opt.host_wait_spin == 0) { PX_HIP(hipEventSynchronize(ev)); return; }
         for (;;) {
@@ -604,7 +603,6 @@ private:
     bool small_pending = false;
     void project_small_blocks(double* x);
     void harvest_small_ranks();
-    std::vector<double> hscal;
     bool csr_wave = false;
     int rotate_lds_cap = 60 * 1024;           // dynamic LDS granted to k_lz_rotate (setup_device)
     int rotate_mfma_lds_cap = 0;              // ... to k_lz_rotate_mfma
@@ -640,10 +638,11 @@ private:
     bool krylov_branch(int idx) const;
     bool batch_eligible(int idx, bool fuse) const;
     void setup_support();
-    int  linesearch_residual_support();
-    int  linesearch_residual_general();
     void setup_dense();
-    int  linesearch_dense();
+    void alloc_candidates();
+    const double* linesearch_and_residuals();
+    void reduce_candidates(int nc);
+    void record_residuals(const double* s);
     void dense_mv(const double* x, double* y, bool scaled);
     void dense_mtv(int nc, const double* Y, long long ystride, bool scaled, double* OUT, long long ostride,
                    const double* old, const double* addc, double* normpart, long long cstride, bool addback);
@@ -673,9 +672,6 @@ private:
                   double cc, const double* dsc, double* part, double* xp_out, const double* xp_old, int blk);
     void spmv(const double* x, double* y);
     void spmv_sparse(const double* x, double* y);
-    int  linesearch();
-    void dual_step_plain();
-    void residual_and_gap();
     bool convergedrank() const;
     bool soc_convergence();
     double dual_feas_host(const std::vector<double>& y, const std::vector<double>& cvec,
@@ -691,12 +687,12 @@ private:
     std::vector<int> tile_base;                 // first residual-partial slot of each PSD block
     DevBuf<int> supp_d;
     DevBuf<unsigned> mask_d;
-    DevBuf<double> cS_d, xsave_d, MtyS_cur, MtyS_cand, ycand_d, respart_d, bpart, bscal;
+    DevBuf<double> cS_d, xsave_d, MtyS_cur, respart_d;
     DevBuf<double> Ediag_d, Ddiag_d; // equilibration diagonals (exit path)
     DevBuf<double> esv_d;            // [2][ns]: support values of E (update only | whole entry), k_primal_update_S
     // dense constraint matrix (proxsdp_problem.M_dense): borrowed device pointer or own upload
     const double* Md = nullptr;
-    DevBuf<double> Md_own, dmv_part, Mtycand_d;
+    DevBuf<double> Md_own, dmv_part;
     DevBuf<unsigned char> offdiag_d;
     int dmv_slices = 1, dmv_qpad = 0;
     static constexpr int DMV_ROWS = 8, DMV_UNR = 4;       // k_dense_mv shape (rows per workgroup, strips in flight)
@@ -706,10 +702,11 @@ private:
     void dense_ev_begin();
     void dense_ev_end();
     void dense_ev_harvest();
+    // linesearch candidates (linesearch_and_residuals): y_c, M'y_c, partials, the scalar record on the device and its
+    // read-back (support path: hbscal; otherwise the pinned hscal_pin)
+    DevBuf<double> ycand_d, Mtycand_d, bpart, bscal;
     std::vector<double> hbscal;
-    PinnedBuf hscal_pin;            // read-back of the general path's scalars (linesearch norms | residual / gap sums)
-    bool residual_ready = false;    // the accepted linesearch candidate's residual scalars are already in hscal
-    void enqueue_residual(double pstep, double dstep);
+    PinnedBuf hscal_pin;
 };
 
 // ------------------------------------------------------------------ setup
