@@ -49,7 +49,9 @@ extern "C" {
  * instead of PROXSDP_E_INVALID; new proxsdp_state and
  * proxsdp_hip_solve_ex (capture / resume of the solver state at an iteration boundary); PROXSDP_E_COMM_ABORTED;
  * later: proxsdp_options gained lanczos_wide_krylov (from reserved_i2[0]), proxsdp_stats wide_krylov_projections
- * (from reserved_s[0]): same struct sizes and offsets, version unchanged */
+ * (from reserved_s[0]): same struct sizes and offsets, version unchanged;
+ * later: equilibration and approx_norm = 0 served with a dense A (proxsdp_hip_dense_scaling, proxsdp_host_equilibrate_rowsums),
+ * proxsdp_stats dense_setup_passes / dense_sigma_steps (the last two reserved_s slots): same sizes and offsets, version unchanged */
 #define PROXSDP_HIP_ABI_VERSION 9
 
 /* error codes (negative return values) */
@@ -210,7 +212,9 @@ typedef struct proxsdp_options {
     /* equilibration (equilibration.jl, pdhg.jl:64-92): off by default; `equilibration` alone
      * survives only if min(M)/max(M) > equilibration_limit, `equilibration_force` always.
      * approx_norm = 0: step size from sigma_max(M) instead of ||M||_F (pdhg.jl:108-119).
-     * Neither is available with a dense A or a block-sharded solve. */
+     * With a dense A (M_dense) both are set up on the device: one extra pass over the matrix for the row sums and the
+     * extrema, the scaling carried in the vectors of the dense products (the borrowed matrix is never modified), sigma_max
+     * by Lanczos through those products.  Neither is available in a block-sharded solve. */
     int32_t equilibration; int32_t equilibration_iters;
     double  equilibration_lb, equilibration_ub, equilibration_limit;
     int32_t equilibration_force; int32_t approx_norm;
@@ -447,7 +451,12 @@ typedef struct proxsdp_stats {
                                            * pairs of dsyevd, the same truncated projection and min_eig); status_string says so */
     int64_t wide_krylov_projections;      /* Krylov-branch projections with a Krylov dimension of 256..511 run by the wide Lanczos
                                            * kernels (lanczos_wide_krylov = 1) */
-    int64_t reserved_s[6];                /* zero */
+    int64_t reserved_s[4];                /* zero */
+    /* (the last two reserved slots: reserved_s keeps its offset) */
+    int64_t dense_setup_passes;           /* set-up passes over a dense A (row sums + extrema, 8*p*n bytes): 1 when equilibration
+                                           * was asked for, else 0 */
+    int64_t dense_sigma_steps;            /* Lanczos steps of the device sigma_max (approx_norm = 0 with a dense A): two passes
+                                           * over the dense A each, counted in dense_passes / dense_ms as well */
 } proxsdp_stats;
 
 /* Result (structs.jl:60-81).  Arrays are caller-allocated with the stated
@@ -616,6 +625,14 @@ int proxsdp_hip_residuals(const double* x, const double* x_old, const double* Mt
                           const double* y, const double* y_old, const double* Mx, const double* Mx_old,
                           const double* bh, int64_t p, int64_t Q, double sigma, double* out);
 
+/* The "Init" section (pdhg.jl:54-142) of a solve with a dense A (prob->M_dense), nothing more: E (p + m) and D (n), the
+ * equilibration diagonals -- ones when equilibration is off or switched itself off, *equilibrated says which --, frob =
+ * ||.||_F and sigma_max = the largest singular value of the solver's matrix E [A;G] D S (S: the sqrt(2)/2 factor on
+ * off-diagonal PSD columns).  sigma_max is computed only when opt->approx_norm = 0, otherwise it is 0.  Any output may
+ * be NULL. */
+int proxsdp_hip_dense_scaling(const proxsdp_problem* prob, const proxsdp_options* opt,
+                              double* E, double* D, double* frob, double* sigma_max, int32_t* equilibrated);
+
 /* ------------------------------------------- host-only helpers (no GPU needed;
  * exercised by the CPU test-suite) */
 /* eigen-decomposition of a small dense symmetric matrix (column-major k x k,
@@ -649,6 +666,11 @@ int proxsdp_host_start_vector(int64_t n, int64_t seed, int32_t init, double* out
  * inverse permutation and the scaled c; for layout tests */
 int proxsdp_host_preprocess(const proxsdp_problem* prob, int64_t* order, int64_t* var_ordering,
                             double* c_scaled, double* frobenius_norm_M);
+/* equilibrate! (equilibration.jl) from the row sums alone: rowsums[r] = sum_j M[r,j]^2 of a Q x n matrix in, E (Q) and
+ * the scalar d (D = d I: the reference replaces v by its mean in every iteration) out -- the iteration a dense A takes,
+ * where M is only streamed.  Uses opt's equilibration_iters / _lb / _ub / _reference_aliasing (NULL: the defaults). */
+int proxsdp_host_equilibrate_rowsums(const double* rowsums, int64_t Q, int64_t n, const proxsdp_options* opt,
+                                     double* E, double* d);
 
 #ifdef __cplusplus
 }

@@ -118,7 +118,9 @@ struct Stats                     # proxsdp_stats
     cert_matvecs::Int64
     dense_truncated_projections::Int64
     wide_krylov_projections::Int64
-    reserved_s::NTuple{6,Int64}
+    reserved_s::NTuple{4,Int64}
+    dense_setup_passes::Int64
+    dense_sigma_steps::Int64
 end
 
 mutable struct CResult           # proxsdp_result

@@ -140,7 +140,8 @@ class Stats(C.Structure):
                 ("batched_profiled_blocks", i64), ("host_eig_merges", i64),
                 ("host_eig_overlap_time", f64), ("sign_short_pass", i64), ("sign_short_fail", i64),
                 ("full_eigs_lanczos_certified", i64), ("full_eigs_lanczos_cert_failed", i64), ("cert_matvecs", i64),
-                ("dense_truncated_projections", i64), ("wide_krylov_projections", i64), ("reserved_s", i64 * 6)]
+                ("dense_truncated_projections", i64), ("wide_krylov_projections", i64), ("reserved_s", i64 * 4),
+                ("dense_setup_passes", i64), ("dense_sigma_steps", i64)]
 
 
 class Result(C.Structure):
@@ -220,6 +221,8 @@ def lib():
     L.proxsdp_host_symeig.argtypes = [i32, pf64, pf64]
     L.proxsdp_host_start_vector.argtypes = [i64, i64, i32, pf64]
     L.proxsdp_host_preprocess.argtypes = [C.POINTER(Problem), pi64, pi64, pf64, pf64]
+    L.proxsdp_hip_dense_scaling.argtypes = [C.POINTER(Problem), C.POINTER(Options), pf64, pf64, pf64, pf64, C.POINTER(i32)]
+    L.proxsdp_host_equilibrate_rowsums.argtypes = [pf64, i64, i64, C.POINTER(Options), pf64, pf64]
     L.proxsdp_hip_rccl_unique_id.argtypes = [C.c_void_p]
     L.proxsdp_hip_rccl_comm_init.argtypes = [i32, C.c_void_p, i32, i32, C.POINTER(C.c_void_p)]
     L.proxsdp_hip_rccl_comm_destroy.argtypes = [C.c_void_p]
@@ -612,6 +615,18 @@ def spmv(M, x, transpose=False):
     return out
 
 
+def dense_scaling(prob, options=None):
+    """proxsdp_hip_dense_scaling: the Init section of a solve with a dense A.  Returns (E, D, frob, sigma_max,
+    equilibrated); sigma_max is 0 unless options.approx_norm = 0."""
+    M = _Marshalled(prob)
+    Q = M.P.p + M.P.m
+    E, D = np.zeros(max(Q, 1)), np.zeros(max(M.P.n, 1))
+    fro, sig, eq = f64(), f64(), i32()
+    _check(lib().proxsdp_hip_dense_scaling(C.byref(M.P), C.byref(options) if options is not None else None,
+                                           _p(E), _p(D), C.byref(fro), C.byref(sig), C.byref(eq)))
+    return E[:Q], D[:M.P.n], fro.value, sig.value, bool(eq.value)
+
+
 # ----------------------------------------------------------------- host-only helpers (no GPU)
 def host_symeig(A, threads=-1):
     """threads: -1 the library's choice (helper threads from k >= 96), 0 serial -- bit-identical results"""
@@ -664,3 +679,13 @@ def host_preprocess(prob, index_base=0):
     fro = f64()
     _check(lib().proxsdp_host_preprocess(C.byref(M.P), _p(order, pi64), _p(inv, pi64), _p(cs), C.byref(fro)))
     return order, inv, cs, fro.value
+
+
+def host_equilibrate_rowsums(rowsums, n, options=None):
+    """proxsdp_host_equilibrate_rowsums: (E, d) of equilibrate! from the row sums of squares of a Q x n matrix."""
+    rs = _f(rowsums)
+    E = np.zeros(max(len(rs), 1))
+    d = f64()
+    _check(lib().proxsdp_host_equilibrate_rowsums(_p(rs), len(rs), int(n), C.byref(options) if options is not None else None,
+                                                  _p(E), C.byref(d)))
+    return E[:len(rs)], d.value

@@ -415,6 +415,27 @@ int proxsdp_hip_spmv(const proxsdp_csc* M, int32_t index_base, int32_t transpose
     });
 }
 
+int proxsdp_hip_dense_scaling(const proxsdp_problem* prob, const proxsdp_options* opt,
+                              double* E, double* D, double* frob, double* sigma_max, int32_t* equilibrated) {
+    return guarded([&]() -> int {
+        if (!prob) throw std::invalid_argument("NULL problem");
+        if (!prob->M_dense) throw std::invalid_argument("proxsdp_hip_dense_scaling needs a dense A (M_dense)");
+        proxsdp_options o = Engine::fix(opt);
+        o.trace_capacity = 0;
+        proxsdp_result dummy{};
+        proxsdp::Solver S(*prob, o, dummy);
+        S.init_only = true;
+        S.run();                                            // returns after the Init section
+        const proxsdp::Prep& R = S.P;
+        for (int64_t i = 0; E && i < R.Q; ++i) E[i] = R.equilibrated ? R.Ediag[i] : 1.0;
+        for (int64_t k = 0; D && k < R.n; ++k) D[k] = R.equilibrated ? R.Ddiag[k] : 1.0;
+        if (frob) *frob = S.g_frob;
+        if (sigma_max) *sigma_max = S.sigma_max;
+        if (equilibrated) *equilibrated = R.equilibrated ? 1 : 0;
+        return 0;
+    });
+}
+
 int proxsdp_hip_primal_update(const double* x, const double* Mty, const double* c, double tau, int64_t n,
                               double* x_out) {
     return guarded([&]() -> int {
@@ -561,6 +582,18 @@ int proxsdp_host_preprocess(const proxsdp_problem* prob, int64_t* order, int64_t
             if (c_scaled) c_scaled[i] = R.c[i];
         }
         if (frobenius_norm_M) *frobenius_norm_M = R.frob;
+        return 0;
+    });
+}
+
+int proxsdp_host_equilibrate_rowsums(const double* rowsums, int64_t Q, int64_t n, const proxsdp_options* opt,
+                                     double* E, double* d) {
+    return guarded([&]() -> int {
+        if (Q <= 0 || n <= 0 || !rowsums || !E || !d) throw std::invalid_argument("invalid argument");
+        const proxsdp_options o = Engine::fix(opt);
+        std::vector<double> Ed;
+        proxsdp::equilibrate_rowsums(rowsums, Q, n, o, Ed, *d);
+        std::copy(Ed.begin(), Ed.end(), E);
         return 0;
     });
 }

@@ -2176,11 +2176,12 @@ k_combine(const double* __restrict__ part, int stride, int cnt, int nq, unsigned
 // flight per thread
 
 // part[cs][r] = sum over the column slice cs of M[r, j] * s_j * x_j   (grid: row groups x slices)
-template <int DMV_ROWS, int DMV_UNR>
-__global__ void __launch_bounds__(TPB)
-k_dense_mv(const double* __restrict__ M, long long ld, int Q, long long n, const double* __restrict__ x,
-           const unsigned char* __restrict__ offdiag, double scale, double* __restrict__ part, int qpad) {
-    __shared__ double sm[DMV_ROWS][NWAVE];
+// (EQ: the equilibrated solve's column scale vector D o s in place of the off-diagonal flags)
+template <int DMV_ROWS, int DMV_UNR, bool EQ>
+__device__ __forceinline__ void
+dense_mv_body(const double* __restrict__ M, long long ld, int Q, long long n, const double* __restrict__ x,
+              const unsigned char* __restrict__ offdiag, double scale, const double* __restrict__ colscale,
+              double* __restrict__ part, int qpad, double (*sm)[NWAVE]) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int r0 = blockIdx.x * DMV_ROWS;
     // column slice of this workgroup, in units of TPB * DMV_UNR columns
@@ -2201,7 +2202,9 @@ k_dense_mv(const double* __restrict__ M, long long ld, int Q, long long n, const
         for (int u = 0; u < DMV_UNR; ++u) {
             const long long j = jb + (long long)u * TPB + threadIdx.x;
             const long long jc = (j < c1) ? j : c1 - 1;
-            const double sc = (offdiag != nullptr && offdiag[jc]) ? scale : 1.0;
+            double sc;
+            if constexpr (EQ) sc = colscale[jc];
+            else sc = (offdiag != nullptr && offdiag[jc]) ? scale : 1.0;
             xv[u] = (j < c1) ? x[jc] * sc : 0.0;
 #pragma unroll
             for (int r = 0; r < DMV_ROWS; ++r) mv[r][u] = rowp[r][jc];
@@ -2222,6 +2225,21 @@ k_dense_mv(const double* __restrict__ M, long long ld, int Q, long long n, const
         part[(long long)blockIdx.y * qpad + r0 + r] = (sm[r][0] + sm[r][1]) + (sm[r][2] + sm[r][3]);
     }
 }
+template <int DMV_ROWS, int DMV_UNR>
+__global__ void __launch_bounds__(TPB)
+k_dense_mv(const double* __restrict__ M, long long ld, int Q, long long n, const double* __restrict__ x,
+           const unsigned char* __restrict__ offdiag, double scale, double* __restrict__ part, int qpad) {
+    __shared__ double sm[DMV_ROWS][NWAVE];
+    dense_mv_body<DMV_ROWS, DMV_UNR, false>(M, ld, Q, n, x, offdiag, scale, nullptr, part, qpad, sm);
+}
+// equilibrated solve: part[cs][r] = sum over the slice of M[r, j] * (D o s)_j * x_j
+template <int DMV_ROWS, int DMV_UNR>
+__global__ void __launch_bounds__(TPB)
+k_dense_mv_eq(const double* __restrict__ M, long long ld, int Q, long long n, const double* __restrict__ x,
+              const double* __restrict__ colscale, double* __restrict__ part, int qpad) {
+    __shared__ double sm[DMV_ROWS][NWAVE];
+    dense_mv_body<DMV_ROWS, DMV_UNR, true>(M, ld, Q, n, x, nullptr, 1.0, colscale, part, qpad, sm);
+}
 // y[r] = sum of the slices (fixed order)
 __global__ void __launch_bounds__(TPB)
 k_dense_mv_fin(const double* __restrict__ part, int qpad, int nslice, int Q, double* __restrict__ y) {
@@ -2231,6 +2249,16 @@ k_dense_mv_fin(const double* __restrict__ part, int qpad, int nslice, int Q, dou
     for (int sidx = 0; sidx < nslice; ++sidx) a += part[(long long)sidx * qpad + r];
     y[r] = a;
 }
+// equilibrated solve: y[r] = E_r * sum of the slices
+__global__ void __launch_bounds__(TPB)
+k_dense_mv_fin_eq(const double* __restrict__ part, int qpad, int nslice, int Q, const double* __restrict__ rowscale,
+                  double* __restrict__ y) {
+    const int r = blockIdx.x * TPB + threadIdx.x;
+    if (r >= Q) return;
+    double a = 0.0;
+    for (int sidx = 0; sidx < nslice; ++sidx) a += part[(long long)sidx * qpad + r];
+    y[r] = a * rowscale[r];
+}
 
 // OUT_c[j] = s_j * sum_k M[k, j] * Y_c[k] (+ the sparse rows of [A;G]) for NC candidate vectors in ONE pass over M
 // (the linesearch candidates tau, 3/4 tau, (3/4)^2 tau share the 8*Q*n bytes), plus the
@@ -2238,15 +2266,22 @@ k_dense_mv_fin(const double* __restrict__ part, int qpad, int nslice, int Q, dou
 // the exit path's dual cone).  Thread = column; the loop over rows keeps DMT_UNR loads in flight.
 // CPT columns per thread (TPB apart: a workgroup reads CPT * 2 KB contiguous bytes of every
 // row), DMT_UNR rows in flight.
-template <int NC, int CPT, int DMT_UNR>
-__global__ void __launch_bounds__(TPB)
-k_dense_mtv(const double* __restrict__ M, long long ld, int Q, long long n, const double* __restrict__ Y,
-            long long ystride, const unsigned char* __restrict__ offdiag, double scale,
-            double* __restrict__ OUT, long long ostride, const double* __restrict__ old,
-            const double* __restrict__ addc, double* __restrict__ part, long long cstride,
-            const int* __restrict__ sp_colptr, const int* __restrict__ sp_row, const double* __restrict__ sp_val,
-            int addback) {
-    __shared__ double sm[NWAVE];
+template <bool EQ>
+__device__ __forceinline__ double dense_y(const double* __restrict__ Y, const double* __restrict__ rowscale, long long off, int k) {
+    if constexpr (EQ) return Y[off + k] * rowscale[k];
+    else return Y[off + k];
+}
+// EQ (equilibrated solve): the dense block takes E o Y_c on the way in (one broadcast load more per row) and the column
+// scale vector D o s on the way out; the sparse rows carry their scaling in sp_val.
+template <int NC, int CPT, int DMT_UNR, bool EQ>
+__device__ __forceinline__ void
+dense_mtv_body(const double* __restrict__ M, long long ld, int Q, long long n, const double* __restrict__ Y,
+               long long ystride, const unsigned char* __restrict__ offdiag, double scale,
+               const double* __restrict__ rowscale, const double* __restrict__ colscale,
+               double* __restrict__ OUT, long long ostride, const double* __restrict__ old,
+               const double* __restrict__ addc, double* __restrict__ part, long long cstride,
+               const int* __restrict__ sp_colptr, const int* __restrict__ sp_row, const double* __restrict__ sp_val,
+               int addback, double* sm) {
     double ss[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) ss[c] = 0.0;
@@ -2281,7 +2316,7 @@ k_dense_mtv(const double* __restrict__ M, long long ld, int Q, long long n, cons
             for (int u = 0; u < DMT_UNR; ++u)
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    const double yv = Y[c * ystride + k + u];
+                    const double yv = dense_y<EQ>(Y, rowscale, c * ystride, k + u);
 #pragma unroll
                     for (int t = 0; t < CPT; ++t) acc[c][t] += mv[u][t] * yv;
                 }
@@ -2291,14 +2326,16 @@ k_dense_mtv(const double* __restrict__ M, long long ld, int Q, long long n, cons
             for (int t = 0; t < CPT; ++t) {
                 const double mvk = col[t][(long long)k * ld];
 #pragma unroll
-                for (int c = 0; c < NC; ++c) acc[c][t] += mvk * Y[c * ystride + k];
+                for (int c = 0; c < NC; ++c) acc[c][t] += mvk * dense_y<EQ>(Y, rowscale, c * ystride, k);
             }
         }
 #pragma unroll
         for (int t = 0; t < CPT; ++t) {
             const long long j = b * span + (long long)t * TPB + threadIdx.x;
             if (j >= n) continue;
-            const double sc = (offdiag != nullptr && offdiag[j]) ? scale : 1.0;
+            double sc;
+            if constexpr (EQ) sc = colscale[j];
+            else sc = (offdiag != nullptr && offdiag[j]) ? scale : 1.0;
             const double o = (old != nullptr) ? old[j] : 0.0;
             const double ad = (addc != nullptr) ? addc[j] : 0.0;
             double spv[NC];                               // sparse rows of M (G), already scaled
@@ -2325,6 +2362,30 @@ k_dense_mtv(const double* __restrict__ M, long long ld, int Q, long long n, cons
         }
     }
 }
+template <int NC, int CPT, int DMT_UNR>
+__global__ void __launch_bounds__(TPB)
+k_dense_mtv(const double* __restrict__ M, long long ld, int Q, long long n, const double* __restrict__ Y,
+            long long ystride, const unsigned char* __restrict__ offdiag, double scale,
+            double* __restrict__ OUT, long long ostride, const double* __restrict__ old,
+            const double* __restrict__ addc, double* __restrict__ part, long long cstride,
+            const int* __restrict__ sp_colptr, const int* __restrict__ sp_row, const double* __restrict__ sp_val,
+            int addback) {
+    __shared__ double sm[NWAVE];
+    dense_mtv_body<NC, CPT, DMT_UNR, false>(M, ld, Q, n, Y, ystride, offdiag, scale, nullptr, nullptr, OUT, ostride, old, addc,
+                                            part, cstride, sp_colptr, sp_row, sp_val, addback, sm);
+}
+template <int NC, int CPT, int DMT_UNR>
+__global__ void __launch_bounds__(TPB)
+k_dense_mtv_eq(const double* __restrict__ M, long long ld, int Q, long long n, const double* __restrict__ Y,
+               long long ystride, const double* __restrict__ rowscale, const double* __restrict__ colscale,
+               double* __restrict__ OUT, long long ostride, const double* __restrict__ old,
+               const double* __restrict__ addc, double* __restrict__ part, long long cstride,
+               const int* __restrict__ sp_colptr, const int* __restrict__ sp_row, const double* __restrict__ sp_val,
+               int addback) {
+    __shared__ double sm[NWAVE];
+    dense_mtv_body<NC, CPT, DMT_UNR, true>(M, ld, Q, n, Y, ystride, nullptr, 1.0, rowscale, colscale, OUT, ostride, old, addc,
+                                           part, cstride, sp_colptr, sp_row, sp_val, addback, sm);
+}
 
 // sum_kj (M[k,j] s_j)^2 partials: ||M||_F of the scaled matrix (pdhg.jl:121)
 __global__ void __launch_bounds__(TPB)
@@ -2348,6 +2409,90 @@ k_dense_frob(const double* __restrict__ M, long long ld, int Q, long long n,
     }
     const double tot = block_sum(ss, sm);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+// The set-up pass of an equilibrated dense solve: per row r of M the partial sums over one column slice of
+//   R_r = sum_j M[r,j]^2  and  R'_r = sum_j (s_j M[r,j])^2   (s_j^2 = 1/2 on off-diagonal PSD columns)
+// and the workgroup's smallest and largest entry (the equilibration_limit test, pdhg.jl:66-73).  Grid and loop shape of
+// k_dense_mv (row groups x column slices, M read once: 8*Q*n bytes); every sum has a fixed order.
+//   part[(2*cs) * qpad + r] = R partial, part[(2*cs + 1) * qpad + r] = R' partial, mm[2*wg], mm[2*wg + 1] = min, max
+template <int DMV_ROWS, int DMV_UNR>
+__global__ void __launch_bounds__(TPB)
+k_dense_rowstats(const double* __restrict__ M, long long ld, int Q, long long n,
+                 const unsigned char* __restrict__ offdiag, double* __restrict__ part, int qpad, double* __restrict__ mm) {
+    __shared__ double sm[2 * DMV_ROWS][NWAVE];
+    __shared__ double smm[NWAVE];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * DMV_ROWS;
+    const long long chunk = (long long)TPB * DMV_UNR;
+    const long long nchunks = (n + chunk - 1) / chunk;
+    const long long per = (nchunks + gridDim.y - 1) / gridDim.y;
+    const long long c0 = (long long)blockIdx.y * per * chunk;
+    const long long c1 = (c0 + per * chunk < n) ? c0 + per * chunk : n;
+    const double* rowp[DMV_ROWS];
+#pragma unroll
+    for (int r = 0; r < DMV_ROWS; ++r) rowp[r] = M + (long long)min(r0 + r, Q - 1) * ld;
+    double acc[DMV_ROWS], accs[DMV_ROWS];
+#pragma unroll
+    for (int r = 0; r < DMV_ROWS; ++r) acc[r] = accs[r] = 0.0;
+    // (an empty slice -- c0 >= n -- reads nothing: its extrema stay at the matrix's first entry)
+    double lo = M[0], hi = lo;
+    for (long long jb = c0; jb < c1; jb += chunk) {
+        double wv2[DMV_UNR], mv[DMV_ROWS][DMV_UNR];
+#pragma unroll
+        for (int u = 0; u < DMV_UNR; ++u) {
+            const long long j = jb + (long long)u * TPB + threadIdx.x;
+            const long long jc = (j < c1) ? j : c1 - 1;
+            wv2[u] = (j < c1) ? (offdiag[jc] ? 0.5 : 1.0) : 0.0;
+#pragma unroll
+            for (int r = 0; r < DMV_ROWS; ++r) mv[r][u] = rowp[r][jc];       // (clamped loads repeat an entry: harmless for min / max)
+        }
+#pragma unroll
+        for (int r = 0; r < DMV_ROWS; ++r)
+#pragma unroll
+            for (int u = 0; u < DMV_UNR; ++u) {
+                const double v2 = mv[r][u] * mv[r][u];
+                acc[r] += (wv2[u] != 0.0) ? v2 : 0.0;
+                accs[r] += v2 * wv2[u];
+                lo = fmin(lo, mv[r][u]); hi = fmax(hi, mv[r][u]);
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < DMV_ROWS; ++r) {
+        const double w = wave_sum(acc[r]), ws = wave_sum(accs[r]);
+        if (lane == 0) { sm[2 * r][wv] = w; sm[2 * r + 1][wv] = ws; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * DMV_ROWS && r0 + (int)(threadIdx.x >> 1) < Q) {
+        const int q = threadIdx.x;
+        part[((long long)blockIdx.y * 2 + (q & 1)) * qpad + r0 + (q >> 1)] = (sm[q][0] + sm[q][1]) + (sm[q][2] + sm[q][3]);
+    }
+    const long long wg = (long long)blockIdx.y * gridDim.x + blockIdx.x;
+    const double bhi = block_max(hi, smm);
+    const double blo = -block_max(-lo, smm);
+    if (threadIdx.x == 0) { mm[2 * wg] = blo; mm[2 * wg + 1] = bhi; }
+}
+// out[r] = R_r, out[qpad + r] = R'_r (slices summed in order); the workgroup past the rows: out[2*qpad], out[2*qpad+1] = min, max
+__global__ void __launch_bounds__(TPB)
+k_dense_rowstats_fin(const double* __restrict__ part, int qpad, int nslice, int Q, const double* __restrict__ mm, int nwg,
+                     double* __restrict__ out) {
+    __shared__ double smm[NWAVE];
+    if (blockIdx.x == gridDim.x - 1) {
+        double lo = mm[0], hi = mm[1];
+        for (int i = threadIdx.x; i < nwg; i += TPB) { lo = fmin(lo, mm[2 * i]); hi = fmax(hi, mm[2 * i + 1]); }
+        const double bhi = block_max(hi, smm);
+        const double blo = -block_max(-lo, smm);
+        if (threadIdx.x == 0) { out[2LL * qpad] = blo; out[2LL * qpad + 1] = bhi; }
+        return;
+    }
+    const int r = blockIdx.x * TPB + threadIdx.x;
+    if (r >= Q) return;
+    double a = 0.0, b = 0.0;
+    for (int sidx = 0; sidx < nslice; ++sidx) {
+        a += part[(long long)sidx * 2 * qpad + r];
+        b += part[((long long)sidx * 2 + 1) * qpad + r];
+    }
+    out[r] = a; out[qpad + r] = b;
 }
 
 // one workgroup per quantity: out[q] = sum or max of part[q*stride .. +cnt); workgroups

@@ -1002,8 +1002,8 @@ inline void Solver::cache_solution(const std::vector<double>& cvec) {
 }
 
 // ---- dense constraint matrix (proxsdp_problem.M_dense; kernels.hip.hpp "Dense constraint matrix")
-inline void Solver::setup_dense() {
-    if (!P.dense()) return;
+inline void Solver::upload_dense() {
+    if (Md != nullptr) return;
     const size_t cnt = (size_t)P.p * (size_t)P.n;
     if (P.Mdense_on_device) {
         Md = P.Mdense;                                   // borrowed, read-only
@@ -1023,6 +1023,101 @@ inline void Solver::setup_dense() {
     dmv_slices = (int)std::min<long long>(dmv_slices, std::max<long long>(chunks, 1));
     dmv_qpad = (int)std::max<int64_t>(P.p, 1);
     dmv_part.alloc((size_t)dmv_slices * dmv_qpad);
+}
+
+// Equilibration on a dense A (the part prepare() deferred): ONE pass over the borrowed matrix for the row sums and the
+// extrema, then the limit check and the scaling iteration on the host (O(Q) per iteration), the scale vectors of the
+// dense products, and ||E A D S||_F^2 = d^2 sum_i e_i^2 R'_i.  Runs before anything reads P.b / P.h / P.c / P.val.
+inline void Solver::setup_dense_scaling() {
+    if (!P.equil_deferred) return;
+    upload_dense();
+    std::vector<double> out((size_t)2 * dmv_qpad + 2, 0.0);
+    if (P.p > 0) {
+        const int rg = ceil_div((int)P.p, DMV_ROWS);
+        const int nwg = rg * dmv_slices;
+        DevBuf<double> spart((size_t)2 * dmv_slices * dmv_qpad), smm((size_t)2 * nwg), sout(out.size());
+        hipLaunchKernelGGL((dev::k_dense_rowstats<DMV_ROWS, DMV_UNR>), dim3(rg, dmv_slices), dim3(dev::TPB), 0, stream,
+                           Md, (long long)P.n, (int)P.p, (long long)P.n, (const unsigned char*)offdiag_d.p, spart.p, dmv_qpad, smm.p);
+        hipLaunchKernelGGL(dev::k_dense_rowstats_fin, dim3(ceil_div((int)P.p, dev::TPB) + 1), dim3(dev::TPB), 0, stream,
+                           (const double*)spart.p, dmv_qpad, dmv_slices, (int)P.p, (const double*)smm.p, nwg, sout.p);
+        sout.download(out.data(), out.size(), stream);
+        PX_HIP(hipStreamSynchronize(stream));
+        st.dense_setup_passes += 1;
+    }
+    finish_dense_equilibration(P, opt, out.data(), out[(size_t)2 * dmv_qpad], out[(size_t)2 * dmv_qpad + 1]);
+    if (!P.equilibrated) return;                         // switched itself off: the plain path, bit for bit
+    const double cte = std::sqrt(2.0) / 2.0;
+    std::vector<double> dcol(P.n);
+    for (int64_t k = 0; k < P.n; ++k) dcol[k] = P.offdiag[k] ? P.Ddiag[k] * cte : P.Ddiag[k];
+    drow_d.alloc(std::max<int64_t>(P.p, 1)); dcol_d.alloc(P.n);
+    drow_d.upload(P.Ediag.data(), P.p, stream); dcol_d.upload(dcol.data(), P.n, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    const double d = P.Ddiag[0];
+    dense_frob2 = 0.0;
+    for (int64_t i = 0; i < P.p; ++i) dense_frob2 += (P.Ediag[i] * d) * (P.Ediag[i] * d) * out[(size_t)dmv_qpad + i];
+}
+
+// sigma_max of the solver's M with a dense A (approx_norm = false, pdhg.jl:108-119): the Lanczos of spectral_norm_host --
+// fixed start vector, full re-orthogonalisation, the same stopping rule -- on the SHORT side (M M' when Q <= n: a basis of
+// Q-vectors on the host, two passes over the dense block per step).  The products are the loop's own (spmv, dense_mtv).
+inline double Solver::spectral_norm_device() {
+    const int64_t n = P.n, Q = P.Q;
+    if (n == 0 || Q == 0) return 0.0;
+    const bool rowside = Q <= n;
+    const int64_t dim = rowside ? Q : n;
+    const int kmax = (int)std::min<int64_t>(dim, 120);
+    DevBuf<double> xd(n), yd(Q), od(rowside ? Q : n);
+    std::vector<std::vector<double>> V;
+    std::vector<double> al, be, v(dim, 1.0 / std::sqrt((double)dim)), w(dim);
+    double sigma2 = 0.0;
+    for (int k = 0; k < kmax; ++k) {
+        V.push_back(v);
+        if (rowside) {                                   // w = M (M' v)
+            yd.upload(v.data(), Q, stream);
+            dense_mtv(1, yd.p, 0, true, xd.p, 0, nullptr, nullptr, nullptr, 0, false);
+            spmv(xd.p, od.p);
+        } else {                                         // w = M' (M v)
+            xd.upload(v.data(), n, stream);
+            spmv(xd.p, yd.p);
+            dense_mtv(1, yd.p, 0, true, od.p, 0, nullptr, nullptr, nullptr, 0, false);
+        }
+        od.download(w.data(), dim, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+        st.dense_sigma_steps += 1;
+        double a = 0.0;
+        for (int64_t c = 0; c < dim; ++c) a += w[c] * v[c];
+        al.push_back(a);
+        for (int pass = 0; pass < 2; ++pass)
+            for (const std::vector<double>& vj : V) {
+                double h = 0.0;
+                for (int64_t c = 0; c < dim; ++c) h += vj[c] * w[c];
+                for (int64_t c = 0; c < dim; ++c) w[c] -= h * vj[c];
+            }
+        double b = 0.0;
+        for (int64_t c = 0; c < dim; ++c) b += w[c] * w[c];
+        b = std::sqrt(b);
+        const int K = k + 1;
+        std::vector<double> T((size_t)K * K, 0.0), d(K);
+        for (int i = 0; i < K; ++i) { T[(size_t)i * K + i] = al[i]; if (i + 1 < K) T[(size_t)i * K + i + 1] = T[(size_t)(i + 1) * K + i] = be[i]; }
+        symeig_dense(K, T.data(), d.data(), true);
+        sigma2 = d[K - 1];
+        const double resid = std::fabs(b * T[(size_t)(K - 1) * K + (K - 1)]);     // beta * last component of the top Ritz vector
+        if (b <= 1e-14 * std::max(1.0, std::fabs(sigma2)) || resid <= 1e-14 * std::fabs(sigma2)) break;
+        be.push_back(b);
+        for (int64_t c = 0; c < dim; ++c) v[c] = w[c] / b;
+    }
+    dense_ev_harvest();
+    dense_passes_seen = st.dense_passes;                 // (set-up work: not in the iterations' algorithmic bytes)
+    return std::sqrt(std::max(sigma2, 0.0));
+}
+
+inline void Solver::setup_dense() {
+    if (!P.dense()) return;
+    upload_dense();
+    if (P.equilibrated) {                                // the set-up pass already has the row sums of the scaled block
+        g_frob = std::sqrt(dense_frob2 + P.frob * P.frob);
+        return;
+    }
     // ||M||_F of the column-scaled matrix (pdhg.jl:121 after norm_scaling)
     const int gx = std::min(PSTRIDE, grid_for(P.n));
     hipLaunchKernelGGL(dev::k_dense_frob, dim3(gx), dim3(dev::TPB), 0, stream,
@@ -1061,6 +1156,15 @@ inline void Solver::dense_mv(const double* x, double* y, bool scaled) {
     if (P.p == 0) return;
     const int rg = ceil_div((int)P.p, DMV_ROWS);
     dense_ev_begin();
+    if (scaled && P.equilibrated) {                      // y = E (M (D o s o x))
+        hipLaunchKernelGGL((dev::k_dense_mv_eq<DMV_ROWS, DMV_UNR>), dim3(rg, dmv_slices), dim3(dev::TPB), 0, stream,
+                           Md, (long long)P.n, (int)P.p, (long long)P.n, x, (const double*)dcol_d.p, dmv_part.p, dmv_qpad);
+        hipLaunchKernelGGL(dev::k_dense_mv_fin_eq, dim3(ceil_div((int)P.p, dev::TPB)), dim3(dev::TPB), 0, stream,
+                           (const double*)dmv_part.p, dmv_qpad, dmv_slices, (int)P.p, (const double*)drow_d.p, y);
+        dense_ev_end();
+        st.dense_passes += 1;
+        return;
+    }
     auto lmv = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(rg, dmv_slices), dim3(dev::TPB), 0, stream,
                            Md, (long long)P.n, (int)P.p, (long long)P.n, x, scaled ? offdiag_d.p : nullptr,
@@ -1087,8 +1191,18 @@ inline void Solver::dense_mtv(int nc, const double* Y, long long ystride, bool s
                            Y, ystride, od, sc, OUT, ostride, old, addc, normpart, cstride,
                            scaled && P.nnz > 0 ? csc_ptr.p : nullptr, csc_row.p, csc_val.p, addback ? 1 : 0);
     };
+    auto launch_eq = [&](auto kern) {                    // OUT_c = (D o s) o (M' (E o Y_c)) + the scaled sparse rows
+        hipLaunchKernelGGL(kern, dim3(gx), dim3(dev::TPB), 0, stream, Md, (long long)P.n, (int)P.p, (long long)P.n,
+                           Y, ystride, (const double*)drow_d.p, (const double*)dcol_d.p, OUT, ostride, old, addc, normpart, cstride,
+                           P.nnz > 0 ? csc_ptr.p : nullptr, csc_row.p, csc_val.p, addback ? 1 : 0);
+    };
     dense_ev_begin();
-    if (nc == 1) launch(dev::k_dense_mtv<1, 1, 8>);
+    if (scaled && P.equilibrated) {
+        if (nc == 1) launch_eq(dev::k_dense_mtv_eq<1, 1, 8>);
+        else if (nc == 2) launch_eq(dev::k_dense_mtv_eq<2, 1, 8>);
+        else launch_eq(dev::k_dense_mtv_eq<3, 1, 8>);
+    }
+    else if (nc == 1) launch(dev::k_dense_mtv<1, 1, 8>);
     else if (nc == 2) launch(dev::k_dense_mtv<2, 1, 8>);
     else launch(dev::k_dense_mtv<3, 1, 8>);      // <3,1,16> 6.41, <3,2,8> 6.39, <3,4,4> 6.47, <3,2,4> 6.37 TB/s: flat
     dense_ev_end();
@@ -1325,8 +1439,8 @@ inline void Solver::write_capture() {
 // chambolle_pock (pdhg.jl:1-530)
 inline void Solver::run() {
     const double t_init0 = now_s();
-    if (!opt.approx_norm && (P.dense() || sharded()))
-        throw std::domain_error("approx_norm=false with a dense A or a block-sharded solve is not implemented");
+    if (!opt.approx_norm && sharded())
+        throw std::domain_error("approx_norm=false with a block-sharded solve is not implemented");
     if (P.n <= 0) throw std::invalid_argument("problem has no variables");
     if (opt.convergence_window <= 0) throw std::invalid_argument("convergence_window must be positive");
     // (the reference's `for i in 1:max_linsearch_steps` simply runs no trial then and keeps stale norms; the batched
@@ -1370,10 +1484,11 @@ inline void Solver::run() {
     ada_count = 0;
     h_gap.init(2 * window); h_pobj.init(2 * window); h_dobj.init(2 * window); h_feas.init(2 * window);
     h_pres.init(2 * window); h_dres.init(2 * window); h_comb.init(2 * window);
-    b_host = P.b; h_host = P.h; c_host = P.c;
 
     // ---- device state ("Init", pdhg.jl:54-142)
     setup_device();
+    setup_dense_scaling();                               // (equilibration on a dense A: finishes what prepare() deferred)
+    b_host = P.b; h_host = P.h; c_host = P.c;
     bool big_block = false;
     for (const BlockInfo& B : P.blocks) big_block = big_block || B.n >= 256;
     // opt-in only: measured on MI355X/ROCm 7.2, loading rocSOLVER's code objects from a second
@@ -1521,8 +1636,12 @@ inline void Solver::run() {
     if (sharded() && !use_support)
         throw std::domain_error("block-sharded solve needs the support-aware path (no SOC / 1x1 cones)");
     double spectral_norm = g_frob;                       // LinearAlgebra.norm(M), pdhg.jl:121
-    if (!opt.approx_norm)                                // Arpack.svds(M, nsv=1), pdhg.jl:108-119
-        spectral_norm = spectral_norm_host(P, [](int K, double* T, double* d) { return symeig_dense(K, T, d, true); });
+    if (!opt.approx_norm) {                              // Arpack.svds(M, nsv=1), pdhg.jl:108-119
+        if (P.dense()) spectral_norm = spectral_norm_device();
+        else spectral_norm = spectral_norm_host(P, [](int K, double* T, double* d) { return symeig_dense(K, T, d, true); });
+        sigma_max = spectral_norm;
+    }
+    if (init_only) return;
     if (spectral_norm < 1e-10) spectral_norm = 1.0;
     primal_step = 1.0 / spectral_norm;
     primal_step_old = primal_step;

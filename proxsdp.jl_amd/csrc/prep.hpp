@@ -45,6 +45,9 @@ struct Prep {
     const double* Mdense = nullptr;
     bool Mdense_on_device = false;
     bool dense() const { return Mdense != nullptr; }
+    // equilibration asked for on a dense A: the limit check and the scaling need one device pass over the
+    // borrowed matrix, so prepare() leaves them to the solver (finish_dense_equilibration)
+    bool equil_deferred = false;
 };
 
 inline double norm2(const double* v, int64_t n) {
@@ -114,6 +117,106 @@ inline void equilibrate_host(const Prep& R, const proxsdp_options& opt, std::vec
     }
     for (int64_t r = 0; r < nQ; ++r) Ed[r] = std::exp(u_[r]);
     for (int64_t k = 0; k < n; ++k) Dd[k] = std::exp(v_[k]);
+}
+
+// The same iteration from the row sums rs[r] = sum_j M[r,j]^2 alone, for a matrix that is only streamed (dense A).
+// v is replaced by its mean in every iteration, so D = d I throughout: row_norms[r] = (E_r d)^2 rs[r], and the v update
+// needs only mean_j col_norms[j] = sum_r row_norms[r] / n.  O(Q) per iteration; both aliasing variants as above.
+inline void equilibrate_rowsums(const double* rs, int64_t nQ, int64_t n, const proxsdp_options& opt,
+                                std::vector<double>& Ed, double& d) {
+    const double alpha = std::pow((double)n / (double)nQ, 0.25), beta = std::pow((double)nQ / (double)n, 0.25);
+    const double alpha2 = alpha * alpha, beta2 = beta * beta, gamma = 0.1;
+    std::vector<double> u(nQ, 0.0), u_(nQ, 0.0);
+    double v = 0.0, v_ = 0.0;
+    Ed.assign(nQ, 1.0); d = 1.0;
+    const bool alias = opt.equilibration_reference_aliasing != 0;
+    for (int64_t it = 1; it <= opt.equilibration_iters; ++it) {
+        for (int64_t r = 0; r < nQ; ++r) Ed[r] = std::exp(u[r]);
+        d = std::exp(v);
+        if (alias) { u = Ed; v = d; }
+        const double step = 2.0 / (gamma * ((double)it + 1.0));
+        double cs = 0.0;
+        for (int64_t r = 0; r < nQ; ++r) {
+            const double s = Ed[r] * d, rn = s * s * rs[r];
+            cs += rn;
+            const double g = rn - alpha2 + gamma * u[r];
+            u[r] = std::min(opt.equilibration_ub, std::max(u[r] - step * g, opt.equilibration_lb));
+        }
+        v -= step * (cs / (double)n - beta2 + gamma * v);
+        v = std::min(opt.equilibration_ub, std::max(v, 0.0));
+        const double a = 2.0 / ((double)it + 2.0), b = (double)it / ((double)it + 2.0);
+        for (int64_t r = 0; r < nQ; ++r) u_[r] = a * u[r] + b * u_[r];
+        v_ = a * v + b * v_;
+    }
+    for (int64_t r = 0; r < nQ; ++r) Ed[r] = std::exp(u_[r]);
+    d = std::exp(v_);
+}
+
+// values of the solver's M (E M D when equilibrated, then the sqrt(2)/2 column factor), its Frobenius norm, its CSR
+inline void finish_matrix(Prep& R) {
+    const double cte = std::sqrt(2.0) / 2.0;
+    const bool equil = R.equilibrated;
+    double ss = 0.0;
+    for (int64_t k = 0; k < R.n; ++k) {
+        const double sc = R.offdiag[k] ? cte : 1.0;
+        for (int64_t q = R.colptr[k]; q < R.colptr[k + 1]; ++q) {
+            double v = R.val_orig[q];
+            if (equil) v = R.Ediag[R.rowidx[q]] * v * R.Ddiag[k];
+            R.val[q] = v * sc;
+            ss += R.val[q] * R.val[q];
+        }
+    }
+    R.frob = std::sqrt(ss);
+
+    // ---- CSR of the scaled M (counting sort; column order inside a row ascending)
+    R.rowptr.assign(R.Q + 1, 0);
+    for (int64_t q = 0; q < R.nnz; ++q) R.rowptr[R.rowidx[q] + 1]++;
+    for (int64_t r = 0; r < R.Q; ++r) R.rowptr[r + 1] += R.rowptr[r];
+    R.colidx.resize(R.nnz); R.rval.resize(R.nnz);
+    std::vector<int64_t> cur(R.rowptr.begin(), R.rowptr.end() - 1);
+    for (int64_t k = 0; k < R.n; ++k)
+        for (int64_t q = R.colptr[k]; q < R.colptr[k + 1]; ++q) {
+            int64_t d = cur[R.rowidx[q]]++;
+            R.colidx[d] = (int32_t)k;
+            R.rval[d] = R.val[q];
+        }
+}
+
+// [b;h] <- E [b;h], c <- D c (pdhg.jl:74-92)
+inline void scale_vectors(Prep& R) {
+    for (int64_t i = 0; i < R.p; ++i) R.b[i] *= R.Ediag[i];
+    for (int64_t i = 0; i < R.m; ++i) R.h[i] *= R.Ediag[R.p + i];
+    for (int64_t k = 0; k < R.n; ++k) R.c[k] *= R.Ddiag[k];       // (c already carries the sqrt(2)/2 factor: it commutes)
+}
+
+// The part of prepare() a dense A defers: `rs` = row sums of squares of the dense block (p), lo / hi = its smallest and
+// largest entry -- one device pass.  Limit check as in prepare() with the sparse rows (G) and their implicit zeros
+// counted in, the scaling from the row sums, then b, h, c, the sparse values and the CSR once more.
+inline void finish_dense_equilibration(Prep& R, const proxsdp_options& opt, const double* rs, double lo, double hi) {
+    R.equil_deferred = false;
+    bool equil = opt.equilibration != 0;
+    if (equil) {
+        if (R.p == 0 || R.n == 0) hi = lo = 0.0;
+        bool first = R.p == 0 || R.n == 0;
+        for (double v : R.val_orig) {
+            if (first) { hi = lo = v; first = false; }
+            hi = std::max(hi, v); lo = std::min(lo, v);
+        }
+        if (R.nnz < R.m * R.n) { hi = std::max(hi, 0.0); lo = std::min(lo, 0.0); }
+        if (hi == 0.0 || lo / hi <= opt.equilibration_limit) equil = false;
+    }
+    if (opt.equilibration_force) equil = true;
+    if (!equil) return;
+    if (R.Q == 0 || R.n == 0) throw std::invalid_argument("equilibration needs a non-empty M");
+    std::vector<double> rows(R.Q, 0.0);
+    std::copy(rs, rs + R.p, rows.begin());
+    for (int64_t q = 0; q < R.nnz; ++q) rows[R.rowidx[q]] += R.val_orig[q] * R.val_orig[q];
+    double d = 1.0;
+    equilibrate_rowsums(rows.data(), R.Q, R.n, opt, R.Ediag, d);
+    R.Ddiag.assign(R.n, d);
+    R.equilibrated = true;
+    scale_vectors(R);
+    finish_matrix(R);
 }
 
 inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullptr) {
@@ -225,7 +328,10 @@ inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullp
     // ---- diagonal preconditioning (pdhg.jl:64-92): only ever active when forced, or when the
     // smallest and largest entries of M (implicit zeros included) are within `equilibration_limit`
     bool equil = opt != nullptr && opt->equilibration != 0;
-    if (equil) {
+    if (dense && opt != nullptr && (opt->equilibration != 0 || opt->equilibration_force != 0)) {
+        R.equil_deferred = true;                         // decided after the device pass over the dense block
+        equil = false;
+    } else if (equil) {
         double hi = 0.0, lo = 0.0;
         if (R.nnz > 0) {
             hi = lo = R.val_orig[0];
@@ -234,40 +340,15 @@ inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullp
         }
         if (hi == 0.0 || lo / hi <= opt->equilibration_limit) equil = false;
     }
-    if (opt != nullptr && opt->equilibration_force) equil = true;
+    if (opt != nullptr && opt->equilibration_force && !R.equil_deferred) equil = true;
     if (equil) {
-        if (dense || P.reduce_fn != nullptr || P.nccl_comm != nullptr) throw std::domain_error("equilibration with a dense A or a block-sharded solve is not implemented");
+        if (P.reduce_fn != nullptr || P.nccl_comm != nullptr) throw std::domain_error("equilibration with a block-sharded solve is not implemented");
         if (R.Q == 0 || R.n == 0) throw std::invalid_argument("equilibration needs a non-empty M");
         equilibrate_host(R, *opt, R.Ediag, R.Ddiag);
         R.equilibrated = true;
-        for (int64_t i = 0; i < R.p; ++i) R.b[i] *= R.Ediag[i];
-        for (int64_t i = 0; i < R.m; ++i) R.h[i] *= R.Ediag[R.p + i];
-        for (int64_t k = 0; k < P.n; ++k) R.c[k] *= R.Ddiag[k];       // (c already carries the sqrt(2)/2 factor: it commutes)
+        scale_vectors(R);
     }
-    double ss = 0.0;
-    for (int64_t k = 0; k < P.n; ++k) {
-        const double sc = R.offdiag[k] ? cte : 1.0;
-        for (int64_t q = R.colptr[k]; q < R.colptr[k + 1]; ++q) {
-            double v = R.val_orig[q];
-            if (equil) v = R.Ediag[R.rowidx[q]] * v * R.Ddiag[k];
-            R.val[q] = v * sc;
-            ss += R.val[q] * R.val[q];
-        }
-    }
-    R.frob = std::sqrt(ss);
-
-    // ---- CSR of the scaled M (counting sort; column order inside a row ascending)
-    R.rowptr.assign(R.Q + 1, 0);
-    for (int64_t q = 0; q < R.nnz; ++q) R.rowptr[R.rowidx[q] + 1]++;
-    for (int64_t r = 0; r < R.Q; ++r) R.rowptr[r + 1] += R.rowptr[r];
-    R.colidx.resize(R.nnz); R.rval.resize(R.nnz);
-    std::vector<int64_t> cur(R.rowptr.begin(), R.rowptr.end() - 1);
-    for (int64_t k = 0; k < P.n; ++k)
-        for (int64_t q = R.colptr[k]; q < R.colptr[k + 1]; ++q) {
-            int64_t d = cur[R.rowidx[q]]++;
-            R.colidx[d] = (int32_t)k;
-            R.rval[d] = R.val[q];
-        }
+    finish_matrix(R);
     return R;
 }
 

@@ -557,6 +557,8 @@ public:
     double g_n = 0, g_Q = 0, g_p = 0, g_m = 0, g_norm_b = 0, g_norm_h = 0, g_norm_c = 0, g_frob = 0;
     bool g_conic = false, g_not_converged_rank = false, g_any_below_full = false;
     double g_elapsed = 0;
+    bool init_only = false;         // proxsdp_hip_dense_scaling: run() returns after the "Init" section
+    double sigma_max = 0.0;         // what approx_norm = false computed (0 otherwise)
     std::thread warm;               // loads rocSOLVER's code objects while the loop runs
     // concurrent block projections: one worker thread per PSD block (up to 8), each driving its
     // block's Lanczos on the block's own stream
@@ -697,6 +699,13 @@ private:
     int dmv_slices = 1, dmv_qpad = 0;
     static constexpr int DMV_ROWS = 8, DMV_UNR = 4;       // k_dense_mv shape (rows per workgroup, strips in flight)
     long long dense_passes_seen = 0;
+    // equilibration / approx_norm = false on a dense A: set-up on the device (one pass over M: row sums + extrema), scale
+    // vectors E (rows of the dense block) and D o s (columns) for the products, Lanczos for sigma_max
+    void upload_dense();
+    void setup_dense_scaling();
+    double spectral_norm_device();
+    DevBuf<double> drow_d, dcol_d;   // E[0..p), D o s
+    double dense_frob2 = 0.0;        // ||E A D S||_F^2 of the dense block, from the set-up pass's row sums
     std::vector<std::pair<hipEvent_t, hipEvent_t>> dense_ev;   // one pair per pass of the current iteration
     size_t dense_ev_used = 0;
     void dense_ev_begin();
