@@ -52,7 +52,7 @@ extern "C" {
  * (from reserved_s[0]): same struct sizes and offsets, version unchanged;
  * later: equilibration and approx_norm = 0 served with a dense A (proxsdp_hip_dense_scaling, proxsdp_host_equilibrate_rowsums),
  * proxsdp_stats dense_setup_passes / dense_sigma_steps (the last two reserved_s slots): same sizes and offsets, version unchanged */
-#define PROXSDP_HIP_ABI_VERSION 9
+#define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
 #define PROXSDP_E_INVALID  (-1)   /* invalid argument / inconsistent problem data */
@@ -624,6 +624,48 @@ int proxsdp_hip_residuals(const double* x, const double* x_old, const double* Mt
                           const double* c, double tau, int64_t n,
                           const double* y, const double* y_old, const double* Mx, const double* Mx_old,
                           const double* bh, int64_t p, int64_t Q, double sigma, double* out);
+
+/* ONE batch of linesearch candidates (linesearch! / dual_step!, pdhg.jl:532-609, with the reductions of compute_residual! /
+ * compute_gap!, residuals.jl:2-71) through the solver's own launches, on host data.  M = [A;G] (Q x n, CSC in storage order),
+ * rows 0 .. p-1 equalities.  Candidate k takes tau[k], theta[k], bt[k], sigma[k]:
+ *   y+_k = ybar - bt box(ybar / bt), ybar = y + bt ((1 + theta) Mx - theta Mx_old);  plain = 0: stored as (y+ - y) + y and
+ *   (M'y+ - Mty_old) + Mty_old (linesearch!'s in-place norm and revert), plain = 1: as computed (dual_step!).
+ * x is the new iterate, x_old the previous one (weighted by xold_coef in the residual), Mx = M x, Mx_old = M x_old.
+ * support = 1: the support-aware path, S = {i : column i non-empty or c_i != 0}; M'y+ is computed on S only, and
+ * k_primal_update_S runs first on x_old with step tau_update and M'y = Mty_old (x_upd, xsave, esv).
+ * scal: 11 per candidate -- 0 |y+ - y|^2 (rows weighted by roww)  1 |M'y+ - Mty_old|^2  2..4 and 5..10 as out[0..2] and
+ * out[3..8] of proxsdp_hip_residuals (b'y, h'y weighted by roww on the support path).
+ * c0 >= 0: afterwards candidate c0's residuals (slots 2..10) are evaluated again with tau_re / sigma_re into scal_re[11]. */
+typedef struct {
+    int64_t struct_size;
+    /* in */
+    int64_t p;
+    const double* bh; const double* y; const double* Mx; const double* Mx_old;        /* Q each */
+    const double* x; const double* x_old; const double* Mty_old;                      /* n each, as c (an argument of the call) */
+    const double* roww;                  /* Q row weights of a block-sharded solve, or NULL */
+    double xold_coef, tau_update;
+    int32_t support, nc, plain, c0;      /* nc = 1..3; c0 < 0: no re-evaluation */
+    double tau[3], theta[3], bt[3], sigma[3];
+    double tau_re, sigma_re;
+    /* out */
+    double* y_out;                       /* nc x Q */
+    double* Mty_out;                     /* nc x ns, ns = |S| (support) or n; capacity nc x n */
+    double* scal;                        /* nc x 11 */
+    double* scal_re;                     /* 11 (c0 >= 0) */
+    int32_t* supp_out;                   /* support = 1: S ascending, capacity n */
+    double* x_upd; double* xsave; double* esv;   /* support = 1: n, capacity n, capacity 2 n ([2][ns]) */
+    int64_t ns;
+    int32_t gq, gx;                      /* workgroup columns of the y passes and of the x / column passes */
+} proxsdp_trial_batch;
+int proxsdp_hip_trial_batch(const proxsdp_csc* M, int32_t index_base, const double* c, proxsdp_trial_batch* t);
+
+/* The non-PSD tail of the projection on host data (n entries): nsoc second-order cones at soc_off / soc_len (x[off] the
+ * scalar part; soc_projection!, prox_operators.jl:145-158) and n_one 1x1 PSD blocks at one_off (:43-45).  x_soc = x after the
+ * SOC projection, gap_in / gap_out = |v| - s per cone before / after it (residuals.jl:73-86), x_clamp = x_soc after
+ * x = max(0, x) on the 1x1 blocks, min_eig their values. */
+int proxsdp_hip_cone_tail(const double* x, int64_t n, const int64_t* soc_off, const int32_t* soc_len, int32_t nsoc,
+                          const int64_t* one_off, int32_t n_one, double* x_soc, double* gap_in, double* gap_out,
+                          double* x_clamp, double* min_eig);
 
 /* The "Init" section (pdhg.jl:54-142) of a solve with a dense A (prob->M_dense), nothing more: E (p + m) and D (n), the
  * equilibration diagonals -- ones when equilibration is off or switched itself off, *equilibrated says which --, frob =

@@ -226,7 +226,7 @@ def lib():
     L.proxsdp_hip_rccl_unique_id.argtypes = [C.c_void_p]
     L.proxsdp_hip_rccl_comm_init.argtypes = [i32, C.c_void_p, i32, i32, C.POINTER(C.c_void_p)]
     L.proxsdp_hip_rccl_comm_destroy.argtypes = [C.c_void_p]
-    if L.proxsdp_hip_abi_version() != 9:
+    if L.proxsdp_hip_abi_version() != 10:
         raise ProxSDPHipError(-1, "ABI version mismatch")
     _lib = L
     return L
@@ -613,6 +613,84 @@ def spmv(M, x, transpose=False):
     out = np.zeros(M.shape[1] if transpose else M.shape[0])
     _check(L.proxsdp_hip_spmv(C.byref(S), 0, 1 if transpose else 0, _p(xin), _p(out)))
     return out
+
+
+NCAND, NSCAL = 3, 11    # candidates per linesearch batch, scalars per candidate (csrc/pdhg_loop.hip.hpp)
+
+
+class TrialBatchIO(C.Structure):
+    """proxsdp_trial_batch (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("p", i64),
+                ("bh", pf64), ("y", pf64), ("Mx", pf64), ("Mx_old", pf64),
+                ("x", pf64), ("x_old", pf64), ("Mty_old", pf64), ("roww", pf64),
+                ("xold_coef", f64), ("tau_update", f64),
+                ("support", i32), ("nc", i32), ("plain", i32), ("c0", i32),
+                ("tau", f64 * 3), ("theta", f64 * 3), ("bt", f64 * 3), ("sigma", f64 * 3),
+                ("tau_re", f64), ("sigma_re", f64),
+                ("y_out", pf64), ("Mty_out", pf64), ("scal", pf64), ("scal_re", pf64),
+                ("supp_out", C.POINTER(i32)), ("x_upd", pf64), ("xsave", pf64), ("esv", pf64),
+                ("ns", i64), ("gq", i32), ("gx", i32)]
+
+
+def trial_batch(colptr, rowval, nzval, Q, *, p, bh, y, Mx, Mx_old, x, x_old, Mty_old, c, tau, theta, bt, sigma,
+                xold_coef=1.0, support=False, roww=None, plain=False, c0=-1, tau_re=0.0, sigma_re=0.0, tau_update=0.0):
+    """proxsdp_hip_trial_batch: one batch of len(tau) linesearch candidates through the solver's launches.  M (Q x n) is
+    given as raw CSC arrays (0-based) and is used in its storage order.  Returns a dict: y (nc x Q), Mty (nc x ns), scal
+    (nc x 11), gq, gx, and -- c0 >= 0 -- scal_re (11); on the support path also supp, x_upd, xsave, esv (2 x ns)."""
+    cp, rv, nz = _i(colptr), _i(rowval), _f(nzval)
+    n, nc = len(cp) - 1, len(tau)
+    rv1, nz1 = (rv, nz) if len(rv) else (np.zeros(1, dtype=np.int64), np.zeros(1))
+    S = CSC(int(Q), n, _p(cp, pi64), _p(rv1, pi64), _p(nz1))
+    ins = {k: _f(v) for k, v in dict(bh=bh, y=y, Mx=Mx, Mx_old=Mx_old, x=x, x_old=x_old, Mty_old=Mty_old).items()}
+    for k, v in ins.items():
+        assert len(v) == (n if k in ("x", "x_old", "Mty_old") else Q), k
+    cc = _f(c)
+    rw = _f(roww) if roww is not None else None
+    assert len(cc) == n and (rw is None or len(rw) == Q) and 1 <= nc <= NCAND
+    assert len(theta) == len(bt) == len(sigma) == nc
+    t = TrialBatchIO()
+    t.struct_size = C.sizeof(TrialBatchIO)
+    t.p = int(p)
+    for k, v in ins.items():
+        setattr(t, k, _p(v))
+    t.roww = _p(rw) if rw is not None else None
+    t.xold_coef, t.tau_update = float(xold_coef), float(tau_update)
+    t.support, t.nc, t.plain, t.c0 = int(bool(support)), nc, int(bool(plain)), int(c0)
+    for k in range(nc):
+        t.tau[k], t.theta[k], t.bt[k], t.sigma[k] = float(tau[k]), float(theta[k]), float(bt[k]), float(sigma[k])
+    t.tau_re, t.sigma_re = float(tau_re), float(sigma_re)
+    out = dict(y=np.zeros((nc, Q)), Mty=np.zeros(nc * n), scal=np.zeros((nc, NSCAL)), scal_re=np.zeros(NSCAL),
+               supp=np.zeros(n, dtype=np.int32), x_upd=np.zeros(n), xsave=np.zeros(n), esv=np.zeros(2 * n))
+    t.y_out, t.Mty_out, t.scal, t.scal_re = _p(out["y"]), _p(out["Mty"]), _p(out["scal"]), _p(out["scal_re"])
+    t.supp_out, t.x_upd, t.xsave, t.esv = _p(out["supp"], C.POINTER(i32)), _p(out["x_upd"]), _p(out["xsave"]), _p(out["esv"])
+    L = lib()
+    L.proxsdp_hip_trial_batch.argtypes = [C.POINTER(CSC), i32, pf64, C.POINTER(TrialBatchIO)]
+    _check(L.proxsdp_hip_trial_batch(C.byref(S), 0, _p(cc), C.byref(t)))
+    ns = int(t.ns)
+    res = dict(y=out["y"], Mty=out["Mty"][:nc * ns].reshape(nc, ns), scal=out["scal"], gq=int(t.gq), gx=int(t.gx))
+    if c0 >= 0:
+        res["scal_re"] = out["scal_re"]
+    if support:
+        res.update(supp=out["supp"][:ns].copy(), x_upd=out["x_upd"], xsave=out["xsave"][:ns].copy(),
+                   esv=out["esv"][:2 * ns].reshape(2, ns).copy())
+    return res
+
+
+def cone_tail(x, soc_off, soc_len, one_off):
+    """proxsdp_hip_cone_tail: (x after the SOC projection, SOC gap before, SOC gap after, x after the 1x1 clamp, min_eig)"""
+    x = _f(x)
+    so, sl, oo = _i(soc_off), np.ascontiguousarray(soc_len, dtype=np.int32), _i(one_off)
+    ns_, no_ = len(so), len(oo)
+    assert len(sl) == ns_
+    pad = lambda a: a if len(a) else np.zeros(1, dtype=a.dtype)
+    so, sl, oo = pad(so), pad(sl), pad(oo)
+    x_soc, x_cl = np.zeros_like(x), np.zeros_like(x)
+    g0, g1, me = np.zeros(max(ns_, 1)), np.zeros(max(ns_, 1)), np.zeros(max(no_, 1))
+    L = lib()
+    L.proxsdp_hip_cone_tail.argtypes = [pf64, i64, pi64, C.POINTER(i32), i32, pi64, i32, pf64, pf64, pf64, pf64, pf64]
+    _check(L.proxsdp_hip_cone_tail(_p(x), len(x), _p(so, pi64), _p(sl, C.POINTER(i32)), ns_, _p(oo, pi64), no_,
+                                   _p(x_soc), _p(g0), _p(g1), _p(x_cl), _p(me)))
+    return x_soc, g0[:ns_], g1[:ns_], x_cl, me[:no_]
 
 
 def dense_scaling(prob, options=None):

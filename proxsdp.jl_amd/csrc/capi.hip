@@ -415,6 +415,44 @@ int proxsdp_hip_spmv(const proxsdp_csc* M, int32_t index_base, int32_t transpose
     });
 }
 
+int proxsdp_hip_trial_batch(const proxsdp_csc* M, int32_t index_base, const double* c, proxsdp_trial_batch* t) {
+    return guarded([&]() -> int {
+        if (!M || !c || !t) throw std::invalid_argument("NULL argument");
+        if (t->struct_size != (int64_t)sizeof(proxsdp_trial_batch)) throw std::invalid_argument("trial batch: struct_size mismatch");
+        // the same preparation as a solve: M as the equality rows of a problem without cones (test_trial_batch sets p)
+        proxsdp_problem pr{};
+        pr.n = M->ncols; pr.p = M->nrows; pr.m = 0;
+        pr.A = *M;
+        std::vector<int64_t> zc((size_t)M->ncols + 1, index_base);
+        pr.G.nrows = 0; pr.G.ncols = M->ncols; pr.G.colptr = zc.data();
+        std::vector<double> zb((size_t)std::max<int64_t>(M->nrows, 1), 0.0);
+        pr.b = zb.data(); pr.h = zb.data(); pr.c = c;
+        pr.index_base = index_base;
+        proxsdp_options o;
+        proxsdp::default_options(&o);
+        proxsdp_result dummy{};
+        proxsdp::Solver S(pr, o, dummy);
+        S.test_trial_batch(*t);
+        return 0;
+    });
+}
+
+int proxsdp_hip_cone_tail(const double* x, int64_t n, const int64_t* soc_off, const int32_t* soc_len, int32_t nsoc,
+                          const int64_t* one_off, int32_t n_one, double* x_soc, double* gap_in, double* gap_out,
+                          double* x_clamp, double* min_eig) {
+    return guarded([&]() -> int {
+        if (n < 1 || nsoc < 0 || n_one < 0 || !x || !x_soc || !x_clamp || (nsoc > 0 && (!soc_off || !soc_len || !gap_in || !gap_out)) ||
+            (n_one > 0 && (!one_off || !min_eig))) throw std::invalid_argument("invalid argument");
+        for (int32_t k = 0; k < nsoc; ++k)
+            if (soc_len[k] < 1 || soc_off[k] < 0 || soc_off[k] > n - soc_len[k]) throw std::invalid_argument("cone outside x");
+        for (int32_t k = 0; k < n_one; ++k)
+            if (one_off[k] < 0 || one_off[k] >= n) throw std::invalid_argument("1x1 block outside x");
+        Engine E(nullptr, 2, 2);
+        E.S.test_cone_tail(x, n, soc_off, soc_len, nsoc, one_off, n_one, x_soc, gap_in, gap_out, x_clamp, min_eig);
+        return 0;
+    });
+}
+
 int proxsdp_hip_dense_scaling(const proxsdp_problem* prob, const proxsdp_options* opt,
                               double* E, double* D, double* frob, double* sigma_max, int32_t* equilibrated) {
     return guarded([&]() -> int {

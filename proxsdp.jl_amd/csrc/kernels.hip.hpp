@@ -1877,19 +1877,6 @@ __device__ __forceinline__ double col_dot(const LongCols& L, int col, const int*
     return acc;
 }
 
-// plain transposed product (test entry point)
-__global__ void __launch_bounds__(TPB)
-k_spmv_csc(const int* __restrict__ colptr, const int* __restrict__ row, const double* __restrict__ val,
-           const double* __restrict__ y, double* __restrict__ out, long long ncols) {
-    long long j = (long long)blockIdx.x * TPB + threadIdx.x;
-    const long long stride = (long long)gridDim.x * TPB;
-    for (; j < ncols; j += stride) {
-        double acc = 0.0;
-        for (int k = colptr[j]; k < colptr[j + 1]; ++k) acc += val[k] * y[row[k]];
-        out[j] = acc;
-    }
-}
-
 // ---------------------------------------------------------------------------
 // Support-aware variants.  S = {i : column i of M is non-empty or c_i != 0} is fixed for
 // the solve; Mty and c vanish outside S, so  x .-= tau.*(Mty .+ c)  (pdhg.jl:622) only

@@ -460,11 +460,26 @@ inline bool Solver::full_eig_by_lanczos(int idx, const double* xp, double* xo, b
     return false;
 }
 
+// the cone tail's launches: 1x1 PSD blocks (one_off -> one_min), SOC projection and SOC gap (soc_off, soc_len -> soc_gap_d)
+inline void Solver::launch_clamp_scalars(double* x, int cnt) {
+    hipLaunchKernelGGL(dev::k_clamp_scalars, dim3(ceil_div(cnt, 256)), dim3(256), 0, stream, x, one_off.p, cnt, one_min.p);
+}
+inline void Solver::launch_soc_project(double* x, int nsoc) {
+    hipLaunchKernelGGL(dev::k_soc_project, dim3(nsoc), dim3(dev::TPB), 0, stream, x, soc_off.p, soc_len.p);
+}
+inline void Solver::launch_soc_gap(const double* x, int nsoc) {
+    hipLaunchKernelGGL(dev::k_soc_gap, dim3(nsoc), dim3(dev::TPB), 0, stream, x, soc_off.p, soc_len.p, soc_gap_d.p);
+}
+// xsave = x[S]; x[S] -= tau (M'y + c)[S] in place, and the support values of the update for the operator-form mat-vec
+inline void Solver::launch_primal_update_S(double* x, double tau) {
+    hipLaunchKernelGGL(dev::k_primal_update_S, dim3(ceil_div(std::max(ns, 1), dev::TPB)), dim3(dev::TPB), 0, stream,
+                       x, supp_d.p, MtyS_cur.p, cS_d.p, tau, xsave_d.p, ns, esv_d.p);
+}
+
 inline void Solver::psd_projection(double* x) {
     std::fill(min_eig.begin(), min_eig.end(), 0.0);
     if (!one_blocks.empty()) {
-        hipLaunchKernelGGL(dev::k_clamp_scalars, dim3(ceil_div(one_blocks.size(), 256)), dim3(256), 0, stream,
-                           x, one_off.p, (int)one_blocks.size(), one_min.p);
+        launch_clamp_scalars(x, (int)one_blocks.size());
         for (int idx : one_blocks) current_rank[idx] = 0;
     }
     if (!small_blocks.empty()) {
@@ -536,8 +551,7 @@ inline void Solver::primal_step_dev() {
         // is written to the other buffer, so off the support buffer xc still holds x_k = x_old
         double* xcur = xbuf[xc].p;
         double* xnew = xbuf[1 - xc].p;
-        hipLaunchKernelGGL(dev::k_primal_update_S, dim3(ceil_div(std::max(ns, 1), dev::TPB)), dim3(dev::TPB), 0, stream,
-                           xcur, supp_d.p, MtyS_cur.p, cS_d.p, primal_step, xsave_d.p, ns, esv_d.p);
+        launch_primal_update_S(xcur, primal_step);
         std::fill(min_eig.begin(), min_eig.end(), 0.0);
         double t0 = now_s();
         // block-sharded solve: a shard whose projection fails (e.g. non-finite input) must still join this
@@ -570,9 +584,7 @@ inline void Solver::primal_step_dev() {
         psd_projection(xo);
         st.t_psd += now_s() - t0;
     }
-    if (!P.socs.empty())
-        hipLaunchKernelGGL(dev::k_soc_project, dim3((int)P.socs.size()), dim3(dev::TPB), 0, stream,
-                           xo, soc_off.p, soc_len.p);
+    if (!P.socs.empty()) launch_soc_project(xo, (int)P.socs.size());
     spmv(xo, Mxbuf[1 - mxc].p);
 }
 
@@ -627,6 +639,97 @@ inline void Solver::reduce_candidates(int nc) {
     g_elapsed = maxs[mi++];
 }
 
+// ---- one batch of linesearch candidates: the launches (shared with the kernel-level test entry, test_trial_batch)
+// the batch's launch shapes: one workgroup column per 256 entries of y (gq) and of the support or every column (gx), capped at
+// PSTRIDE (the kernels stride over the rest); the candidates' slices of ycand_d / Mtycand_d / bpart
+inline Solver::BatchShape Solver::batch_shape() const {
+    BatchShape b;
+    b.gq = std::min(PSTRIDE, grid_for(std::max<int64_t>(P.Q, 1)));
+    b.gx = std::min(PSTRIDE, grid_for(use_support ? std::max<int64_t>(ns, 1) : P.n));   // the support, or every column
+    b.cstride = (long long)NSCAL * PSTRIDE;
+    b.ystride = std::max<int64_t>(P.Q, 1);
+    b.mstride = use_support ? std::max<int64_t>(ns, 1) : P.n;
+    return b;
+}
+// residual / gap reductions of candidates c0 .. c0 + nc - 1 (their partials land in the records 0 .. nc - 1)
+inline void Solver::batch_residuals(const dev::TrialBatch& tb, int nc, int c0, double xold_coef) {
+    const BatchShape b = batch_shape();
+    const int gq = b.gq, gx = b.gx;
+    const long long cstride = b.cstride, ystride = b.ystride, mstride = b.mstride;
+    double* mty_cur = use_support ? MtyS_cur.p : Mtybuf[mtyc].p;
+    const double* roww = roww_d.p;
+    const double* yc0 = ycand_d.p + (size_t)c0 * ystride;
+    const double* mc0 = Mtycand_d.p + (size_t)c0 * mstride;
+    if (use_support)
+        hipLaunchKernelGGL(dev::k_residual_xy_batch, dim3(std::max(gx, gq), nc, 2), dim3(dev::TPB), 0, stream,
+                           xbuf[1 - xc].p, supp_d.p, ns, xsave_d.p, xold_coef, mc0, mstride, mty_cur, cS_d.p, gx,
+                           yc0, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, gq,
+                           tb, bpart.p, PSTRIDE, cstride, roww);
+    else
+        hipLaunchKernelGGL(dev::k_residual_xy_full_batch, dim3(std::max(gx, gq), nc, 2), dim3(dev::TPB), 0, stream,
+                           xbuf[1 - xc].p, xbuf[xc].p, xold_coef, mc0, mstride, mty_cur, c_d.p, (long long)P.n, gx,
+                           yc0, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, gq,
+                           tb, bpart.p, PSTRIDE, cstride);
+}
+// y+, M'y+ and their norms for nc candidates, then their residuals
+// (the vector paths differ only in the launches that compute M'y+ and the residuals)
+inline void Solver::batch_evaluate(const dev::TrialBatch& tb, int nc, double xold_coef) {
+    const BatchShape b = batch_shape();
+    const int gq = b.gq;
+    const long long cstride = b.cstride, ystride = b.ystride;
+    hipLaunchKernelGGL(dev::k_dual_trial_batch, dim3(gq, nc), dim3(dev::TPB), 0, stream,
+                       ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, tb,
+                       ycand_d.p, ystride, bpart.p, cstride, roww_d.p);
+    batch_mty(tb, nc);
+    batch_residuals(tb, nc, 0, xold_coef);
+}
+// M'y_c of the candidates in ycand_d + |M'y_c - M'y_old|^2 partials
+inline void Solver::batch_mty(const dev::TrialBatch& tb, int nc) {
+    const BatchShape b = batch_shape();
+    const int gx = b.gx;
+    const long long cstride = b.cstride, ystride = b.ystride, mstride = b.mstride;
+    double* mty_cur = use_support ? MtyS_cur.p : Mtybuf[mtyc].p;
+    if (use_support)
+        hipLaunchKernelGGL(dev::k_spmvT_S_batch, dim3(gx, nc), dim3(dev::TPB), 0, stream,
+                           csc_ptr.p, csc_row.p, csc_val.p, supp_d.p, ns, ycand_d.p, ystride,
+                           Mtycand_d.p, mstride, mty_cur, bpart.p + PSTRIDE, cstride, tb.plain);
+    else if (P.dense())
+        dense_mtv(nc, ycand_d.p, ystride, true, Mtycand_d.p, mstride, mty_cur, nullptr, bpart.p + PSTRIDE, cstride, !tb.plain);
+    else
+        hipLaunchKernelGGL(dev::k_spmv_csc_norm_batch, dim3(gx, nc), dim3(dev::TPB), 0, stream,
+                           csc_ptr.p, csc_row.p, csc_val.p, ycand_d.p, ystride, Mtycand_d.p, mstride, mty_cur,
+                           (long long)P.n, bpart.p + PSTRIDE, cstride, tb.plain);
+}
+// the scalar record: NSCAL per candidate, then (support path) the two off-support residual maxima that the fused
+// reconstruction reduced -- independent of the candidate, combined by two extra workgroups.  Returns the record.
+inline const double* Solver::batch_read_back(int nc) {
+    const BatchShape b = batch_shape();
+    const int gq = b.gq, gx = b.gx;
+    unsigned long long ismax = 0;
+    for (int c = 0; c < nc; ++c) ismax |= 0x1ECull << (NSCAL * c);      // bits 2,3,5,6,7,8 of every candidate
+    if (use_support) {
+        // (measured, tools/_ab in round 5: letting this kernel write its scalars straight into pinned host memory -- as the
+        // small-model path does -- costs the rank-63 iteration 3 %: a kernel that stores to host memory ends with a system-scope
+        // release, and behind the reconstruction that means writing 64 MB of dirty L2 lines back first)
+        hipLaunchKernelGGL(dev::k_combine_multi, dim3(nc * NSCAL + 2), dim3(dev::TPB), 0, stream,
+                           (const double*)bpart.p, PSTRIDE, std::max(gq, gx), ismax, bscal.p, nc * NSCAL,
+                           (const double*)respart_d.p, rstride, n_res_wg, bscal.p + NCAND * NSCAL);
+        PX_HIP(hipMemcpyAsync(hbscal.data(), bscal.p, (NCAND * NSCAL + 2) * sizeof(double), hipMemcpyDeviceToHost, stream));
+        wait_stream();
+        reduce_candidates(nc);
+        return hbscal.data();
+    }
+    // small models: the scalars go STRAIGHT into pinned host memory (no copy launch: 6 us of a 60 us iteration); larger ones keep
+    // the copy (a kernel that stores to host memory ends with a system-scope release of everything the iteration left dirty)
+    const bool zc = zero_copy_small();
+    hipLaunchKernelGGL(dev::k_combine_multi, dim3(nc * NSCAL), dim3(dev::TPB), 0, stream,
+                       (const double*)bpart.p, PSTRIDE, std::max(gq, gx), ismax, zc ? hscal_pin.p : bscal.p, nc * NSCAL,
+                       (const double*)nullptr, 0, 0, (double*)nullptr);
+    if (!zc) PX_HIP(hipMemcpyAsync(hscal_pin.p, bscal.p, NCAND * NSCAL * sizeof(double), hipMemcpyDeviceToHost, stream));
+    wait_stream();
+    return hscal_pin.p;
+}
+
 // Up to NCAND consecutive step-size candidates tau, 0.75 tau, 0.75^2 tau are evaluated by ONE batch of launches -- y+, M'y+ and
 // their norms, then the residual / gap reductions, pure reductions over each candidate's y and M'y -- and ONE read-back; the host
 // takes the first candidate the reference's loop would have accepted.  Per candidate the arithmetic is that of a batch of one, so
@@ -635,71 +738,9 @@ inline void Solver::reduce_candidates(int nc) {
 // Returns the accepted candidate's scalar record.
 inline const double* Solver::linesearch_and_residuals() {
     const int ncmax = opt.general_batch != 0 ? NCAND : 1;
-    const int gq = std::min(PSTRIDE, grid_for(std::max<int64_t>(P.Q, 1)));
-    const int gx = std::min(PSTRIDE, grid_for(use_support ? std::max<int64_t>(ns, 1) : P.n));   // the support, or every column
-    const long long cstride = (long long)NSCAL * PSTRIDE;
-    const long long ystride = std::max<int64_t>(P.Q, 1), mstride = use_support ? std::max<int64_t>(ns, 1) : P.n;
+    const long long ystride = batch_shape().ystride, mstride = batch_shape().mstride;
     const double xold_coef = (iter == 1 && opt.advanced_initialization) ? 0.0 : 1.0;   // x_old = 0 at k = 1
-    double* mty_cur = use_support ? MtyS_cur.p : Mtybuf[mtyc].p;
-    const double* roww = roww_d.p;
-    auto residuals = [&](const dev::TrialBatch& tb, int nc, int c0) {        // candidates c0 .. c0 + nc - 1
-        const double* yc0 = ycand_d.p + (size_t)c0 * ystride;
-        const double* mc0 = Mtycand_d.p + (size_t)c0 * mstride;
-        if (use_support)
-            hipLaunchKernelGGL(dev::k_residual_xy_batch, dim3(std::max(gx, gq), nc, 2), dim3(dev::TPB), 0, stream,
-                               xbuf[1 - xc].p, supp_d.p, ns, xsave_d.p, xold_coef, mc0, mstride, mty_cur, cS_d.p, gx,
-                               yc0, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, gq,
-                               tb, bpart.p, PSTRIDE, cstride, roww);
-        else
-            hipLaunchKernelGGL(dev::k_residual_xy_full_batch, dim3(std::max(gx, gq), nc, 2), dim3(dev::TPB), 0, stream,
-                               xbuf[1 - xc].p, xbuf[xc].p, xold_coef, mc0, mstride, mty_cur, c_d.p, (long long)P.n, gx,
-                               yc0, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, gq,
-                               tb, bpart.p, PSTRIDE, cstride);
-    };
-    // (the vector paths differ only in the launches that compute M'y+ and the residuals)
-    auto evaluate = [&](const dev::TrialBatch& tb, int nc) {
-        hipLaunchKernelGGL(dev::k_dual_trial_batch, dim3(gq, nc), dim3(dev::TPB), 0, stream,
-                           ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, tb,
-                           ycand_d.p, ystride, bpart.p, cstride, roww);
-        if (use_support)
-            hipLaunchKernelGGL(dev::k_spmvT_S_batch, dim3(gx, nc), dim3(dev::TPB), 0, stream,
-                               csc_ptr.p, csc_row.p, csc_val.p, supp_d.p, ns, ycand_d.p, ystride,
-                               Mtycand_d.p, mstride, mty_cur, bpart.p + PSTRIDE, cstride, tb.plain);
-        else if (P.dense())
-            dense_mtv(nc, ycand_d.p, ystride, true, Mtycand_d.p, mstride, mty_cur, nullptr, bpart.p + PSTRIDE, cstride, !tb.plain);
-        else
-            hipLaunchKernelGGL(dev::k_spmv_csc_norm_batch, dim3(gx, nc), dim3(dev::TPB), 0, stream,
-                               csc_ptr.p, csc_row.p, csc_val.p, ycand_d.p, ystride, Mtycand_d.p, mstride, mty_cur,
-                               (long long)P.n, bpart.p + PSTRIDE, cstride, tb.plain);
-        residuals(tb, nc, 0);
-    };
-    // the scalar record: NSCAL per candidate, then (support path) the two off-support residual maxima that the fused
-    // reconstruction reduced -- independent of the candidate, combined by two extra workgroups
-    const double* rec = use_support ? hbscal.data() : hscal_pin.p;
-    auto read_back = [&](int nc) {
-        unsigned long long ismax = 0;
-        for (int c = 0; c < nc; ++c) ismax |= 0x1ECull << (NSCAL * c);      // bits 2,3,5,6,7,8 of every candidate
-        if (use_support) {
-            // (measured, tools/_ab in round 5: letting this kernel write its scalars straight into pinned host memory -- as the
-            // small-model path does -- costs the rank-63 iteration 3 %: a kernel that stores to host memory ends with a system-scope
-            // release, and behind the reconstruction that means writing 64 MB of dirty L2 lines back first)
-            hipLaunchKernelGGL(dev::k_combine_multi, dim3(nc * NSCAL + 2), dim3(dev::TPB), 0, stream,
-                               (const double*)bpart.p, PSTRIDE, std::max(gq, gx), ismax, bscal.p, nc * NSCAL,
-                               (const double*)respart_d.p, rstride, n_res_wg, bscal.p + NCAND * NSCAL);
-            PX_HIP(hipMemcpyAsync(hbscal.data(), bscal.p, (NCAND * NSCAL + 2) * sizeof(double), hipMemcpyDeviceToHost, stream));
-            wait_stream();
-            reduce_candidates(nc);
-            return;
-        }
-        // small models: the scalars go STRAIGHT into pinned host memory (no copy launch: 6 us of a 60 us iteration); larger ones keep
-        // the copy (a kernel that stores to host memory ends with a system-scope release of everything the iteration left dirty)
-        const bool zc = zero_copy_small();
-        hipLaunchKernelGGL(dev::k_combine_multi, dim3(nc * NSCAL), dim3(dev::TPB), 0, stream,
-                           (const double*)bpart.p, PSTRIDE, std::max(gq, gx), ismax, zc ? hscal_pin.p : bscal.p, nc * NSCAL,
-                           (const double*)nullptr, 0, 0, (double*)nullptr);
-        if (!zc) PX_HIP(hipMemcpyAsync(hscal_pin.p, bscal.p, NCAND * NSCAL * sizeof(double), hipMemcpyDeviceToHost, stream));
-        wait_stream();
-    };
+    const double* rec = nullptr;
     auto commit = [&](int c) {                           // y <- y_c, M'y <- M'y_c (one launch)
         const long long nm = use_support ? ns : P.n;
         hipLaunchKernelGGL(dev::k_copy2, dim3(grid_for((long long)P.Q + nm)), dim3(dev::TPB), 0, stream,
@@ -723,8 +764,8 @@ inline const double* Solver::linesearch_and_residuals() {
         }
         if (!ls) { nc = 1; tb.tau[0] = primal_step; tb.theta[0] = 1.0; tb.bt[0] = dual_step; tb.sigma[0] = dual_step; tb.plain = 1; }
         tb.nc = nc;
-        evaluate(tb, nc);
-        read_back(nc);
+        batch_evaluate(tb, nc, xold_coef);
+        rec = batch_read_back(nc);
         for (int c = 0; c < nc && s_acc == nullptr; ++c) {
             ++trials;
             const double* sc = rec + NSCAL * c;
@@ -745,8 +786,8 @@ inline const double* Solver::linesearch_and_residuals() {
                     dev::TrialBatch t1{};
                     t1.nc = 1; t1.tau[0] = primal_step; t1.theta[0] = theta; t1.bt[0] = beta * primal_step;
                     t1.sigma[0] = beta * primal_step;
-                    residuals(t1, 1, c);
-                    read_back(1);
+                    batch_residuals(t1, 1, c, xold_coef);
+                    rec = batch_read_back(1);
                     sc = rec;                            // (its two norms, slots 0 and 1, are not read any more)
                 }
             }
@@ -801,8 +842,7 @@ inline bool Solver::convergedrank() const {
 // soc_convergence (residuals.jl:73-86)
 inline bool Solver::soc_convergence() {
     if (P.socs.empty()) return true;
-    hipLaunchKernelGGL(dev::k_soc_gap, dim3((int)P.socs.size()), dim3(dev::TPB), 0, stream,
-                       xbuf[xc].p, soc_off.p, soc_len.p, soc_gap_d.p);
+    launch_soc_gap(xbuf[xc].p, (int)P.socs.size());
     std::vector<double> g(P.socs.size());
     soc_gap_d.download(g.data(), g.size(), stream);
     PX_HIP(hipStreamSynchronize(stream));
@@ -1210,15 +1250,15 @@ inline void Solver::dense_mtv(int nc, const double* Y, long long ystride, bool s
 }
 
 // ---- support-aware path
-inline void Solver::setup_support() {
-    use_support = false;
-    // (without linesearch the support path runs on request -- support_path = 1 -- and inside a block-sharded solve, which is built on it)
-    if (opt.support_path == 0 || (!opt.line_search_flag && opt.support_path < 0)) return;
-    if (!P.socs.empty() || !one_blocks.empty() || P.blocks.empty()) return;
+// S = {i : column i of M is non-empty or c_i != 0}, ascending
+inline std::vector<int> Solver::support_list() const {
     std::vector<int> supp;
     for (int64_t k = 0; k < P.n; ++k)
         if (P.colptr[k + 1] > P.colptr[k] || P.c[k] != 0.0) supp.push_back((int)k);
-    if (opt.support_path < 0 && (8 * (int64_t)supp.size() > P.n || P.n < 4096)) return;   // auto: only when it pays
+    return supp;
+}
+// the support's device vectors: the list, its bit mask, c on S, and the buffers k_primal_update_S writes
+inline void Solver::upload_support(const std::vector<int>& supp) {
     ns = (int)supp.size();
     std::vector<unsigned> mask((size_t)(P.n + 31) / 32 + 1, 0u);
     std::vector<double> cS(std::max(ns, 1), 0.0);
@@ -1228,6 +1268,17 @@ inline void Solver::setup_support() {
     supp_d.upload(supp.data(), ns, stream); mask_d.upload(mask.data(), mask.size(), stream);
     cS_d.upload(cS.data(), ns, stream);
     MtyS_cur.zero(stream); xsave_d.zero(stream);
+    esv_d.alloc((size_t)2 * std::max(ns, 1)); esv_d.zero(stream);
+    PX_HIP(hipStreamSynchronize(stream));                 // host vectors go out of scope
+}
+inline void Solver::setup_support() {
+    use_support = false;
+    // (without linesearch the support path runs on request -- support_path = 1 -- and inside a block-sharded solve, which is built on it)
+    if (opt.support_path == 0 || (!opt.line_search_flag && opt.support_path < 0)) return;
+    if (!P.socs.empty() || !one_blocks.empty() || P.blocks.empty()) return;
+    const std::vector<int> supp = support_list();
+    if (opt.support_path < 0 && (8 * (int64_t)supp.size() > P.n || P.n < 4096)) return;   // auto: only when it pays
+    upload_support(supp);
     // residual partial slots: one per reconstruction tile of every block + the tail workgroups
     tile_base.clear();
     int base = 0;
@@ -1242,7 +1293,6 @@ inline void Solver::setup_support() {
     rstride = base;
     respart_d.alloc((size_t)2 * std::max(base, 1)); respart_d.zero(stream);
     // operator-form mat-vec: the support update as a symmetric sparse matrix per block (ELL)
-    esv_d.alloc((size_t)2 * std::max(ns, 1)); esv_d.zero(stream);
     if (opt.lanczos_operator != 0) {
         size_t s0 = 0;
         for (size_t idx = 0; idx < P.blocks.size(); ++idx) {
@@ -1321,33 +1371,150 @@ inline void Solver::setup_support() {
     use_support = true;
 }
 
+// sparse operator on the device, both orientations, int32 indices
+inline void Solver::upload_sparse_operator() {
+    std::vector<int> rp(P.Q + 1), cp(P.n + 1);
+    // (prepare() guarantees n, Q, nnz < 2^31: the casts below cannot truncate)
+    for (int64_t i = 0; i <= P.Q; ++i) rp[i] = (int)P.rowptr[i];
+    for (int64_t i = 0; i <= P.n; ++i) cp[i] = (int)P.colptr[i];
+    csr_ptr.alloc(P.Q + 1); csr_col.alloc(std::max<int64_t>(P.nnz, 1)); csr_val.alloc(std::max<int64_t>(P.nnz, 1));
+    csc_ptr.alloc(P.n + 1); csc_row.alloc(std::max<int64_t>(P.nnz, 1)); csc_val.alloc(std::max<int64_t>(P.nnz, 1));
+    csr_ptr.upload(rp.data(), P.Q + 1, stream); csc_ptr.upload(cp.data(), P.n + 1, stream);
+    csr_col.upload(P.colidx.data(), P.nnz, stream); csr_val.upload(P.rval.data(), P.nnz, stream);
+    csc_row.upload(P.rowidx.data(), P.nnz, stream); csc_val.upload(P.val.data(), P.nnz, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    csr_wave = P.Q > 0 && (double)P.nnz / (double)P.Q > 8.0;
+    setup_long_rows(rp);
+}
+
 // ---- hooks for the kernel-level test entry points
 inline void Solver::test_project(int idx, double* xp, int tr) {
     target_rank.assign(1, tr); current_rank.assign(1, 0); min_eig.assign(1, 0.0);
     iter = 1;
     project_block(idx, xp - P.blocks[idx].off, xp - P.blocks[idx].off, false);
 }
+// the iterate's buffers as the "Init" section allocates them (x, M'y: n; y, Mx: Q; two of each), zeroed
+inline void Solver::test_alloc_iterate() {
+    for (int k = 0; k < 2; ++k) {
+        xbuf[k].alloc(P.n); Mtybuf[k].alloc(P.n);
+        ybuf[k].alloc(std::max<int64_t>(P.Q, 1)); Mxbuf[k].alloc(std::max<int64_t>(P.Q, 1));
+        xbuf[k].zero(stream); Mtybuf[k].zero(stream); ybuf[k].zero(stream); Mxbuf[k].zero(stream);
+    }
+    xc = yc = mxc = mtyc = 0;
+}
 inline void Solver::test_spmv(bool transpose, const double* in, double* out) {
     setup_device();
-    std::vector<int> rp(P.Q + 1), cp(P.n + 1);
-    for (int64_t i = 0; i <= P.Q; ++i) rp[i] = (int)P.rowptr[i];
-    for (int64_t i = 0; i <= P.n; ++i) cp[i] = (int)P.colptr[i];
-    const int64_t nz = std::max<int64_t>(P.nnz, 1);
-    csr_ptr.alloc(P.Q + 1); csr_col.alloc(nz); csr_val.alloc(nz);
-    csc_ptr.alloc(P.n + 1); csc_row.alloc(nz); csc_val.alloc(nz);
-    csr_ptr.upload(rp.data(), P.Q + 1, stream); csc_ptr.upload(cp.data(), P.n + 1, stream);
-    csr_col.upload(P.colidx.data(), P.nnz, stream); csr_val.upload(P.rval.data(), P.nnz, stream);
-    csc_row.upload(P.rowidx.data(), P.nnz, stream); csc_val.upload(P.val.data(), P.nnz, stream);
-    csr_wave = P.Q > 0 && (double)P.nnz / (double)P.Q > 8.0;
-    setup_long_rows(rp);
-    DevBuf<double> xin(std::max<int64_t>(transpose ? P.Q : P.n, 1)), xout(std::max<int64_t>(transpose ? P.n : P.Q, 1));
-    xin.upload(in, transpose ? P.Q : P.n, stream);
-    if (transpose)
-        hipLaunchKernelGGL(dev::k_spmv_csc, dim3(grid_for(P.n)), dim3(dev::TPB), 0, stream,
-                           csc_ptr.p, csc_row.p, csc_val.p, xin.p, xout.p, (long long)P.n);
-    else
+    upload_sparse_operator();
+    if (transpose) {
+        // M'y as the linesearch computes it: ONE plain candidate against a zero M'y_old
+        test_alloc_iterate();
+        use_support = false;
+        alloc_candidates();
+        ycand_d.upload(in, P.Q, stream);
+        dev::TrialBatch tb{};
+        tb.nc = 1; tb.plain = 1;
+        batch_mty(tb, 1);
+        Mtycand_d.download(out, P.n, stream);
+    } else {
+        DevBuf<double> xin(std::max<int64_t>(P.n, 1)), xout(std::max<int64_t>(P.Q, 1));
+        xin.upload(in, P.n, stream);
         spmv(xin.p, xout.p);
-    xout.download(out, transpose ? P.n : P.Q, stream);
+        xout.download(out, P.Q, stream);
+    }
+    PX_HIP(hipStreamSynchronize(stream));
+}
+// one batch of the linesearch on host data (include/proxsdp_hip.h proxsdp_trial_batch).  The problem was prepared with every
+// row of M as an equality row (no cones: columns keep their order and their storage order); p is set here.
+inline void Solver::test_trial_batch(proxsdp_trial_batch& t) {
+    const int64_t n = P.n, Q = P.Q;
+    if (n < 1 || Q < 1 || t.p < 0 || t.p > Q || t.nc < 1 || t.nc > NCAND || t.c0 >= t.nc)
+        throw std::invalid_argument("trial batch: n, Q >= 1, 0 <= p <= Q, 1 <= nc <= 3, c0 < nc");
+    if (!t.bh || !t.y || !t.Mx || !t.Mx_old || !t.x || !t.x_old || !t.Mty_old || !t.y_out || !t.Mty_out || !t.scal ||
+        (t.c0 >= 0 && !t.scal_re) || (t.support && (!t.supp_out || !t.x_upd || !t.xsave || !t.esv)))
+        throw std::invalid_argument("trial batch: NULL array");
+    P.p = t.p; P.m = Q - t.p;
+    setup_device();
+    upload_sparse_operator();
+    test_alloc_iterate();
+    c_d.alloc(n); c_d.upload(P.c.data(), n, stream);
+    bh_d.alloc(Q); bh_d.upload(t.bh, Q, stream);
+    if (t.roww) { roww_d.alloc(Q); roww_d.upload(t.roww, Q, stream); }
+    ybuf[yc].upload(t.y, Q, stream);
+    Mxbuf[1 - mxc].upload(t.Mx, Q, stream); Mxbuf[mxc].upload(t.Mx_old, Q, stream);
+    xbuf[xc].upload(t.x_old, n, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    use_support = t.support != 0;
+    if (use_support) {
+        const std::vector<int> supp = support_list();
+        upload_support(supp);
+        n_res_wg = 0; rstride = 0;                       // (no reconstruction ran: no off-support partials)
+        respart_d.alloc(2); respart_d.zero(stream);
+        std::vector<double> mtyS(std::max(ns, 1), 0.0);
+        for (int s = 0; s < ns; ++s) mtyS[s] = t.Mty_old[supp[s]];
+        MtyS_cur.upload(mtyS.data(), ns, stream);
+        // primal_step!'s update on the support, in place on x_old; the new iterate (what the projection would write) is t.x
+        launch_primal_update_S(xbuf[xc].p, t.tau_update);
+        xbuf[xc].download(t.x_upd, n, stream);
+        xsave_d.download(t.xsave, ns, stream);
+        esv_d.download(t.esv, (size_t)2 * ns, stream);
+        std::copy(supp.begin(), supp.end(), t.supp_out);
+        PX_HIP(hipStreamSynchronize(stream));
+    } else {
+        Mtybuf[mtyc].upload(t.Mty_old, n, stream);
+    }
+    t.ns = use_support ? ns : n;
+    xbuf[1 - xc].upload(t.x, n, stream);
+    alloc_candidates();
+    dev::TrialBatch tb{};
+    tb.nc = t.nc; tb.plain = t.plain;
+    for (int c = 0; c < t.nc; ++c) { tb.tau[c] = t.tau[c]; tb.theta[c] = t.theta[c]; tb.bt[c] = t.bt[c]; tb.sigma[c] = t.sigma[c]; }
+    batch_evaluate(tb, t.nc, t.xold_coef);
+    const double* rec = batch_read_back(t.nc);
+    std::copy(rec, rec + (size_t)t.nc * NSCAL, t.scal);
+    const BatchShape b = batch_shape();
+    t.gq = b.gq; t.gx = b.gx;
+    for (int c = 0; c < t.nc; ++c) {
+        PX_HIP(hipMemcpyAsync(t.y_out + (size_t)c * Q, ycand_d.p + (size_t)c * b.ystride, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (t.ns > 0)
+            PX_HIP(hipMemcpyAsync(t.Mty_out + (size_t)c * t.ns, Mtycand_d.p + (size_t)c * b.mstride, (size_t)t.ns * sizeof(double), hipMemcpyDeviceToHost, stream));
+    }
+    PX_HIP(hipStreamSynchronize(stream));
+    if (t.c0 >= 0) {                                     // the re-evaluation leg: candidate c0's residuals with the final steps
+        dev::TrialBatch t1{};
+        t1.nc = 1; t1.tau[0] = t.tau_re; t1.theta[0] = t.theta[t.c0]; t1.bt[0] = t.sigma_re; t1.sigma[0] = t.sigma_re;
+        batch_residuals(t1, 1, t.c0, t.xold_coef);
+        rec = batch_read_back(1);
+        std::copy(rec, rec + NSCAL, t.scal_re);
+    }
+}
+// the cone tail on host data: SOC gap, SOC projection, SOC gap again, then the 1x1 PSD blocks (disjoint entries)
+inline void Solver::test_cone_tail(const double* x, int64_t n, const int64_t* so, const int32_t* sl, int nsoc,
+                                   const int64_t* oo, int none, double* x_soc, double* gap_in, double* gap_out,
+                                   double* x_clamp, double* mineig) {
+    DevBuf<double> xd(std::max<int64_t>(n, 1));
+    xd.upload(x, n, stream);
+    if (nsoc > 0) {
+        std::vector<long long> off(so, so + nsoc);
+        std::vector<int> len(sl, sl + nsoc);
+        soc_off.alloc(nsoc); soc_len.alloc(nsoc); soc_gap_d.alloc(nsoc);
+        soc_off.upload(off.data(), nsoc, stream); soc_len.upload(len.data(), nsoc, stream);
+        launch_soc_gap(xd.p, nsoc);
+        soc_gap_d.download(gap_in, nsoc, stream);
+        launch_soc_project(xd.p, nsoc);
+        launch_soc_gap(xd.p, nsoc);
+        soc_gap_d.download(gap_out, nsoc, stream);
+        PX_HIP(hipStreamSynchronize(stream));            // host vectors go out of scope
+    }
+    xd.download(x_soc, n, stream);
+    if (none > 0) {
+        std::vector<long long> off(oo, oo + none);
+        one_off.alloc(none); one_min.alloc(none);
+        one_off.upload(off.data(), none, stream);
+        launch_clamp_scalars(xd.p, none);
+        one_min.download(mineig, none, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+    }
+    xd.download(x_clamp, n, stream);
     PX_HIP(hipStreamSynchronize(stream));
 }
 
@@ -1520,20 +1687,7 @@ inline void Solver::run() {
     }
     part.alloc((size_t)NQ * PSTRIDE); part.zero(stream);
     scal.alloc(NQ); scal.zero(stream);
-    {   // sparse operator, both orientations, int32 indices
-        std::vector<int> rp(P.Q + 1), cp(P.n + 1);
-        // (prepare() guarantees n, Q, nnz < 2^31: the casts below cannot truncate)
-        for (int64_t i = 0; i <= P.Q; ++i) rp[i] = (int)P.rowptr[i];
-        for (int64_t i = 0; i <= P.n; ++i) cp[i] = (int)P.colptr[i];
-        csr_ptr.alloc(P.Q + 1); csr_col.alloc(std::max<int64_t>(P.nnz, 1)); csr_val.alloc(std::max<int64_t>(P.nnz, 1));
-        csc_ptr.alloc(P.n + 1); csc_row.alloc(std::max<int64_t>(P.nnz, 1)); csc_val.alloc(std::max<int64_t>(P.nnz, 1));
-        csr_ptr.upload(rp.data(), P.Q + 1, stream); csc_ptr.upload(cp.data(), P.n + 1, stream);
-        csr_col.upload(P.colidx.data(), P.nnz, stream); csr_val.upload(P.rval.data(), P.nnz, stream);
-        csc_row.upload(P.rowidx.data(), P.nnz, stream); csc_val.upload(P.val.data(), P.nnz, stream);
-        PX_HIP(hipStreamSynchronize(stream));
-        csr_wave = P.Q > 0 && (double)P.nnz / (double)P.Q > 8.0;
-        setup_long_rows(rp);
-    }
+    upload_sparse_operator();
     eig.resize(nb);
     // small blocks by the sign function in one launch: auto (and small_block_batch = 2) unless the tiled sign projection is
     // switched off or the solve asks for tolerances below that engine's 1e-10-of-the-scale floor (as full_eig_by_sign)

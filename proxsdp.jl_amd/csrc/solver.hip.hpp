@@ -432,6 +432,10 @@ public:
     long long test_rank() const { return current_rank.empty() ? 0 : current_rank[0]; }
     double test_min_eig() const { return min_eig.empty() ? 0.0 : min_eig[0]; }
     void test_spmv(bool transpose, const double* in, double* out);
+    void test_trial_batch(proxsdp_trial_batch& t);
+    void test_cone_tail(const double* x, int64_t n, const int64_t* so, const int32_t* sl, int nsoc,
+                        const int64_t* oo, int none, double* x_soc, double* gap_in, double* gap_out,
+                        double* x_clamp, double* mineig);
 
     bool debug = std::getenv("PROXSDP_HIP_DEBUG") != nullptr;
     proxsdp_options opt;
@@ -641,7 +645,22 @@ private:
     bool batch_eligible(int idx, bool fuse) const;
     void setup_support();
     void setup_dense();
+    std::vector<int> support_list() const;
+    void upload_support(const std::vector<int>& supp);
+    void upload_sparse_operator();
+    void test_alloc_iterate();
+    void launch_clamp_scalars(double* x, int cnt);
+    void launch_soc_project(double* x, int nsoc);
+    void launch_soc_gap(const double* x, int nsoc);
+    void launch_primal_update_S(double* x, double tau);
     void alloc_candidates();
+    // one batch of linesearch candidates (pdhg_loop.hip.hpp): launch shapes, the launches, the read-back
+    struct BatchShape { int gq, gx; long long cstride, ystride, mstride; };
+    BatchShape batch_shape() const;
+    void batch_evaluate(const dev::TrialBatch& tb, int nc, double xold_coef);
+    void batch_mty(const dev::TrialBatch& tb, int nc);
+    void batch_residuals(const dev::TrialBatch& tb, int nc, int c0, double xold_coef);
+    const double* batch_read_back(int nc);
     const double* linesearch_and_residuals();
     void reduce_candidates(int nc);
     void record_residuals(const double* s);

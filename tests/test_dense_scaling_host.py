@@ -47,5 +47,5 @@ def test_dense_scaling_stats_took_the_last_reserved_slots():
     assert B.Stats.reserved_s.offset == B.Stats.wide_krylov_projections.offset + 8
     assert B.Stats.dense_setup_passes.offset == B.Stats.reserved_s.offset + 32
     assert ctypes.sizeof(B.Stats) == B.Stats.dense_sigma_steps.offset + 8
-    assert B.lib().proxsdp_hip_abi_version() == 9
+    assert B.lib().proxsdp_hip_abi_version() == 10
     assert {"proxsdp_hip_dense_scaling", "proxsdp_host_equilibrate_rowsums"} <= set(B.header_symbols())

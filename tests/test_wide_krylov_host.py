@@ -20,7 +20,7 @@ def test_wide_krylov_option_default_by_name_and_layout():
     assert B.Stats.wide_krylov_projections.offset == B.Stats.dense_truncated_projections.offset + 8
     assert B.Stats.reserved_s.offset == B.Stats.wide_krylov_projections.offset + 8
     assert o.struct_size == ctypes.sizeof(B.Options)             # sizeof(proxsdp_options) on the C side
-    assert B.lib().proxsdp_hip_abi_version() == 9
+    assert B.lib().proxsdp_hip_abi_version() == 10
     assert "wide_krylov_projections" in [f[0] for f in B.Stats._fields_]
 
 
