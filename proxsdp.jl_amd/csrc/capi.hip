@@ -506,8 +506,8 @@ int proxsdp_hip_dual_trial(const double* y, const double* Mx, const double* Mx_o
         hipLaunchKernelGGL(proxsdp::dev::k_dual_trial_batch, dim3(g, 1), dim3(proxsdp::dev::TPB), 0, st,
                            (const double*)dy.p, (const double*)d1.p, (const double*)d0.p, (const double*)dbh.p,
                            (int)p, (int)Q, tb, dout.p, (long long)Q, part.p, 0LL);
-        hipLaunchKernelGGL(proxsdp::dev::k_combine, dim3(1), dim3(proxsdp::dev::TPB), 0, st,
-                           (const double*)part.p, proxsdp::PSTRIDE, g, 1, 0u, sc.p);
+        hipLaunchKernelGGL(proxsdp::dev::k_combine_multi, dim3(1), dim3(proxsdp::dev::TPB), 0, st,
+                           (const double*)part.p, proxsdp::PSTRIDE, g, 0ull, sc.p, 1, (const double*)nullptr, 0, 0, (double*)nullptr);
         dout.download(y_out, Q, st);
         double nrm = 0.0;
         sc.download(&nrm, 1, st);
@@ -536,15 +536,18 @@ int proxsdp_hip_residuals(const double* x, const double* x_old, const double* Mt
         // one candidate of the linesearch's residual batch: the x part lands in quantities 2..4, the y part in 5..10
         proxsdp::dev::TrialBatch tb{};
         tb.nc = 1; tb.tau[0] = tau; tb.sigma[0] = sigma;
-        hipLaunchKernelGGL(proxsdp::dev::k_residual_xy_full_batch, dim3(std::max(gx, gq), 1, 2), dim3(proxsdp::dev::TPB), 0, st,
-                           (const double*)dx.p, (const double*)dxo.p, 1.0, (const double*)dm.p, (long long)n,
-                           (const double*)dmo.p, (const double*)dc.p, (long long)n, gx,
+        hipLaunchKernelGGL(proxsdp::dev::k_residual_xy<false>, dim3(std::max(gx, gq), 1, 2), dim3(proxsdp::dev::TPB), 0, st,
+                           (const double*)dx.p, (const int*)nullptr, (long long)n, (const double*)dxo.p, 1.0,
+                           (const double*)dm.p, (long long)n, (const double*)dmo.p, (const double*)dc.p, gx,
                            (const double*)dy.p, (long long)Q, (const double*)dyo.p, (const double*)d1.p, (const double*)d0.p,
-                           (const double*)dbh.p, (int)p, (int)Q, gq, tb, part.p, proxsdp::PSTRIDE, 0LL);
-        hipLaunchKernelGGL(proxsdp::dev::k_combine, dim3(1), dim3(proxsdp::dev::TPB), 0, st,
-                           (const double*)(part.p + (size_t)2 * proxsdp::PSTRIDE), proxsdp::PSTRIDE, gx, 3, 0x3u, sc.p);
-        hipLaunchKernelGGL(proxsdp::dev::k_combine, dim3(1), dim3(proxsdp::dev::TPB), 0, st,
-                           (const double*)(part.p + (size_t)5 * proxsdp::PSTRIDE), proxsdp::PSTRIDE, gq, 6, 0xFu, sc.p + 3);
+                           (const double*)dbh.p, (int)p, (int)Q, gq, tb, part.p, proxsdp::PSTRIDE, 0LL, (const double*)nullptr);
+        // one workgroup per quantity: the x part's three over gx partials, the y part's six over gq
+        hipLaunchKernelGGL(proxsdp::dev::k_combine_multi, dim3(3), dim3(proxsdp::dev::TPB), 0, st,
+                           (const double*)(part.p + (size_t)2 * proxsdp::PSTRIDE), proxsdp::PSTRIDE, gx, 0x3ull, sc.p, 3,
+                           (const double*)nullptr, 0, 0, (double*)nullptr);
+        hipLaunchKernelGGL(proxsdp::dev::k_combine_multi, dim3(6), dim3(proxsdp::dev::TPB), 0, st,
+                           (const double*)(part.p + (size_t)5 * proxsdp::PSTRIDE), proxsdp::PSTRIDE, gq, 0xFull, sc.p + 3, 6,
+                           (const double*)nullptr, 0, 0, (double*)nullptr);
         sc.download(out, 9, st);
         PX_HIP(hipStreamSynchronize(st));
         return 0;

@@ -1768,8 +1768,8 @@ k_spmv_csr_wave(const int* __restrict__ rowptr, const int* __restrict__ col, con
 // ---- long columns of M (round 6).  The transposed products below give every column to ONE thread, which walks its entries
 // with two dependent memory round trips per entry (row index, then y[row]): ~250 ns per entry.  Sensor localisation has three
 // columns -- the entries of the identity block, present in every anchor constraint -- with thousands of entries: ONE launch of
-// k_spmvT_S_batch took 2.07 ms, 88 % of the GPU time of the reference's SENSORLOC benchmark family (profiles/r06a_kernel_stats_
-// sensorloc400.md).  Columns longer than LONGCOL entries are now summed by a whole wave: the products val[k] * y[row[k]] of 64
+// k_spmvT_batch on the support path took 2.07 ms, 88 % of the GPU time of the reference's SENSORLOC benchmark family (profiles/
+// r06a_kernel_stats_sensorloc400.md). Columns longer than LONGCOL entries are now summed by a whole wave: the products val[k] * y[row[k]] of 64
 // entries are formed in parallel (FP contraction is off here: the product is rounded on its own in the scalar loop too) and
 // ADDED IN THE SCALAR LOOP'S ORDER by a serial chain over the lanes -- the same bits, ~7 ns per entry instead of ~250.
 constexpr int LONGCOL = 192;         // entries from which a column goes to a wave
@@ -1937,24 +1937,29 @@ k_dual_trial_batch(const double* __restrict__ y, const double* __restrict__ Mx, 
     if (threadIdx.x == 0) part[(long long)c * cstride + blockIdx.x] = tot;
 }
 
-// MtyS_c = (M' y_c)|S for every candidate + |MtyS_c - MtyS_old|^2 partials (pdhg.jl:556-563)
+// The candidate batch of both vector paths.  SUPP: loop index s stands for column / entry supp[s] of x (the support path: cnt = |S|,
+// every per-entry array is compact on S); otherwise for s itself (the general path: cnt = n, full vectors).  A compile-time
+// choice: neither path pays a branch or a load for the other.
+// Mty_c = M' y_c over those columns for every candidate (M in CSC: one dot per column, thread per column; columns are mostly
+// empty or short) + |Mty_c - Mty_old|^2 partials (pdhg.jl:556-563)
+template <bool SUPP>
 __global__ void __launch_bounds__(TPB)
-k_spmvT_S_batch(const int* __restrict__ colptr, const int* __restrict__ row, const double* __restrict__ val,
-                const int* __restrict__ supp, int ns, const double* __restrict__ ycand, long long ystride,
-                double* __restrict__ MtyScand, long long mstride, const double* __restrict__ MtyS_old,
-                double* __restrict__ part, long long cstride, int plain = 0) {
+k_spmvT_batch(const int* __restrict__ colptr, const int* __restrict__ row, const double* __restrict__ val,
+              const int* __restrict__ supp, long long cnt, const double* __restrict__ ycand, long long ystride,
+              double* __restrict__ Mtycand, long long mstride, const double* __restrict__ Mty_old,
+              double* __restrict__ part, long long cstride, int plain) {
     __shared__ double sm[NWAVE];
     __shared__ LongCols lc;
     const int c = blockIdx.y;
     const double* y = ycand + (long long)c * ystride;
-    double* out = MtyScand + (long long)c * mstride;
+    double* out = Mtycand + (long long)c * mstride;
+    auto colof = [supp](long long s) { return SUPP ? supp[s] : (int)s; };
     double ss = 0.0;
-    long_cols_collect(lc, colptr, row, val, y, (long long)blockIdx.x * TPB + threadIdx.x, (long long)gridDim.x * TPB, (long long)ns,
-                      [supp](long long s) { return supp[s]; });
-    for (int s = blockIdx.x * TPB + threadIdx.x; s < ns; s += gridDim.x * TPB) {
-        const int col = supp[s];
-        const double acc = col_dot(lc, col, colptr, row, val, y);
-        const double o = MtyS_old[s];
+    const long long first = (long long)blockIdx.x * TPB + threadIdx.x, stride = (long long)gridDim.x * TPB;
+    long_cols_collect(lc, colptr, row, val, y, first, stride, cnt, colof);
+    for (long long s = first; s < cnt; s += stride) {
+        const double acc = col_dot(lc, colof(s), colptr, row, val, y);
+        const double o = Mty_old[s];
         const double d = acc - o;
         out[s] = plain ? acc : d + o;          // pdhg.jl:560,574 (plain: dual_step!'s mul!(Mty, Mt, y), pdhg.jl:606)
         ss += d * d;
@@ -1963,26 +1968,28 @@ k_spmvT_S_batch(const int* __restrict__ colptr, const int* __restrict__ row, con
     if (threadIdx.x == 0) part[(long long)c * cstride + blockIdx.x] = tot;
 }
 
-// on-support part of compute_residual! + c.x (residuals.jl:22,41-48), per candidate
-// part[c][q][wg], q = 0: max |dPx|  1: max |Px_old|  2: sum c*x
+// x part of compute_residual! (residuals.jl:41-48) + c.x (residuals.jl:22) over the same entries, per candidate (on the support
+// path the off-support part is fused into the reconstruction); part[c][q][wg], q = 0: max |(x - tau Mty) - (x_old - tau Mty_old)|
+// 1: max |x_old - tau Mty_old|  2: sum c*x
+template <bool SUPP>
 __device__ __forceinline__ void
-residual_xS_body(const double* __restrict__ xnew, const int* __restrict__ supp, int ns,
-                 const double* __restrict__ xsave, double xold_coef,
-                 const double* __restrict__ MtyScand, long long mstride, const double* __restrict__ MtyS_old,
-                 const double* __restrict__ cS, const TrialBatch& tb, double* __restrict__ part, int pstride,
-                 long long cstride, int gx, double* __restrict__ sm) {
+residual_x_body(const double* __restrict__ xnew, const int* __restrict__ supp, long long cnt,
+                const double* __restrict__ xold, double xold_coef,
+                const double* __restrict__ Mtycand, long long mstride, const double* __restrict__ Mty_old,
+                const double* __restrict__ cv, const TrialBatch& tb, double* __restrict__ part, int pstride,
+                long long cstride, int gx, double* __restrict__ sm) {
     if ((int)blockIdx.x >= gx) return;
     const int c = blockIdx.y;
     const double tau = tb.tau[c];
-    const double* MtyS = MtyScand + (long long)c * mstride;
+    const double* Mty = Mtycand + (long long)c * mstride;
     double m0 = 0.0, m1 = 0.0, s2 = 0.0;
-    for (int s = blockIdx.x * TPB + threadIdx.x; s < ns; s += gx * TPB) {
-        const double xi = xnew[supp[s]];
-        const double pold = xold_coef * xsave[s] - tau * MtyS_old[s];
-        const double pnew = xi - tau * MtyS[s];
+    for (long long s = (long long)blockIdx.x * TPB + threadIdx.x; s < cnt; s += (long long)gx * TPB) {
+        const double xi = xnew[SUPP ? (long long)supp[s] : s];
+        const double pold = xold_coef * xold[s] - tau * Mty_old[s];
+        const double pnew = xi - tau * Mty[s];
         m0 = fmax(m0, fabs(pnew - pold));
         m1 = fmax(m1, fabs(pold));
-        s2 += cS[s] * xi;
+        s2 += cv[s] * xi;
     }
     const double r0 = block_max(m0, sm), r1 = block_max(m1, sm), r2 = block_sum(s2, sm);
     if (threadIdx.x == 0) {
@@ -2024,95 +2031,26 @@ residual_y_body(const double* __restrict__ ycand, long long ystride, const doubl
     }
 }
 
-// both residual parts of every candidate in ONE launch: grid (max(gs, gq), nc, 2), z = 0 the
-// on-support x part, z = 1 the y part (they are independent; one link less in the per-iteration chain)
+// both residual parts of every candidate in ONE launch: grid (max(gx, gq), nc, 2), z = 0 the x part, z = 1 the y part
+// (they are independent; one link less in the per-iteration chain)
+template <bool SUPP>
 __global__ void __launch_bounds__(TPB)
-k_residual_xy_batch(const double* __restrict__ xnew, const int* __restrict__ supp, int ns,
-                    const double* __restrict__ xsave, double xold_coef,
-                    const double* __restrict__ MtyScand, long long mstride, const double* __restrict__ MtyS_old,
-                    const double* __restrict__ cS, int gs,
-                    const double* __restrict__ ycand, long long ystride, const double* __restrict__ yold,
-                    const double* __restrict__ Mx, const double* __restrict__ Mx_old,
-                    const double* __restrict__ bh, int p, int Q, int gq,
-                    TrialBatch tb, double* __restrict__ part, int pstride, long long cstride,
-                    const double* __restrict__ roww = nullptr) {
+k_residual_xy(const double* __restrict__ xnew, const int* __restrict__ supp, long long cnt,
+              const double* __restrict__ xold, double xold_coef,
+              const double* __restrict__ Mtycand, long long mstride, const double* __restrict__ Mty_old,
+              const double* __restrict__ cv, int gx,
+              const double* __restrict__ ycand, long long ystride, const double* __restrict__ yold,
+              const double* __restrict__ Mx, const double* __restrict__ Mx_old,
+              const double* __restrict__ bh, int p, int Q, int gq,
+              TrialBatch tb, double* __restrict__ part, int pstride, long long cstride,
+              const double* __restrict__ roww) {
     __shared__ double sm[NWAVE];
     if (blockIdx.z == 0)
-        residual_xS_body(xnew, supp, ns, xsave, xold_coef, MtyScand, mstride, MtyS_old, cS, tb,
-                         part + 2 * (long long)pstride, pstride, cstride, gs, sm);
+        residual_x_body<SUPP>(xnew, supp, cnt, xold, xold_coef, Mtycand, mstride, Mty_old, cv, tb,
+                              part + 2 * (long long)pstride, pstride, cstride, gx, sm);
     else
         residual_y_body(ycand, ystride, yold, Mx, Mx_old, bh, p, Q, tb,
                         part + 5 * (long long)pstride, pstride, cstride, gq, sm, roww);
-}
-
-// The same batch on the GENERAL path (no support set: full-vector passes).  Mty_c = M' y_c for every candidate (M in CSC: one
-// dot per column, thread per column; columns are mostly empty or short) + |Mty_c - Mty_old|^2 partials (pdhg.jl:556-563)
-__global__ void __launch_bounds__(TPB)
-k_spmv_csc_norm_batch(const int* __restrict__ colptr, const int* __restrict__ row, const double* __restrict__ val,
-                      const double* __restrict__ ycand, long long ystride, double* __restrict__ Mtycand, long long mstride,
-                      const double* __restrict__ Mty_old, long long ncols, double* __restrict__ part, long long cstride,
-                      int plain) {
-    __shared__ double sm[NWAVE];
-    const int c = blockIdx.y;
-    const double* y = ycand + (long long)c * ystride;
-    double* out = Mtycand + (long long)c * mstride;
-    __shared__ LongCols lc;
-    double ss = 0.0;
-    long long j = (long long)blockIdx.x * TPB + threadIdx.x;
-    const long long stride = (long long)gridDim.x * TPB;
-    long_cols_collect(lc, colptr, row, val, y, j, stride, ncols, [](long long s) { return (int)s; });
-    for (; j < ncols; j += stride) {
-        const double acc = col_dot(lc, (int)j, colptr, row, val, y);
-        const double o = Mty_old[j];
-        const double d = acc - o;
-        out[j] = plain ? acc : d + o;          // pdhg.jl:560,574 (plain: dual_step!'s mul!(Mty, Mt, y), pdhg.jl:606)
-        ss += d * d;
-    }
-    const double tot = block_sum(ss, sm);
-    if (threadIdx.x == 0) part[(long long)c * cstride + blockIdx.x] = tot;
-}
-// x part of compute_residual! (residuals.jl:41-48) + c.x (residuals.jl:22) over the whole vector, per candidate;
-// part[c][q][wg], q = 0: max |(x - tau Mty) - (x_old - tau Mty_old)|  1: max |x_old - tau Mty_old|  2: sum c*x
-__device__ __forceinline__ void
-residual_x_full_body(const double* __restrict__ x, const double* __restrict__ xold, double xold_coef,
-                     const double* __restrict__ Mtycand, long long mstride, const double* __restrict__ Mty_old,
-                     const double* __restrict__ cv, long long N, const TrialBatch& tb, double* __restrict__ part,
-                     int pstride, long long cstride, int gx, double* __restrict__ sm) {
-    if ((int)blockIdx.x >= gx) return;
-    const int c = blockIdx.y;
-    const double tau = tb.tau[c];
-    const double* Mty = Mtycand + (long long)c * mstride;
-    double m0 = 0.0, m1 = 0.0, s2 = 0.0;
-    for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < N; i += (long long)gx * TPB) {
-        const double xi = x[i];
-        const double pold = xold_coef * xold[i] - tau * Mty_old[i];
-        const double pnew = xi - tau * Mty[i];
-        m0 = fmax(m0, fabs(pnew - pold));
-        m1 = fmax(m1, fabs(pold));
-        s2 += cv[i] * xi;
-    }
-    const double r0 = block_max(m0, sm), r1 = block_max(m1, sm), r2 = block_sum(s2, sm);
-    if (threadIdx.x == 0) {
-        double* pp = part + (long long)c * cstride;
-        pp[blockIdx.x] = r0; pp[pstride + blockIdx.x] = r1; pp[2 * pstride + blockIdx.x] = r2;
-    }
-}
-// grid (max(gx, gq), nc, 2): z = 0 the x part over the whole vector, z = 1 the y part
-__global__ void __launch_bounds__(TPB)
-k_residual_xy_full_batch(const double* __restrict__ x, const double* __restrict__ xold, double xold_coef,
-                         const double* __restrict__ Mtycand, long long mstride, const double* __restrict__ Mty_old,
-                         const double* __restrict__ cv, long long N, int gx,
-                         const double* __restrict__ ycand, long long ystride, const double* __restrict__ yold,
-                         const double* __restrict__ Mx, const double* __restrict__ Mx_old,
-                         const double* __restrict__ bh, int p, int Q, int gq,
-                         TrialBatch tb, double* __restrict__ part, int pstride, long long cstride) {
-    __shared__ double sm[NWAVE];
-    if (blockIdx.z == 0)
-        residual_x_full_body(x, xold, xold_coef, Mtycand, mstride, Mty_old, cv, N, tb,
-                             part + 2 * (long long)pstride, pstride, cstride, gx, sm);
-    else
-        residual_y_body(ycand, ystride, yold, Mx, Mx_old, bh, p, Q, tb,
-                        part + 5 * (long long)pstride, pstride, cstride, gq, sm, nullptr);
 }
 
 // non-PSD tail of x (SOC + free variables): x_new = x_trial copied to the other buffer,
@@ -2133,24 +2071,6 @@ k_tail_copy_res(const double* __restrict__ xin, double* __restrict__ xout, long 
 }
 
 #pragma clang fp contract(fast)
-// final fixed-order combine of per-workgroup partials: out[q] = sum or max over
-// part[q*stride .. q*stride+cnt).  One workgroup; ismax bit q selects max.
-__global__ void __launch_bounds__(TPB)
-k_combine(const double* __restrict__ part, int stride, int cnt, int nq, unsigned ismax, double* __restrict__ out) {
-    __shared__ double sm[NWAVE];
-    for (int q = 0; q < nq; ++q) {
-        const bool mx = (ismax >> q) & 1u;
-        double a = 0.0;
-        for (int i = threadIdx.x; i < cnt; i += TPB) {
-            const double v = part[(long long)q * stride + i];
-            a = mx ? fmax(a, v) : a + v;
-        }
-        double r = mx ? block_max(a, sm) : block_sum(a, sm);
-        if (threadIdx.x == 0) out[q] = r;
-        __syncthreads();
-    }
-}
-
 // ---------------------------------------------------------------------------
 // Dense constraint matrix (randSDP-scale models: every A_k dense, M = 64 GB at
 // n = 2000, m = 4000).  M is the caller's ROW-MAJOR Q x n array, used in place:

@@ -595,7 +595,7 @@ constexpr int NSCAL = 11;   // scalars per candidate: q0,q1 sums | q2,q3 max, q4
 // the candidates' buffers: y_c, M'y_c (on the support, or every column), their partials and the scalar record
 inline void Solver::alloc_candidates() {
     ycand_d.alloc((size_t)NCAND * std::max<int64_t>(P.Q, 1)); ycand_d.zero(stream);
-    Mtycand_d.alloc((size_t)NCAND * (use_support ? std::max<int64_t>(ns, 1) : P.n)); Mtycand_d.zero(stream);
+    Mtycand_d.alloc((size_t)NCAND * batch_shape().mstride); Mtycand_d.zero(stream);
     bpart.alloc((size_t)NCAND * NSCAL * PSTRIDE); bpart.zero(stream);
     bscal.alloc(64); bscal.zero(stream);
     hbscal.assign(64, 0.0);
@@ -641,38 +641,34 @@ inline void Solver::reduce_candidates(int nc) {
 
 // ---- one batch of linesearch candidates: the launches (shared with the kernel-level test entry, test_trial_batch)
 // the batch's launch shapes: one workgroup column per 256 entries of y (gq) and of the support or every column (gx), capped at
-// PSTRIDE (the kernels stride over the rest); the candidates' slices of ycand_d / Mtycand_d / bpart
+// PSTRIDE (the kernels stride over the rest); the candidates' slices of ycand_d / Mtycand_d / bpart; and the one place that
+// tells the vector paths apart for the batch (the support path keeps M'y on S in one buffer, which commit overwrites)
 inline Solver::BatchShape Solver::batch_shape() const {
     BatchShape b;
+    if (use_support) { b.supp = supp_d.p; b.cnt = ns; b.xold = xsave_d.p; b.cv = cS_d.p; b.mty_cur = b.mty_commit = MtyS_cur.p; }
+    else { b.supp = nullptr; b.cnt = P.n; b.xold = xbuf[xc].p; b.cv = c_d.p; b.mty_cur = Mtybuf[mtyc].p; b.mty_commit = Mtybuf[1 - mtyc].p; }
     b.gq = std::min(PSTRIDE, grid_for(std::max<int64_t>(P.Q, 1)));
-    b.gx = std::min(PSTRIDE, grid_for(use_support ? std::max<int64_t>(ns, 1) : P.n));   // the support, or every column
+    b.gx = std::min(PSTRIDE, grid_for(std::max<long long>(b.cnt, 1)));
     b.cstride = (long long)NSCAL * PSTRIDE;
     b.ystride = std::max<int64_t>(P.Q, 1);
-    b.mstride = use_support ? std::max<int64_t>(ns, 1) : P.n;
+    b.mstride = std::max<long long>(b.cnt, 1);
     return b;
 }
 // residual / gap reductions of candidates c0 .. c0 + nc - 1 (their partials land in the records 0 .. nc - 1)
 inline void Solver::batch_residuals(const dev::TrialBatch& tb, int nc, int c0, double xold_coef) {
     const BatchShape b = batch_shape();
-    const int gq = b.gq, gx = b.gx;
-    const long long cstride = b.cstride, ystride = b.ystride, mstride = b.mstride;
-    double* mty_cur = use_support ? MtyS_cur.p : Mtybuf[mtyc].p;
-    const double* roww = roww_d.p;
-    const double* yc0 = ycand_d.p + (size_t)c0 * ystride;
-    const double* mc0 = Mtycand_d.p + (size_t)c0 * mstride;
-    if (use_support)
-        hipLaunchKernelGGL(dev::k_residual_xy_batch, dim3(std::max(gx, gq), nc, 2), dim3(dev::TPB), 0, stream,
-                           xbuf[1 - xc].p, supp_d.p, ns, xsave_d.p, xold_coef, mc0, mstride, mty_cur, cS_d.p, gx,
-                           yc0, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, gq,
-                           tb, bpart.p, PSTRIDE, cstride, roww);
-    else
-        hipLaunchKernelGGL(dev::k_residual_xy_full_batch, dim3(std::max(gx, gq), nc, 2), dim3(dev::TPB), 0, stream,
-                           xbuf[1 - xc].p, xbuf[xc].p, xold_coef, mc0, mstride, mty_cur, c_d.p, (long long)P.n, gx,
-                           yc0, ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, gq,
-                           tb, bpart.p, PSTRIDE, cstride);
+    const double* yc0 = ycand_d.p + (size_t)c0 * b.ystride;
+    const double* mc0 = Mtycand_d.p + (size_t)c0 * b.mstride;
+    // (the general path's residuals have never taken the row weights that k_dual_trial_batch gets on both paths: kept as it is)
+    const double* roww = b.supp != nullptr ? roww_d.p : nullptr;
+    hipLaunchKernelGGL(b.supp != nullptr ? dev::k_residual_xy<true> : dev::k_residual_xy<false>,
+                       dim3(std::max(b.gx, b.gq), nc, 2), dim3(dev::TPB), 0, stream,
+                       xbuf[1 - xc].p, b.supp, b.cnt, b.xold, xold_coef, mc0, b.mstride, b.mty_cur, b.cv, b.gx,
+                       yc0, b.ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, b.gq,
+                       tb, bpart.p, PSTRIDE, b.cstride, roww);
 }
 // y+, M'y+ and their norms for nc candidates, then their residuals
-// (the vector paths differ only in the launches that compute M'y+ and the residuals)
+// (the vector paths differ only in the view batch_shape() gives and, for a dense M, in the M'y+ product)
 inline void Solver::batch_evaluate(const dev::TrialBatch& tb, int nc, double xold_coef) {
     const BatchShape b = batch_shape();
     const int gq = b.gq;
@@ -686,19 +682,13 @@ inline void Solver::batch_evaluate(const dev::TrialBatch& tb, int nc, double xol
 // M'y_c of the candidates in ycand_d + |M'y_c - M'y_old|^2 partials
 inline void Solver::batch_mty(const dev::TrialBatch& tb, int nc) {
     const BatchShape b = batch_shape();
-    const int gx = b.gx;
-    const long long cstride = b.cstride, ystride = b.ystride, mstride = b.mstride;
-    double* mty_cur = use_support ? MtyS_cur.p : Mtybuf[mtyc].p;
-    if (use_support)
-        hipLaunchKernelGGL(dev::k_spmvT_S_batch, dim3(gx, nc), dim3(dev::TPB), 0, stream,
-                           csc_ptr.p, csc_row.p, csc_val.p, supp_d.p, ns, ycand_d.p, ystride,
-                           Mtycand_d.p, mstride, mty_cur, bpart.p + PSTRIDE, cstride, tb.plain);
-    else if (P.dense())
-        dense_mtv(nc, ycand_d.p, ystride, true, Mtycand_d.p, mstride, mty_cur, nullptr, bpart.p + PSTRIDE, cstride, !tb.plain);
+    if (b.supp == nullptr && P.dense())
+        dense_mtv(nc, ycand_d.p, b.ystride, true, Mtycand_d.p, b.mstride, b.mty_cur, nullptr, bpart.p + PSTRIDE, b.cstride, !tb.plain);
     else
-        hipLaunchKernelGGL(dev::k_spmv_csc_norm_batch, dim3(gx, nc), dim3(dev::TPB), 0, stream,
-                           csc_ptr.p, csc_row.p, csc_val.p, ycand_d.p, ystride, Mtycand_d.p, mstride, mty_cur,
-                           (long long)P.n, bpart.p + PSTRIDE, cstride, tb.plain);
+        hipLaunchKernelGGL(b.supp != nullptr ? dev::k_spmvT_batch<true> : dev::k_spmvT_batch<false>,
+                           dim3(b.gx, nc), dim3(dev::TPB), 0, stream,
+                           csc_ptr.p, csc_row.p, csc_val.p, b.supp, b.cnt, ycand_d.p, b.ystride,
+                           Mtycand_d.p, b.mstride, b.mty_cur, bpart.p + PSTRIDE, b.cstride, tb.plain);
 }
 // the scalar record: NSCAL per candidate, then (support path) the two off-support residual maxima that the fused
 // reconstruction reduced -- independent of the candidate, combined by two extra workgroups.  Returns the record.
@@ -738,14 +728,13 @@ inline const double* Solver::batch_read_back(int nc) {
 // Returns the accepted candidate's scalar record.
 inline const double* Solver::linesearch_and_residuals() {
     const int ncmax = opt.general_batch != 0 ? NCAND : 1;
-    const long long ystride = batch_shape().ystride, mstride = batch_shape().mstride;
     const double xold_coef = (iter == 1 && opt.advanced_initialization) ? 0.0 : 1.0;   // x_old = 0 at k = 1
     const double* rec = nullptr;
     auto commit = [&](int c) {                           // y <- y_c, M'y <- M'y_c (one launch)
-        const long long nm = use_support ? ns : P.n;
-        hipLaunchKernelGGL(dev::k_copy2, dim3(grid_for((long long)P.Q + nm)), dim3(dev::TPB), 0, stream,
-                           ybuf[1 - yc].p, (const double*)(ycand_d.p + (size_t)c * ystride), (long long)P.Q,
-                           use_support ? MtyS_cur.p : Mtybuf[1 - mtyc].p, (const double*)(Mtycand_d.p + (size_t)c * mstride), nm);
+        const BatchShape b = batch_shape();
+        hipLaunchKernelGGL(dev::k_copy2, dim3(grid_for((long long)P.Q + b.cnt)), dim3(dev::TPB), 0, stream,
+                           ybuf[1 - yc].p, (const double*)(ycand_d.p + (size_t)c * b.ystride), (long long)P.Q,
+                           b.mty_commit, (const double*)(Mtycand_d.p + (size_t)c * b.mstride), b.cnt);
     };
     const bool ls = opt.line_search_flag;
     if (ls) primal_step = primal_step * std::sqrt(1.0 + theta);
@@ -1162,7 +1151,8 @@ inline void Solver::setup_dense() {
     const int gx = std::min(PSTRIDE, grid_for(P.n));
     hipLaunchKernelGGL(dev::k_dense_frob, dim3(gx), dim3(dev::TPB), 0, stream,
                        Md, (long long)P.n, (int)P.p, (long long)P.n, offdiag_d.p, std::sqrt(2.0) / 2.0, part.p);
-    hipLaunchKernelGGL(dev::k_combine, dim3(1), dim3(dev::TPB), 0, stream, part.p, PSTRIDE, gx, 1, 0u, scal.p);
+    hipLaunchKernelGGL(dev::k_combine_multi, dim3(1), dim3(dev::TPB), 0, stream, (const double*)part.p, PSTRIDE, gx, 0ull, scal.p, 1,
+                       (const double*)nullptr, 0, 0, (double*)nullptr);
     double ss = 0.0;
     PX_HIP(hipMemcpyAsync(&ss, scal.p, sizeof(double), hipMemcpyDeviceToHost, stream));
     PX_HIP(hipStreamSynchronize(stream));
@@ -1462,7 +1452,7 @@ inline void Solver::test_trial_batch(proxsdp_trial_batch& t) {
     } else {
         Mtybuf[mtyc].upload(t.Mty_old, n, stream);
     }
-    t.ns = use_support ? ns : n;
+    t.ns = batch_shape().cnt;
     xbuf[1 - xc].upload(t.x, n, stream);
     alloc_candidates();
     dev::TrialBatch tb{};

@@ -655,7 +655,14 @@ private:
     void launch_primal_update_S(double* x, double tau);
     void alloc_candidates();
     // one batch of linesearch candidates (pdhg_loop.hip.hpp): launch shapes, the launches, the read-back
-    struct BatchShape { int gq, gx; long long cstride, ystride, mstride; };
+    struct BatchShape {
+        int gq, gx; long long cstride, ystride, mstride;
+        // the vector path: the batch runs over cnt entries of x -- supp[0 .. cnt) (the support path; c, x_old and M'y are
+        // compact on the support) or, with supp == nullptr, every entry (the general path; full vectors)
+        const int* supp; long long cnt;
+        const double* xold; const double* cv;        // x_old and c on those entries
+        double* mty_cur; double* mty_commit;         // M'y of the iterate, and where commit puts the accepted candidate's
+    };
     BatchShape batch_shape() const;
     void batch_evaluate(const dev::TrialBatch& tb, int nc, double xold_coef);
     void batch_mty(const dev::TrialBatch& tb, int nc);

@@ -1422,8 +1422,8 @@ def _long_column_model(n=120, copies=6, seed=3):
 @pytest.mark.parametrize("support", [0, 1])
 def test_long_columns_of_the_constraint_matrix_follow_the_oracle(support):
     """Round 6: columns of M beyond 192 entries are summed by a wave -- products in parallel, additions in the scalar loop's order
-    (kernels.hip.hpp `wave_col_dot_inorder`) -- in the transposed products of both vector paths (`k_spmv_csc_norm_batch`: dense
-    passes, `k_spmvT_S_batch`: support path).  A model with one column of 1429 entries against the oracle: identical linesearch
+    (kernels.hip.hpp `wave_col_dot_inorder`) -- in the transposed products of both vector paths (`k_spmvT_batch<false>`: dense
+    passes, `k_spmvT_batch<true>`: support path).  A model with one column of 1429 entries against the oracle: identical linesearch
     trials and mat-vec counts, traces to 1e-9; and the two paths against each other."""
     import oracle
     pr = _long_column_model()

@@ -1,7 +1,7 @@
 """The linesearch's production kernels and the cone tail against exact references (vector_kernel_cases.py), through
-proxsdp_hip_trial_batch / proxsdp_hip_cone_tail, which run the solver's own launches (k_dual_trial_batch,
-k_spmv_csc_norm_batch / k_spmvT_S_batch with the wave-per-long-column sums, k_residual_xy_full_batch / k_residual_xy_batch,
-k_combine_multi, k_primal_update_S; k_soc_project, k_soc_gap, k_clamp_scalars).
+proxsdp_hip_trial_batch / proxsdp_hip_cone_tail, which run the solver's own launches (k_dual_trial_batch, both
+instantiations of k_spmvT_batch with the wave-per-long-column sums and of k_residual_xy -- <false> on the general path,
+<true> on the support path --, k_combine_multi, k_primal_update_S; k_soc_project, k_soc_gap, k_clamp_scalars).
 
 y+ and M'y+ of every candidate and the six maxima are compared with `==` on bits: the element-wise expressions are compiled
 without contraction, the column sums are specified in storage order, a maximum has no order.  The five sums are compared
@@ -140,8 +140,22 @@ def test_grid_stride_support_order(capped):
     assert w["Q"] > out["gq"] * V.TPB and len(out["supp"]) > out["gx"] * V.TPB
 
 
+# ----------------------------------------------------------------- the column map is the only difference between the paths
+@pytest.mark.parametrize("cs", V.identity_support_cases(), ids=lambda cs: cs["name"])
+def test_identity_support_is_the_general_path(cs):
+    """a support that holds every column: the support path's y+, M'y+ and all 11 scalars are the general path's bits"""
+    for plain in (False, True):
+        gen = _run(cs, nc=3, support=False, plain=plain)
+        sup = _run(cs, nc=3, support=True, plain=plain)
+        assert np.array_equal(sup["supp"], np.arange(cs["n"]))
+        what = f"{cs['name']} plain={plain}: support path against general path,"
+        _same_bits(sup["y"], gen["y"], what + " y+")
+        _same_bits(sup["Mty"], gen["Mty"], what + " M'y+")
+        _same_bits(sup["scal"], gen["scal"], what + " scalars")
+
+
 def test_transposed_spmv_entry_runs_the_production_kernel():
-    """proxsdp_hip_spmv(transpose=1) is k_spmv_csc_norm_batch with one plain candidate: bits of the storage-order loop
+    """proxsdp_hip_spmv(transpose=1) is k_spmvT_batch<false> with one plain candidate: bits of the storage-order loop
     (binding.spmv sorts the rows of a column, so storage order is ascending rows here)"""
     import scipy.sparse as sp
     cs = V.column_case()

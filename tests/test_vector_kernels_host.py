@@ -83,6 +83,17 @@ def test_special_fixtures_hold_what_their_names_say():
         assert len(set(v)) == 3 and not math.isclose(v[1] / v[0], 0.75) and not math.isclose(v[2] / v[1], v[1] / v[0])
 
 
+def test_identity_support_fixtures_have_every_column_in_the_support():
+    cases = V.identity_support_cases()
+    assert [(cs["Q"], cs["n"]) for cs in cases] == [(1, 1), (64, 64), (65, 65), (257, 257), (300, 130)]
+    for cs in cases:
+        assert np.all(cs["c"] != 0.0) and cs["roww"] is None                      # (else the GPU test could pass vacuously)
+        assert np.array_equal(V.support_of(cs), np.arange(cs["n"]))
+    lens = np.diff(cases[-1]["colptr"])
+    assert sorted(lens[lens > V.LONGCOL].tolist()) == [V.LONGCOL + 1, 300] and 300 > V.LC_GROUP
+    assert all(np.diff(cs["colptr"]).max() <= 5 for cs in cases[:-1])
+
+
 def test_vectorised_column_dots_are_the_plain_loop():
     cs = V.column_case()
     y = np.random.default_rng(0).standard_normal(cs["Q"])

@@ -156,6 +156,20 @@ def capped_keep(n):
     return s + s // 1000
 
 
+def identity_support_cases():
+    """c is non-zero in EVERY column, so the support is 0 .. n-1: the support path runs the general path's loops over the
+    same entries, through its column map.  Q = n in {1, 64, 65, 257} with short columns, and Q = 300, n = 130 with one column
+    just past LONGCOL (193 entries) and one past a round of LC_GROUP (300)."""
+    out = []
+    for size in (1, 64, 65, 257):
+        lens = np.minimum(short_lengths(size, np.random.default_rng(3000 + size)), size)
+        out.append(make_case(f"identity{size}", size, lens, size // 3, 4000 + size, c_density=2.0))
+    lens = short_lengths(130, np.random.default_rng(17))
+    lens[[41, 129]] = (LONGCOL + 1, 300)
+    out.append(make_case("identity_long", 300, lens, 97, 4300, c_density=2.0))
+    return out
+
+
 # ----------------------------------------------------------------- references
 def col_dots_loop(colptr, row, val, y, cols=None):
     """the specification: one sequential float64 accumulation per column, in storage order"""
