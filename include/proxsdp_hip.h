@@ -51,7 +51,10 @@ extern "C" {
  * later: proxsdp_options gained lanczos_wide_krylov (from reserved_i2[0]), proxsdp_stats wide_krylov_projections
  * (from reserved_s[0]): same struct sizes and offsets, version unchanged;
  * later: equilibration and approx_norm = 0 served with a dense A (proxsdp_hip_dense_scaling, proxsdp_host_equilibrate_rowsums),
- * proxsdp_stats dense_setup_passes / dense_sigma_steps (the last two reserved_s slots): same sizes and offsets, version unchanged */
+ * proxsdp_stats dense_setup_passes / dense_sigma_steps (the last two reserved_s slots): same sizes and offsets, version unchanged;
+ * later: a block-sharded solve accepts SOC cones, 1x1 PSD cones and variables outside every cone (such a shard runs the general
+ * vector path); proxsdp_stats.reserved_s[0] counts its iterations (PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS); proxsdp_trial_batch
+ * support = 2: same sizes and offsets, version unchanged */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -110,12 +113,19 @@ typedef struct proxsdp_problem {
      * oracle/eig.py:start_vector). */
     const double* eig_resid;
     /* optional block-sharded solve (multi-GPU, one process per GPU).
-     * When reduce_fn != NULL this problem is ONE SHARD of a block-diagonal model (its PSD
-     * blocks/variables and the constraint rows that touch only them).  The library calls
+     * When reduce_fn != NULL this problem is ONE SHARD of a model whose cones are distributed over
+     * the shards (the cones it owns -- PSD blocks of any side, 1x1 included, SOC cones -- the
+     * variables outside every cone it owns, and the constraint rows that touch only them; rows that
+     * touch several shards are coupling rows, below).  A shard may hold no PSD block at all.  A shard
+     * with at least one PSD block, no SOC and no 1x1 block runs the support-aware vector path, any
+     * other shard the general one; shards of one solve may differ.  Not served in a sharded solve:
+     * approx_norm = 0, equilibration, M_dense, the state seam.  The library calls
      *     reduce_fn(reduce_ctx, sums, nsum, maxs, nmax)
      * with host arrays; the callee must replace sums[] by the element-wise SUM and maxs[] by
      * the element-wise MAX over all shards (e.g. two RCCL all-reduces) and return 0.  It is
-     * called once at start-up and once per PDHG iteration (plus rare extra calls), by every
+     * called once at start-up and once per PDHG iteration (plus rare extra calls: another
+     * linesearch batch, check_dual_feas, the global SOC stop test -- which every shard enters,
+     * SOC-free ones included -- and the exit path), by every
      * shard in the same order.  Only scalars cross shards: the reference's serial loop over
      * blocks (prox_operators.jl:40) becomes one block set per GPU. */
     void* reduce_ctx;
@@ -143,7 +153,9 @@ typedef struct proxsdp_problem {
      * which must replace buf[] by the element-wise SUM over all shards (one RCCL all-reduce on a
      * device buffer when reduce_vec_on_device = 1, host memory otherwise) and return 0 after the
      * result is in place.  coupling_owned[k] = 1 on exactly ONE shard per row: that shard counts
-     * the row in the scalar sums (b'y, |y+ - y|^2, ...), the others skip it. */
+     * the row in the scalar sums (b'y, h'y, |y+ - y|^2, ...), the others skip it -- on both vector
+     * paths.  Which variables a shard owns is the caller's choice (whole cones; free variables
+     * anywhere): a poor assignment only makes more rows coupling rows, up to all of them. */
     int64_t n_coupling;
     const int64_t* coupling_rows;
     const int32_t* coupling_owned;
@@ -451,13 +463,18 @@ typedef struct proxsdp_stats {
                                            * pairs of dsyevd, the same truncated projection and min_eig); status_string says so */
     int64_t wide_krylov_projections;      /* Krylov-branch projections with a Krylov dimension of 256..511 run by the wide Lanczos
                                            * kernels (lanczos_wide_krylov = 1) */
-    int64_t reserved_s[4];                /* zero */
+    int64_t reserved_s[4];                /* [0] = sharded_general_iterations (PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS below):
+                                           * iterations a block-sharded solve ran on the general vector path on THIS shard (a
+                                           * shard with an SOC, a 1x1 PSD block or no PSD block; 0 on a support-path shard and
+                                           * in a solve that is not sharded); [1..3] zero */
     /* (the last two reserved slots: reserved_s keeps its offset) */
     int64_t dense_setup_passes;           /* set-up passes over a dense A (row sums + extrema, 8*p*n bytes): 1 when equilibration
                                            * was asked for, else 0 */
     int64_t dense_sigma_steps;            /* Lanczos steps of the device sigma_max (approx_norm = 0 with a dense A): two passes
                                            * over the dense A each, counted in dense_passes / dense_ms as well */
 } proxsdp_stats;
+/* named slots of proxsdp_stats.reserved_s (the array keeps its four slots and its offset; a slot that gets a meaning keeps its place) */
+#define PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS 0
 
 /* Result (structs.jl:60-81).  Arrays are caller-allocated with the stated
  * lengths (NULL = not wanted); values are unscaled and in USER variable order
@@ -635,6 +652,8 @@ int proxsdp_hip_residuals(const double* x, const double* x_old, const double* Mt
  * k_primal_update_S runs first on x_old with step tau_update and M'y = Mty_old (x_upd, xsave, esv).
  * scal: 11 per candidate -- 0 |y+ - y|^2 (rows weighted by roww)  1 |M'y+ - Mty_old|^2  2..4 and 5..10 as out[0..2] and
  * out[3..8] of proxsdp_hip_residuals (b'y, h'y weighted by roww on the support path).
+ * support = 2: the general path as a shard of a block-sharded solve runs it -- as support = 0, but b'y and h'y (slots 9, 10)
+ * are weighted by roww too; with support = 0 they stay unweighted whatever roww is.
  * c0 >= 0: afterwards candidate c0's residuals (slots 2..10) are evaluated again with tau_re / sigma_re into scal_re[11]. */
 typedef struct {
     int64_t struct_size;
@@ -644,7 +663,7 @@ typedef struct {
     const double* x; const double* x_old; const double* Mty_old;                      /* n each, as c (an argument of the call) */
     const double* roww;                  /* Q row weights of a block-sharded solve, or NULL */
     double xold_coef, tau_update;
-    int32_t support, nc, plain, c0;      /* nc = 1..3; c0 < 0: no re-evaluation */
+    int32_t support, nc, plain, c0;      /* support = 0, 1 or 2 (above); nc = 1..3; c0 < 0: no re-evaluation */
     double tau[3], theta[3], bt[3], sigma[3];
     double tau_re, sigma_re;
     /* out */

@@ -122,6 +122,9 @@ struct Stats                     # proxsdp_stats
     dense_setup_passes::Int64
     dense_sigma_steps::Int64
 end
+# named slots of Stats.reserved_s (PROXSDP_STATS_* in the header, 0-based there): iterations a block-sharded solve ran on
+# the general vector path on this shard
+sharded_general_iterations(s::Stats) = s.reserved_s[1]
 
 mutable struct CResult           # proxsdp_result
     status::Int32

@@ -155,6 +155,9 @@ class Result(C.Structure):
                 ("status_string", C.c_char * 256), ("stats", Stats)]
 
 
+# named slots of Stats.reserved_s (include/proxsdp_hip.h PROXSDP_STATS_*): SolveResult.stats lists them under their names
+STATS_RESERVED_SLOTS = {"sharded_general_iterations": 0}
+
 STATE_NHIST = 7
 STATE_HIST_NAMES = ("dual_gap", "prim_obj", "dual_obj", "feasibility", "primal_residual", "dual_residual", "comb_residual")
 STATE_SCAL_NAMES = ("primal_step", "primal_step_old", "dual_step", "beta", "theta", "adapt_level",
@@ -345,6 +348,8 @@ class SolveResult:
         self.primal, self.dual_cone, self.dual_eq, self.dual_in, self.slack_eq, self.slack_in = arrays
         self.stats = {k: (list(getattr(R.stats, k)) if k.startswith("reserved") else getattr(R.stats, k))
                       for k, _ in Stats._fields_}
+        for k, slot in STATS_RESERVED_SLOTS.items():
+            self.stats[k] = int(R.stats.reserved_s[slot])
         self.trace = trace[:R.trace_rows].copy()
         for k in ("certificate_found", "primal_feasible_user_tol", "dual_feasible_user_tol"):
             setattr(self, k, bool(getattr(self, k)))
@@ -633,10 +638,15 @@ class TrialBatchIO(C.Structure):
 
 
 def trial_batch(colptr, rowval, nzval, Q, *, p, bh, y, Mx, Mx_old, x, x_old, Mty_old, c, tau, theta, bt, sigma,
-                xold_coef=1.0, support=False, roww=None, plain=False, c0=-1, tau_re=0.0, sigma_re=0.0, tau_update=0.0):
+                xold_coef=1.0, support=False, roww=None, plain=False, c0=-1, tau_re=0.0, sigma_re=0.0, tau_update=0.0,
+                sharded_rows=False):
     """proxsdp_hip_trial_batch: one batch of len(tau) linesearch candidates through the solver's launches.  M (Q x n) is
     given as raw CSC arrays (0-based) and is used in its storage order.  Returns a dict: y (nc x Q), Mty (nc x ns), scal
-    (nc x 11), gq, gx, and -- c0 >= 0 -- scal_re (11); on the support path also supp, x_upd, xsave, esv (2 x ns)."""
+    (nc x 11), gq, gx, and -- c0 >= 0 -- scal_re (11); on the support path also supp, x_upd, xsave, esv (2 x ns).
+    sharded_rows (general path only): the residual pass of a block-sharded solve's general path, b'y and h'y weighted by
+    roww (proxsdp_trial_batch.support = 2); without it they stay unweighted on the general path."""
+    if sharded_rows and support:
+        raise ValueError("sharded_rows is the general path's switch: the support path always takes the row weights")
     cp, rv, nz = _i(colptr), _i(rowval), _f(nzval)
     n, nc = len(cp) - 1, len(tau)
     rv1, nz1 = (rv, nz) if len(rv) else (np.zeros(1, dtype=np.int64), np.zeros(1))
@@ -655,7 +665,7 @@ def trial_batch(colptr, rowval, nzval, Q, *, p, bh, y, Mx, Mx_old, x, x_old, Mty
         setattr(t, k, _p(v))
     t.roww = _p(rw) if rw is not None else None
     t.xold_coef, t.tau_update = float(xold_coef), float(tau_update)
-    t.support, t.nc, t.plain, t.c0 = int(bool(support)), nc, int(bool(plain)), int(c0)
+    t.support, t.nc, t.plain, t.c0 = (2 if sharded_rows else int(bool(support))), nc, int(bool(plain)), int(c0)
     for k in range(nc):
         t.tau[k], t.theta[k], t.bt[k], t.sigma[k] = float(tau[k]), float(theta[k]), float(bt[k]), float(sigma[k])
     t.tau_re, t.sigma_re = float(tau_re), float(sigma_re)

@@ -579,13 +579,28 @@ inline void Solver::primal_step_dev() {
     double* xo = xbuf[1 - xc].p;
     hipLaunchKernelGGL(dev::k_primal_update, dim3(grid_for(P.n)), dim3(dev::TPB), 0, stream,
                        xo, xi, Mtybuf[mtyc].p, c_d.p, primal_step, (long long)P.n);
-    if (!P.blocks.empty()) {
-        double t0 = now_s();
-        psd_projection(xo);
-        st.t_psd += now_s() - t0;
+    auto project = [&]() {
+        if (!P.blocks.empty()) {
+            double t0 = now_s();
+            psd_projection(xo);
+            st.t_psd += now_s() - t0;
+        }
+        if (!P.socs.empty()) launch_soc_project(xo, (int)P.socs.size());
+    };
+    if (sharded()) {
+        // the general path inside a block-sharded solve (a shard with an SOC, a 1x1 block or no PSD block at all): as on the
+        // support path above, a failing shard keeps its error and still joins this iteration's collectives
+        st.reserved_s[PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS]++;
+        try {
+            if (opt.debug_fail_iteration > 0 && iter == opt.debug_fail_iteration)
+                throw std::runtime_error("injected projection failure (options.debug_fail_iteration)");
+            project();
+        } catch (...) { shard_error = std::current_exception(); }
+    } else {
+        project();
     }
-    if (!P.socs.empty()) launch_soc_project(xo, (int)P.socs.size());
     spmv(xo, Mxbuf[1 - mxc].p);
+    if (!coup_rows.empty()) reduce_coupling(Mxbuf[1 - mxc].p);
 }
 
 // ---- linesearch! / dual_step! (pdhg.jl:532-609) + compute_residual! + compute_gap! (residuals.jl:2-71) on every vector path
@@ -659,8 +674,9 @@ inline void Solver::batch_residuals(const dev::TrialBatch& tb, int nc, int c0, d
     const BatchShape b = batch_shape();
     const double* yc0 = ycand_d.p + (size_t)c0 * b.ystride;
     const double* mc0 = Mtycand_d.p + (size_t)c0 * b.mstride;
-    // (the general path's residuals have never taken the row weights that k_dual_trial_batch gets on both paths: kept as it is)
-    const double* roww = b.supp != nullptr ? roww_d.p : nullptr;
+    // (outside a block-sharded solve the general path's residuals have never taken the row weights that k_dual_trial_batch
+    // gets on both paths: kept as it is, and with it that solve's bits; inside one, b'y and h'y count a coupling row once)
+    const double* roww = (b.supp != nullptr || general_row_weights) ? roww_d.p : nullptr;
     hipLaunchKernelGGL(b.supp != nullptr ? dev::k_residual_xy<true> : dev::k_residual_xy<false>,
                        dim3(std::max(b.gx, b.gq), nc, 2), dim3(dev::TPB), 0, stream,
                        xbuf[1 - xc].p, b.supp, b.cnt, b.xold, xold_coef, mc0, b.mstride, b.mty_cur, b.cv, b.gx,
@@ -717,7 +733,14 @@ inline const double* Solver::batch_read_back(int nc) {
                        (const double*)nullptr, 0, 0, (double*)nullptr);
     if (!zc) PX_HIP(hipMemcpyAsync(hscal_pin.p, bscal.p, NCAND * NSCAL * sizeof(double), hipMemcpyDeviceToHost, stream));
     wait_stream();
-    return hscal_pin.p;
+    if (!sharded()) return hscal_pin.p;
+    // block-sharded solve: the host must see ONE combined record, so the pinned one is copied and reduced in hbscal.  The two
+    // off-support slots are global after the reduce (a support-path shard of the same solve fills them); this path's slots 2
+    // and 3 cover every entry already, so it contributes 0 to them
+    std::copy(hscal_pin.p, hscal_pin.p + (size_t)nc * NSCAL, hbscal.begin());
+    hbscal[NCAND * NSCAL] = hbscal[NCAND * NSCAL + 1] = 0.0;
+    reduce_candidates(nc);
+    return hbscal.data();
 }
 
 // Up to NCAND consecutive step-size candidates tau, 0.75 tau, 0.75^2 tau are evaluated by ONE batch of launches -- y+, M'y+ and
@@ -797,8 +820,11 @@ inline void Solver::record_residuals(const double* s) {
     if (debug && iter <= 5)
         std::fprintf(stderr, "[dbg] it %lld res: %.6e %.6e cx %.6e | %.6e %.6e eq %.6e in %.6e by %.6e hy %.6e\n",
                      iter, s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10]);
-    const double m0 = use_support ? std::max(s[2], hbscal[NCAND * NSCAL]) : s[2];          // (+ the off-support maxima)
-    const double m1 = use_support ? std::max(s[3], hbscal[NCAND * NSCAL + 1]) : s[3];
+    // (+ the off-support maxima: global after the reduce of a block-sharded solve, so every shard folds them, whatever its own
+    // path -- or a support-path shard and a general-path shard of one solve would compute different residuals)
+    const bool fold = use_support || sharded();
+    const double m0 = fold ? std::max(s[2], hbscal[NCAND * NSCAL]) : s[2];
+    const double m1 = fold ? std::max(s[3], hbscal[NCAND * NSCAL + 1]) : s[3];
     const double pres = std::sqrt(g_n) * m0 / std::max({m1, g_norm_b, g_norm_h, 1.0});
     const double dres = std::sqrt(g_Q) * s[5] / std::max({s[6], g_norm_c, 1.0});
     h_pres.at(iter) = pres;
@@ -830,13 +856,22 @@ inline bool Solver::convergedrank() const {
 
 // soc_convergence (residuals.jl:73-86)
 inline bool Solver::soc_convergence() {
-    if (P.socs.empty()) return true;
-    launch_soc_gap(xbuf[xc].p, (int)P.socs.size());
-    std::vector<double> g(P.socs.size());
-    soc_gap_d.download(g.data(), g.size(), stream);
-    PX_HIP(hipStreamSynchronize(stream));
-    for (double v : g) if (v >= opt.tol_soc) return false;
-    return true;
+    bool open = false;                                   // some gap >= tol_soc
+    if (!P.socs.empty()) {
+        launch_soc_gap(xbuf[xc].p, (int)P.socs.size());
+        std::vector<double> g(P.socs.size());
+        soc_gap_d.download(g.data(), g.size(), stream);
+        PX_HIP(hipStreamSynchronize(stream));
+        for (double v : g) open = open || v >= opt.tol_soc;
+    }
+    // block-sharded solve: the answer is the model's.  All shards arrive here together (the conditions in front of this call
+    // are built from reduced scalars), SOC-free ones included: one extra scalar reduce
+    if (sharded()) {
+        std::vector<double> sums, maxs = {open ? 1.0 : 0.0};
+        reduce(sums, maxs);
+        open = maxs[0] > 0.5;
+    }
+    return !open;
 }
 
 // certificate_parameters (pdhg.jl:670-676)
@@ -1419,8 +1454,9 @@ inline void Solver::test_trial_batch(proxsdp_trial_batch& t) {
     const int64_t n = P.n, Q = P.Q;
     if (n < 1 || Q < 1 || t.p < 0 || t.p > Q || t.nc < 1 || t.nc > NCAND || t.c0 >= t.nc)
         throw std::invalid_argument("trial batch: n, Q >= 1, 0 <= p <= Q, 1 <= nc <= 3, c0 < nc");
+    if (t.support < 0 || t.support > 2) throw std::invalid_argument("trial batch: support must be 0, 1 or 2");
     if (!t.bh || !t.y || !t.Mx || !t.Mx_old || !t.x || !t.x_old || !t.Mty_old || !t.y_out || !t.Mty_out || !t.scal ||
-        (t.c0 >= 0 && !t.scal_re) || (t.support && (!t.supp_out || !t.x_upd || !t.xsave || !t.esv)))
+        (t.c0 >= 0 && !t.scal_re) || (t.support == 1 && (!t.supp_out || !t.x_upd || !t.xsave || !t.esv)))
         throw std::invalid_argument("trial batch: NULL array");
     P.p = t.p; P.m = Q - t.p;
     setup_device();
@@ -1433,7 +1469,8 @@ inline void Solver::test_trial_batch(proxsdp_trial_batch& t) {
     Mxbuf[1 - mxc].upload(t.Mx, Q, stream); Mxbuf[mxc].upload(t.Mx_old, Q, stream);
     xbuf[xc].upload(t.x_old, n, stream);
     PX_HIP(hipStreamSynchronize(stream));
-    use_support = t.support != 0;
+    use_support = t.support == 1;
+    general_row_weights = t.support == 2;                // (the general path of a block-sharded solve: weighted b'y, h'y)
     if (use_support) {
         const std::vector<int> supp = support_list();
         upload_support(supp);
@@ -1634,8 +1671,8 @@ inline void Solver::run() {
         g_frob = sharded() ? std::sqrt(sums[6]) : P.frob;
         g_conic = maxs[0] > 0.5;
     }
-    // (a block-sharded solve always runs the support-aware batched path: the library-only knob support_path is overridden below;
-    //  round 6: check_dual_feas and line_search_flag = false are served there too)
+    // (a block-sharded solve chooses its vector path per shard: the library-only knob support_path is overridden below;
+    //  check_dual_feas and line_search_flag = false are served on both)
     if (opt.max_iter <= 0) max_iter_local = g_conic ? opt.max_iter_conic : opt.max_iter_lp;
     else max_iter_local = opt.max_iter;
     ada_count = 0;
@@ -1685,6 +1722,17 @@ inline void Solver::run() {
         (opt.small_block_batch < 0 && opt.full_eig_sign != 0 &&
          std::min({opt.tol_gap, opt.tol_feasibility, opt.tol_primal, opt.tol_dual}) >= 1e-8);
     small_jacobi_max = small_sign ? (opt.small_block_batch == 2 ? 1 : 2) : 64;   // (measured, tools/gpurun_jacobi_vs_sign.py: from side 3 on the sign kernel wins)
+    // block-sharded solve: the vector path of THIS shard, known before the block lists are built.  A shard whose cones allow
+    // the support path (at least one PSD block, no SOC, no 1x1 block -- setup_support's own conditions) runs it, as every
+    // sharded solve used to, with its small blocks not batched; any other shard runs the general path with the small-block
+    // launches of a single-process solve.  Shards of one solve may differ: only reduced scalars steer the iteration.
+    bool shard_general = false;
+    if (sharded()) {
+        shard_general = P.blocks.empty() || !P.socs.empty();
+        for (const BlockInfo& B : P.blocks) shard_general = shard_general || B.n == 1;
+        opt.support_path = shard_general ? 0 : 1;
+        general_row_weights = shard_general;
+    }
     {
         std::vector<long long> offs;
         const double* ur = user_resid;
@@ -1699,7 +1747,7 @@ inline void Solver::run() {
             // 1.1 ms for one rocSOLVER call; two blocks of side 10 and 5: 1.4x faster batched; seven of side 2: 6.4x) and,
             // round 5, the one-workgroup LDS-resident sign projection (small_sign.hip.hpp) for sides 3 .. 64
             if (opt.small_block_batch != 0 && B.n <= (small_sign ? std::max(small_jacobi_max, std::min(64, small_sign_cap)) : (opt.small_block_batch > 0 ? 64 : 32)) &&
-                B.n <= opt.min_size_krylov_eigs && !sharded())
+                B.n <= opt.min_size_krylov_eigs && (!sharded() || shard_general))
                 small_blocks.push_back((int)idx);
             else
                 large_blocks.push_back((int)idx);
@@ -1772,13 +1820,12 @@ inline void Solver::run() {
         soc_off.upload(so.data(), so.size(), stream); soc_len.upload(sl.data(), sl.size(), stream);
         PX_HIP(hipStreamSynchronize(stream));
     }
-    if (sharded()) opt.support_path = 1;                 // the sharded loop is built on the batched path
     if (P.dense()) opt.support_path = 0;                 // every column of a dense M is in the support
-    setup_support();
+    setup_support();                                     // (a block-sharded solve chose opt.support_path above)
     setup_dense();
     alloc_candidates();
-    if (sharded() && !use_support)
-        throw std::domain_error("block-sharded solve needs the support-aware path (no SOC / 1x1 cones)");
+    if (sharded() && use_support == shard_general)
+        throw std::logic_error("block-sharded solve: the shard's vector path is not the one chosen for it");
     double spectral_norm = g_frob;                       // LinearAlgebra.norm(M), pdhg.jl:121
     if (!opt.approx_norm) {                              // Arpack.svds(M, nsv=1), pdhg.jl:108-119
         if (P.dense()) spectral_norm = spectral_norm_device();

@@ -711,6 +711,9 @@ private:
     bool have_snapshot = false;
     // support-aware vector passes
     bool use_support = false;
+    // the general path inside a block-sharded solve: its residual pass takes the row weights (b'y and h'y count a coupling
+    // row on its owner only), as the support path's always does; a solve that is not sharded keeps the null pointer
+    bool general_row_weights = false;
     int ns = 0, rstride = 0, n_res_wg = 0;
     std::vector<int> tile_base;                 // first residual-partial slot of each PSD block
     DevBuf<int> supp_d;
