@@ -686,6 +686,45 @@ int proxsdp_hip_cone_tail(const double* x, int64_t n, const int64_t* soc_off, co
                           const int64_t* one_off, int32_t n_one, double* x_soc, double* gap_in, double* gap_out,
                           double* x_clamp, double* min_eig);
 
+/* ONE product of the sign-function projection (full_eig! without an eigendecomposition, prox_operators.jl:111-126) through the
+ * solver's own launch code (Solver::sym_gemm), on host data: k_sym_gemm (tile = 64), k_sym_gemm32 (32) or k_sym_gemm48 (48).
+ * P, Q, Y: symmetric n x n, column-major; they are zero-padded to ld = 64 ceil(n / 64) as the solver's work matrices are.
+ * With m_i = dsc[i] (use_dsc != 0) or 1:
+ *   epilogue 0 (plain): T = m0 P Q                                   part: Frobenius^2 partials of T
+ *   epilogue 1 (poly) : T = ca m0 I + cb m1 Y + cc m2 P Q            (the identity term on the WHOLE diagonal, padding included)
+ *   epilogue 2 (final): packed xp = (P + m0 P Q) / 2, off-diagonals x sqrt(2)     part: partials of the trace of Q[:n, :n]
+ *   epilogue 3        : as 2 with the fused residual partials: over the entries whose bit mask_off + index is CLEAR in mask,
+ *                       respart[0][w] = max |xp - xold|, respart[1][w] = max |xold| of workgroup w's tile
+ * The upper triangle of T holds the computed product, the lower one its mirror.  T (ld x ld), part, xp and respart are
+ * prefilled with `sentinel`, so that the caller sees what the launch wrote.  part may be NULL for epilogues 0 and 1 (no
+ * partials are formed then).  Refused with PROXSDP_E_INVALID: tile = 48 where the solver's rule refuses it (48 ceil(n / 48) > ld,
+ * or the 72 KiB of dynamic LDS were not granted), tile = 32 or 48 with epilogue 2 or 3. */
+typedef struct {
+    int64_t struct_size;
+    /* in */
+    int32_t n, tile, epilogue, use_dsc;
+    const double* P; const double* Q; const double* Y;   /* n x n each; Y: epilogue 1 only */
+    double ca, cb, cc;
+    double dsc[3];
+    const double* xold;                  /* epilogue 3: packed, n (n + 1) / 2 */
+    const uint32_t* mask; int64_t mask_words, mask_off;   /* epilogue 3: support bits; 32 mask_words >= mask_off + n (n + 1) / 2 */
+    double sentinel;
+    /* out */
+    double* T;                           /* ld x ld (epilogues 0, 1) */
+    double* part;                        /* one slot per launched workgroup; capacity >= (ld / 32 + 1)^2 / 2 + 8 */
+    double* xp;                          /* n (n + 1) / 2 (epilogues 2, 3) */
+    double* respart;                     /* 2 x grid (epilogue 3) */
+    int32_t ld, grid;                    /* leading dimension of T, workgroups launched */
+} proxsdp_sym_product;
+int proxsdp_hip_sym_product(proxsdp_sym_product* t);
+
+/* The head of a sign-function projection of one packed block of side n, as Solver::full_eig_by_sign launches it:
+ * k_unpack_sym (A = smat(packed) in full storage; A, ld x ld, is prefilled with `sentinel`: the kernel writes the n x n leading
+ * part only), k_sign_scalars stage 0, the first product Y0 = A A / f^2 on the tile shape the solver chooses (on a zero-padded
+ * A), k_sign_scalars stage 1.  sc[16]: sc[0] = 1 / f^2, sc[6] = f = ||A||_F, sc[1] = 1 / s, sc[4] = s = f sqrt(g) with
+ * g = ||Y0||_F, sc[8..10] = {1, 1 / g, 1 / g^2}; the other slots are zero. */
+int proxsdp_hip_sign_unpack(const double* packed, int64_t n, double sentinel, double* A, double* sc);
+
 /* The "Init" section (pdhg.jl:54-142) of a solve with a dense A (prob->M_dense), nothing more: E (p + m) and D (n), the
  * equilibration diagonals -- ones when equilibration is off or switched itself off, *equilibrated says which --, frob =
  * ||.||_F and sigma_max = the largest singular value of the solver's matrix E [A;G] D S (S: the sqrt(2)/2 factor on

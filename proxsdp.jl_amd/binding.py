@@ -226,6 +226,8 @@ def lib():
     L.proxsdp_host_preprocess.argtypes = [C.POINTER(Problem), pi64, pi64, pf64, pf64]
     L.proxsdp_hip_dense_scaling.argtypes = [C.POINTER(Problem), C.POINTER(Options), pf64, pf64, pf64, pf64, C.POINTER(i32)]
     L.proxsdp_host_equilibrate_rowsums.argtypes = [pf64, i64, i64, C.POINTER(Options), pf64, pf64]
+    L.proxsdp_hip_sym_product.argtypes = [C.POINTER(SymProductIO)]
+    L.proxsdp_hip_sign_unpack.argtypes = [pf64, i64, f64, pf64, pf64]
     L.proxsdp_hip_rccl_unique_id.argtypes = [C.c_void_p]
     L.proxsdp_hip_rccl_comm_init.argtypes = [i32, C.c_void_p, i32, i32, C.POINTER(C.c_void_p)]
     L.proxsdp_hip_rccl_comm_destroy.argtypes = [C.c_void_p]
@@ -608,15 +610,16 @@ def full_eig_kernel(packed, n, sign=1, repeat=1):
     return out, ms.value, rk.value, npr.value
 
 
-def spmv(M, x, transpose=False):
+def spmv(M, x, transpose=False, index_base=0):
+    """index_base = 1: colptr and rowval are handed over 1-based, as the Julia shim does"""
     L = lib()
     M = sp.csc_matrix(M, dtype=np.float64)
     M.sort_indices()
-    cp, rv, nz = _i(M.indptr), _i(M.indices), _f(M.data)
+    cp, rv, nz = _i(M.indptr) + int(index_base), _i(M.indices) + int(index_base), _f(M.data)
     S = CSC(M.shape[0], M.shape[1], _p(cp, pi64), _p(rv, pi64), _p(nz))
     xin = _f(x)
     out = np.zeros(M.shape[1] if transpose else M.shape[0])
-    _check(L.proxsdp_hip_spmv(C.byref(S), 0, 1 if transpose else 0, _p(xin), _p(out)))
+    _check(L.proxsdp_hip_spmv(C.byref(S), int(index_base), 1 if transpose else 0, _p(xin), _p(out)))
     return out
 
 
@@ -701,6 +704,85 @@ def cone_tail(x, soc_off, soc_len, one_off):
     _check(L.proxsdp_hip_cone_tail(_p(x), len(x), _p(so, pi64), _p(sl, C.POINTER(i32)), ns_, _p(oo, pi64), no_,
                                    _p(x_soc), _p(g0), _p(g1), _p(x_cl), _p(me)))
     return x_soc, g0[:ns_], g1[:ns_], x_cl, me[:no_]
+
+
+SYM_EPILOGUES = {"plain": 0, "poly": 1, "final": 2, "final_res": 3}    # proxsdp_sym_product.epilogue
+SYM_SENTINEL = -7.25e300                                                 # default prefill of the outputs: no product comes near it
+
+
+class SymProductIO(C.Structure):
+    """proxsdp_sym_product (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64),
+                ("n", i32), ("tile", i32), ("epilogue", i32), ("use_dsc", i32),
+                ("P", pf64), ("Q", pf64), ("Y", pf64),
+                ("ca", f64), ("cb", f64), ("cc", f64), ("dsc", f64 * 3),
+                ("xold", pf64), ("mask", C.POINTER(C.c_uint32)), ("mask_words", i64), ("mask_off", i64),
+                ("sentinel", f64),
+                ("T", pf64), ("part", pf64), ("xp", pf64), ("respart", pf64),
+                ("ld", i32), ("grid", i32)]
+
+
+def sym_product(P, Q, *, tile, epilogue="plain", Y=None, ca=0.0, cb=0.0, cc=0.0, dsc=None, xold=None, mask=None,
+                mask_off=0, sentinel=SYM_SENTINEL, want_part=True):
+    """proxsdp_hip_sym_product: ONE product of the sign iteration through Solver::sym_gemm, on tiles of side `tile` (32, 48, 64).
+    P, Q (and Y for "poly"): symmetric n x n.  Returns a dict: ld, grid, and -- "plain" / "poly" -- T (ld x ld, padding
+    included; entries the launch did not write hold `sentinel`) and part (grid slots, None without want_part); -- "final" /
+    "final_res" -- xp (packed), part (trace partials) and, for "final_res", respart (2 x grid)."""
+    Pm = np.asfortranarray(P, dtype=np.float64)
+    Qm = np.asfortranarray(Q, dtype=np.float64)
+    n = Pm.shape[0]
+    assert Pm.shape == (n, n) == Qm.shape
+    epi = SYM_EPILOGUES[epilogue]
+    ld = 64 * ((n + 63) // 64)
+    cap = (ld // 32 + 1) ** 2 // 2 + 8
+    t = SymProductIO()
+    t.struct_size = C.sizeof(SymProductIO)
+    t.n, t.tile, t.epilogue, t.use_dsc = n, int(tile), epi, int(dsc is not None)
+    t.P, t.Q = _p(Pm), _p(Qm)
+    if epi == 1:
+        Ym = np.asfortranarray(Y, dtype=np.float64)
+        assert Ym.shape == (n, n)
+        t.Y = _p(Ym)
+    t.ca, t.cb, t.cc = float(ca), float(cb), float(cc)
+    for k in range(3):
+        t.dsc[k] = float(dsc[k]) if dsc is not None else 0.0
+    t.sentinel = float(sentinel)
+    N = n * (n + 1) // 2
+    out = {}
+    if epi < 2:
+        out["T"] = np.zeros((ld, ld), order="F")
+        t.T = _p(out["T"])
+    else:
+        out["xp"] = np.zeros(N)
+        t.xp = _p(out["xp"])
+    if want_part or epi >= 2:
+        part = np.zeros(cap)
+        t.part = _p(part)
+    if epi == 3:
+        xo = _f(xold)
+        mk = np.ascontiguousarray(mask, dtype=np.uint32)
+        assert len(xo) == N
+        t.xold, t.mask, t.mask_words, t.mask_off = _p(xo), _p(mk, C.POINTER(C.c_uint32)), len(mk), int(mask_off)
+        resp = np.zeros(2 * cap)
+        t.respart = _p(resp)
+    _check(lib().proxsdp_hip_sym_product(C.byref(t)))
+    assert t.ld == ld and t.grid <= cap
+    out.update(ld=ld, grid=int(t.grid), part=part[:t.grid].copy() if (want_part or epi >= 2) else None)
+    if epi == 3:
+        out["respart"] = resp[:2 * t.grid].reshape(2, t.grid).copy()
+    return out
+
+
+def sign_unpack(packed, n, sentinel=SYM_SENTINEL):
+    """proxsdp_hip_sign_unpack: (A, sc) -- A (ld x ld) as k_unpack_sym leaves a matrix prefilled with `sentinel`, sc[16] the
+    device scalars after the first product (sc[0] = 1/f^2, sc[6] = f, sc[1] = 1/s, sc[4] = s, sc[8..10] = {1, 1/g, 1/g^2})."""
+    xin = _f(packed)
+    assert len(xin) == n * (n + 1) // 2
+    ld = 64 * ((n + 63) // 64)
+    A = np.zeros((ld, ld), order="F")
+    sc = np.zeros(16)
+    _check(lib().proxsdp_hip_sign_unpack(_p(xin), n, float(sentinel), _p(A), _p(sc)))
+    return A, sc
 
 
 def dense_scaling(prob, options=None):

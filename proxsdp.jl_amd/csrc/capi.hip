@@ -453,6 +453,26 @@ int proxsdp_hip_cone_tail(const double* x, int64_t n, const int64_t* soc_off, co
     });
 }
 
+int proxsdp_hip_sym_product(proxsdp_sym_product* t) {
+    return guarded([&]() -> int {
+        if (!t) throw std::invalid_argument("NULL argument");
+        if (t->struct_size != (int64_t)sizeof(proxsdp_sym_product)) throw std::invalid_argument("sym product: struct_size mismatch");
+        if (t->n < 1 || t->n > 4096) throw std::invalid_argument("sym product: n out of range");
+        Engine E(nullptr, t->n, 2);
+        E.S.test_sym_product(*t);
+        return 0;
+    });
+}
+
+int proxsdp_hip_sign_unpack(const double* packed, int64_t n, double sentinel, double* A, double* sc) {
+    return guarded([&]() -> int {
+        if (!packed || !A || !sc || n < 1 || n > 4096) throw std::invalid_argument("invalid argument");
+        Engine E(nullptr, n, 2);
+        E.S.test_sign_unpack(packed, sentinel, A, sc);
+        return 0;
+    });
+}
+
 int proxsdp_hip_dense_scaling(const proxsdp_problem* prob, const proxsdp_options* opt,
                               double* E, double* D, double* frob, double* sigma_max, int32_t* equilibrated) {
     return guarded([&]() -> int {

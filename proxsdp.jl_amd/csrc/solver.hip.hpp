@@ -436,6 +436,8 @@ public:
     void test_cone_tail(const double* x, int64_t n, const int64_t* so, const int32_t* sl, int nsoc,
                         const int64_t* oo, int none, double* x_soc, double* gap_in, double* gap_out,
                         double* x_clamp, double* mineig);
+    void test_sym_product(proxsdp_sym_product& t);
+    void test_sign_unpack(const double* packed, double sentinel, double* A, double* sc);
 
     bool debug = std::getenv("PROXSDP_HIP_DEBUG") != nullptr;
     proxsdp_options opt;
@@ -698,6 +700,12 @@ private:
     template <int EPI, bool FUSE>
     void sym_gemm(EigWork& W, const double* Pm, const double* Qm, double* T, const double* Y, double ca, double cb,
                   double cc, const double* dsc, double* part, double* xp_out, const double* xp_old, int blk);
+    // tile shape of the sign iteration's products, and what follows from it (shared with the kernel-level test entries)
+    bool sign_tile48_fits(int n, int ld) const { return sg48_ok && ceil_div(n, dev::SG_T48) * dev::SG_T48 <= ld; }
+    static int sym_gemm_grid(const EigWork& W, bool final_epi);
+    void sign_choose_tiles(EigWork& W);
+    void sign_unpack(EigWork& W, const double* xp_in, double* A, double* sc);
+    void sign_scale(EigWork& W, double* sc);
     void spmv(const double* x, double* y);
     void spmv_sparse(const double* x, double* y);
     bool convergedrank() const;
@@ -1911,32 +1919,76 @@ inline void Solver::full_eig_values(EigWork& W, const double* xp, double offscal
     if (info != 0) throw HipError("rocsolver_dsyevd did not converge (info=" + std::to_string(info) + ")");
 }
 
+// workgroups Solver::sym_gemm launches for one product on W's tile shape: one per tile of the block upper triangle, rounded up
+// to a multiple of 8 (the XCD-interleaved tile order; the padding workgroups return at once).  The final product always runs
+// on 64 x 64 tiles: its residual partials are indexed by them.
+inline int Solver::sym_gemm_grid(const EigWork& W, bool final_epi) {
+    const int side = final_epi ? W.nt : (W.sg_nt48 > 0 ? W.sg_nt48 : (W.sg_small ? 2 * W.nt : W.nt));
+    return 8 * ceil_div(side * (side + 1) / 2, 8);
+}
+
 // full_eig! (prox_operators.jl:111-126)
 template <int EPI, bool FUSE>
 inline void Solver::sym_gemm(EigWork& W, const double* Pm, const double* Qm, double* T, const double* Y, double ca,
                              double cb, double cc, const double* dsc, double* part, double* xp_out,
                              const double* xp_old, int blk) {
     W.lst.sign_products++;
+    const int grid = sym_gemm_grid(W, EPI == dev::SG_FINAL);
     if constexpr (EPI != dev::SG_FINAL) {
         if (W.sg_nt48 > 0) {                                // 48 x 48 tiles: fewer, larger tiles where that shortens the busiest CU's queue
-            const int grid48 = 8 * ceil_div(W.sg_nt48 * (W.sg_nt48 + 1) / 2, 8);
-            hipLaunchKernelGGL((dev::k_sym_gemm48<EPI, 4>), dim3(grid48), dim3(dev::TPB), dev::sg48_lds_bytes(4), stream, Pm, Qm, W.sg_ld,
+            hipLaunchKernelGGL((dev::k_sym_gemm48<EPI, 4>), dim3(grid), dim3(dev::TPB), dev::sg48_lds_bytes(4), stream, Pm, Qm, W.sg_ld,
                                W.sg_nt48, T, Y, ca, cb, cc, dsc, part);
             return;
         }
         if (W.sg_small) {                                   // 32 x 32 tiles: small blocks need the workgroups
-            const int nt32 = 2 * W.nt;
-            const int grid32 = 8 * ceil_div(nt32 * (nt32 + 1) / 2, 8);
-            hipLaunchKernelGGL((dev::k_sym_gemm32<EPI>), dim3(grid32), dim3(dev::TPB), 0, stream, Pm, Qm, W.sg_ld, nt32, T, Y,
+            hipLaunchKernelGGL((dev::k_sym_gemm32<EPI>), dim3(grid), dim3(dev::TPB), 0, stream, Pm, Qm, W.sg_ld, 2 * W.nt, T, Y,
                                ca, cb, cc, dsc, part);
             return;
         }
     }
-    const int grid = 8 * ceil_div(W.nt * (W.nt + 1) / 2, 8);
     hipLaunchKernelGGL((dev::k_sym_gemm<EPI, FUSE>), dim3(grid), dim3(dev::TPB), 0, stream, Pm, Qm, W.sg_ld, W.nt, T, Y,
                        ca, cb, cc, dsc, part, W.n, xp_out, xp_old, FUSE ? (const unsigned*)mask_d.p : nullptr,
                        FUSE ? (long long)P.blocks[blk].off : 0LL, FUSE ? respart_d.p + tile_base[blk] : nullptr,
                        FUSE ? rstride : 0);
+}
+
+// Tile shape of W's products (W.nt set): 32 x 32 up to the padded side sign_small_tile_max, 48 x 48 where they fit and shorten
+// the busiest CU's queue, else 64 x 64; W.sg_npart = workgroups (= `part` slots) of a product of that shape.
+inline void Solver::sign_choose_tiles(EigWork& W) {
+    const int n = W.n, ld = W.nt * dev::TILE;
+    const int small_max = opt.sign_small_tile_max > 0 ? opt.sign_small_tile_max : 3072;   // measured: 32-tiles win up to n ~ 3500
+    W.sg_small = ld <= small_max;
+    const int nt32 = 2 * W.nt;
+    // tile shape by makespan: the busiest of the 256 CUs runs ceil(tiles / 256) tiles of T x T entries each.  n = 1000: 528 tiles of
+    // 32 x 32 (3 x 1024) against 231 of 48 x 48 (1 x 2304); n = 800: 325 (2 x 1024) against 153 (2304) -- the 32-tiles stay.  Measured
+    // (tools/gpurun_tile48_sizes.sh, ms per projection 32 / 48): 700: 0.44 / 0.44, 800: 0.77 / 0.83, 1000: 1.21 / 1.00, 1200: 1.57 / 2.0,
+    // 1500: 2.9 / ~3.6, 2000 (a tie of the rule): 6.6 / 6.4, 2500: 12.9 / 13.2 -- the rule picks the faster one each time.
+    // PROXSDP_HIP_SIGN_TILE48 = 0 / 1: never / whenever the tiles fit (measurement)
+    W.sg_nt48 = 0;
+    const int nb48 = ceil_div(n, dev::SG_T48);
+    const char* env = std::getenv("PROXSDP_HIP_SIGN_TILE48");
+    const int knob = env != nullptr ? std::atoi(env) : -1;
+    if (W.sg_small && knob != 0 && sign_tile48_fits(n, ld)) {
+        const int cus = 256;
+        const long long c32 = (long long)ceil_div(nt32 * (nt32 + 1) / 2, cus) * 32 * 32;
+        const long long c48 = (long long)ceil_div(nb48 * (nb48 + 1) / 2, cus) * 48 * 48;
+        if (knob == 1 || c48 <= c32) W.sg_nt48 = nb48;
+    }
+    W.sg_npart = sym_gemm_grid(W, false);
+}
+
+// A = smat(xp_in) in full storage (the padding of A is not written) and sc[0] = 1 / f^2, sc[6] = f = ||A||_F
+inline void Solver::sign_unpack(EigWork& W, const double* xp_in, double* A, double* sc) {
+    const int ntile = W.nt * (W.nt + 1) / 2;
+    hipLaunchKernelGGL(dev::k_unpack_sym, dim3(ntile), dim3(dev::TPB), 0, stream, xp_in, W.n, A, W.nt * dev::TILE,
+                       dev::INV_SQRT2, W.sg_part.p);
+    hipLaunchKernelGGL(dev::k_sign_scalars, dim3(1), dim3(dev::TPB), 0, stream, (const double*)W.sg_part.p, ntile, 0, sc);
+}
+
+// Y0 = A A / f^2 and its Frobenius norm g: s = f sqrt(g) >= ||A||_2   (sc[1], sc[4], sc[8..10])
+inline void Solver::sign_scale(EigWork& W, double* sc) {
+    sym_gemm<dev::SG_PLAIN, false>(W, W.sgA.p, W.sgA.p, W.sgY.p, nullptr, 0, 0, 0, sc + 0, W.sg_part.p, nullptr, nullptr, -1);
+    hipLaunchKernelGGL(dev::k_sign_scalars, dim3(1), dim3(dev::TPB), 0, stream, (const double*)W.sg_part.p, W.sg_npart, 1, sc);
 }
 
 // full_eig! without an eigendecomposition: X+ = (X + X sign(X)) / 2, sign by an odd-polynomial
@@ -1957,7 +2009,7 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
         if (opt.full_eig_sign < 0 && std::min({opt.tol_gap, opt.tol_feasibility, opt.tol_primal, opt.tol_dual}) < 1e-8) return false;
     }
     const int ld = W.nt * dev::TILE;
-    const int ntile = W.nt * (W.nt + 1) / 2, grid = 8 * ceil_div(ntile, 8);
+    const int grid = sym_gemm_grid(W, true);
     if (W.sg_ld != ld) {
         // first use: the five work matrices must fit -- whoever asks (auto mode, full_eig_sign = 1, or the opt-in
         // psd_sign_engine with force = true: ADVICE r4); no room, or an allocation that fails anyway (several block
@@ -1976,35 +2028,12 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
             return false;
         }
         W.sgA.zero(stream);                                  // the padding stays zero: only entries < n are rewritten
-        const int small_max = opt.sign_small_tile_max > 0 ? opt.sign_small_tile_max : 3072;   // measured: 32-tiles win up to n ~ 3500
-        W.sg_small = ld <= small_max;
-        const int nt32 = 2 * W.nt;
-        W.sg_npart = W.sg_small ? 8 * ceil_div(nt32 * (nt32 + 1) / 2, 8) : grid;
-        // tile shape by makespan: the busiest of the 256 CUs runs ceil(tiles / 256) tiles of T x T entries each.  n = 1000: 528 tiles of
-        // 32 x 32 (3 x 1024) against 231 of 48 x 48 (1 x 2304); n = 800: 325 (2 x 1024) against 153 (2304) -- the 32-tiles stay.  Measured
-        // (tools/gpurun_tile48_sizes.sh, ms per projection 32 / 48): 700: 0.44 / 0.44, 800: 0.77 / 0.83, 1000: 1.21 / 1.00, 1200: 1.57 / 2.0,
-        // 1500: 2.9 / ~3.6, 2000 (a tie of the rule): 6.6 / 6.4, 2500: 12.9 / 13.2 -- the rule picks the faster one each time.
-        // PROXSDP_HIP_SIGN_TILE48 = 0 / 1: never / whenever the tiles fit (measurement)
-        W.sg_nt48 = 0;
-        {
-            const int nb48 = ceil_div(n, dev::SG_T48);
-            const char* env = std::getenv("PROXSDP_HIP_SIGN_TILE48");
-            const int knob = env != nullptr ? std::atoi(env) : -1;
-            if (W.sg_small && sg48_ok && knob != 0 && nb48 * dev::SG_T48 <= ld) {
-                const int cus = 256;
-                const long long c32 = (long long)ceil_div(nt32 * (nt32 + 1) / 2, cus) * 32 * 32;
-                const long long c48 = (long long)ceil_div(nb48 * (nb48 + 1) / 2, cus) * 48 * 48;
-                if (knob == 1 || c48 <= c32) {
-                    W.sg_nt48 = nb48;
-                    W.sg_npart = 8 * ceil_div(nb48 * (nb48 + 1) / 2, 8);
-                    // rows / columns [48 nb48, ld) are never written by these tiles and are read by every product's K loop
-                    W.sgX.zero(stream); W.sgX2.zero(stream); W.sgY.zero(stream); W.sgQ.zero(stream);
-                    // (measured and dropped: walking the tiles in S x S patches per XCD instead of column-major ranges -- half the
-                    // operand blocks per XCD's L2 -- changes nothing, 0.95 - 0.98 ms per projection either way: the Infinity Cache
-                    // serves the misses under the 24 loads in flight; eight k-steps per group instead of four: slower, 1.01 ms)
-                }
-            }
-        }
+        sign_choose_tiles(W);
+        // rows / columns [48 nb48, ld) are never written by the 48-tiles and are read by every product's K loop
+        // (measured and dropped: walking the tiles in S x S patches per XCD instead of column-major ranges -- half the
+        // operand blocks per XCD's L2 -- changes nothing, 0.95 - 0.98 ms per projection either way: the Infinity Cache
+        // serves the misses under the 24 loads in flight; eight k-steps per group instead of four: slower, 1.01 ms)
+        if (W.sg_nt48 > 0) { W.sgX.zero(stream); W.sgX2.zero(stream); W.sgY.zero(stream); W.sgQ.zero(stream); }
         W.sg_part.alloc(W.sg_npart); W.sg_part2.alloc(W.sg_npart); W.sg_sc.alloc(16); W.sg_host.alloc(16);
         W.sg_sc.zero(stream);
         W.sg_ld = ld;
@@ -2017,12 +2046,8 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
     }
     const bool fz = fuse && use_support;
     double* sc = W.sg_sc.p;
-    hipLaunchKernelGGL(dev::k_unpack_sym, dim3(ntile), dim3(dev::TPB), 0, stream, xp_in, n, W.sgA.p, ld,
-                       dev::INV_SQRT2, W.sg_part.p);
-    hipLaunchKernelGGL(dev::k_sign_scalars, dim3(1), dim3(dev::TPB), 0, stream, (const double*)W.sg_part.p, ntile, 0, sc);
-    // Y0 = A A / f^2 and its Frobenius norm g: s = f sqrt(g) >= ||A||_2
-    sym_gemm<dev::SG_PLAIN, false>(W, W.sgA.p, W.sgA.p, W.sgY.p, nullptr, 0, 0, 0, sc + 0, W.sg_part.p, nullptr, nullptr, -1);
-    hipLaunchKernelGGL(dev::k_sign_scalars, dim3(1), dim3(dev::TPB), 0, stream, (const double*)W.sg_part.p, W.sg_npart, 1, sc);
+    sign_unpack(W, xp_in, W.sgA.p, sc);
+    sign_scale(W, sc);
     double* X = W.sgX.p;
     double* Xn = W.sgX2.p;
     // rows [from, SIGN_STEPS) of the table; `first`: X does not exist yet (the step works on A and Y0)
@@ -2132,6 +2157,99 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
     min_eig[idx] = 0.0;                                      // prox_operators.jl:114
     W.last_npos = current_rank[idx];
     return true;
+}
+
+// ONE product of the sign iteration on host data (include/proxsdp_hip.h proxsdp_sym_product), launched by sym_gemm itself on the
+// tile shape asked for.  eig[0] was sized for side t.n (alloc_eigwork); operands are zero-padded to ld as full_eig_by_sign
+// leaves its work matrices, every output buffer is prefilled with the sentinel.
+inline void Solver::test_sym_product(proxsdp_sym_product& t) {
+    EigWork& W = eig[0];
+    const int n = W.n, ld = W.nt * dev::TILE;
+    const int64_t N = W.N;
+    const bool fin = t.epilogue >= 2, fuse = t.epilogue == 3;
+    if (t.tile != 32 && t.tile != 48 && t.tile != 64) throw std::invalid_argument("sym product: tile must be 32, 48 or 64");
+    if (t.epilogue < 0 || t.epilogue > 3) throw std::invalid_argument("sym product: epilogue must be 0 .. 3");
+    if (fin && t.tile != 64) throw std::invalid_argument("sym product: the final product runs on 64 x 64 tiles only");
+    if (t.tile == 48 && !sign_tile48_fits(n, ld))
+        throw std::invalid_argument("sym product: 48 x 48 tiles do not fit this side (48 ceil(n / 48) > ld, or no LDS grant)");
+    if (!t.P || !t.Q || (t.epilogue == 1 && !t.Y) || (!fin && !t.T) || (fin && (!t.xp || !t.part)) ||
+        (fuse && (!t.xold || !t.mask || !t.respart || t.mask_off < 0 || t.mask_words * 32 < t.mask_off + N)))
+        throw std::invalid_argument("sym product: missing buffer");
+    W.sg_ld = ld;
+    W.sg_small = t.tile != 64;
+    W.sg_nt48 = t.tile == 48 ? ceil_div(n, dev::SG_T48) : 0;
+    const int grid = sym_gemm_grid(W, fin);
+    const size_t sz = (size_t)ld * ld;
+    std::vector<double> pad(sz);
+    auto padded = [&](const double* M, DevBuf<double>& d) {
+        std::fill(pad.begin(), pad.end(), 0.0);
+        for (int j = 0; j < n; ++j) std::copy(M + (size_t)j * n, M + (size_t)j * n + n, pad.begin() + (size_t)j * ld);
+        d.alloc(sz);
+        d.upload(pad.data(), sz, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+    };
+    auto filled = [&](DevBuf<double>& d, size_t count) {
+        std::vector<double> h(count, t.sentinel);
+        d.alloc(count);
+        d.upload(h.data(), count, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+    };
+    DevBuf<double> dP, dQ, dY, dT, dpart, dsc, dxp, dxold;
+    padded(t.P, dP); padded(t.Q, dQ);
+    if (t.epilogue == 1) padded(t.Y, dY);
+    if (!fin) filled(dT, sz);
+    if (t.part) filled(dpart, grid);
+    if (t.use_dsc) { dsc.alloc(3); dsc.upload(t.dsc, 3, stream); }
+    if (fin) filled(dxp, N);
+    if (fuse) {
+        dxold.alloc(N); dxold.upload(t.xold, N, stream);
+        mask_d.alloc(t.mask_words); mask_d.upload(t.mask, t.mask_words, stream);
+        P.blocks.assign(1, BlockInfo{n, N, t.mask_off});
+        tile_base.assign(1, 0);
+        rstride = grid;
+        filled(respart_d, (size_t)2 * grid);
+    }
+    const double* sc = t.use_dsc ? dsc.p : nullptr;
+    switch (t.epilogue) {
+        case 0: sym_gemm<dev::SG_PLAIN, false>(W, dP.p, dQ.p, dT.p, nullptr, t.ca, t.cb, t.cc, sc, dpart.p, nullptr, nullptr, -1); break;
+        case 1: sym_gemm<dev::SG_POLY, false>(W, dP.p, dQ.p, dT.p, dY.p, t.ca, t.cb, t.cc, sc, dpart.p, nullptr, nullptr, -1); break;
+        case 2: sym_gemm<dev::SG_FINAL, false>(W, dP.p, dQ.p, nullptr, nullptr, t.ca, t.cb, t.cc, sc, dpart.p, dxp.p, nullptr, -1); break;
+        default: sym_gemm<dev::SG_FINAL, true>(W, dP.p, dQ.p, nullptr, nullptr, t.ca, t.cb, t.cc, sc, dpart.p, dxp.p, dxold.p, 0); break;
+    }
+    PX_HIP(hipGetLastError());
+    if (!fin) dT.download(t.T, sz, stream);
+    if (t.part) dpart.download(t.part, grid, stream);
+    if (fin) dxp.download(t.xp, N, stream);
+    if (fuse) respart_d.download(t.respart, (size_t)2 * grid, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    t.ld = ld;
+    t.grid = grid;
+}
+
+// The head of a sign projection on a packed block (eig[0] sized for it): k_unpack_sym into a matrix prefilled with the sentinel
+// (A, ld x ld: what the kernel writes and what it leaves), then -- on a cleared matrix, the tile shape the solver chooses --
+// sign_unpack and sign_scale as full_eig_by_sign runs them; sc[16] as k_sign_scalars documents it.
+inline void Solver::test_sign_unpack(const double* packed, double sentinel, double* A, double* sc) {
+    EigWork& W = eig[0];
+    const int ld = W.nt * dev::TILE;
+    const size_t sz = (size_t)ld * ld;
+    DevBuf<double> xp(W.N), As(sz), dsc(16);
+    xp.upload(packed, W.N, stream);
+    std::vector<double> h(sz, sentinel);
+    As.upload(h.data(), sz, stream);
+    W.sgA.alloc(sz); W.sgY.alloc(sz);
+    W.sgA.zero(stream); W.sgY.zero(stream);
+    W.sg_ld = ld;
+    sign_choose_tiles(W);
+    W.sg_part.alloc(W.sg_npart);
+    dsc.zero(stream);
+    sign_unpack(W, xp.p, As.p, dsc.p);
+    sign_unpack(W, xp.p, W.sgA.p, dsc.p);
+    sign_scale(W, dsc.p);
+    PX_HIP(hipGetLastError());
+    As.download(A, sz, stream);
+    dsc.download(sc, 16, stream);
+    PX_HIP(hipStreamSynchronize(stream));
 }
 
 inline void Solver::full_eig_project(int idx, const double* xp_in, double* xp_out, bool fuse) {

@@ -91,6 +91,20 @@ def test_reconstruct_mfma_at_full_size_and_high_rank():
             assert abs(b[j * (j + 1) // 2 + i] - v) <= 1e-12 * max(1.0, abs(v))
 
 
+def _spmv_rows_within_bound(M, x, got):
+    """every row of M x on its own: |got_i - sum_j m_ij x_j| <= nnz_i 2^-53 sum_j |m_ij x_j| (one rounding per product and per
+    addition, in any order; an empty row is exactly 0), the sum taken in rational arithmetic"""
+    from fractions import Fraction
+    R = sp.csr_matrix(M)
+    assert got.shape == (R.shape[0],)
+    for i in range(R.shape[0]):
+        cols, vals = R.indices[R.indptr[i]:R.indptr[i + 1]], R.data[R.indptr[i]:R.indptr[i + 1]]
+        terms = [Fraction(float(v)) * Fraction(float(x[j])) for v, j in zip(vals, cols)]
+        exact, mag = sum(terms, Fraction(0)), sum((abs(t) for t in terms), Fraction(0))
+        err = abs(Fraction(float(got[i])) - exact)
+        assert err <= len(terms) * Fraction(1, 2 ** 53) * mag, (i, len(terms), float(got[i]), float(exact), float(err))
+
+
 def test_spmv_both_orientations():
     rng = np.random.default_rng(1)
     for (rows, cols, dens) in [(50, 400, 0.05), (300, 40, 0.3), (7, 5000, 0.9), (1000, 1000, 0.002)]:
@@ -105,6 +119,8 @@ def test_spmv_both_orientations():
     M = M.tocsc()
     x = rng.standard_normal(20000)
     assert _rel(B.spmv(M, x), M @ x) < 1e-13
+    _spmv_rows_within_bound(M, x, B.spmv(M, x))               # (the norm above is the long row's: the others row by row)
+    _spmv_rows_within_bound(M, x, B.spmv(M, x, index_base=1))
     # several rows beyond the segment threshold (8192 entries), random values, mixed with short
     # and medium rows: segmented workgroup-per-4096-entries path + fixed-order combination
     cols = 140000
@@ -113,6 +129,7 @@ def test_spmv_both_orientations():
     M = sp.csc_matrix((rng.standard_normal(len(r)), (r, np.concatenate(rows))), shape=(len(rows) + 2, cols))
     x = rng.standard_normal(cols)
     assert _rel(B.spmv(M, x), M @ x) < 1e-13
+    _spmv_rows_within_bound(M, x, B.spmv(M, x))
     y = rng.standard_normal(M.shape[0])
     assert _rel(B.spmv(M, y, transpose=True), M.T @ y) < 1e-13
 
