@@ -54,7 +54,10 @@ extern "C" {
  * proxsdp_stats dense_setup_passes / dense_sigma_steps (the last two reserved_s slots): same sizes and offsets, version unchanged;
  * later: a block-sharded solve accepts SOC cones, 1x1 PSD cones and variables outside every cone (such a shard runs the general
  * vector path); proxsdp_stats.reserved_s[0] counts its iterations (PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS); proxsdp_trial_batch
- * support = 2: same sizes and offsets, version unchanged */
+ * support = 2: same sizes and offsets, version unchanged;
+ * later: proxsdp_hip_solve_sharded (a whole model, split by the library, one shard per host thread and device of ONE process),
+ * with its test entries proxsdp_host_split_shard, proxsdp_host_group_reduce, proxsdp_hip_coupling_sum: functions only, no
+ * struct changed -- as for proxsdp_hip_dense_scaling before, the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -322,7 +325,8 @@ typedef struct proxsdp_options {
                                   * iteration k (a block-sharded solve must then abort on EVERY shard after that
                                   * iteration's scalar reduce instead of leaving the peers in a collective); 0 = never.
                                   * Honoured only when PROXSDP_HIP_FAULT_INJECTION=1 is set in the environment as well
-                                  * (otherwise PROXSDP_E_INVALID): a test switch, not a user option */
+                                  * (otherwise PROXSDP_E_INVALID): a test switch, not a user option.  In a call of
+                                  * proxsdp_hip_solve_sharded with several shards it applies to the LAST shard only */
     int32_t host_wait_spin;      /* how the solver thread waits for the GPU at its per-cycle / per-iteration read-backs:
                                   * 1 = poll hipStreamQuery (no sleep: the wake-up of a blocked wait costs tens of
                                   * microseconds per synchronisation and leaves the core cold for the K x K eigensolve
@@ -554,6 +558,50 @@ int  proxsdp_hip_solve_ex(const proxsdp_problem* prob, const proxsdp_options* op
 const char* proxsdp_hip_last_error(void);
 int  proxsdp_hip_device_count(void);          /* <0: PROXSDP_E_HIP */
 
+/* ------------------------------------------- block-sharded solve from ONE call
+ * `prob` is the WHOLE model (either index base); the library splits it into n_shards shards itself, runs one shard per
+ * host thread -- thread s on device device_ids[s] (repeats allowed; NULL = every shard on options.device_id) --, and returns
+ * the whole model's result in the caller's order.  No process group, no communicator, no callback: the shards share one
+ * in-process group (csrc/shard_group.hpp).  Per reduce every shard writes its packed [sums | maxs] record into its slot,
+ * the shards meet at a barrier, and each combines the records in shard order (acc = rec[0]; acc += rec[r], r = 1, 2, ...;
+ * element-wise maximum) -- the same bits on every shard.  The coupling rows of M x are summed by one kernel per shard that
+ * reads every shard's partial buffer (peer access between the devices, enabled once; pinned host memory where a pair of
+ * devices has none) and adds them in shard order.
+ *   prob        must not itself be a shard: reduce_fn, reduce_vec_fn, nccl_comm or n_coupling != 0 give PROXSDP_E_INVALID;
+ *               so does M_dense.  approx_norm = 0 and equilibration / equilibration_force != 0 give PROXSDP_E_UNSUPP.  There is
+ *               no state seam.  eig_resid (optional) is split per cone.
+ *   psd_owner / soc_owner / free_owner: shard of every PSD cone / SOC cone / variable outside every cone (ascending id), each
+ *               may be NULL = ONE round-robin over the PSD cones, then the SOC cones, then the free variables.  A cone is
+ *               never split.  An owner outside 0 .. n_shards - 1, a variable in two cones or a shard that would own no
+ *               variable give PROXSDP_E_INVALID before any thread starts.
+ *   rows        a row whose entries all lie in one shard's variables is private to it (a row without entries: shard 0); every
+ *               other row is a coupling row, carried by all shards on their own columns and owned by the lowest shard that
+ *               touches it.
+ *   res         the whole model: primal, dual_cone (n), dual_eq, slack_eq (p), dual_in, slack_in (m) in user order -- a
+ *               private row from its shard, a coupling row from its owner.  status, iter, objectives, gap, residuals,
+ *               final_rank, time, status_string: the global values every shard agrees on (shard 0's copy).  Trace rows
+ *               are shard 0's, except column 13 (mat-vecs: summed over the shards) and column 10 (the shard that holds the
+ *               model's first PSD cone).  res->stats: counters, byte counts and the summed durations of profiled launches
+ *               (*_ms) ADDED over the shards; the wall-clock timers (init_time, loop_time, exit_time, t_primal, t_psd,
+ *               t_linesearch, t_residual, host_eig_time, host_eig_overlap_time) are the MAXIMUM over the shards.
+ *   shard_stats n_shards entries (or NULL): every shard's own struct.
+ * Inside the call the AUTO values of block_threads and host_merge_threads are divided among the shards (8 / n_shards worker
+ * threads -- none below 2 -- and 3 / n_shards merge helpers per shard); explicit values are honoured.  Both knobs leave every
+ * result bit-identical.  n_shards = 1 runs the plain solve's arithmetic.
+ * The call never returns PROXSDP_E_COMM_ABORTED, and no barrier of the group hangs: a shard that leaves the solve for any
+ * reason wakes the others, a barrier wait longer than PROXSDP_HIP_COLLECTIVE_TIMEOUT_S seconds (default 300) abandons the
+ * group, and a shard whose projection fails still joins that iteration's reduce, so that all shards stop after the same
+ * iteration.  That bound covers the barriers ONLY, not the final join: before it frees its device buffers every shard waits,
+ * without a deadline, until all shards have left the solve (a peer's coupling-sum kernel may still be reading them), and the
+ * call joins all its threads.  A shard that is gone is noticed at once; a shard that is HUNG -- stuck inside a device call --
+ * keeps the other shards and the call waiting for as long as it is stuck.  The return value
+ * and proxsdp_hip_last_error() are those of the lowest shard that failed for reasons of its own; the text names the shard and
+ * the iteration every shard stopped in. */
+int  proxsdp_hip_solve_sharded(const proxsdp_problem* prob, const proxsdp_options* opt,
+                               int32_t n_shards, const int32_t* device_ids,
+                               const int32_t* psd_owner, const int32_t* soc_owner, const int32_t* free_owner,
+                               proxsdp_result* res, proxsdp_stats* shard_stats);
+
 /* ------------------------------------------- RCCL communicator helpers (block-sharded solves)
  * The library loads librccl at run time (dlopen; it does not link it).  One rank calls _unique_id and
  * ships the 128 bytes to the others by any means (MPI, torch.distributed, a file); every rank then calls
@@ -733,8 +781,46 @@ int proxsdp_hip_sign_unpack(const double* packed, int64_t n, double sentinel, do
 int proxsdp_hip_dense_scaling(const proxsdp_problem* prob, const proxsdp_options* opt,
                               double* E, double* D, double* frob, double* sigma_max, int32_t* equilibrated);
 
+/* The coupling-row sum of an in-process shard group (k_coupling_sum, through the solver's own launch code) on host data:
+ * parts = n_shards partial buffers of `len` doubles each (row-major n_shards x len), rows = len row numbers into a vector of
+ * n doubles (each in 0 .. n-1, otherwise PROXSDP_E_INVALID; they should be distinct).  v_out = v_in with
+ * v_out[rows[k]] = ((parts[0][k] + parts[1][k]) + parts[2][k]) + ... */
+int proxsdp_hip_coupling_sum(const double* parts, int32_t n_shards, int64_t len, const int64_t* rows,
+                             const double* v_in, int64_t n, double* v_out);
+
 /* ------------------------------------------- host-only helpers (no GPU needed;
  * exercised by the CPU test-suite) */
+/* One shard of proxsdp_hip_solve_sharded's split (csrc/shard_split.hpp: the C++ restatement of sharded.py's
+ * split_block_diagonal), all arguments as there.  The sizes are always written; an array is written when its pointer is not
+ * NULL (call once with every pointer NULL for the sizes, allocate, call again).  Everything that comes out is 0-BASED,
+ * whatever prob->index_base: vars / rows_eq / rows_in = the caller's variable and row numbers the shard holds (ascending),
+ * coupling_rows = positions in the shard's own row numbering (equalities first), psd_ids / soc_ids = the caller's cone
+ * numbers, psd_idx / soc_idx = the shard's own variable numbers, eig_resid = the shard's share of prob->eig_resid (the
+ * vectors of its PSD cones, in the caller's cone order).  Rejects what proxsdp_hip_solve_sharded rejects before it
+ * starts a thread (PROXSDP_E_INVALID). */
+typedef struct proxsdp_shard {
+    int64_t struct_size;
+    int64_t n, p, m, nnz_A, nnz_G, n_coupling, n_psd, len_psd, n_soc, len_soc, len_eig; /* out: sizes */
+    int64_t* vars; int64_t* rows_eq; int64_t* rows_in;                               /* n, p, m */
+    int64_t* coupling_rows; int32_t* coupling_owned;                                 /* n_coupling each */
+    int64_t* A_colptr; int64_t* A_rowval; double* A_nzval;                           /* n + 1, nnz_A, nnz_A */
+    int64_t* G_colptr; int64_t* G_rowval; double* G_nzval;                           /* n + 1, nnz_G, nnz_G */
+    double* b; double* h; double* c;                                                 /* p, m, n */
+    int64_t* psd_ids; int64_t* psd_ptr; int64_t* psd_idx;                            /* n_psd, n_psd + 1, len_psd */
+    int64_t* soc_ids; int64_t* soc_ptr; int64_t* soc_idx;                            /* n_soc, n_soc + 1, len_soc */
+    double* eig_resid;                          /* len_eig: the start vectors of the shard's PSD cones (0 without prob->eig_resid) */
+} proxsdp_shard;
+int proxsdp_host_split_shard(const proxsdp_problem* prob, int32_t n_shards, const int32_t* psd_owner,
+                             const int32_t* soc_owner, const int32_t* free_owner, int32_t shard, proxsdp_shard* out);
+/* The scalar reduce of an in-process shard group alone: n_shards threads run `rounds` rounds of barrier + combine.
+ * records: rounds x n_shards x (nsum + nmax), shard s's packed [sums | maxs] record of round k at
+ * records[(k n_shards + s)(nsum + nmax)]; out: n_shards x rounds x (nsum + nmax), what shard s holds after round k.
+ * leave_shard >= 0: that thread leaves the group after leave_after completed rounds (the abandon path); every other thread
+ * must then come back with an error instead of waiting.  rounds_done[s] = rounds shard s completed, failed[s] = 1 when its
+ * next round threw.  timeout_s <= 0: PROXSDP_HIP_COLLECTIVE_TIMEOUT_S (default 300). */
+int proxsdp_host_group_reduce(int32_t n_shards, int32_t rounds, int32_t nsum, int32_t nmax, const double* records,
+                              int32_t leave_shard, int32_t leave_after, double timeout_s,
+                              double* out, int32_t* rounds_done, int32_t* failed);
 /* eigen-decomposition of a small dense symmetric matrix (column-major k x k,
  * overwritten by eigenvectors; d ascending) -- the K x K Rayleigh quotient of
  * the thick-restart Lanczos */

@@ -182,8 +182,14 @@ _csc(M::SparseArrays.SparseMatrixCSC{Float64,Int64}) =
 Drop-in for `chambolle_pock(aff, con, options)` (src/pdhg.jl:1-530).  `aff`/`con` are only read;
 the library works on private copies (the reference mutates `aff`: src/scaling.jl:24,
 src/pdhg.jl:647-663).
+
+`n_shards > 1` (or `device_ids` given): the block-sharded solve from this one call (`proxsdp_hip_solve_sharded`) -- the
+library splits the model over `n_shards` shards, runs them as host threads of this process, shard `s` on device
+`device_ids[s]` (0-based HIP ordinals; default: all on the device the options name), and returns the whole model's
+result in the caller's order.  Cones are dealt out round-robin (PSD cones, then SOC cones, then the free variables).
 """
-function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result)
+function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
+                            n_shards::Integer = 1, device_ids::Union{Nothing,AbstractVector{<:Integer}} = nothing)
     psd_ptr = Int64[0]; psd_idx = Int64[]
     for s in con.sdpcone
         append!(psd_idx, s.vec_i); push!(psd_ptr, length(psd_idx))
@@ -198,7 +204,10 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result)
     opt = _options_buffer(options)
     res = CResult()
     A, G = aff.A, aff.G
-    GC.@preserve A G aff psd_ptr psd_idx soc_ptr soc_idx primal dual_cone dual_eq dual_in slack_eq slack_in opt begin
+    sharded = n_shards > 1 || device_ids !== nothing
+    devs = device_ids === nothing ? Int32[] : Int32.(device_ids)
+    (device_ids === nothing || length(devs) == n_shards) || error("device_ids: one device per shard")
+    GC.@preserve A G aff psd_ptr psd_idx soc_ptr soc_idx primal dual_cone dual_eq dual_in slack_eq slack_in opt devs begin
         prob = Problem(n, p, m, _csc(A), _csc(G), pointer(aff.b), pointer(aff.h), pointer(aff.c),
                        length(con.sdpcone), pointer(psd_ptr), pointer(psd_idx),
                        length(con.socone), pointer(soc_ptr), pointer(soc_idx),
@@ -210,8 +219,15 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result)
         res.dual_eq = pointer(dual_eq); res.dual_in = pointer(dual_in)
         res.slack_eq = pointer(slack_eq); res.slack_in = pointer(slack_in)
         res.trace = Ptr{Float64}(C_NULL); res.trace_rows = 0
-        rc = ccall((:proxsdp_hip_solve, libproxsdp_hip), Cint,
-                   (Ref{Problem}, Ptr{UInt64}, Ref{CResult}), prob, opt, res)
+        rc = if sharded
+            ccall((:proxsdp_hip_solve_sharded, libproxsdp_hip), Cint,
+                  (Ref{Problem}, Ptr{UInt64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ref{CResult}, Ptr{Stats}),
+                  prob, opt, Int32(n_shards), device_ids === nothing ? Ptr{Int32}(C_NULL) : pointer(devs),
+                  C_NULL, C_NULL, C_NULL, res, C_NULL)                # default owners, no per-shard stats
+        else
+            ccall((:proxsdp_hip_solve, libproxsdp_hip), Cint,
+                  (Ref{Problem}, Ptr{UInt64}, Ref{CResult}), prob, opt, res)
+        end
         if rc != 0
             msg = unsafe_string(ccall((:proxsdp_hip_last_error, libproxsdp_hip), Cstring, ()))
             error("libproxsdp_hip: error $(rc): $(msg)")

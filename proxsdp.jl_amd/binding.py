@@ -171,6 +171,16 @@ class State(C.Structure):
                 ("scal", f64 * 16), ("ints", i64 * 8)]
 
 
+class ShardIO(C.Structure):
+    """proxsdp_shard (include/proxsdp_hip.h)"""
+    _fields_ = ([("struct_size", i64)] +
+                [(k, i64) for k in ("n", "p", "m", "nnz_A", "nnz_G", "n_coupling", "n_psd", "len_psd", "n_soc", "len_soc", "len_eig")] +
+                [("vars", pi64), ("rows_eq", pi64), ("rows_in", pi64), ("coupling_rows", pi64), ("coupling_owned", C.POINTER(i32)),
+                 ("A_colptr", pi64), ("A_rowval", pi64), ("A_nzval", pf64), ("G_colptr", pi64), ("G_rowval", pi64), ("G_nzval", pf64),
+                 ("b", pf64), ("h", pf64), ("c", pf64),
+                 ("psd_ids", pi64), ("psd_ptr", pi64), ("psd_idx", pi64), ("soc_ids", pi64), ("soc_ptr", pi64), ("soc_idx", pi64), ("eig_resid", pf64)])
+
+
 _lib = None
 
 
@@ -228,6 +238,12 @@ def lib():
     L.proxsdp_host_equilibrate_rowsums.argtypes = [pf64, i64, i64, C.POINTER(Options), pf64, pf64]
     L.proxsdp_hip_sym_product.argtypes = [C.POINTER(SymProductIO)]
     L.proxsdp_hip_sign_unpack.argtypes = [pf64, i64, f64, pf64, pf64]
+    L.proxsdp_hip_solve_sharded.argtypes = [C.POINTER(Problem), C.POINTER(Options), i32, C.POINTER(i32), C.POINTER(i32),
+                                            C.POINTER(i32), C.POINTER(i32), C.POINTER(Result), C.POINTER(Stats)]
+    L.proxsdp_host_split_shard.argtypes = [C.POINTER(Problem), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32,
+                                           C.POINTER(ShardIO)]
+    L.proxsdp_host_group_reduce.argtypes = [i32, i32, i32, i32, pf64, i32, i32, f64, pf64, C.POINTER(i32), C.POINTER(i32)]
+    L.proxsdp_hip_coupling_sum.argtypes = [pf64, i32, i64, pi64, pf64, i64, pf64]
     L.proxsdp_hip_rccl_unique_id.argtypes = [C.c_void_p]
     L.proxsdp_hip_rccl_comm_init.argtypes = [i32, C.c_void_p, i32, i32, C.POINTER(C.c_void_p)]
     L.proxsdp_hip_rccl_comm_destroy.argtypes = [C.c_void_p]
@@ -508,6 +524,116 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
     arrays = [a[:k] for a, k in zip(arrays, (n, n, p, m, p, m))]
     out = SolveResult(R, n, p, m, arrays, trace)
     out.state = _state_dict(cs, carr, n, Q, nb) if (cs is not None and cs.ints[3] == 1) else None
+    return out
+
+
+def _owner_arrays(owners, soc_owners, free_owners):
+    """int32 arrays (kept alive by the caller) and their pointers; None -> NULL = the library's round-robin default"""
+    arrs = [None if o is None else np.ascontiguousarray(o, dtype=np.int32) for o in (owners, soc_owners, free_owners)]
+    # (an empty list is a valid owner list of a model without such cones: hand over a pointer, not NULL)
+    arrs = [a if (a is None or len(a)) else np.zeros(1, dtype=np.int32) for a in arrs]
+    return arrs, [None if a is None else _p(a, C.POINTER(i32)) for a in arrs]
+
+
+def solve_sharded_inprocess(prob, n_shards, device_ids=None, owners=None, soc_owners=None, free_owners=None, options=None,
+                            trace_capacity=0, eig_resid=None, index_base=0):
+    """proxsdp_hip_solve_sharded: the WHOLE model in, split by the library into n_shards shards that run as host threads of
+    this process (shard s on device_ids[s]; default: all on options.device_id), the whole model's result out, in the
+    caller's order.  owners / soc_owners / free_owners: shard per PSD cone / SOC cone / free variable (None = one
+    round-robin, sharded.default_owners).  Returns (SolveResult, [per-shard stats dicts])."""
+    L = lib()
+    o = options if options is not None else default_options()
+    if trace_capacity:
+        o.trace_capacity = int(trace_capacity)
+    n_shards = int(n_shards)
+    M = _Marshalled(prob, eig_resid, index_base)
+    keep, ptrs = _owner_arrays(owners, soc_owners, free_owners)
+    dev = None
+    if device_ids is not None:
+        dev = np.ascontiguousarray(device_ids, dtype=np.int32)
+        if len(dev) != n_shards:
+            raise ValueError("device_ids: one device per shard")
+    n, p, m = M.P.n, M.P.p, M.P.m
+    arrays = [np.zeros(max(k, 1)) for k in (n, n, p, m, p, m)]
+    trace = np.zeros((max(o.trace_capacity, 1), TRACE_COLS))
+    R = Result()
+    R.primal, R.dual_cone, R.dual_eq, R.dual_in, R.slack_eq, R.slack_in = [_p(a) for a in arrays]
+    R.trace = _p(trace)
+    SS = (Stats * max(n_shards, 1))()
+    _check(L.proxsdp_hip_solve_sharded(C.byref(M.P), C.byref(o), n_shards, _p(dev, C.POINTER(i32)) if dev is not None else None,
+                                       ptrs[0], ptrs[1], ptrs[2], C.byref(R), SS))
+    del keep
+    arrays = [a[:k] for a, k in zip(arrays, (n, n, p, m, p, m))]
+    sol = SolveResult(R, n, p, m, arrays, trace)
+    shard_stats = []
+    for s in range(n_shards):
+        d = {k: (list(getattr(SS[s], k)) if k.startswith("reserved") else getattr(SS[s], k)) for k, _ in Stats._fields_}
+        for k, slot in STATS_RESERVED_SLOTS.items():
+            d[k] = int(SS[s].reserved_s[slot])
+        shard_stats.append(d)
+    return sol, shard_stats
+
+
+def host_split_shard(prob, n_shards, shard, owners=None, soc_owners=None, free_owners=None, index_base=0, raw_problem=None,
+                     eig_resid=None):
+    """proxsdp_host_split_shard: one shard of the library's own split (csrc/shard_split.hpp), everything 0-based.  Returns a
+    dict: vars, rows_eq, rows_in, coupling_rows, coupling_owned, A / G (scipy CSC), b, h, c, psd_ids, soc_ids, psd / soc
+    (lists of the shard's own variable numbers per cone) and eig_resid (the shard's share of the start vectors `eig_resid`,
+    one per PSD cone of the model; empty without them).  raw_problem: a callable that edits the marshalled proxsdp_problem
+    before the call (tests of the rejected inputs)."""
+    L = lib()
+    M = _Marshalled(prob, eig_resid, index_base)
+    if raw_problem is not None:
+        raw_problem(M.P)
+    keep, ptrs = _owner_arrays(owners, soc_owners, free_owners)
+    S = ShardIO()
+    S.struct_size = C.sizeof(ShardIO)
+    call = lambda: _check(L.proxsdp_host_split_shard(C.byref(M.P), int(n_shards), ptrs[0], ptrs[1], ptrs[2], int(shard), C.byref(S)))
+    call()                                             # sizes
+    sizes = dict(vars=S.n, rows_eq=S.p, rows_in=S.m, coupling_rows=S.n_coupling, coupling_owned=S.n_coupling,
+                 A_colptr=S.n + 1, A_rowval=S.nnz_A, A_nzval=S.nnz_A, G_colptr=S.n + 1, G_rowval=S.nnz_G, G_nzval=S.nnz_G,
+                 b=S.p, h=S.m, c=S.n, psd_ids=S.n_psd, psd_ptr=S.n_psd + 1, psd_idx=S.len_psd,
+                 soc_ids=S.n_soc, soc_ptr=S.n_soc + 1, soc_idx=S.len_soc, eig_resid=S.len_eig)
+    out = {}
+    for name, t in ShardIO._fields_:
+        if name not in sizes:
+            continue
+        dt = np.float64 if t is pf64 else (np.int32 if name == "coupling_owned" else np.int64)
+        out[name] = np.full(max(sizes[name], 1), -7, dtype=dt)
+        setattr(S, name, out[name].ctypes.data_as(t))
+    call()
+    del keep
+    out = {k: v[:sizes[k]] for k, v in out.items()}
+    n_, p_, m_ = int(S.n), int(S.p), int(S.m)
+    res = {k: out[k] for k in ("vars", "rows_eq", "rows_in", "coupling_rows", "coupling_owned", "b", "h", "c", "psd_ids", "soc_ids", "eig_resid")}
+    res["A"] = sp.csc_matrix((out["A_nzval"], out["A_rowval"], out["A_colptr"]), shape=(p_, n_))
+    res["G"] = sp.csc_matrix((out["G_nzval"], out["G_rowval"], out["G_colptr"]), shape=(m_, n_))
+    for kind in ("psd", "soc"):
+        ptr, idx = out[kind + "_ptr"], out[kind + "_idx"]
+        res[kind] = [idx[ptr[k]:ptr[k + 1]].copy() for k in range(len(ptr) - 1)]
+    return res
+
+
+def host_group_reduce(records, nsum, leave_shard=-1, leave_after=0, timeout_s=0.0):
+    """proxsdp_host_group_reduce: records (rounds x shards x width) through the in-process group's barrier + combine, one
+    thread per shard.  Returns (out: shards x rounds x width, rounds_done, failed)."""
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    K, S, w = rec.shape
+    out = np.zeros((S, max(K, 1), w))
+    done, failed = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+    _check(lib().proxsdp_host_group_reduce(S, K, int(nsum), w - int(nsum), _p(rec), int(leave_shard), int(leave_after),
+                                           float(timeout_s), _p(out), _p(done, C.POINTER(i32)), _p(failed, C.POINTER(i32))))
+    return out[:, :K], done, failed
+
+
+def coupling_sum(parts, rows, v):
+    """proxsdp_hip_coupling_sum: v with v[rows[k]] = ((parts[0][k] + parts[1][k]) + ...) -- the in-process group's kernel"""
+    parts = np.ascontiguousarray(parts, dtype=np.float64)
+    S, Ln = parts.shape
+    rows, vin = _i(rows), _f(v)
+    assert len(rows) == Ln
+    out = np.zeros_like(vin)
+    _check(lib().proxsdp_hip_coupling_sum(_p(parts), S, Ln, _p(rows, pi64), _p(vin), len(vin), _p(out)))
     return out
 
 

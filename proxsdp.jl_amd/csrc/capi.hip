@@ -2,11 +2,13 @@
 // this boundary: every entry point catches, records the message in a
 // thread-local buffer and returns a negative PROXSDP_E_* code.  There is no CPU
 // fallback: without a HIP device the compute entry points fail with PROXSDP_E_HIP.
+#include <functional>
 #include <memory>
 #include <new>
 #include <string>
 
 #include "pdhg_loop.hip.hpp"
+#include "shard_split.hpp"
 
 namespace {
 thread_local std::string g_last_error;
@@ -184,6 +186,250 @@ int proxsdp_hip_solve_ex(const proxsdp_problem* prob, const proxsdp_options* opt
         return PROXSDP_E_COMM_ABORTED;
     }
     return rc;
+}
+
+// ---- block-sharded solve from one call: in-process shards (shard_split.hpp, shard_group.hpp)
+namespace {
+struct ShardRun {
+    proxsdp::ShardData data;
+    proxsdp_result res{};
+    std::vector<double> primal, dual_cone, dual_eq, dual_in, slack_eq, slack_in, trace;
+    int code = 0;
+    bool peer = false;                 // stopped because another shard did
+    bool left = false;                 // has left the group
+    long long iter = -1;               // iteration it stopped in (-1: the solver was never constructed)
+    std::string err;
+};
+
+// counters, byte counts and summed event durations add up over the shards; wall-clock timers take the maximum
+void merge_shard_stats(proxsdp_stats& a, const proxsdp_stats& b) {
+#define PX_SUM(f) a.f += b.f
+#define PX_MAX(f) a.f = std::max(a.f, b.f)
+    PX_SUM(lanczos_matvecs); PX_SUM(lanczos_restarts); PX_SUM(lanczos_calls); PX_SUM(full_eigs); PX_SUM(krylov_fallbacks);
+    PX_SUM(linesearch_trials); PX_SUM(symv_launches); PX_SUM(symv_profiled); PX_SUM(symv_profiled_ms); PX_SUM(symv_bytes);
+    PX_SUM(algorithmic_bytes);
+    PX_MAX(init_time); PX_MAX(loop_time); PX_MAX(exit_time); PX_MAX(t_primal); PX_MAX(t_psd); PX_MAX(t_linesearch); PX_MAX(t_residual);
+    PX_SUM(dense_passes); PX_SUM(dense_ms); PX_SUM(fop_projections); PX_SUM(exit_matvecs);
+    PX_MAX(host_eig_time);
+    PX_SUM(host_eigs); PX_SUM(device_eigs); PX_SUM(batched_small_eigs); PX_SUM(mfma_reconstructions); PX_SUM(orth_profiled);
+    PX_SUM(orth_profiled_ms); PX_SUM(full_eig_solver_ms); PX_SUM(full_eig_recon_ms); PX_SUM(cycle_launches);
+    PX_SUM(full_eigs_lanczos); PX_SUM(cycle_steps); PX_SUM(cycle_ms); PX_SUM(warm_starts); PX_SUM(full_eigs_sign);
+    PX_SUM(sign_products); PX_SUM(sign_engine_projections); PX_SUM(sign_engine_rejected); PX_SUM(sign_engine_checks);
+    PX_SUM(sign_engine_mismatches); PX_SUM(full_eigs_lanczos_checks); PX_SUM(full_eigs_lanczos_mismatches);
+    PX_SUM(batched_block_steps); PX_SUM(rccl_reductions); PX_SUM(batched_profiled_blocks); PX_SUM(host_eig_merges);
+    PX_MAX(host_eig_overlap_time);
+    PX_SUM(sign_short_pass); PX_SUM(sign_short_fail); PX_SUM(full_eigs_lanczos_certified); PX_SUM(full_eigs_lanczos_cert_failed);
+    PX_SUM(cert_matvecs); PX_SUM(dense_truncated_projections); PX_SUM(wide_krylov_projections);
+    for (int k = 0; k < 4; ++k) PX_SUM(reserved_s[k]);
+    PX_SUM(dense_setup_passes); PX_SUM(dense_sigma_steps);
+#undef PX_SUM
+#undef PX_MAX
+}
+
+// body(s) for every shard of a group: shard 0 on the calling thread, the others on threads of their own.  When a thread cannot
+// be started (std::system_error), the shards that never started leave the group -- the started ones would otherwise wait for
+// them --, the started ones are joined, and the error is the caller's
+void run_shard_threads(int n_shards, proxsdp::ShardGroup& group, const std::function<void(int)>& body) {
+    std::vector<std::thread> th;
+    th.reserve((size_t)std::max(n_shards - 1, 0));
+    try {
+        for (int s = 1; s < n_shards; ++s) th.emplace_back(std::cref(body), s);
+    } catch (...) {
+        for (int s = (int)th.size(); s < n_shards; ++s) group.leave();       // shard 0 and shards th.size() + 1 ...
+        for (auto& t : th) t.join();
+        throw;
+    }
+    body(0);
+    for (auto& t : th) t.join();
+}
+}  // namespace
+
+int proxsdp_hip_solve_sharded(const proxsdp_problem* prob, const proxsdp_options* opt, int32_t n_shards,
+                              const int32_t* device_ids, const int32_t* psd_owner, const int32_t* soc_owner,
+                              const int32_t* free_owner, proxsdp_result* res, proxsdp_stats* shard_stats) {
+    int shard_rc = 0;
+    std::string shard_msg;
+    const int rc = guarded([&]() -> int {
+        if (!prob || !res) throw std::invalid_argument("NULL problem or result");
+        const proxsdp_options o = [&]() {
+            proxsdp_options t = Engine::fix(opt);
+            if (t.trace_capacity > 0 && !res->trace) t.trace_capacity = 0;
+            return t;
+        }();
+        res->status = PROXSDP_STATUS_NOT_CALLED;
+        res->trace_rows = 0;
+        res->result_count = 0;
+        res->certificate_found = 0;
+        res->status_string[0] = 0;
+        // ---- everything that is rejected before a thread starts
+        const proxsdp::ShardPlan L = proxsdp::plan_shards(*prob, n_shards, psd_owner, soc_owner, free_owner);
+        if (!o.approx_norm) throw std::domain_error("approx_norm=false with a block-sharded solve is not implemented");
+        if (o.equilibration != 0 || o.equilibration_force != 0)
+            throw std::domain_error("equilibration with a block-sharded solve is not implemented");
+        if (o.debug_fail_iteration > 0) {
+            const char* e = std::getenv("PROXSDP_HIP_FAULT_INJECTION");
+            if (!(e && e[0] == '1')) throw std::invalid_argument("debug_fail_iteration needs PROXSDP_HIP_FAULT_INJECTION=1 in the environment (test switch)");
+        }
+        int ndev = 0;
+        PX_HIP(hipGetDeviceCount(&ndev));
+        if (ndev <= 0) throw proxsdp::HipError("no HIP device available");
+        proxsdp::ShardGroup group(n_shards);
+        for (int s = 0; s < n_shards; ++s) {
+            group.device[s] = device_ids ? device_ids[s] : o.device_id;
+            if (group.device[s] < 0 || group.device[s] >= ndev) throw std::invalid_argument("device_ids: device out of range");
+        }
+        // shards on different devices read each other's partial buffers: peer access for every ordered pair of distinct
+        // devices, or the partials are staged in pinned host memory by all
+        for (int a = 0; a < n_shards && !group.stage_host; ++a)
+            for (int b = 0; b < n_shards; ++b) {
+                if (group.device[a] == group.device[b]) continue;
+                int can = 0;
+                if (hipDeviceCanAccessPeer(&can, group.device[a], group.device[b]) != hipSuccess || !can) {
+                    (void)hipGetLastError();
+                    group.stage_host = true;
+                    break;
+                }
+            }
+        std::vector<ShardRun> runs(n_shards);
+        for (int s = 0; s < n_shards; ++s) {
+            ShardRun& R = runs[s];
+            R.data = proxsdp::split_shard(*prob, L, s);
+            const size_t n = R.data.vars.size(), p = R.data.rows_eq.size(), m = R.data.rows_in.size();
+            R.primal.assign(n, 0.0); R.dual_cone.assign(n, 0.0);
+            R.dual_eq.assign(p + 1, 0.0); R.slack_eq.assign(p + 1, 0.0); R.dual_in.assign(m + 1, 0.0); R.slack_in.assign(m + 1, 0.0);
+            R.trace.assign((size_t)std::max(o.trace_capacity, 0) * PROXSDP_TRACE_COLS + 1, 0.0);
+            R.res.primal = R.primal.data(); R.res.dual_cone = R.dual_cone.data();
+            R.res.dual_eq = R.dual_eq.data(); R.res.slack_eq = R.slack_eq.data();
+            R.res.dual_in = R.dual_in.data(); R.res.slack_in = R.slack_in.data();
+            R.res.trace = R.trace.data();
+        }
+        // ---- one host thread per shard; whatever happens in it ends in its ShardRun, and it always leaves the group
+        auto body = [&](int s) {
+            ShardRun& R = runs[s];
+            R.code = guarded([&]() -> int {
+                proxsdp_options os = o;
+                os.device_id = group.device[s];
+                if (n_shards > 1) {
+                    // the AUTO helper-thread counts are shared among the shards of the process (both knobs leave every
+                    // result bit-identical); explicit values are the caller's business
+                    if (os.block_threads < 0) os.block_threads = 8 / n_shards >= 2 ? 8 / n_shards : 0;
+                    if (os.host_merge_threads < 0) os.host_merge_threads = 3 / n_shards;
+                    if (s != n_shards - 1) os.debug_fail_iteration = 0;       // fault injection: the last shard only
+                }
+                const proxsdp_problem sp = R.data.problem();
+                proxsdp::Solver S(sp, os, R.res, &group, s);
+                // on the way out, however that happens: finish this shard's own launches (its last coupling-sum kernel reads
+                // the peers' buffers), leave the group, and keep this solver's device buffers until every shard has left
+                struct Farewell {
+                    proxsdp::Solver& S; proxsdp::ShardGroup& g; bool& left;
+                    ~Farewell() {
+                        if (S.stream.main) (void)hipStreamSynchronize(S.stream.main);
+                        g.leave(); left = true;
+                        g.wait_all_left();
+                    }
+                } farewell{S, group, R.left};
+                try {
+                    S.run();
+                } catch (const proxsdp::PeerFailure&) {
+                    R.peer = true; R.iter = S.current_iteration();
+                    throw;
+                } catch (...) {
+                    R.iter = S.current_iteration();
+                    throw;
+                }
+                R.iter = S.current_iteration();
+                return 0;
+            });
+            if (R.code != 0) R.err = g_last_error;          // (thread-local: carried over to the caller's thread below)
+            if (!R.left) group.leave();                      // (the solver was never constructed)
+        };
+        run_shard_threads(n_shards, group, body);
+        if (shard_stats) for (int s = 0; s < n_shards; ++s) shard_stats[s] = runs[s].res.stats;
+        // ---- the lowest shard that failed for reasons of its own (else the lowest that failed at all)
+        int bad = -1;
+        for (int s = 0; s < n_shards && bad < 0; ++s) if (runs[s].code != 0 && !runs[s].peer) bad = s;
+        for (int s = 0; s < n_shards && bad < 0; ++s) if (runs[s].code != 0) bad = s;
+        if (bad >= 0) {
+            shard_rc = runs[bad].code;
+            shard_msg = "shard " + std::to_string(bad) + " of " + std::to_string(n_shards) + ": " + runs[bad].err +
+                        " [shards stopped in iteration";
+            for (int s = 0; s < n_shards; ++s) shard_msg += " " + std::to_string(runs[s].iter);
+            shard_msg += "]";
+            return 0;
+        }
+        // ---- the whole model's result
+        const proxsdp_result& R0 = runs[0].res;
+        res->status = R0.status; res->certificate_found = R0.certificate_found;
+        res->primal_feasible_user_tol = R0.primal_feasible_user_tol; res->dual_feasible_user_tol = R0.dual_feasible_user_tol;
+        res->result_count = R0.result_count; res->final_rank = R0.final_rank; res->iter = R0.iter;
+        res->primal_residual = R0.primal_residual; res->dual_residual = R0.dual_residual;
+        res->objval = R0.objval; res->dual_objval = R0.dual_objval; res->gap = R0.gap; res->time = R0.time;
+        res->dual_feasibility = R0.dual_feasibility;
+        std::memcpy(res->status_string, R0.status_string, sizeof(res->status_string));
+        for (int s = 0; s < n_shards; ++s) {
+            const ShardRun& R = runs[s];
+            proxsdp::gather_shard(R.data, R.primal.data(), R.dual_cone.data(), R.dual_eq.data(), R.dual_in.data(),
+                                  R.slack_eq.data(), R.slack_in.data(), *res);
+        }
+        res->stats = R0.stats;
+        for (int s = 1; s < n_shards; ++s) merge_shard_stats(res->stats, runs[s].res.stats);
+        if (o.trace_capacity > 0) {
+            const int64_t rows = R0.trace_rows;
+            for (int s = 1; s < n_shards; ++s)
+                if (runs[s].res.trace_rows != rows) throw std::logic_error("the shards' traces differ in length");
+            std::copy(runs[0].trace.begin(), runs[0].trace.begin() + rows * PROXSDP_TRACE_COLS, res->trace);
+            const int first_psd = prob->n_psd > 0 ? L.psd_owner[0] : 0;
+            for (int64_t r = 0; r < rows; ++r) {
+                double mv = 0.0;
+                for (int s = 0; s < n_shards; ++s) mv += runs[s].trace[r * PROXSDP_TRACE_COLS + 13];
+                res->trace[r * PROXSDP_TRACE_COLS + 13] = mv;
+                res->trace[r * PROXSDP_TRACE_COLS + 10] = runs[first_psd].trace[r * PROXSDP_TRACE_COLS + 10];
+            }
+            res->trace_rows = rows;
+        }
+        return 0;
+    });
+    if (rc == 0 && shard_rc != 0) {
+        g_last_error = shard_msg;
+        return shard_rc;
+    }
+    return rc;
+}
+
+int proxsdp_hip_coupling_sum(const double* parts, int32_t n_shards, int64_t len, const int64_t* rows,
+                             const double* v_in, int64_t n, double* v_out) {
+    return guarded([&]() -> int {
+        if (!parts || !rows || !v_in || !v_out || n_shards < 1 || n_shards > 1024 || len < 1 || n < 1 ||
+            len >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31))
+            throw std::invalid_argument("invalid argument");
+        std::vector<int> r32(len);
+        for (int64_t k = 0; k < len; ++k) {
+            if (rows[k] < 0 || rows[k] >= n) throw std::invalid_argument("row outside the vector");
+            r32[k] = (int)rows[k];
+        }
+        Engine E(nullptr, 2, 2);
+        proxsdp::Solver& S = E.S;
+        // one device buffer per shard, as in a solve (separate allocations: odd lengths leave the later ones unaligned to
+        // nothing but the allocator's granularity -- the kernel makes no alignment assumption beyond 8 bytes)
+        std::vector<proxsdp::DevBuf<double>> part(n_shards);
+        std::vector<const double*> tab(n_shards);
+        for (int s = 0; s < n_shards; ++s) {
+            part[s].alloc((size_t)len);
+            part[s].upload(parts + (size_t)s * len, (size_t)len, S.stream);
+            tab[s] = part[s].p;
+        }
+        proxsdp::DevBuf<const double*> tab_d((size_t)n_shards);
+        proxsdp::DevBuf<int> rows_d((size_t)len);
+        proxsdp::DevBuf<double> v((size_t)n);
+        tab_d.upload(tab.data(), (size_t)n_shards, S.stream);
+        rows_d.upload(r32.data(), (size_t)len, S.stream);
+        v.upload(v_in, (size_t)n, S.stream);
+        S.launch_coupling_sum(tab_d.p, n_shards, rows_d.p, (int)len, v.p);
+        PX_HIP(hipGetLastError());
+        v.download(v_out, (size_t)n, S.stream);
+        PX_HIP(hipStreamSynchronize(S.stream));
+        return 0;
+    });
 }
 
 int proxsdp_hip_psd_project(const double* packed_in, int64_t n, int32_t target_rank, int32_t mode,
@@ -643,6 +889,63 @@ int proxsdp_host_preprocess(const proxsdp_problem* prob, int64_t* order, int64_t
             if (c_scaled) c_scaled[i] = R.c[i];
         }
         if (frobenius_norm_M) *frobenius_norm_M = R.frob;
+        return 0;
+    });
+}
+
+int proxsdp_host_split_shard(const proxsdp_problem* prob, int32_t n_shards, const int32_t* psd_owner,
+                             const int32_t* soc_owner, const int32_t* free_owner, int32_t shard, proxsdp_shard* out) {
+    return guarded([&]() -> int {
+        if (!prob || !out) throw std::invalid_argument("NULL problem or output");
+        if (out->struct_size != (int64_t)sizeof(proxsdp_shard)) throw std::invalid_argument("proxsdp_shard.struct_size mismatch");
+        const proxsdp::ShardPlan L = proxsdp::plan_shards(*prob, n_shards, psd_owner, soc_owner, free_owner);
+        if (shard < 0 || shard >= n_shards) throw std::invalid_argument("shard outside 0 .. n_shards - 1");
+        const proxsdp::ShardData S = proxsdp::split_shard(*prob, L, shard);
+        out->n = (int64_t)S.vars.size(); out->p = (int64_t)S.rows_eq.size(); out->m = (int64_t)S.rows_in.size();
+        out->nnz_A = (int64_t)S.A_rowval.size(); out->nnz_G = (int64_t)S.G_rowval.size();
+        out->n_coupling = (int64_t)S.coup_rows.size();
+        out->n_psd = (int64_t)S.psd_ids.size(); out->len_psd = (int64_t)S.psd_idx.size();
+        out->n_soc = (int64_t)S.soc_ids.size(); out->len_soc = (int64_t)S.soc_idx.size();
+        out->len_eig = (int64_t)S.eig_resid.size();
+        auto put = [](const auto& v, auto* dst) { if (dst) std::copy(v.begin(), v.end(), dst); };
+        put(S.vars, out->vars); put(S.rows_eq, out->rows_eq); put(S.rows_in, out->rows_in);
+        put(S.coup_rows, out->coupling_rows); put(S.coup_owned, out->coupling_owned);
+        put(S.A_colptr, out->A_colptr); put(S.A_rowval, out->A_rowval); put(S.A_nzval, out->A_nzval);
+        put(S.G_colptr, out->G_colptr); put(S.G_rowval, out->G_rowval); put(S.G_nzval, out->G_nzval);
+        put(S.b, out->b); put(S.h, out->h); put(S.c, out->c);
+        put(S.psd_ids, out->psd_ids); put(S.psd_ptr, out->psd_ptr); put(S.psd_idx, out->psd_idx);
+        put(S.soc_ids, out->soc_ids); put(S.soc_ptr, out->soc_ptr); put(S.soc_idx, out->soc_idx);
+        put(S.eig_resid, out->eig_resid);
+        return 0;
+    });
+}
+
+int proxsdp_host_group_reduce(int32_t n_shards, int32_t rounds, int32_t nsum, int32_t nmax, const double* records,
+                              int32_t leave_shard, int32_t leave_after, double timeout_s,
+                              double* out, int32_t* rounds_done, int32_t* failed) {
+    return guarded([&]() -> int {
+        if (n_shards < 1 || n_shards > 256 || rounds < 0 || nsum < 0 || nmax < 0 || nsum + nmax < 1 || !records || !out ||
+            !rounds_done || !failed || leave_shard >= n_shards)
+            throw std::invalid_argument("invalid argument");
+        const size_t w = (size_t)nsum + (size_t)nmax;
+        proxsdp::ShardGroup group(n_shards, timeout_s);
+        auto body = [&](int s) {
+            rounds_done[s] = 0; failed[s] = 0;
+            try {
+                for (int k = 0; k < rounds; ++k) {
+                    if (s == leave_shard && k == leave_after) break;
+                    const double* rec = records + ((size_t)k * n_shards + s) * w;
+                    std::vector<double> sums(rec, rec + nsum), maxs(rec + nsum, rec + w);
+                    group.reduce(s, sums, maxs);
+                    double* o = out + ((size_t)s * rounds + k) * w;
+                    std::copy(sums.begin(), sums.end(), o);
+                    std::copy(maxs.begin(), maxs.end(), o + nsum);
+                    rounds_done[s] = k + 1;
+                }
+            } catch (...) { failed[s] = 1; }
+            group.leave();
+        };
+        run_shard_threads(n_shards, group, body);
         return 0;
     });
 }

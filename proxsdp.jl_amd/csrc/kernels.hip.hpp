@@ -2445,6 +2445,22 @@ k_scatter_rows(double* __restrict__ v, const int* __restrict__ rows, int cnt, co
     if (k < cnt) v[rows[k]] = buf[k];
 }
 
+// coupling rows of an in-process shard group (shard_group.hpp): part[s] is shard s's gathered partial buffer -- this
+// device's memory, a peer's, or pinned host memory.  One thread per row adds them in shard order,
+// ((part[0][k] + part[1][k]) + part[2][k]) + ..., and writes the sum straight into row rows[k] of M x (the all-reduce and
+// k_scatter_rows in one launch).  Plain additions in a fixed order: the same bits on every shard.  cnt is small to
+// moderate and the launch is latency-bound: no vector loads, no atomics, no wait inside the kernel (the shards met at a
+// host barrier before the launch).
+__global__ void __launch_bounds__(TPB)
+k_coupling_sum(const double* const* __restrict__ part, int nshard, const int* __restrict__ rows, int cnt,
+               double* __restrict__ v) {
+    const int k = blockIdx.x * TPB + threadIdx.x;
+    if (k >= cnt) return;
+    double acc = part[0][k];
+    for (int s = 1; s < nshard; ++s) acc += part[s][k];
+    v[rows[k]] = acc;
+}
+
 // v .*= d (removing the equilibration at the exit path, pdhg.jl:751-755)
 __global__ void __launch_bounds__(TPB)
 k_scale_by(double* __restrict__ v, const double* __restrict__ d, long long n) {

@@ -50,6 +50,29 @@ inline void Solver::setup_long_rows(const std::vector<int>& rp) {
 // (RCCL on the device buffer, or through host memory) -- SURVEY.md section 8e
 inline void Solver::reduce_coupling(double* Mx_dev) {
     const int nc = (int)coup_rows.size();
+    if (group) {
+        // in-process group: gather this shard's partials, finish them (stream synchronisation), meet the peers, then ONE
+        // kernel on this shard's stream reads every shard's partials and writes the sums into M x.  The partials are
+        // double-buffered by the parity of this call counter: a shard overwrites a buffer only after a later barrier, which
+        // every peer reaches after its own sum kernel of this call has finished (it synchronises its stream before it)
+        const int par = (int)(coup_calls++ & 1);
+        hipLaunchKernelGGL(dev::k_gather_rows, dim3(ceil_div(nc, dev::TPB)), dim3(dev::TPB), 0, stream,
+                           (const double*)Mx_dev, (const int*)coup_rows_d.p, nc, coup_part_d[par].p);
+        if (group->stage_host) coup_part_d[par].download(coup_part_h[par].p, nc, stream);
+        wait_stream();
+        group->barrier();
+        const int S = group->size();
+        if (!coup_tab_ready) {                              // (every shard published its buffers before its first barrier)
+            std::vector<const double*> tab;
+            for (int q = 0; q < 2; ++q)
+                for (int s = 0; s < S; ++s) tab.push_back(group->coup_part[q][s]);
+            coup_tab_d.alloc(tab.size());
+            PX_HIP(hipMemcpy(coup_tab_d.p, tab.data(), tab.size() * sizeof(const double*), hipMemcpyHostToDevice));
+            coup_tab_ready = true;
+        }
+        launch_coupling_sum(coup_tab_d.p + (size_t)par * S, S, coup_rows_d.p, nc, Mx_dev);
+        return;
+    }
     hipLaunchKernelGGL(dev::k_gather_rows, dim3(ceil_div(nc, dev::TPB)), dim3(dev::TPB), 0, stream,
                        (const double*)Mx_dev, (const int*)coup_rows_d.p, nc, coup_buf_d.p);
     if (nccl) {
@@ -70,6 +93,36 @@ inline void Solver::reduce_coupling(double* Mx_dev) {
     }
     hipLaunchKernelGGL(dev::k_scatter_rows, dim3(ceil_div(nc, dev::TPB)), dim3(dev::TPB), 0, stream,
                        Mx_dev, (const int*)coup_rows_d.p, nc, (const double*)coup_buf_d.p);
+}
+
+// in-process group: this shard's two partial buffers, published to the peers; peer access to every other device of the
+// group, enabled once (where some pair of devices has none, the group stages the partials in pinned host memory instead)
+inline void Solver::setup_group_coupling() {
+    const size_t nc = coup_rows.size();
+    const int S = group->size();
+    for (int par = 0; par < 2; ++par) {
+        coup_part_d[par].alloc(nc); coup_part_d[par].zero(stream);
+        if (group->stage_host) {
+            coup_part_h[par].alloc(nc, hipHostMallocPortable | hipHostMallocMapped);
+            group->coup_part[par][group_rank] = coup_part_h[par].p;
+        } else {
+            group->coup_part[par][group_rank] = coup_part_d[par].p;
+        }
+    }
+    if (!group->stage_host) {
+        const int mine = group->device[group_rank];
+        for (int s = 0; s < S; ++s) {
+            const int d = group->device[s];
+            if (d == mine) continue;
+            bool seen = false;
+            for (int q = 0; q < s; ++q) seen = seen || group->device[q] == d;
+            if (seen) continue;
+            const hipError_t e = hipDeviceEnablePeerAccess(d, 0);
+            if (e == hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
+            else PX_HIP(e);
+        }
+    }
+    PX_HIP(hipStreamSynchronize(stream));
 }
 
 // psd_projection! (prox_operators.jl:33-66), one block: reads the packed block of xin,
@@ -640,7 +693,7 @@ inline void Solver::reduce_candidates(int nc) {
     reduce(sums, maxs);
     if (maxs.back() > 0.5) {
         if (shard_error) { std::exception_ptr e = shard_error; shard_error = nullptr; std::rethrow_exception(e); }
-        throw std::runtime_error("another shard of the block-sharded solve failed in this iteration");
+        throw PeerFailure("another shard of the block-sharded solve failed in this iteration");
     }
     size_t si = 0, mi = 0;
     for (int c = 0; c < NCAND; ++c) {
@@ -1711,6 +1764,7 @@ inline void Solver::run() {
         coup_rows_d.upload(coup_rows.data(), coup_rows.size(), stream);
         roww_d.upload(rw.data(), P.Q, stream);
         PX_HIP(hipStreamSynchronize(stream));
+        if (group) setup_group_coupling();
     }
     part.alloc((size_t)NQ * PSTRIDE); part.zero(stream);
     scal.alloc(NQ); scal.zero(stream);

@@ -39,6 +39,7 @@
 #include "small_sign.hip.hpp"
 #include "sign_project.hip.hpp"
 #include "rccl_dl.hpp"
+#include "shard_group.hpp"
 #include "prep.hpp"
 
 namespace proxsdp {
@@ -99,9 +100,9 @@ struct PinnedBuf {
     PinnedBuf(PinnedBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
     PinnedBuf& operator=(PinnedBuf&& o) noexcept { if (this != &o) { release(); p = o.p; o.p = nullptr; } return *this; }
     ~PinnedBuf() { release(); }
-    void alloc(size_t count) {
+    void alloc(size_t count, unsigned flags = hipHostMallocDefault) {
         release();
-        if (hipHostMalloc((void**)&p, count * sizeof(double), hipHostMallocDefault) != hipSuccess) { p = nullptr; throw std::bad_alloc(); }
+        if (hipHostMalloc((void**)&p, count * sizeof(double), flags) != hipSuccess) { p = nullptr; throw std::bad_alloc(); }
     }
     void release() { if (p) { (void)hipHostFree(p); p = nullptr; } }
 };
@@ -311,8 +312,10 @@ class Solver {
 public:
     // time0 is stamped BEFORE prepare(): the reference's clock starts at the top of chambolle_pock
     // (pdhg.jl:13), so preprocessing and equilibration count towards Result.time and time_limit
-    Solver(const proxsdp_problem& prob, const proxsdp_options& opt_in, proxsdp_result& res_out)
-        : opt(opt_in), res(res_out), time0(now_s()), P(prepare(prob, &opt_in)) {
+    // grp / grp_rank: this solver is shard grp_rank of an in-process shard group (proxsdp_hip_solve_sharded)
+    Solver(const proxsdp_problem& prob, const proxsdp_options& opt_in, proxsdp_result& res_out,
+           ShardGroup* grp = nullptr, int grp_rank = 0)
+        : opt(opt_in), res(res_out), time0(now_s()), P(prepare(prob, &opt_in)), group(grp), group_rank(grp_rank) {
         user_resid = prob.eig_resid;
         reduce_fn = prob.reduce_fn;
         reduce_ctx = prob.reduce_ctx;
@@ -326,7 +329,7 @@ public:
             reduce_fn = nullptr;                     // (ignored when a communicator is given)
         }
         if (prob.n_coupling > 0) {
-            if ((!prob.reduce_fn || !prob.reduce_vec_fn) && nccl == nullptr)
+            if ((!prob.reduce_fn || !prob.reduce_vec_fn) && nccl == nullptr && group == nullptr)
                 throw std::invalid_argument("coupling rows need nccl_comm, or reduce_fn and reduce_vec_fn");
             if (!prob.coupling_rows || !prob.coupling_owned)
                 throw std::invalid_argument("coupling rows need coupling_rows and coupling_owned");
@@ -453,7 +456,22 @@ public:
     // block-sharded solve: scalar all-reduce across shards (include/proxsdp_hip.h)
     int (*reduce_fn)(void*, double*, int32_t, double*, int32_t) = nullptr;
     void* reduce_ctx = nullptr;
-    bool sharded() const { return reduce_fn != nullptr || nccl != nullptr; }
+    bool sharded() const { return reduce_fn != nullptr || nccl != nullptr || group != nullptr; }
+    // third mode, next to the callbacks and the native RCCL path: the shards are host threads of this process and share one
+    // group object (shard_group.hpp) -- scalar records through process memory, coupling rows by k_coupling_sum through the
+    // peers' device pointers
+    ShardGroup* group = nullptr;
+    int group_rank = 0;
+    unsigned long long coup_calls = 0;              // reduce_coupling calls so far: their parity picks the partial buffer
+    DevBuf<double> coup_part_d[2];                  // this shard's gathered partials, double-buffered
+    PinnedBuf coup_part_h[2];                       // ... staged in pinned host memory when a pair of devices has no peer access
+    DevBuf<const double*> coup_tab_d;               // [parity][shard] -> partial buffer, filled after the first barrier
+    bool coup_tab_ready = false;
+    void setup_group_coupling();
+    long long current_iteration() const { return iter; }   // (the iteration a failed shard stopped in: proxsdp_hip_solve_sharded)
+    void launch_coupling_sum(const double* const* tab, int nshard, const int* rows, int cnt, double* v) {
+        hipLaunchKernelGGL(dev::k_coupling_sum, dim3(ceil_div(cnt, dev::TPB)), dim3(dev::TPB), 0, stream, tab, nshard, rows, cnt, v);
+    }
     std::exception_ptr shard_error;                 // this shard's projection failed in the current iteration (see primal_step_dev)
     // native RCCL path (proxsdp_problem.nccl_comm): one all-gather of the packed scalar record per reduce, combined
     // on the host in rank order (the same bits on every rank); all-reduce of the coupling buffer on the stream
@@ -540,6 +558,7 @@ public:
     }
     void reduce_vec_host(std::vector<double>& v) {
         if (v.empty()) return;
+        if (group) { group->reduce_vec(group_rank, v); return; }
         if (nccl) {                                  // (exit path: slacks of the coupling rows)
             Rccl& rc = Rccl::get();
             if (nccl_tmp.n < v.size()) nccl_tmp.alloc(v.size());
@@ -555,6 +574,7 @@ public:
     }
     void reduce(std::vector<double>& sums, std::vector<double>& maxs) {
         if (nccl) { reduce_native(sums, maxs); return; }
+        if (group) { group->reduce(group_rank, sums, maxs); return; }
         if (!reduce_fn) return;
         if (reduce_fn(reduce_ctx, sums.data(), (int32_t)sums.size(), maxs.data(), (int32_t)maxs.size()) != 0)
             throw std::runtime_error("reduce_fn failed");

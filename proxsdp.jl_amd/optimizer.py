@@ -65,12 +65,24 @@ class Optimizer:
 
     # -- _optimize!
     def optimize(self, problem, eig_resid=None, trace_capacity=0, reduce=None, coupling=None, index_base=0,
-                 nccl_comm=None, resume=None, capture_iteration=None):
+                 nccl_comm=None, resume=None, capture_iteration=None, shards=None, device_ids=None, owners=None,
+                 soc_owners=None, free_owners=None):
+        """shards=k: the block-sharded solve from one call (binding.solve_sharded_inprocess) -- the library splits the model
+        into k shards and runs them as host threads of this process, shard s on device_ids[s] (default: all on
+        options.device_id); the result is the whole model's, the per-shard stats are kept in `self.shard_stats`."""
         self.empty()
         self.problem = problem
-        sol = binding.solve(problem, self.options, eig_resid=eig_resid, trace_capacity=trace_capacity,
-                            reduce=reduce, coupling=coupling, index_base=index_base, nccl_comm=nccl_comm,
-                            resume=resume, capture_iteration=capture_iteration)
+        self.shard_stats = None
+        if shards is not None:
+            if reduce is not None or coupling is not None or nccl_comm or resume is not None or capture_iteration is not None:
+                raise ValueError("shards=...: the model must be whole (no reduce / coupling / nccl_comm) and there is no state seam")
+            sol, self.shard_stats = binding.solve_sharded_inprocess(
+                problem, shards, device_ids=device_ids, owners=owners, soc_owners=soc_owners, free_owners=free_owners,
+                options=self.options, trace_capacity=trace_capacity, eig_resid=eig_resid, index_base=index_base)
+        else:
+            sol = binding.solve(problem, self.options, eig_resid=eig_resid, trace_capacity=trace_capacity,
+                                reduce=reduce, coupling=coupling, index_base=index_base, nccl_comm=nccl_comm,
+                                resume=resume, capture_iteration=capture_iteration)
         sign = -1.0 if problem.max_sense else 1.0          # :336-337
         sol.objval = sign * sol.objval + problem.objective_constant
         sol.dual_objval = sign * sol.dual_objval + problem.objective_constant
