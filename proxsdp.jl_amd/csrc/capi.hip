@@ -153,30 +153,32 @@ int proxsdp_hip_solve(const proxsdp_problem* prob, const proxsdp_options* opt, p
     return proxsdp_hip_solve_ex(prob, opt, res, nullptr, nullptr);
 }
 
+// both solve entry points: the result before the solve; a trace the caller gave no buffer for is not written
+static proxsdp_options begin_solve(const proxsdp_options* opt, proxsdp_result* res) {
+    proxsdp_options o = Engine::fix(opt);
+    res->status = PROXSDP_STATUS_NOT_CALLED;
+    res->trace_rows = 0; res->result_count = 0; res->certificate_found = 0;
+    res->status_string[0] = 0;
+    if (o.trace_capacity > 0 && !res->trace) o.trace_capacity = 0;
+    return o;
+}
+
 int proxsdp_hip_solve_ex(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
                          const proxsdp_state* resume, proxsdp_state* capture) {
     bool comm_aborted = false;
     const int rc = guarded([&]() -> int {
         if (!prob || !res) throw std::invalid_argument("NULL problem or result");
-        proxsdp_options o = Engine::fix(opt);
-        res->status = PROXSDP_STATUS_NOT_CALLED;
-        res->trace_rows = 0;
-        res->result_count = 0;
-        res->certificate_found = 0;
-        res->status_string[0] = 0;
-        if (o.trace_capacity > 0 && !res->trace) o.trace_capacity = 0;
+        const proxsdp_options o = begin_solve(opt, res);
         proxsdp::Solver S(*prob, o, *res);
         S.resume_state = resume;
         S.capture_state = capture;
         try {
             S.run();
         } catch (...) {
-            // native RCCL path: this rank leaves the solve -- stop its own pending collectives so that its stream drains;
-            // the peers' waits are bounded (Solver::wait_collective) and fail the same way.  Only when a collective of this
-            // solve may be pending: an argument error raised before the first one leaves the caller's communicator alone
-            // (ADVICE r4).  ncclCommAbort releases the communicator: the caller learns it through PROXSDP_E_COMM_ABORTED.
-            if (S.nccl && !S.nccl_aborted && S.collective_enqueued) S.abort_comm();
-            comm_aborted = S.nccl_aborted;
+            // this rank leaves the solve: the transport stops its own pending collectives so that its stream drains (RCCL:
+            // ncclCommAbort, only when a collective of this solve was enqueued; the peers' waits are bounded and fail the
+            // same way).  An aborted communicator is released: the caller learns it through PROXSDP_E_COMM_ABORTED.
+            comm_aborted = S.comm && S.comm->abort_if_pending();
             throw;
         }
         return 0;
@@ -251,21 +253,10 @@ int proxsdp_hip_solve_sharded(const proxsdp_problem* prob, const proxsdp_options
     std::string shard_msg;
     const int rc = guarded([&]() -> int {
         if (!prob || !res) throw std::invalid_argument("NULL problem or result");
-        const proxsdp_options o = [&]() {
-            proxsdp_options t = Engine::fix(opt);
-            if (t.trace_capacity > 0 && !res->trace) t.trace_capacity = 0;
-            return t;
-        }();
-        res->status = PROXSDP_STATUS_NOT_CALLED;
-        res->trace_rows = 0;
-        res->result_count = 0;
-        res->certificate_found = 0;
-        res->status_string[0] = 0;
+        const proxsdp_options o = begin_solve(opt, res);
         // ---- everything that is rejected before a thread starts
         const proxsdp::ShardPlan L = proxsdp::plan_shards(*prob, n_shards, psd_owner, soc_owner, free_owner);
-        if (!o.approx_norm) throw std::domain_error("approx_norm=false with a block-sharded solve is not implemented");
-        if (o.equilibration != 0 || o.equilibration_force != 0)
-            throw std::domain_error("equilibration with a block-sharded solve is not implemented");
+        proxsdp::reject_for_shard(false, !o.approx_norm, o.equilibration != 0 || o.equilibration_force != 0);
         if (o.debug_fail_iteration > 0) {
             const char* e = std::getenv("PROXSDP_HIP_FAULT_INJECTION");
             if (!(e && e[0] == '1')) throw std::invalid_argument("debug_fail_iteration needs PROXSDP_HIP_FAULT_INJECTION=1 in the environment (test switch)");
@@ -424,7 +415,7 @@ int proxsdp_hip_coupling_sum(const double* parts, int32_t n_shards, int64_t len,
         tab_d.upload(tab.data(), (size_t)n_shards, S.stream);
         rows_d.upload(r32.data(), (size_t)len, S.stream);
         v.upload(v_in, (size_t)n, S.stream);
-        S.launch_coupling_sum(tab_d.p, n_shards, rows_d.p, (int)len, v.p);
+        proxsdp::launch_coupling_sum(S.stream, tab_d.p, n_shards, rows_d.p, (int)len, v.p);
         PX_HIP(hipGetLastError());
         v.download(v_out, (size_t)n, S.stream);
         PX_HIP(hipStreamSynchronize(S.stream));
@@ -882,7 +873,7 @@ int proxsdp_host_preprocess(const proxsdp_problem* prob, int64_t* order, int64_t
                             double* c_scaled, double* frobenius_norm_M) {
     return guarded([&]() -> int {
         if (!prob) throw std::invalid_argument("NULL problem");
-        proxsdp::Prep R = proxsdp::prepare(*prob);
+        proxsdp::Prep R = proxsdp::prepare(*prob, nullptr, prob->reduce_fn != nullptr || prob->nccl_comm != nullptr);
         for (int64_t i = 0; i < R.n; ++i) {
             if (order) order[i] = R.ord[i];
             if (var_ordering) var_ordering[i] = R.inv[i];

@@ -46,85 +46,6 @@ inline void Solver::setup_long_rows(const std::vector<int>& rp) {
     PX_HIP(hipStreamSynchronize(stream));
 }
 
-// block-sharded solve: the coupling rows of M x hold this shard's partial sums; all-reduce them
-// (RCCL on the device buffer, or through host memory) -- SURVEY.md section 8e
-inline void Solver::reduce_coupling(double* Mx_dev) {
-    const int nc = (int)coup_rows.size();
-    if (group) {
-        // in-process group: gather this shard's partials, finish them (stream synchronisation), meet the peers, then ONE
-        // kernel on this shard's stream reads every shard's partials and writes the sums into M x.  The partials are
-        // double-buffered by the parity of this call counter: a shard overwrites a buffer only after a later barrier, which
-        // every peer reaches after its own sum kernel of this call has finished (it synchronises its stream before it)
-        const int par = (int)(coup_calls++ & 1);
-        hipLaunchKernelGGL(dev::k_gather_rows, dim3(ceil_div(nc, dev::TPB)), dim3(dev::TPB), 0, stream,
-                           (const double*)Mx_dev, (const int*)coup_rows_d.p, nc, coup_part_d[par].p);
-        if (group->stage_host) coup_part_d[par].download(coup_part_h[par].p, nc, stream);
-        wait_stream();
-        group->barrier();
-        const int S = group->size();
-        if (!coup_tab_ready) {                              // (every shard published its buffers before its first barrier)
-            std::vector<const double*> tab;
-            for (int q = 0; q < 2; ++q)
-                for (int s = 0; s < S; ++s) tab.push_back(group->coup_part[q][s]);
-            coup_tab_d.alloc(tab.size());
-            PX_HIP(hipMemcpy(coup_tab_d.p, tab.data(), tab.size() * sizeof(const double*), hipMemcpyHostToDevice));
-            coup_tab_ready = true;
-        }
-        launch_coupling_sum(coup_tab_d.p + (size_t)par * S, S, coup_rows_d.p, nc, Mx_dev);
-        return;
-    }
-    hipLaunchKernelGGL(dev::k_gather_rows, dim3(ceil_div(nc, dev::TPB)), dim3(dev::TPB), 0, stream,
-                       (const double*)Mx_dev, (const int*)coup_rows_d.p, nc, coup_buf_d.p);
-    if (nccl) {
-        // native: in-place sum over the shards on THIS stream -- no host synchronisation, no callback
-        Rccl& rc = Rccl::get();
-        collective_enqueued = true;
-        rc.check(rc.AllReduce(coup_buf_d.p, coup_buf_d.p, (size_t)nc, ncclFloat64, ncclSum, nccl, stream), "ncclAllReduce");
-        st.rccl_reductions++;
-    } else if (reduce_vec_on_device) {
-        PX_HIP(hipStreamSynchronize(stream));               // the collective runs on the caller's stream
-        if (reduce_vec_fn(reduce_ctx, coup_buf_d.p, nc, 1) != 0) throw std::runtime_error("reduce_vec_fn failed");
-    } else {
-        coup_host.resize(nc);
-        coup_buf_d.download(coup_host.data(), nc, stream);
-        PX_HIP(hipStreamSynchronize(stream));
-        reduce_vec_host(coup_host);
-        coup_buf_d.upload(coup_host.data(), nc, stream);
-    }
-    hipLaunchKernelGGL(dev::k_scatter_rows, dim3(ceil_div(nc, dev::TPB)), dim3(dev::TPB), 0, stream,
-                       Mx_dev, (const int*)coup_rows_d.p, nc, (const double*)coup_buf_d.p);
-}
-
-// in-process group: this shard's two partial buffers, published to the peers; peer access to every other device of the
-// group, enabled once (where some pair of devices has none, the group stages the partials in pinned host memory instead)
-inline void Solver::setup_group_coupling() {
-    const size_t nc = coup_rows.size();
-    const int S = group->size();
-    for (int par = 0; par < 2; ++par) {
-        coup_part_d[par].alloc(nc); coup_part_d[par].zero(stream);
-        if (group->stage_host) {
-            coup_part_h[par].alloc(nc, hipHostMallocPortable | hipHostMallocMapped);
-            group->coup_part[par][group_rank] = coup_part_h[par].p;
-        } else {
-            group->coup_part[par][group_rank] = coup_part_d[par].p;
-        }
-    }
-    if (!group->stage_host) {
-        const int mine = group->device[group_rank];
-        for (int s = 0; s < S; ++s) {
-            const int d = group->device[s];
-            if (d == mine) continue;
-            bool seen = false;
-            for (int q = 0; q < s; ++q) seen = seen || group->device[q] == d;
-            if (seen) continue;
-            const hipError_t e = hipDeviceEnablePeerAccess(d, 0);
-            if (e == hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
-            else PX_HIP(e);
-        }
-    }
-    PX_HIP(hipStreamSynchronize(stream));
-}
-
 // psd_projection! (prox_operators.jl:33-66), one block: reads the packed block of xin,
 // writes the projected block into xout (xin == xout on the dense path)
 // the branch condition of psd_projection! (prox_operators.jl:46-49)
@@ -599,6 +520,17 @@ inline void Solver::harvest_small_ranks() {
 
 // primal_step! (pdhg.jl:611-637)
 inline void Solver::primal_step_dev() {
+    // block-sharded solve: a shard whose projection fails (e.g. non-finite input) must still join this iteration's
+    // collectives, or its peers wait in them for ever: the error is kept, a flag travels with the iteration's scalar
+    // record (reduce_candidates), and every shard aborts after that reduce
+    auto shard_guard = [&](auto&& project) {
+        if (!sharded()) { project(); return; }
+        try {
+            if (opt.debug_fail_iteration > 0 && iter == opt.debug_fail_iteration)
+                throw std::runtime_error("injected projection failure (options.debug_fail_iteration)");
+            project();
+        } catch (...) { shard_error = std::current_exception(); }
+    };
     if (use_support) {
         // x_k (buffer xc) becomes the matrix to project IN PLACE on the support; the projection
         // is written to the other buffer, so off the support buffer xc still holds x_k = x_old
@@ -607,53 +539,32 @@ inline void Solver::primal_step_dev() {
         launch_primal_update_S(xcur, primal_step);
         std::fill(min_eig.begin(), min_eig.end(), 0.0);
         double t0 = now_s();
-        // block-sharded solve: a shard whose projection fails (e.g. non-finite input) must still join this
-        // iteration's collectives, or its peers wait in them for ever: the error is kept, a flag travels with the
-        // iteration's scalar record (reduce_candidates), and every shard aborts after that reduce
-        if (sharded()) {
-            try {
-                if (opt.debug_fail_iteration > 0 && iter == opt.debug_fail_iteration)
-                    throw std::runtime_error("injected projection failure (options.debug_fail_iteration)");
-                project_blocks(big_blocks, xcur, xnew, true);
-            } catch (...) { shard_error = std::current_exception(); }
-        } else {
-            project_blocks(big_blocks, xcur, xnew, true);
-        }
+        shard_guard([&]() { project_blocks(big_blocks, xcur, xnew, true); });
         st.t_psd += now_s() - t0;
         if (P.sdplen < P.n)
             hipLaunchKernelGGL(dev::k_tail_copy_res, dim3(n_res_wg - tile_base.back()), dim3(dev::TPB), 0, stream,
                                xcur, xnew, (long long)P.sdplen, (long long)P.n, mask_d.p,
                                respart_d.p + tile_base.back(), rstride);
         spmv(xnew, Mxbuf[1 - mxc].p);
-        if (!coup_rows.empty()) reduce_coupling(Mxbuf[1 - mxc].p);
+        reduce_coupling(Mxbuf[1 - mxc].p);
         return;
     }
     const double* xi = xbuf[xc].p;
     double* xo = xbuf[1 - xc].p;
     hipLaunchKernelGGL(dev::k_primal_update, dim3(grid_for(P.n)), dim3(dev::TPB), 0, stream,
                        xo, xi, Mtybuf[mtyc].p, c_d.p, primal_step, (long long)P.n);
-    auto project = [&]() {
+    // the general path inside a block-sharded solve: a shard with an SOC, a 1x1 block or no PSD block at all
+    if (sharded()) st.reserved_s[PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS]++;
+    shard_guard([&]() {
         if (!P.blocks.empty()) {
             double t0 = now_s();
             psd_projection(xo);
             st.t_psd += now_s() - t0;
         }
         if (!P.socs.empty()) launch_soc_project(xo, (int)P.socs.size());
-    };
-    if (sharded()) {
-        // the general path inside a block-sharded solve (a shard with an SOC, a 1x1 block or no PSD block at all): as on the
-        // support path above, a failing shard keeps its error and still joins this iteration's collectives
-        st.reserved_s[PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS]++;
-        try {
-            if (opt.debug_fail_iteration > 0 && iter == opt.debug_fail_iteration)
-                throw std::runtime_error("injected projection failure (options.debug_fail_iteration)");
-            project();
-        } catch (...) { shard_error = std::current_exception(); }
-    } else {
-        project();
-    }
+    });
     spmv(xo, Mxbuf[1 - mxc].p);
-    if (!coup_rows.empty()) reduce_coupling(Mxbuf[1 - mxc].p);
+    reduce_coupling(Mxbuf[1 - mxc].p);
 }
 
 // ---- linesearch! / dual_step! (pdhg.jl:532-609) + compute_residual! + compute_gap! (residuals.jl:2-71) on every vector path
@@ -1686,8 +1597,7 @@ inline void Solver::write_capture() {
 // chambolle_pock (pdhg.jl:1-530)
 inline void Solver::run() {
     const double t_init0 = now_s();
-    if (!opt.approx_norm && sharded())
-        throw std::domain_error("approx_norm=false with a block-sharded solve is not implemented");
+    if (sharded()) reject_for_shard(false, !opt.approx_norm, false);
     if (P.n <= 0) throw std::invalid_argument("problem has no variables");
     if (opt.convergence_window <= 0) throw std::invalid_argument("convergence_window must be positive");
     // (the reference's `for i in 1:max_linsearch_steps` simply runs no trial then and keeps stale norms; the batched
@@ -1758,13 +1668,13 @@ inline void Solver::run() {
         PX_HIP(hipStreamSynchronize(stream));
     }
     if (!coup_rows.empty()) {
-        coup_rows_d.alloc(coup_rows.size()); coup_buf_d.alloc(coup_rows.size()); roww_d.alloc(std::max<int64_t>(P.Q, 1));
+        coup_rows_d.alloc(coup_rows.size()); roww_d.alloc(std::max<int64_t>(P.Q, 1));
         std::vector<double> rw(P.Q, 1.0);
         for (size_t k = 0; k < coup_rows.size(); ++k) if (!coup_owned[k]) rw[coup_rows[k]] = 0.0;
         coup_rows_d.upload(coup_rows.data(), coup_rows.size(), stream);
         roww_d.upload(rw.data(), P.Q, stream);
         PX_HIP(hipStreamSynchronize(stream));
-        if (group) setup_group_coupling();
+        comm->setup_coupling(coup_rows.size(), stream);
     }
     part.alloc((size_t)NQ * PSTRIDE); part.zero(stream);
     scal.alloc(NQ); scal.zero(stream);

@@ -219,7 +219,15 @@ inline void finish_dense_equilibration(Prep& R, const proxsdp_options& opt, cons
     finish_matrix(R);
 }
 
-inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullptr) {
+// What a block-sharded solve does not serve, whatever its transport and entry point: each caller names what it has found
+// (prepare() is told by ITS caller that the problem is a shard)
+inline void reject_for_shard(bool dense_A, bool exact_norm, bool equilibration) {
+    if (dense_A) throw std::invalid_argument("A_dense cannot be combined with a block-sharded solve (reduce_fn / nccl_comm)");
+    if (exact_norm) throw std::domain_error("approx_norm=false with a block-sharded solve is not implemented");
+    if (equilibration) throw std::domain_error("equilibration with a block-sharded solve is not implemented");
+}
+
+inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullptr, bool shard = false) {
     Prep R;
     const int base = P.index_base;
     if (base != 0 && base != 1) throw std::invalid_argument("index_base must be 0 or 1");
@@ -230,8 +238,7 @@ inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullp
     R.n = P.n; R.p = P.p; R.m = P.m; R.Q = P.p + P.m;
     const bool dense = P.M_dense != nullptr;
     if (!dense) check_csc(P.A, P.p, P.n, base, "A");
-    else if (P.reduce_fn != nullptr || P.nccl_comm != nullptr)
-        throw std::invalid_argument("A_dense cannot be combined with a block-sharded solve (reduce_fn / nccl_comm)");
+    else if (shard) reject_for_shard(true, false, false);
     check_csc(P.G, P.m, P.n, base, "G");
     if ((P.p > 0 && !P.b) || (P.m > 0 && !P.h) || (P.n > 0 && !P.c))
         throw std::invalid_argument("b, h or c is NULL");
@@ -342,7 +349,7 @@ inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullp
     }
     if (opt != nullptr && opt->equilibration_force && !R.equil_deferred) equil = true;
     if (equil) {
-        if (P.reduce_fn != nullptr || P.nccl_comm != nullptr) throw std::domain_error("equilibration with a block-sharded solve is not implemented");
+        if (shard) reject_for_shard(false, false, true);
         if (R.Q == 0 || R.n == 0) throw std::invalid_argument("equilibration needs a non-empty M");
         equilibrate_host(R, *opt, R.Ediag, R.Ddiag);
         R.equilibrated = true;

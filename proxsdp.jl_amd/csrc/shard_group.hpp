@@ -1,7 +1,7 @@
-// In-process shard group: the collectives of a block-sharded solve whose shards are host THREADS of one process
-// (proxsdp_hip_solve_sharded), next to the callback mode (reduce_fn / reduce_vec_fn) and the native RCCL mode (nccl_comm).
-// No HIP calls here: the group moves host records and publishes device pointers; the kernel that sums the coupling rows
-// through those pointers is launched by Solver::reduce_coupling.
+// In-process shard group: the meeting point of a block-sharded solve whose shards are host THREADS of one process
+// (proxsdp_hip_solve_sharded).  GroupComm (shard_comm.hip.hpp) is the transport built on it; the callbacks and the RCCL
+// communicator are the other two.  No HIP calls here: the group moves host records and publishes device pointers; the
+// kernel that sums the coupling rows through those pointers is launched by GroupComm.
 //
 // barrier(): all shards meet, or the call throws.  It never hangs a caller: a shard that leaves the solve for any reason
 // (leave(): an argument error in its sub-problem, a failed projection, an exception, or simply the end of its solve) wakes
@@ -35,16 +35,30 @@ struct PeerFailure : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
 
+// how long a shard waits for its peers in one collective, whatever the transport
+inline double collective_timeout_s() {
+    const char* e = std::getenv("PROXSDP_HIP_COLLECTIVE_TIMEOUT_S");
+    return (e && std::atof(e) > 0.0) ? std::atof(e) : 300.0;
+}
+
+// The shards' packed records [sums | maxs] combined in rank order -- acc = rec(0); acc += rec(r) for r = 1, 2, ... and the
+// element-wise std::max(acc, rec(r)) in the same order: sharded.make_reduce's order, the same bits on every shard.
+// rec(r) points to shard r's record, wherever the transport keeps it.
+template <typename Rec>
+inline void combine_in_rank_order(Rec rec, int world, size_t ns, size_t nm, double* sums, double* maxs) {
+    for (size_t q = 0; q < ns + nm; ++q) {
+        double a = rec(0)[q];
+        for (int r = 1; r < world; ++r) a = q < ns ? a + rec(r)[q] : std::max(a, rec(r)[q]);
+        (q < ns ? sums[q] : maxs[q - ns]) = a;
+    }
+}
+
 class ShardGroup {
 public:
     explicit ShardGroup(int n_shards, double timeout_s = -1.0)
-        : coup_part(2, std::vector<double*>(n_shards, nullptr)), device(n_shards, 0), S_(n_shards), calls_(n_shards, 0) {
+        : coup_part(2, std::vector<double*>(n_shards, nullptr)), device(n_shards, 0), S_(n_shards),
+          timeout_s_(timeout_s > 0.0 ? timeout_s : collective_timeout_s()), calls_(n_shards, 0) {
         for (int par = 0; par < 2; ++par) rec_[par].resize(n_shards);
-        if (timeout_s <= 0.0) {
-            const char* e = std::getenv("PROXSDP_HIP_COLLECTIVE_TIMEOUT_S");
-            timeout_s = (e && std::atof(e) > 0.0) ? std::atof(e) : 300.0;
-        }
-        timeout_s_ = timeout_s;
     }
     int size() const { return S_; }
 
@@ -99,7 +113,7 @@ public:
     }
 
     // store rec[0 .. n) as shard r's record of this call, meet, and return the parity under which all records are readable
-    // (record(par, s)) until this shard's next-but-one call
+    // (rec_[par][s]) until this shard's next-but-one call
     int exchange(int r, const double* rec, size_t n) {
         const int par = (int)(calls_[r]++ & 1);
         rec_[par][r].assign(rec, rec + n);
@@ -109,35 +123,20 @@ public:
                 throw std::logic_error("block-sharded solve: the shards' records differ in length (different call sequences)");
         return par;
     }
-    const std::vector<double>& record(int par, int s) const { return rec_[par][s]; }
 
-    // scalar reduce: the packed record [sums | maxs] of every shard, combined in shard order -- acc = rec[0]; acc += rec[r]
-    // for r = 1, 2, ... and the element-wise maximum: sharded.make_reduce's order, the same bits on every shard
+    // scalar reduce: the packed record [sums | maxs] of every shard, combined in shard order
     void reduce(int r, std::vector<double>& sums, std::vector<double>& maxs) {
         const size_t ns = sums.size(), nm = maxs.size();
         if (ns + nm == 0) return;
         std::vector<double> mine(sums);
         mine.insert(mine.end(), maxs.begin(), maxs.end());
         const int par = exchange(r, mine.data(), ns + nm);
-        for (size_t q = 0; q < ns; ++q) {
-            double a = rec_[par][0][q];
-            for (int s = 1; s < S_; ++s) a += rec_[par][s][q];
-            sums[q] = a;
-        }
-        for (size_t q = 0; q < nm; ++q) {
-            double a = rec_[par][0][ns + q];
-            for (int s = 1; s < S_; ++s) a = std::max(a, rec_[par][s][ns + q]);
-            maxs[q] = a;
-        }
+        combine_in_rank_order([&](int s) { return rec_[par][s].data(); }, S_, ns, nm, sums.data(), maxs.data());
     }
     // element-wise sum of a host vector over the shards, in shard order (exit path: slacks of the coupling rows)
     void reduce_vec(int r, std::vector<double>& v) {
         const int par = exchange(r, v.data(), v.size());
-        for (size_t q = 0; q < v.size(); ++q) {
-            double a = rec_[par][0][q];
-            for (int s = 1; s < S_; ++s) a += rec_[par][s][q];
-            v[q] = a;
-        }
+        combine_in_rank_order([&](int s) { return rec_[par][s].data(); }, S_, v.size(), 0, v.data(), nullptr);
     }
 
     // coupling rows: coup_part[parity][s] = shard s's gathered partial buffer (device memory on device[s], or pinned host
@@ -153,7 +152,7 @@ private:
                           : "another shard of the block-sharded solve left the solve";
     }
     const int S_;
-    double timeout_s_ = 300.0;
+    const double timeout_s_;
     std::mutex mu_;
     std::condition_variable cv_;
     int arrived_ = 0, left_ = 0;

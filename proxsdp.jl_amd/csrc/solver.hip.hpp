@@ -115,6 +115,22 @@ static inline int grid_for(long long n) {          // memory-bound passes: cap t
     long long g = (n + dev::TPB - 1) / dev::TPB;
     return (int)std::max<long long>(1, std::min<long long>(g, 2048));
 }
+// spin on a stream or event query until it reports completion; every 4096 polls the caller may give up (by throwing)
+template <typename Query, typename GiveUp>
+inline void poll_ready(Query query, GiveUp give_up) {
+    for (unsigned spins = 0;; ++spins) {
+        const hipError_t e = query();
+        if (e == hipSuccess) return;
+        if (e != hipErrorNotReady) PX_HIP(e);
+        if ((spins & 0xfff) == 0xfff) give_up();
+#if defined(__x86_64__)
+        _mm_pause();
+#endif
+    }
+}
+}  // namespace proxsdp
+#include "shard_comm.hip.hpp"       // (the transports of a block-sharded solve: built on the buffers and macros above)
+namespace proxsdp {
 
 // structs.jl:2-30
 struct CircularVector {
@@ -315,26 +331,17 @@ public:
     // grp / grp_rank: this solver is shard grp_rank of an in-process shard group (proxsdp_hip_solve_sharded)
     Solver(const proxsdp_problem& prob, const proxsdp_options& opt_in, proxsdp_result& res_out,
            ShardGroup* grp = nullptr, int grp_rank = 0)
-        : opt(opt_in), res(res_out), time0(now_s()), P(prepare(prob, &opt_in)), group(grp), group_rank(grp_rank) {
+        : opt(opt_in), res(res_out), time0(now_s()), P(prepare(prob, &opt_in, grp != nullptr || prob.reduce_fn != nullptr || prob.nccl_comm != nullptr)) {
         user_resid = prob.eig_resid;
-        reduce_fn = prob.reduce_fn;
-        reduce_ctx = prob.reduce_ctx;
-        if (prob.nccl_comm != nullptr) {
-            // native path: the library issues the collectives itself on its own stream (rccl_dl.hpp)
-            Rccl& rc = Rccl::get();
-            rc.require();
-            nccl = static_cast<ncclComm_t>(prob.nccl_comm);
-            rc.check(rc.CommCount(nccl, &nccl_world), "ncclCommCount");
-            rc.check(rc.CommUserRank(nccl, &nccl_rank), "ncclCommUserRank");
-            reduce_fn = nullptr;                     // (ignored when a communicator is given)
-        }
+        // the transport: the group, else the communicator (reduce_fn is ignored beside one), else the callbacks
+        if (grp) comm.reset(new GroupComm(*grp, grp_rank, opt.host_wait_spin != 0));
+        else if (prob.nccl_comm != nullptr) comm.reset(new RcclComm(prob.nccl_comm, st));
+        else if (prob.reduce_fn != nullptr) comm.reset(new CallbackComm(prob));
         if (prob.n_coupling > 0) {
-            if ((!prob.reduce_fn || !prob.reduce_vec_fn) && nccl == nullptr && group == nullptr)
+            if ((!prob.reduce_fn || !prob.reduce_vec_fn) && prob.nccl_comm == nullptr && grp == nullptr)
                 throw std::invalid_argument("coupling rows need nccl_comm, or reduce_fn and reduce_vec_fn");
             if (!prob.coupling_rows || !prob.coupling_owned)
                 throw std::invalid_argument("coupling rows need coupling_rows and coupling_owned");
-            reduce_vec_fn = nccl ? nullptr : prob.reduce_vec_fn;
-            reduce_vec_on_device = nccl ? true : prob.reduce_vec_on_device != 0;
             for (int64_t k = 0; k < prob.n_coupling; ++k) {
                 const int64_t r = prob.coupling_rows[k];
                 if (r < 0 || r >= prob.p + prob.m) throw std::invalid_argument("coupling row out of range");
@@ -453,91 +460,25 @@ public:
     EigEvents ev;
     proxsdp_stats st{};
     const double* user_resid = nullptr;
-    // block-sharded solve: scalar all-reduce across shards (include/proxsdp_hip.h)
-    int (*reduce_fn)(void*, double*, int32_t, double*, int32_t) = nullptr;
-    void* reduce_ctx = nullptr;
-    bool sharded() const { return reduce_fn != nullptr || nccl != nullptr || group != nullptr; }
-    // third mode, next to the callbacks and the native RCCL path: the shards are host threads of this process and share one
-    // group object (shard_group.hpp) -- scalar records through process memory, coupling rows by k_coupling_sum through the
-    // peers' device pointers
-    ShardGroup* group = nullptr;
-    int group_rank = 0;
-    unsigned long long coup_calls = 0;              // reduce_coupling calls so far: their parity picks the partial buffer
-    DevBuf<double> coup_part_d[2];                  // this shard's gathered partials, double-buffered
-    PinnedBuf coup_part_h[2];                       // ... staged in pinned host memory when a pair of devices has no peer access
-    DevBuf<const double*> coup_tab_d;               // [parity][shard] -> partial buffer, filled after the first barrier
-    bool coup_tab_ready = false;
-    void setup_group_coupling();
+    // block-sharded solve: how this shard reaches the others (shard_comm.hip.hpp); none when the solve is not sharded
+    std::unique_ptr<ShardComm> comm;
+    bool sharded() const { return comm != nullptr; }
     long long current_iteration() const { return iter; }   // (the iteration a failed shard stopped in: proxsdp_hip_solve_sharded)
-    void launch_coupling_sum(const double* const* tab, int nshard, const int* rows, int cnt, double* v) {
-        hipLaunchKernelGGL(dev::k_coupling_sum, dim3(ceil_div(cnt, dev::TPB)), dim3(dev::TPB), 0, stream, tab, nshard, rows, cnt, v);
-    }
     std::exception_ptr shard_error;                 // this shard's projection failed in the current iteration (see primal_step_dev)
-    // native RCCL path (proxsdp_problem.nccl_comm): one all-gather of the packed scalar record per reduce, combined
-    // on the host in rank order (the same bits on every rank); all-reduce of the coupling buffer on the stream
-    ncclComm_t nccl = nullptr;
-    int nccl_world = 1, nccl_rank = 0;
-    DevBuf<double> nccl_send, nccl_recv, nccl_tmp;
-    PinnedBuf nccl_host;
-    size_t nccl_cap = 0;
-    void reduce_native(std::vector<double>& sums, std::vector<double>& maxs);
+    void reduce(std::vector<double>& sums, std::vector<double>& maxs) { if (comm) comm->reduce(stream, sums, maxs); }
+    void reduce_vec_host(std::vector<double>& v) { if (!v.empty()) comm->reduce_vec_host(stream, v); }
     // coupling rows of a block-sharded solve (include/proxsdp_hip.h): partial M x summed over the shards
-    int (*reduce_vec_fn)(void*, double*, int64_t, int32_t) = nullptr;
-    bool reduce_vec_on_device = false;
     std::vector<int> coup_rows;
     std::vector<char> coup_owned;
     DevBuf<int> coup_rows_d;
-    DevBuf<double> coup_buf_d, roww_d;
-    std::vector<double> coup_host;
-    void reduce_coupling(double* Mx_dev);          // Mx[coupling rows] <- sum over shards
+    DevBuf<double> roww_d;
+    void reduce_coupling(double* Mx_dev) {         // Mx[coupling rows] <- sum over shards
+        if (!coup_rows.empty()) comm->reduce_coupling(stream, Mx_dev, coup_rows_d.p, (int)coup_rows.size());
+    }
     // wait for the solver's (or the calling block thread's) stream at a read-back on the critical path
     void wait_stream() {
-        hipStream_t s = stream;
-        if (nccl) { wait_collective(s); return; }
-        if (opt.host_wait_spin == 0) { PX_HIP(hipStreamSynchronize(s)); return; }
-        for (;;) {
-            const hipError_t e = hipStreamQuery(s);
-            if (e == hipSuccess) return;
-            if (e != hipErrorNotReady) PX_HIP(e);
-#if defined(__x86_64__)
-            _mm_pause();
-#endif
-        }
+        if (!comm || !comm->bounded_wait(stream)) wait_for_stream(stream, opt.host_wait_spin != 0);
     }
-    // Native RCCL path: every host wait that may sit behind a collective is BOUNDED (a peer that left the
-    // solve -- an exception between two collectives, a dead process -- used to leave this rank in
-    // hipStreamSynchronize for ever).  After PROXSDP_HIP_COLLECTIVE_TIMEOUT_S seconds (default 300) without progress
-    // this rank aborts its communicator (ncclCommAbort: its own pending collective kernels stop) and fails the solve.
-    double collective_timeout_s = -1.0;
-    void wait_collective(hipStream_t s) {
-        if (collective_timeout_s < 0.0) {
-            const char* e = std::getenv("PROXSDP_HIP_COLLECTIVE_TIMEOUT_S");
-            collective_timeout_s = (e && std::atof(e) > 0.0) ? std::atof(e) : 300.0;
-        }
-        const double t0 = now_s();
-        for (unsigned spins = 0;; ++spins) {
-            const hipError_t e = hipStreamQuery(s);
-            if (e == hipSuccess) return;
-            if (e != hipErrorNotReady) PX_HIP(e);
-            if ((spins & 0xfff) == 0xfff && now_s() - t0 > collective_timeout_s) {
-                abort_comm();
-                throw std::runtime_error("block-sharded solve: a collective did not complete within " +
-                                         std::to_string((int)collective_timeout_s) + " s (did another shard leave the solve?)");
-            }
-#if defined(__x86_64__)
-            _mm_pause();
-#endif
-        }
-    }
-    // local abort of the native communicator (it is unusable afterwards; the caller destroys it)
-    void abort_comm() {
-        if (!nccl) return;
-        Rccl& rc = Rccl::get();
-        if (rc.ok() && rc.CommAbort) (void)rc.CommAbort(nccl);
-        nccl_aborted = true;
-    }
-    bool nccl_aborted = false;
-    bool collective_enqueued = false;     // a collective of this solve may be pending on the stream (abort only then)
     // state seam (proxsdp_hip_solve_ex): continue from / write out the iterate at an iteration boundary
     const proxsdp_state* resume_state = nullptr;
     proxsdp_state* capture_state = nullptr;
@@ -546,38 +487,8 @@ public:
     void write_capture();
     int ada_count = 0;                    // pdhg.jl:306-332 (a local of chambolle_pock)
     void wait_event(hipEvent_t ev) {
-        if (opt.host_wait_spin == 0) { PX_HIP(hipEventSynchronize(ev)); return; }
-        for (;;) {
-            const hipError_t e = hipEventQuery(ev);
-            if (e == hipSuccess) return;
-            if (e != hipErrorNotReady) PX_HIP(e);
-#if defined(__x86_64__)
-            _mm_pause();
-#endif
-        }
-    }
-    void reduce_vec_host(std::vector<double>& v) {
-        if (v.empty()) return;
-        if (group) { group->reduce_vec(group_rank, v); return; }
-        if (nccl) {                                  // (exit path: slacks of the coupling rows)
-            Rccl& rc = Rccl::get();
-            if (nccl_tmp.n < v.size()) nccl_tmp.alloc(v.size());
-            nccl_tmp.upload(v.data(), v.size(), stream);
-            collective_enqueued = true;
-            rc.check(rc.AllReduce(nccl_tmp.p, nccl_tmp.p, v.size(), ncclFloat64, ncclSum, nccl, stream), "ncclAllReduce");
-            nccl_tmp.download(v.data(), v.size(), stream);
-            wait_collective(stream);
-            st.rccl_reductions++;
-            return;
-        }
-        if (reduce_vec_fn(reduce_ctx, v.data(), (int64_t)v.size(), 0) != 0) throw std::runtime_error("reduce_vec_fn failed");
-    }
-    void reduce(std::vector<double>& sums, std::vector<double>& maxs) {
-        if (nccl) { reduce_native(sums, maxs); return; }
-        if (group) { group->reduce(group_rank, sums, maxs); return; }
-        if (!reduce_fn) return;
-        if (reduce_fn(reduce_ctx, sums.data(), (int32_t)sums.size(), maxs.data(), (int32_t)maxs.size()) != 0)
-            throw std::runtime_error("reduce_fn failed");
+        if (opt.host_wait_spin == 0) PX_HIP(hipEventSynchronize(ev));
+        else poll_ready([&]() { return hipEventQuery(ev); }, []() {});
     }
     // global (all-shard) problem constants; equal to the local ones when not sharded
     double g_n = 0, g_Q = 0, g_p = 0, g_m = 0, g_norm_b = 0, g_norm_h = 0, g_norm_c = 0, g_frob = 0;
@@ -2423,40 +2334,6 @@ inline void Solver::merge_block_stats() {
         W.mv_iter = 0; W.recon_r = 0;
     }
 #undef PX_MERGE
-}
-
-// scalar reduce of a block-sharded solve over RCCL: every rank's packed record [sums | maxs] is all-gathered on the
-// solver's stream (one collective, <= 400 bytes per rank: latency-bound over xGMI) and combined on the host in
-// rank order, so every rank computes the same bits and takes the same step-size / rank / termination decisions
-inline void Solver::reduce_native(std::vector<double>& sums, std::vector<double>& maxs) {
-    const size_t ns = sums.size(), nm = maxs.size(), n = ns + nm;
-    if (n == 0) return;
-    Rccl& rc = Rccl::get();
-    const size_t W = (size_t)nccl_world;
-    if (nccl_cap < n) {
-        nccl_cap = std::max<size_t>(n, 64);
-        nccl_send.alloc(nccl_cap); nccl_recv.alloc(nccl_cap * W); nccl_host.alloc(nccl_cap * (W + 1));
-    }
-    double* h = nccl_host.p;
-    std::copy(sums.begin(), sums.end(), h);
-    std::copy(maxs.begin(), maxs.end(), h + ns);
-    PX_HIP(hipMemcpyAsync(nccl_send.p, h, n * sizeof(double), hipMemcpyHostToDevice, stream));
-    collective_enqueued = true;
-    rc.check(rc.AllGather(nccl_send.p, nccl_recv.p, n, ncclFloat64, nccl, stream), "ncclAllGather");
-    double* all = h + nccl_cap;
-    PX_HIP(hipMemcpyAsync(all, nccl_recv.p, n * W * sizeof(double), hipMemcpyDeviceToHost, stream));
-    wait_collective(stream);
-    for (size_t q = 0; q < ns; ++q) {
-        double a = all[q];
-        for (size_t r = 1; r < W; ++r) a += all[r * n + q];
-        sums[q] = a;
-    }
-    for (size_t q = 0; q < nm; ++q) {
-        double a = all[ns + q];
-        for (size_t r = 1; r < W; ++r) a = std::max(a, all[r * n + ns + q]);
-        maxs[q] = a;
-    }
-    st.rccl_reductions++;
 }
 
 }  // namespace proxsdp

@@ -212,3 +212,19 @@ def test_a_shard_that_leaves_makes_the_others_return(S, leave_shard, leave_after
         assert done[s] == leave_after
         assert failed[s] == (0 if s == leave_shard else 1)
         assert np.array_equal(out[s, :leave_after], exp[:leave_after])       # the rounds before it are whole
+
+
+def test_stand_alone_group_check_builds_and_passes(tmp_path):
+    """tests/c_harness/shard_group_check.cpp: reduce / reduce_vec of the group from 1, 2, 3 and 8 threads against a serial
+    rank-order sum, bit for bit, with a shard that leaves mid-way -- shard_group.hpp alone, no HIP, no library.  (The
+    same program is what the thread and address sanitizers are pointed at; here it is built plain.)"""
+    import pathlib
+    import subprocess
+    root = pathlib.Path(__file__).resolve().parent.parent
+    exe = tmp_path / "shard_group_check"
+    cmd = ["g++", "-std=c++17", "-O1", "-pthread", "-Wall", "-Werror", f"-I{root / 'proxsdp.jl_amd' / 'csrc'}",
+           str(root / "tests" / "c_harness" / "shard_group_check.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.count(": ok") == 4, r.stdout
