@@ -57,7 +57,10 @@ extern "C" {
  * support = 2: same sizes and offsets, version unchanged;
  * later: proxsdp_hip_solve_sharded (a whole model, split by the library, one shard per host thread and device of ONE process),
  * with its test entries proxsdp_host_split_shard, proxsdp_host_group_reduce, proxsdp_hip_coupling_sum: functions only, no
- * struct changed -- as for proxsdp_hip_dense_scaling before, the version stays */
+ * struct changed -- as for proxsdp_hip_dense_scaling before, the version stays;
+ * later: proxsdp_hip_solve_factored (the low-rank factors of the PSD solution beside the result) with the new struct
+ * proxsdp_psd_factors and the test entries proxsdp_hip_factor_residual / _kernel: functions and one new struct, no existing
+ * struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -602,6 +605,51 @@ int  proxsdp_hip_solve_sharded(const proxsdp_problem* prob, const proxsdp_option
                                const int32_t* psd_owner, const int32_t* soc_owner, const int32_t* free_owner,
                                proxsdp_result* res, proxsdp_stats* shard_stats);
 
+/* ------------------------------------------- the solve, with the low-rank factors of its PSD solution
+ * The projection computes the PSD iterate as X = V Lam+ V' from r Ritz pairs (prox_operators.jl:89-109) and the reference
+ * returns only the matrix (Result.primal): a caller who needs the factor -- Goemans-Williamson rounding, sensor positions, a
+ * rank-one symbol vector -- pays a dense eigendecomposition of what was just built from it.  This entry hands the factor out.
+ * The solve is proxsdp_hip_solve's, bit for bit (iterates, counts, res, stats other than exit_time); the factors are taken
+ * at the snapshot that fills res (the last one when a certificate search takes several), from the block exactly as it is
+ * returned in res->primal -- res->primal itself may be NULL.  Cones in the caller's cone order; a PSD cone's variable list
+ * is its upper triangle column by column, so row i of V is row i of the matrix.
+ *   cap[k]      columns the caller has room for; 0 = nothing wanted for cone k: nothing is computed or written for it (rank,
+ *               rank_found, source, resid, xnorm = 0)
+ *   vectors     cone k at vectors + vec_ptr[k]: side_k x rank[k], column-major, ld = side_k; values at values + val_ptr[k]:
+ *               rank[k] eigenvalues, descending, all > 0.  When rank_found[k] > cap[k] the cap[k] largest pairs are written
+ *   source      PROXSDP_FACTOR_RITZ: the Ritz pairs of the last projection (the block is still their reconstruction: the
+ *               Krylov branch, a Lanczos-served full_eig!, not equilibrated) -- one gather and one 8 side rank byte
+ *               download, no eigensolve, accurate to the reconstruction's rounding, orthonormal to what the Lanczos run
+ *               left (krylovkit_tol);  PROXSDP_FACTOR_EIG: one dsyevd of the final block, pairs with lambda > 0 kept (the
+ *               other full_eig! engines, equilibrated solves, a snapshot inside a certificate search before the next
+ *               projection);  PROXSDP_FACTOR_NONE: a 1x1 cone (V = [1], lambda = x when x > 0, else rank 0)
+ *   resid       ||X_k - V diag(values) V'||_F of what was written against the returned block, xnorm = ||X_k||_F, both over
+ *               the full symmetric matrix (off-diagonals count twice), computed on the device (k_factor_residual); with
+ *               rank_found[k] > cap[k] resid reports what was cut
+ * PROXSDP_E_INVALID before any device call: fac NULL, a wrong struct_size, n_psd != prob->n_psd, a NULL array (vectors /
+ * values may be NULL only when no cone asks for a column), a negative cap, a vec_ptr / val_ptr span smaller than
+ * side_k cap[k] / cap[k] (cap counted up to side_k: a block has no more pairs).  PROXSDP_E_UNSUPP: prob is a shard
+ * (reduce_fn, reduce_vec_fn, nccl_comm, n_coupling != 0).  proxsdp_hip_solve_sharded and the state seam have no such variant. */
+#define PROXSDP_FACTOR_NONE 0
+#define PROXSDP_FACTOR_RITZ 1
+#define PROXSDP_FACTOR_EIG  2
+typedef struct proxsdp_psd_factors {
+    int64_t struct_size;     /* = sizeof(proxsdp_psd_factors) */
+    int64_t n_psd;           /* IN: must equal prob->n_psd */
+    const int64_t* cap;      /* IN  n_psd: columns available for cone k (0 = none wanted for it) */
+    const int64_t* vec_ptr;  /* IN  n_psd+1: offsets into vectors; vec_ptr[k+1]-vec_ptr[k] >= side_k*cap[k] */
+    const int64_t* val_ptr;  /* IN  n_psd+1: offsets into values;  >= cap[k] */
+    double*  vectors;        /* OUT cone k: side_k x rank[k], column-major, ld = side_k */
+    double*  values;         /* OUT cone k: rank[k] eigenvalues, DESCENDING, all > 0 */
+    int64_t* rank;           /* OUT n_psd: columns written = min(cap[k], rank_found[k]) */
+    int64_t* rank_found;     /* OUT n_psd: positive pairs the block has */
+    int32_t* source;         /* OUT n_psd: PROXSDP_FACTOR_* */
+    double*  resid;          /* OUT n_psd: ||X_k - V diag(lam) V'||_F, X_k = the block as returned in res->primal */
+    double*  xnorm;          /* OUT n_psd: ||X_k||_F */
+} proxsdp_psd_factors;
+int  proxsdp_hip_solve_factored(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                                proxsdp_psd_factors* fac);
+
 /* ------------------------------------------- RCCL communicator helpers (block-sharded solves)
  * The library loads librccl at run time (dlopen; it does not link it).  One rank calls _unique_id and
  * ships the 128 bytes to the others by any means (MPI, torch.distributed, a file); every rank then calls
@@ -657,6 +705,18 @@ int proxsdp_hip_reconstruct(const double* Z, const double* lambda, int64_t n, in
  * SYRK (v_mfma_f64_16x16x4_f64), -1 = the library's choice (options.reconstruct_mfma auto) */
 int proxsdp_hip_reconstruct_kernel(const double* Z, const double* lambda, int64_t n, int32_t r, int32_t mfma,
                                    double* packed_out, int32_t repeat, double* ms);
+
+/* *resid2 = ||X - V diag(lam) V'||_F^2 and *xnorm2 = ||X||_F^2 for X = smat(packed) with PLAIN entries (upper triangle
+ * column by column, no sqrt(2)) of side n, V n x r column-major with leading dimension ldv >= n (rows n .. ldv-1 are never
+ * read), both norms over the full symmetric matrix: k_factor_residual, the MFMA SYRK tiling of the reconstruction with the
+ * tiles' partial sums added in tile order.  r = 0 (V, lam may be NULL): *resid2 = *xnorm2. */
+int proxsdp_hip_factor_residual(const double* packed, int64_t n, const double* V, int64_t ldv,
+                                const double* lam, int32_t r, double* resid2, double* xnorm2);
+/* the same, timed: repeat > 0 re-launches the kernel on the device-resident data, *ms = mean kernel time (events); the sums
+ * returned are then those of one more launch after the timed ones (the kernel only reads the block: they are the same) */
+int proxsdp_hip_factor_residual_kernel(const double* packed, int64_t n, const double* V, int64_t ldv,
+                                       const double* lam, int32_t r, double* resid2, double* xnorm2,
+                                       int32_t repeat, double* ms);
 
 /* full_eig! (prox_operators.jl:111-126) of one packed block, timed: sign = 0 rocSOLVER dsyevd + reconstruction,
  * 1 = the sign-function projection (options.full_eig_sign) with the default options.sign_start_row, 100 + k = the

@@ -154,6 +154,22 @@ mutable struct CResult           # proxsdp_result
     CResult() = new()
 end
 
+struct PsdFactors                # proxsdp_psd_factors
+    struct_size::Int64
+    n_psd::Int64
+    cap::Ptr{Int64}
+    vec_ptr::Ptr{Int64}
+    val_ptr::Ptr{Int64}
+    vectors::Ptr{Float64}
+    values::Ptr{Float64}
+    rank::Ptr{Int64}
+    rank_found::Ptr{Int64}
+    source::Ptr{Int32}
+    resid::Ptr{Float64}
+    xnorm::Ptr{Float64}
+end
+const FACTOR_NONE = Int32(0); const FACTOR_RITZ = Int32(1); const FACTOR_EIG = Int32(2)   # PROXSDP_FACTOR_*
+
 # proxsdp_options is filled by name, exactly like MOI.RawOptimizerAttribute does for the
 # reference (src/MOI_wrapper.jl:84-93): an opaque, suitably large and aligned buffer plus
 # proxsdp_hip_default_options / proxsdp_hip_set_option keeps this file independent of the C
@@ -187,9 +203,17 @@ src/pdhg.jl:647-663).
 library splits the model over `n_shards` shards, runs them as host threads of this process, shard `s` on device
 `device_ids[s]` (0-based HIP ordinals; default: all on the device the options name), and returns the whole model's
 result in the caller's order.  Cones are dealt out round-robin (PSD cones, then SOC cones, then the free variables).
+
+`factors = true` or a vector of column caps, one per PSD cone (0 = none for that cone): the same solve through
+`proxsdp_hip_solve_factored`; the return value is then `(result, factors)` with `factors[k] = (values, vectors, info)`,
+`X_k ≈ vectors * Diagonal(values) * vectors'`, values descending and positive, `info = (rank, rank_found, source, resid,
+xnorm)` -- what a caller of the reference computes with `eigen` on the returned block.  Not with `n_shards > 1`.
+(This wrapper cannot be executed where the library is tested: there is no Julia there.  Its struct is checked against the
+header field by field, the call itself is exercised through the ctypes binding.)
 """
 function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
-                            n_shards::Integer = 1, device_ids::Union{Nothing,AbstractVector{<:Integer}} = nothing)
+                            n_shards::Integer = 1, device_ids::Union{Nothing,AbstractVector{<:Integer}} = nothing,
+                            factors::Union{Nothing,Bool,AbstractVector{<:Integer}} = nothing)
     psd_ptr = Int64[0]; psd_idx = Int64[]
     for s in con.sdpcone
         append!(psd_idx, s.vec_i); push!(psd_ptr, length(psd_idx))
@@ -207,7 +231,20 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
     sharded = n_shards > 1 || device_ids !== nothing
     devs = device_ids === nothing ? Int32[] : Int32.(device_ids)
     (device_ids === nothing || length(devs) == n_shards) || error("device_ids: one device per shard")
-    GC.@preserve A G aff psd_ptr psd_idx soc_ptr soc_idx primal dual_cone dual_eq dual_in slack_eq slack_in opt devs begin
+    want_factors = factors !== nothing && factors !== false
+    (want_factors && sharded) && error("factors: not available in a block-sharded solve")
+    nb = length(con.sdpcone)
+    sides = Int64[s.sq_side for s in con.sdpcone]
+    caps = !want_factors ? zeros(Int64, nb) : factors === true ? copy(sides) : min.(Int64.(factors), sides)
+    length(caps) == nb || error("factors: one cap per PSD cone")
+    fvec_ptr = Int64[0]; fval_ptr = Int64[0]
+    for k in 1:nb
+        push!(fvec_ptr, fvec_ptr[end] + sides[k] * caps[k]); push!(fval_ptr, fval_ptr[end] + caps[k])
+    end
+    fvectors = zeros(max(fvec_ptr[end], 1)); fvalues = zeros(max(fval_ptr[end], 1))
+    frank = zeros(Int64, max(nb, 1)); ffound = zeros(Int64, max(nb, 1)); fsource = zeros(Int32, max(nb, 1))
+    fresid = zeros(max(nb, 1)); fxnorm = zeros(max(nb, 1))
+    GC.@preserve A G aff psd_ptr psd_idx soc_ptr soc_idx primal dual_cone dual_eq dual_in slack_eq slack_in opt devs caps fvec_ptr fval_ptr fvectors fvalues frank ffound fsource fresid fxnorm begin
         prob = Problem(n, p, m, _csc(A), _csc(G), pointer(aff.b), pointer(aff.h), pointer(aff.c),
                        length(con.sdpcone), pointer(psd_ptr), pointer(psd_idx),
                        length(con.socone), pointer(soc_ptr), pointer(soc_idx),
@@ -224,6 +261,12 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
                   (Ref{Problem}, Ptr{UInt64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ref{CResult}, Ptr{Stats}),
                   prob, opt, Int32(n_shards), device_ids === nothing ? Ptr{Int32}(C_NULL) : pointer(devs),
                   C_NULL, C_NULL, C_NULL, res, C_NULL)                # default owners, no per-shard stats
+        elseif want_factors
+            fac = PsdFactors(sizeof(PsdFactors), nb, pointer(caps), pointer(fvec_ptr), pointer(fval_ptr),
+                             pointer(fvectors), pointer(fvalues), pointer(frank), pointer(ffound), pointer(fsource),
+                             pointer(fresid), pointer(fxnorm))
+            ccall((:proxsdp_hip_solve_factored, libproxsdp_hip), Cint,
+                  (Ref{Problem}, Ptr{UInt64}, Ref{CResult}, Ref{PsdFactors}), prob, opt, res, fac)
         else
             ccall((:proxsdp_hip_solve, libproxsdp_hip), Cint,
                   (Ref{Problem}, Ptr{UInt64}, Ref{CResult}), prob, opt, res)
@@ -234,11 +277,17 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
         end
     end
     status_string = String(UInt8[c for c in res.status_string if c != 0x00])
-    return ResultType(
+    result = ResultType(
         res.status, status_string, primal, dual_cone, dual_eq, dual_in, slack_eq, slack_in,
         res.primal_residual, res.dual_residual, res.objval, res.dual_objval, res.gap, res.time,
         res.iter, res.final_rank, res.primal_feasible_user_tol != 0,
         res.dual_feasible_user_tol != 0, res.certificate_found != 0, res.result_count)
+    want_factors || return result
+    out = [(fvalues[fval_ptr[k]+1:fval_ptr[k]+frank[k]],
+            reshape(fvectors[fvec_ptr[k]+1:fvec_ptr[k]+sides[k]*frank[k]], Int(sides[k]), Int(frank[k])),
+            (rank = frank[k], rank_found = ffound[k], source = fsource[k], resid = fresid[k], xnorm = fxnorm[k]))
+           for k in 1:nb]
+    return result, out
 end
 
 end # module

@@ -181,6 +181,17 @@ class ShardIO(C.Structure):
                  ("psd_ids", pi64), ("psd_ptr", pi64), ("psd_idx", pi64), ("soc_ids", pi64), ("soc_ptr", pi64), ("soc_idx", pi64), ("eig_resid", pf64)])
 
 
+class PsdFactors(C.Structure):
+    """proxsdp_psd_factors (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("n_psd", i64), ("cap", pi64), ("vec_ptr", pi64), ("val_ptr", pi64),
+                ("vectors", pf64), ("values", pf64), ("rank", pi64), ("rank_found", pi64), ("source", C.POINTER(i32)),
+                ("resid", pf64), ("xnorm", pf64)]
+
+
+FACTOR_NONE, FACTOR_RITZ, FACTOR_EIG = 0, 1, 2
+FACTOR_SOURCE_NAMES = {FACTOR_NONE: "NONE", FACTOR_RITZ: "RITZ", FACTOR_EIG: "EIG"}
+
+
 _lib = None
 
 
@@ -222,6 +233,10 @@ def lib():
     L.proxsdp_hip_solve.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Result)]
     L.proxsdp_hip_solve_ex.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Result),
                                        C.POINTER(State), C.POINTER(State)]
+    L.proxsdp_hip_solve_factored.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Result),
+                                             C.POINTER(PsdFactors)]
+    L.proxsdp_hip_factor_residual.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64]
+    L.proxsdp_hip_factor_residual_kernel.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64, i32, pf64]
     L.proxsdp_hip_psd_project.argtypes = [pf64, i64, i32, i32, C.POINTER(Options), pf64, pf64,
                                           C.POINTER(i32), pf64, pi64, C.POINTER(i32), C.POINTER(i32)]
     L.proxsdp_hip_eigsolve.argtypes = [pf64, i64, i32, C.POINTER(Options), pf64, i32, pf64, pf64,
@@ -444,8 +459,62 @@ def _state_dict(S, arr, n, Q, n_psd):
     return d
 
 
+def psd_sides(prob):
+    """side of every PSD cone of `prob`, in cone order"""
+    return [int(round((np.sqrt(8.0 * len(v) + 1.0) - 1.0) / 2.0)) for v in prob.psd]
+
+
+def _factors_struct(sides, factors):
+    """proxsdp_psd_factors for cones of the given sides, and the arrays behind it.  factors: True = room for every pair of
+    every cone (cap = side), or {cone number: cap} (cones not named: cap 0, nothing computed for them)."""
+    nb = len(sides)
+    if factors is True:
+        cap = np.array(sides, dtype=np.int64).reshape(nb)
+    else:
+        cap = np.zeros(nb, dtype=np.int64)
+        for k, c in dict(factors).items():
+            if not 0 <= int(k) < nb:
+                raise ValueError(f"factors: no PSD cone {k}")
+            if int(c) < 0:
+                raise ValueError("factors: negative cap")
+            cap[int(k)] = min(int(c), sides[int(k)])           # (a block has at most `side` pairs)
+    vec_ptr = np.zeros(nb + 1, dtype=np.int64)
+    val_ptr = np.zeros(nb + 1, dtype=np.int64)
+    for k in range(nb):
+        vec_ptr[k + 1] = vec_ptr[k] + sides[k] * cap[k]
+        val_ptr[k + 1] = val_ptr[k] + cap[k]
+    arr = dict(cap=cap, vec_ptr=vec_ptr, val_ptr=val_ptr,
+               vectors=np.full(max(int(vec_ptr[-1]), 1), np.nan), values=np.full(max(int(val_ptr[-1]), 1), np.nan),
+               rank=np.zeros(max(nb, 1), dtype=np.int64), rank_found=np.zeros(max(nb, 1), dtype=np.int64),
+               source=np.zeros(max(nb, 1), dtype=np.int32), resid=np.zeros(max(nb, 1)), xnorm=np.zeros(max(nb, 1)))
+    F = PsdFactors()
+    F.struct_size = C.sizeof(PsdFactors)
+    F.n_psd = nb
+    F.cap, F.vec_ptr, F.val_ptr = _p(cap, pi64), _p(vec_ptr, pi64), _p(val_ptr, pi64)
+    F.vectors, F.values = _p(arr["vectors"]), _p(arr["values"])
+    F.rank, F.rank_found = _p(arr["rank"], pi64), _p(arr["rank_found"], pi64)
+    F.source = arr["source"].ctypes.data_as(C.POINTER(i32))
+    F.resid, F.xnorm = _p(arr["resid"]), _p(arr["xnorm"])
+    return F, arr
+
+
+def _factors_list(sides, arr):
+    """[(values, vectors, info)] per PSD cone: values (rank,) descending, vectors (side, rank), info = dict(rank, rank_found,
+    source, source_name, resid, xnorm, cap)"""
+    out = []
+    for k, sd in enumerate(sides):
+        r = int(arr["rank"][k])
+        vals = arr["values"][arr["val_ptr"][k]:arr["val_ptr"][k] + r].copy()
+        vecs = arr["vectors"][arr["vec_ptr"][k]:arr["vec_ptr"][k] + sd * r].reshape(r, sd).T.copy()
+        src = int(arr["source"][k])
+        out.append((vals, vecs, dict(rank=r, rank_found=int(arr["rank_found"][k]), source=src,
+                                     source_name=FACTOR_SOURCE_NAMES.get(src, "?"), resid=float(arr["resid"][k]),
+                                     xnorm=float(arr["xnorm"][k]), cap=int(arr["cap"][k]))))
+    return out
+
+
 def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, coupling=None, index_base=0, nccl_comm=None,
-          resume=None, capture_iteration=None):
+          resume=None, capture_iteration=None, factors=False, primal=True):
     """proxsdp_hip_solve: replaces chambolle_pock(aff, con, options) (MOI_wrapper.jl:310).
     Returns the minimisation objective; sign/constant fix-up is the caller's
     (MOI_wrapper.jl:336-337), see optimizer.Optimizer.
@@ -458,8 +527,15 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
     the coupling rows itself on its own stream (proxsdp_problem.nccl_comm); `reduce` / reduce_vec are not used.
     resume: optional state dict (as returned in `.state`, or by oracle.export_state) -- the solve continues with iteration
     state['iteration'] + 1 (proxsdp_hip_solve_ex); capture_iteration: k >= 1 -- the state after iteration k comes back as
-    `.state` (None when the solve ended before k).  Vectors are in the solver's internal order and scaling."""
+    `.state` (None when the solve ended before k).  Vectors are in the solver's internal order and scaling.
+    factors: True or {cone number: cap} -- proxsdp_hip_solve_factored: the same solve, and `.psd_factors` = one
+    (values, vectors, info) per PSD cone with X_k ~ vectors diag(values) vectors' (values descending and > 0; info: rank,
+    rank_found, source / source_name, resid, xnorm, cap); True asks for every pair, a dict caps the columns per cone (cones
+    it does not name get nothing).  Not with resume / capture_iteration, and not for a shard.
+    primal = False: proxsdp_result.primal = NULL (`.primal` comes back None)."""
     L = lib()
+    if factors is not False and factors is not None and (resume is not None or capture_iteration is not None):
+        raise ValueError("factors cannot be combined with the state seam")
     o = options if options is not None else default_options()
     if trace_capacity:
         o.trace_capacity = int(trace_capacity)
@@ -509,9 +585,23 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
     R = Result()
     R.primal, R.dual_cone, R.dual_eq, R.dual_in, R.slack_eq, R.slack_in = [_p(a) for a in arrays]
     R.trace = _p(trace)
+    if not primal:
+        R.primal = None
+    if factors is not False and factors is not None:
+        sides = psd_sides(prob)
+        F, farr = _factors_struct(sides, factors)
+        _check(L.proxsdp_hip_solve_factored(C.byref(M.P), C.byref(o), C.byref(R), C.byref(F)))
+        arrays = [a[:k] for a, k in zip(arrays, (n, n, p, m, p, m))]
+        if not primal:
+            arrays[0] = None
+        out = SolveResult(R, n, p, m, arrays, trace)
+        out.psd_factors = _factors_list(sides, farr)
+        return out
     if resume is None and capture_iteration is None:
         _check(L.proxsdp_hip_solve(C.byref(M.P), C.byref(o), C.byref(R)))
         arrays = [a[:k] for a, k in zip(arrays, (n, n, p, m, p, m))]
+        if not primal:
+            arrays[0] = None
         return SolveResult(R, n, p, m, arrays, trace)
     Q, nb = p + m, int(M.P.n_psd)
     rs = cs = None
@@ -720,6 +810,24 @@ def reconstruct(Z, lam, n, repeat=0, mfma=-1):
     ms = f64(0.0)
     _check(L.proxsdp_hip_reconstruct_kernel(Zc.ctypes.data_as(pf64), _p(lam), n, r, mfma, _p(out), repeat, C.byref(ms)))
     return (out, ms.value) if repeat else out
+
+
+def factor_residual(packed, n, V, lam, repeat=0):
+    """(||X - V diag(lam) V'||_F^2, ||X||_F^2) of X = smat(packed), PLAIN entries (upper triangle column by column, no
+    sqrt(2)), by k_factor_residual.  V: (ldv, r) with ldv >= n -- rows n .. ldv-1 are padding the kernel must not read;
+    r = 0 is allowed.  repeat > 0: also the mean kernel time in ms."""
+    L = lib()
+    x = _f(packed)
+    lam = _f(lam)
+    r = len(lam)
+    Vc = np.asfortranarray(np.asarray(V, dtype=np.float64).reshape(-1, r) if r else np.zeros((n, 0)))
+    ldv = Vc.shape[0] if r else n
+    if len(x) != n * (n + 1) // 2 or (r and ldv < n):
+        raise ValueError("factor_residual: packed / V have the wrong shape")
+    r2, x2, ms = f64(0.0), f64(0.0), f64(0.0)
+    _check(L.proxsdp_hip_factor_residual_kernel(_p(x), n, Vc.ctypes.data_as(pf64) if r else None, ldv,
+                                                _p(lam) if r else None, r, C.byref(r2), C.byref(x2), int(repeat), C.byref(ms)))
+    return (r2.value, x2.value, ms.value) if repeat else (r2.value, x2.value)
 
 
 def full_eig_kernel(packed, n, sign=1, repeat=1):

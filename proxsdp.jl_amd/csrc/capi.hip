@@ -163,8 +163,9 @@ static proxsdp_options begin_solve(const proxsdp_options* opt, proxsdp_result* r
     return o;
 }
 
-int proxsdp_hip_solve_ex(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
-                         const proxsdp_state* resume, proxsdp_state* capture) {
+// the solve behind proxsdp_hip_solve_ex and proxsdp_hip_solve_factored (fac: validated by the caller, or NULL)
+static int solve_impl(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                      const proxsdp_state* resume, proxsdp_state* capture, proxsdp_psd_factors* fac) {
     bool comm_aborted = false;
     const int rc = guarded([&]() -> int {
         if (!prob || !res) throw std::invalid_argument("NULL problem or result");
@@ -172,6 +173,7 @@ int proxsdp_hip_solve_ex(const proxsdp_problem* prob, const proxsdp_options* opt
         proxsdp::Solver S(*prob, o, *res);
         S.resume_state = resume;
         S.capture_state = capture;
+        S.factors_out = fac;
         try {
             S.run();
         } catch (...) {
@@ -188,6 +190,49 @@ int proxsdp_hip_solve_ex(const proxsdp_problem* prob, const proxsdp_options* opt
         return PROXSDP_E_COMM_ABORTED;
     }
     return rc;
+}
+
+int proxsdp_hip_solve_ex(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                         const proxsdp_state* resume, proxsdp_state* capture) {
+    return solve_impl(prob, opt, res, resume, capture, nullptr);
+}
+
+// the solve with the factors of its PSD solution (Solver::extract_factors): every argument is checked here, on the host,
+// before a solver -- and with it the device -- exists
+int proxsdp_hip_solve_factored(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                               proxsdp_psd_factors* fac) {
+    const int rc = guarded([&]() -> int {
+        if (!prob || !res || !fac) throw std::invalid_argument("NULL problem, result or factors");
+        if (fac->struct_size != (int64_t)sizeof(proxsdp_psd_factors))
+            throw std::invalid_argument("proxsdp_psd_factors.struct_size mismatch");
+        if (prob->n_psd < 0 || fac->n_psd != prob->n_psd) throw std::invalid_argument("proxsdp_psd_factors.n_psd != problem.n_psd");
+        if (prob->n_psd > 0 && !prob->psd_ptr) throw std::invalid_argument("psd_ptr/psd_idx is NULL");
+        if (!fac->cap || !fac->vec_ptr || !fac->val_ptr || !fac->rank || !fac->rank_found || !fac->source || !fac->resid ||
+            !fac->xnorm)
+            throw std::invalid_argument("proxsdp_psd_factors: NULL array");
+        bool any = false;
+        for (int64_t k = 0; k < fac->n_psd; ++k) {
+            const int64_t len = prob->psd_ptr[k + 1] - prob->psd_ptr[k];
+            if (len <= 0) throw std::invalid_argument("empty PSD cone");
+            int64_t side = (int64_t)((std::sqrt(8.0 * (double)len + 1.0) - 1.0) / 2.0);
+            while (side * (side + 1) / 2 < len) ++side;
+            while (side * (side + 1) / 2 > len) --side;
+            if (side * (side + 1) / 2 != len) throw std::invalid_argument("PSD cone length is not triangular");
+            const int64_t cap = fac->cap[k];
+            if (cap < 0) throw std::invalid_argument("proxsdp_psd_factors.cap is negative");
+            any = any || cap > 0;
+            const int64_t want = std::min(cap, side);           // (a block has at most `side` pairs)
+            if (fac->vec_ptr[k] < 0 || fac->val_ptr[k] < 0 || fac->vec_ptr[k + 1] - fac->vec_ptr[k] < side * want ||
+                fac->val_ptr[k + 1] - fac->val_ptr[k] < want)
+                throw std::invalid_argument("proxsdp_psd_factors: vec_ptr / val_ptr span too small for cap");
+        }
+        if (any && (!fac->vectors || !fac->values)) throw std::invalid_argument("proxsdp_psd_factors: NULL vectors / values");
+        if (prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0)
+            throw std::domain_error("proxsdp_hip_solve_factored does not serve a shard of a block-sharded solve");
+        return 0;
+    });
+    if (rc != 0) return rc;
+    return solve_impl(prob, opt, res, nullptr, nullptr, fac);
 }
 
 // ---- block-sharded solve from one call: in-process shards (shard_split.hpp, shard_group.hpp)
@@ -625,6 +670,51 @@ int proxsdp_hip_reconstruct_kernel(const double* Z, const double* lambda, int64_
             PX_HIP(hipEventElapsedTime(&t, a, b));
             *ms = (double)t / repeat;
             (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+        }
+        return 0;
+    });
+}
+
+int proxsdp_hip_factor_residual(const double* packed, int64_t n, const double* V, int64_t ldv,
+                                const double* lam, int32_t r, double* resid2, double* xnorm2) {
+    return proxsdp_hip_factor_residual_kernel(packed, n, V, ldv, lam, r, resid2, xnorm2, 0, nullptr);
+}
+
+int proxsdp_hip_factor_residual_kernel(const double* packed, int64_t n, const double* V, int64_t ldv,
+                                       const double* lam, int32_t r, double* resid2, double* xnorm2,
+                                       int32_t repeat, double* ms) {
+    return guarded([&]() -> int {
+        if (!packed || !resid2 || !xnorm2 || (r > 0 && (!V || !lam))) throw std::invalid_argument("NULL buffer");
+        if (r < 0) throw std::invalid_argument("r < 0");
+        if (n < 1 || n > 46340) throw std::invalid_argument("n out of range");
+        if (r > 0 && (ldv < n || ldv >= (int64_t)1 << 31)) throw std::invalid_argument("ldv out of range");
+        Engine E(nullptr, n, 2);
+        proxsdp::Solver& S = E.S;
+        const int64_t N = n * (n + 1) / 2;
+        const size_t vcount = r > 0 ? (size_t)ldv * (r - 1) + (size_t)n : 0;   // the last column ends at its row n - 1
+        proxsdp::DevBuf<double> x(N), Vd(std::max<size_t>(1, vcount)), ld(std::max(1, r));
+        x.upload(packed, N, S.stream);
+        Vd.upload(V, vcount, S.stream);
+        ld.upload(lam, r, S.stream);
+        S.factor_residual(x.p, (int)n, Vd.p, (int)ldv, ld.p, r, *resid2, *xnorm2);
+        if (repeat > 0 && ms) {
+            const int nt = proxsdp::ceil_div((int)n, proxsdp::dev::TILE);
+            const int grid = 8 * proxsdp::ceil_div(nt * (nt + 1) / 2, 8);
+            hipEvent_t a, b;
+            PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
+            PX_HIP(hipEventRecord(a, S.stream));
+            for (int i = 0; i < repeat; ++i)
+                hipLaunchKernelGGL(proxsdp::dev::k_factor_residual, dim3(grid), dim3(proxsdp::dev::TPB), 0, S.stream,
+                                   (const double*)x.p, (int)n, (const double*)Vd.p, (int)ldv, (const double*)ld.p, (int)r,
+                                   S.fac_part.p);
+            PX_HIP(hipEventRecord(b, S.stream));
+            PX_HIP(hipEventSynchronize(b));
+            float t = 0.f;
+            PX_HIP(hipEventElapsedTime(&t, a, b));
+            *ms = (double)t / repeat;
+            (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+            // what comes back is the LAST launch's: a kernel that wrote to the block would show here
+            S.factor_residual(x.p, (int)n, Vd.p, (int)ldv, ld.p, r, *resid2, *xnorm2);
         }
         return 0;
     });

@@ -1419,6 +1419,109 @@ k_reconstruct_mfma(const double* __restrict__ Z, int ldz, const double* __restri
 }
 
 // ---------------------------------------------------------------------------
+// Residual of a set of factors against a packed block, for the factors a solve hands back
+// (proxsdp_hip_solve_factored):
+//   resid^2 = sum_ij (x_ij - sum_k lambda_k V[i,k] V[j,k])^2,   xnorm^2 = sum_ij x_ij^2
+// over the FULL symmetric matrix (an off-diagonal entry of the packed triangle counts twice).  xp holds PLAIN entries
+// (no sqrt(2): the exit path has already taken it out) and is only read.  The tiling, the staging and the MFMA loop are
+// k_reconstruct_mfma's, operand for operand (same LDS layout and reads, see there); instead of storing its 16 entries a
+// lane loads the packed entries -- requested before the MFMA loop, like the fused residual's x_old, so that the 8 N
+// bytes stream in under it -- and squares the differences.  One partial pair per TILE (part[2 tile], part[2 tile + 1]),
+// summed by the caller in tile order: the result does not depend on which workgroup ran when.  r = 0 is allowed
+// (resid = xnorm; lam and V are then never dereferenced); rows >= n of a padded V (ldv > n) are never read.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(TPB)
+k_factor_residual(const double* __restrict__ xp, int n, const double* __restrict__ V, int ldv,
+                  const double* __restrict__ lam, int r, double* __restrict__ part) {
+    __shared__ double sA[2][MF_KC][MF_LD];      // lambda_k V[J*64 + row, k]
+    __shared__ double sB[2][MF_KC][MF_LD];      // V[I*64 + row, k]
+    __shared__ double s_red[NWAVE];
+    const int nt_ = (n + TILE - 1) / TILE;
+    const int tile = xcd_tile(blockIdx.x, nt_ * (nt_ + 1) / 2);
+    if (tile >= nt_ * (nt_ + 1) / 2) return;
+    int I, J;
+    tile_coords(tile, I, J);
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int gja = J * TILE + lane, gib = I * TILE + lane;
+    const bool ja_ok = gja < n, ib_ok = gib < n;
+    const double* __restrict__ zA = V + (ja_ok ? gja : 0);
+    const double* __restrict__ zB = V + (ib_ok ? gib : 0);
+    constexpr int MF_U = MF_KC / NWAVE;
+    double pa[MF_U], pb[MF_U];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int u = 0; u < MF_U; ++u) {
+            const int k = k0 + w + 4 * u;
+            const bool kok = k < r;
+            const long long ko = (long long)(kok ? k : 0) * ldv;
+            pa[u] = (kok && ja_ok) ? zA[ko] * lam[k] : 0.0;
+            pb[u] = (kok && ib_ok) ? zB[ko] : 0.0;
+        }
+    };
+    auto stash = [&](int buf) {
+#pragma unroll
+        for (int u = 0; u < MF_U; ++u) { sA[buf][w + 4 * u][lane] = pa[u]; sB[buf][w + 4 * u][lane] = pb[u]; }
+    };
+    v4f64 acc[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[b] = (v4f64){0.0, 0.0, 0.0, 0.0};
+    // this lane's 16 packed entries (clamped to a valid entry where the tile hangs over the edge or the diagonal)
+    double xv[16];
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int gjc = min(J * TILE + w * 16 + l4 + 4 * reg, n - 1);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int gic = min(I * TILE + b * 16 + l15, gjc);
+            xv[reg * 4 + b] = xp[(long long)gjc * (gjc + 1) / 2 + gic];
+        }
+    }
+    fetch(0);
+    stash(0);
+    __syncthreads();
+    int cur = 0;
+    for (int k0 = 0; k0 < r; k0 += MF_KC) {
+        const bool more = k0 + MF_KC < r;
+        if (more) fetch(k0 + MF_KC);
+#pragma unroll
+        for (int q = 0; q < MF_KC / 4; ++q) {
+            const double a = sA[cur][4 * q + l4][w * 16 + l15];
+            double bv[4];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) bv[b] = sB[cur][4 * q + l4][b * 16 + l15];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv[b], acc[b], 0, 0, 0);
+        }
+        if (more) {
+            stash(cur ^ 1);
+            __syncthreads();
+            cur ^= 1;
+        }
+    }
+    double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int gj = J * TILE + w * 16 + l4 + 4 * reg;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int gi = I * TILE + b * 16 + l15;
+            if (gj < n && gi <= gj) {
+                const double wt = (gi == gj) ? 1.0 : 2.0;
+                const double x = xv[reg * 4 + b];
+                const double d = x - acc[b][reg];
+                s0 += wt * (d * d);
+                s1 += wt * (x * x);
+            }
+        }
+    }
+    const double r0 = block_sum(s0, s_red);
+    const double r1 = block_sum(s1, s_red);
+    if (threadIdx.x == 0) { part[2 * tile] = r0; part[2 * tile + 1] = r1; }
+}
+
+// ---------------------------------------------------------------------------
 // Basis rotation out[:, c] = sum_j V[:, j] U[j, c] as fp64 MFMA tiles (round 3).  At K = 127 the scalar k_lz_rotate
 // takes 55-60 us for 63-100 columns (4-5 % of the rank-63 iteration: 1.5 rotations per iteration); it is a skinny
 // GEMM -- 64 rows x ncols x K per workgroup -- so: the workgroup's V tile (K x 64, zero padded to a multiple of 4) goes

@@ -136,6 +136,7 @@ inline void Solver::project_block(int idx, const double* xin, double* xout, bool
     const double* xp = xin + P.blocks[idx].off;
     double* xo = xout + P.blocks[idx].off;
     current_rank[idx] = 0;
+    W.ritz_ok = false;                        // the block is about to be rewritten
     const bool krylov = lanczos_done || krylov_branch(idx);
     // operator-form mat-vec: legal when this block's x_prev is known in factored form (or is
     // zero off the support) and the update is the sparse support update of this iteration
@@ -218,6 +219,8 @@ inline void Solver::project_block(int idx, const double* xin, double* xout, bool
         std::swap(W.lam.p, W.Flam.p);            // the eigenvalues just uploaded become the next projection's factors
         std::swap(W.lam.n, W.Flam.n);
         W.have_factors = true; W.x_prev_sparse = false;
+    } else {                                  // no F to swap into: the pairs stay in Z / vals (extract_factors)
+        W.ritz_first = first; W.ritz_r = npos; W.ritz_ok = true;
     }
     if (W.sign_check_pending) verify_sign_engine(idx, xo);
 }
@@ -356,7 +359,7 @@ inline bool Solver::full_eig_by_lanczos(int idx, const double* xp, double* xo, b
     auto use_reference_result = [&]() {
         W.fel_disabled = true;
         W.lst.full_eigs_lanczos_mismatches++;
-        W.have_factors = false; W.x_prev_sparse = false; W.use_fop = false;
+        W.have_factors = false; W.x_prev_sparse = false; W.use_fop = false; W.ritz_ok = false;
         if (xp != xo) { full_eig_project(idx, xp, xo, fuse); return; }   // input intact: the ordinary dense call
         // in-place call: the input is gone, the scratch buffer holds the dense engine's projection of it
         PX_HIP(hipMemcpyAsync(xo, W.sg_out.p, (size_t)W.N * sizeof(double), hipMemcpyDeviceToDevice, stream));
@@ -413,6 +416,8 @@ inline bool Solver::full_eig_by_lanczos(int idx, const double* xp, double* xo, b
             std::swap(W.lam.p, W.Flam.p);
             std::swap(W.lam.n, W.Flam.n);
             W.have_factors = true; W.x_prev_sparse = false;
+        } else {
+            W.ritz_first = 0; W.ritz_r = npos; W.ritz_ok = true;
         }
         if (verify) {
             if (W.sg_cmp.n < 2) W.sg_cmp.alloc(2);
@@ -984,6 +989,8 @@ inline void Solver::cache_solution(const std::vector<double>& cvec) {
         reduce_vec_host(part_);
         for (size_t k = 0; k < coup_rows.size(); ++k) slack[coup_rows[k]] = part_[k];
     }
+    // the factors of this snapshot's PSD blocks, before the lambda_min Lanczos below reuses the blocks' workspaces
+    if (factors_out) extract_factors(x);
     std::vector<double> deq, din, dcone;
     double dfeas = dual_feas_host(y, cvec, &deq, &din, &dcone);
     harvest_small_ranks();
@@ -1025,8 +1032,79 @@ inline void Solver::cache_solution(const std::vector<double>& cvec) {
     // search continues from here, the operator-form factors F diag(Flam) F' still describe the
     // UNscaled iterate: drop them so the next projection reads the (rescaled) packed buffer, as the
     // fused residual and the dense / full-eig paths do.
-    for (EigWork& W : eig) { W.have_factors = false; W.x_prev_sparse = false; }
+    for (EigWork& W : eig) { W.have_factors = false; W.x_prev_sparse = false; W.ritz_ok = false; }
     st.exit_time += now_s() - t0;
+}
+
+// The low-rank factors of the PSD blocks of the snapshot cache_solution is taking (proxsdp_hip_solve_factored): for cone k
+// the positive eigenpairs of the block exactly as it sits in xbuf[xc] -- plain entries in the caller's scale, what is
+// downloaded into res->primal (x is that download).  Where the block still IS the reconstruction of the last projection's
+// Ritz pairs (the operator form's factors F / Flam, or the pairs a converged Krylov projection left in Z / vals) those pairs
+// are handed out: a gather and a download, no eigensolve.  Any other block of side >= 2 -- full_eig! engines, equilibrated
+// solves (the rescale by D is not a congruence the pairs survive), a snapshot taken before any projection -- gets one
+// dsyevd of the block, pairs with lambda > 0 kept.  Either way the cap[k] largest pairs go out, descending, and
+// k_factor_residual measures them against the block: resid reports what the pairs miss, truncation included.
+inline void Solver::extract_factors(const std::vector<double>& x) {
+    proxsdp_psd_factors& F = *factors_out;
+    for (size_t idx = 0; idx < P.blocks.size(); ++idx) {
+        const BlockInfo& B = P.blocks[idx];
+        const int64_t cap = F.cap[idx];
+        double* vout = F.vectors + F.vec_ptr[idx];
+        double* lout = F.values + F.val_ptr[idx];
+        F.rank[idx] = 0; F.rank_found[idx] = 0; F.source[idx] = PROXSDP_FACTOR_NONE;
+        F.resid[idx] = 0.0; F.xnorm[idx] = 0.0;
+        if (cap <= 0) continue;                               // nothing wanted for this cone: nothing computed
+        if (B.n == 1) {
+            const double xv = x[B.off];
+            F.xnorm[idx] = std::fabs(xv);
+            if (xv > 0.0) { vout[0] = 1.0; lout[0] = xv; F.rank[idx] = 1; F.rank_found[idx] = 1; }
+            else F.resid[idx] = std::fabs(xv);
+            continue;
+        }
+        EigWork& W = eig[idx];
+        const int n = B.n;
+        const double* xp = xbuf[xc].p + B.off;
+        const double* Vsrc = nullptr;
+        int ldv = 0;
+        std::vector<double> lam;                              // candidate pairs: lam[c] belongs to column c of Vsrc
+        if (!P.equilibrated && (W.have_factors || W.ritz_ok)) {
+            F.source[idx] = PROXSDP_FACTOR_RITZ;
+            ldv = W.npad;
+            if (W.have_factors) {
+                Vsrc = W.F.p + (size_t)W.F_first * W.npad;
+                lam.resize(W.F_r);
+                if (W.F_r > 0) { W.Flam.download(lam.data(), W.F_r, stream); PX_HIP(hipStreamSynchronize(stream)); }
+            } else {
+                Vsrc = W.Z.p + (size_t)W.ritz_first * W.npad;
+                lam.assign(W.vals.begin() + W.ritz_first, W.vals.begin() + W.ritz_first + W.ritz_r);
+            }
+        } else {
+            F.source[idx] = PROXSDP_FACTOR_EIG;
+            full_eig_values(W, xp, 1.0, true, lam);           // (plain entries: no off-diagonal factor)
+            Vsrc = W.A.p; ldv = n;
+        }
+        // the positive pairs, largest first (KrylovKit's pairs come descending, ARPACK's and dsyevd's ascending)
+        std::vector<int> order;
+        for (int c = 0; c < (int)lam.size(); ++c) if (lam[c] > 0.0) order.push_back(c);
+        std::stable_sort(order.begin(), order.end(), [&lam](int a, int b) { return lam[a] > lam[b]; });
+        const int found = (int)order.size();
+        const int k = (int)std::min<int64_t>(cap, found);
+        F.rank_found[idx] = found; F.rank[idx] = k;
+        if (k > 0) {
+            if (fac_V.n < (size_t)n * k) fac_V.alloc((size_t)n * k);
+            if (fac_lam.n < (size_t)k) fac_lam.alloc(k);
+            for (int j = 0; j < k; ++j) {
+                lout[j] = lam[order[j]];
+                PX_HIP(hipMemcpyAsync(fac_V.p + (size_t)j * n, Vsrc + (size_t)order[j] * ldv, (size_t)n * sizeof(double),
+                                      hipMemcpyDeviceToDevice, stream));
+            }
+            fac_lam.upload(lout, k, stream);
+            fac_V.download(vout, (size_t)n * k, stream);
+        }
+        double r2 = 0.0, x2 = 0.0;
+        factor_residual(xp, n, fac_V.p, n, fac_lam.p, k, r2, x2);
+        F.resid[idx] = std::sqrt(r2); F.xnorm[idx] = std::sqrt(x2);
+    }
 }
 
 // ---- dense constraint matrix (proxsdp_problem.M_dense; kernels.hip.hpp "Dense constraint matrix")

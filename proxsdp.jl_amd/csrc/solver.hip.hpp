@@ -248,6 +248,12 @@ struct EigWork {
     bool have_factors = false;                     // x_prev of this block is F[:, F_first .. +F_r) diag(Flam) F'
     bool x_prev_sparse = true;                     // x_prev is zero off the support (initial iterate)
     bool use_fop = false;                          // the projection in progress uses the operator form
+    // a block without the operator form's structures keeps no F: there the last converged Krylov projection's pairs stay
+    // where the run left them -- Z[:, ritz_first .. +ritz_r) and vals[ritz_first ..) -- and ritz_ok says that x_prev of this
+    // block is still their reconstruction: set at the end of that projection, dropped by whatever writes Z / vals (lanczos,
+    // lanczos_batch) or the block (project_block, the exit path's rescale).  Read by extract_factors only.
+    bool ritz_ok = false;
+    int ritz_first = 0, ritz_r = 0;
     int last_npos = -1;                            // positive eigenvalues found by the last full_eig! of this block
     // early read-back of the recurrence coefficients (host_eig_merge): side stream + events + pinned mirror
     hipStream_t side = nullptr;
@@ -433,6 +439,13 @@ public:
     void launch_symv_finish(EigWork& W, const double* xp, int kclose, double tol, bool use_carry);
     void launch_reconstruct(EigWork& W, const double* Z, int ldz, const double* lam, int r, double* xp_out,
                             const double* xp_old = nullptr, int blk = -1);
+    // factors of the PSD solution (proxsdp_hip_solve_factored): where the caller wants them (null: a plain solve, no new
+    // code runs), the residual kernel's launch, and the extraction at the snapshot that fills `res`
+    proxsdp_psd_factors* factors_out = nullptr;
+    DevBuf<double> fac_V, fac_lam, fac_part;
+    void factor_residual(const double* xp, int n, const double* V, int ldv, const double* lam, int r,
+                         double& resid2, double& xnorm2);
+    void extract_factors(const std::vector<double>& x);
     void rotate(EigWork& W, int K, const std::vector<double>& U, int ldu, int ncols, double* out, int copy_src, int copy_dst,
                 const double* extra, int nextra);
 
@@ -990,6 +1003,23 @@ inline void Solver::launch_reconstruct(EigWork& W, const double* Z, int ldz, con
                            (double*)nullptr, 0);
 }
 
+// ||X - V diag(lam) V'||_F^2 and ||X||_F^2 of a packed block with plain entries (k_factor_residual): device pointers in, the
+// tiles' partial pairs summed on the host in tile order.  Synchronises the stream.
+inline void Solver::factor_residual(const double* xp, int n, const double* V, int ldv, const double* lam, int r,
+                                    double& resid2, double& xnorm2) {
+    const int nt = ceil_div(n, dev::TILE);
+    const int tiles = nt * (nt + 1) / 2;
+    if (fac_part.n < (size_t)2 * tiles) fac_part.alloc((size_t)2 * tiles);
+    hipLaunchKernelGGL(dev::k_factor_residual, dim3(8 * ceil_div(tiles, 8)), dim3(dev::TPB), 0, stream,
+                       xp, n, V, ldv, lam, r, fac_part.p);
+    PX_HIP(hipGetLastError());
+    std::vector<double> h((size_t)2 * tiles);
+    fac_part.download(h.data(), h.size(), stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    resid2 = 0.0; xnorm2 = 0.0;
+    for (int t = 0; t < tiles; ++t) { resid2 += h[2 * t]; xnorm2 += h[2 * t + 1]; }
+}
+
 inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int ldu, int ncols,
                            double* out, int copy_src, int copy_dst, const double* extra, int nextra) {
     // U: host column-major (ldu x >=ncols); upload the K x ncols part compactly from a
@@ -1515,6 +1545,7 @@ inline bool Solver::lanczos_certificate(EigWork& W, const double* xp, int npos, 
 }
 
 inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive_part) {
+    W.ritz_ok = false;                                   // Z / vals are about to be rewritten
     if (opt.krylovkit_eager && opt.eigsolver != 1 && !positive_part) { lanczos_eager(W, xp, nev); return; }
     LzRun& R = W.lzrun;
     if (!lz_init(W, R, nev, positive_part)) return;
@@ -1704,6 +1735,7 @@ inline void Solver::lanczos_batch(const std::vector<int>& blocks, const double* 
     for (int q = 0; q < nb; ++q) {
         EigWork& W = eig[blocks[q]];
         W.use_fop = false;
+        W.ritz_ok = false;
         W.batch_slot = q;
         live[q] = ran[q] = lz_init(W, Rq(q), nevs[q], false) ? 1 : 0;
         if (Rq(q).krylovdim > 63) throw std::invalid_argument("lanczos_batch: krylovdim > 63");

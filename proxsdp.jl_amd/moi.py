@@ -352,6 +352,14 @@ class Model:
         v = ci.flip * slack[list(ci.rows)] + ci.shift
         return float(v[0]) if ci.scalar else v
 
+    def constraint_primal_factor(self, ci):
+        """(values, vectors, info) of a PSD constraint's cone: its matrix ~ vectors diag(values) vectors', values descending
+        and > 0, row i of `vectors` = row i of the matrix (optimize(factors=True) or factors={cone number: cap}, cone number
+        = ci.value - 1).  The reference has no such attribute: its caller runs `eigen` on constraint_primal."""
+        if ci.kind != "psd":
+            raise TypeError("constraint_primal_factor: not a PositiveSemidefiniteConeTriangle constraint")
+        return self.optimizer.constraint_primal_psd_factor(ci.value - 1)
+
     def constraint_dual(self, ci):
         sol = self.optimizer.sol
         if ci.kind == "psd":

@@ -66,8 +66,10 @@ class Optimizer:
     # -- _optimize!
     def optimize(self, problem, eig_resid=None, trace_capacity=0, reduce=None, coupling=None, index_base=0,
                  nccl_comm=None, resume=None, capture_iteration=None, shards=None, device_ids=None, owners=None,
-                 soc_owners=None, free_owners=None):
-        """shards=k: the block-sharded solve from one call (binding.solve_sharded_inprocess) -- the library splits the model
+                 soc_owners=None, free_owners=None, factors=False):
+        """factors=True | {cone: cap}: the low-rank factors of the PSD solution come back with the result
+        (binding.solve: proxsdp_hip_solve_factored; `sol.psd_factors`, constraint_primal_psd_factor); not with shards=k.
+        shards=k: the block-sharded solve from one call (binding.solve_sharded_inprocess) -- the library splits the model
         into k shards and runs them as host threads of this process, shard s on device_ids[s] (default: all on
         options.device_id); the result is the whole model's, the per-shard stats are kept in `self.shard_stats`."""
         self.empty()
@@ -76,13 +78,15 @@ class Optimizer:
         if shards is not None:
             if reduce is not None or coupling is not None or nccl_comm or resume is not None or capture_iteration is not None:
                 raise ValueError("shards=...: the model must be whole (no reduce / coupling / nccl_comm) and there is no state seam")
+            if factors is not False and factors is not None:
+                raise ValueError("shards=...: the block-sharded solve does not return factors")
             sol, self.shard_stats = binding.solve_sharded_inprocess(
                 problem, shards, device_ids=device_ids, owners=owners, soc_owners=soc_owners, free_owners=free_owners,
                 options=self.options, trace_capacity=trace_capacity, eig_resid=eig_resid, index_base=index_base)
         else:
             sol = binding.solve(problem, self.options, eig_resid=eig_resid, trace_capacity=trace_capacity,
                                 reduce=reduce, coupling=coupling, index_base=index_base, nccl_comm=nccl_comm,
-                                resume=resume, capture_iteration=capture_iteration)
+                                resume=resume, capture_iteration=capture_iteration, factors=factors)
         sign = -1.0 if problem.max_sense else 1.0          # :336-337
         sol.objval = sign * sol.objval + problem.objective_constant
         sol.dual_objval = sign * sol.dual_objval + problem.objective_constant
@@ -132,6 +136,13 @@ class Optimizer:
 
     def constraint_primal_psd(self, k):
         return self.sol.primal[self.problem.psd[k]]
+
+    def constraint_primal_psd_factor(self, k):
+        """(values, vectors, info) of PSD cone k: X_k ~ vectors diag(values) vectors' (optimize(..., factors=...))"""
+        f = getattr(self.sol, "psd_factors", None)
+        if f is None:
+            raise RuntimeError("no factors: call optimize(..., factors=True) or factors={cone: cap}")
+        return f[k]
 
     def constraint_dual_psd(self, k):
         return self.sol.dual_cone[self.problem.psd[k]]
