@@ -60,7 +60,9 @@ extern "C" {
  * struct changed -- as for proxsdp_hip_dense_scaling before, the version stays;
  * later: proxsdp_hip_solve_factored (the low-rank factors of the PSD solution beside the result) with the new struct
  * proxsdp_psd_factors and the test entries proxsdp_hip_factor_residual / _kernel: functions and one new struct, no existing
- * struct changed: the version stays */
+ * struct changed: the version stays;
+ * later: proxsdp_hip_solve_from (warm start from a previous solution's primal / duals / factors) with the new struct
+ * proxsdp_start and the test entry proxsdp_hip_start_point: functions and one new struct, the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -649,6 +651,57 @@ typedef struct proxsdp_psd_factors {
 } proxsdp_psd_factors;
 int  proxsdp_hip_solve_factored(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
                                 proxsdp_psd_factors* fac);
+
+/* ------------------------------------------- warm start: the solve, entered from a point the caller gives
+ * Every other entry starts at x = 0 (or tau c, advanced_initialization), y = 0, as the reference does (its warm start is a
+ * stub: MOI_wrapper.jl:302).  This one enters proxsdp_hip_solve's loop at iteration 1 from the caller's point, given in the
+ * units a result comes back in, so a previous result -- and the factors proxsdp_hip_solve_factored handed out -- can be fed
+ * straight back:
+ *   internal x  = primal gathered into the solver's order, off-diagonal PSD entries x sqrt(2), divided by D in an equilibrated
+ *                 solve; internal y = [dual_eq; dual_in] divided by E: the inverse of what fills a result (cache_solution,
+ *                 pdhg.jl:745-787), entry by entry on the device (k_start_gather)
+ *   rank[k] >= 0  cone k starts at V diag(values) V', built by the solver's own reconstruction kernel straight into the
+ *                 iterate (no packed triangle crosses the host); the entries of `primal` for that cone are ignored;
+ *                 rank[k] = 0 is a zero block; rank[k] = -1: no factors for this cone (its entries come from `primal`)
+ *   primal NULL   every variable outside a factored cone keeps its cold value (tau c under advanced_initialization, else 0)
+ *   M x and M'y of the point come from the solver's own product launches; x_old, y_old, (M x)_old, (M'y)_old equal the
+ *   current vectors; history, rank_update, update_cont, ada_count, current_rank, min_eig and theta start as in a cold solve.
+ *   The point is NOT projected: the first iteration's primal step does that.
+ *   target rank of cone k: target_rank[k] > 0 wins (capped at the side); otherwise, with factors for the cone,
+ *                 min(side, max(initial_target_rank, rank[k] + 1)) -- the projection then sees the first non-positive
+ *                 eigenvalue and the rank test passes at once; otherwise initial_target_rank.  A start pays only with the
+ *                 right target rank: at the cold default of 2 the first projection truncates the point.
+ *   primal_step, beta: 0 = the cold values (1 / norm(M), initial_beta); dual_step = primal_step as in a cold solve.
+ * A start that gives no point at all (primal, dual_eq, dual_in NULL and no cone with rank >= 0) leaves the cold vectors as
+ * they are (x_old = 0): with target_rank, primal_step and beta at 0 as well that is proxsdp_hip_solve bit for bit, as is
+ * start == NULL.  fac != NULL additionally returns the factors as proxsdp_hip_solve_factored does, so solves chain.
+ * PROXSDP_E_INVALID before any device call: a wrong struct_size; n_psd neither 0 nor prob->n_psd; a NULL rank / vec_ptr /
+ * val_ptr with n_psd != 0; rank[k] < -1 or > side_k; a vec_ptr / val_ptr span smaller than side_k rank[k] / rank[k]; NULL
+ * vectors / values while some rank[k] > 0; a non-finite entry anywhere; a value <= 0; a negative target_rank, primal_step or
+ * beta; (fac: as proxsdp_hip_solve_factored).  PROXSDP_E_UNSUPP: prob is a shard (reduce_fn, reduce_vec_fn, nccl_comm,
+ * n_coupling != 0).  There is no sharded variant and no combination with the state seam. */
+typedef struct proxsdp_start {
+    int64_t struct_size;       /* = sizeof(proxsdp_start) */
+    const double* primal;      /* n, caller's variable order and scale (what res->primal holds), or NULL */
+    const double* dual_eq;     /* p, as res->dual_eq, or NULL (= 0) */
+    const double* dual_in;     /* m, as res->dual_in, or NULL (= 0) */
+    int64_t n_psd;             /* 0 = no factors given; otherwise must equal prob->n_psd */
+    const int64_t* rank;       /* n_psd: columns given for cone k; -1 = no factors for this cone */
+    const int64_t* vec_ptr;    /* n_psd+1 offsets into vectors, as in proxsdp_psd_factors */
+    const int64_t* val_ptr;    /* n_psd+1 offsets into values */
+    const double* vectors;     /* cone k: side_k x rank[k], column-major, ld = side_k */
+    const double* values;      /* rank[k] values, all finite and > 0 (any order; V need not be orthonormal) */
+    const int64_t* target_rank;/* n_psd or NULL; entry 0 = derive (above) */
+    double primal_step, beta;  /* 0 = the cold values */
+} proxsdp_start;
+int  proxsdp_hip_solve_from(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                            const proxsdp_start* start, proxsdp_psd_factors* fac /* may be NULL */);
+/* test entry: the "Init" section and the start path of proxsdp_hip_solve_from, nothing more.  Writes the internal x, Mty (n),
+ * y, Mx (Q), target_rank (n_psd), scal[0..5] and iteration = 0 into the caller-allocated `out` (struct_size, n, Q, n_psd must
+ * match; current_rank, min_eig, hist and hist_len are not touched).  Unlike the state seam it is served with equilibration
+ * and with a dense A.  start may be NULL (the cold point). */
+int  proxsdp_hip_start_point(const proxsdp_problem* prob, const proxsdp_options* opt, const proxsdp_start* start,
+                             proxsdp_state* out);
 
 /* ------------------------------------------- RCCL communicator helpers (block-sharded solves)
  * The library loads librccl at run time (dlopen; it does not link it).  One rank calls _unique_id and

@@ -170,6 +170,22 @@ struct PsdFactors                # proxsdp_psd_factors
 end
 const FACTOR_NONE = Int32(0); const FACTOR_RITZ = Int32(1); const FACTOR_EIG = Int32(2)   # PROXSDP_FACTOR_*
 
+struct Start                     # proxsdp_start
+    struct_size::Int64
+    primal::Ptr{Float64}
+    dual_eq::Ptr{Float64}
+    dual_in::Ptr{Float64}
+    n_psd::Int64
+    rank::Ptr{Int64}
+    vec_ptr::Ptr{Int64}
+    val_ptr::Ptr{Int64}
+    vectors::Ptr{Float64}
+    values::Ptr{Float64}
+    target_rank::Ptr{Int64}
+    primal_step::Float64
+    beta::Float64
+end
+
 # proxsdp_options is filled by name, exactly like MOI.RawOptimizerAttribute does for the
 # reference (src/MOI_wrapper.jl:84-93): an opaque, suitably large and aligned buffer plus
 # proxsdp_hip_default_options / proxsdp_hip_set_option keeps this file independent of the C
@@ -208,12 +224,19 @@ result in the caller's order.  Cones are dealt out round-robin (PSD cones, then 
 `proxsdp_hip_solve_factored`; the return value is then `(result, factors)` with `factors[k] = (values, vectors, info)`,
 `X_k ≈ vectors * Diagonal(values) * vectors'`, values descending and positive, `info = (rank, rank_found, source, resid,
 xnorm)` -- what a caller of the reference computes with `eigen` on the returned block.  Not with `n_shards > 1`.
+`start = (primal = ..., dual_eq = ..., dual_in = ..., factors = ..., target_rank = ..., primal_step = ..., beta = ...)`
+(a NamedTuple, every field optional): a warm start through `proxsdp_hip_solve_from`.  `primal`, `dual_eq`, `dual_in` are
+what a previous `Result` holds; `factors[k] = (values, vectors)` or `nothing` per PSD cone (the factors a previous
+`factors = true` solve returned: that cone then starts at `vectors * Diagonal(values) * vectors'` and at target rank
+`length(values) + 1`); `target_rank[k] > 0` overrides the target rank of cone k.  Combines with `factors`, not with
+`n_shards > 1`.
 (This wrapper cannot be executed where the library is tested: there is no Julia there.  Its struct is checked against the
 header field by field, the call itself is exercised through the ctypes binding.)
 """
 function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
                             n_shards::Integer = 1, device_ids::Union{Nothing,AbstractVector{<:Integer}} = nothing,
-                            factors::Union{Nothing,Bool,AbstractVector{<:Integer}} = nothing)
+                            factors::Union{Nothing,Bool,AbstractVector{<:Integer}} = nothing,
+                            start::Union{Nothing,NamedTuple} = nothing)
     psd_ptr = Int64[0]; psd_idx = Int64[]
     for s in con.sdpcone
         append!(psd_idx, s.vec_i); push!(psd_ptr, length(psd_idx))
@@ -244,7 +267,34 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
     fvectors = zeros(max(fvec_ptr[end], 1)); fvalues = zeros(max(fval_ptr[end], 1))
     frank = zeros(Int64, max(nb, 1)); ffound = zeros(Int64, max(nb, 1)); fsource = zeros(Int32, max(nb, 1))
     fresid = zeros(max(nb, 1)); fxnorm = zeros(max(nb, 1))
-    GC.@preserve A G aff psd_ptr psd_idx soc_ptr soc_idx primal dual_cone dual_eq dual_in slack_eq slack_in opt devs caps fvec_ptr fval_ptr fvectors fvalues frank ffound fsource fresid fxnorm begin
+    # warm start: the caller's arrays as Float64 / Int64 vectors, the factors of every cone concatenated column-major
+    (start !== nothing && sharded) && error("start: not available in a block-sharded solve")
+    sget(name) = (start !== nothing && haskey(start, name)) ? getfield(start, name) : nothing
+    s_primal = sget(:primal) === nothing ? Float64[] : Vector{Float64}(sget(:primal))
+    s_deq = sget(:dual_eq) === nothing ? Float64[] : Vector{Float64}(sget(:dual_eq))
+    s_din = sget(:dual_in) === nothing ? Float64[] : Vector{Float64}(sget(:dual_in))
+    (sget(:primal) === nothing || length(s_primal) == n) || error("start.primal: length n")
+    (sget(:dual_eq) === nothing || length(s_deq) == p) || error("start.dual_eq: length p")
+    (sget(:dual_in) === nothing || length(s_din) == m) || error("start.dual_in: length m")
+    s_fac = sget(:factors)
+    s_rank = fill(Int64(-1), max(nb, 1)); s_vec_ptr = Int64[0]; s_val_ptr = Int64[0]
+    s_vectors = Float64[]; s_values = Float64[]
+    if s_fac !== nothing
+        length(s_fac) == nb || error("start.factors: one entry per PSD cone")
+        for k in 1:nb
+            if s_fac[k] !== nothing
+                vals = Vector{Float64}(s_fac[k][1]); V = Matrix{Float64}(s_fac[k][2])
+                size(V) == (sides[k], length(vals)) || error("start.factors[$k]: vectors must be side x rank")
+                s_rank[k] = length(vals); append!(s_vectors, vec(V)); append!(s_values, vals)
+            end
+            push!(s_vec_ptr, length(s_vectors)); push!(s_val_ptr, length(s_values))
+        end
+    end
+    push!(s_vectors, 0.0); push!(s_values, 0.0)                          # (never empty: a valid pointer)
+    s_tr = sget(:target_rank) === nothing ? Int64[] : Vector{Int64}(sget(:target_rank))
+    (sget(:target_rank) === nothing || length(s_tr) == nb) || error("start.target_rank: one entry per PSD cone")
+    ptr_or_null(v, given) = given ? pointer(v) : Ptr{eltype(v)}(C_NULL)
+    GC.@preserve A G aff psd_ptr psd_idx soc_ptr soc_idx primal dual_cone dual_eq dual_in slack_eq slack_in opt devs caps fvec_ptr fval_ptr fvectors fvalues frank ffound fsource fresid fxnorm s_primal s_deq s_din s_rank s_vec_ptr s_val_ptr s_vectors s_values s_tr begin
         prob = Problem(n, p, m, _csc(A), _csc(G), pointer(aff.b), pointer(aff.h), pointer(aff.c),
                        length(con.sdpcone), pointer(psd_ptr), pointer(psd_idx),
                        length(con.socone), pointer(soc_ptr), pointer(soc_idx),
@@ -261,6 +311,23 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
                   (Ref{Problem}, Ptr{UInt64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ref{CResult}, Ptr{Stats}),
                   prob, opt, Int32(n_shards), device_ids === nothing ? Ptr{Int32}(C_NULL) : pointer(devs),
                   C_NULL, C_NULL, C_NULL, res, C_NULL)                # default owners, no per-shard stats
+        elseif start !== nothing
+            st = Start(sizeof(Start), ptr_or_null(s_primal, sget(:primal) !== nothing),
+                       ptr_or_null(s_deq, sget(:dual_eq) !== nothing && p > 0), ptr_or_null(s_din, sget(:dual_in) !== nothing && m > 0),
+                       s_fac === nothing ? 0 : nb, pointer(s_rank), pointer(s_vec_ptr), pointer(s_val_ptr),
+                       pointer(s_vectors), pointer(s_values), ptr_or_null(s_tr, sget(:target_rank) !== nothing && nb > 0),
+                       sget(:primal_step) === nothing ? 0.0 : Float64(sget(:primal_step)),
+                       sget(:beta) === nothing ? 0.0 : Float64(sget(:beta)))
+            if want_factors
+                fac = PsdFactors(sizeof(PsdFactors), nb, pointer(caps), pointer(fvec_ptr), pointer(fval_ptr),
+                                 pointer(fvectors), pointer(fvalues), pointer(frank), pointer(ffound), pointer(fsource),
+                                 pointer(fresid), pointer(fxnorm))
+                ccall((:proxsdp_hip_solve_from, libproxsdp_hip), Cint,
+                      (Ref{Problem}, Ptr{UInt64}, Ref{CResult}, Ref{Start}, Ref{PsdFactors}), prob, opt, res, st, fac)
+            else
+                ccall((:proxsdp_hip_solve_from, libproxsdp_hip), Cint,
+                      (Ref{Problem}, Ptr{UInt64}, Ref{CResult}, Ref{Start}, Ptr{Cvoid}), prob, opt, res, st, C_NULL)
+            end
         elseif want_factors
             fac = PsdFactors(sizeof(PsdFactors), nb, pointer(caps), pointer(fvec_ptr), pointer(fval_ptr),
                              pointer(fvectors), pointer(fvalues), pointer(frank), pointer(ffound), pointer(fsource),

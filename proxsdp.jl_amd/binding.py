@@ -188,6 +188,13 @@ class PsdFactors(C.Structure):
                 ("resid", pf64), ("xnorm", pf64)]
 
 
+class Start(C.Structure):
+    """proxsdp_start (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("primal", pf64), ("dual_eq", pf64), ("dual_in", pf64), ("n_psd", i64),
+                ("rank", pi64), ("vec_ptr", pi64), ("val_ptr", pi64), ("vectors", pf64), ("values", pf64),
+                ("target_rank", pi64), ("primal_step", f64), ("beta", f64)]
+
+
 FACTOR_NONE, FACTOR_RITZ, FACTOR_EIG = 0, 1, 2
 FACTOR_SOURCE_NAMES = {FACTOR_NONE: "NONE", FACTOR_RITZ: "RITZ", FACTOR_EIG: "EIG"}
 
@@ -235,6 +242,9 @@ def lib():
                                        C.POINTER(State), C.POINTER(State)]
     L.proxsdp_hip_solve_factored.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Result),
                                              C.POINTER(PsdFactors)]
+    L.proxsdp_hip_solve_from.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Result),
+                                         C.POINTER(Start), C.POINTER(PsdFactors)]
+    L.proxsdp_hip_start_point.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Start), C.POINTER(State)]
     L.proxsdp_hip_factor_residual.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64]
     L.proxsdp_hip_factor_residual_kernel.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64, i32, pf64]
     L.proxsdp_hip_psd_project.argtypes = [pf64, i64, i32, i32, C.POINTER(Options), pf64, pf64,
@@ -513,8 +523,107 @@ def _factors_list(sides, arr):
     return out
 
 
+START_KEYS = ("primal", "dual_eq", "dual_in", "factors", "target_rank", "primal_step", "beta")
+
+
+def start_from_result(res):
+    """The start dictionary of a previous SolveResult: its primal and duals, and -- when the solve returned them
+    (solve(factors=...)) -- the factors of every PSD cone.  A cone whose factors were cut by `cap` (info["rank_found"] >
+    info["rank"]) or that asked for none (cap 0) gets None: it starts from its entries of `primal`."""
+    d = dict(primal=None if res.primal is None else np.array(res.primal, dtype=np.float64),
+             dual_eq=np.array(res.dual_eq, dtype=np.float64), dual_in=np.array(res.dual_in, dtype=np.float64))
+    fl = getattr(res, "psd_factors", None)
+    if fl is not None:
+        fac = []
+        for vals, vecs, info in fl:
+            cut = info["rank_found"] > info["rank"] or info.get("cap", 1) <= 0
+            fac.append(None if cut else (np.array(vals, dtype=np.float64), np.array(vecs, dtype=np.float64)))
+        if d["primal"] is None and any(f is None for f in fac):
+            raise ValueError("start: a cone without complete factors needs the result's primal (solve(primal=True))")
+        d["factors"] = fac
+    return d
+
+
+def _start_struct(n, p, m, sides, start):
+    """proxsdp_start for a model with n variables, p + m rows and PSD cones of the given sides, and the arrays behind it.
+    start: a dict with any of START_KEYS, or a previous SolveResult (start_from_result).  factors: one entry per PSD cone,
+    (values, vectors[, info]) with vectors of shape (side, rank), or None = no factors for that cone."""
+    if isinstance(start, SolveResult):
+        start = start_from_result(start)
+    start = dict(start)
+    unknown = set(start) - set(START_KEYS)
+    if unknown:
+        raise ValueError(f"start: unknown keys {sorted(unknown)}")
+    nb = len(sides)
+    S = Start()
+    S.struct_size = C.sizeof(Start)
+    arr = {}
+    for k, ln in (("primal", n), ("dual_eq", p), ("dual_in", m)):
+        v = start.get(k)
+        if v is None:
+            continue
+        v = _f(v).ravel()
+        if len(v) != ln:
+            raise ValueError(f"start[{k!r}] must have length {ln}")
+        arr[k] = v if len(v) else np.zeros(1)
+        setattr(S, k, _p(arr[k]))
+    fac = start.get("factors")
+    if fac is not None:
+        fac = list(fac)
+        if len(fac) != nb:
+            raise ValueError(f"start['factors'] must have one entry per PSD cone ({nb})")
+        rank = np.full(max(nb, 1), -1, dtype=np.int64)
+        vec_ptr, val_ptr = np.zeros(nb + 1, dtype=np.int64), np.zeros(nb + 1, dtype=np.int64)
+        vecs, vals = [], []
+        for k, f in enumerate(fac):
+            if f is not None:
+                lam, V = _f(f[0]).ravel(), np.asarray(f[1], dtype=np.float64)
+                V = V.reshape(sides[k], -1) if V.size else np.zeros((sides[k], 0))
+                if V.shape != (sides[k], len(lam)):
+                    raise ValueError(f"start['factors'][{k}]: vectors must be (side, rank) = ({sides[k]}, {len(lam)})")
+                rank[k] = len(lam)
+                vecs.append(V.ravel(order="F")); vals.append(lam)
+            vec_ptr[k + 1] = vec_ptr[k] + (sides[k] * rank[k] if rank[k] > 0 else 0)
+            val_ptr[k + 1] = val_ptr[k] + max(int(rank[k]), 0)
+        arr.update(rank=rank, vec_ptr=vec_ptr, val_ptr=val_ptr,
+                   vectors=_f(np.concatenate(vecs + [np.zeros(1)])), values=_f(np.concatenate(vals + [np.zeros(1)])))
+        S.n_psd = nb
+        S.rank, S.vec_ptr, S.val_ptr = _p(rank, pi64), _p(vec_ptr, pi64), _p(val_ptr, pi64)
+        S.vectors, S.values = _p(arr["vectors"]), _p(arr["values"])
+    tr = start.get("target_rank")
+    if tr is not None:
+        tr = _i(tr).ravel()
+        if len(tr) != nb:
+            raise ValueError(f"start['target_rank'] must have one entry per PSD cone ({nb})")
+        arr["target_rank"] = tr if len(tr) else np.zeros(1, dtype=np.int64)
+        S.target_rank = _p(arr["target_rank"], pi64)
+    S.primal_step = float(start.get("primal_step") or 0.0)
+    S.beta = float(start.get("beta") or 0.0)
+    return S, arr
+
+
+def start_point(prob, options=None, start=None, index_base=0, eig_resid=None):
+    """proxsdp_hip_start_point: the "Init" section and the start path of a warm-started solve, nothing more.  Returns the
+    solver's internal x, Mty (n), y, Mx (p + m), target_rank, the scalars primal_step, primal_step_old, dual_step, beta,
+    theta, adapt_level and iteration = 0.  start = None: the cold point."""
+    L = lib()
+    o = options if options is not None else default_options()
+    M = _Marshalled(prob, eig_resid, index_base)
+    n, Q, nb = int(M.P.n), int(M.P.p + M.P.m), int(M.P.n_psd)
+    st = None
+    if start is not None:
+        st, sarr = _start_struct(n, int(M.P.p), int(M.P.m), psd_sides(prob), start)
+    S, arr = _state_struct(n, Q, nb, o.convergence_window)
+    _check(L.proxsdp_hip_start_point(C.byref(M.P), C.byref(o), C.byref(st) if st is not None else None, C.byref(S)))
+    d = dict(iteration=int(S.iteration), x=arr["x"][:n].copy(), y=arr["y"][:Q].copy(), Mty=arr["Mty"][:n].copy(),
+             Mx=arr["Mx"][:Q].copy(), target_rank=arr["target_rank"][:nb].copy())
+    for q, nme in enumerate(STATE_SCAL_NAMES[:6]):
+        d[nme] = float(S.scal[q])
+    return d
+
+
 def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, coupling=None, index_base=0, nccl_comm=None,
-          resume=None, capture_iteration=None, factors=False, primal=True):
+          resume=None, capture_iteration=None, factors=False, primal=True, start=None):
     """proxsdp_hip_solve: replaces chambolle_pock(aff, con, options) (MOI_wrapper.jl:310).
     Returns the minimisation objective; sign/constant fix-up is the caller's
     (MOI_wrapper.jl:336-337), see optimizer.Optimizer.
@@ -532,8 +641,16 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
     (values, vectors, info) per PSD cone with X_k ~ vectors diag(values) vectors' (values descending and > 0; info: rank,
     rank_found, source / source_name, resid, xnorm, cap); True asks for every pair, a dict caps the columns per cone (cones
     it does not name get nothing).  Not with resume / capture_iteration, and not for a shard.
-    primal = False: proxsdp_result.primal = NULL (`.primal` comes back None)."""
+    primal = False: proxsdp_result.primal = NULL (`.primal` comes back None).
+    start: warm start (proxsdp_hip_solve_from) -- a dict with any of primal, dual_eq, dual_in (as a result holds them),
+    factors = [(values, vectors) | None per PSD cone], target_rank (per cone, 0 = derive), primal_step, beta; or a previous
+    SolveResult, whose psd_factors are used when it has them (a cone cut by `cap` starts from its primal entries).  The
+    loop is entered at iteration 1 from that point, each factored cone at target rank rank + 1 unless target_rank says
+    otherwise.  Combines with factors=; not with resume / capture_iteration / reduce / coupling / nccl_comm."""
     L = lib()
+    if start is not None and (resume is not None or capture_iteration is not None or reduce is not None or
+                              coupling is not None or nccl_comm):
+        raise ValueError("start cannot be combined with the state seam or a block-sharded solve")
     if factors is not False and factors is not None and (resume is not None or capture_iteration is not None):
         raise ValueError("factors cannot be combined with the state seam")
     o = options if options is not None else default_options()
@@ -587,10 +704,16 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
     R.trace = _p(trace)
     if not primal:
         R.primal = None
+    st = None
+    if start is not None:
+        st, sarr = _start_struct(n, p, m, psd_sides(prob), start)
     if factors is not False and factors is not None:
         sides = psd_sides(prob)
         F, farr = _factors_struct(sides, factors)
-        _check(L.proxsdp_hip_solve_factored(C.byref(M.P), C.byref(o), C.byref(R), C.byref(F)))
+        if st is not None:
+            _check(L.proxsdp_hip_solve_from(C.byref(M.P), C.byref(o), C.byref(R), C.byref(st), C.byref(F)))
+        else:
+            _check(L.proxsdp_hip_solve_factored(C.byref(M.P), C.byref(o), C.byref(R), C.byref(F)))
         arrays = [a[:k] for a, k in zip(arrays, (n, n, p, m, p, m))]
         if not primal:
             arrays[0] = None
@@ -598,7 +721,10 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
         out.psd_factors = _factors_list(sides, farr)
         return out
     if resume is None and capture_iteration is None:
-        _check(L.proxsdp_hip_solve(C.byref(M.P), C.byref(o), C.byref(R)))
+        if st is not None:
+            _check(L.proxsdp_hip_solve_from(C.byref(M.P), C.byref(o), C.byref(R), C.byref(st), None))
+        else:
+            _check(L.proxsdp_hip_solve(C.byref(M.P), C.byref(o), C.byref(R)))
         arrays = [a[:k] for a, k in zip(arrays, (n, n, p, m, p, m))]
         if not primal:
             arrays[0] = None

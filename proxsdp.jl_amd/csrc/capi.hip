@@ -165,7 +165,8 @@ static proxsdp_options begin_solve(const proxsdp_options* opt, proxsdp_result* r
 
 // the solve behind proxsdp_hip_solve_ex and proxsdp_hip_solve_factored (fac: validated by the caller, or NULL)
 static int solve_impl(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
-                      const proxsdp_state* resume, proxsdp_state* capture, proxsdp_psd_factors* fac) {
+                      const proxsdp_state* resume, proxsdp_state* capture, proxsdp_psd_factors* fac,
+                      const proxsdp_start* start = nullptr) {
     bool comm_aborted = false;
     const int rc = guarded([&]() -> int {
         if (!prob || !res) throw std::invalid_argument("NULL problem or result");
@@ -174,6 +175,7 @@ static int solve_impl(const proxsdp_problem* prob, const proxsdp_options* opt, p
         S.resume_state = resume;
         S.capture_state = capture;
         S.factors_out = fac;
+        S.start = start;
         try {
             S.run();
         } catch (...) {
@@ -199,9 +201,7 @@ int proxsdp_hip_solve_ex(const proxsdp_problem* prob, const proxsdp_options* opt
 
 // the solve with the factors of its PSD solution (Solver::extract_factors): every argument is checked here, on the host,
 // before a solver -- and with it the device -- exists
-int proxsdp_hip_solve_factored(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
-                               proxsdp_psd_factors* fac) {
-    const int rc = guarded([&]() -> int {
+static void check_factors_arg(const proxsdp_problem* prob, const proxsdp_result* res, const proxsdp_psd_factors* fac) {
         if (!prob || !res || !fac) throw std::invalid_argument("NULL problem, result or factors");
         if (fac->struct_size != (int64_t)sizeof(proxsdp_psd_factors))
             throw std::invalid_argument("proxsdp_psd_factors.struct_size mismatch");
@@ -229,10 +229,97 @@ int proxsdp_hip_solve_factored(const proxsdp_problem* prob, const proxsdp_option
         if (any && (!fac->vectors || !fac->values)) throw std::invalid_argument("proxsdp_psd_factors: NULL vectors / values");
         if (prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0)
             throw std::domain_error("proxsdp_hip_solve_factored does not serve a shard of a block-sharded solve");
+}
+
+int proxsdp_hip_solve_factored(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                               proxsdp_psd_factors* fac) {
+    const int rc = guarded([&]() -> int { check_factors_arg(prob, res, fac); return 0; });
+    if (rc != 0) return rc;
+    return solve_impl(prob, opt, res, nullptr, nullptr, fac);
+}
+
+// ---- warm start (proxsdp_start): every argument is checked here, on the host, before a solver -- and with it the device -- exists
+static void check_start_arg(const proxsdp_problem* prob, const proxsdp_start* st) {
+    if (!prob) throw std::invalid_argument("NULL problem");
+    if (!st) return;
+    if (st->struct_size != (int64_t)sizeof(proxsdp_start)) throw std::invalid_argument("proxsdp_start.struct_size mismatch");
+    if (prob->n < 0 || prob->p < 0 || prob->m < 0 || prob->n_psd < 0) throw std::invalid_argument("negative dimension");
+    if (st->n_psd != 0 && st->n_psd != prob->n_psd) throw std::invalid_argument("proxsdp_start.n_psd is neither 0 nor problem.n_psd");
+    if (prob->n_psd > 0 && !prob->psd_ptr) throw std::invalid_argument("psd_ptr/psd_idx is NULL");
+    if (st->n_psd != 0 && (!st->rank || !st->vec_ptr || !st->val_ptr)) throw std::invalid_argument("proxsdp_start: NULL rank / vec_ptr / val_ptr");
+    if (!(st->primal_step >= 0.0) || !std::isfinite(st->primal_step) || !(st->beta >= 0.0) || !std::isfinite(st->beta))
+        throw std::invalid_argument("proxsdp_start: primal_step and beta must be finite and >= 0");
+    auto all_finite = [](const double* v, int64_t len) {
+        for (int64_t i = 0; i < len; ++i) if (!std::isfinite(v[i])) return false;
+        return true;
+    };
+    if (st->target_rank)
+        for (int64_t k = 0; k < prob->n_psd; ++k)
+            if (st->target_rank[k] < 0) throw std::invalid_argument("proxsdp_start.target_rank is negative");
+    bool any = false;
+    for (int64_t k = 0; k < st->n_psd; ++k) {
+        const int64_t len = prob->psd_ptr[k + 1] - prob->psd_ptr[k];
+        if (len <= 0) throw std::invalid_argument("empty PSD cone");
+        int64_t side = (int64_t)((std::sqrt(8.0 * (double)len + 1.0) - 1.0) / 2.0);
+        while (side * (side + 1) / 2 < len) ++side;
+        while (side * (side + 1) / 2 > len) --side;
+        if (side * (side + 1) / 2 != len) throw std::invalid_argument("PSD cone length is not triangular");
+        const int64_t r = st->rank[k];
+        if (r < -1 || r > side) throw std::invalid_argument("proxsdp_start.rank must be -1 .. side");
+        if (r <= 0) continue;
+        any = true;
+        if (st->vec_ptr[k] < 0 || st->val_ptr[k] < 0 || st->vec_ptr[k + 1] - st->vec_ptr[k] < side * r ||
+            st->val_ptr[k + 1] - st->val_ptr[k] < r)
+            throw std::invalid_argument("proxsdp_start: vec_ptr / val_ptr span too small for rank");
+    }
+    if (any && (!st->vectors || !st->values)) throw std::invalid_argument("proxsdp_start: NULL vectors / values");
+    for (int64_t k = 0; k < st->n_psd; ++k) {
+        const int64_t r = st->rank[k];
+        if (r <= 0) continue;
+        const int64_t len = prob->psd_ptr[k + 1] - prob->psd_ptr[k];
+        const int64_t side = (int64_t)std::llround((std::sqrt(8.0 * (double)len + 1.0) - 1.0) / 2.0);
+        if (!all_finite(st->vectors + st->vec_ptr[k], side * r) || !all_finite(st->values + st->val_ptr[k], r))
+            throw std::invalid_argument("proxsdp_start: non-finite factor entry");
+        for (int64_t j = 0; j < r; ++j)
+            if (!(st->values[st->val_ptr[k] + j] > 0.0)) throw std::invalid_argument("proxsdp_start.values must be > 0");
+    }
+    if ((st->primal && !all_finite(st->primal, prob->n)) || (st->dual_eq && !all_finite(st->dual_eq, prob->p)) ||
+        (st->dual_in && !all_finite(st->dual_in, prob->m)))
+        throw std::invalid_argument("proxsdp_start: non-finite entry in primal / dual_eq / dual_in");
+    if (prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0)
+        throw std::domain_error("a warm start does not serve a shard of a block-sharded solve");
+}
+
+int proxsdp_hip_solve_from(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                           const proxsdp_start* start, proxsdp_psd_factors* fac) {
+    const int rc = guarded([&]() -> int {
+        if (!prob || !res) throw std::invalid_argument("NULL problem or result");
+        check_start_arg(prob, start);
+        if (fac) check_factors_arg(prob, res, fac);
         return 0;
     });
     if (rc != 0) return rc;
-    return solve_impl(prob, opt, res, nullptr, nullptr, fac);
+    return solve_impl(prob, opt, res, nullptr, nullptr, fac, start);
+}
+
+int proxsdp_hip_start_point(const proxsdp_problem* prob, const proxsdp_options* opt, const proxsdp_start* start,
+                            proxsdp_state* out) {
+    return guarded([&]() -> int {
+        if (!prob || !out) throw std::invalid_argument("NULL problem or state");
+        check_start_arg(prob, start);
+        if (out->struct_size != (int64_t)sizeof(proxsdp_state)) throw std::invalid_argument("proxsdp_state.struct_size mismatch");
+        if (out->n != prob->n || out->Q != prob->p + prob->m || out->n_psd != prob->n_psd)
+            throw std::invalid_argument("start point: n / Q / n_psd do not match the problem");
+        if (!out->x || !out->Mty || (out->Q > 0 && (!out->y || !out->Mx)) || (out->n_psd > 0 && !out->target_rank))
+            throw std::invalid_argument("start point: NULL array");
+        proxsdp_result dummy{};
+        const proxsdp_options o = begin_solve(opt, &dummy);
+        proxsdp::Solver S(*prob, o, dummy);
+        S.start = start;
+        S.start_out = out;
+        S.run();
+        return 0;
+    });
 }
 
 // ---- block-sharded solve from one call: in-process shards (shard_split.hpp, shard_group.hpp)

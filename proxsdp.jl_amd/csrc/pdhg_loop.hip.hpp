@@ -720,7 +720,7 @@ inline const double* Solver::batch_read_back(int nc) {
 // Returns the accepted candidate's scalar record.
 inline const double* Solver::linesearch_and_residuals() {
     const int ncmax = opt.general_batch != 0 ? NCAND : 1;
-    const double xold_coef = (iter == 1 && opt.advanced_initialization) ? 0.0 : 1.0;   // x_old = 0 at k = 1
+    const double xold_coef = (iter == 1 && opt.advanced_initialization && !start_active) ? 0.0 : 1.0;   // x_old = 0 at k = 1 (a warm start has x_old = x)
     const double* rec = nullptr;
     auto commit = [&](int c) {                           // y <- y_c, M'y <- M'y_c (one launch)
         const BatchShape b = batch_shape();
@@ -1637,6 +1637,125 @@ inline void Solver::apply_resume() {
     for (EigWork& W : eig) { W.have_factors = false; W.x_prev_sparse = false; }
 }
 
+// enter the loop from the caller's point (include/proxsdp_hip.h proxsdp_start; validated by the entry point): called after
+// the "Init" section built every buffer and the cold point.  Nothing of size n is built in a host loop: the point is uploaded
+// as the caller holds it and brought into the solver's order and scale by k_start_gather; a factored cone goes through the
+// solver's own reconstruction launch straight into the iterate; M x and M'y come from the solver's product launches.
+inline void Solver::apply_start() {
+    const proxsdp_start& s = *start;
+    const size_t nb = P.blocks.size();
+    auto given = [&](size_t idx) -> long long { return s.n_psd > 0 ? (long long)s.rank[idx] : -1; };
+    // target ranks and step scalars: they hold for a start without a point as well
+    bool any_fac = false;
+    for (size_t idx = 0; idx < nb; ++idx) {
+        const long long side = P.blocks[idx].n, r = given(idx);
+        any_fac = any_fac || r >= 0;
+        if (s.target_rank && s.target_rank[idx] > 0) target_rank[idx] = std::min<long long>(s.target_rank[idx], side);
+        else if (r >= 0) target_rank[idx] = std::min<long long>(side, std::max<long long>(std::max(opt.initial_target_rank, 1), r + 1));
+    }
+    if (s.primal_step > 0.0) { primal_step = s.primal_step; primal_step_old = primal_step; dual_step = primal_step; }
+    if (s.beta > 0.0) beta = s.beta;
+    if (!s.primal && !s.dual_eq && !s.dual_in && !any_fac) return;      // no point given: the cold vectors stay (x_old = 0)
+    start_active = true;
+    if (P.equilibrated && Ddiag_d.n == 0) {                              // (the exit path finds them uploaded)
+        Ddiag_d.alloc(P.n); Ediag_d.alloc(std::max<int64_t>(P.Q, 1));
+        Ddiag_d.upload(P.Ddiag.data(), P.n, stream); Ediag_d.upload(P.Ediag.data(), P.Q, stream);
+    }
+    const double sqrt2 = std::sqrt(2.0);
+    start_src_d.alloc((size_t)std::max<int64_t>(std::max(P.n, P.Q), 1));
+    auto gather = [&](const long long* ord, const unsigned char* od, const double* D, double* out, long long k0, long long k1) {
+        if (k1 <= k0) return;
+        hipLaunchKernelGGL(dev::k_start_gather, dim3(grid_for(k1 - k0)), dim3(dev::TPB), 0, stream,
+                           (const double*)start_src_d.p, ord, od, D, sqrt2, out, k0, k1);
+    };
+    if (s.primal) {                                      // every entry outside the factored cones
+        static_assert(sizeof(long long) == sizeof(int64_t), "variable order is uploaded as it is");
+        start_ord_d.alloc(P.n);
+        start_ord_d.upload(reinterpret_cast<const long long*>(P.ord.data()), P.n, stream);
+        if (offdiag_d.n == 0) { offdiag_d.alloc(P.n); offdiag_d.upload(P.offdiag.data(), P.n, stream); }
+        start_src_d.upload(s.primal, P.n, stream);
+        const double* Dd = P.equilibrated ? Ddiag_d.p : nullptr;
+        long long k = 0;
+        for (size_t idx = 0; idx < nb; ++idx) {
+            if (given(idx) < 0) continue;
+            gather(start_ord_d.p, offdiag_d.p, Dd, xbuf[xc].p, k, P.blocks[idx].off);
+            k = P.blocks[idx].off + P.blocks[idx].N;
+        }
+        gather(start_ord_d.p, offdiag_d.p, Dd, xbuf[xc].p, k, P.n);
+        PX_HIP(hipGetLastError());
+        PX_HIP(hipStreamSynchronize(stream));            // (start_src_d takes the duals next)
+    }
+    std::vector<double> ones(nb, 0.0), lamh;
+    for (size_t idx = 0; idx < nb; ++idx) {              // factored cones: x_k = V diag(lambda / d) V' (D = d I)
+        const long long r = given(idx);
+        if (r < 0) continue;
+        const BlockInfo& B = P.blocks[idx];
+        double* xp = xbuf[xc].p + B.off;
+        if (r == 0) { PX_HIP(hipMemsetAsync(xp, 0, (size_t)B.N * sizeof(double), stream)); continue; }
+        const double* V = s.vectors + s.vec_ptr[idx];
+        const double* lam = s.values + s.val_ptr[idx];
+        lamh.assign(lam, lam + r);
+        if (P.equilibrated) for (double& v : lamh) v /= P.Ddiag[B.off];
+        if (B.n == 1) {                                  // (no workspace: the one entry, in the kernel's order of operations)
+            ones[idx] = V[0] * (V[0] * lamh[0]);
+            PX_HIP(hipMemcpyAsync(xp, &ones[idx], sizeof(double), hipMemcpyHostToDevice, stream));
+            continue;
+        }
+        EigWork& W = eig[idx];
+        start_V.alloc((size_t)W.npad * r); start_V.zero(stream);       // padded to the workspace's leading dimension
+        PX_HIP(hipMemcpy2DAsync(start_V.p, (size_t)W.npad * sizeof(double), V, (size_t)B.n * sizeof(double),
+                                (size_t)B.n * sizeof(double), (size_t)r, hipMemcpyHostToDevice, stream));
+        start_lam.alloc(r); start_lam.upload(lamh.data(), r, stream);
+        launch_reconstruct(W, start_V.p, W.npad, start_lam.p, (int)r, xp);
+        PX_HIP(hipGetLastError());
+        PX_HIP(hipStreamSynchronize(stream));            // (the staging buffers serve the next cone)
+    }
+    if (P.Q > 0 && (s.dual_eq || s.dual_in)) {           // y = [dual_eq; dual_in] / E, then M'y
+        if (s.dual_eq) start_src_d.upload(s.dual_eq, P.p, stream);
+        else if (P.p > 0) PX_HIP(hipMemsetAsync(start_src_d.p, 0, (size_t)P.p * sizeof(double), stream));
+        if (s.dual_in) PX_HIP(hipMemcpyAsync(start_src_d.p + P.p, s.dual_in, (size_t)P.m * sizeof(double), hipMemcpyHostToDevice, stream));
+        else if (P.m > 0) PX_HIP(hipMemsetAsync(start_src_d.p + P.p, 0, (size_t)P.m * sizeof(double), stream));
+        gather(nullptr, nullptr, P.equilibrated ? Ediag_d.p : nullptr, ybuf[yc].p, 0, P.Q);
+        const BatchShape b = batch_shape();
+        PX_HIP(hipMemcpyAsync(ycand_d.p, ybuf[yc].p, (size_t)P.Q * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        dev::TrialBatch tb{};                            // ONE plain candidate: M'y as computed (on the support, or every column)
+        tb.nc = 1; tb.plain = 1;
+        batch_mty(tb, 1);
+        PX_HIP(hipMemcpyAsync(b.mty_cur, Mtycand_d.p, (size_t)b.cnt * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    }
+    spmv(xbuf[xc].p, Mxbuf[mxc].p);                      // M x (sparse rows, and the dense block with its scale vectors)
+    PX_HIP(hipGetLastError());
+    PX_HIP(hipStreamSynchronize(stream));
+    if (P.dense()) { dense_ev_harvest(); dense_passes_seen = st.dense_passes; }   // (set-up work, as the sigma_max passes)
+    // the ping-pong pairs' current buffers hold the point, so x_old = x, y_old = y, (M x)_old = M x, (M'y)_old = M'y at
+    // iteration 1; the iterate is a general matrix: the first projection reads the packed buffer
+    for (EigWork& W : eig) { W.have_factors = false; W.x_prev_sparse = false; W.ritz_ok = false; }
+}
+
+// proxsdp_hip_start_point: the internal vectors after the start path
+inline void Solver::write_start_point() {
+    proxsdp_state& s = *start_out;
+    PX_HIP(hipStreamSynchronize(stream));
+    xbuf[xc].download(s.x, P.n, stream);
+    if (P.Q > 0) { ybuf[yc].download(s.y, P.Q, stream); Mxbuf[mxc].download(s.Mx, P.Q, stream); }
+    if (use_support) {
+        std::vector<int> supp(ns);
+        std::vector<double> mtyS(std::max(ns, 1), 0.0);
+        supp_d.download(supp.data(), ns, stream);
+        MtyS_cur.download(mtyS.data(), ns, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+        std::fill(s.Mty, s.Mty + P.n, 0.0);
+        for (int q = 0; q < ns; ++q) s.Mty[supp[q]] = mtyS[q];
+    } else {
+        Mtybuf[mtyc].download(s.Mty, P.n, stream);
+    }
+    PX_HIP(hipStreamSynchronize(stream));
+    s.scal[0] = primal_step; s.scal[1] = primal_step_old; s.scal[2] = dual_step;
+    s.scal[3] = beta; s.scal[4] = theta; s.scal[5] = adapt_level;
+    for (size_t idx = 0; idx < P.blocks.size(); ++idx) s.target_rank[idx] = target_rank[idx];
+    s.iteration = 0;
+}
+
 // write capture_state: the stream is idle (every iteration ends with a synchronisation)
 inline void Solver::write_capture() {
     proxsdp_state& s = *capture_state;
@@ -1888,6 +2007,8 @@ inline void Solver::run() {
     PX_HIP(hipStreamSynchronize(stream));
     long long k_first = 1;
     if (resume_state) { apply_resume(); k_first = resume_state->iteration + 1; }
+    if (start) apply_start();
+    if (start_out) { write_start_point(); return; }
     if (capture_state) { check_state_shape(*capture_state, "capture"); capture_state->ints[3] = 0; }
     st.init_time = now_s() - t_init0;
 

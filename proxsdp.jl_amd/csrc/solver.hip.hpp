@@ -498,6 +498,15 @@ public:
     void check_state_shape(const proxsdp_state& s, const char* what) const;
     void apply_resume();
     void write_capture();
+    // warm start (proxsdp_hip_solve_from): the caller's point, validated by the entry; start_out: proxsdp_hip_start_point
+    // (run() returns after the start path and writes the internal vectors there)
+    const proxsdp_start* start = nullptr;
+    proxsdp_state* start_out = nullptr;
+    bool start_active = false;            // the start gave a point: x_old = x at iteration 1 (a cold solve has x_old = 0)
+    DevBuf<long long> start_ord_d;
+    DevBuf<double> start_src_d, start_V, start_lam;
+    void apply_start();
+    void write_start_point();
     int ada_count = 0;                    // pdhg.jl:306-332 (a local of chambolle_pock)
     void wait_event(hipEvent_t ev) {
         if (opt.host_wait_spin == 0) PX_HIP(hipEventSynchronize(ev));

@@ -160,6 +160,9 @@ class Model:
         self._soc = []
         self.sense = FEASIBILITY_SENSE
         self.objective = ScalarAffineFunction([], 0.0)
+        self._primal_start = {}    # VariablePrimalStart: variable -> value
+        self._dual_start = {}      # ConstraintDualStart: (kind, row) -> the library's dual of that row
+        self._last = None          # shape and raw result of the last optimize (optimize(warm=True))
         self.optimizer.empty()
 
     def is_empty(self):
@@ -307,8 +310,86 @@ class Model:
                        objective_constant=float(self.objective.constant) if self.sense != FEASIBILITY_SENSE else 0.0,
                        name=name)
 
-    def optimize(self, **kw):
-        return self.optimizer.optimize(self.problem(), **kw)
+    # -- start values (MOI.VariablePrimalStart, MOI.ConstraintDualStart; the reference declares neither: MOI_wrapper.jl:302)
+    def set_variable_primal_start(self, vi, value):
+        """VariablePrimalStart of one variable or a list of them; None removes it."""
+        if isinstance(vi, (int, np.integer)):
+            vi, value = [vi], [value]
+        elif value is None:
+            value = [None] * len(vi)
+        for v, x in zip(vi, value):
+            if not (1 <= int(v) <= self.nvar):
+                raise ValueError(f"invalid variable index {v}")
+            if x is None:
+                self._primal_start.pop(int(v), None)
+            else:
+                self._primal_start[int(v)] = float(x)
+
+    def variable_primal_start(self, vi):
+        return self._primal_start.get(int(vi))
+
+    def set_constraint_dual_start(self, ci, value):
+        """ConstraintDualStart of a constraint that lives in rows of A / G (every scalar constraint, and the vector ones in
+        Zeros / Nonpositives / Nonnegatives), through the inverse of constraint_dual's map; None removes it."""
+        if ci.kind not in ("zeros", "nonpos") or not ci.rows:
+            raise TypeError("ConstraintDualStart: only for constraints the model maps to rows")
+        vals = [None] * len(ci.rows) if value is None else np.atleast_1d(np.asarray(value, dtype=float))
+        if len(vals) != len(ci.rows):
+            raise ValueError("dimension mismatch")
+        for r, v in zip(ci.rows, vals):
+            if v is None:
+                self._dual_start.pop((ci.kind, r), None)
+            else:
+                self._dual_start[(ci.kind, r)] = -ci.flip * float(v)     # constraint_dual: d = flip * -(dual row)
+
+    def constraint_dual_start(self, ci):
+        if ci.kind not in ("zeros", "nonpos") or not ci.rows:
+            raise TypeError("ConstraintDualStart: only for constraints the model maps to rows")
+        d = [self._dual_start.get((ci.kind, r)) for r in ci.rows]
+        if any(v is None for v in d):
+            return None
+        d = -ci.flip * np.array(d)
+        return float(d[0]) if ci.scalar else d
+
+    def _shape(self):
+        return (self.nvar, len(self._zeros), len(self._nonpos), tuple(map(tuple, self._psd)), tuple(map(tuple, self._soc)))
+
+    def start_values(self, warm=False):
+        """The start dictionary optimize hands to the optimizer (None: a cold solve): with warm = True the model's last raw
+        result -- its factors when it has them -- when n, p, m and the cones are unchanged, overlaid with the start values
+        set on variables and constraints.  Without a previous result, variables and rows without a start value start at 0.
+        A PSD cone that holds a variable with a start value starts from its entries, not from factors."""
+        from . import binding
+        st = {}
+        if warm and self._last is not None and self._last[0] == self._shape():
+            st = binding.start_from_result(self._last[1])
+        if self._primal_start:
+            x = np.zeros(self.nvar) if st.get("primal") is None else st["primal"]
+            for v, val in self._primal_start.items():
+                x[v - 1] = val
+            st["primal"] = x
+            if st.get("factors") is not None:
+                st["factors"] = [None if any(int(v) in self._primal_start for v in cone) else f
+                                 for cone, f in zip(self._psd, st["factors"])]
+        for kind, key, cnt in (("zeros", "dual_eq", len(self._zeros)), ("nonpos", "dual_in", len(self._nonpos))):
+            rows = {r: v for (k, r), v in self._dual_start.items() if k == kind}
+            if rows:
+                y = np.zeros(cnt) if st.get(key) is None else st[key]
+                for r, v in rows.items():
+                    y[r] = v
+                st[key] = y
+        return st or None
+
+    def optimize(self, warm=False, **kw):
+        """warm = True: start from the model's last result (start_values) and keep this solve's factors for the next one
+        (factors=True unless the caller says otherwise).  Start values set on variables / constraints are used either way."""
+        if "start" not in kw:
+            kw["start"] = self.start_values(warm)
+        if warm:
+            kw.setdefault("factors", True)
+        sol = self.optimizer.optimize(self.problem(), **kw)
+        self._last = (self._shape(), sol)
+        return sol
 
     # -- attributes (src/MOI_wrapper.jl:84-139)
     def set(self, name, value):

@@ -66,8 +66,11 @@ class Optimizer:
     # -- _optimize!
     def optimize(self, problem, eig_resid=None, trace_capacity=0, reduce=None, coupling=None, index_base=0,
                  nccl_comm=None, resume=None, capture_iteration=None, shards=None, device_ids=None, owners=None,
-                 soc_owners=None, free_owners=None, factors=False):
-        """factors=True | {cone: cap}: the low-rank factors of the PSD solution come back with the result
+                 soc_owners=None, free_owners=None, factors=False, start=None):
+        """start: warm start (binding.solve: proxsdp_hip_solve_from) -- a dict (primal, dual_eq, dual_in, factors,
+        target_rank, primal_step, beta; all in the units of a result) or a previous result of this optimizer; combines with
+        factors=, not with shards=k, the state seam or a shard.
+        factors=True | {cone: cap}: the low-rank factors of the PSD solution come back with the result
         (binding.solve: proxsdp_hip_solve_factored; `sol.psd_factors`, constraint_primal_psd_factor); not with shards=k.
         shards=k: the block-sharded solve from one call (binding.solve_sharded_inprocess) -- the library splits the model
         into k shards and runs them as host threads of this process, shard s on device_ids[s] (default: all on
@@ -80,13 +83,15 @@ class Optimizer:
                 raise ValueError("shards=...: the model must be whole (no reduce / coupling / nccl_comm) and there is no state seam")
             if factors is not False and factors is not None:
                 raise ValueError("shards=...: the block-sharded solve does not return factors")
+            if start is not None:
+                raise ValueError("shards=...: the block-sharded solve has no warm start")
             sol, self.shard_stats = binding.solve_sharded_inprocess(
                 problem, shards, device_ids=device_ids, owners=owners, soc_owners=soc_owners, free_owners=free_owners,
                 options=self.options, trace_capacity=trace_capacity, eig_resid=eig_resid, index_base=index_base)
         else:
             sol = binding.solve(problem, self.options, eig_resid=eig_resid, trace_capacity=trace_capacity,
                                 reduce=reduce, coupling=coupling, index_base=index_base, nccl_comm=nccl_comm,
-                                resume=resume, capture_iteration=capture_iteration, factors=factors)
+                                resume=resume, capture_iteration=capture_iteration, factors=factors, start=start)
         sign = -1.0 if problem.max_sense else 1.0          # :336-337
         sol.objval = sign * sol.objval + problem.objective_constant
         sol.dual_objval = sign * sol.dual_objval + problem.objective_constant
