@@ -62,14 +62,7 @@ struct Engine {
     }
     void set_resid(const double* resid) {
         proxsdp::EigWork& W = S.eig[0];
-        W.resid_host.assign(W.npad, 0.0);
-        if (resid) std::copy(resid, resid + W.n, W.resid_host.begin());
-        else proxsdp::start_vector(W.n, (uint64_t)S.opt.eigsolver_resid_seed,
-                                   S.opt.eigsolver == 1 ? S.opt.arpack_resid_init : S.opt.krylovkit_resid_init,
-                                   W.resid_host.data());
-        double nr = proxsdp::norm2(W.resid_host.data(), W.n);
-        if (!(nr > 0.0)) throw std::invalid_argument("Lanczos start vector has zero norm");
-        for (int i = 0; i < W.n; ++i) W.resid_host[i] /= nr;
+        S.lanczos_start_vector(W, resid);
         W.resid.upload(W.resid_host.data(), W.npad, S.stream);
         PX_HIP(hipStreamSynchronize(S.stream));
     }
@@ -214,10 +207,8 @@ static void check_factors_arg(const proxsdp_problem* prob, const proxsdp_result*
         for (int64_t k = 0; k < fac->n_psd; ++k) {
             const int64_t len = prob->psd_ptr[k + 1] - prob->psd_ptr[k];
             if (len <= 0) throw std::invalid_argument("empty PSD cone");
-            int64_t side = (int64_t)((std::sqrt(8.0 * (double)len + 1.0) - 1.0) / 2.0);
-            while (side * (side + 1) / 2 < len) ++side;
-            while (side * (side + 1) / 2 > len) --side;
-            if (side * (side + 1) / 2 != len) throw std::invalid_argument("PSD cone length is not triangular");
+            const int64_t side = proxsdp::psd_side(len);
+            if (side < 0) throw std::invalid_argument("PSD cone length is not triangular");
             const int64_t cap = fac->cap[k];
             if (cap < 0) throw std::invalid_argument("proxsdp_psd_factors.cap is negative");
             any = any || cap > 0;
@@ -260,10 +251,8 @@ static void check_start_arg(const proxsdp_problem* prob, const proxsdp_start* st
     for (int64_t k = 0; k < st->n_psd; ++k) {
         const int64_t len = prob->psd_ptr[k + 1] - prob->psd_ptr[k];
         if (len <= 0) throw std::invalid_argument("empty PSD cone");
-        int64_t side = (int64_t)((std::sqrt(8.0 * (double)len + 1.0) - 1.0) / 2.0);
-        while (side * (side + 1) / 2 < len) ++side;
-        while (side * (side + 1) / 2 > len) --side;
-        if (side * (side + 1) / 2 != len) throw std::invalid_argument("PSD cone length is not triangular");
+        const int64_t side = proxsdp::psd_side(len);
+        if (side < 0) throw std::invalid_argument("PSD cone length is not triangular");
         const int64_t r = st->rank[k];
         if (r < -1 || r > side) throw std::invalid_argument("proxsdp_start.rank must be -1 .. side");
         if (r <= 0) continue;
@@ -276,8 +265,7 @@ static void check_start_arg(const proxsdp_problem* prob, const proxsdp_start* st
     for (int64_t k = 0; k < st->n_psd; ++k) {
         const int64_t r = st->rank[k];
         if (r <= 0) continue;
-        const int64_t len = prob->psd_ptr[k + 1] - prob->psd_ptr[k];
-        const int64_t side = (int64_t)std::llround((std::sqrt(8.0 * (double)len + 1.0) - 1.0) / 2.0);
+        const int64_t side = proxsdp::psd_side(prob->psd_ptr[k + 1] - prob->psd_ptr[k]);   // (triangular: checked above)
         if (!all_finite(st->vectors + st->vec_ptr[k], side * r) || !all_finite(st->values + st->val_ptr[k], r))
             throw std::invalid_argument("proxsdp_start: non-finite factor entry");
         for (int64_t j = 0; j < r; ++j)
@@ -708,17 +696,8 @@ int proxsdp_hip_symv_packed(const double* packed, int64_t n, const double* v, do
         W.w.download(y, n, S.stream);
         PX_HIP(hipStreamSynchronize(S.stream));
         if (repeat > 0 && ms) {
-            hipEvent_t a, b;
-            PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
             for (int i = 0; i < 3; ++i) S.launch_symv(W, x.p, vd.p, false);
-            PX_HIP(hipEventRecord(a, S.stream));
-            for (int i = 0; i < repeat; ++i) S.launch_symv(W, x.p, vd.p, false);
-            PX_HIP(hipEventRecord(b, S.stream));
-            PX_HIP(hipEventSynchronize(b));
-            float t = 0.f;
-            PX_HIP(hipEventElapsedTime(&t, a, b));
-            *ms = (double)t / repeat;
-            (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+            *ms = proxsdp::time_launches(S.stream, repeat, [&]() { S.launch_symv(W, x.p, vd.p, false); });
         }
         return 0;
     });
@@ -747,16 +726,7 @@ int proxsdp_hip_reconstruct_kernel(const double* Z, const double* lambda, int64_
         x.download(packed_out, N, S.stream);
         PX_HIP(hipStreamSynchronize(S.stream));
         if (repeat > 0 && ms) {
-            hipEvent_t a, b;
-            PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
-            PX_HIP(hipEventRecord(a, S.stream));
-            for (int i = 0; i < repeat; ++i) S.launch_reconstruct(W, Zd.p, (int)n, ld.p, r, x.p);
-            PX_HIP(hipEventRecord(b, S.stream));
-            PX_HIP(hipEventSynchronize(b));
-            float t = 0.f;
-            PX_HIP(hipEventElapsedTime(&t, a, b));
-            *ms = (double)t / repeat;
-            (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+            *ms = proxsdp::time_launches(S.stream, repeat, [&]() { S.launch_reconstruct(W, Zd.p, (int)n, ld.p, r, x.p); });
         }
         return 0;
     });
@@ -787,19 +757,11 @@ int proxsdp_hip_factor_residual_kernel(const double* packed, int64_t n, const do
         if (repeat > 0 && ms) {
             const int nt = proxsdp::ceil_div((int)n, proxsdp::dev::TILE);
             const int grid = 8 * proxsdp::ceil_div(nt * (nt + 1) / 2, 8);
-            hipEvent_t a, b;
-            PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
-            PX_HIP(hipEventRecord(a, S.stream));
-            for (int i = 0; i < repeat; ++i)
+            *ms = proxsdp::time_launches(S.stream, repeat, [&]() {
                 hipLaunchKernelGGL(proxsdp::dev::k_factor_residual, dim3(grid), dim3(proxsdp::dev::TPB), 0, S.stream,
                                    (const double*)x.p, (int)n, (const double*)Vd.p, (int)ldv, (const double*)ld.p, (int)r,
                                    S.fac_part.p);
-            PX_HIP(hipEventRecord(b, S.stream));
-            PX_HIP(hipEventSynchronize(b));
-            float t = 0.f;
-            PX_HIP(hipEventElapsedTime(&t, a, b));
-            *ms = (double)t / repeat;
-            (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+            });
             // what comes back is the LAST launch's: a kernel that wrote to the block would show here
             S.factor_residual(x.p, (int)n, Vd.p, (int)ldv, ld.p, r, *resid2, *xnorm2);
         }

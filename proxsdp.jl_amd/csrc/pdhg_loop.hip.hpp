@@ -83,7 +83,7 @@ inline void Solver::project_blocks(const std::vector<int>& blocks, const double*
             if (cnt < 2) { rest.push_back(cand[i0]); i0 = i1; continue; }
             size_t ng = (cnt + dev::LZB_MAX - 1) / dev::LZB_MAX;
             const int want = opt.block_batch_groups < 0 ? 1 : (int)opt.block_batch_groups;   // (auto = 1: measured, see the header)
-            if (parallel_blocks && want >= 2 && cnt >= 4) ng = std::max<size_t>(ng, std::min<size_t>((size_t)want, cnt / 2));
+            if (parallel_blocks() && want >= 2 && cnt >= 4) ng = std::max<size_t>(ng, std::min<size_t>((size_t)want, cnt / 2));
             for (size_t q = 0; q < ng; ++q) {
                 const size_t a = i0 + q * cnt / ng, b = i0 + (q + 1) * cnt / ng;
                 groups.emplace_back(cand.begin() + a, cand.begin() + b);
@@ -106,7 +106,7 @@ inline void Solver::project_blocks(const std::vector<int>& blocks, const double*
     // (groups run side by side only ON REQUEST -- block_batch_groups >= 2; a model with more than LZB_MAX equal-side
     // blocks splits into several groups by necessity, and those run one after the other as in rounds 3-4: auto = sequential)
     const int want_groups = opt.block_batch_groups < 0 ? 1 : (int)opt.block_batch_groups;
-    bool leaders_have_streams = parallel_blocks && groups.size() >= 2 && want_groups >= 2;
+    bool leaders_have_streams = parallel_blocks() && groups.size() >= 2 && want_groups >= 2;
     for (const std::vector<int>& g : groups) leaders_have_streams = leaders_have_streams && eig[g[0]].stream != nullptr;
     if (leaders_have_streams) {
         std::vector<int> leaders;
@@ -1240,9 +1240,9 @@ inline void Solver::setup_dense() {
 // bracketing is free); harvested after the iteration's last synchronisation
 inline void Solver::dense_ev_begin() {
     if (dense_ev_used == dense_ev.size()) {
-        hipEvent_t a, b;
-        PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
-        dense_ev.emplace_back(a, b);
+        Event a, b;
+        a.create(); b.create();
+        dense_ev.emplace_back(std::move(a), std::move(b));
     }
     PX_HIP(hipEventRecord(dense_ev[dense_ev_used].first, stream));
 }
@@ -1461,20 +1461,12 @@ inline void Solver::test_project(int idx, double* xp, int tr) {
     project_block(idx, xp - P.blocks[idx].off, xp - P.blocks[idx].off, false);
 }
 // the iterate's buffers as the "Init" section allocates them (x, M'y: n; y, Mx: Q; two of each), zeroed
-inline void Solver::test_alloc_iterate() {
-    for (int k = 0; k < 2; ++k) {
-        xbuf[k].alloc(P.n); Mtybuf[k].alloc(P.n);
-        ybuf[k].alloc(std::max<int64_t>(P.Q, 1)); Mxbuf[k].alloc(std::max<int64_t>(P.Q, 1));
-        xbuf[k].zero(stream); Mtybuf[k].zero(stream); ybuf[k].zero(stream); Mxbuf[k].zero(stream);
-    }
-    xc = yc = mxc = mtyc = 0;
-}
 inline void Solver::test_spmv(bool transpose, const double* in, double* out) {
     setup_device();
     upload_sparse_operator();
     if (transpose) {
         // M'y as the linesearch computes it: ONE plain candidate against a zero M'y_old
-        test_alloc_iterate();
+        alloc_iterate_pairs();
         use_support = false;
         alloc_candidates();
         ycand_d.upload(in, P.Q, stream);
@@ -1503,7 +1495,7 @@ inline void Solver::test_trial_batch(proxsdp_trial_batch& t) {
     P.p = t.p; P.m = Q - t.p;
     setup_device();
     upload_sparse_operator();
-    test_alloc_iterate();
+    alloc_iterate_pairs();
     c_d.alloc(n); c_d.upload(P.c.data(), n, stream);
     bh_d.alloc(Q); bh_d.upload(t.bh, Q, stream);
     if (t.roww) { roww_d.alloc(Q); roww_d.upload(t.roww, Q, stream); }
@@ -1791,9 +1783,8 @@ inline void Solver::write_capture() {
     s.ints[3] = 1;
 }
 
-// chambolle_pock (pdhg.jl:1-530)
-inline void Solver::run() {
-    const double t_init0 = now_s();
+// ------------------------------------------------------------------ chambolle_pock (pdhg.jl:1-530) in phases
+inline void Solver::check_run_options() {
     if (sharded()) reject_for_shard(false, !opt.approx_norm, false);
     if (P.n <= 0) throw std::invalid_argument("problem has no variables");
     if (opt.convergence_window <= 0) throw std::invalid_argument("convergence_window must be positive");
@@ -1805,6 +1796,10 @@ inline void Solver::run() {
         const char* e = std::getenv("PROXSDP_HIP_FAULT_INJECTION");
         if (!(e && e[0] == '1')) throw std::invalid_argument("debug_fail_iteration needs PROXSDP_HIP_FAULT_INJECTION=1 in the environment (test switch)");
     }
+}
+
+// Params and Residuals of the reference at their initial values (host state only)
+inline void Solver::init_parameters() {
     theta = opt.initial_theta; adapt_level = opt.initial_adapt_level; beta = opt.initial_beta;
     const int window = opt.convergence_window;
     const size_t nb = P.blocks.size();
@@ -1812,37 +1807,38 @@ inline void Solver::run() {
     for (size_t idx = 0; idx < nb; ++idx)               // 2 in the reference (pdhg.jl:19-20)
         target_rank[idx] = std::min<long long>(std::max(opt.initial_target_rank, 1), P.blocks[idx].n);
     time_limit = opt.time_limit;
-    {   // global constants (sums over shards of a block-sharded solve; local values otherwise)
-        double pw = (double)P.p, mw = (double)P.m, nb2 = P.norm_b * P.norm_b, nh2 = P.norm_h * P.norm_h;
-        for (size_t k = 0; k < coup_rows.size(); ++k) {          // a coupling row counts on its owner only
-            if (coup_owned[k]) continue;
-            const int r = coup_rows[k];
-            if (r < P.p) { pw -= 1.0; nb2 -= P.b_orig[r] * P.b_orig[r]; }
-            else { mw -= 1.0; nh2 -= P.h_orig[r - P.p] * P.h_orig[r - P.p]; }
-        }
-        std::vector<double> sums = {(double)P.n, pw, mw, std::max(nb2, 0.0), std::max(nh2, 0.0),
-                                    P.norm_c * P.norm_c, P.frob * P.frob};
-        std::vector<double> maxs = {(nb > 0 || !P.socs.empty()) ? 1.0 : 0.0};
-        reduce(sums, maxs);
-        g_n = sums[0]; g_p = sums[1]; g_m = sums[2]; g_Q = g_p + g_m;
-        g_norm_b = sharded() ? std::sqrt(sums[3]) : P.norm_b;
-        g_norm_h = sharded() ? std::sqrt(sums[4]) : P.norm_h;
-        g_norm_c = sharded() ? std::sqrt(sums[5]) : P.norm_c;
-        g_frob = sharded() ? std::sqrt(sums[6]) : P.frob;
-        g_conic = maxs[0] > 0.5;
-    }
-    // (a block-sharded solve chooses its vector path per shard: the library-only knob support_path is overridden below;
-    //  check_dual_feas and line_search_flag = false are served on both)
-    if (opt.max_iter <= 0) max_iter_local = g_conic ? opt.max_iter_conic : opt.max_iter_lp;
-    else max_iter_local = opt.max_iter;
     ada_count = 0;
     h_gap.init(2 * window); h_pobj.init(2 * window); h_dobj.init(2 * window); h_feas.init(2 * window);
     h_pres.init(2 * window); h_dres.init(2 * window); h_comb.init(2 * window);
+}
 
-    // ---- device state ("Init", pdhg.jl:54-142)
-    setup_device();
-    setup_dense_scaling();                               // (equilibration on a dense A: finishes what prepare() deferred)
-    b_host = P.b; h_host = P.h; c_host = P.c;
+// global constants (sums over shards of a block-sharded solve; local values otherwise), and the iteration limit they choose
+inline void Solver::reduce_global_constants() {
+    double pw = (double)P.p, mw = (double)P.m, nb2 = P.norm_b * P.norm_b, nh2 = P.norm_h * P.norm_h;
+    for (size_t k = 0; k < coup_rows.size(); ++k) {          // a coupling row counts on its owner only
+        if (coup_owned[k]) continue;
+        const int r = coup_rows[k];
+        if (r < P.p) { pw -= 1.0; nb2 -= P.b_orig[r] * P.b_orig[r]; }
+        else { mw -= 1.0; nh2 -= P.h_orig[r - P.p] * P.h_orig[r - P.p]; }
+    }
+    std::vector<double> sums = {(double)P.n, pw, mw, std::max(nb2, 0.0), std::max(nh2, 0.0),
+                                P.norm_c * P.norm_c, P.frob * P.frob};
+    std::vector<double> maxs = {(!P.blocks.empty() || !P.socs.empty()) ? 1.0 : 0.0};
+    reduce(sums, maxs);
+    g_n = sums[0]; g_p = sums[1]; g_m = sums[2]; g_Q = g_p + g_m;
+    g_norm_b = sharded() ? std::sqrt(sums[3]) : P.norm_b;
+    g_norm_h = sharded() ? std::sqrt(sums[4]) : P.norm_h;
+    g_norm_c = sharded() ? std::sqrt(sums[5]) : P.norm_c;
+    g_frob = sharded() ? std::sqrt(sums[6]) : P.frob;
+    g_conic = maxs[0] > 0.5;
+    // (a block-sharded solve chooses its vector path per shard: the library-only knob support_path is overridden in
+    //  classify_blocks; check_dual_feas and line_search_flag = false are served on both)
+    if (opt.max_iter <= 0) max_iter_local = g_conic ? opt.max_iter_conic : opt.max_iter_lp;
+    else max_iter_local = opt.max_iter;
+}
+
+// the threads that help from the host side: rocSOLVER's loader (opt-in) and the QL helpers
+inline void Solver::start_host_helpers() {
     bool big_block = false;
     for (const BlockInfo& B : P.blocks) big_block = big_block || B.n >= 256;
     // opt-in only: measured on MI355X/ROCm 7.2, loading rocSOLVER's code objects from a second
@@ -1850,11 +1846,22 @@ inline void Solver::run() {
     // exit path pays the one-off ~3 s initialisation itself in a cold process
     if (big_block && opt.rocsolver_warmup == 1) start_rocsolver_warmup();
     if (opt.host_eig_threads > 0) QlPool::get().ensure(opt.host_eig_threads);
+}
+
+// the four ping-pong pairs of the iterate, zero (also what the kernel-level test entries start from: they upload their own
+// c and [b; h], so the rest of alloc_iterate is not theirs)
+inline void Solver::alloc_iterate_pairs() {
     for (int k = 0; k < 2; ++k) {
         xbuf[k].alloc(P.n); Mtybuf[k].alloc(P.n);
         ybuf[k].alloc(std::max<int64_t>(P.Q, 1)); Mxbuf[k].alloc(std::max<int64_t>(P.Q, 1));
         xbuf[k].zero(stream); Mtybuf[k].zero(stream); ybuf[k].zero(stream); Mxbuf[k].zero(stream);
     }
+    xc = yc = mxc = mtyc = 0;
+}
+
+// x, y, M x, M'y; c and [b; h]; the coupling rows of a block-sharded solve; the reduction scratch
+inline void Solver::alloc_iterate() {
+    alloc_iterate_pairs();
     c_d.alloc(P.n); c_d.upload(P.c.data(), P.n, stream);
     bh_d.alloc(std::max<int64_t>(P.Q, 1));
     {
@@ -1875,7 +1882,12 @@ inline void Solver::run() {
     }
     part.alloc((size_t)NQ * PSTRIDE); part.zero(stream);
     scal.alloc(NQ); scal.zero(stream);
-    upload_sparse_operator();
+}
+
+// the PSD blocks by the engine that projects them -- 1x1 (clamped), small (one batched launch), large (an eigensolver each)
+// -- with every eigensolver block's Lanczos workspace and start vector; a shard's vector path
+inline void Solver::classify_blocks() {
+    const size_t nb = P.blocks.size();
     eig.resize(nb);
     // small blocks by the sign function in one launch: auto (and small_block_batch = 2) unless the tiled sign projection is
     // switched off or the solve asks for tolerances below that engine's 1e-10-of-the-scale floor (as full_eig_by_sign)
@@ -1887,92 +1899,92 @@ inline void Solver::run() {
     // the support path (at least one PSD block, no SOC, no 1x1 block -- setup_support's own conditions) runs it, as every
     // sharded solve used to, with its small blocks not batched; any other shard runs the general path with the small-block
     // launches of a single-process solve.  Shards of one solve may differ: only reduced scalars steer the iteration.
-    bool shard_general = false;
+    shard_general = false;
     if (sharded()) {
         shard_general = P.blocks.empty() || !P.socs.empty();
         for (const BlockInfo& B : P.blocks) shard_general = shard_general || B.n == 1;
         opt.support_path = shard_general ? 0 : 1;
         general_row_weights = shard_general;
     }
-    {
+    const double* ur = user_resid;
+    for (size_t idx = 0; idx < nb; ++idx) {
+        const BlockInfo& B = P.blocks[idx];
+        if (B.n == 1) { one_blocks.push_back((int)idx); if (ur) ur += 1; continue; }
+        EigWork& W = eig[idx];
+        big_blocks.push_back((int)idx);
+        // side 2..64 and never on the Krylov path: ONE launch for all of them (dense vector path): batched Jacobi
+        // (auto: side 2 only -- measured: 80 / 140 / 370 us per iteration at side 3 / 8 / 16 where the sign kernel stays at 60; at side 22 the
+        // single-workgroup Jacobi takes 950 us, at side 50 5.9 ms against
+        // 1.1 ms for one rocSOLVER call; two blocks of side 10 and 5: 1.4x faster batched; seven of side 2: 6.4x) and,
+        // round 5, the one-workgroup LDS-resident sign projection (small_sign.hip.hpp) for sides 3 .. 64
+        if (opt.small_block_batch != 0 && B.n <= (small_sign ? std::max(small_jacobi_max, std::min(64, small_sign_cap)) : (opt.small_block_batch > 0 ? 64 : 32)) &&
+            B.n <= opt.min_size_krylov_eigs && (!sharded() || shard_general))
+            small_blocks.push_back((int)idx);
+        else
+            large_blocks.push_back((int)idx);
+        // Krylov workspace: the largest target rank the Krylov path may see, and room for
+        // full_eig!-by-Lanczos (up to 94 pairs) on blocks that can take it
+        int max_nev = std::min<int>(std::max<int>(opt.max_target_rank_krylov_eigs, 2), B.n);
+        if (opt.full_eig_lanczos != 0 && B.n > opt.min_size_krylov_eigs && B.n >= 400)
+            max_nev = std::max(max_nev, std::min(94, B.n / 4));
+        alloc_eigwork(W, B.n, max_nev);
+        lanczos_start_vector(W, ur);
+        if (ur) ur += B.n;
+        W.resid.upload(W.resid_host.data(), W.npad, stream);
+    }
+    if (small_blocks.size() < 2 && opt.small_block_batch < 0 && !small_sign) {   // auto, Jacobi only: a batch needs several blocks
+        large_blocks = big_blocks; small_blocks.clear();
+    }
+}
+
+// several eigensolver-sized blocks: project them concurrently, one worker thread and one
+// stream per block (the per-block Lanczos chains are launch-latency-bound, so they overlap
+// almost perfectly: MIMO n=512 x 8 on one GPU).  options.block_threads = 0 disables.
+inline void Solver::start_block_workers() {
+    int nthreads = opt.block_threads < 0 ? 8 : std::min(opt.block_threads, 64);
+    // (blocks handled by the batched small-block kernel need no worker / stream of their own)
+    const std::vector<int>& pool_blocks = small_blocks.empty() ? big_blocks : large_blocks;
+    nthreads = std::min<int>(nthreads, (int)pool_blocks.size());
+    if (nthreads < 2) return;
+    for (int idx : pool_blocks) {
+        eig[idx].stream.create();
+        eig[idx].done.create(hipEventDisableTiming);
+    }
+    ev_main.create(hipEventDisableTiming);
+    PX_HIP(hipStreamSynchronize(stream));           // workspace zero-fills precede any block-stream work
+    const int dev_id = opt.device_id;
+    block_pool.reset(new BlockPool(nthreads, [dev_id]() { (void)hipSetDevice(dev_id); }));
+}
+
+// the batched small-block launch: offsets, sides and rank records of its blocks, and the kernels' LDS grants
+inline void Solver::setup_small_batch() {
+    if (small_blocks.empty()) return;
+    std::vector<long long> so; std::vector<int> ss;
+    for (int idx : small_blocks) { so.push_back(P.blocks[idx].off); ss.push_back(P.blocks[idx].n); small_maxn = std::max(small_maxn, P.blocks[idx].n); }
+    small_off.alloc(so.size()); small_side.alloc(ss.size()); small_rank.alloc(3 * ss.size() + 2); small_rank.zero(stream);   // [rank | npos] per block, then the sign kernel's cumulative [pass, fail] counters
+    small_off.upload(so.data(), so.size(), stream); small_side.upload(ss.data(), ss.size(), stream);
+    small_rank_host.alloc(2 * ss.size() + 2);      // (ints: rank | positive count | schedule-test outcome per block)
+    small_sign_maxn = 0;
+    int jac_maxn = 0;
+    for (int sd : ss) { if (sd > small_jacobi_max) small_sign_maxn = std::max(small_sign_maxn, sd); else jac_maxn = std::max(jac_maxn, sd); }
+    const size_t lds = ((size_t)2 * jac_maxn * (jac_maxn | 1) + 64) * sizeof(double) + 64 * sizeof(int);
+    if (lds > 48 * 1024)
+        PX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dev::k_small_psd_project),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (small_sign_maxn > 0 && dev::small_sign_lds_bytes(small_sign_maxn) > 48 * 1024)
+        PX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dev::k_small_sign_project),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dev::small_sign_lds_bytes(small_sign_maxn)));
+    PX_HIP(hipStreamSynchronize(stream));
+}
+
+// offsets of the 1x1 PSD blocks (clamped by one launch) and of the second-order cones
+inline void Solver::setup_soc() {
+    if (!one_blocks.empty()) {
         std::vector<long long> offs;
-        const double* ur = user_resid;
-        for (size_t idx = 0; idx < nb; ++idx) {
-            const BlockInfo& B = P.blocks[idx];
-            if (B.n == 1) { one_blocks.push_back((int)idx); offs.push_back(B.off); if (ur) ur += 1; continue; }
-            EigWork& W = eig[idx];
-            big_blocks.push_back((int)idx);
-            // side 2..64 and never on the Krylov path: ONE launch for all of them (dense vector path): batched Jacobi
-            // (auto: side 2 only -- measured: 80 / 140 / 370 us per iteration at side 3 / 8 / 16 where the sign kernel stays at 60; at side 22 the
-            // single-workgroup Jacobi takes 950 us, at side 50 5.9 ms against
-            // 1.1 ms for one rocSOLVER call; two blocks of side 10 and 5: 1.4x faster batched; seven of side 2: 6.4x) and,
-            // round 5, the one-workgroup LDS-resident sign projection (small_sign.hip.hpp) for sides 3 .. 64
-            if (opt.small_block_batch != 0 && B.n <= (small_sign ? std::max(small_jacobi_max, std::min(64, small_sign_cap)) : (opt.small_block_batch > 0 ? 64 : 32)) &&
-                B.n <= opt.min_size_krylov_eigs && (!sharded() || shard_general))
-                small_blocks.push_back((int)idx);
-            else
-                large_blocks.push_back((int)idx);
-            // Krylov workspace: the largest target rank the Krylov path may see, and room for
-            // full_eig!-by-Lanczos (up to 94 pairs) on blocks that can take it
-            int max_nev = std::min<int>(std::max<int>(opt.max_target_rank_krylov_eigs, 2), B.n);
-            if (opt.full_eig_lanczos != 0 && B.n > opt.min_size_krylov_eigs && B.n >= 400)
-                max_nev = std::max(max_nev, std::min(94, B.n / 4));
-            alloc_eigwork(W, B.n, max_nev);
-            W.resid_host.resize(W.npad, 0.0);
-            if (ur) { std::copy(ur, ur + B.n, W.resid_host.begin()); ur += B.n; }
-            else start_vector(B.n, (uint64_t)opt.eigsolver_resid_seed,
-                              opt.eigsolver == 1 ? opt.arpack_resid_init : opt.krylovkit_resid_init,
-                              W.resid_host.data());
-            double nr = norm2(W.resid_host.data(), B.n);        // KrylovKit: v = x0 / norm(x0)
-            if (!(nr > 0.0)) throw std::invalid_argument("Lanczos start vector has zero norm");
-            for (int i = 0; i < B.n; ++i) W.resid_host[i] /= nr;
-            W.resid.upload(W.resid_host.data(), W.npad, stream);
-        }
-        if (small_blocks.size() < 2 && opt.small_block_batch < 0 && !small_sign) {   // auto, Jacobi only: a batch needs several blocks
-            large_blocks = big_blocks; small_blocks.clear();
-        }
-        // several eigensolver-sized blocks: project them concurrently, one worker thread and one
-        // stream per block (the per-block Lanczos chains are launch-latency-bound, so they overlap
-        // almost perfectly: MIMO n=512 x 8 on one GPU).  options.block_threads = 0 disables.
-        {
-            int nthreads = opt.block_threads < 0 ? 8 : std::min(opt.block_threads, 64);
-            // (blocks handled by the batched small-block kernel need no worker / stream of their own)
-            const std::vector<int>& pool_blocks = small_blocks.empty() ? big_blocks : large_blocks;
-            nthreads = std::min<int>(nthreads, (int)pool_blocks.size());
-            if (nthreads >= 2) {
-                for (int idx : pool_blocks) {
-                    PX_HIP(hipStreamCreate(&eig[idx].stream));
-                    PX_HIP(hipEventCreateWithFlags(&eig[idx].done, hipEventDisableTiming));
-                }
-                PX_HIP(hipEventCreateWithFlags(&ev_main, hipEventDisableTiming));
-                PX_HIP(hipStreamSynchronize(stream));           // workspace zero-fills precede any block-stream work
-                start_workers(nthreads);
-                parallel_blocks = true;
-            }
-        }
-        if (!small_blocks.empty()) {
-            std::vector<long long> so; std::vector<int> ss;
-            for (int idx : small_blocks) { so.push_back(P.blocks[idx].off); ss.push_back(P.blocks[idx].n); small_maxn = std::max(small_maxn, P.blocks[idx].n); }
-            small_off.alloc(so.size()); small_side.alloc(ss.size()); small_rank.alloc(3 * ss.size() + 2); small_rank.zero(stream);   // [rank | npos] per block, then the sign kernel's cumulative [pass, fail] counters
-            small_off.upload(so.data(), so.size(), stream); small_side.upload(ss.data(), ss.size(), stream);
-            small_rank_host.alloc(2 * ss.size() + 2);      // (ints: rank | positive count | schedule-test outcome per block)
-            small_sign_maxn = 0;
-            int jac_maxn = 0;
-            for (int sd : ss) { if (sd > small_jacobi_max) small_sign_maxn = std::max(small_sign_maxn, sd); else jac_maxn = std::max(jac_maxn, sd); }
-            const size_t lds = ((size_t)2 * jac_maxn * (jac_maxn | 1) + 64) * sizeof(double) + 64 * sizeof(int);
-            if (lds > 48 * 1024)
-                PX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dev::k_small_psd_project),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (small_sign_maxn > 0 && dev::small_sign_lds_bytes(small_sign_maxn) > 48 * 1024)
-                PX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dev::k_small_sign_project),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)dev::small_sign_lds_bytes(small_sign_maxn)));
-            PX_HIP(hipStreamSynchronize(stream));
-        }
-        if (!offs.empty()) {
-            one_off.alloc(offs.size()); one_min.alloc(offs.size());
-            one_off.upload(offs.data(), offs.size(), stream);
-            PX_HIP(hipStreamSynchronize(stream));
-        }
+        for (int idx : one_blocks) offs.push_back(P.blocks[idx].off);
+        one_off.alloc(offs.size()); one_min.alloc(offs.size());
+        one_off.upload(offs.data(), offs.size(), stream);
+        PX_HIP(hipStreamSynchronize(stream));
     }
     if (!P.socs.empty()) {
         std::vector<long long> so; std::vector<int> sl;
@@ -1981,269 +1993,264 @@ inline void Solver::run() {
         soc_off.upload(so.data(), so.size(), stream); soc_len.upload(sl.data(), sl.size(), stream);
         PX_HIP(hipStreamSynchronize(stream));
     }
-    if (P.dense()) opt.support_path = 0;                 // every column of a dense M is in the support
-    setup_support();                                     // (a block-sharded solve chose opt.support_path above)
-    setup_dense();
-    alloc_candidates();
-    if (sharded() && use_support == shard_general)
-        throw std::logic_error("block-sharded solve: the shard's vector path is not the one chosen for it");
+}
+
+// the spectral norm and the steps it gives; advanced initialisation.  False: proxsdp_hip_dense_scaling wanted the norm only
+inline bool Solver::initial_steps() {
     double spectral_norm = g_frob;                       // LinearAlgebra.norm(M), pdhg.jl:121
     if (!opt.approx_norm) {                              // Arpack.svds(M, nsv=1), pdhg.jl:108-119
         if (P.dense()) spectral_norm = spectral_norm_device();
         else spectral_norm = spectral_norm_host(P, [](int K, double* T, double* d) { return symeig_dense(K, T, d, true); });
         sigma_max = spectral_norm;
     }
-    if (init_only) return;
+    if (init_only) return false;
     if (spectral_norm < 1e-10) spectral_norm = 1.0;
     primal_step = 1.0 / spectral_norm;
     primal_step_old = primal_step;
     dual_step = primal_step;
+    std::vector<double> x0;
     if (opt.advanced_initialization) {                   // x = tau*c (pdhg.jl:138-142)
-        std::vector<double> x0(P.n);
+        x0.resize(P.n);
         for (int64_t i = 0; i < P.n; ++i) x0[i] = primal_step * P.c[i];
         xbuf[xc].upload(x0.data(), P.n, stream);
-        PX_HIP(hipStreamSynchronize(stream));
     }
+    PX_HIP(hipStreamSynchronize(stream));                // (the set-up is complete; x0 goes out of scope)
+    return true;
+}
+
+// certificate_infeasibility (pdhg.jl:655-668) / certificate_dual_infeasibility (pdhg.jl:639-653)
+inline void Solver::cert_infeas() {
+    std::fill(c_host.begin(), c_host.end(), 0.0);
+    c_d.zero(stream);
+    if (use_support) cS_d.zero(stream);
+    certificate_parameters();
+}
+inline void Solver::cert_dual_infeas() {
+    std::fill(b_host.begin(), b_host.end(), 0.0);
+    std::fill(h_host.begin(), h_host.end(), 0.0);
+    bh_d.zero(stream);
+    certificate_parameters();
+}
+inline void Solver::snapshot() { cache_solution(P.c_orig); }
+
+// A stop rule fired: record its reason.  True: the loop stops.  False: it goes on -- with certificate search on and no
+// search running yet, the search for a certificate of `kind` starts here (data zeroed, limits raised, the point
+// snapshotted).  With a search already running the rule stops the loop, except in the limit branch (`at_limit`,
+// pdhg.jl:334-382): there a running search neither snapshots nor stops, and the caller re-tests the raised limits.
+inline bool Solver::declare(int reason, const std::string& str, Cert kind, bool at_limit) {
+    stop_reason = reason;
+    stop_reason_string = str;
+    if (opt.certificate_search && !certificate_search) {
+        if (kind == Cert::infeasible) cert_infeas(); else cert_dual_infeas();
+        snapshot();
+        return false;
+    }
+    if (at_limit && opt.certificate_search && certificate_search) return false;
+    return true;
+}
+
+// dual feasibility of the current y against the cost vector `cvec`: the largest over the shards
+inline void Solver::update_dual_feasibility(const std::vector<double>& cvec) {
+    std::vector<double> y(P.Q);
+    ybuf[yc].download(y.data(), P.Q, stream);
     PX_HIP(hipStreamSynchronize(stream));
-    long long k_first = 1;
-    if (resume_state) { apply_resume(); k_first = resume_state->iteration + 1; }
-    if (start) apply_start();
-    if (start_out) { write_start_point(); return; }
-    if (capture_state) { check_state_shape(*capture_state, "capture"); capture_state->ints[3] = 0; }
-    st.init_time = now_s() - t_init0;
+    dual_feasibility = dual_feas_host(y, cvec, nullptr, nullptr, nullptr);
+    if (sharded()) {                                     // every shard tests its own columns: the model's value is the largest
+        std::vector<double> sums, maxs = {dual_feasibility};
+        reduce(sums, maxs);
+        dual_feasibility = maxs[0];
+    }
+}
 
-    auto snapshot = [&]() { cache_solution(P.c_orig); };
-    auto cert_infeas = [&]() {                           // certificate_infeasibility (pdhg.jl:655-668)
-        std::fill(c_host.begin(), c_host.end(), 0.0);
-        c_d.zero(stream);
-        if (use_support) cS_d.zero(stream);
-        certificate_parameters();
-    };
-    auto cert_dual_infeas = [&]() {                      // certificate_dual_infeasibility (pdhg.jl:639-653)
-        std::fill(b_host.begin(), b_host.end(), 0.0);
-        std::fill(h_host.begin(), h_host.end(), 0.0);
-        bh_d.zero(stream);
-        certificate_parameters();
-    };
-    int n_snap = 0;
+// one iteration of the "CP loop" up to its log line (pdhg.jl:145-183)
+inline void Solver::iterate(long long k) {
+    const size_t nb = P.blocks.size();
+    iter = k;
+    lz_matvec_iter = 0; recon_r_iter = 0;
+    const double tp0 = now_s();
+    primal_step_dev();
+    st.t_primal += now_s() - tp0;                    // "primal" section of pdhg.jl:150 (includes t_psd)
+    // (the residual / gap REDUCTIONS ride in the candidates' batch and its read-back -- they are part of t_linesearch;
+    // t_residual counts what is left of compute_residual! / compute_gap!: the host scalars)
+    const double tl0 = now_s();
+    const double* s_acc = linesearch_and_residuals();
+    const double tl1 = now_s();
+    record_residuals(s_acc);
+    st.t_linesearch += tl1 - tl0;
+    st.t_residual += now_s() - tl1;
+    {   // algorithmic bytes of this iteration
+        const double t = (double)last_trials;
+        double bb = 8.0 * (double)P.n * (11.0 + 3.0 * t) + 12.0 * (double)P.nnz * (1.0 + t) +
+                    8.0 * (double)P.Q * (8.0 + 6.0 * t);
+        if (P.dense()) {                             // M x + one M'y pass per candidate batch
+            dense_ev_harvest();
+            bb += 8.0 * (double)P.p * (double)P.n * (double)(st.dense_passes - dense_passes_seen);
+            dense_passes_seen = st.dense_passes;
+        }
+        // per-block L and r are accumulated over blocks in lz_matvec_iter / recon_r_iter;
+        // single-block instances (all BASELINE configs) make this exact
+        if (nb > 0) {
+            const BlockInfo& B0 = P.blocks[0];
+            bb += (8.0 * (double)B0.N + 16.0 * (double)B0.n) * (double)lz_matvec_iter +
+                  8.0 * (double)B0.n * (double)recon_r_iter;
+        }
+        st.algorithmic_bytes += bb;
+    }
+    if (res.trace && res.trace_rows < opt.trace_capacity) {
+        double* row = res.trace + (size_t)res.trace_rows * PROXSDP_TRACE_COLS;
+        row[0] = (double)k; row[1] = h_pobj.at(k); row[2] = h_dobj.at(k); row[3] = h_gap.at(k);
+        row[4] = h_feas.at(k); row[5] = h_pres.at(k); row[6] = h_dres.at(k); row[7] = primal_step;
+        row[8] = beta; row[9] = theta; row[10] = nb ? (double)target_rank[0] : 0.0; row[11] = (double)last_trials;
+        row[12] = now_s() - loop_t0; row[13] = (double)lz_matvec_iter;
+        res.trace_rows++;
+    }
+    if (opt.check_dual_feas && k % opt.check_dual_feas_freq == 0) {
+        std::vector<double> cc(P.c_orig);
+        if (stop_reason == 6) std::fill(cc.begin(), cc.end(), 0.0);
+        update_dual_feasibility(cc);
+    }
+    if (opt.log_verbose && opt.log_freq > 0 && k % opt.log_freq == 0)
+        std::printf("|%9lld| %+.4e %+.4e %.2e %.2e %.2e %.2e %4lld %8.2f\n", k, h_pobj.at(k), h_dobj.at(k),
+                    h_gap.at(k), h_feas.at(k), h_pres.at(k), h_dres.at(k), nb ? target_rank[0] : 0,
+                    now_s() - time0);
+}
 
-    // ---- "CP loop" (pdhg.jl:145-484)
-    const double t_loop0 = now_s();
-    const long long kmax = 2 * max_iter_local;
-    for (long long k = k_first; k <= kmax; ++k) {
-        if (capture_state && k == capture_state->iteration + 1 && k > k_first) write_capture();
-        iter = k;
-        lz_matvec_iter = 0; recon_r_iter = 0;
-        const double tp0 = now_s();
-        primal_step_dev();
-        st.t_primal += now_s() - tp0;                    // "primal" section of pdhg.jl:150 (includes t_psd)
-        // (the residual / gap REDUCTIONS ride in the candidates' batch and its read-back -- they are part of t_linesearch;
-        // t_residual counts what is left of compute_residual! / compute_gap!: the host scalars)
-        const double tl0 = now_s();
-        const double* s_acc = linesearch_and_residuals();
-        const double tl1 = now_s();
-        record_residuals(s_acc);
-        st.t_linesearch += tl1 - tl0;
-        st.t_residual += now_s() - tl1;
-        {   // algorithmic bytes of this iteration
-            const double t = (double)last_trials;
-            double bb = 8.0 * (double)P.n * (11.0 + 3.0 * t) + 12.0 * (double)P.nnz * (1.0 + t) +
-                        8.0 * (double)P.Q * (8.0 + 6.0 * t);
-            if (P.dense()) {                             // M x + one M'y pass per candidate batch
-                dense_ev_harvest();
-                bb += 8.0 * (double)P.p * (double)P.n * (double)(st.dense_passes - dense_passes_seen);
-                dense_passes_seen = st.dense_passes;
-            }
-            for (size_t idx = 0; idx < nb; ++idx) {
-                if (P.blocks[idx].n < 2) continue;
-                // per-block L and r are accumulated over blocks in lz_matvec_iter / recon_r_iter;
-                // single-block instances (all BASELINE configs) make this exact
-                (void)idx;
-            }
-            if (nb > 0) {
-                const BlockInfo& B0 = P.blocks[0];
-                bb += (8.0 * (double)B0.N + 16.0 * (double)B0.n) * (double)lz_matvec_iter +
-                      8.0 * (double)B0.n * (double)recon_r_iter;
-            }
-            st.algorithmic_bytes += bb;
-        }
-        if (res.trace && res.trace_rows < opt.trace_capacity) {
-            double* row = res.trace + (size_t)res.trace_rows * PROXSDP_TRACE_COLS;
-            row[0] = (double)k; row[1] = h_pobj.at(k); row[2] = h_dobj.at(k); row[3] = h_gap.at(k);
-            row[4] = h_feas.at(k); row[5] = h_pres.at(k); row[6] = h_dres.at(k); row[7] = primal_step;
-            row[8] = beta; row[9] = theta; row[10] = nb ? (double)target_rank[0] : 0.0; row[11] = (double)last_trials;
-            row[12] = now_s() - t_loop0; row[13] = (double)lz_matvec_iter;
-            res.trace_rows++;
-        }
-        if (opt.check_dual_feas && k % opt.check_dual_feas_freq == 0) {
-            std::vector<double> y(P.Q);
-            ybuf[yc].download(y.data(), P.Q, stream);
-            PX_HIP(hipStreamSynchronize(stream));
-            std::vector<double> cc(P.c_orig);
-            if (stop_reason == 6) std::fill(cc.begin(), cc.end(), 0.0);
-            dual_feasibility = dual_feas_host(y, cc, nullptr, nullptr, nullptr);
-            if (sharded()) {                             // every shard tests its own columns: the model's value is the largest
-                std::vector<double> sums, maxs = {dual_feasibility};
-                reduce(sums, maxs);
-                dual_feasibility = maxs[0];
-            }
-        }
-        if (opt.log_verbose && opt.log_freq > 0 && k % opt.log_freq == 0)
-            std::printf("|%9lld| %+.4e %+.4e %.2e %.2e %.2e %.2e %4lld %8.2f\n", k, h_pobj.at(k), h_dobj.at(k),
-                        h_gap.at(k), h_feas.at(k), h_pres.at(k), h_dres.at(k), nb ? target_rank[0] : 0,
-                        now_s() - time0);
-        if (iter < certificate_search_min_iter) continue;
+// the stop, rank and step rules after iteration k, in the reference's order (pdhg.jl:184-483; oracle/pdhg.py)
+inline Solver::Loop Solver::after_iteration(long long k) {
+    const int window = opt.convergence_window;
+    const size_t nb = P.blocks.size();
+    if (iter < certificate_search_min_iter) return Loop::next;
 
-        if (opt.certificate_search && certificate_search) {          // pdhg.jl:184-244
-            if (stop_reason == 6) {
-                if (h_dobj.at(k) > opt.certificate_obj_tol) {
-                    std::vector<double> y(P.Q);
-                    ybuf[yc].download(y.data(), P.Q, stream);
-                    PX_HIP(hipStreamSynchronize(stream));
-                    std::vector<double> zc(P.n, 0.0);
-                    dual_feasibility = dual_feas_host(y, zc, nullptr, nullptr, nullptr);
-                    if (sharded()) {
-                        std::vector<double> sums, maxs = {dual_feasibility};
-                        reduce(sums, maxs);
-                        dual_feasibility = maxs[0];
-                    }
-                    if (dual_feasibility < opt.tol_feasibility_dual) {
-                        certificate_found = true;
-                        stop_reason_string += " [Dual ray found]";
-                        break;
-                    }
-                }
-            } else {
-                if (h_pobj.at(k) < -opt.certificate_obj_tol && h_feas.at(iter) < opt.tol_feasibility) {
+    if (opt.certificate_search && certificate_search) {          // pdhg.jl:184-244
+        if (stop_reason == 6) {
+            if (h_dobj.at(k) > opt.certificate_obj_tol) {
+                update_dual_feasibility(std::vector<double>(P.n, 0.0));
+                if (dual_feasibility < opt.tol_feasibility_dual) {
                     certificate_found = true;
-                    stop_reason_string += " [Primal ray found]";
-                    break;
+                    stop_reason_string += " [Dual ray found]";
+                    return Loop::stop;
                 }
             }
-            if ((h_pobj.at(k) < -opt.certificate_fail_tol && h_dobj.at(k) < -opt.certificate_fail_tol &&
-                 h_feas.at(iter) < -opt.certificate_fail_tol) || std::isnan(h_comb.at(k))) {
-                stop_reason_string += " [Failed to find certificate]";
-                break;
+        } else {
+            if (h_pobj.at(k) < -opt.certificate_obj_tol && h_feas.at(iter) < opt.tol_feasibility) {
+                certificate_found = true;
+                stop_reason_string += " [Primal ray found]";
+                return Loop::stop;
             }
         }
-
-        // ---- convergence / rank update / divergence / adaptive steps (pdhg.jl:246-332)
-        rank_update += 1;
-        if (h_gap.at(iter) <= opt.tol_gap && h_feas.at(iter) <= opt.tol_feasibility &&
-            (!opt.check_dual_feas || dual_feasibility < opt.tol_feasibility_dual)) {
-            if ((sharded() ? !g_not_converged_rank : convergedrank()) && soc_convergence() && iter > opt.min_iter) {
-                if (!certificate_search) {
-                    stop_reason = 1;
-                    stop_reason_string = "Optimal solution found";
-                } else {
-                    stop_reason_string += " [Failed to find certificate - type 2]";
-                }
-                break;
-            } else if (rank_update > window) {
-                update_cont += 1;
-                if (update_cont > 0) {
-                    for (size_t idx = 0; idx < nb; ++idx) bump_rank((int)idx);
-                    rank_update = 0; update_cont = 0;
-                }
-            }
-        } else if (k > window && h_comb.at(k - window) < h_comb.at(k) && rank_update > window) {
-            update_cont += 1;
-            if (update_cont > opt.divergence_min_update) {
-                if (sharded() && g_any_below_full) { rank_update = 0; update_cont = 0; }
-                for (size_t idx = 0; idx < nb; ++idx) {
-                    if (target_rank[idx] < P.blocks[idx].n) { rank_update = 0; update_cont = 0; }
-                    bump_rank((int)idx);
-                }
-            }
-        } else if (h_pres.at(k) > opt.tol_primal && h_dres.at(k) < opt.tol_dual && k > window) {
-            if (++ada_count > opt.adapt_window) {
-                ada_count = 0;
-                if (opt.line_search_flag) { beta *= (1.0 - adapt_level); primal_step /= std::sqrt(1.0 - adapt_level); }
-                else { primal_step /= (1.0 - adapt_level); dual_step *= (1.0 - adapt_level); }
-                adapt_level *= opt.adapt_decay;
-            }
-        } else if (h_pres.at(k) < opt.tol_primal && h_dres.at(k) > opt.tol_dual && k > window) {
-            if (++ada_count > opt.adapt_window) {
-                ada_count = 0;
-                if (opt.line_search_flag) { beta /= (1.0 - adapt_level); primal_step *= std::sqrt(1.0 - adapt_level); }
-                else { primal_step *= (1.0 - adapt_level); dual_step /= (1.0 - adapt_level); }
-                adapt_level *= opt.adapt_decay;
-            }
-        }
-
-        // ---- iteration / time limits (pdhg.jl:334-382)
-        const double elapsed = sharded() ? g_elapsed : now_s() - time0;
-        if (iter >= max_iter_local || elapsed >= time_limit) {
-            if (iter > opt.min_iter_time_infeas && h_gap.max_abs_diff() < opt.infeas_stable_gap_tol &&
-                h_gap.at(k) > opt.infeas_limit_gap_tol) {
-                if (h_feas.at(iter) <= opt.tol_feasibility / 100) {
-                    stop_reason = 5;
-                    stop_reason_string = "Problem declared unbounded due to lack of improvement";
-                    if (opt.certificate_search && !certificate_search) { cert_dual_infeas(); snapshot(); ++n_snap; }
-                    else if (opt.certificate_search && certificate_search) {}
-                    else break;
-                } else if (h_feas.at(iter) > opt.infeas_feasibility_tol) {
-                    stop_reason = 6;
-                    stop_reason_string = "Problem declared infeasible due to lack of improvement";
-                    if (opt.certificate_search && !certificate_search) { cert_infeas(); snapshot(); ++n_snap; }
-                    else if (opt.certificate_search && certificate_search) {}
-                    else break;
-                }
-            } else if (iter >= max_iter_local) {
-                stop_reason = 3;
-                stop_reason_string = "Iteration limit of " + std::to_string(max_iter_local) + " was hit";
-            } else {
-                stop_reason = 2;
-                stop_reason_string = "Time limit hit, limit: " + std::to_string(time_limit) +
-                                     " time: " + std::to_string(now_s() - time0);
-            }
-            if (iter >= max_iter_local || elapsed >= time_limit) break;
-        }
-        if (opt.certificate_search && certificate_search) continue;
-
-        // ---- objective blow-up / stalls (pdhg.jl:389-483)
-        if ((iter > opt.min_iter_max_obj && h_dobj.at(k) > opt.max_obj) || std::isnan(h_dobj.at(k))) {
-            stop_reason = 6;
-            stop_reason_string = "Infeasible: |Dual objective| = " + std::to_string(h_dobj.at(k)) +
-                                 " > maximum allowed = " + std::to_string(opt.max_obj);
-            if (opt.certificate_search && !certificate_search) { cert_infeas(); snapshot(); ++n_snap; }
-            else break;
-        }
-        if ((iter > opt.min_iter_max_obj && h_pobj.at(k) < -opt.max_obj) || std::isnan(h_pobj.at(k))) {
-            stop_reason = 5;
-            stop_reason_string = "Unbounded: |Primal objective| = " + std::to_string(h_pobj.at(k)) +
-                                 " > maximum allowed = " + std::to_string(opt.max_obj);
-            if (opt.certificate_search && !certificate_search) { cert_dual_infeas(); snapshot(); ++n_snap; }
-            else break;
-        }
-        if (iter > opt.min_iter_max_obj && h_gap.at(k) > opt.infeas_limit_gap_tol &&
-            h_feas.at(iter) > opt.infeas_feasibility_tol &&
-            h_feas.max_abs_diff() < opt.infeas_stable_feasibility_tol) {
-            stop_reason = 6;
-            stop_reason_string = "Infeasible: feasibility stalled at " + std::to_string(h_feas.at(iter));
-            if (opt.certificate_search && !certificate_search) { cert_infeas(); snapshot(); ++n_snap; }
-            else break;
-        }
-        if (iter > opt.min_iter_max_obj && h_gap.at(k) > 1 - opt.infeas_gap_tol &&
-            h_gap.max_abs_diff() < opt.infeas_stable_gap_tol) {
-            if (std::fabs(h_dobj.at(k)) > std::fabs(h_pobj.at(k)) && h_feas.at(iter) > opt.infeas_feasibility_tol) {
-                stop_reason = 6;
-                stop_reason_string = "Infeasible: duality gap stalled at 100 % with |Dual objective| >> |Primal objective|";
-                if (opt.certificate_search && !certificate_search) { cert_infeas(); snapshot(); ++n_snap; }
-                else break;
-            } else if (std::fabs(h_pobj.at(k)) > std::fabs(h_dobj.at(k)) && h_feas.at(iter) <= opt.tol_feasibility) {
-                stop_reason = 5;
-                stop_reason_string = "Unbounded: duality gap stalled at 100 % with |Dual objective| << |Primal objective|";
-                if (opt.certificate_search && !certificate_search) { cert_dual_infeas(); snapshot(); ++n_snap; }
-                else break;
-            }
+        if ((h_pobj.at(k) < -opt.certificate_fail_tol && h_dobj.at(k) < -opt.certificate_fail_tol &&
+             h_feas.at(iter) < -opt.certificate_fail_tol) || std::isnan(h_comb.at(k))) {
+            stop_reason_string += " [Failed to find certificate]";
+            return Loop::stop;
         }
     }
+
+    // ---- convergence / rank update / divergence / adaptive steps (pdhg.jl:246-332)
+    rank_update += 1;
+    if (h_gap.at(iter) <= opt.tol_gap && h_feas.at(iter) <= opt.tol_feasibility &&
+        (!opt.check_dual_feas || dual_feasibility < opt.tol_feasibility_dual)) {
+        if ((sharded() ? !g_not_converged_rank : convergedrank()) && soc_convergence() && iter > opt.min_iter) {
+            if (!certificate_search) {
+                stop_reason = 1;
+                stop_reason_string = "Optimal solution found";
+            } else {
+                stop_reason_string += " [Failed to find certificate - type 2]";
+            }
+            return Loop::stop;
+        } else if (rank_update > window) {
+            update_cont += 1;
+            if (update_cont > 0) {
+                for (size_t idx = 0; idx < nb; ++idx) bump_rank((int)idx);
+                rank_update = 0; update_cont = 0;
+            }
+        }
+    } else if (k > window && h_comb.at(k - window) < h_comb.at(k) && rank_update > window) {
+        update_cont += 1;
+        if (update_cont > opt.divergence_min_update) {
+            if (sharded() && g_any_below_full) { rank_update = 0; update_cont = 0; }
+            for (size_t idx = 0; idx < nb; ++idx) {
+                if (target_rank[idx] < P.blocks[idx].n) { rank_update = 0; update_cont = 0; }
+                bump_rank((int)idx);
+            }
+        }
+    } else if (h_pres.at(k) > opt.tol_primal && h_dres.at(k) < opt.tol_dual && k > window) {
+        if (++ada_count > opt.adapt_window) {
+            ada_count = 0;
+            if (opt.line_search_flag) { beta *= (1.0 - adapt_level); primal_step /= std::sqrt(1.0 - adapt_level); }
+            else { primal_step /= (1.0 - adapt_level); dual_step *= (1.0 - adapt_level); }
+            adapt_level *= opt.adapt_decay;
+        }
+    } else if (h_pres.at(k) < opt.tol_primal && h_dres.at(k) > opt.tol_dual && k > window) {
+        if (++ada_count > opt.adapt_window) {
+            ada_count = 0;
+            if (opt.line_search_flag) { beta /= (1.0 - adapt_level); primal_step *= std::sqrt(1.0 - adapt_level); }
+            else { primal_step *= (1.0 - adapt_level); dual_step /= (1.0 - adapt_level); }
+            adapt_level *= opt.adapt_decay;
+        }
+    }
+
+    // ---- iteration / time limits (pdhg.jl:334-382)
+    const double elapsed = sharded() ? g_elapsed : now_s() - time0;
+    if (iter >= max_iter_local || elapsed >= time_limit) {
+        if (iter > opt.min_iter_time_infeas && h_gap.max_abs_diff() < opt.infeas_stable_gap_tol &&
+            h_gap.at(k) > opt.infeas_limit_gap_tol) {
+            if (h_feas.at(iter) <= opt.tol_feasibility / 100) {
+                if (declare(5, "Problem declared unbounded due to lack of improvement", Cert::dual_infeasible, true))
+                    return Loop::stop;
+            } else if (h_feas.at(iter) > opt.infeas_feasibility_tol) {
+                if (declare(6, "Problem declared infeasible due to lack of improvement", Cert::infeasible, true))
+                    return Loop::stop;
+            }
+        } else if (iter >= max_iter_local) {
+            stop_reason = 3;
+            stop_reason_string = "Iteration limit of " + std::to_string(max_iter_local) + " was hit";
+        } else {
+            stop_reason = 2;
+            stop_reason_string = "Time limit hit, limit: " + std::to_string(time_limit) +
+                                 " time: " + std::to_string(now_s() - time0);
+        }
+        // (a search that began just above raised both limits: the same elapsed time against the new ones)
+        if (iter >= max_iter_local || elapsed >= time_limit) return Loop::stop;
+    }
+    if (opt.certificate_search && certificate_search) return Loop::next;
+
+    // ---- objective blow-up / stalls (pdhg.jl:389-483)
+    if ((iter > opt.min_iter_max_obj && h_dobj.at(k) > opt.max_obj) || std::isnan(h_dobj.at(k))) {
+        if (declare(6, "Infeasible: |Dual objective| = " + std::to_string(h_dobj.at(k)) +
+                       " > maximum allowed = " + std::to_string(opt.max_obj), Cert::infeasible))
+            return Loop::stop;
+    }
+    if ((iter > opt.min_iter_max_obj && h_pobj.at(k) < -opt.max_obj) || std::isnan(h_pobj.at(k))) {
+        if (declare(5, "Unbounded: |Primal objective| = " + std::to_string(h_pobj.at(k)) +
+                       " > maximum allowed = " + std::to_string(opt.max_obj), Cert::dual_infeasible))
+            return Loop::stop;
+    }
+    if (iter > opt.min_iter_max_obj && h_gap.at(k) > opt.infeas_limit_gap_tol &&
+        h_feas.at(iter) > opt.infeas_feasibility_tol &&
+        h_feas.max_abs_diff() < opt.infeas_stable_feasibility_tol) {
+        if (declare(6, "Infeasible: feasibility stalled at " + std::to_string(h_feas.at(iter)), Cert::infeasible))
+            return Loop::stop;
+    }
+    if (iter > opt.min_iter_max_obj && h_gap.at(k) > 1 - opt.infeas_gap_tol &&
+        h_gap.max_abs_diff() < opt.infeas_stable_gap_tol) {
+        if (std::fabs(h_dobj.at(k)) > std::fabs(h_pobj.at(k)) && h_feas.at(iter) > opt.infeas_feasibility_tol) {
+            if (declare(6, "Infeasible: duality gap stalled at 100 % with |Dual objective| >> |Primal objective|", Cert::infeasible))
+                return Loop::stop;
+        } else if (std::fabs(h_pobj.at(k)) > std::fabs(h_dobj.at(k)) && h_feas.at(iter) <= opt.tol_feasibility) {
+            if (declare(5, "Unbounded: duality gap stalled at 100 % with |Dual objective| << |Primal objective|", Cert::dual_infeasible))
+                return Loop::stop;
+        }
+    }
+    return Loop::next;
+}
+
+// after the loop: pending capture, event harvest, the solution (pdhg.jl:486-529), debug summaries
+inline void Solver::finish() {
     PX_HIP(hipStreamSynchronize(stream));
     if (capture_state && capture_state->ints[3] == 0 && iter == capture_state->iteration) write_capture();
     for (EigWork& W : eig) harvest_full_eig_events(W);
     merge_block_stats();
-    st.loop_time = now_s() - t_loop0;
+    st.loop_time = now_s() - loop_t0;
     if (warm.joinable()) warm.join();
 
     // ---- results (pdhg.jl:486-529)
@@ -2256,7 +2263,6 @@ inline void Solver::run() {
     } else {
         cache_solution(P.c_orig);
     }
-    (void)n_snap;
     if (debug && dbg_lz[5] > 0)
         std::fprintf(stderr, "[proxsdp] single-block Lanczos: %.0f cycles; per cycle: wait for the GPU %.1f us | after-cycle host logic (eigensolve, "
                      "convergence, restart rotation staging) %.1f us; per projection: results (Ritz coefficients + rotation staging) %.1f us\n",
@@ -2274,6 +2280,50 @@ inline void Solver::run() {
                      dbg_batch[4], 1e6 * dbg_batch[0] / dbg_batch[4], 1e6 * dbg_batch[1] / dbg_batch[4],
                      1e6 * dbg_batch[2] / dbg_batch[4], 1e6 * dbg_batch[3] / dbg_batch[4]);
     res.stats = st;
+}
+
+inline void Solver::run() {
+    const double t_init0 = now_s();
+    check_run_options();
+    init_parameters();
+    reduce_global_constants();
+
+    // ---- device state ("Init", pdhg.jl:54-142)
+    setup_device();
+    setup_dense_scaling();                               // (equilibration on a dense A: finishes what prepare() deferred)
+    b_host = P.b; h_host = P.h; c_host = P.c;
+    start_host_helpers();
+    alloc_iterate();
+    upload_sparse_operator();
+    classify_blocks();
+    start_block_workers();
+    setup_small_batch();
+    setup_soc();
+    if (P.dense()) opt.support_path = 0;                 // every column of a dense M is in the support
+    setup_support();                                     // (a block-sharded solve chose opt.support_path in classify_blocks)
+    setup_dense();
+    alloc_candidates();
+    if (sharded() && use_support == shard_general)
+        throw std::logic_error("block-sharded solve: the shard's vector path is not the one chosen for it");
+    if (!initial_steps()) return;
+
+    // ---- where the loop enters: cold, resumed (proxsdp_hip_solve_ex) or from the caller's point (proxsdp_hip_solve_from)
+    long long k_first = 1;
+    if (resume_state) { apply_resume(); k_first = resume_state->iteration + 1; }
+    if (start) apply_start();
+    if (start_out) { write_start_point(); return; }
+    if (capture_state) { check_state_shape(*capture_state, "capture"); capture_state->ints[3] = 0; }
+    st.init_time = now_s() - t_init0;
+
+    // ---- "CP loop" (pdhg.jl:145-484)
+    loop_t0 = now_s();
+    const long long kmax = 2 * max_iter_local;
+    for (long long k = k_first; k <= kmax; ++k) {
+        if (capture_state && k == capture_state->iteration + 1 && k > k_first) write_capture();
+        iterate(k);
+        if (after_iteration(k) == Loop::stop) break;
+    }
+    finish();
 }
 
 }  // namespace proxsdp

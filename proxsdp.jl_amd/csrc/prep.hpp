@@ -227,6 +227,14 @@ inline void reject_for_shard(bool dense_A, bool exact_norm, bool equilibration) 
     if (equilibration) throw std::domain_error("equilibration with a block-sharded solve is not implemented");
 }
 
+// side of a PSD cone from the length of its packed triangle; -1 when the length is not triangular
+inline int64_t psd_side(int64_t len) {
+    int64_t side = (int64_t)((std::sqrt(8.0 * (double)len + 1.0) - 1.0) / 2.0);
+    while (side * (side + 1) / 2 < len) ++side;
+    while (side * (side + 1) / 2 > len) --side;
+    return side * (side + 1) / 2 == len ? side : -1;
+}
+
 inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullptr, bool shard = false) {
     Prep R;
     const int base = P.index_base;
@@ -254,10 +262,8 @@ inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullp
     for (int64_t k = 0; k < P.n_psd; ++k) {
         int64_t len = P.psd_ptr[k + 1] - P.psd_ptr[k];
         if (len <= 0) throw std::invalid_argument("empty PSD cone");
-        int64_t side = (int64_t)((std::sqrt(8.0 * (double)len + 1.0) - 1.0) / 2.0);
-        while (side * (side + 1) / 2 < len) ++side;
-        while (side * (side + 1) / 2 > len) --side;
-        if (side * (side + 1) / 2 != len) throw std::invalid_argument("PSD cone length is not triangular");
+        const int64_t side = psd_side(len);
+        if (side < 0) throw std::invalid_argument("PSD cone length is not triangular");
         if (side > 46340) throw std::invalid_argument("PSD side too large");
         R.blocks.push_back({(int)side, len, pos});
         int64_t q = P.psd_ptr[k];

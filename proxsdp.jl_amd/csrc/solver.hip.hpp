@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "host_util.hpp"
+#include "block_pool.hpp"
 #include "kernels.hip.hpp"
 #include "lanczos_block1.hip.hpp"
 #include "lanczos_wide.hip.hpp"
@@ -107,6 +108,48 @@ struct PinnedBuf {
     void release() { if (p) { (void)hipHostFree(p); p = nullptr; } }
 };
 
+// move-only owners of the runtime's handles, beside the two buffers above: create() on an owner that holds a handle does
+// nothing, the destructor ignores errors, and the implicit conversion hands the raw handle to the runtime's calls.
+// Declare them AFTER the buffers they are used with: members are destroyed in reverse order, handles first.
+template <typename H, typename Traits>
+struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned& operator=(Owned&& o) noexcept { if (this != &o) { release(); h = o.h; o.h = nullptr; } return *this; }
+    ~Owned() { release(); }
+    void release() { if (h) { Traits::destroy(h); h = nullptr; } }
+    operator H() const { return h; }
+};
+struct EventTraits { static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); } };
+struct StreamTraits { static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); } };
+struct BlasTraits { static void destroy(rocblas_handle b) { (void)rocblas_destroy_handle(b); } };
+struct Event : Owned<hipEvent_t, EventTraits> {
+    void create(unsigned flags = hipEventDefault) { if (!h) PX_HIP(hipEventCreateWithFlags(&h, flags)); }
+};
+struct Stream : Owned<hipStream_t, StreamTraits> {
+    void create(unsigned flags = hipStreamDefault) { if (!h) PX_HIP(hipStreamCreateWithFlags(&h, flags)); }
+};
+struct BlasHandle : Owned<rocblas_handle, BlasTraits> {
+    void create() { if (!h) PX_ROC(rocblas_create_handle(&h)); }
+};
+
+// milliseconds per call of `launch`, run `repeat` times on `s` between two events
+template <typename F>
+inline double time_launches(hipStream_t s, int repeat, F&& launch) {
+    Event a, b;
+    a.create(); b.create();
+    PX_HIP(hipEventRecord(a, s));
+    for (int i = 0; i < repeat; ++i) launch();
+    PX_HIP(hipEventRecord(b, s));
+    PX_HIP(hipEventSynchronize(b));
+    float t = 0.f;
+    PX_HIP(hipEventElapsedTime(&t, a, b));
+    return (double)t / repeat;
+}
+
 static inline double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -147,14 +190,14 @@ struct CircularVector {
 
 // ------------------------------------------------------------------ per-block Lanczos workspace
 struct EigEvents {                  // optional profiling of the dominant kernel
-    std::vector<hipEvent_t> e0, e1;
+    std::vector<Event> e0, e1;
     size_t used = 0;
     // start / stop events of one more profiled launch (created on first use)
     std::pair<hipEvent_t, hipEvent_t> acquire() {
         if (used == e0.size()) {
-            hipEvent_t a, b;
-            PX_HIP(hipEventCreate(&a)); PX_HIP(hipEventCreate(&b));
-            e0.push_back(a); e1.push_back(b);
+            Event a, b;
+            a.create(); b.create();
+            e0.push_back(std::move(a)); e1.push_back(std::move(b));
         }
         ++used;
         return {e0[used - 1], e1[used - 1]};
@@ -173,9 +216,9 @@ struct EigEvents {                  // optional profiling of the dominant kernel
 // projected concurrently) override it for their thread with the block's own stream, so every
 // launch / copy / synchronisation inside the per-block code lands on that stream.
 struct StreamRef {
-    hipStream_t main = nullptr;
+    Stream main;
     static inline thread_local hipStream_t tl = nullptr;
-    operator hipStream_t() const { return tl ? tl : main; }
+    operator hipStream_t() const { return tl ? tl : main.h; }
 };
 
 // Host state of ONE thick-restart Lanczos run (one PSD block): what KrylovKit keeps between the restarts of an
@@ -255,9 +298,7 @@ struct EigWork {
     bool ritz_ok = false;
     int ritz_first = 0, ritz_r = 0;
     int last_npos = -1;                            // positive eigenvalues found by the last full_eig! of this block
-    // early read-back of the recurrence coefficients (host_eig_merge): side stream + events + pinned mirror
-    hipStream_t side = nullptr;
-    hipEvent_t ev_mid = nullptr, ev_early = nullptr;
+    // early read-back of the recurrence coefficients (host_eig_merge): side stream + events (below) + pinned mirror
     PinnedBuf rec_early;
     SplitEig split;
     int batch_slot = 0;                            // position of this block in the batched run in progress
@@ -270,16 +311,11 @@ struct EigWork {
     bool fel_disabled = false;                     // ... switched off after a failed verification (full_eig_lanczos_verify)
     int fel_cert_fails = 0;                        // failed certificates of this block (full_eig_lanczos_certify)
     DevBuf<double> warm_part;                      // partial sums of the warm start (k_lz_warm_sum)
-    hipEvent_t cye[2] = {nullptr, nullptr};        // profiled k_lz_block1 launch
-    bool cye_pending = false;
+    bool cye_pending = false;                      // cye[] hold a profiled k_lz_block1 launch
     const double* esv = nullptr;                   // support values of E for the projection in progress
     // per-block execution context: counters are merged into the solver's after the projections
-    hipStream_t stream = nullptr;                  // own stream (concurrent block projections)
-    hipEvent_t done = nullptr;
     proxsdp_stats lst{};
     long long mv_iter = 0, recon_r = 0;
-    EigEvents ev, evo;                             // profiled mat-vec / orthogonalisation launches
-    hipEvent_t fe[3] = {nullptr, nullptr, nullptr};   // full_eig!: before solver | after solver | after reconstruction
     bool fe_pending = false;
     // full_eig! by the matrix sign function (sign_project.hip.hpp): A | X | X' | Y | Q, ld x ld each
     DevBuf<double> sgA, sgX, sgX2, sgY, sgQ, sg_part, sg_part2, sg_sc;
@@ -287,7 +323,6 @@ struct EigWork {
     int sg_ld = 0;
     int sg_npart = 0;
     int sg_row = -1, sg_ok = 16, sg_idle = 0, sg_hold = 0;   // shortened schedule of the sign iteration (full_eig_by_sign)
-    hipEvent_t sg_ev = nullptr;
     bool sg_small = false;                         // products on 32 x 32 tiles (blocks up to side 3072)
     int sg_nt48 = 0;                               // > 0: products on 48 x 48 tiles, this many per side (chosen by makespan)
     bool sg_pending = false;                       // fe[] hold a sign projection's events (all of it is "solver")
@@ -299,7 +334,17 @@ struct EigWork {
     bool sign_disabled = false, sign_check_pending = false;
     DevBuf<double> sg_cmp;                         // max |difference|, max |value| of a verification
     DevBuf<double> sg_out;
+    // streams and events last: destroyed before the buffers above
+    Stream stream;                                 // own stream (concurrent block projections)
+    Event done;
+    Stream side;                                   // early read-back of the recurrence coefficients
+    Event ev_mid, ev_early;
+    EigEvents ev, evo;                             // profiled mat-vec / orthogonalisation launches
+    Event fe[3];                                   // full_eig!: before solver | after solver | after reconstruction
+    Event cye[2];                                  // profiled k_lz_block1 launch
+    Event sg_ev;
 };
+static_assert(std::is_nothrow_move_constructible<EigWork>::value, "eig.resize() moves workspaces");
 
 
 // `c` mat-vec launches of block W in the stats (negative: launches counted before that did no work)
@@ -360,33 +405,42 @@ public:
     Solver(const proxsdp_options& opt_in, proxsdp_result& res_out) : opt(opt_in), res(res_out) {
         time0 = now_s();
     }
+    // no thread is alive when the members go; the handles (last members) are destroyed before the buffers
     ~Solver() {
         if (warm.joinable()) warm.join();
-        stop_workers();
-        for (EigWork& W : eig) {
-            for (auto e : W.ev.e0) (void)hipEventDestroy(e);
-            for (auto e : W.ev.e1) (void)hipEventDestroy(e);
-            for (auto e : W.evo.e0) (void)hipEventDestroy(e);
-            for (auto e : W.evo.e1) (void)hipEventDestroy(e);
-            for (auto e : W.fe) if (e) (void)hipEventDestroy(e);
-            for (auto e : W.cye) if (e) (void)hipEventDestroy(e);
-            if (W.done) (void)hipEventDestroy(W.done);
-            if (W.stream) (void)hipStreamDestroy(W.stream);
-            if (W.ev_mid) (void)hipEventDestroy(W.ev_mid);
-            if (W.ev_early) (void)hipEventDestroy(W.ev_early);
-            if (W.sg_ev) (void)hipEventDestroy(W.sg_ev);
-            if (W.side) (void)hipStreamDestroy(W.side);
-        }
-        if (ev_main) (void)hipEventDestroy(ev_main);
-        for (auto& pr : dense_ev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-        if (blas) (void)rocblas_destroy_handle(blas);
-        if (stream.main) (void)hipStreamDestroy(stream.main);
+        block_pool.reset();
     }
     void run();
+    // the phases of run(), in its order (pdhg_loop.hip.hpp)
+    void check_run_options();
+    void init_parameters();
+    void reduce_global_constants();
+    void start_host_helpers();
+    void alloc_iterate_pairs();
+    void alloc_iterate();
+    void classify_blocks();
+    void start_block_workers();
+    void setup_small_batch();
+    void setup_soc();
+    bool initial_steps();
+    enum class Loop { next, stop };
+    void iterate(long long k);
+    Loop after_iteration(long long k);
+    void finish();
+    // a stop rule's declaration and the certificate search it may start (after_iteration)
+    enum class Cert { infeasible, dual_infeasible };
+    bool declare(int reason, const std::string& str, Cert kind, bool at_limit = false);
+    void cert_infeas();
+    void cert_dual_infeas();
+    void snapshot();
+    void update_dual_feasibility(const std::vector<double>& cvec);
+    double loop_t0 = 0;             // start of the loop (trace column 12, stats.loop_time)
+    bool shard_general = false;     // block-sharded solve: this shard runs the general vector path (classify_blocks)
 
     // pieces also used by the kernel-level test entry points
     void setup_device();
     void alloc_eigwork(EigWork& W, int n, int max_nev);
+    void lanczos_start_vector(EigWork& W, const double* user);
     void lanczos(EigWork& W, const double* xp, int nev, bool positive_part = false);
     void lz_launch_step(EigWork& W, const double* xp, int k, int kfirst, double step_tol, bool& presymv);
     void lz_launch_finish(EigWork& W, int k, double tol, bool use_carry);
@@ -404,9 +458,8 @@ public:
     struct BatchCtx {
         DevBuf<double> U;
         PinnedBuf U_host, rec_host;
-        hipEvent_t ev = nullptr;                   // end of a batched cycle's record copies (the speculated mat-vecs run behind it)
         std::unique_ptr<SpinPool> pool;            // helper threads for the per-block restart logic
-        ~BatchCtx() { if (ev) (void)hipEventDestroy(ev); }
+        Event ev;                                  // end of a batched cycle's record copies (the speculated mat-vecs run behind it)
     };
     std::vector<std::unique_ptr<BatchCtx>> batch_ctx;
     std::mutex batch_stats_mu;
@@ -467,10 +520,6 @@ public:
     proxsdp_result& res;
     double time0 = 0;               // (declared before P: initialised first)
     Prep P;
-    StreamRef stream;
-    rocblas_handle blas = nullptr;
-    std::vector<EigWork> eig;
-    EigEvents ev;
     proxsdp_stats st{};
     const double* user_resid = nullptr;
     // block-sharded solve: how this shard reaches the others (shard_comm.hip.hpp); none when the solve is not sharded
@@ -522,18 +571,8 @@ public:
     // concurrent block projections: one worker thread per PSD block (up to 8), each driving its
     // block's Lanczos on the block's own stream
     std::mutex blas_mutex;
-    std::vector<std::thread> workers;
-    std::mutex pool_mu;
-    std::condition_variable pool_cv, pool_done_cv;
-    std::vector<int> pool_queue;               // block indices waiting for a worker
-    int pool_pending = 0;
-    bool pool_stop = false;
-    std::exception_ptr pool_error;
-    std::function<void(int)> pool_job;
-    hipEvent_t ev_main = nullptr;
-    bool parallel_blocks = false;
-    void start_workers(int nthreads);
-    void stop_workers();
+    std::unique_ptr<BlockPool> block_pool;     // (block_pool.hpp) up while the blocks are projected concurrently
+    bool parallel_blocks() const { return block_pool != nullptr; }
     void run_blocks(const std::vector<int>& blocks, const std::function<void(int)>& job);
     void merge_block_stats();
     void start_rocsolver_warmup();
@@ -603,7 +642,6 @@ private:
     std::vector<int> support_list() const;
     void upload_support(const std::vector<int>& supp);
     void upload_sparse_operator();
-    void test_alloc_iterate();
     void launch_clamp_scalars(double* x, int cnt);
     void launch_soc_project(double* x, int nsoc);
     void launch_soc_gap(const double* x, int nsoc);
@@ -696,8 +734,7 @@ private:
     double spectral_norm_device();
     DevBuf<double> drow_d, dcol_d;   // E[0..p), D o s
     double dense_frob2 = 0.0;        // ||E A D S||_F^2 of the dense block, from the set-up pass's row sums
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> dense_ev;   // one pair per pass of the current iteration
-    size_t dense_ev_used = 0;
+    size_t dense_ev_used = 0;                // (dense_ev, below: one pair of events per pass of the current iteration)
     void dense_ev_begin();
     void dense_ev_end();
     void dense_ev_harvest();
@@ -706,6 +743,16 @@ private:
     DevBuf<double> ycand_d, Mtycand_d, bpart, bscal;
     std::vector<double> hbscal;
     PinnedBuf hscal_pin;
+
+public:
+    // The last members, destroyed first and in reverse: ev_main, dense_ev, the rocBLAS handle and the main stream go before
+    // any buffer, as they always did; then every block's workspace (its own streams and events before its buffers,
+    // EigWork's order); then the solver's buffers above.
+    std::vector<EigWork> eig;
+    StreamRef stream;
+    BlasHandle blas;
+    std::vector<std::pair<Event, Event>> dense_ev;
+    Event ev_main;                             // run_blocks: the block streams start behind it
 };
 
 // ------------------------------------------------------------------ setup
@@ -766,6 +813,18 @@ inline void Solver::alloc_eigwork(EigWork& W, int n, int max_nev) {
     W.resid.zero(stream);
 }
 
+// W.resid_host <- the block's Lanczos start vector, normalised: the caller's (`user`, W.n entries) or start_vector's
+inline void Solver::lanczos_start_vector(EigWork& W, const double* user) {
+    W.resid_host.assign(W.npad, 0.0);
+    if (user) std::copy(user, user + W.n, W.resid_host.begin());
+    else start_vector(W.n, (uint64_t)opt.eigsolver_resid_seed,
+                      opt.eigsolver == 1 ? opt.arpack_resid_init : opt.krylovkit_resid_init,
+                      W.resid_host.data());
+    double nr = norm2(W.resid_host.data(), W.n);         // KrylovKit: v = x0 / norm(x0)
+    if (!(nr > 0.0)) throw std::invalid_argument("Lanczos start vector has zero norm");
+    for (int i = 0; i < W.n; ++i) W.resid_host[i] /= nr;
+}
+
 inline void Solver::setup_device() {
     int ndev = 0;
     PX_HIP(hipGetDeviceCount(&ndev));
@@ -774,7 +833,7 @@ inline void Solver::setup_device() {
     if (opt.lanczos_wide_krylov != 0 && opt.lanczos_wide_krylov != 1) throw std::invalid_argument("lanczos_wide_krylov must be 0 or 1");
     if (opt.lanczos_cycle_kernel == 1) opt.lanczos_cycle_kernel = 0;   // (1 selected the retired persistent cycle kernel)
     PX_HIP(hipSetDevice(opt.device_id));
-    PX_HIP(hipStreamCreate(&stream.main));
+    stream.main.create();
     // gfx950: 160 KiB of LDS per CU.  The restart rotation at K = 127, keep = 78 needs 145 KiB (U tile + V tile): with 144 KiB
     // it fell into two launches (54 us on average, profiles/r03b); take the largest grant the runtime accepts
     rotate_lds_cap = 60 * 1024;
@@ -816,7 +875,7 @@ inline void Solver::setup_device() {
         if (ok) { block1_lds_cap = kb * 1024; break; }
         (void)hipGetLastError();
     }
-    PX_ROC(rocblas_create_handle(&blas));
+    blas.create();
     PX_ROC(rocblas_set_stream(blas, stream));
 }
 
@@ -865,7 +924,7 @@ inline void Solver::launch_block1(EigWork& W, const double* xp, int kfirst, int 
                           : (two ? dev::k_lz_block1<2, false> : dev::k_lz_block1<1, false>);
     const bool prof = opt.profile_symv_every > 0;
     if (prof) {
-        if (W.cye[0] == nullptr) { PX_HIP(hipEventCreate(&W.cye[0])); PX_HIP(hipEventCreate(&W.cye[1])); }
+        W.cye[0].create(); W.cye[1].create();
         hipExtLaunchKernelGGL(kern, dim3(1), dim3(dev::B1_TPB), lds, stream, W.cye[0], W.cye[1], 0, a);
         W.cye_pending = true;
     } else {
@@ -884,10 +943,10 @@ inline void Solver::start_rocsolver_warmup() {
     const int dev_id = opt.device_id;
     warm = std::thread([dev_id]() {
         if (hipSetDevice(dev_id) != hipSuccess) return;
-        hipStream_t s = nullptr;
-        rocblas_handle h = nullptr;
-        if (hipStreamCreate(&s) != hipSuccess) return;
-        if (rocblas_create_handle(&h) == rocblas_status_success) {
+        try {
+            Stream s;
+            BlasHandle h;                               // (destroyed before its stream)
+            s.create(); h.create();
             (void)rocblas_set_stream(h, s);
             double* buf = nullptr;
             rocblas_int* info = nullptr;
@@ -903,9 +962,7 @@ inline void Solver::start_rocsolver_warmup() {
             }
             if (buf) (void)hipFree(buf);
             if (info) (void)hipFree(info);
-            (void)rocblas_destroy_handle(h);
-        }
-        (void)hipStreamDestroy(s);
+        } catch (...) {}                                // (a warm-up that cannot get its stream or handle does nothing)
     });
 }
 
@@ -1605,9 +1662,9 @@ inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive
         W.split.M.nchunk = merge_helpers() + 1;
     }
     if (use_split && W.side == nullptr) {
-        PX_HIP(hipStreamCreateWithFlags(&W.side, hipStreamNonBlocking));
-        PX_HIP(hipEventCreateWithFlags(&W.ev_mid, hipEventDisableTiming));
-        PX_HIP(hipEventCreateWithFlags(&W.ev_early, hipEventDisableTiming));
+        W.side.create(hipStreamNonBlocking);
+        W.ev_mid.create(hipEventDisableTiming);
+        W.ev_early.create(hipEventDisableTiming);
         W.rec_early.alloc(EigWork::REC_DOUBLES);
     }
     // the one-workgroup kernel rotates in the next cycle's prologue: Solver::rotate only stages U while the restart logic runs
@@ -1779,7 +1836,7 @@ inline void Solver::lanczos_batch(const std::vector<int>& blocks, const double* 
     double tp0 = debug ? now_s() : 0.0;                  // PROXSDP_HIP_DEBUG: host-time split of the batched run
     auto lap = [&](double& acc) { if (debug && !concurrent) { const double t = now_s(); acc += t - tp0; tp0 = t; } };
     std::vector<char> presymv(nb, 0);                // the first mat-vec of the block's next cycle is already in Ppart (speculated)
-    if (C.ev == nullptr) PX_HIP(hipEventCreateWithFlags(&C.ev, hipEventDisableTiming));
+    C.ev.create(hipEventDisableTiming);
     double* const rec_out = C.rec_host.p;
     const int rec_n = (int)EigWork::REC_DOUBLES;
     while (true) {
@@ -2012,7 +2069,7 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
     }
     const bool prof = opt.profile_symv_every > 0;
     if (prof) {
-        if (W.fe[0] == nullptr) for (auto& e : W.fe) PX_HIP(hipEventCreate(&e));
+        for (Event& e : W.fe) e.create();
         harvest_full_eig_events(W);
         PX_HIP(hipEventRecord(W.fe[0], stream));
     }
@@ -2086,7 +2143,7 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
         // intact): the GPU runs it while the host reads the three scalars and goes back to enqueueing the iteration
         const bool ahead = (const double*)xp_out != xp_in;
         if (ahead) {
-            if (W.sg_ev == nullptr) PX_HIP(hipEventCreateWithFlags(&W.sg_ev, hipEventDisableTiming));
+            W.sg_ev.create(hipEventDisableTiming);
             PX_HIP(hipEventRecord(W.sg_ev, stream));
             launch_final();
             wait_event(W.sg_ev);
@@ -2230,7 +2287,7 @@ inline void Solver::full_eig_project(int idx, const double* xp_in, double* xp_ou
     std::vector<double> D;
     const bool prof = opt.profile_symv_every > 0;
     if (prof) {
-        if (W.fe[0] == nullptr) for (auto& e : W.fe) PX_HIP(hipEventCreate(&e));
+        for (Event& e : W.fe) e.create();
         harvest_full_eig_events(W);                       // previous call's events (completed: see the sync below)
         PX_HIP(hipEventRecord(W.fe[0], stream));
     }
@@ -2279,72 +2336,27 @@ inline void Solver::harvest_full_eig_events(EigWork& W) {
     if (hipEventElapsedTime(&b, W.fe[1], W.fe[2]) == hipSuccess) W.lst.full_eig_recon_ms += b;
 }
 
-// ---- worker pool for concurrent block projections
-inline void Solver::start_workers(int nthreads) {
-    const int dev_id = opt.device_id;
-    for (int t = 0; t < nthreads; ++t)
-        workers.emplace_back([this, dev_id]() {
-            (void)hipSetDevice(dev_id);
-            for (;;) {
-                int idx;
-                {
-                    std::unique_lock<std::mutex> lk(pool_mu);
-                    pool_cv.wait(lk, [this]() { return pool_stop || !pool_queue.empty(); });
-                    if (pool_stop) return;
-                    idx = pool_queue.back();
-                    pool_queue.pop_back();
-                }
-                try {
-                    StreamRef::tl = eig[idx].stream;
-                    PX_HIP(hipStreamWaitEvent(eig[idx].stream, ev_main, 0));
-                    pool_job(idx);
-                    PX_HIP(hipEventRecord(eig[idx].done, eig[idx].stream));
-                } catch (...) {
-                    std::lock_guard<std::mutex> lk(pool_mu);
-                    if (!pool_error) pool_error = std::current_exception();
-                }
-                StreamRef::tl = nullptr;
-                {
-                    std::lock_guard<std::mutex> lk(pool_mu);
-                    if (--pool_pending == 0) pool_done_cv.notify_all();
-                }
-            }
-        });
-}
-inline void Solver::stop_workers() {
-    {
-        std::lock_guard<std::mutex> lk(pool_mu);
-        pool_stop = true;
-    }
-    pool_cv.notify_all();
-    for (std::thread& t : workers) if (t.joinable()) t.join();
-    workers.clear();
-}
+// ---- concurrent block projections (the job pool itself: block_pool.hpp)
 // run job(idx) for every listed block: concurrently on the blocks' streams when the pool is
 // up, otherwise in sequence on the solver's stream.  Returns after all host work is done and
 // the solver's stream has been made to wait for the block streams.
 inline void Solver::run_blocks(const std::vector<int>& blocks, const std::function<void(int)>& job) {
     bool have_streams = true;
     for (int idx : blocks) have_streams = have_streams && eig[idx].stream != nullptr;
-    if (!parallel_blocks || blocks.size() < 2 || !have_streams) {
+    if (!parallel_blocks() || blocks.size() < 2 || !have_streams) {
         for (int idx : blocks) job(idx);
         merge_block_stats();
         return;
     }
     PX_HIP(hipEventRecord(ev_main, stream.main));
-    {
-        std::lock_guard<std::mutex> lk(pool_mu);
-        pool_job = job;
-        pool_queue.assign(blocks.rbegin(), blocks.rend());
-        pool_pending = (int)blocks.size();
-        pool_error = nullptr;
-    }
-    pool_cv.notify_all();
-    {
-        std::unique_lock<std::mutex> lk(pool_mu);
-        pool_done_cv.wait(lk, [this]() { return pool_pending == 0; });
-    }
-    if (pool_error) std::rethrow_exception(pool_error);
+    // on a worker: the block's stream is the thread's stream, behind the main stream's work so far
+    block_pool->run(blocks, [this, &job](int idx) {
+        struct TlReset { ~TlReset() { StreamRef::tl = nullptr; } } reset;
+        StreamRef::tl = eig[idx].stream;
+        PX_HIP(hipStreamWaitEvent(eig[idx].stream, ev_main, 0));
+        job(idx);
+        PX_HIP(hipEventRecord(eig[idx].done, eig[idx].stream));
+    });
     for (int idx : blocks) PX_HIP(hipStreamWaitEvent(stream.main, eig[idx].done, 0));
     merge_block_stats();
 }

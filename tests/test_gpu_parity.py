@@ -413,6 +413,52 @@ def test_unbounded_lp_certificate_search():
     assert "Primal ray found" in sol.status_string
 
 
+# (model, options, certificate_search values): each forces one stop rule of pdhg.jl:184-483 that no other GPU test reaches, on the
+# two-variable LPs.  The last three end a running search without a certificate -- at the raised iteration limit, by the
+# "Failed to find certificate" test (a negative certificate_fail_tol makes it pass) and by its type-2 form (the zeroed problem
+# passes a loose convergence test once iter > min_iter) -- which only the number of iterations run tells apart: the result is
+# the snapshot taken at the declaration.
+_SEARCH = dict(max_iter=2000, max_obj=10.0, certificate_obj_tol=1e30)
+STOP_EXITS = {
+    "dual_objective_above_max_obj": ("infeasible_lp", dict(max_iter=2000, max_obj=10.0), (1, 0)),
+    "feasibility_stalled": ("infeasible_lp", dict(max_iter=3000, infeas_stable_feasibility_tol=1.0), (1, 0)),
+    "gap_stalled_infeasible": ("infeasible_lp", dict(max_iter=3000, infeas_stable_gap_tol=1.0, infeas_gap_tol=0.9), (1, 0)),
+    "gap_stalled_unbounded": ("unbounded_lp", dict(max_obj=1e300), (1, 0)),
+    "no_improvement_infeasible": ("infeasible_lp", dict(max_iter=1500, infeas_stable_gap_tol=1.0), (1, 0)),
+    "no_improvement_unbounded": ("unbounded_lp", dict(max_iter=1500, min_iter_max_obj=100000), (1, 0)),
+    "search_ends_at_the_limit": ("infeasible_lp", _SEARCH, (1,)),
+    "search_fails": ("infeasible_lp", dict(_SEARCH, certificate_fail_tol=-1e300), (1,)),
+    "search_fails_type_2": ("infeasible_lp", dict(_SEARCH, tol_gap=1e30, tol_feasibility=1e30, min_iter=1500), (1,)),
+}
+
+
+@pytest.mark.parametrize("name,certificate_search", [(k, cs) for k in sorted(STOP_EXITS) for cs in STOP_EXITS[k][2]])
+def test_stop_rules_end_as_in_the_oracle(name, certificate_search):
+    """Every declaration of pdhg.jl:334-483 -- the two at the iteration limit ("lack of improvement"), the dual-objective
+    bound, the feasibility stall, the two duality-gap stalls -- without a certificate search (the rule stops the loop) and
+    with one (the rule starts it; the loop ends with a ray, or without one: then the result is the snapshot taken at the
+    declaration), and the three ways a search ends without a certificate: status, iteration count, certificate flag, status
+    string and the number of iterations actually run (trace rows) are the oracle's for the same options.  In the strings
+    only floating-point numbers are compared as placeholders (the two sides print them differently); integers count."""
+    import re
+    import kat_problems
+    model, kw, _ = STOP_EXITS[name]
+    pr = getattr(kat_problems, model)()
+    sol = Optimizer(certificate_search=certificate_search, **kw).optimize(pr, trace_capacity=4000)
+    o = Options()
+    o.set("certificate_search", bool(certificate_search))
+    for k, v in kw.items():
+        o.set(k, v)
+    ref = oracle.solve(pr, o, trace=True)
+    print(name, certificate_search, "|", sol.status, sol.iter, sol.certificate_found, len(sol.trace), sol.status_string, "| oracle",
+          ref.status, ref.iter, ref.certificate_found, len(ref.trace), ref.status_string)
+    blank = lambda t: re.sub(r"[-+]?\d+\.\d+([eE][-+]?\d+)?|[-+]?\d+[eE][-+]?\d+", "#", t)
+    assert ref.status in (5, 6) and "limit" not in ref.status_string          # (the case still forces the rule it is named for)
+    assert len(ref.trace) < 4000 and len(sol.trace) == len(ref.trace)
+    assert (sol.status, sol.iter, sol.certificate_found) == (ref.status, ref.iter, ref.certificate_found)
+    assert blank(sol.status_string) == blank(ref.status_string)
+
+
 def test_certificate_search_on_a_psd_model_support_and_dense_paths():
     """Certificate search on an infeasible SDP whose PSD block (side 110) takes the Lanczos path: the
     snapshot taken when infeasibility is declared rescales the iterate IN PLACE (pdhg.jl:749-755), after

@@ -228,3 +228,20 @@ def test_stand_alone_group_check_builds_and_passes(tmp_path):
     assert r.returncode == 0, r.stdout
     r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.count(": ok") == 4, r.stdout
+
+
+def test_stand_alone_block_pool_check_builds_and_passes(tmp_path):
+    """tests/c_harness/block_pool_check.cpp: the job pool of the concurrent block projections with 1, 2 and 8 threads --
+    every listed index runs exactly once per call, a job's first error is rethrown after the call's other jobs ran, the
+    pool serves the next call and is destroyed with idle workers -- block_pool.hpp alone, no HIP, no library.  (The same
+    program is what the thread and address sanitizers are pointed at; here it is built plain.)"""
+    import pathlib
+    import subprocess
+    root = pathlib.Path(__file__).resolve().parent.parent
+    exe = tmp_path / "block_pool_check"
+    cmd = ["g++", "-std=c++17", "-O1", "-pthread", "-Wall", "-Werror", f"-I{root / 'proxsdp.jl_amd' / 'csrc'}",
+           str(root / "tests" / "c_harness" / "block_pool_check.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.count(": ok") == 3, r.stdout
