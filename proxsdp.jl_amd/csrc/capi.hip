@@ -8,6 +8,7 @@
 #include <string>
 
 #include "pdhg_loop.hip.hpp"
+#include "projection.hip.hpp"
 #include "shard_split.hpp"
 
 namespace {
@@ -567,7 +568,7 @@ int proxsdp_hip_psd_project(const double* packed_in, int64_t n, int32_t target_r
         proxsdp::DevBuf<double> x(N);
         x.upload(packed_in, N, S.stream);
         S.P.blocks.push_back({(int)n, N, 0});
-        if (mode == 2) S.eig[0].last_npos = target_rank;
+        if (mode == 2) S.eig[0].xprev.last_npos = target_rank;
         if (mode == 3 || mode == 5) {                       // the small-block kernels on this one block: 3 batched Jacobi, 5 LDS-resident sign projection
             if (n < 2 || n > 64) throw std::invalid_argument("mode 3 / 5: 2 <= n <= 64");
             proxsdp::DevBuf<long long> off(1); proxsdp::DevBuf<int> side(1), rk(2);
@@ -588,10 +589,8 @@ int proxsdp_hip_psd_project(const double* packed_in, int64_t n, int32_t target_r
                 // target_rank doubles as the start row of the schedule here (1 = full table ... 9 = row 8, the solver's default)
                 static const proxsdp::dev::SignSchedule sched;
                 const int j0 = std::max(0, std::min(target_rank - 1, proxsdp::dev::SIGN_STEPS - 3));
-                int rfail = 0;
-                for (int k = 0; k < proxsdp::dev::SIGN_STEPS; ++k) if (sched.l[k] <= 1e-10 * sched.gain[j0]) rfail = k;
                 hipLaunchKernelGGL(proxsdp::dev::k_small_sign_project, dim3(1), dim3(proxsdp::dev::SS_TPB), lds, S.stream,
-                                   x.p, (const long long*)off.p, (const int*)side.p, 2, 64, rk.p, rk.p + 1, j0, rfail, (int*)nullptr);
+                                   x.p, (const long long*)off.p, (const int*)side.p, 2, 64, rk.p, rk.p + 1, j0, sched.fallback_row(j0), (int*)nullptr);
             }
             int hr[2] = {0, 0};
             rk.download(hr, 2, S.stream);

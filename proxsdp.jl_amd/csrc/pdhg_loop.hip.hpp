@@ -46,399 +46,6 @@ inline void Solver::setup_long_rows(const std::vector<int>& rp) {
     PX_HIP(hipStreamSynchronize(stream));
 }
 
-// psd_projection! (prox_operators.jl:33-66), one block: reads the packed block of xin,
-// writes the projected block into xout (xin == xout on the dense path)
-// the branch condition of psd_projection! (prox_operators.jl:46-49)
-inline bool Solver::krylov_branch(int idx) const {
-    return !opt.full_eig_decomp && target_rank[idx] <= opt.max_target_rank_krylov_eigs &&
-           eig[idx].n > opt.min_size_krylov_eigs && (iter % opt.full_eig_freq) > opt.full_eig_len;
-}
-// may this block's Lanczos run ride in a batched launch (solver.hip.hpp lanczos_batch)?
-inline bool Solver::batch_eligible(int idx, bool fuse) const {
-    const EigWork& W = eig[idx];
-    if (opt.block_batch == 0 || !krylov_branch(idx)) return false;
-    if (opt.eigsolver == 1 || opt.psd_sign_engine == 1 || opt.lanczos_warm_start > 0 || opt.krylovkit_eager)
-        return false;
-    // operator-form blocks keep their own path (their step kernels take per-block factor ranks)
-    if (fuse && use_support && opt.lanczos_operator != 0 && W.fop_ok && (W.have_factors || W.x_prev_sparse)) return false;
-    return std::max(2 * (int)target_rank[idx] + 1, (int)opt.eigsolver_min_lanczos) <= 63;
-}
-// psd_projection!'s loop over the blocks (prox_operators.jl:40-61): blocks of equal side whose Lanczos runs can
-// be batched go through ONE launch per step (groups of up to LZB_MAX), the rest through run_blocks
-// (one stream + host thread per block, or in sequence)
-inline void Solver::project_blocks(const std::vector<int>& blocks, const double* xin, double* xout, bool fuse) {
-    std::vector<int> rest;
-    std::vector<std::vector<int>> groups;
-    if (opt.block_batch != 0 && blocks.size() >= 2) {
-        std::vector<int> cand;
-        for (int idx : blocks) (batch_eligible(idx, fuse) ? cand : rest).push_back(idx);
-        std::stable_sort(cand.begin(), cand.end(), [this](int a, int b) { return eig[a].n < eig[b].n; });
-        size_t i0 = 0;
-        while (i0 < cand.size()) {
-            size_t i1 = i0;
-            while (i1 < cand.size() && eig[cand[i1]].n == eig[cand[i0]].n) ++i1;
-            // equal-side run [i0, i1): groups of up to LZB_MAX blocks; with the worker pool up, at least two groups of >= 2
-            // blocks on request (options.block_batch_groups) so that they can overlap
-            const size_t cnt = i1 - i0;
-            if (cnt < 2) { rest.push_back(cand[i0]); i0 = i1; continue; }
-            size_t ng = (cnt + dev::LZB_MAX - 1) / dev::LZB_MAX;
-            const int want = opt.block_batch_groups < 0 ? 1 : (int)opt.block_batch_groups;   // (auto = 1: measured, see the header)
-            if (parallel_blocks() && want >= 2 && cnt >= 4) ng = std::max<size_t>(ng, std::min<size_t>((size_t)want, cnt / 2));
-            for (size_t q = 0; q < ng; ++q) {
-                const size_t a = i0 + q * cnt / ng, b = i0 + (q + 1) * cnt / ng;
-                groups.emplace_back(cand.begin() + a, cand.begin() + b);
-            }
-            i0 = i1;
-        }
-        std::sort(rest.begin(), rest.end());
-    } else {
-        rest = blocks;
-    }
-    // groups run CONCURRENTLY when the block worker pool is up (one worker thread + the leader block's stream per group):
-    // while one group's restart logic runs on the host the other group's cycle runs on the GPU (the step launches are
-    // latency-bound: two groups side by side advance about as fast as one).  Per block nothing changes.
-    if (batch_ctx.size() < groups.size()) {
-        const size_t have = batch_ctx.size();
-        batch_ctx.resize(groups.size());
-        for (size_t q = have; q < groups.size(); ++q) batch_ctx[q].reset(new BatchCtx());
-    }
-    for (const std::vector<int>& g : groups) for (int idx : g) current_rank[idx] = 0;
-    // (groups run side by side only ON REQUEST -- block_batch_groups >= 2; a model with more than LZB_MAX equal-side
-    // blocks splits into several groups by necessity, and those run one after the other as in rounds 3-4: auto = sequential)
-    const int want_groups = opt.block_batch_groups < 0 ? 1 : (int)opt.block_batch_groups;
-    bool leaders_have_streams = parallel_blocks() && groups.size() >= 2 && want_groups >= 2;
-    for (const std::vector<int>& g : groups) leaders_have_streams = leaders_have_streams && eig[g[0]].stream != nullptr;
-    if (leaders_have_streams) {
-        std::vector<int> leaders;
-        std::vector<int> slot_of(eig.size(), -1);
-        for (size_t q = 0; q < groups.size(); ++q) { leaders.push_back(groups[q][0]); slot_of[groups[q][0]] = (int)q; }
-        run_blocks(leaders, [this, xin, &groups, &slot_of](int leader) {
-            const std::vector<int>& g = groups[slot_of[leader]];
-            std::vector<int> nevs;
-            for (int idx : g) nevs.push_back((int)target_rank[idx]);
-            lanczos_batch(g, xin, nevs, slot_of[leader]);
-        });
-    } else {
-        for (size_t q = 0; q < groups.size(); ++q) {
-            std::vector<int> nevs;
-            for (int idx : groups[q]) nevs.push_back((int)target_rank[idx]);
-            lanczos_batch(groups[q], xin, nevs, (int)q);
-        }
-    }
-    for (const std::vector<int>& g : groups)
-        for (int idx : g) project_block(idx, xin, xout, fuse, true);
-    if (!groups.empty()) merge_block_stats();
-    if (!rest.empty()) run_blocks(rest, [this, xin, xout, fuse](int idx) { project_block(idx, xin, xout, fuse); });
-}
-
-inline void Solver::project_block(int idx, const double* xin, double* xout, bool fuse, bool lanczos_done) {
-    EigWork& W = eig[idx];
-    const double* xp = xin + P.blocks[idx].off;
-    double* xo = xout + P.blocks[idx].off;
-    current_rank[idx] = 0;
-    W.ritz_ok = false;                        // the block is about to be rewritten
-    const bool krylov = lanczos_done || krylov_branch(idx);
-    // operator-form mat-vec: legal when this block's x_prev is known in factored form (or is
-    // zero off the support) and the update is the sparse support update of this iteration
-    W.use_fop = !lanczos_done && fuse && use_support && opt.lanczos_operator != 0 && W.fop_ok && krylov &&
-                (W.have_factors || W.x_prev_sparse) && !(opt.krylovkit_eager && opt.eigsolver != 1);
-    // (a Krylov dimension beyond the step kernels -- the wide kernels or the dense stand-in -- takes the packed-tile mat-vec)
-    if (std::max(2 * (int)target_rank[idx] + 1, (int)opt.eigsolver_min_lanczos) > dev::LZ_KMAX) W.use_fop = false;
-    if (W.use_fop) {
-        if (!W.have_factors) { W.F_r = 0; W.F_first = 0; }
-        W.esv = esv_d.p + (W.have_factors ? 0 : ns);
-    }
-    if (!krylov) {
-        // full_eig! (prox_operators.jl:111-126): every positive eigenpair.  In the IMPLICIT full-eig
-        // regime (target_rank beyond max_target_rank_krylov_eigs: the reference falls back to LAPACK
-        // because its Krylov wrapper is capped, prox_operators.jl:46-49) the positive part is
-        // low-rank and known from the previous projection: it is computed by the Lanczos engine
-        // (operator form allowed) instead of a dense O(n^3) eigensolver -- see full_eig_by_lanczos.
-        // An explicit full_eig_decomp = true / periodic full_eig_freq request always gets the dense solver.
-        const bool implicit = !opt.full_eig_decomp && (iter % opt.full_eig_freq) > opt.full_eig_len &&
-                              W.n > opt.min_size_krylov_eigs;
-        if (!implicit && opt.full_eig_lanczos != 1) {
-            W.have_factors = false; W.x_prev_sparse = false; W.use_fop = false;
-            full_eig_project(idx, xp, xo, fuse);
-            return;
-        }
-        W.use_fop = fuse && use_support && opt.lanczos_operator != 0 && W.fop_ok && (W.have_factors || W.x_prev_sparse);
-        if (W.use_fop) {
-            if (!W.have_factors) { W.F_r = 0; W.F_first = 0; }
-            W.esv = esv_d.p + (W.have_factors ? 0 : ns);
-        }
-        if (full_eig_by_lanczos(idx, xp, xo, fuse)) return;
-        W.have_factors = false; W.x_prev_sparse = false; W.use_fop = false;
-        full_eig_project(idx, xp, xo, fuse);
-        return;
-    }
-    const bool used_fop = W.use_fop;
-    const int nev = (int)target_rank[idx];
-    if (!lanczos_done && !krylovdim_fits(nev)) {          // Krylov dimension beyond the step kernels: dense eigensolver, same projection
-        W.use_fop = false;
-        truncated_project_dense(idx, xp, xo, fuse, nev);
-        return;
-    }
-    if (!lanczos_done) {                      // (a batched run has already filled W.vals / W.Z)
-        if (exact_projection_by_sign(idx, xp, xo, fuse, nev)) return;
-        const double t_kry = opt.psd_sign_engine == 1 ? now_s() : 0.0;
-        lanczos(W, xp, nev);
-        if (opt.psd_sign_engine == 1 && W.converged) {
-            const double ms = (now_s() - t_kry) * 1e3;
-            W.kry_ms = W.kry_ms < 0 ? ms : 0.75 * W.kry_ms + 0.25 * ms;
-        }
-    }
-    W.use_fop = false;
-    if (used_fop) W.lst.fop_projections++;
-    if (!W.converged) {                       // prox_operators.jl:55-57
-        W.lst.krylov_fallbacks++;
-        W.have_factors = false; W.x_prev_sparse = false;
-        full_eig_project(idx, xp, xo, fuse);
-        return;
-    }
-    double mn = W.vals[0];
-    for (double v : W.vals) mn = std::min(mn, v);
-    min_eig[idx] = mn;                        // prox_operators.jl:95 / :74
-    int first = 0, npos = 0;
-    if (opt.eigsolver == 1) {                 // ascending arc.d, all nev used (prox_operators.jl:78-85)
-        for (int i = 0; i < nev; ++i) if (W.vals[i] > 0.0) ++npos;
-        first = nev - npos;
-    } else {                                  // descending, min(target_rank, converged) used (:99-106)
-        const int k = std::min(nev, W.converged_eigs);
-        for (int i = 0; i < k; ++i) if (W.vals[i] > 0.0) ++npos;
-    }
-    current_rank[idx] += npos;
-    W.last_npos = npos;                       // (lower bound: estimate for a later full_eig!-by-Lanczos)
-    if (npos > 0) W.lam.upload(W.vals.data() + first, npos, stream);
-    launch_reconstruct(W, W.Z.p + (size_t)first * W.npad, W.npad, W.lam.p, npos, xo,
-                       fuse ? xp : nullptr, fuse ? idx : -1);
-    W.recon_r += npos;
-    if (W.fop_ok) {                           // x_new = Z[:, first..] diag(lam) Z': keep the factors
-        std::swap(W.Z.p, W.F.p);
-        W.F_first = first; W.F_r = npos;
-        std::swap(W.lam.p, W.Flam.p);            // the eigenvalues just uploaded become the next projection's factors
-        std::swap(W.lam.n, W.Flam.n);
-        W.have_factors = true; W.x_prev_sparse = false;
-    } else {                                  // no F to swap into: the pairs stay in Z / vals (extract_factors)
-        W.ritz_first = first; W.ritz_r = npos; W.ritz_ok = true;
-    }
-    if (W.sign_check_pending) verify_sign_engine(idx, xo);
-}
-
-// psd_sign_engine = 1: the Krylov branch computes the top target_rank eigenpairs and keeps the positive ones
-// (prox_operators.jl:89-109).  Whenever fewer than target_rank eigenvalues are positive that IS the exact
-// projection, min_eig (the smallest returned value) is <= 0, and the two decisions min_eig feeds
-// (pdhg.jl:272 `> tol_psd`, residuals.jl:93 `< tol_psd`) are settled -- so the sign-function projection
-// (sign_project.hip.hpp) may stand in for the Lanczos engine when it is the cheaper way to the same matrix:
-// hub-row / clustered spectra that cost hundreds of mat-vecs per projection (maxG51: 541), many mid-size
-// blocks (MIMO).  It is chosen per block from measured wall-clock averages of both engines, only when the
-// previous projection was not truncated, and VERIFIED afterwards: #{lambda > 0} >= target_rank means the
-// reference would have truncated, and the projection is redone by the Lanczos engine.
-inline double sign_cost_model_ms(int ld) {                   // measured on MI355X (profiles/r02c_sign_projection_summary.md)
-    static const int L[] = {128, 512, 1024, 1536, 2048, 3072, 4096};
-    static const double T[] = {0.30, 0.60, 2.05, 4.8, 11.3, 31.2, 71.2};
-    if (ld <= L[0]) return T[0];
-    for (int i = 1; i < 7; ++i)
-        if (ld <= L[i]) return T[i - 1] + (T[i] - T[i - 1]) * (double)(ld - L[i - 1]) / (L[i] - L[i - 1]);
-    return T[6] * std::pow((double)ld / 4096.0, 3.0);
-}
-inline bool Solver::exact_projection_by_sign(int idx, const double* xp, double* xo, bool fuse, int nev) {
-    if (opt.psd_sign_engine != 1) return false;
-    EigWork& W = eig[idx];
-    W.sign_check_pending = false;                                         // (a verification whose Lanczos half fell back)
-    if (W.n < 33 || W.n > 16384) return false;
-    if (W.kry_ms < 0.0 || W.last_npos < 0) return false;                  // no Lanczos measurement of this block yet
-    if (W.last_npos >= nev) return false;                                 // truncation was active last time: the reference's engine decides
-    if (W.sign_backoff > 0) { --W.sign_backoff; return false; }           // after a rejected attempt
-    const double est = W.sign_ms >= 0.0 ? W.sign_ms : sign_cost_model_ms(W.nt * dev::TILE);
-    if (W.kry_ms < 1.5 * est) { W.sign_streak = 0; return false; }
-    if (W.sign_streak >= 256) { W.sign_streak = 0; return false; }        // re-measure the Lanczos engine now and then
-    if (W.sign_disabled) return false;
-    const bool inplace = xp == xo;
-    if (W.sign_verified_left <= 0) {
-        // verification round (first use, then every 64th projection): BOTH engines run on this input; the Lanczos
-        // result is the one used, and the engine may serve the next 64 projections only if the two agree.
-        // Single-vector Lanczos returns one eigenvector per DISTINCT eigenvalue: where the iterate has repeated
-        // positive eigenvalues (MIMO's first iterates) the reference's projection is not the exact one, the
-        // comparison fails, and the block stays with the reference's engine for the rest of the solve.
-        if (W.sg_out.n < (size_t)W.N) W.sg_out.alloc(W.N);
-        const long long cr = current_rank[idx];
-        const double me = min_eig[idx];
-        const int lnp = W.last_npos;
-        if (full_eig_by_sign(idx, xp, W.sg_out.p, false, true)) W.sign_check_pending = current_rank[idx] < nev;
-        current_rank[idx] = cr; min_eig[idx] = me; W.last_npos = lnp;
-        return false;
-    }
-    double* out = xo;
-    if (inplace) {                                                        // keep the input: the check below may reject
-        if (W.sg_out.n < (size_t)W.N) W.sg_out.alloc(W.N);
-        out = W.sg_out.p;
-    }
-    const double t0 = now_s();
-    if (!full_eig_by_sign(idx, xp, out, fuse, true)) return false;
-    const double ms = (now_s() - t0) * 1e3;
-    W.sign_ms = W.sign_ms < 0 ? ms : 0.75 * W.sign_ms + 0.25 * ms;
-    const int npos = (int)current_rank[idx];
-    if (npos >= nev) {                                                    // truncation would be active: not the same projection
-        W.lst.sign_engine_rejected++;
-        current_rank[idx] = 0;
-        W.sign_backoff = 32;
-        return false;
-    }
-    if (inplace) PX_HIP(hipMemcpyAsync(xo, out, (size_t)W.N * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    W.lst.sign_engine_projections++;
-    W.sign_streak++;
-    W.sign_verified_left--;
-    min_eig[idx] = 0.0;                 // the reference's value is lambda_min of the returned pairs, <= 0: same decisions
-    W.have_factors = false; W.x_prev_sparse = false; W.use_fop = false;
-    return true;
-}
-
-// second half of a verification round: xo holds the Lanczos engine's projection, W.sg_out the sign function's
-inline void Solver::verify_sign_engine(int idx, const double* xo) {
-    EigWork& W = eig[idx];
-    W.sign_check_pending = false;
-    if (W.sg_cmp.n < 2) W.sg_cmp.alloc(2);
-    W.sg_cmp.zero(stream);
-    hipLaunchKernelGGL(dev::k_maxdiff, dim3(grid_for(W.N)), dim3(dev::TPB), 0, stream, xo, (const double*)W.sg_out.p,
-                       (long long)W.N, W.sg_cmp.p);
-    double h[2] = {0.0, 0.0};
-    W.sg_cmp.download(h, 2, stream);
-    PX_HIP(hipStreamSynchronize(stream));
-    W.lst.sign_engine_checks++;
-    if (h[0] <= 1e-8 * std::max(h[1], 1e-300)) {
-        W.sign_verified_left = 64;
-    } else {
-        W.sign_disabled = true;
-        W.lst.sign_engine_mismatches++;
-    }
-}
-
-// full_eig! needs X+ = sum over lambda_i > 0 of lambda_i v_i v_i' -- every POSITIVE eigenpair, not
-// the spectrum (prox_operators.jl:115-124), current_rank = #{lambda_i > tol_psd}, min_eig = 0.  The
-// reference calls LAPACK dsyevr because it has no partial solver with an unknown count; on this path
-// (target_rank beyond max_target_rank_krylov_eigs) the iterate is typically low-rank, so the positive
-// part is the top of the spectrum: run the Lanczos engine for g = (positives last time) + slack
-// largest pairs; if the smallest of them is <= 0 (and all g converged to krylovkit_tol) every
-// positive eigenvalue is among them.  Otherwise enlarge g once, then fall back to the dense solver.
-// rocSOLVER dsyevd takes 139 ms at n = 4000 (1.5 TF/s); this takes the cost of a Krylov projection.
-inline bool Solver::full_eig_by_lanczos(int idx, const double* xp, double* xo, bool fuse) {
-    EigWork& W = eig[idx];
-    if (opt.full_eig_lanczos == 0 || opt.eigsolver == 1 || W.n <= opt.min_size_krylov_eigs) return false;
-    if (W.last_npos < 0) return false;                       // no estimate yet: dense eigensolver first
-    if (W.fel_disabled) return false;                        // a verification failed earlier in this solve
-    // krylovdim = 2 nev + 1 <= cap - 1, and never beyond the step kernels' 255 columns (a wide workspace included)
-    const int maxnev = std::min((std::min(W.cap, dev::MAXK - 4) - 2) / 2, W.n - 1);
-    int g = W.last_npos + std::max(3, W.last_npos / 8);
-    if (8 * W.last_npos > W.n) return false;                 // many positive pairs: the dense solver is the cheaper tool
-    const bool used_fop = W.use_fop;
-    // Verification (options.full_eig_lanczos_verify): this engine is the library's own algorithm, and single-vector
-    // Lanczos returns ONE eigenvector per distinct eigenvalue -- a repeated positive eigenvalue, or a start vector
-    // deficient in an eigendirection, would silently drop a copy from X+.  On the first call of a block and every
-    // k-th after it the reference's engine (full_eig_project: sign function / dsyevd) ALSO projects the same input
-    // (into a scratch buffer, BEFORE the reconstruction overwrites an in-place input); the results are compared
-    // below and a mismatch hands the block back to the dense engine for the rest of the solve.
-    const int vk = opt.full_eig_lanczos_verify < 0 ? 256 : opt.full_eig_lanczos_verify;
-    bool verify = vk > 0 && (W.fel_served % vk) == 0;
-    long long ref_rank = 0;
-    int ref_npos = 0;
-    bool ref_sign = false;
-    if (verify) {
-        if (W.sg_out.n < (size_t)W.N) W.sg_out.alloc(W.N);
-        const long long cr = current_rank[idx];
-        const double me = min_eig[idx];
-        const int lnp = W.last_npos;
-        const bool hf = W.have_factors, xs = W.x_prev_sparse, uf = W.use_fop;
-        const long long fe0 = W.lst.full_eigs, fs0 = W.lst.full_eigs_sign;
-        full_eig_project(idx, xp, W.sg_out.p, false);
-        ref_rank = current_rank[idx]; ref_npos = W.last_npos; ref_sign = W.lst.full_eigs_sign > fs0;
-        current_rank[idx] = cr; min_eig[idx] = me; W.last_npos = lnp;
-        W.have_factors = hf; W.x_prev_sparse = xs; W.use_fop = uf;
-        W.lst.full_eigs = fe0; W.lst.full_eigs_sign = fs0;   // (the check is not a full_eig! call of the solve)
-    }
-    auto use_reference_result = [&]() {
-        W.fel_disabled = true;
-        W.lst.full_eigs_lanczos_mismatches++;
-        W.have_factors = false; W.x_prev_sparse = false; W.use_fop = false; W.ritz_ok = false;
-        if (xp != xo) { full_eig_project(idx, xp, xo, fuse); return; }   // input intact: the ordinary dense call
-        // in-place call: the input is gone, the scratch buffer holds the dense engine's projection of it
-        PX_HIP(hipMemcpyAsync(xo, W.sg_out.p, (size_t)W.N * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        W.lst.full_eigs++;
-        if (ref_sign) W.lst.full_eigs_sign++;
-        current_rank[idx] = ref_rank; min_eig[idx] = 0.0; W.last_npos = ref_npos;
-    };
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (g > maxnev || g < 1) break;
-        lanczos(W, xp, g, true);
-        if (!W.converged) {                                   // more positives than g, or no convergence
-            if (attempt == 0 && g < maxnev) { g = std::min(2 * g + 2, maxnev); continue; }
-            break;
-        }
-        const int npos = W.count;
-        W.fel_served++;
-        // guard: between consecutive projections of this regime the number of positive eigenvalues
-        // moves by a few; a collapse means the Krylov space was fooled (e.g. decoupled coordinates
-        // resolved long before the small positive pairs): let the dense solver decide
-        if (npos + 2 + W.last_npos / 8 < W.last_npos) break;
-        // per-call certificate (Solver::lanczos_certificate): nothing positive may be left outside the returned pairs
-        const int cert_m = opt.full_eig_lanczos_certify < 0 ? 10 : opt.full_eig_lanczos_certify;
-        if (cert_m >= 2) {
-            double theta = 0.0, cscale = 0.0;
-            if (lanczos_certificate(W, xp, npos, cert_m, theta, cscale)) {
-                const double posres = lanczos_posres();
-                if (!(theta <= posres * cscale)) {
-                    // a positive direction the run did not see: the dense engine projects this input (intact: the
-                    // reconstruction has not run yet); three failures leave the block to the dense engine for good
-                    W.lst.full_eigs_lanczos_cert_failed++;
-                    if (++W.fel_cert_fails >= 3) W.fel_disabled = true;
-                    if (debug) std::fprintf(stderr, "[proxsdp] certificate failed: block %d iteration %lld theta %.3e scale %.3e npos %d\n",
-                                            idx, (long long)iter, theta, cscale, npos);
-                    break;
-                }
-                W.lst.full_eigs_lanczos_certified++;
-            }
-        }
-        int rank = 0;
-        for (int i = 0; i < npos; ++i) if (W.vals[i] > opt.tol_psd) ++rank;
-        // (values are descending: the positive ones are the first npos)
-        W.use_fop = false;
-        if (used_fop) W.lst.fop_projections++;
-        W.lst.full_eigs++; W.lst.full_eigs_lanczos++;
-        current_rank[idx] = rank;
-        min_eig[idx] = 0.0;                                  // prox_operators.jl:114
-        W.last_npos = npos;
-        if (npos > 0) W.lam.upload(W.vals.data(), npos, stream);
-        launch_reconstruct(W, W.Z.p, W.npad, W.lam.p, npos, xo, fuse ? xp : nullptr, fuse ? idx : -1);
-        W.recon_r += npos;
-        if (W.fop_ok) {
-            std::swap(W.Z.p, W.F.p);
-            W.F_first = 0; W.F_r = npos;
-            std::swap(W.lam.p, W.Flam.p);
-            std::swap(W.lam.n, W.Flam.n);
-            W.have_factors = true; W.x_prev_sparse = false;
-        } else {
-            W.ritz_first = 0; W.ritz_r = npos; W.ritz_ok = true;
-        }
-        if (verify) {
-            if (W.sg_cmp.n < 2) W.sg_cmp.alloc(2);
-            W.sg_cmp.zero(stream);
-            hipLaunchKernelGGL(dev::k_maxdiff, dim3(grid_for(W.N)), dim3(dev::TPB), 0, stream, (const double*)xo,
-                               (const double*)W.sg_out.p, (long long)W.N, W.sg_cmp.p);
-            double h[2] = {0.0, 0.0};
-            W.sg_cmp.download(h, 2, stream);
-            PX_HIP(hipStreamSynchronize(stream));
-            W.lst.full_eigs_lanczos_checks++;
-            if (!(h[0] <= 1e-8 * std::max(h[1], 1e-300))) {
-                W.lst.full_eigs--; W.lst.full_eigs_lanczos--;
-                use_reference_result();
-            }
-        }
-        return true;
-    }
-    W.use_fop = false;
-    return false;
-}
-
 // the cone tail's launches: 1x1 PSD blocks (one_off -> one_min), SOC projection and SOC gap (soc_off, soc_len -> soc_gap_d)
 inline void Solver::launch_clamp_scalars(double* x, int cnt) {
     hipLaunchKernelGGL(dev::k_clamp_scalars, dim3(ceil_div(cnt, 256)), dim3(256), 0, stream, x, one_off.p, cnt, one_min.p);
@@ -453,74 +60,6 @@ inline void Solver::launch_soc_gap(const double* x, int nsoc) {
 inline void Solver::launch_primal_update_S(double* x, double tau) {
     hipLaunchKernelGGL(dev::k_primal_update_S, dim3(ceil_div(std::max(ns, 1), dev::TPB)), dim3(dev::TPB), 0, stream,
                        x, supp_d.p, MtyS_cur.p, cS_d.p, tau, xsave_d.p, ns, esv_d.p);
-}
-
-inline void Solver::psd_projection(double* x) {
-    std::fill(min_eig.begin(), min_eig.end(), 0.0);
-    if (!one_blocks.empty()) {
-        launch_clamp_scalars(x, (int)one_blocks.size());
-        for (int idx : one_blocks) current_rank[idx] = 0;
-    }
-    if (!small_blocks.empty()) {
-        project_small_blocks(x);
-        project_blocks(large_blocks, x, x, false);
-    } else {
-        project_blocks(big_blocks, x, x, false);
-    }
-}
-
-// all small PSD blocks in one launch (kernels.hip.hpp k_small_psd_project); ranks come back with the
-// iteration's next synchronisation (pinned buffer)
-inline void Solver::project_small_blocks(double* x) {
-    harvest_small_ranks();
-    const int nb = (int)small_blocks.size();
-    // ranks, positive counts and the schedule-test outcomes [nb each] go STRAIGHT into pinned host memory (no copy launch)
-    // (small models only, as the scalars of the linesearch: zero_copy_small; otherwise through the device buffer and one copy)
-    const bool zc = zero_copy_small();
-    int* rk_host = zc ? reinterpret_cast<int*>(small_rank_host.p) : small_rank.p;
-    if (zc) for (int q = 0; q < nb; ++q) rk_host[2 * nb + q] = 0;          // (the previous launch's values were harvested above)
-    else PX_HIP(hipMemsetAsync(small_rank.p + 2 * nb, 0, (size_t)nb * sizeof(int), stream));
-    bool any_jacobi = false;
-    int jac_maxn = 0;
-    for (int idx : small_blocks) if (P.blocks[idx].n <= small_jacobi_max) { any_jacobi = true; jac_maxn = std::max(jac_maxn, P.blocks[idx].n); }
-    if (any_jacobi) {
-        const int ld = jac_maxn | 1;
-        const size_t lds = ((size_t)2 * jac_maxn * ld + 64) * sizeof(double) + 64 * sizeof(int);
-        hipLaunchKernelGGL(dev::k_small_psd_project, dim3(nb), dim3(dev::TPB), lds, stream,
-                           x, (const long long*)small_off.p, (const int*)small_side.p, opt.tol_psd, rk_host, rk_host + nb,
-                           2, small_jacobi_max);
-    }
-    if (small_sign_maxn > 0) {
-        // shortened, tested schedule as Solver::full_eig_by_sign: start at row 8 (sign_start_row overrides), fall back inside the kernel
-        static const dev::SignSchedule sched;
-        int jmax = 0;
-        for (int j = 1; j + 2 < dev::SIGN_STEPS; ++j) if (std::sqrt(4e-13 * (double)dev::SS_MAXN) / sched.gain[j] <= 1e-10) jmax = j;   // (the test's tau at the largest side)
-        const int j0 = std::max(0, std::min(opt.sign_start_row < 0 ? 8 : (int)opt.sign_start_row, jmax));
-        int rfail = 0;
-        for (int k = 0; k < dev::SIGN_STEPS; ++k) if (sched.l[k] <= 1e-10 * sched.gain[j0]) rfail = k;
-        hipLaunchKernelGGL(dev::k_small_sign_project, dim3(nb), dim3(dev::SS_TPB), dev::small_sign_lds_bytes(small_sign_maxn), stream,
-                           x, (const long long*)small_off.p, (const int*)small_side.p, small_jacobi_max + 1, dev::SS_MAXN,
-                           rk_host, rk_host + nb, j0, rfail, j0 > 0 ? rk_host + 2 * nb : (int*)nullptr);
-        st.full_eigs_sign += nb; st.sign_products += 57LL * nb;      // (counted per block below for the Jacobi ones)
-        for (int idx : small_blocks) if (P.blocks[idx].n <= small_jacobi_max) { st.full_eigs_sign--; st.sign_products -= 57; }
-    }
-    if (!zc) PX_HIP(hipMemcpyAsync(small_rank_host.p, small_rank.p, (size_t)3 * nb * sizeof(int), hipMemcpyDeviceToHost, stream));
-    small_pending = true;
-    st.full_eigs += nb; st.batched_small_eigs += nb;
-    for (int idx : small_blocks) { current_rank[idx] = 0; min_eig[idx] = 0.0; }
-}
-// (called after a stream synchronisation has happened since the launch: every iteration ends with one)
-inline void Solver::harvest_small_ranks() {
-    if (!small_pending) return;
-    small_pending = false;
-    const int* r = reinterpret_cast<const int*>(small_rank_host.p);
-    for (size_t q = 0; q < small_blocks.size(); ++q) {
-        if (r[q] < 0) throw HipError("sign-function projection of a small block produced non-finite values");
-        current_rank[small_blocks[q]] = r[q];
-    }
-    // the shortened schedule's tests made inside k_small_sign_project (cumulative counters behind the ranks)
-    const int* flag = r + 2 * small_blocks.size();            // per block: 1 = test passed, 2 = failed (fall-back rows ran), 0 = no test
-    for (size_t q = 0; q < small_blocks.size(); ++q) { st.sign_short_pass += flag[q] == 1; st.sign_short_fail += flag[q] == 2; }
 }
 
 // primal_step! (pdhg.jl:611-637)
@@ -1032,7 +571,7 @@ inline void Solver::cache_solution(const std::vector<double>& cvec) {
     // search continues from here, the operator-form factors F diag(Flam) F' still describe the
     // UNscaled iterate: drop them so the next projection reads the (rescaled) packed buffer, as the
     // fused residual and the dense / full-eig paths do.
-    for (EigWork& W : eig) { W.have_factors = false; W.x_prev_sparse = false; W.ritz_ok = false; }
+    for (EigWork& W : eig) { W.have_factors = false; W.xprev.sparse = false; W.ritz_ok = false; }
     st.exit_time += now_s() - t0;
 }
 
@@ -1626,7 +1165,7 @@ inline void Solver::apply_resume() {
         std::copy(s.hist + (size_t)q * s.hist_len, s.hist + (size_t)(q + 1) * s.hist_len, H[q]->v.begin());
     iter = s.iteration;
     // the iterate is a general matrix now: neither zero off the support nor known in factored form
-    for (EigWork& W : eig) { W.have_factors = false; W.x_prev_sparse = false; }
+    for (EigWork& W : eig) { W.have_factors = false; W.xprev.sparse = false; }
 }
 
 // enter the loop from the caller's point (include/proxsdp_hip.h proxsdp_start; validated by the entry point): called after
@@ -1721,7 +1260,7 @@ inline void Solver::apply_start() {
     if (P.dense()) { dense_ev_harvest(); dense_passes_seen = st.dense_passes; }   // (set-up work, as the sigma_max passes)
     // the ping-pong pairs' current buffers hold the point, so x_old = x, y_old = y, (M x)_old = M x, (M'y)_old = M'y at
     // iteration 1; the iterate is a general matrix: the first projection reads the packed buffer
-    for (EigWork& W : eig) { W.have_factors = false; W.x_prev_sparse = false; W.ritz_ok = false; }
+    for (EigWork& W : eig) { W.have_factors = false; W.xprev.sparse = false; W.ritz_ok = false; }
 }
 
 // proxsdp_hip_start_point: the internal vectors after the start path

@@ -289,15 +289,20 @@ struct EigWork {
     int ell_w = 0, F_first = 0, F_r = 0;
     bool fop_ok = false;                           // structures built (support path, narrow rows)
     bool have_factors = false;                     // x_prev of this block is F[:, F_first .. +F_r) diag(Flam) F'
-    bool x_prev_sparse = true;                     // x_prev is zero off the support (initial iterate)
     bool use_fop = false;                          // the projection in progress uses the operator form
+    // what else the dispatch (projection.hip.hpp) knows of x_prev; have_factors, F_first / F_r and ritz_ok stay beside the
+    // buffers they describe: the Lanczos drivers read or drop them
+    struct XPrev {
+        bool sparse = true;                        // x_prev is zero off the support (initial iterate)
+        int last_npos = -1;                        // positive eigenvalues found by the last projection of this block
+    } xprev;
+    void forget_factors() { have_factors = false; xprev.sparse = false; use_fop = false; }   // x_prev is only the packed block now
     // a block without the operator form's structures keeps no F: there the last converged Krylov projection's pairs stay
     // where the run left them -- Z[:, ritz_first .. +ritz_r) and vals[ritz_first ..) -- and ritz_ok says that x_prev of this
     // block is still their reconstruction: set at the end of that projection, dropped by whatever writes Z / vals (lanczos,
-    // lanczos_batch) or the block (project_block, the exit path's rescale).  Read by extract_factors only.
+    // lanczos_batch) or the block (project_block, project_blocks, the exit path's rescale).  Read by extract_factors only.
     bool ritz_ok = false;
     int ritz_first = 0, ritz_r = 0;
-    int last_npos = -1;                            // positive eigenvalues found by the last full_eig! of this block
     // early read-back of the recurrence coefficients (host_eig_merge): side stream + events (below) + pinned mirror
     PinnedBuf rec_early;
     SplitEig split;
@@ -307,9 +312,11 @@ struct EigWork {
     int b1_rot_K = 0;                              // > 0: a rotation is pending, U (K x kfirst, compact) at b1_rot_U (pinned staging)
     const double* b1_rot_U = nullptr;
     LzRun lzrun;                                   // host state of the run in progress (buffers reused across projections)
-    long long fel_served = 0;                      // full_eig! calls of this block served by the Lanczos engine
-    bool fel_disabled = false;                     // ... switched off after a failed verification (full_eig_lanczos_verify)
-    int fel_cert_fails = 0;                        // failed certificates of this block (full_eig_lanczos_certify)
+    struct LanczosFullEig {                        // full_eig! served by the Lanczos engine (full_eig_by_lanczos)
+        long long served = 0;                      // calls of this block it served
+        bool disabled = false;                     // ... switched off after a failed verification (full_eig_lanczos_verify)
+        int cert_fails = 0;                        // failed certificates of this block (full_eig_lanczos_certify)
+    } fel;
     DevBuf<double> warm_part;                      // partial sums of the warm start (k_lz_warm_sum)
     bool cye_pending = false;                      // cye[] hold a profiled k_lz_block1 launch
     const double* esv = nullptr;                   // support values of E for the projection in progress
@@ -326,12 +333,14 @@ struct EigWork {
     bool sg_small = false;                         // products on 32 x 32 tiles (blocks up to side 3072)
     int sg_nt48 = 0;                               // > 0: products on 48 x 48 tiles, this many per side (chosen by makespan)
     bool sg_pending = false;                       // fe[] hold a sign projection's events (all of it is "solver")
-    // cost-based engine choice on the Krylov branch (psd_sign_engine): wall-clock averages of this block's
-    // Lanczos and sign projections, projections since the last Lanczos probe, scratch for in-place calls
-    double kry_ms = -1.0, sign_ms = -1.0;
-    int sign_streak = 0, sign_backoff = 0;
-    int sign_verified_left = 0;                    // projections the engine may still serve before it is checked again
-    bool sign_disabled = false, sign_check_pending = false;
+    // cost-based engine choice on the Krylov branch (psd_sign_engine, exact_projection_by_sign): wall-clock averages of this
+    // block's Lanczos and sign projections, projections since the last Lanczos probe; below it the scratch for in-place calls
+    struct SignStandIn {
+        double kry_ms = -1.0, sign_ms = -1.0;
+        int streak = 0, backoff = 0;
+        int verified_left = 0;                     // projections the engine may still serve before it is checked again
+        bool disabled = false, check_pending = false;
+    } sign;
     DevBuf<double> sg_cmp;                         // max |difference|, max |value| of a verification
     DevBuf<double> sg_out;
     // streams and events last: destroyed before the buffers above
@@ -482,6 +491,7 @@ public:
     void lz_merge_vectors(EigWork& W, struct LzRun& R, int ncols);
     bool lz_split_first(EigWork& W, struct LzRun& R, int k1);
     void full_eig_values(EigWork& W, const double* xp, double offscale, bool vectors, std::vector<double>& Dhost);
+    void begin_full_eig_events(EigWork& W);
     void harvest_full_eig_events(EigWork& W);
     int block1_lds_cap = 0;                       // dynamic LDS granted to k_lz_block1 (setup_device)
     DevBuf<long long> b1_dbg;                     // PROXSDP_HIP_DEBUG_B1: tick sums of k_lz_block1 (prologue | loop | epilogue | steps | launches)
@@ -633,10 +643,20 @@ private:
 
     void primal_step_dev();
     void psd_projection(double* x);
-    void project_block(int idx, const double* xin, double* xout, bool fuse, bool lanczos_done = false);
+    // the dispatch of psd_projection! (projection.hip.hpp), in call order
     void project_blocks(const std::vector<int>& blocks, const double* xin, double* xout, bool fuse);
     bool krylov_branch(int idx) const;
     bool batch_eligible(int idx, bool fuse) const;
+    bool fop_eligible(const EigWork& W, bool fuse) const;
+    void arm_fop(EigWork& W);
+    void project_block(int idx, const double* xin, double* xout, bool fuse);
+    void full_eig_branch(int idx, const double* xp, double* xo, bool fuse);
+    void krylov_run(int idx, const double* xp, double* xo, bool fuse, int nev);
+    void finish_krylov_run(int idx, const double* xp, double* xo, bool fuse, int nev);
+    void ritz_pairs_to_block(int idx, const double* xp, double* xo, bool fuse, int first, int npos);
+    void dense_pairs_to_block(int idx, const double* xp_in, double* xp_out, bool fuse, int npos);
+    struct ShadowBookkeeping;
+    bool matches_shadow(EigWork& W, const double* xo);
     void setup_support();
     void setup_dense();
     std::vector<int> support_list() const;
@@ -681,8 +701,9 @@ private:
     }
     // the step kernels run Krylov dimensions up to 255; with lanczos_wide_krylov = 1 the wide kernels up to 511 (not under
     // krylovkit_eager, whose driver is written on the step kernels)
+    int krylov_dim(int nev) const { return std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos); }   // (eigsolver.jl: krylovdim / ncv)
     bool krylovdim_fits(int nev) const {
-        const int kd = std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos);
+        const int kd = krylov_dim(nev);
         if (kd <= dev::LZ_KMAX) return true;
         return opt.lanczos_wide_krylov == 1 && kd <= dev::LZW_MAXK - 1 && !(opt.krylovkit_eager && opt.eigsolver != 1);
     }
@@ -766,7 +787,7 @@ inline void Solver::alloc_eigwork(EigWork& W, int n, int max_nev) {
     // max(2 target_rank + 1, eigsolver_min_lanczos) is larger (options.jl:76,88 accept any value) is served by the dense
     // eigensolver instead (Solver::truncated_project_dense): the workspace is sized for what the kernels can run
     // (with lanczos_wide_krylov = 1 up to 511 columns: the wide kernels, lanczos_wide.hip.hpp)
-    const int kd_want = std::max(2 * max_nev + 1, (int)opt.eigsolver_min_lanczos);
+    const int kd_want = krylov_dim(max_nev);
     W.wide = opt.lanczos_wide_krylov == 1 && kd_want > dev::LZ_KMAX;
     int kd = std::min(kd_want, W.wide ? dev::LZW_MAXK - 1 : dev::LZ_KMAX);
     W.cap = kd + 1;
@@ -1158,7 +1179,7 @@ inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int 
 // with A = Symmetric(smat(xp)).  eigsolver == 1 selects ARPACK's acceptance rule
 // (dsaupd: |resid_i| <= tol*max(eps^(2/3), |theta_i|) for all nev wanted values,
 // eigsolver.jl:668-746) on the same thick-restart engine.
-// positive_part (full_eig! served by this engine, pdhg_loop.hip.hpp full_eig_by_lanczos): the wanted
+// positive_part (full_eig! served by this engine, projection.hip.hpp full_eig_by_lanczos): the wanted
 // set is "every eigenpair with lambda > 0", at most nev of them.  A cycle ends the run when all
 // positive Ritz pairs are converged to tol AND the first non-positive Ritz pair j is itself resolved
 // to 1e-7 of the spectral scale (the solver's own tol_psd is 1e-7; measured on the n = 4000 default
@@ -1175,7 +1196,7 @@ inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     // a restart rotation deferred into a launch that never came (an exception in the last run) is void
     W.b1_rot_K = 0; W.b1_rot_U = nullptr;
     R.arpack = (opt.eigsolver == 1);
-    int krylovdim = std::max(2 * nev + 1, (int)opt.eigsolver_min_lanczos);
+    int krylovdim = krylov_dim(nev);
     // positive-part mode is the library's own algorithm (not KrylovKit's call): a larger Krylov space
     // resolves the bulk-edge pairs that decide it with fewer restarts (options.full_eig_lanczos_kdim10)
     if (positive_part) {
@@ -2068,11 +2089,7 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
         W.sg_ld = ld;
     }
     const bool prof = opt.profile_symv_every > 0;
-    if (prof) {
-        for (Event& e : W.fe) e.create();
-        harvest_full_eig_events(W);
-        PX_HIP(hipEventRecord(W.fe[0], stream));
-    }
+    if (prof) begin_full_eig_events(W);
     const bool fz = fuse && use_support;
     double* sc = W.sg_sc.p;
     sign_unpack(W, xp_in, W.sgA.p, sc);
@@ -2119,8 +2136,7 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
     static const dev::SignSchedule sched;
     const int row_opt = opt.sign_start_row;
     const double tau = 4e-13 * (double)n;
-    int jmax = 0;
-    for (int j = 1; j + 2 < dev::SIGN_STEPS; ++j) if (std::sqrt(tau) / sched.gain[j] <= 1e-10) jmax = j;
+    const int jmax = sched.max_start_row(tau);
     // auto: per block, start at row 8 (the iterates of the SDPLIB solves fail its test once in 70 .. 400 projections);
     // a failure moves the next 8 projections two rows down (an eigenvalue crossing zero lingers for a few iterations),
     // a second failure soon after lowers the block's row for good (back up one row per 64 clean projections);
@@ -2166,9 +2182,7 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
                 if (W.sg_ok < 16) W.sg_row = std::max(0, W.sg_row - 1);
                 W.sg_hold = 8; W.sg_ok = 0;
             }
-            int r = 0;
-            for (int k = 0; k < dev::SIGN_STEPS; ++k) if (sched.l[k] <= 1e-10 * sched.gain[j0]) r = k;
-            run_rows(r, false);
+            run_rows(sched.fallback_row(j0), false);
         }
     }
     if (!resolved) {
@@ -2184,7 +2198,7 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
     if (!force) { W.lst.full_eigs++; W.lst.full_eigs_sign++; }
     current_rank[idx] = std::max(0, std::min(npos, n));
     min_eig[idx] = 0.0;                                      // prox_operators.jl:114
-    W.last_npos = current_rank[idx];
+    W.xprev.last_npos = current_rank[idx];
     return true;
 }
 
@@ -2279,61 +2293,6 @@ inline void Solver::test_sign_unpack(const double* packed, double sentinel, doub
     As.download(A, sz, stream);
     dsc.download(sc, 16, stream);
     PX_HIP(hipStreamSynchronize(stream));
-}
-
-inline void Solver::full_eig_project(int idx, const double* xp_in, double* xp_out, bool fuse) {
-    if (full_eig_by_sign(idx, xp_in, xp_out, fuse)) return;
-    EigWork& W = eig[idx];
-    std::vector<double> D;
-    const bool prof = opt.profile_symv_every > 0;
-    if (prof) {
-        for (Event& e : W.fe) e.create();
-        harvest_full_eig_events(W);                       // previous call's events (completed: see the sync below)
-        PX_HIP(hipEventRecord(W.fe[0], stream));
-    }
-    full_eig_values(W, xp_in, dev::INV_SQRT2, true, D);
-    if (prof) PX_HIP(hipEventRecord(W.fe[1], stream));
-    W.lst.full_eigs++;
-    const int n = W.n;
-    int npos = 0, rank = 0;
-    for (int i = 0; i < n; ++i) { if (D[i] > 0.0) ++npos; if (D[i] > opt.tol_psd) ++rank; }
-    current_rank[idx] = rank;
-    min_eig[idx] = 0.0;
-    W.last_npos = npos;
-    // ascending order: the positive eigenpairs are the trailing npos columns
-    launch_reconstruct(W, W.A.p + (size_t)(n - npos) * n, n, W.D.p + (n - npos), npos, xp_out,
-                       fuse ? xp_in : nullptr, fuse ? idx : -1);
-    if (prof) { PX_HIP(hipEventRecord(W.fe[2], stream)); W.fe_pending = true; }
-    W.recon_r += npos;
-}
-// The Krylov branch (prox_operators.jl:68-109) for a Krylov dimension the step kernels cannot hold (> 255 columns:
-// target_rank > 127, or eigsolver_min_lanczos > 255): the same truncated projection from the dense eigensolver -- the
-// top `nev` eigenpairs of dsyevd are what a converged KrylovKit / ARPACK run returns, min_eig is the smallest of them
-// (:74,:95), the positive ones among them rebuild the block (:78-85,:99-106).
-inline void Solver::truncated_project_dense(int idx, const double* xp_in, double* xp_out, bool fuse, int nev) {
-    EigWork& W = eig[idx];
-    std::vector<double> D;
-    full_eig_values(W, xp_in, dev::INV_SQRT2, true, D);
-    const int n = W.n, k = std::min(nev, n);
-    int npos = 0;
-    for (int i = n - k; i < n; ++i) if (D[i] > 0.0) ++npos;       // ascending: the top k are the trailing k
-    min_eig[idx] = D[n - k];
-    current_rank[idx] += npos;
-    W.last_npos = npos;
-    W.converged = true; W.converged_eigs = k;
-    launch_reconstruct(W, W.A.p + (size_t)(n - npos) * n, n, W.D.p + (n - npos), npos, xp_out,
-                       fuse ? xp_in : nullptr, fuse ? idx : -1);
-    W.recon_r += npos;
-    W.have_factors = false; W.x_prev_sparse = false; W.use_fop = false;
-    W.lst.dense_truncated_projections++;
-}
-inline void Solver::harvest_full_eig_events(EigWork& W) {
-    if (!W.fe_pending) return;
-    W.fe_pending = false;
-    if (hipEventSynchronize(W.fe[2]) != hipSuccess) return;
-    float a = 0.f, b = 0.f;
-    if (hipEventElapsedTime(&a, W.fe[0], W.fe[1]) == hipSuccess) W.lst.full_eig_solver_ms += a;
-    if (hipEventElapsedTime(&b, W.fe[1], W.fe[2]) == hipSuccess) W.lst.full_eig_recon_ms += b;
 }
 
 // ---- concurrent block projections (the job pool itself: block_pool.hpp)

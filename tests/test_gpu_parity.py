@@ -1899,6 +1899,29 @@ def _spectrum_cases(n, rng):
     return lam
 
 
+def test_sign_engine_leaves_a_block_of_side_32_to_lanczos():
+    """psd_sign_engine = 1 on a block below side 33 (exact_projection_by_sign's side exit, which comes before every exit
+    that depends on a measurement): the Krylov branch projects it.  Three positive eigenvalues under target rank 6, so the
+    truncated projection is the exact one (numpy.linalg.eigh); min_eig < 0 is the smallest pair Lanczos returned -- the
+    stand-in would report 0."""
+    n, tr = 32, 6
+    rng = np.random.default_rng(32)
+    lam = np.concatenate([[3.0, 2.0, 1.0], -rng.uniform(0.5, 2.0, n - 3)])
+    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    X = (Q * lam) @ Q.T
+    X = (X + X.T) / 2
+    w, V = np.linalg.eigh(X)
+    ref = svec((V * np.maximum(w, 0.0)) @ V.T)
+    o = B.default_options()
+    B.set_option(o, "psd_sign_engine", 1)
+    out, info = B.psd_project(svec(X), n, tr, mode=0, options=o)
+    plain, info0 = B.psd_project(svec(X), n, tr, mode=0)
+    print("max error", np.abs(out - ref).max(), info)
+    assert np.abs(out - ref).max() <= 2e-9 * np.abs(svec(X)).max()
+    assert info["rank"] == 3 and info["fell_back"] == 0 and info["nmatvec"] > 0 and info["min_eig"] < 0.0
+    assert np.array_equal(out, plain) and info == info0
+
+
 @pytest.mark.parametrize("n", [33, 64, 100, 257, 501, 1000, 1001, 1430])
 def test_sign_function_projection_against_lapack(n):
     """full_eig! by the matrix sign function (sign_project.hip.hpp; psd_project mode 4): X+ = (X + X sign X)/2
