@@ -50,6 +50,9 @@ extern "C" {
  * proxsdp_hip_solve_ex (capture / resume of the solver state at an iteration boundary); PROXSDP_E_COMM_ABORTED;
  * later: proxsdp_options gained lanczos_wide_krylov (from reserved_i2[0]), proxsdp_stats wide_krylov_projections
  * (from reserved_s[0]): same struct sizes and offsets, version unchanged;
+ * later: proxsdp_options gained device_eig_merge (the LAST slot of reserved_i2), proxsdp_stats.reserved_s[1..2] count the device
+ * merges and their fallbacks (PROXSDP_STATS_DEVICE_EIG_MERGES / _FALLBACKS), new test entry proxsdp_device_symeig_split: same
+ * sizes and offsets, version unchanged;
  * later: equilibration and approx_norm = 0 served with a dense A (proxsdp_hip_dense_scaling, proxsdp_host_equilibrate_rowsums),
  * proxsdp_stats dense_setup_passes / dense_sigma_steps (the last two reserved_s slots): same sizes and offsets, version unchanged;
  * later: a block-sharded solve accepts SOC cones, 1x1 PSD cones and variables outside every cone (such a shard runs the general
@@ -391,7 +394,17 @@ typedef struct proxsdp_options {
                                   * dimensions; wide_krylov_projections counts them).  Larger dimensions stay dense either way.
                                   * The workspace is wide only for a block whose max(2 max_target_rank_krylov_eigs + 1,
                                   * eigsolver_min_lanczos) exceeds 255.  Other values: PROXSDP_E_INVALID */
-    int32_t reserved_i2[7];      /* zero */
+    int32_t reserved_i2[6];      /* zero */
+    int32_t device_eig_merge;    /* (the last reserved_i2 slot: reserved_i2 keeps its offset)  the rank-one merge of the split
+                                  * K x K eigensolve (host_eig_merge) on the DEVICE (csrc/merge_device.hip.hpp): the host keeps the
+                                  * two QL decompositions and the deflation plan; secular roots, Gu-Eisenstat weights, the
+                                  * eigenvector product and the coefficients of the restart rotation are five short launches
+                                  * and never visit the host.  -1 auto = on for the step kernels wherever the split runs with a
+                                  * Krylov dimension >= 64, 0 = off (the merge stays on the host), 1 = on wherever the split
+                                  * runs (with host_eig_merge = 1 from Krylov dimension 24 on).  Wide, batched and one-workgroup
+                                  * runs and block worker threads keep the host merge; a merge the device hands back (a root at
+                                  * the iteration cap, a non-finite value) or could not take is counted in
+                                  * device_eig_merge_fallbacks and redone on the host. */
     double  full_eig_lanczos_warm_pow; /* start vector of a Lanczos-served full_eig! (positive-part run, the library's own engine): the
                                   * previous projection's Ritz vectors are summed with weights (lam_0 / lam_c)^p -- the pairs with the SMALL
                                   * eigenvalues are the ones such a run converges last, so they get the larger share.  Default 1.0
@@ -475,7 +488,10 @@ typedef struct proxsdp_stats {
     int64_t reserved_s[4];                /* [0] = sharded_general_iterations (PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS below):
                                            * iterations a block-sharded solve ran on the general vector path on THIS shard (a
                                            * shard with an SOC, a 1x1 PSD block or no PSD block; 0 on a support-path shard and
-                                           * in a solve that is not sharded); [1..3] zero */
+                                           * in a solve that is not sharded); [1] = device_eig_merges: merges of host_eig_merges
+                                           * whose O(k^2) part ran on the device (device_eig_merge); [2] = device_eig_merge_fallbacks:
+                                           * merges the host did while the device path was switched on (a shape or a thread it does
+                                           * not serve, or a merge it handed back); [3] zero */
     /* (the last two reserved slots: reserved_s keeps its offset) */
     int64_t dense_setup_passes;           /* set-up passes over a dense A (row sums + extrema, 8*p*n bytes): 1 when equilibration
                                            * was asked for, else 0 */
@@ -484,6 +500,8 @@ typedef struct proxsdp_stats {
 } proxsdp_stats;
 /* named slots of proxsdp_stats.reserved_s (the array keeps its four slots and its offset; a slot that gets a meaning keeps its place) */
 #define PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS 0
+#define PROXSDP_STATS_DEVICE_EIG_MERGES 1
+#define PROXSDP_STATS_DEVICE_EIG_MERGE_FALLBACKS 2
 
 /* Result (structs.jl:60-81).  Arrays are caller-allocated with the stated
  * lengths (NULL = not wanted); values are unscaled and in USER variable order
@@ -959,6 +977,21 @@ int proxsdp_host_symeig_split(int32_t K, int32_t m, int32_t k1, const double* D,
 /* the same with `threads` helper threads for the merge's independent pieces (options.host_merge_threads): bit-identical */
 int proxsdp_host_symeig_split_threads(int32_t K, int32_t m, int32_t k1, const double* D, const double* f,
                                       const double* al, const double* be, int32_t threads, double* U, double* d, int32_t* info);
+/* The same split with the rank-one merge on the DEVICE (options.device_eig_merge, csrc/merge_device.hip.hpp): first part and
+ * tail QL on the host, then the code the Lanczos driver runs -- plan without Qf, packed upload, the merge kernels -- on
+ * options-independent defaults (device 0's current context, a stream of its own).  Same outputs as proxsdp_host_symeig_split;
+ * PROXSDP_E_INTERNAL when the device hands the merge back.  Needs a HIP device. */
+int proxsdp_device_symeig_split(int32_t K, int32_t m, int32_t k1, const double* D, const double* f,
+                                const double* al, const double* be, double* U, double* d, int32_t* info);
+/* The planner of that merge (Rank1Merge::plan), for tests: the same split, then plan() with (with_qf = 1, what the host merge
+ * runs) or without Qf (what the device merge runs).  Q1 (k1 x k1) and Q2 (k2 x k2): the two parts' eigenvectors, column-major;
+ * Qf (K x K, written only when with_qf): the assembled and rotated eigenvector matrix in pole order; d, z (K): poles and
+ * weights after deflation; colsrc (K): pole p is column colsrc[p] of Q1 when >= 0, else column -(colsrc[p] + 1) of Q2;
+ * nd (K): the non-deflated poles, counts[0] of them; rot_idx (2 K) / rot_cs (2 K): the rotations (pj, j) / (c, s) in order,
+ * counts[2] of them (x = Qf[:, pj], y = Qf[:, j]: x <- c x + s y, y <- c y - s x); counts[1]: deflated poles. */
+int proxsdp_host_merge_plan(int32_t K, int32_t m, int32_t k1, const double* D, const double* f, const double* al,
+                            const double* be, int32_t with_qf, double* Q1, double* Q2, double* Qf, double* d, double* z,
+                            int32_t* colsrc, int32_t* nd, int32_t* rot_idx, double* rot_cs, int32_t* counts);
 /* the library's Lanczos start vector (init 3/2/1 as options.jl:98-103) */
 int proxsdp_host_start_vector(int64_t n, int64_t seed, int32_t init, double* out);
 /* preprocess!/norm_scaling (scaling.jl): returns the variable order, the

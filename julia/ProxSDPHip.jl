@@ -125,6 +125,10 @@ end
 # named slots of Stats.reserved_s (PROXSDP_STATS_* in the header, 0-based there): iterations a block-sharded solve ran on
 # the general vector path on this shard
 sharded_general_iterations(s::Stats) = s.reserved_s[1]
+# merges of host_eig_merges whose O(k^2) part ran on the device (option device_eig_merge), and merges the host did while
+# that path was switched on
+device_eig_merges(s::Stats) = s.reserved_s[2]
+device_eig_merge_fallbacks(s::Stats) = s.reserved_s[3]
 
 mutable struct CResult           # proxsdp_result
     status::Int32

@@ -113,7 +113,7 @@ def _opt_fields():
     a("sign_start_row", i32); a("general_batch", i32); a("full_eig_lanczos_certify", i32); a("host_merge_threads", i32); a("reserved_i", i32 * 1)
     a("full_eig_lanczos_tol", f64); a("reserved_d", f64 * 1)
     a("equilibration_reference_aliasing", i32); a("reserved_i3", i32 * 2)
-    a("block_batch_groups", i32); a("lanczos_wide_krylov", i32); a("reserved_i2", i32 * 7); a("full_eig_lanczos_warm_pow", f64); a("reserved_d2", f64 * 3)
+    a("block_batch_groups", i32); a("lanczos_wide_krylov", i32); a("reserved_i2", i32 * 6); a("device_eig_merge", i32); a("full_eig_lanczos_warm_pow", f64); a("reserved_d2", f64 * 3)
     return F
 
 
@@ -156,7 +156,7 @@ class Result(C.Structure):
 
 
 # named slots of Stats.reserved_s (include/proxsdp_hip.h PROXSDP_STATS_*): SolveResult.stats lists them under their names
-STATS_RESERVED_SLOTS = {"sharded_general_iterations": 0}
+STATS_RESERVED_SLOTS = {"sharded_general_iterations": 0, "device_eig_merges": 1, "device_eig_merge_fallbacks": 2}
 
 STATE_NHIST = 7
 STATE_HIST_NAMES = ("dual_gap", "prim_obj", "dual_obj", "feasibility", "primal_residual", "dual_residual", "comb_residual")
@@ -1199,6 +1199,47 @@ def host_symeig_split(D, f, al, be, k1, threads=0):
     _check(L.proxsdp_host_symeig_split_threads(K, m, int(k1), _p(D) if m else None, _p(f) if m else None, _p(al), _p(be),
                                                int(threads), _p(U), _p(d), info))
     return d, U.T.copy(), dict(nondeflated=info[0], deflated=info[1], max_secular_iterations=info[2])
+
+
+def device_symeig_split(D, f, al, be, k1):
+    """proxsdp_device_symeig_split: host_symeig_split with the rank-one merge run by the device kernels the Lanczos driver
+    uses (options.device_eig_merge).  Returns (d ascending, U, info dict); needs a HIP device."""
+    D = _f(D); f = _f(f); al = _f(al); be = _f(be)
+    K, m = len(al), len(D)
+    U = np.zeros((K, K))
+    d = np.zeros(K)
+    info = (i32 * 3)()
+    L = lib()
+    L.proxsdp_device_symeig_split.argtypes = [i32, i32, i32, pf64, pf64, pf64, pf64, pf64, pf64, C.POINTER(i32)]
+    L.proxsdp_device_symeig_split.restype = C.c_int
+    _check(L.proxsdp_device_symeig_split(K, m, int(k1), _p(D) if m else None, _p(f) if m else None, _p(al), _p(be),
+                                         _p(U), _p(d), info))
+    return d, U.T.copy(), dict(nondeflated=info[0], deflated=info[1], max_secular_iterations=info[2])
+
+
+def host_merge_plan(D, f, al, be, k1, with_qf):
+    """proxsdp_host_merge_plan: the split at k1 and Rank1Merge::plan() with or without Qf.  Returns a dict: Q1, Q2 (the two
+    parts' eigenvectors), Qf (None without it), d, z, colsrc, nd, rots = [(pj, j, c, s), ...], deflated."""
+    D = _f(D); f = _f(f); al = _f(al); be = _f(be)
+    K, m = len(al), len(D)
+    k1 = int(k1); k2 = K - k1
+    Q1 = np.zeros((k1, k1)); Q2 = np.zeros((k2, k2)); Qf = np.zeros((K, K))
+    d = np.zeros(K); z = np.zeros(K)
+    colsrc = np.zeros(K, dtype=np.int32); nd = np.zeros(K, dtype=np.int32)
+    ridx = np.zeros(2 * K, dtype=np.int32); rcs = np.zeros(2 * K)
+    counts = (i32 * 3)()
+    pi32 = C.POINTER(i32)
+    L = lib()
+    L.proxsdp_host_merge_plan.argtypes = [i32, i32, i32, pf64, pf64, pf64, pf64, i32, pf64, pf64, pf64, pf64, pf64,
+                                          pi32, pi32, pi32, pf64, pi32]
+    L.proxsdp_host_merge_plan.restype = C.c_int
+    _check(L.proxsdp_host_merge_plan(K, m, k1, _p(D) if m else None, _p(f) if m else None, _p(al), _p(be), int(bool(with_qf)),
+                                     _p(Q1), _p(Q2), _p(Qf), _p(d), _p(z), colsrc.ctypes.data_as(pi32), nd.ctypes.data_as(pi32),
+                                     ridx.ctypes.data_as(pi32), _p(rcs), counts))
+    k, ndf, nrot = counts[0], counts[1], counts[2]
+    rots = [(int(ridx[2 * q]), int(ridx[2 * q + 1]), float(rcs[2 * q]), float(rcs[2 * q + 1])) for q in range(nrot)]
+    return dict(Q1=Q1.T.copy(), Q2=Q2.T.copy(), Qf=Qf.T.copy() if with_qf else None, d=d, z=z, colsrc=colsrc.copy(),
+                nd=nd[:k].copy(), rots=rots, deflated=ndf)
 
 
 def host_preprocess(prob, index_base=0):

@@ -1001,6 +1001,61 @@ int proxsdp_host_symeig_split_threads(int32_t K, int32_t m, int32_t k1, const do
         return 0;
     });
 }
+int proxsdp_device_symeig_split(int32_t K, int32_t m, int32_t k1, const double* D, const double* f,
+                                const double* al, const double* be, double* U, double* d, int32_t* info) {
+    return guarded([&]() -> int {
+        if (K < 2 || m < 0 || m >= K || k1 < 1 || k1 >= K || !al || !be || !U || !d) throw std::invalid_argument("invalid argument");
+        if (!proxsdp::DeviceMerge::eligible(K)) throw std::invalid_argument("device merge serves 2 <= K <= 255");
+        proxsdp::SplitEig S;
+        if (S.first(k1, m, D, f, al, be) != 0 || S.tail(K, al, be) != 0) throw std::invalid_argument("split eigensolver failed");
+        proxsdp::DeviceMerge dm;                             // (declared before the stream: buffers outlive the handle)
+        proxsdp::Stream st;
+        st.create(hipStreamNonBlocking);
+        dm.stage_first(S, st);
+        std::vector<double> Dd(K), fd(K);
+        const bool ok = dm.run(S, K, 1.0, st, [](hipEvent_t e) { PX_HIP(hipEventSynchronize(e)); }, Dd.data(), fd.data());
+        std::vector<double> Ud((size_t)K * K);
+        std::vector<int> it(std::max(dm.k, 1), 0);
+        dm.Uall.download(Ud.data(), Ud.size(), st);
+        if (dm.k > 0) dm.iters_d.download(it.data(), (size_t)dm.k, st);
+        PX_HIP(hipStreamSynchronize(st));
+        if (!ok) throw std::runtime_error("device merge handed the eigensolve back");
+        for (int c = 0; c < K; ++c) {                        // the device's order is descending
+            d[c] = Dd[K - 1 - c];
+            std::copy(Ud.begin() + (size_t)(K - 1 - c) * K, Ud.begin() + (size_t)(K - c) * K, U + (size_t)c * K);
+        }
+        if (info) { info[0] = dm.k; info[1] = dm.ndf; info[2] = dm.k > 0 ? *std::max_element(it.begin(), it.end()) : 0; }
+        return 0;
+    });
+}
+
+int proxsdp_host_merge_plan(int32_t K, int32_t m, int32_t k1, const double* D, const double* f, const double* al,
+                            const double* be, int32_t with_qf, double* Q1, double* Q2, double* Qf, double* d, double* z,
+                            int32_t* colsrc, int32_t* nd, int32_t* rot_idx, double* rot_cs, int32_t* counts) {
+    return guarded([&]() -> int {
+        if (K < 2 || m < 0 || m >= K || k1 < 1 || k1 >= K || !al || !be || !Q1 || !Q2 || !Qf || !d || !z || !colsrc || !nd ||
+            !rot_idx || !rot_cs || !counts) throw std::invalid_argument("invalid argument");
+        proxsdp::SplitEig S;
+        if (S.first(k1, m, D, f, al, be) != 0 || S.tail(K, al, be) != 0) throw std::invalid_argument("split eigensolver failed");
+        const int k2 = K - k1;
+        proxsdp::Rank1Merge& M = S.M;
+        M.plan(k1, k2, S.Q1.data(), S.d1.data(), S.Q2.data(), S.d2.data(), S.beta, with_qf != 0);
+        std::copy(S.Q1.begin(), S.Q1.end(), Q1);
+        std::copy(S.Q2.begin(), S.Q2.end(), Q2);
+        if (with_qf) std::copy(M.Qf.begin(), M.Qf.end(), Qf);
+        std::copy(M.d.begin(), M.d.end(), d);
+        std::copy(M.z.begin(), M.z.end(), z);
+        std::copy(M.colsrc.begin(), M.colsrc.end(), colsrc);
+        std::copy(M.nd.begin(), M.nd.end(), nd);
+        for (size_t q = 0; q < M.rots.size(); ++q) {
+            rot_idx[2 * q] = M.rots[q].pj; rot_idx[2 * q + 1] = M.rots[q].j;
+            rot_cs[2 * q] = M.rots[q].c; rot_cs[2 * q + 1] = M.rots[q].s;
+        }
+        counts[0] = M.k; counts[1] = (int)M.df.size(); counts[2] = (int)M.rots.size();
+        return 0;
+    });
+}
+
 int proxsdp_host_start_vector(int64_t n, int64_t seed, int32_t init, double* out) {
     if (n < 0 || !out) { g_last_error = "invalid argument"; return PROXSDP_E_INVALID; }
     proxsdp::start_vector(n, (uint64_t)seed, init, out);

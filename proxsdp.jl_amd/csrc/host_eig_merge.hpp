@@ -61,6 +61,17 @@ static inline void rank1_panel_8x4(const double* Qf, int K, const int* qcol, int
 }
 #endif
 
+// whether vectors() below takes the AVX2 + FMA panel kernel for its blocks of eight rows (checked once at run time; the
+// scalar loop serves the remaining rows and any other host).  The device merge reproduces the host's bits and asks too.
+static inline bool rank1_panel_uses_fma() {
+#if defined(__x86_64__)
+    static const bool have_fma = __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma");
+    return have_fma;
+#else
+    return false;
+#endif
+}
+
 // par(n, body): run body(0) .. body(n-1), possibly on helper threads (the driver passes its spin pool); nullptr = serial.
 // Every root / column is computed by the same code whichever thread takes it: results do not depend on the runner.
 using ParFor = std::function<void(int, const std::function<void(int)>&)>;
@@ -171,6 +182,19 @@ struct Rank1Merge {
     // Build the merged problem.  Q1 (k1 x k1), Q2 (k2 x k2) column-major eigenvectors of T1', T2' (d1, d2 ascending);
     // beta = the coupling entry T[k1-1, k1] (T1' and T2' already carry the -|beta| corrections on their corner entries).
     void build(int k1_, int k2_, const double* Q1, const double* d1, const double* Q2, const double* d2, double beta) {
+        plan(k1_, k2_, Q1, d1, Q2, d2, beta, true);
+        solve();
+    }
+
+    // First half of build(): the merged pole list, z, the deflation scan and the non-deflated poles dn / zn.
+    // with_Qf = false (device merge, merge_device.hip.hpp): Qf is neither assembled nor rotated; colsrc and rots record
+    // what assembles it -- column p of Qf is column colsrc[p] of Q1 (rows [0, k1)) when colsrc[p] >= 0, otherwise column
+    // -(colsrc[p] + 1) of Q2 (rows [k1, K)), and then the rotations apply in list order:
+    //     x = Qf[:, pj], y = Qf[:, j]:   x <- c x + s y,   y <- c y - s x
+    struct Rot { int pj, j; double c, s; };
+    std::vector<int> colsrc;
+    std::vector<Rot> rots;
+    void plan(int k1_, int k2_, const double* Q1, const double* d1, const double* Q2, const double* d2, double beta, bool with_Qf) {
         const double eps = 2.220446049250313e-16;
         k1 = k1_; k2 = k2_; K = k1 + k2;
         const double sgn = beta < 0.0 ? -1.0 : 1.0;
@@ -178,19 +202,22 @@ struct Rank1Merge {
         const double isq2 = 0.70710678118654752440;
         // ---- merge the two sorted pole lists
         d.assign(K, 0.0); z.assign(K, 0.0); ctype.assign(K, 0);
-        Qf.assign((size_t)K * K, 0.0);
+        colsrc.assign(K, 0); rots.clear();
+        if (with_Qf) Qf.assign((size_t)K * K, 0.0);
         {
             int a = 0, b = 0;
             for (int p = 0; p < K; ++p) {
                 const bool takeA = (b >= k2) || (a < k1 && d1[a] <= d2[b]);
-                double* col = Qf.data() + (size_t)p * K;
+                double* col = with_Qf ? Qf.data() + (size_t)p * K : nullptr;
                 if (takeA) {
                     d[p] = d1[a]; z[p] = Q1[(size_t)a * k1 + (k1 - 1)] * isq2; ctype[p] = 1;
-                    for (int r = 0; r < k1; ++r) col[r] = Q1[(size_t)a * k1 + r];
+                    colsrc[p] = a;
+                    if (with_Qf) for (int r = 0; r < k1; ++r) col[r] = Q1[(size_t)a * k1 + r];
                     ++a;
                 } else {
                     d[p] = d2[b]; z[p] = sgn * Q2[(size_t)b * k2] * isq2; ctype[p] = 2;
-                    for (int r = 0; r < k2; ++r) col[k1 + r] = Q2[(size_t)b * k2 + r];
+                    colsrc[p] = -(b + 1);
+                    if (with_Qf) for (int r = 0; r < k2; ++r) col[k1 + r] = Q2[(size_t)b * k2 + r];
                     ++b;
                 }
             }
@@ -213,12 +240,15 @@ struct Rank1Merge {
                 c /= tau; s = -s / tau;
                 if (std::fabs(t * c * s) <= tol) {
                     z[j] = tau; z[pj] = 0.0;
-                    double* __restrict__ x = Qf.data() + (size_t)pj * K;
-                    double* __restrict__ y = Qf.data() + (size_t)j * K;
-                    for (int r = 0; r < K; ++r) {
-                        const double xr = x[r], yr = y[r];
-                        x[r] = c * xr + s * yr;
-                        y[r] = c * yr - s * xr;
+                    rots.push_back(Rot{pj, j, c, s});
+                    if (with_Qf) {
+                        double* __restrict__ x = Qf.data() + (size_t)pj * K;
+                        double* __restrict__ y = Qf.data() + (size_t)j * K;
+                        for (int r = 0; r < K; ++r) {
+                            const double xr = x[r], yr = y[r];
+                            x[r] = c * xr + s * yr;
+                            y[r] = c * yr - s * xr;
+                        }
                     }
                     const double tt = d[pj] * c * c + d[j] * s * s;
                     d[j] = d[pj] * s * s + d[j] * c * c;
@@ -239,6 +269,11 @@ struct Rank1Merge {
         // (a rotation can leave d[pj] marginally above the next pole: keep the non-deflated poles increasing)
         for (int j = 1; j < k; ++j)
             if (!(dn[j] > dn[j - 1])) dn[j] = std::nextafter(dn[j - 1], 1e300);
+    }
+
+    // Second half of build(): secular roots, Gu-Eisenstat weights, the eigenvectors of D + rho z z' and the order of
+    // the K eigenvalues, from what plan() left.
+    void solve() {
         // ---- secular equation: roots and the differences dn[j] - lam[i]
         lam.assign(k, 0.0);
         delta.assign((size_t)k * k, 0.0);
@@ -356,7 +391,7 @@ struct Rank1Merge {
                 int r = 0;
 #if defined(__x86_64__)
                 // (the panel kernel needs AVX2 + FMA: checked once at run time, the scalar loop below serves any other host)
-                static const bool have_fma = __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma");
+                const bool have_fma = rank1_panel_uses_fma();
                 for (; have_fma && r + 8 <= nr; r += 8)
                     rank1_panel_8x4(Qf.data(), K, qcol.data(), kk, r0 + r, w0, w1, w2, w3, u[0] ? u[0] + r : nullptr,
                                     u[1] ? u[1] + r : nullptr, u[2] ? u[2] + r : nullptr, u[3] ? u[3] + r : nullptr);

@@ -575,6 +575,14 @@ struct SplitEig {
         return rc;
     }
     int second(int K_, const double* al, const double* be) {
+        if (tail(K_, al, be) != 0) return 1;
+        merge_host();
+        return 0;
+    }
+    // the two pieces of second(): the QL of the tridiagonal tail T2' (Q2, d2), and the merge on the host.  The device
+    // merge (merge_device.hip.hpp) runs between them and calls merge_host() only when it has to hand a merge back.
+    void merge_host() { M.build(k1, K - k1, Q1.data(), d1.data(), Q2.data(), d2.data(), beta); }
+    int tail(int K_, const double* al, const double* be) {
         K = K_;
         const int k2 = K - k1;
         if (!have_first || k2 < 1) return 1;
@@ -584,9 +592,7 @@ struct SplitEig {
             if (j + 1 < k2) { Q2[(size_t)j * k2 + j + 1] = be[k1 + j]; Q2[(size_t)(j + 1) * k2 + j] = be[k1 + j]; }
         }
         Q2[0] -= std::fabs(beta);
-        if (symeig_dense(k2, Q2.data(), d2.data(), true, 0) != 0) return 1;
-        M.build(k1, k2, Q1.data(), d1.data(), Q2.data(), d2.data(), beta);
-        return 0;
+        return symeig_dense(k2, Q2.data(), d2.data(), true, 0) != 0 ? 1 : 0;
     }
 };
 
@@ -641,7 +647,7 @@ inline const std::vector<OptEntry>& option_table() {
         PX_OPT(rocsolver_warmup, OT_I32), PX_OPT(debug_fail_iteration, OT_I32), PX_OPT(host_wait_spin, OT_I32), PX_OPT(sign_start_row, OT_I32), PX_OPT(general_batch, OT_I32),
         PX_OPT(full_eig_lanczos_certify, OT_I32), PX_OPT(full_eig_lanczos_tol, OT_F64), PX_OPT(host_merge_threads, OT_I32),
         PX_OPT(equilibration_reference_aliasing, OT_I32), PX_OPT(block_batch_groups, OT_I32), PX_OPT(full_eig_lanczos_warm_pow, OT_F64),
-        PX_OPT(lanczos_wide_krylov, OT_I32),
+        PX_OPT(lanczos_wide_krylov, OT_I32), PX_OPT(device_eig_merge, OT_I32),
     };
     return t;
 }
@@ -686,7 +692,7 @@ inline void default_options(proxsdp_options* o) {      // options.jl:1-132
     o->host_eig_merge = -1; o->block_batch = -1; o->rocsolver_warmup = 0; o->host_wait_spin = -1; o->sign_start_row = -1; o->general_batch = -1;
     o->full_eig_lanczos_certify = -1; o->full_eig_lanczos_tol = 0.0; o->host_merge_threads = -1;
     o->equilibration_reference_aliasing = 1; o->block_batch_groups = -1; o->full_eig_lanczos_warm_pow = 1.0;
-    o->lanczos_wide_krylov = 0;
+    o->lanczos_wide_krylov = 0; o->device_eig_merge = -1;
 }
 
 inline int set_option(proxsdp_options* o, const char* name, double v) {

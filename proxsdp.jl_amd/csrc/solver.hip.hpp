@@ -173,6 +173,7 @@ inline void poll_ready(Query query, GiveUp give_up) {
 }
 }  // namespace proxsdp
 #include "shard_comm.hip.hpp"       // (the transports of a block-sharded solve: built on the buffers and macros above)
+#include "merge_device.hip.hpp"     // (the rank-one merge of the split eigensolve on the device: the same buffers and owners)
 namespace proxsdp {
 
 // structs.jl:2-30
@@ -244,6 +245,11 @@ struct LzRun {
     SplitEig& split_ref() { return *splitp; }
     bool split_ready = false;         // split.first() succeeded for the cycle in progress
     bool merge_active = false;        // D / f of the last eigensolve came from the merge: U holds no vectors yet
+    // device merge (merge_device.hip.hpp, options.device_eig_merge)
+    bool dev_wanted = false;          // the option asks for it at this run's Krylov dimension (a merge on the host is a fallback)
+    bool dev_merge = false;           // ... and the run is one the device path serves: this run's merges go to the device
+    bool dev_staged = false;          // Q1 of the cycle in progress is on its way to the device
+    bool merge_on_device = false;     // the last merge ran there: the Ritz-vector coefficients are DeviceMerge::Uall
     std::vector<double> erow;
 };
 
@@ -306,6 +312,7 @@ struct EigWork {
     // early read-back of the recurrence coefficients (host_eig_merge): side stream + events (below) + pinned mirror
     PinnedBuf rec_early;
     SplitEig split;
+    DeviceMerge dmerge;                            // buffers of the device merge (allocated on first use)
     int batch_slot = 0;                            // position of this block in the batched run in progress
     // one-workgroup cycle kernel (lanczos_block1.hip.hpp): the restart rotation is deferred into the next cycle's launch
     bool b1_defer = false;                         // Solver::rotate stages U and returns (set around lz_after_cycle)
@@ -511,6 +518,7 @@ public:
     void extract_factors(const std::vector<double>& x);
     void rotate(EigWork& W, int K, const std::vector<double>& U, int ldu, int ncols, double* out, int copy_src, int copy_dst,
                 const double* extra, int nextra);
+    void rotate_launch(EigWork& W, int K, const double* Ud, int ncols, double* out, int copy_src, int copy_dst);
 
     // test hooks (capi.hip)
     void test_project(int idx, double* xp, int tr);
@@ -1140,10 +1148,15 @@ inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int 
     }
     W.U.upload(tmp, (size_t)K * ncols + (size_t)std::max(nextra, 0), stream);
     if (nextra > 0) W.arrow_p = W.U.p + (size_t)K * ncols;
+    rotate_launch(W, K, W.U.p, ncols, out, copy_src, copy_dst);
+}
+
+// the launches of rotate(): out[:, :ncols] = V[:, :K] U, U (K x ncols, compact, column-major) on the device
+inline void Solver::rotate_launch(EigWork& W, int K, const double* Ud, int ncols, double* out, int copy_src, int copy_dst) {
     if (W.lzrun.wide) {                                  // wide run: LDS-tiled over K (neither form below fits at K > 255)
         if (ncols > 0 || copy_src >= 0)
             hipLaunchKernelGGL(dev::k_lzw_rotate, dim3(W.nt, std::max(1, ceil_div(ncols, dev::LZW_RC))), dim3(dev::TPB), 0, stream,
-                               (const double*)W.V.p, W.npad, K, (const double*)W.U.p, ncols, out, W.npad, copy_src, copy_dst);
+                               (const double*)W.V.p, W.npad, K, Ud, ncols, out, W.npad, copy_src, copy_dst);
         return;
     }
     // fp64 MFMA form from K = 32 / 16 columns on (skinny GEMM); grid = row tiles x groups of 16 columns; LDS: V tile + one U group
@@ -1152,7 +1165,7 @@ inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int 
         const size_t lds_m = ((size_t)Kp * dev::RM_LDV + (size_t)dev::RM_CG * (Kp + 2)) * sizeof(double);
         if (K >= 32 && ncols >= 16 && (int)lds_m <= rotate_mfma_lds_cap) {
             hipLaunchKernelGGL(dev::k_lz_rotate_mfma, dim3(W.nt, ceil_div(ncols, dev::RM_CG)), dim3(dev::TPB), lds_m, stream,
-                               (const double*)W.V.p, W.npad, K, (const double*)W.U.p, ncols, out, W.npad, copy_src, copy_dst);
+                               (const double*)W.V.p, W.npad, K, Ud, ncols, out, W.npad, copy_src, copy_dst);
             return;
         }
     }
@@ -1168,7 +1181,7 @@ inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int 
         const bool last = (c0 + cn >= ncols);
         if (cn > 0 || (last && copy_src >= 0))
             hipLaunchKernelGGL(dev::k_lz_rotate, dim3(W.nt), dim3(dev::TPB), (size_t)K * cn * 8 + vbytes, stream,
-                               W.V.p, W.npad, W.n, K, W.U.p + (size_t)c0 * K, K, cn,
+                               W.V.p, W.npad, W.n, K, Ud + (size_t)c0 * K, K, cn,
                                out + (size_t)c0 * W.npad, W.npad, last ? copy_src : -1, copy_dst - c0);
         c0 += std::max(cn, 1);
     } while (c0 < ncols);
@@ -1224,6 +1237,7 @@ inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     R.howmany = nev; R.numiter = 1; R.converged = 0; R.K = 0; R.kfirst = 0; R.pos_count = -1;
     R.pos_fail = false; R.presymv = false; R.betaK = 0.0;
     R.split_ready = false; R.merge_active = false;
+    R.dev_wanted = R.dev_merge = R.dev_staged = R.merge_on_device = false;
     R.splitp = &W.split;
     return true;
 }
@@ -1284,23 +1298,39 @@ inline bool Solver::lz_after_cycle(EigWork& W, LzRun& R, bool speculated) {
         return false;
     }
     if (betaK <= tol && K < R.howmany && !R.arpack) R.howmany = K;
-    R.merge_active = false;
+    R.merge_active = false; R.merge_on_device = false;
     if (K > 1 && R.split_ready && K == krylovdim) {
-        // split + rank-one merge: T1' was decomposed while the GPU ran the cycle; here the tail and the merge
+        // split + rank-one merge: T1' was decomposed while the GPU ran the cycle; here the tail and the merge --
+        // on the device (merge_device.hip.hpp: D and f come back in one small record, the vectors stay there) or on the host
         const double te0 = now_s();
-        if (R.split_ref().second(K, al.data(), be.data()) == 0) {
-            R.erow.resize(K);
-            R.split_ref().M.row_of_vectors(K - 1, R.erow.data());
-            for (int c = 0; c < K; ++c) {                // :LR -> descending
-                D[c] = R.split_ref().M.evals[K - 1 - c];
-                f[c] = betaK * R.erow[K - 1 - c];
+        double waited = 0.0;                             // (host_eig_time is host compute: not the wait for the record)
+        SplitEig& Sp = R.split_ref();
+        if (Sp.tail(K, al.data(), be.data()) == 0) {
+            bool on_device = false;
+            if (R.dev_merge && R.dev_staged)
+                on_device = W.dmerge.run(Sp, K, betaK, stream, [&](hipEvent_t e) {
+                    const double tw0 = now_s();
+                    wait_event(e);
+                    waited = now_s() - tw0;
+                }, D.data(), f.data());
+            if (on_device) {
+                W.lst.reserved_s[PROXSDP_STATS_DEVICE_EIG_MERGES]++;
+            } else {
+                if (R.dev_wanted) W.lst.reserved_s[PROXSDP_STATS_DEVICE_EIG_MERGE_FALLBACKS]++;
+                Sp.merge_host();
+                R.erow.resize(K);
+                Sp.M.row_of_vectors(K - 1, R.erow.data());
+                for (int c = 0; c < K; ++c) {            // :LR -> descending
+                    D[c] = Sp.M.evals[K - 1 - c];
+                    f[c] = betaK * R.erow[K - 1 - c];
+                }
             }
-            R.merge_active = true;
+            R.merge_active = true; R.merge_on_device = on_device;
             W.lst.host_eigs++; W.lst.host_eig_merges++;
         }
-        W.lst.host_eig_time += now_s() - te0;
+        W.lst.host_eig_time += now_s() - te0 - waited;
     }
-    R.split_ready = false;
+    R.split_ready = false; R.dev_staged = false;
     // (after a merge the Ritz-vector coefficients are formed in lz_restart / lz_finish_run, for the columns actually needed)
     if (!R.merge_active) lz_rayleigh(W, R, K, betaK, true, kfirst == 0);
     int converged = 0;
@@ -1379,9 +1409,16 @@ inline void Solver::lz_restart(EigWork& W, LzRun& R, int K, int keep, bool specu
     // arrow part of the restarted T for k_lz_orth: f (couplings of v_K with the kept Ritz
     // vectors) and D (their Ritz values)
     // (the wide kernels measure both passes: no arrow part)
-    if (!R.wide) for (int j = 0; j < keep; ++j) { W.arrow_host.p[j] = f[j]; W.arrow_host.p[dev::MAXK + j] = D[j]; }
-    if (R.merge_active) lz_merge_vectors(W, R, keep);
-    rotate(W, K, R.U, K, keep, W.Z.p, K, keep, W.arrow_host.p, R.wide ? 0 : 2 * dev::MAXK);   // Z[:, :keep] = V U[:, :keep]; Z[:, keep] = V[:, K]
+    if (R.merge_on_device) {
+        // the merge's record is f | D in the layout k_lz_orth reads (it stays put until the next merge, a whole cycle away)
+        // and its U is on the device already: no staging, no upload
+        W.arrow_p = W.dmerge.rec_d.p;
+        rotate_launch(W, K, W.dmerge.Uall.p, keep, W.Z.p, K, keep);
+    } else {
+        if (!R.wide) for (int j = 0; j < keep; ++j) { W.arrow_host.p[j] = f[j]; W.arrow_host.p[dev::MAXK + j] = D[j]; }
+        if (R.merge_active) lz_merge_vectors(W, R, keep);
+        rotate(W, K, R.U, K, keep, W.Z.p, K, keep, W.arrow_host.p, R.wide ? 0 : 2 * dev::MAXK);   // Z[:, :keep] = V U[:, :keep]; Z[:, keep] = V[:, K]
+    }
     std::swap(W.V.p, W.Z.p);
     std::fill(R.T.begin(), R.T.end(), 0.0);
     const int ld = R.ld;
@@ -1404,6 +1441,7 @@ inline void Solver::lz_finish_run(EigWork& W, LzRun& R) {
         if (R.pos_fail || R.pos_count < 0) { W.converged = false; return; }
         W.count = R.pos_count; W.converged_eigs = R.pos_count; W.converged = true;
         W.vals.assign(R.D.begin(), R.D.begin() + R.pos_count);
+        if (R.pos_count > 0 && R.merge_on_device) { rotate_launch(W, K, W.dmerge.Uall.p, R.pos_count, W.Z.p, -1, 0); return; }
         if (R.pos_count > 0 && R.merge_active) lz_merge_vectors(W, R, R.pos_count);
         if (R.pos_count > 0) rotate(W, K, R.U, K, R.pos_count, W.Z.p, -1, 0, nullptr, 0);
         return;
@@ -1429,6 +1467,7 @@ inline void Solver::lz_finish_run(EigWork& W, LzRun& R) {
     W.vals.assign(R.D.begin(), R.D.begin() + howmany);
     W.converged_eigs = R.converged;
     W.converged = (R.converged != 0);                    // eigsolver.jl:816-818
+    if (R.merge_on_device) { rotate_launch(W, K, W.dmerge.Uall.p, howmany, W.Z.p, -1, 0); return; }
     if (R.merge_active) lz_merge_vectors(W, R, howmany);
     rotate(W, K, R.U, K, howmany, W.Z.p, -1, 0, nullptr, 0);          // Ritz vectors B*v
 }
@@ -1520,6 +1559,9 @@ inline bool Solver::lz_split_first(EigWork& W, LzRun& R, int k1) {
         ok = R.split_ref().first(k1, m, Dk.data(), fk.data(), al_e, be_e) == 0;
     }
     R.split_ready = ok;
+    // device merge: Q1 goes up on the side stream now, under the remaining steps; the merge's launches wait on its event
+    R.dev_staged = false;
+    if (ok && R.dev_merge) { W.dmerge.stage_first(R.split_ref(), W.side); R.dev_staged = true; }
     W.lst.host_eig_overlap_time += now_s() - t0;
     return ok;
 }
@@ -1682,6 +1724,10 @@ inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive
         W.split.M.par = &merge_par;
         W.split.M.nchunk = merge_helpers() + 1;
     }
+    // the merge itself on the device (options.device_eig_merge): single-block runs of the step kernels on the solver's own
+    // thread; a batched run has no split, a block worker thread keeps the host merge (counted as a fallback)
+    R.dev_wanted = use_split && (opt.device_eig_merge == 1 || (opt.device_eig_merge < 0 && krylovdim >= 64));
+    R.dev_merge = R.dev_wanted && rot_sink == nullptr && StreamRef::tl == nullptr && DeviceMerge::eligible(krylovdim);
     if (use_split && W.side == nullptr) {
         W.side.create(hipStreamNonBlocking);
         W.ev_mid.create(hipEventDisableTiming);
@@ -2338,6 +2384,7 @@ inline void Solver::merge_block_stats() {
         PX_MERGE(sign_engine_checks); PX_MERGE(sign_engine_mismatches);
         PX_MERGE(batched_block_steps);
         PX_MERGE(host_eigs); PX_MERGE(host_eig_time); PX_MERGE(host_eig_merges); PX_MERGE(host_eig_overlap_time);
+        PX_MERGE(reserved_s[PROXSDP_STATS_DEVICE_EIG_MERGES]); PX_MERGE(reserved_s[PROXSDP_STATS_DEVICE_EIG_MERGE_FALLBACKS]);
         PX_MERGE(warm_starts); PX_MERGE(device_eigs); PX_MERGE(mfma_reconstructions);
         PX_MERGE(cycle_launches); PX_MERGE(cycle_steps); PX_MERGE(cycle_ms);
         PX_MERGE(fop_projections);
