@@ -65,7 +65,9 @@ extern "C" {
  * proxsdp_psd_factors and the test entries proxsdp_hip_factor_residual / _kernel: functions and one new struct, no existing
  * struct changed: the version stays;
  * later: proxsdp_hip_solve_from (warm start from a previous solution's primal / duals / factors) with the new struct
- * proxsdp_start and the test entry proxsdp_hip_start_point: functions and one new struct, the version stays */
+ * proxsdp_start and the test entry proxsdp_hip_start_point: functions and one new struct, the version stays;
+ * later: the test entries proxsdp_hip_reconstruct_fused, proxsdp_hip_rotate and proxsdp_hip_tail_copy with their own structs:
+ * functions and new structs, no existing struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -903,6 +905,79 @@ int proxsdp_hip_sym_product(proxsdp_sym_product* t);
  * A), k_sign_scalars stage 1.  sc[16]: sc[0] = 1 / f^2, sc[6] = f = ||A||_F, sc[1] = 1 / s, sc[4] = s = f sqrt(g) with
  * g = ||Y0||_F, sc[8..10] = {1, 1 / g, 1 / g^2}; the other slots are zero. */
 int proxsdp_hip_sign_unpack(const double* packed, int64_t n, double sentinel, double* A, double* sc);
+
+/* ONE rank-r reconstruction of a packed block through the solver's own launch code (Solver::launch_reconstruct, called as
+ * ritz_pairs_to_block calls it on the support path), on host data: k_reconstruct_packed<FUSE_RES> or k_reconstruct_mfma<FUSE_RES>,
+ *   xp[(i, j)] = s_ij sum_k lam[k] Z[i, k] Z[j, k],  s = sqrt(2) off the diagonal, 1 on it   (prox_operators.jl:92-106, 17-31).
+ * Z: ldz x r column-major, ldz >= n; the rows n .. ldz-1 are never read.  mfma = 0 / 1 forces the scalar / the MFMA kernel,
+ * -1 leaves the choice to the solver (MFMA from r = 16 on).
+ * xold != NULL: the fused launch of the support path.  The block is the one at packed offset mask_off of a vector whose support
+ * bits are `mask` (bit mask_off + idx of entry idx), its residual slots are slots 0 .. grid-1 of a buffer of stride grid: over the
+ * entries whose bit is CLEAR, respart[b] = max |xp - xold| and respart[grid + b] = max |xold| of workgroup b's tile; the padding
+ * workgroups write nothing.  xold = NULL: the unfused launch with the same ldz; respart is never written.
+ * xp (n (n + 1) / 2) and ALL respart_cap >= 2 grid entries of respart are prefilled with `sentinel`, so that the caller sees what
+ * the launch wrote and that nothing was written behind 2 grid.  Refused with PROXSDP_E_INVALID: r < 0, ldz < n,
+ * 32 mask_words < mask_off + n (n + 1) / 2, mask_off < 0, respart_cap < 2 grid (grid = 8 ceil(nt (nt + 1) / 16), nt = ceil(n / 64)). */
+typedef struct {
+    int64_t struct_size;
+    /* in */
+    int32_t n, r, ldz, mfma;
+    const double* Z; const double* lam;          /* ldz x r, r (both may be NULL when r = 0) */
+    const double* xold;                          /* packed, n (n + 1) / 2, or NULL: unfused */
+    const uint32_t* mask; int64_t mask_words, mask_off;
+    int64_t respart_cap;
+    double sentinel;
+    /* out */
+    double* xp;                                  /* n (n + 1) / 2 */
+    double* respart;                             /* respart_cap */
+    int32_t grid, kernel;                        /* workgroups launched; 0: k_reconstruct_packed ran, 1: k_reconstruct_mfma */
+} proxsdp_reconstruct_fused;
+int proxsdp_hip_reconstruct_fused(proxsdp_reconstruct_fused* t);
+
+/* ONE basis rotation out[:, c] = sum_j V[:, j] U[j, c], c < ncols (the restart rotation and the final Ritz vectors of the
+ * Lanczos driver; KrylovKit basistransform!) through Solver::rotate -- the pinned staging copy of U, its upload, then
+ * Solver::rotate_launch: k_lz_rotate (one or several launches), k_lz_rotate_mfma or k_lzw_rotate -- on a workspace sized as an
+ * eigsolve sizes it for the Krylov dimension max(K, Kv - 1, out_cols - 1).  V: n x Kv column-major, Kv >= max(K, copy_src + 1);
+ * it is zero-padded to npad = 64 ceil(n / 64) rows, as the step kernels keep the basis.  U: K x ncols, compact column-major.
+ * Behind U, in the same upload, ride 8 NaN where a restart puts its arrow part: reading past row K of a column of U shows.
+ * copy_src >= 0: out[:, copy_dst] = V[:, copy_src] as well (the residual column of a restart).  wide = 1: the rotation of a
+ * wide run (Krylov dimension 256 .. 511, options.lanczos_wide_krylov), which needs the wide workspace.
+ * out: npad x out_cols, prefilled with `sentinel`.  form: which kernel ran (PROXSDP_ROTATE_*, 0 when nothing was launched),
+ * launches: how many launches it took.  Refused with PROXSDP_E_INVALID: ncols < 0 or > K, K < 1, Kv too small, copy_dst or
+ * ncols outside out_cols, wide = 1 with a Krylov dimension <= 255 (no wide workspace), wide = 0 with one > 255. */
+#define PROXSDP_ROTATE_SCALAR 1
+#define PROXSDP_ROTATE_MFMA   2
+#define PROXSDP_ROTATE_WIDE   3
+typedef struct {
+    int64_t struct_size;
+    /* in */
+    int32_t n, K, ncols, Kv, copy_src, copy_dst, wide, out_cols;
+    const double* V; const double* U;
+    double sentinel;
+    /* out */
+    double* out;                                 /* npad x out_cols */
+    int32_t npad, form, launches, reserved;
+} proxsdp_rotation;
+int proxsdp_hip_rotate(proxsdp_rotation* t);
+
+/* The support path's copy of the non-PSD tail (k_tail_copy_res through Solver::launch_tail_copy) on `wgs` workgroups:
+ * xout[i] = xin[i] for start <= i < N (xout, N entries, is prefilled with `sentinel`), and per workgroup w
+ * respart[w] = +0 (x_new = x_old there), respart[wgs + w] = max |xin[i]| over the entries i = start + 256 w + t (+ 256 wgs ..)
+ * of its grid stride whose bit i of `mask` is CLEAR.  Refused with PROXSDP_E_INVALID: start < 0 or >= N, wgs < 1,
+ * 32 mask_words < N. */
+typedef struct {
+    int64_t struct_size;
+    /* in */
+    int64_t N, start;
+    const double* xin;
+    const uint32_t* mask; int64_t mask_words;
+    int32_t wgs, reserved;
+    double sentinel;
+    /* out */
+    double* xout;                                /* N */
+    double* respart;                             /* 2 x wgs */
+} proxsdp_tail_copy;
+int proxsdp_hip_tail_copy(proxsdp_tail_copy* t);
 
 /* The "Init" section (pdhg.jl:54-142) of a solve with a dense A (prob->M_dense), nothing more: E (p + m) and D (n), the
  * equilibration diagonals -- ones when equilibration is off or switched itself off, *equilibrated says which --, frob =

@@ -263,6 +263,9 @@ def lib():
     L.proxsdp_host_equilibrate_rowsums.argtypes = [pf64, i64, i64, C.POINTER(Options), pf64, pf64]
     L.proxsdp_hip_sym_product.argtypes = [C.POINTER(SymProductIO)]
     L.proxsdp_hip_sign_unpack.argtypes = [pf64, i64, f64, pf64, pf64]
+    L.proxsdp_hip_reconstruct_fused.argtypes = [C.POINTER(ReconstructFusedIO)]
+    L.proxsdp_hip_rotate.argtypes = [C.POINTER(RotationIO)]
+    L.proxsdp_hip_tail_copy.argtypes = [C.POINTER(TailCopyIO)]
     L.proxsdp_hip_solve_sharded.argtypes = [C.POINTER(Problem), C.POINTER(Options), i32, C.POINTER(i32), C.POINTER(i32),
                                             C.POINTER(i32), C.POINTER(i32), C.POINTER(Result), C.POINTER(Stats)]
     L.proxsdp_host_split_shard.argtypes = [C.POINTER(Problem), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32,
@@ -1143,6 +1146,111 @@ def sign_unpack(packed, n, sentinel=SYM_SENTINEL):
     sc = np.zeros(16)
     _check(lib().proxsdp_hip_sign_unpack(_p(xin), n, float(sentinel), _p(A), _p(sc)))
     return A, sc
+
+
+pu32 = C.POINTER(C.c_uint32)
+ROTATE_FORMS = {0: "none", 1: "scalar", 2: "mfma", 3: "wide"}            # PROXSDP_ROTATE_*
+RESPART_GUARD = 16                                                        # slots asked for behind 2 grid: nothing may write them
+
+
+class ReconstructFusedIO(C.Structure):
+    """proxsdp_reconstruct_fused (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64),
+                ("n", i32), ("r", i32), ("ldz", i32), ("mfma", i32),
+                ("Z", pf64), ("lam", pf64), ("xold", pf64),
+                ("mask", pu32), ("mask_words", i64), ("mask_off", i64),
+                ("respart_cap", i64), ("sentinel", f64),
+                ("xp", pf64), ("respart", pf64),
+                ("grid", i32), ("kernel", i32)]
+
+
+class RotationIO(C.Structure):
+    """proxsdp_rotation (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64),
+                ("n", i32), ("K", i32), ("ncols", i32), ("Kv", i32), ("copy_src", i32), ("copy_dst", i32), ("wide", i32),
+                ("out_cols", i32),
+                ("V", pf64), ("U", pf64), ("sentinel", f64),
+                ("out", pf64),
+                ("npad", i32), ("form", i32), ("launches", i32), ("reserved", i32)]
+
+
+class TailCopyIO(C.Structure):
+    """proxsdp_tail_copy (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64),
+                ("N", i64), ("start", i64),
+                ("xin", pf64), ("mask", pu32), ("mask_words", i64),
+                ("wgs", i32), ("reserved", i32), ("sentinel", f64),
+                ("xout", pf64), ("respart", pf64)]
+
+
+def reconstruct_fused(Z, lam, n, *, mfma=-1, xold=None, mask=None, mask_off=0, sentinel=SYM_SENTINEL):
+    """proxsdp_hip_reconstruct_fused: ONE reconstruction through Solver::launch_reconstruct.  Z: (ldz, r) with ldz >= n (rows
+    n .. ldz-1 are padding the kernels must not read), lam: (r,).  xold (packed) with mask / mask_off: the fused launch of the
+    support path; without xold the unfused one.  Returns a dict: xp (packed), respart (2 x grid), guard (the RESPART_GUARD slots
+    behind them), grid, kernel ("packed" / "mfma"); what the launch did not write holds `sentinel`."""
+    Zm = np.asfortranarray(Z, dtype=np.float64)
+    ldz, r = Zm.shape
+    lm = _f(lam)
+    assert len(lm) == r
+    N = n * (n + 1) // 2
+    nt = (n + 63) // 64
+    grid = 8 * ((nt * (nt + 1) // 2 + 7) // 8) if n >= 1 else 8
+    t = ReconstructFusedIO()
+    t.struct_size = C.sizeof(ReconstructFusedIO)
+    t.n, t.r, t.ldz, t.mfma = n, r, ldz, int(mfma)
+    if r > 0:
+        t.Z, t.lam = _p(Zm), _p(lm)
+    if xold is not None:
+        xo = _f(xold)
+        mk = np.ascontiguousarray(mask, dtype=np.uint32)
+        assert len(xo) == N
+        t.xold, t.mask, t.mask_words, t.mask_off = _p(xo), _p(mk, pu32), len(mk), int(mask_off)
+    xp = np.zeros(max(N, 1))
+    resp = np.zeros(2 * grid + RESPART_GUARD)
+    t.respart_cap, t.sentinel = len(resp), float(sentinel)
+    t.xp, t.respart = _p(xp), _p(resp)
+    _check(lib().proxsdp_hip_reconstruct_fused(C.byref(t)))
+    assert t.grid == grid
+    return dict(xp=xp[:N], respart=resp[:2 * grid].reshape(2, grid).copy(), guard=resp[2 * grid:].copy(), grid=grid,
+                kernel=("packed", "mfma")[t.kernel])
+
+
+def rotate(V, U, K, *, copy_src=-1, copy_dst=0, wide=0, out_cols=None, sentinel=SYM_SENTINEL):
+    """proxsdp_hip_rotate: out[:, :ncols] = V[:, :K] U through Solver::rotate.  V: (n, Kv), U: (K, ncols).  Returns a dict:
+    out (npad, out_cols), form ("scalar" / "mfma" / "wide" / "none"), launches."""
+    Vm = np.asfortranarray(V, dtype=np.float64)
+    Um = np.asfortranarray(U, dtype=np.float64)
+    n, Kv = Vm.shape
+    ncols = Um.shape[1]
+    assert Um.shape[0] == K
+    if out_cols is None:
+        out_cols = max(ncols, copy_dst + 1 if copy_src >= 0 else 0, 1)
+    npad = 64 * ((n + 63) // 64)
+    out = np.zeros((npad, max(out_cols, 1)), order="F")
+    t = RotationIO()
+    t.struct_size = C.sizeof(RotationIO)
+    t.n, t.K, t.ncols, t.Kv, t.copy_src, t.copy_dst, t.wide, t.out_cols = n, int(K), ncols, Kv, int(copy_src), int(copy_dst), int(wide), int(out_cols)
+    t.V, t.sentinel, t.out = _p(Vm), float(sentinel), _p(out)
+    if Um.size:
+        t.U = _p(Um)
+    _check(lib().proxsdp_hip_rotate(C.byref(t)))
+    assert t.npad == npad
+    return dict(out=out, form=ROTATE_FORMS[t.form], launches=int(t.launches))
+
+
+def tail_copy(xin, start, mask, wgs, sentinel=SYM_SENTINEL):
+    """proxsdp_hip_tail_copy: k_tail_copy_res through Solver::launch_tail_copy on `wgs` workgroups.  Returns (xout, respart):
+    xout (N, prefilled with `sentinel`), respart (2, wgs)."""
+    xi = _f(xin)
+    mk = np.ascontiguousarray(mask, dtype=np.uint32)
+    t = TailCopyIO()
+    t.struct_size = C.sizeof(TailCopyIO)
+    t.N, t.start, t.wgs, t.sentinel = len(xi), int(start), int(wgs), float(sentinel)
+    xout = np.zeros(len(xi))
+    resp = np.zeros(2 * max(int(wgs), 1))
+    t.xin, t.mask, t.mask_words, t.xout, t.respart = _p(xi), _p(mk, pu32), len(mk), _p(xout), _p(resp)
+    _check(lib().proxsdp_hip_tail_copy(C.byref(t)))
+    return xout, resp.reshape(2, -1).copy()
 
 
 def dense_scaling(prob, options=None):

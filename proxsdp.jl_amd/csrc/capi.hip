@@ -839,6 +839,67 @@ int proxsdp_hip_sym_product(proxsdp_sym_product* t) {
     });
 }
 
+int proxsdp_hip_reconstruct_fused(proxsdp_reconstruct_fused* t) {
+    return guarded([&]() -> int {
+        if (!t) throw std::invalid_argument("NULL argument");
+        if (t->struct_size != (int64_t)sizeof(proxsdp_reconstruct_fused)) throw std::invalid_argument("reconstruct: struct_size mismatch");
+        if (t->n < 1 || t->n > 46340) throw std::invalid_argument("reconstruct: n out of range");
+        if (t->r < 0) throw std::invalid_argument("reconstruct: r < 0");
+        if (t->ldz < t->n) throw std::invalid_argument("reconstruct: ldz < n");
+        if (t->mfma < -1 || t->mfma > 1) throw std::invalid_argument("reconstruct: mfma must be -1, 0 or 1");
+        if ((t->r > 0 && (!t->Z || !t->lam)) || !t->xp || !t->respart) throw std::invalid_argument("reconstruct: NULL buffer");
+        const int64_t N = (int64_t)t->n * (t->n + 1) / 2;
+        if (t->xold && (!t->mask || t->mask_off < 0 || t->mask_words * 32 < t->mask_off + N))
+            throw std::invalid_argument("reconstruct: the mask does not cover the block");
+        const int nt = proxsdp::ceil_div(t->n, proxsdp::dev::TILE);
+        if (t->respart_cap < 2 * (int64_t)(8 * proxsdp::ceil_div(nt * (nt + 1) / 2, 8))) throw std::invalid_argument("reconstruct: respart_cap < 2 grid");
+        proxsdp_options o = Engine::fix(nullptr);
+        o.reconstruct_mfma = t->mfma;
+        Engine E(&o, t->n, 2);
+        E.S.test_reconstruct_fused(*t);
+        return 0;
+    });
+}
+
+int proxsdp_hip_rotate(proxsdp_rotation* t) {
+    return guarded([&]() -> int {
+        if (!t) throw std::invalid_argument("NULL argument");
+        if (t->struct_size != (int64_t)sizeof(proxsdp_rotation)) throw std::invalid_argument("rotation: struct_size mismatch");
+        if (t->n < 1 || t->n > 46340) throw std::invalid_argument("rotation: n out of range");
+        if (t->K < 1) throw std::invalid_argument("rotation: K < 1");
+        if (t->ncols < 0 || t->ncols > t->K) throw std::invalid_argument("rotation: ncols must be 0 .. K");
+        if (t->copy_src < -1 || t->Kv < std::max(t->K, t->copy_src + 1)) throw std::invalid_argument("rotation: V has too few columns");
+        if (t->out_cols < 1 || t->ncols > t->out_cols || (t->copy_src >= 0 && (t->copy_dst < 0 || t->copy_dst >= t->out_cols)))
+            throw std::invalid_argument("rotation: a written column lies outside out");
+        if (t->wide != 0 && t->wide != 1) throw std::invalid_argument("rotation: wide must be 0 or 1");
+        if (!t->V || (t->ncols > 0 && !t->U) || !t->out) throw std::invalid_argument("rotation: NULL buffer");
+        // the workspace rule of Solver::alloc_eigwork: the wide records exist from Krylov dimension 256 on, with the option set
+        const int kd = std::max(t->K, std::max(t->Kv, t->out_cols) - 1);
+        if (t->wide && kd <= proxsdp::dev::LZ_KMAX) throw std::invalid_argument("rotation: wide = 1 needs the wide workspace (Krylov dimension > 255)");
+        if (kd > (t->wide ? proxsdp::dev::LZW_MAXK - 1 : proxsdp::dev::LZ_KMAX)) throw std::invalid_argument("rotation: Krylov dimension out of range");
+        proxsdp_options o = Engine::fix(nullptr);
+        o.lanczos_wide_krylov = t->wide;
+        o.eigsolver_min_lanczos = kd;
+        Engine E(&o, t->n, 2);
+        E.S.test_rotate(*t);
+        return 0;
+    });
+}
+
+int proxsdp_hip_tail_copy(proxsdp_tail_copy* t) {
+    return guarded([&]() -> int {
+        if (!t) throw std::invalid_argument("NULL argument");
+        if (t->struct_size != (int64_t)sizeof(proxsdp_tail_copy)) throw std::invalid_argument("tail copy: struct_size mismatch");
+        if (t->N < 1 || t->start < 0 || t->start >= t->N) throw std::invalid_argument("tail copy: start must be 0 .. N-1");
+        if (t->wgs < 1 || t->wgs > 65536) throw std::invalid_argument("tail copy: wgs out of range");
+        if (!t->xin || !t->mask || !t->xout || !t->respart) throw std::invalid_argument("tail copy: NULL buffer");
+        if (t->mask_words * 32 < t->N) throw std::invalid_argument("tail copy: the mask does not cover x");
+        Engine E(nullptr, 2, 2);
+        E.S.test_tail_copy(*t);
+        return 0;
+    });
+}
+
 int proxsdp_hip_sign_unpack(const double* packed, int64_t n, double sentinel, double* A, double* sc) {
     return guarded([&]() -> int {
         if (!packed || !A || !sc || n < 1 || n > 4096) throw std::invalid_argument("invalid argument");

@@ -62,6 +62,13 @@ inline void Solver::launch_primal_update_S(double* x, double tau) {
                        x, supp_d.p, MtyS_cur.p, cS_d.p, tau, xsave_d.p, ns, esv_d.p);
 }
 
+// the non-PSD tail of x on the support path (k_tail_copy_res): its workgroups own the residual slots behind the blocks' tiles
+inline void Solver::launch_tail_copy(const double* xin, double* xout) {
+    hipLaunchKernelGGL(dev::k_tail_copy_res, dim3(n_res_wg - tile_base.back()), dim3(dev::TPB), 0, stream,
+                       xin, xout, (long long)P.sdplen, (long long)P.n, mask_d.p,
+                       respart_d.p + tile_base.back(), rstride);
+}
+
 // primal_step! (pdhg.jl:611-637)
 inline void Solver::primal_step_dev() {
     // block-sharded solve: a shard whose projection fails (e.g. non-finite input) must still join this iteration's
@@ -85,10 +92,7 @@ inline void Solver::primal_step_dev() {
         double t0 = now_s();
         shard_guard([&]() { project_blocks(big_blocks, xcur, xnew, true); });
         st.t_psd += now_s() - t0;
-        if (P.sdplen < P.n)
-            hipLaunchKernelGGL(dev::k_tail_copy_res, dim3(n_res_wg - tile_base.back()), dim3(dev::TPB), 0, stream,
-                               xcur, xnew, (long long)P.sdplen, (long long)P.n, mask_d.p,
-                               respart_d.p + tile_base.back(), rstride);
+        if (P.sdplen < P.n) launch_tail_copy(xcur, xnew);
         spmv(xnew, Mxbuf[1 - mxc].p);
         reduce_coupling(Mxbuf[1 - mxc].p);
         return;

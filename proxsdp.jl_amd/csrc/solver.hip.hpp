@@ -283,6 +283,7 @@ struct EigWork {
     std::vector<double> resid_host;
     PinnedBuf Ustage[2];            // pinned: the upload is a truly asynchronous copy (a pageable source makes the runtime stage and wait)
     int ustage_next = 0;
+    int rot_form = 0, rot_launches = 0;   // the last rotate_launch: PROXSDP_ROTATE_SCALAR / _MFMA / _WIDE (0: nothing launched), its launches
     // results of the last call
     std::vector<double> vals;
     int count = 0, converged_eigs = 0, numiter = 0, prev_numiter = 1;
@@ -531,6 +532,10 @@ public:
                         const int64_t* oo, int none, double* x_soc, double* gap_in, double* gap_out,
                         double* x_clamp, double* mineig);
     void test_sym_product(proxsdp_sym_product& t);
+    void test_reconstruct_fused(proxsdp_reconstruct_fused& t);
+    void test_rotate(proxsdp_rotation& t);
+    void test_tail_copy(proxsdp_tail_copy& t);
+    void launch_tail_copy(const double* xin, double* xout);
     void test_sign_unpack(const double* packed, double sentinel, double* A, double* sc);
 
     bool debug = std::getenv("PROXSDP_HIP_DEBUG") != nullptr;
@@ -1153,10 +1158,13 @@ inline void Solver::rotate(EigWork& W, int K, const std::vector<double>& U, int 
 
 // the launches of rotate(): out[:, :ncols] = V[:, :K] U, U (K x ncols, compact, column-major) on the device
 inline void Solver::rotate_launch(EigWork& W, int K, const double* Ud, int ncols, double* out, int copy_src, int copy_dst) {
+    W.rot_form = 0; W.rot_launches = 0;
     if (W.lzrun.wide) {                                  // wide run: LDS-tiled over K (neither form below fits at K > 255)
-        if (ncols > 0 || copy_src >= 0)
+        if (ncols > 0 || copy_src >= 0) {
+            W.rot_form = PROXSDP_ROTATE_WIDE; W.rot_launches = 1;
             hipLaunchKernelGGL(dev::k_lzw_rotate, dim3(W.nt, std::max(1, ceil_div(ncols, dev::LZW_RC))), dim3(dev::TPB), 0, stream,
                                (const double*)W.V.p, W.npad, K, Ud, ncols, out, W.npad, copy_src, copy_dst);
+        }
         return;
     }
     // fp64 MFMA form from K = 32 / 16 columns on (skinny GEMM); grid = row tiles x groups of 16 columns; LDS: V tile + one U group
@@ -1164,6 +1172,7 @@ inline void Solver::rotate_launch(EigWork& W, int K, const double* Ud, int ncols
         const int Kp = (K + 3) & ~3;
         const size_t lds_m = ((size_t)Kp * dev::RM_LDV + (size_t)dev::RM_CG * (Kp + 2)) * sizeof(double);
         if (K >= 32 && ncols >= 16 && (int)lds_m <= rotate_mfma_lds_cap) {
+            W.rot_form = PROXSDP_ROTATE_MFMA; W.rot_launches = 1;
             hipLaunchKernelGGL(dev::k_lz_rotate_mfma, dim3(W.nt, ceil_div(ncols, dev::RM_CG)), dim3(dev::TPB), lds_m, stream,
                                (const double*)W.V.p, W.npad, K, Ud, ncols, out, W.npad, copy_src, copy_dst);
             return;
@@ -1179,10 +1188,12 @@ inline void Solver::rotate_launch(EigWork& W, int K, const double* Ud, int ncols
     do {
         const int cn = std::max(0, std::min(maxcols, ncols - c0));
         const bool last = (c0 + cn >= ncols);
-        if (cn > 0 || (last && copy_src >= 0))
+        if (cn > 0 || (last && copy_src >= 0)) {
+            W.rot_form = PROXSDP_ROTATE_SCALAR; W.rot_launches++;
             hipLaunchKernelGGL(dev::k_lz_rotate, dim3(W.nt), dim3(dev::TPB), (size_t)K * cn * 8 + vbytes, stream,
                                W.V.p, W.npad, W.n, K, Ud + (size_t)c0 * K, K, cn,
                                out + (size_t)c0 * W.npad, W.npad, last ? copy_src : -1, copy_dst - c0);
+        }
         c0 += std::max(cn, 1);
     } while (c0 < ncols);
 }
@@ -2338,6 +2349,96 @@ inline void Solver::test_sign_unpack(const double* packed, double sentinel, doub
     PX_HIP(hipGetLastError());
     As.download(A, sz, stream);
     dsc.download(sc, 16, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+}
+
+// ONE rank-r reconstruction on host data (include/proxsdp_hip.h proxsdp_reconstruct_fused) through launch_reconstruct, as
+// ritz_pairs_to_block calls it on the support path: eig[0] was sized for side t.n, the block sits at packed offset mask_off of
+// a vector whose support mask is t.mask, its residual slots start at slot 0 of a buffer of stride grid.  xp and the whole of
+// respart (respart_cap slots: whatever lies behind 2 grid is a guard zone) are prefilled with the sentinel.
+inline void Solver::test_reconstruct_fused(proxsdp_reconstruct_fused& t) {
+    EigWork& W = eig[0];
+    const int n = W.n, r = t.r;
+    const int64_t N = W.N;
+    const bool fuse = t.xold != nullptr;
+    const int grid = 8 * ceil_div(W.nt * (W.nt + 1) / 2, 8);
+    if (t.respart_cap < 2 * (int64_t)grid) throw std::invalid_argument("reconstruct: respart_cap < 2 grid");
+    auto filled = [&](DevBuf<double>& d, size_t count) {
+        std::vector<double> h(count, t.sentinel);
+        d.alloc(count);
+        d.upload(h.data(), count, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+    };
+    DevBuf<double> dZ(std::max<size_t>(1, (size_t)t.ldz * r)), dlam(std::max(1, r)), dxp, dxold;
+    dZ.upload(t.Z, (size_t)t.ldz * r, stream);
+    dlam.upload(t.lam, r, stream);
+    filled(dxp, N);
+    filled(respart_d, (size_t)t.respart_cap);
+    use_support = fuse;
+    if (fuse) {
+        dxold.alloc(N); dxold.upload(t.xold, N, stream);
+        mask_d.alloc(t.mask_words); mask_d.upload(t.mask, t.mask_words, stream);
+        P.blocks.assign(1, BlockInfo{n, N, t.mask_off});
+        tile_base.assign(1, 0);
+        rstride = grid;
+    }
+    const auto before = W.lst.mfma_reconstructions;
+    launch_reconstruct(W, dZ.p, t.ldz, dlam.p, r, dxp.p, fuse ? dxold.p : nullptr, fuse ? 0 : -1);
+    PX_HIP(hipGetLastError());
+    dxp.download(t.xp, N, stream);
+    respart_d.download(t.respart, (size_t)t.respart_cap, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    t.grid = grid;
+    t.kernel = W.lst.mfma_reconstructions > before ? 1 : 0;
+}
+
+// ONE basis rotation on host data (include/proxsdp_hip.h proxsdp_rotation) through Solver::rotate -- the pinned staging copy of
+// U, its upload and rotate_launch -- from W.V into W.Z, as the restart and the final Ritz-vector rotation run it.  eig[0] was
+// sized for a Krylov dimension that holds every column named; V goes into the zeroed basis (padding rows stay zero, as the
+// step kernels leave them), the first out_cols columns of Z are prefilled with the sentinel.
+inline void Solver::test_rotate(proxsdp_rotation& t) {
+    EigWork& W = eig[0];
+    const int n = W.n, npad = W.npad;
+    if (W.wide != (t.wide != 0)) throw std::logic_error("rotation: the workspace is not the one asked for");
+    if (std::max(t.Kv, t.out_cols) > W.cap) throw std::logic_error("rotation: workspace too small");
+    std::vector<double> h((size_t)npad * std::max(t.Kv, t.out_cols), 0.0);
+    for (int j = 0; j < t.Kv; ++j) std::copy(t.V + (size_t)j * n, t.V + (size_t)j * n + n, h.begin() + (size_t)j * npad);
+    W.V.upload(h.data(), (size_t)npad * t.Kv, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    std::fill(h.begin(), h.end(), t.sentinel);
+    W.Z.upload(h.data(), (size_t)npad * t.out_cols, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    W.lzrun.wide = t.wide != 0;
+    const std::vector<double> U(t.U, t.U + (size_t)t.K * t.ncols);
+    // behind U, where a restart's arrow part rides in the same upload: NaN, which no kernel may take for rows of U
+    const std::vector<double> behind(8, std::numeric_limits<double>::quiet_NaN());
+    rotate(W, t.K, U, t.K, t.ncols, W.Z.p, t.copy_src, t.copy_dst, behind.data(), (int)behind.size());
+    PX_HIP(hipGetLastError());
+    W.Z.download(t.out, (size_t)npad * t.out_cols, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    t.npad = npad;
+    t.form = W.rot_form;
+    t.launches = W.rot_launches;
+}
+
+// The support path's copy of the non-PSD tail x[start .. N) (include/proxsdp_hip.h proxsdp_tail_copy) through launch_tail_copy,
+// on t.wgs workgroups whose residual slots are the whole buffer (no PSD block in front); xout and respart prefilled.
+inline void Solver::test_tail_copy(proxsdp_tail_copy& t) {
+    std::vector<double> h((size_t)std::max<int64_t>(t.N, 2 * (int64_t)t.wgs), t.sentinel);
+    DevBuf<double> dxin(t.N), dxout(t.N);
+    dxin.upload(t.xin, t.N, stream);
+    dxout.upload(h.data(), t.N, stream);
+    mask_d.alloc(t.mask_words); mask_d.upload(t.mask, t.mask_words, stream);
+    respart_d.alloc((size_t)2 * t.wgs); respart_d.upload(h.data(), (size_t)2 * t.wgs, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    P.n = t.N; P.sdplen = t.start;
+    tile_base.assign(1, 0);
+    n_res_wg = t.wgs;
+    rstride = t.wgs;
+    launch_tail_copy(dxin.p, dxout.p);
+    PX_HIP(hipGetLastError());
+    dxout.download(t.xout, t.N, stream);
+    respart_d.download(t.respart, (size_t)2 * t.wgs, stream);
     PX_HIP(hipStreamSynchronize(stream));
 }
 
