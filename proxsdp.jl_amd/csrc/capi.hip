@@ -7,8 +7,10 @@
 #include <new>
 #include <string>
 
+#include "lanczos.hip.hpp"
 #include "pdhg_loop.hip.hpp"
 #include "projection.hip.hpp"
+#include "test_hooks.hip.hpp"
 #include "shard_split.hpp"
 
 namespace {
@@ -755,7 +757,7 @@ int proxsdp_hip_factor_residual_kernel(const double* packed, int64_t n, const do
         S.factor_residual(x.p, (int)n, Vd.p, (int)ldv, ld.p, r, *resid2, *xnorm2);
         if (repeat > 0 && ms) {
             const int nt = proxsdp::ceil_div((int)n, proxsdp::dev::TILE);
-            const int grid = 8 * proxsdp::ceil_div(nt * (nt + 1) / 2, 8);
+            const int grid = proxsdp::tile_grid(nt);
             *ms = proxsdp::time_launches(S.stream, repeat, [&]() {
                 hipLaunchKernelGGL(proxsdp::dev::k_factor_residual, dim3(grid), dim3(proxsdp::dev::TPB), 0, S.stream,
                                    (const double*)x.p, (int)n, (const double*)Vd.p, (int)ldv, (const double*)ld.p, (int)r,
@@ -852,7 +854,7 @@ int proxsdp_hip_reconstruct_fused(proxsdp_reconstruct_fused* t) {
         if (t->xold && (!t->mask || t->mask_off < 0 || t->mask_words * 32 < t->mask_off + N))
             throw std::invalid_argument("reconstruct: the mask does not cover the block");
         const int nt = proxsdp::ceil_div(t->n, proxsdp::dev::TILE);
-        if (t->respart_cap < 2 * (int64_t)(8 * proxsdp::ceil_div(nt * (nt + 1) / 2, 8))) throw std::invalid_argument("reconstruct: respart_cap < 2 grid");
+        if (t->respart_cap < 2 * (int64_t)proxsdp::tile_grid(nt)) throw std::invalid_argument("reconstruct: respart_cap < 2 grid");
         proxsdp_options o = Engine::fix(nullptr);
         o.reconstruct_mfma = t->mfma;
         Engine E(&o, t->n, 2);
@@ -1045,11 +1047,10 @@ int proxsdp_host_symeig_split_threads(int32_t K, int32_t m, int32_t k1, const do
         proxsdp::SplitEig S;
         std::unique_ptr<proxsdp::SpinPool> pool;
         proxsdp::ParFor par;
-        struct Guard { proxsdp::SpinPool* p; ~Guard() { if (p) p->disarm(); } } guard{nullptr};
+        proxsdp::ArmedPool helpers;
         if (threads > 0) {
             pool.reset(new proxsdp::SpinPool(std::min<int>(threads, 15)));
-            pool->arm();
-            guard.p = pool.get();
+            helpers.arm(pool.get());
             par = [&pool](int n, const std::function<void(int)>& body) { pool->run(n, body); };
             S.M.par = &par;
             S.M.nchunk = std::min<int>(threads, 15) + 1;

@@ -447,6 +447,15 @@ inline int symeig_tridiag_from(int K, int m, const double* Qa, const double* da,
     return ql_implicit(K, U, d, e.data());
 }
 
+// :LR (descending) order from an ascending eigensolve: D = the eigenvalues reversed, f = betaK x the eigenvectors' last
+// row (lastrow[j * stride] belongs to eigenvalue j) reversed
+inline void lz_descending(int K, const double* evals, const double* lastrow, size_t stride, double betaK, double* D, double* f) {
+    for (int c = 0; c < K; ++c) {
+        D[c] = evals[K - 1 - c];
+        f[c] = betaK * lastrow[(size_t)(K - 1 - c) * stride];
+    }
+}
+
 // ------------------------------------------------------------------ spin pool
 // A few helper threads for SHORT independent host jobs on the critical path (the per-block restart logic of a batched
 // multi-block Lanczos run: 8 K x K eigensolves of ~10 us each per cycle).  Waking a sleeping thread costs more than such a
@@ -535,6 +544,16 @@ private:
     std::atomic<uint64_t> ticket_{0};                    // [generation : 32 | next job index : 32]
     std::atomic<int> done_{0}, njobs_{0};
     std::atomic<const std::function<void(int)>*> job_{nullptr};
+};
+// a pool armed for a scope (none: nothing happens): the helpers stop spinning when the scope ends, by an exception too
+struct ArmedPool {
+    SpinPool* p = nullptr;
+    ArmedPool() = default;
+    explicit ArmedPool(SpinPool* pool) { arm(pool); }
+    ArmedPool(const ArmedPool&) = delete;
+    ArmedPool& operator=(const ArmedPool&) = delete;
+    ~ArmedPool() { if (p) p->disarm(); }
+    void arm(SpinPool* pool) { p = pool; if (p) p->arm(); }
 };
 
 // ------------------------------------------------------------------ split + rank-one merge (host_eig_merge.hpp)

@@ -614,7 +614,7 @@ inline void Solver::extract_factors(const std::vector<double>& x) {
             F.source[idx] = PROXSDP_FACTOR_RITZ;
             ldv = W.npad;
             if (W.have_factors) {
-                Vsrc = W.F.p + (size_t)W.F_first * W.npad;
+                Vsrc = W.prev_factors().V;
                 lam.resize(W.F_r);
                 if (W.F_r > 0) { W.Flam.download(lam.data(), W.F_r, stream); PX_HIP(hipStreamSynchronize(stream)); }
             } else {
@@ -895,7 +895,7 @@ inline void Solver::setup_support() {
     for (const BlockInfo& B : P.blocks) {
         tile_base.push_back(base);
         const int nt = ceil_div(B.n, dev::TILE);
-        base += 8 * ceil_div(nt * (nt + 1) / 2, 8);      // reconstruction grid (padded to 8 XCDs)
+        base += tile_grid(nt);                           // reconstruction grid
     }
     tile_base.push_back(base);
     if (P.sdplen < P.n) base += std::min(256, ceil_div(P.n - P.sdplen, dev::TPB));
@@ -995,131 +995,6 @@ inline void Solver::upload_sparse_operator() {
     PX_HIP(hipStreamSynchronize(stream));
     csr_wave = P.Q > 0 && (double)P.nnz / (double)P.Q > 8.0;
     setup_long_rows(rp);
-}
-
-// ---- hooks for the kernel-level test entry points
-inline void Solver::test_project(int idx, double* xp, int tr) {
-    target_rank.assign(1, tr); current_rank.assign(1, 0); min_eig.assign(1, 0.0);
-    iter = 1;
-    project_block(idx, xp - P.blocks[idx].off, xp - P.blocks[idx].off, false);
-}
-// the iterate's buffers as the "Init" section allocates them (x, M'y: n; y, Mx: Q; two of each), zeroed
-inline void Solver::test_spmv(bool transpose, const double* in, double* out) {
-    setup_device();
-    upload_sparse_operator();
-    if (transpose) {
-        // M'y as the linesearch computes it: ONE plain candidate against a zero M'y_old
-        alloc_iterate_pairs();
-        use_support = false;
-        alloc_candidates();
-        ycand_d.upload(in, P.Q, stream);
-        dev::TrialBatch tb{};
-        tb.nc = 1; tb.plain = 1;
-        batch_mty(tb, 1);
-        Mtycand_d.download(out, P.n, stream);
-    } else {
-        DevBuf<double> xin(std::max<int64_t>(P.n, 1)), xout(std::max<int64_t>(P.Q, 1));
-        xin.upload(in, P.n, stream);
-        spmv(xin.p, xout.p);
-        xout.download(out, P.Q, stream);
-    }
-    PX_HIP(hipStreamSynchronize(stream));
-}
-// one batch of the linesearch on host data (include/proxsdp_hip.h proxsdp_trial_batch).  The problem was prepared with every
-// row of M as an equality row (no cones: columns keep their order and their storage order); p is set here.
-inline void Solver::test_trial_batch(proxsdp_trial_batch& t) {
-    const int64_t n = P.n, Q = P.Q;
-    if (n < 1 || Q < 1 || t.p < 0 || t.p > Q || t.nc < 1 || t.nc > NCAND || t.c0 >= t.nc)
-        throw std::invalid_argument("trial batch: n, Q >= 1, 0 <= p <= Q, 1 <= nc <= 3, c0 < nc");
-    if (t.support < 0 || t.support > 2) throw std::invalid_argument("trial batch: support must be 0, 1 or 2");
-    if (!t.bh || !t.y || !t.Mx || !t.Mx_old || !t.x || !t.x_old || !t.Mty_old || !t.y_out || !t.Mty_out || !t.scal ||
-        (t.c0 >= 0 && !t.scal_re) || (t.support == 1 && (!t.supp_out || !t.x_upd || !t.xsave || !t.esv)))
-        throw std::invalid_argument("trial batch: NULL array");
-    P.p = t.p; P.m = Q - t.p;
-    setup_device();
-    upload_sparse_operator();
-    alloc_iterate_pairs();
-    c_d.alloc(n); c_d.upload(P.c.data(), n, stream);
-    bh_d.alloc(Q); bh_d.upload(t.bh, Q, stream);
-    if (t.roww) { roww_d.alloc(Q); roww_d.upload(t.roww, Q, stream); }
-    ybuf[yc].upload(t.y, Q, stream);
-    Mxbuf[1 - mxc].upload(t.Mx, Q, stream); Mxbuf[mxc].upload(t.Mx_old, Q, stream);
-    xbuf[xc].upload(t.x_old, n, stream);
-    PX_HIP(hipStreamSynchronize(stream));
-    use_support = t.support == 1;
-    general_row_weights = t.support == 2;                // (the general path of a block-sharded solve: weighted b'y, h'y)
-    if (use_support) {
-        const std::vector<int> supp = support_list();
-        upload_support(supp);
-        n_res_wg = 0; rstride = 0;                       // (no reconstruction ran: no off-support partials)
-        respart_d.alloc(2); respart_d.zero(stream);
-        std::vector<double> mtyS(std::max(ns, 1), 0.0);
-        for (int s = 0; s < ns; ++s) mtyS[s] = t.Mty_old[supp[s]];
-        MtyS_cur.upload(mtyS.data(), ns, stream);
-        // primal_step!'s update on the support, in place on x_old; the new iterate (what the projection would write) is t.x
-        launch_primal_update_S(xbuf[xc].p, t.tau_update);
-        xbuf[xc].download(t.x_upd, n, stream);
-        xsave_d.download(t.xsave, ns, stream);
-        esv_d.download(t.esv, (size_t)2 * ns, stream);
-        std::copy(supp.begin(), supp.end(), t.supp_out);
-        PX_HIP(hipStreamSynchronize(stream));
-    } else {
-        Mtybuf[mtyc].upload(t.Mty_old, n, stream);
-    }
-    t.ns = batch_shape().cnt;
-    xbuf[1 - xc].upload(t.x, n, stream);
-    alloc_candidates();
-    dev::TrialBatch tb{};
-    tb.nc = t.nc; tb.plain = t.plain;
-    for (int c = 0; c < t.nc; ++c) { tb.tau[c] = t.tau[c]; tb.theta[c] = t.theta[c]; tb.bt[c] = t.bt[c]; tb.sigma[c] = t.sigma[c]; }
-    batch_evaluate(tb, t.nc, t.xold_coef);
-    const double* rec = batch_read_back(t.nc);
-    std::copy(rec, rec + (size_t)t.nc * NSCAL, t.scal);
-    const BatchShape b = batch_shape();
-    t.gq = b.gq; t.gx = b.gx;
-    for (int c = 0; c < t.nc; ++c) {
-        PX_HIP(hipMemcpyAsync(t.y_out + (size_t)c * Q, ycand_d.p + (size_t)c * b.ystride, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (t.ns > 0)
-            PX_HIP(hipMemcpyAsync(t.Mty_out + (size_t)c * t.ns, Mtycand_d.p + (size_t)c * b.mstride, (size_t)t.ns * sizeof(double), hipMemcpyDeviceToHost, stream));
-    }
-    PX_HIP(hipStreamSynchronize(stream));
-    if (t.c0 >= 0) {                                     // the re-evaluation leg: candidate c0's residuals with the final steps
-        dev::TrialBatch t1{};
-        t1.nc = 1; t1.tau[0] = t.tau_re; t1.theta[0] = t.theta[t.c0]; t1.bt[0] = t.sigma_re; t1.sigma[0] = t.sigma_re;
-        batch_residuals(t1, 1, t.c0, t.xold_coef);
-        rec = batch_read_back(1);
-        std::copy(rec, rec + NSCAL, t.scal_re);
-    }
-}
-// the cone tail on host data: SOC gap, SOC projection, SOC gap again, then the 1x1 PSD blocks (disjoint entries)
-inline void Solver::test_cone_tail(const double* x, int64_t n, const int64_t* so, const int32_t* sl, int nsoc,
-                                   const int64_t* oo, int none, double* x_soc, double* gap_in, double* gap_out,
-                                   double* x_clamp, double* mineig) {
-    DevBuf<double> xd(std::max<int64_t>(n, 1));
-    xd.upload(x, n, stream);
-    if (nsoc > 0) {
-        std::vector<long long> off(so, so + nsoc);
-        std::vector<int> len(sl, sl + nsoc);
-        soc_off.alloc(nsoc); soc_len.alloc(nsoc); soc_gap_d.alloc(nsoc);
-        soc_off.upload(off.data(), nsoc, stream); soc_len.upload(len.data(), nsoc, stream);
-        launch_soc_gap(xd.p, nsoc);
-        soc_gap_d.download(gap_in, nsoc, stream);
-        launch_soc_project(xd.p, nsoc);
-        launch_soc_gap(xd.p, nsoc);
-        soc_gap_d.download(gap_out, nsoc, stream);
-        PX_HIP(hipStreamSynchronize(stream));            // host vectors go out of scope
-    }
-    xd.download(x_soc, n, stream);
-    if (none > 0) {
-        std::vector<long long> off(oo, oo + none);
-        one_off.alloc(none); one_min.alloc(none);
-        one_off.upload(off.data(), none, stream);
-        launch_clamp_scalars(xd.p, none);
-        one_min.download(mineig, none, stream);
-        PX_HIP(hipStreamSynchronize(stream));
-    }
-    xd.download(x_clamp, n, stream);
-    PX_HIP(hipStreamSynchronize(stream));
 }
 
 // ---- state seam (include/proxsdp_hip.h proxsdp_state)
@@ -1806,10 +1681,10 @@ inline void Solver::finish() {
     } else {
         cache_solution(P.c_orig);
     }
-    if (debug && dbg_lz[5] > 0)
+    if (debug && dbg_lz.cycles > 0)
         std::fprintf(stderr, "[proxsdp] single-block Lanczos: %.0f cycles; per cycle: wait for the GPU %.1f us | after-cycle host logic (eigensolve, "
                      "convergence, restart rotation staging) %.1f us; per projection: results (Ritz coefficients + rotation staging) %.1f us\n",
-                     dbg_lz[5], 1e6 * dbg_lz[0] / dbg_lz[5], 1e6 * dbg_lz[1] / dbg_lz[5], 1e6 * dbg_lz[3] / std::max(1.0, (double)st.lanczos_calls));
+                     dbg_lz.cycles, 1e6 * dbg_lz.wait / dbg_lz.cycles, 1e6 * dbg_lz.after_cycle / dbg_lz.cycles, 1e6 * dbg_lz.results / std::max(1.0, (double)st.lanczos_calls));
     if (b1_dbg.p != nullptr) {
         long long t[8] = {0};
         b1_dbg.download(t, 8, stream);
@@ -1818,10 +1693,10 @@ inline void Solver::finish() {
             std::fprintf(stderr, "[proxsdp] k_lz_block1: %lld launches, %lld steps; per launch: prologue %.2f us | step loop %.2f us (%.2f us per step) | "
                          "epilogue %.2f us\n", t[4], t[3], 0.01 * t[0] / t[4], 0.01 * t[1] / t[4], 0.01 * t[1] / std::max(1LL, t[3]), 0.01 * t[2] / t[4]);
     }
-    if (debug && dbg_batch[4] > 0)
+    if (debug && dbg_batch.cycles > 0)
         std::fprintf(stderr, "[dbg] batched Lanczos: %.0f cycles; per cycle enqueue %.1f us, wait %.1f us, restart logic %.1f us, flush %.1f us\n",
-                     dbg_batch[4], 1e6 * dbg_batch[0] / dbg_batch[4], 1e6 * dbg_batch[1] / dbg_batch[4],
-                     1e6 * dbg_batch[2] / dbg_batch[4], 1e6 * dbg_batch[3] / dbg_batch[4]);
+                     dbg_batch.cycles, 1e6 * dbg_batch.enqueue / dbg_batch.cycles, 1e6 * dbg_batch.wait / dbg_batch.cycles,
+                     1e6 * dbg_batch.restart / dbg_batch.cycles, 1e6 * dbg_batch.flush / dbg_batch.cycles);
     res.stats = st;
 }
 

@@ -1,5 +1,5 @@
-// psd_projection! (prox_operators.jl:33-126): which engine projects which block.  The engines themselves -- lanczos*,
-// full_eig_by_sign, full_eig_values, launch_reconstruct, the sym_gemm family -- are in solver.hip.hpp; this file only decides,
+// psd_projection! (prox_operators.jl:33-126): which engine projects which block.  The engines themselves are lanczos.hip.hpp (lanczos*) and
+// solver.hip.hpp (full_eig_by_sign, full_eig_values, launch_reconstruct, the sym_gemm family); this file only decides,
 // in call order: the cone's blocks, one block, the Krylov branch, the full_eig! branch, the dense engines.
 #pragma once
 #include "solver.hip.hpp"
@@ -145,7 +145,7 @@ inline bool Solver::krylov_branch(int idx) const {
     return !opt.full_eig_decomp && target_rank[idx] <= opt.max_target_rank_krylov_eigs &&
            eig[idx].n > opt.min_size_krylov_eigs && (iter % opt.full_eig_freq) > opt.full_eig_len;
 }
-// may this block's Lanczos run ride in a batched launch (solver.hip.hpp lanczos_batch)?
+// may this block's Lanczos run ride in a batched launch (lanczos.hip.hpp lanczos_batch)?
 inline bool Solver::batch_eligible(int idx, bool fuse) const {
     if (opt.block_batch == 0 || !krylov_branch(idx)) return false;
     if (opt.eigsolver == 1 || opt.psd_sign_engine == 1 || opt.lanczos_warm_start > 0 || opt.krylovkit_eager)
