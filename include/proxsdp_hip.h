@@ -61,6 +61,8 @@ extern "C" {
  * later: proxsdp_hip_solve_sharded (a whole model, split by the library, one shard per host thread and device of ONE process),
  * with its test entries proxsdp_host_split_shard, proxsdp_host_group_reduce, proxsdp_hip_coupling_sum: functions only, no
  * struct changed -- as for proxsdp_hip_dense_scaling before, the version stays;
+ * later: proxsdp_stats.reserved_s[3] counts the Lanczos steps on the owner form of the operator-form mat-vec
+ * (PROXSDP_STATS_FOP_OWNER_STEPS; switch: environment PROXSDP_HIP_FOP_OWNER): same sizes and offsets, version unchanged;
  * later: proxsdp_hip_solve_factored (the low-rank factors of the PSD solution beside the result) with the new struct
  * proxsdp_psd_factors and the test entries proxsdp_hip_factor_residual / _kernel: functions and one new struct, no existing
  * struct changed: the version stays;
@@ -493,7 +495,9 @@ typedef struct proxsdp_stats {
                                            * in a solve that is not sharded); [1] = device_eig_merges: merges of host_eig_merges
                                            * whose O(k^2) part ran on the device (device_eig_merge); [2] = device_eig_merge_fallbacks:
                                            * merges the host did while the device path was switched on (a shape or a thread it does
-                                           * not serve, or a merge it handed back); [3] zero */
+                                           * not serve, or a merge it handed back); [3] = fop_owner_steps: k_lz_orth launches of the
+                                           * operator-form Lanczos step that read t = Vp'v finished by the mat-vec launch's
+                                           * column owners (environment PROXSDP_HIP_FOP_OWNER = 0: never; unset: where it applies) */
     /* (the last two reserved slots: reserved_s keeps its offset) */
     int64_t dense_setup_passes;           /* set-up passes over a dense A (row sums + extrema, 8*p*n bytes): 1 when equilibration
                                            * was asked for, else 0 */
@@ -504,6 +508,7 @@ typedef struct proxsdp_stats {
 #define PROXSDP_STATS_SHARDED_GENERAL_ITERATIONS 0
 #define PROXSDP_STATS_DEVICE_EIG_MERGES 1
 #define PROXSDP_STATS_DEVICE_EIG_MERGE_FALLBACKS 2
+#define PROXSDP_STATS_FOP_OWNER_STEPS 3
 
 /* Result (structs.jl:60-81).  Arrays are caller-allocated with the stated
  * lengths (NULL = not wanted); values are unscaled and in USER variable order

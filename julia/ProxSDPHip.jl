@@ -129,6 +129,8 @@ sharded_general_iterations(s::Stats) = s.reserved_s[1]
 # that path was switched on
 device_eig_merges(s::Stats) = s.reserved_s[2]
 device_eig_merge_fallbacks(s::Stats) = s.reserved_s[3]
+# k_lz_orth launches of the operator-form Lanczos step on the owner form (t = Vp'v finished in the mat-vec launch)
+fop_owner_steps(s::Stats) = s.reserved_s[4]
 
 mutable struct CResult           # proxsdp_result
     status::Int32

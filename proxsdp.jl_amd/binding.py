@@ -156,7 +156,8 @@ class Result(C.Structure):
 
 
 # named slots of Stats.reserved_s (include/proxsdp_hip.h PROXSDP_STATS_*): SolveResult.stats lists them under their names
-STATS_RESERVED_SLOTS = {"sharded_general_iterations": 0, "device_eig_merges": 1, "device_eig_merge_fallbacks": 2}
+STATS_RESERVED_SLOTS = {"sharded_general_iterations": 0, "device_eig_merges": 1, "device_eig_merge_fallbacks": 2,
+                        "fop_owner_steps": 3}
 
 STATE_NHIST = 7
 STATE_HIST_NAMES = ("dual_gap", "prim_obj", "dual_obj", "feasibility", "primal_residual", "dual_residual", "comb_residual")

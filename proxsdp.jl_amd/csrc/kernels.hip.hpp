@@ -469,12 +469,15 @@ struct FopArgs {
     const double* lam;       // their (positive) eigenvalues
     int rp;                  // how many (0: x_prev = 0 off the support)
     const double* tpart;     // [rp][pld] partial dots Vp' v written by k_fop*
+    const double* tred;      // [RLD] owner form: the complete sums t = Vp' v, written by the column owners of k_fop*
     const double* ebuf;      // (E v)_i
     const double* apart;     // [pld] partials of v' E v
 };
 // NCHP = 0: the mat-vec came from the packed tiles (Ppart / Apart).  NCHP > 0: it is rebuilt from
 // the operator-form pieces (16*NCHP*4 >= rp): A v = Vp (lam o (Vp' v)) + E v.
-template <int NCH, int NCHP>
+// OWN (NCHP > 0): t = Vp' v arrives complete in fo.tred (the column owners, fop_owner_body, added the row blocks' shares in
+// the order of the tree below); without it every workgroup loads the nt records of fo.tpart and repeats that tree.
+template <int NCH, int NCHP, bool OWN = false>
 __device__ __forceinline__ void
 lz_orth_body(const double* __restrict__ Ppart, int nt, int npad, const double* __restrict__ V, int ldv, int k,
              double* __restrict__ wbuf, const double* __restrict__ hred, double* __restrict__ hpart_out, int pld,
@@ -486,7 +489,7 @@ lz_orth_body(const double* __restrict__ Ppart, int nt, int npad, const double* _
     const int stop = ctl->stop;                      // tested after the loads below are in flight
     constexpr int NC = 16 * NCH;
     constexpr int NCP = 16 * (NCHP > 0 ? NCHP : 1);
-    __shared__ double s_t[NWAVE * 4 * 4 * NCP];      // per-wave group sums of the producers' Vp'v records, [wave][group][column]
+    __shared__ double s_t[OWN ? 1 : NWAVE * 4 * 4 * NCP];   // per-wave group sums of the producers' Vp'v records, [wave][group][column]
     __shared__ double s_u[4 * NCP];
     __shared__ double s_h[4 * NC];
     __shared__ double s_q[4 * NC];
@@ -499,7 +502,8 @@ lz_orth_body(const double* __restrict__ Ppart, int nt, int npad, const double* _
     double pv[16];                                   // mat-vec partial slots wv, wv+4, ...
     double av[8];                                    // per-tile shares of w' P~ w'
     constexpr int NLP = (NCHP > 0 ? NCHP : 1);       // 64-column chunks of the Vp'v records (lane <-> column)
-    double vrp[NCP], tp[16][NLP], eb = 0.0, ap = 0.0; // operator form: Vp columns, Vp'v partials, (E v)_i, v'Ev partials
+    double vrp[NCP], tp[OWN ? 1 : 16][NLP], eb = 0.0, ap = 0.0; // operator form: Vp columns, Vp'v partials, (E v)_i, v'Ev partials
+    double t_j = 0.0, t_l0 = 0.0, t_l1 = 0.0;        // owner form: t_c for thread <-> column and lane <-> column
     if constexpr (NCHP == 0) {
 #pragma unroll
         for (int u = 0; u < 16; ++u) pv[u] = (wv + u * NWAVE < nt) ? Ppart[(long long)(wv + u * NWAVE) * npad + i] : 0.0;   // (uniform test)
@@ -512,13 +516,19 @@ lz_orth_body(const double* __restrict__ Ppart, int nt, int npad, const double* _
             const int cc = min(wv + 4 * c, max(fo.rp - 1, 0));
             vrp[c] = fo.Vp[(long long)cc * ldv + i];
         }
-        // Vp'v partials: records of the producers wv, wv + 4, ... (lane <-> column)
+        if constexpr (OWN) {
+            t_j = fo.tred[min((int)threadIdx.x, RLD - 1)];
+            t_l0 = fo.tred[lane];
+            if constexpr (NCHP > 1) t_l1 = fo.tred[lane + WAVE];
+        } else {
+            // Vp'v partials: records of the producers wv, wv + 4, ... (lane <-> column)
 #pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const long long rec = (long long)min(wv + NWAVE * u, pld - 1) * RLD;
+            for (int u = 0; u < 16; ++u) {
+                const long long rec = (long long)min(wv + NWAVE * u, pld - 1) * RLD;
 #pragma unroll
-            for (int ch = 0; ch < NLP; ++ch)
-                tp[u][ch] = ((ch == 0 || 64 * ch < fo.rp) && (wv + NWAVE * u < nt || pld > WAVE)) ? fo.tpart[rec + 64 * ch + lane] : 0.0;
+                for (int ch = 0; ch < NLP; ++ch)
+                    tp[u][ch] = ((ch == 0 || 64 * ch < fo.rp) && (wv + NWAVE * u < nt || pld > WAVE)) ? fo.tpart[rec + 64 * ch + lane] : 0.0;
+            }
         }
         eb = fo.ebuf[i];
         ap = fo.apart[gl0];
@@ -570,18 +580,20 @@ lz_orth_body(const double* __restrict__ Ppart, int nt, int npad, const double* _
         if (lane == 0) s_red[wv] = a;
     } else {
         // t = Vp' v: this wave's share of the producers' records, fixed order; the four waves meet in s_t
+        if constexpr (!OWN) {
 #pragma unroll
-        for (int ch = 0; ch < NLP; ++ch) {
-            double pr[16], q4[4];
+            for (int ch = 0; ch < NLP; ++ch) {
+                double pr[16], q4[4];
 #pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                pr[u] = tp[u][ch];
-                if (64 * ch < fo.rp)
-                    for (int g = wv + NWAVE * u + WAVE; g < pld; g += WAVE) pr[u] += fo.tpart[(long long)g * RLD + 64 * ch + lane];   // n > 4096
+                for (int u = 0; u < 16; ++u) {
+                    pr[u] = tp[u][ch];
+                    if (64 * ch < fo.rp)
+                        for (int g = wv + NWAVE * u + WAVE; g < pld; g += WAVE) pr[u] += fo.tpart[(long long)g * RLD + 64 * ch + lane];   // n > 4096
+                }
+                tree_in_wave(pr, q4);
+#pragma unroll
+                for (int a = 0; a < 4; ++a) s_t[(wv * 4 + a) * (64 * NLP) + 64 * ch + lane] = q4[a];
             }
-            tree_in_wave(pr, q4);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) s_t[(wv * 4 + a) * (64 * NLP) + 64 * ch + lane] = q4[a];
         }
         if (lane >= pld) ap = 0.0;
         else for (int g = lane + WAVE; g < pld; g += WAVE) ap += fo.apart[g];
@@ -598,14 +610,18 @@ lz_orth_body(const double* __restrict__ Ppart, int nt, int npad, const double* _
         wi = ((s_acc[0][lane] + s_acc[1][lane]) + (s_acc[2][lane] + s_acc[3][lane])) * (INV_SQRT2 * binv);
     } else {
         // v'Av = t' Lam t + v'Ev;   u = Lam t for the row-wise rebuild below
-        auto tsum = [&](int c) { return tree_across(s_t, 64 * NLP, c); };   // t_c from the waves' group sums (c < 64 NLP)
+        // t_c from the waves' group sums (c < 64 NLP); owner form: the value loaded from fo.tred
+        auto tsum = [&](int c, double own) {
+            if constexpr (OWN) return own;
+            else return tree_across(s_t, 64 * NLP, c);
+        };
         double tl = 0.0;
-        if (lane < fo.rp) { const double t0 = tsum(lane); tl = lam_l0 * t0 * t0; }
-        if constexpr (NCHP > 1) if (lane + WAVE < fo.rp) { const double t1 = tsum(lane + WAVE); tl += lam_l1 * t1 * t1; }
+        if (lane < fo.rp) { const double t0 = tsum(lane, t_l0); tl = lam_l0 * t0 * t0; }
+        if constexpr (NCHP > 1) if (lane + WAVE < fo.rp) { const double t1 = tsum(lane + WAVE, t_l1); tl += lam_l1 * t1 * t1; }
         tl = wave_sum(tl);
         alpha = (tl + s_red[0]) * binv * binv;
         wi = eb * binv;                              // + Vp u / beta, folded into the exchange below
-        if (j < 4 * NCP) s_u[j] = (j < fo.rp) ? lam_j * tsum(j) : 0.0;
+        if (j < 4 * NCP) s_u[j] = (j < fo.rp) ? lam_j * tsum(j, t_j) : 0.0;
     }
     double ck = alpha;
     if (first) {
@@ -681,7 +697,7 @@ lz_orth_body(const double* __restrict__ Ppart, int nt, int npad, const double* _
     }
     PX_TL(1, k, 6);
 }
-template <int NCH, int NCHP>
+template <int NCH, int NCHP, bool OWN = false>
 __global__ void __launch_bounds__(TPB)
 k_lz_orth(const double* __restrict__ Ppart, int nt, int npad, const double* __restrict__ V, int ldv, int k,
           double* __restrict__ wbuf, const double* __restrict__ hred, double* __restrict__ hpart_out, int pld,
@@ -689,8 +705,8 @@ k_lz_orth(const double* __restrict__ Ppart, int nt, int npad, const double* __re
           const double* __restrict__ alphas, const double* __restrict__ betas,
           const double* __restrict__ Apart, int napart, int first, const double* __restrict__ arrow, int keep,
           FopArgs fo) {
-    lz_orth_body<NCH, NCHP>(Ppart, nt, npad, V, ldv, k, wbuf, hred, hpart_out, pld, hsum_out, ctl, alphas, betas, Apart,
-                            napart, first, arrow, keep, fo);
+    lz_orth_body<NCH, NCHP, OWN>(Ppart, nt, npad, V, ldv, k, wbuf, hred, hpart_out, pld, hsum_out, ctl, alphas, betas, Apart,
+                                 napart, first, arrow, keep, fo);
 }
 
 // second pass applied and the step closed:
@@ -986,7 +1002,55 @@ struct EllOverflow {
     const int* ov_col;
     const int* ov_sidx;
 };
-template <int NCHP>
+// The owner form of t = Vp' v (nt <= 64 row blocks, rp <= 2 nt): workgroup g of a second set takes the WHOLE of column g (and
+// of column g + nt < rp) while the row workgroups keep E v and v'Ev only (fop_body<., false>).  Wave wv holds the 64-row
+// blocks wv, wv + 4, ... (lane <-> row), so the 16 things fold16_all reduces over the lanes are row blocks here, columns in
+// the records form -- per block the same tree over its rows, i.e. the very number a record holds.  The 64 block sums (+0.0
+// from block nt on, as the zero records) are then added as k_lz_orth adds the records, tree_in_wave (lanes ^2, ^1 of a
+// wave) and tree_across (s_o, lanes of wave 0), and t_c goes to tred[c]: k_lz_orth<., ., true> reads rp numbers where every
+// one of its workgroups loaded nt records and repeated that tree.  Same sums, same bits.
+__device__ __forceinline__ void fop_owner_body(const double* __restrict__ v, const double* __restrict__ Vp, int ldv, int rp,
+                                               int nt, double* __restrict__ tred, int g, const LanczosCtl* __restrict__ ctl) {
+    __shared__ double s_o[2 * NWAVE * 4];                // [column slot][wave][group] sums of four row blocks
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const bool own1 = g + nt < rp;                       // (uniform over the workgroup)
+    if (g >= rp) return;
+    const int stop = (ctl != nullptr) ? ctl->stop : 0;   // tested once the loads are in flight
+    double vb[16], vc0[16], vc1[16];                     // v and the owned columns, row blocks wv + 4u
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        const long long r = (long long)min(wv + NWAVE * u, nt - 1) * LZ_ROWS + lane;
+        vb[u] = v[r];
+        vc0[u] = Vp[(long long)g * ldv + r];
+        if (own1) vc1[u] = Vp[(long long)(g + nt) * ldv + r];
+    }
+    if (stop) return;
+    // per row block the record's tree, then levels g^8, g^4 of the records' tree
+    auto own_col = [&](const double (&vc)[16], int slot) {
+        double t[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) t[u] = (wv + NWAVE * u < nt) ? vc[u] * vb[u] : 0.0;   // (uniform test)
+        double s = fold16_all(t, lane);                  // lane holds row block wv + 4 (lane & 15)
+        s = s + lane_xor<2>(s);                          // tree_in_wave: (p[4a] + p[4a+2]) + (p[4a+1] + p[4a+3])
+        s = s + lane_xor<1>(s);
+        if (lane < 16 && (lane & 3) == 0) s_o[(slot * NWAVE + wv) * 4 + (lane >> 2)] = s;
+    };
+    own_col(vc0, 0);
+    if (own1) own_col(vc1, 1);
+    __syncthreads();
+    if (wv == 0) {                                       // tree_across: levels g^2, g^1 (waves), then g^16, g^32 (groups)
+        const int q = lane & 3, sl = (lane >> 2) & 1;    // lanes 0..3: column g, lanes 4..7: column g + nt
+        const double* so = s_o + sl * NWAVE * 4 + q;
+        double a = (so[0 * 4] + so[2 * 4]) + (so[1 * 4] + so[3 * 4]);
+        a = a + lane_xor<1>(a);                          // (a[0] + a[1]), (a[2] + a[3])
+        a = a + lane_xor<2>(a);
+        if (lane == 0) tred[g] = a;
+        if (lane == 4 && own1) tred[g + nt] = a;
+    }
+}
+// the row-local pieces of workgroup g: (E v)_i, its share of v'Ev and, REC (records form), its record of Vp'v
+template <int NCHP, bool REC = true>
 __device__ __forceinline__ void fop_body(const double* __restrict__ v, const double* __restrict__ Vp, int ldv, int rp,
                                          const int* __restrict__ ell_col, const int* __restrict__ ell_sidx, int ell_w,
                                          int npad, const double* __restrict__ esv, double* __restrict__ tpart, int pld,
@@ -1000,9 +1064,11 @@ __device__ __forceinline__ void fop_body(const double* __restrict__ v, const dou
     PX_TL(0, tlk, 0);
     const int stop = (ctl != nullptr) ? ctl->stop : 0;   // tested once the first loads are in flight
     const double vi = v[i];
-    double vrp[NCP];
+    [[maybe_unused]] double vrp[REC ? NCP : 1];
+    if constexpr (REC) {
 #pragma unroll
-    for (int c = 0; c < NCP; ++c) vrp[c] = Vp[(long long)min(wv + 4 * c, max(rp - 1, 0)) * ldv + i];
+        for (int c = 0; c < NCP; ++c) vrp[c] = Vp[(long long)min(wv + 4 * c, max(rp - 1, 0)) * ldv + i];
+    }
     // E v: the waves split the ELL entries of the row (first 4 entries per wave prefetched)
     int col0[4], sx0[4];
 #pragma unroll
@@ -1053,15 +1119,17 @@ __device__ __forceinline__ void fop_body(const double* __restrict__ v, const dou
             }
         }
     }
-    // Vp' v partials of this workgroup's rows
+    if constexpr (REC) {
+        // Vp' v partials of this workgroup's rows
 #pragma unroll
-    for (int ch = 0; ch < NCHP; ++ch) {
-        double t[16];
+        for (int ch = 0; ch < NCHP; ++ch) {
+            double t[16];
 #pragma unroll
-        for (int c = 0; c < 16; ++c) t[c] = vrp[16 * ch + c] * vi;
-        const double ts = fold16_all(t, lane);
-        const int cc = wv + 4 * (16 * ch + lane);
-        if (lane < 16 && cc < rp) tpart[(long long)g * RLD + cc] = ts;
+            for (int c = 0; c < 16; ++c) t[c] = vrp[16 * ch + c] * vi;
+            const double ts = fold16_all(t, lane);
+            const int cc = wv + 4 * (16 * ch + lane);
+            if (lane < 16 && cc < rp) tpart[(long long)g * RLD + cc] = ts;
+        }
     }
     __syncthreads();
     PX_TL(0, tlk, 3);
@@ -1073,18 +1141,23 @@ __device__ __forceinline__ void fop_body(const double* __restrict__ v, const dou
     }
     PX_TL(0, tlk, 4);
 }
-// first mat-vec of a cycle (on the normalised v_k); grid = nt
-template <int NCHP>
+// first mat-vec of a cycle (on the normalised v_k); grid = nt, owner form (OWN): 2 nt -- the column owners behind the rows
+template <int NCHP, bool OWN = false>
 __global__ void __launch_bounds__(TPB)
 k_fop(const double* __restrict__ v, const double* __restrict__ Vp, int ldv, int rp,
       const int* __restrict__ ell_col, const int* __restrict__ ell_sidx, int ell_w, int npad,
       const double* __restrict__ esv, double* __restrict__ tpart, int pld, double* __restrict__ ebuf,
-      double* __restrict__ apart, const LanczosCtl* __restrict__ ctl, EllOverflow ov) {
+      double* __restrict__ apart, const LanczosCtl* __restrict__ ctl, EllOverflow ov, double* __restrict__ tred) {
     __shared__ double s_e[NWAVE * LZ_ROWS];
-    fop_body<NCHP>(v, Vp, ldv, rp, ell_col, ell_sidx, ell_w, npad, esv, tpart, pld, ebuf, apart, blockIdx.x, s_e, ctl, ov);
+    if constexpr (OWN) {
+        const int nt = (int)gridDim.x / 2;
+        if ((int)blockIdx.x >= nt) { fop_owner_body(v, Vp, ldv, rp, nt, tred, (int)blockIdx.x - nt, ctl); return; }
+    }
+    fop_body<NCHP, !OWN>(v, Vp, ldv, rp, ell_col, ell_sidx, ell_w, npad, esv, tpart, pld, ebuf, apart, blockIdx.x, s_e, ctl, ov);
 }
-// closing work of step k (workgroups [0, nt)) + operator rows of step k+1 on w' ([nt, 2 nt))
-template <int NCHP, int NCH>
+// closing work of step k (workgroups [0, nt)) + operator rows of step k+1 on w' ([nt, 2 nt)); owner form (OWN): grid = 3 nt,
+// the column owners of step k+1 in [2 nt, 3 nt)
+template <int NCHP, int NCH, bool OWN = false>
 __global__ void __launch_bounds__(TPB)
 k_fop_finish(const double* __restrict__ wbuf, double* __restrict__ V, int ldv, int k,
              const double* __restrict__ hpart_in, int pld, const double* __restrict__ h1,
@@ -1092,7 +1165,7 @@ k_fop_finish(const double* __restrict__ wbuf, double* __restrict__ V, int ldv, i
              int use_carry, int nt, const double* __restrict__ Vp, int rp,
              const int* __restrict__ ell_col, const int* __restrict__ ell_sidx, int ell_w, int npad,
              const double* __restrict__ esv, double* __restrict__ tpart, double* __restrict__ ebuf,
-             double* __restrict__ apart, double* __restrict__ hred, EllOverflow ov) {
+             double* __restrict__ apart, double* __restrict__ hred, EllOverflow ov, double* __restrict__ tred) {
     __shared__ double s_a[2 * NWAVE * TILE];
     __shared__ double s_b[NWAVE * LZ_ROWS];
     __shared__ double s_beta;
@@ -1100,8 +1173,11 @@ k_fop_finish(const double* __restrict__ wbuf, double* __restrict__ V, int ldv, i
         lz_finish_body<NCH>(wbuf, V, ldv, k, hpart_in, pld, h1, alphas, betas, ctl, tol, use_carry, blockIdx.x,
                             s_a, s_b, &s_beta, hred, nt);
     } else {
-        fop_body<NCHP>(wbuf, Vp, ldv, rp, ell_col, ell_sidx, ell_w, npad, esv, tpart, pld, ebuf, apart,
-                       (int)blockIdx.x - nt, s_b, ctl, ov, k + 1);
+        if constexpr (OWN) {
+            if ((int)blockIdx.x >= 2 * nt) { fop_owner_body(wbuf, Vp, ldv, rp, nt, tred, (int)blockIdx.x - 2 * nt, ctl); return; }
+        }
+        fop_body<NCHP, !OWN>(wbuf, Vp, ldv, rp, ell_col, ell_sidx, ell_w, npad, esv, tpart, pld, ebuf, apart,
+                             (int)blockIdx.x - nt, s_b, ctl, ov, k + 1);
     }
 }
 

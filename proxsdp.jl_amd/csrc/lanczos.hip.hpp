@@ -29,14 +29,23 @@ inline EigEvents* Solver::profiled_launch(EigWork& W, int phase) const {
     return phase == 0 ? &W.ev : &W.evo;
 }
 
+// the operator-form launches of the run in progress are on the owner form (LzPlan::fop_owner): the mat-vec launches write
+// W.tred, k_lz_orth reads it.  (lanczos_certificate launches under the plan of the run it certifies: the form's own
+// conditions are tested again)
+inline bool lz_fop_owner(const EigWork& W) {
+    return W.use_fop && W.lzrun.plan.fop_owner && W.pld <= dev::WAVE && W.F_r > 0 && W.F_r <= 2 * W.nt;
+}
+
 inline void Solver::launch_symv(EigWork& W, const double* xp, const double* v, bool use_ctl, dev::LanczosCtl* ctl) {
     EigEvents* const prof = profiled_launch(W, 0);
     if (W.use_fop) {
-        auto kern = (W.F_r <= 64) ? dev::k_fop<1> : dev::k_fop<2>;
-        launch_prof(prof, kern, dim3(W.nt), stream,
+        const bool own = lz_fop_owner(W);
+        auto kern = own ? ((W.F_r <= 64) ? dev::k_fop<1, true> : dev::k_fop<2, true>)
+                        : ((W.F_r <= 64) ? dev::k_fop<1> : dev::k_fop<2>);
+        launch_prof(prof, kern, dim3(own ? 2 * W.nt : W.nt), stream,          // (owner form: nt column owners behind the rows)
                     v, W.prev_factors().V, W.npad, W.F_r,
                     (const int*)W.ell_col.p, (const int*)W.ell_sidx.p, W.ell_w, W.npad, W.esv, W.tpart.p, W.pld,
-                    W.ebuf.p, W.apartf.p, (const dev::LanczosCtl*)(use_ctl ? W.ctl_p : nullptr), W.ov);
+                    W.ebuf.p, W.apartf.p, (const dev::LanczosCtl*)(use_ctl ? W.ctl_p : nullptr), W.ov, W.tred.p);
     } else {
         launch_prof(prof, dev::k_symv_packed, dim3(W.napart), stream,
                     xp, W.n, W.nt, W.npad, v, W.Ppart.p, (const dev::LanczosCtl*)(use_ctl ? (ctl ? ctl : W.ctl_p) : nullptr), W.Apart.p);
@@ -52,13 +61,15 @@ inline void Solver::launch_symv_finish(EigWork& W, const double* xp, int kclose,
     with_nch(kclose + 1, [&](auto nch) {
         constexpr int NCH = decltype(nch)::value;
         if (W.use_fop) {
-            auto kern = (W.F_r <= 64) ? dev::k_fop_finish<1, NCH> : dev::k_fop_finish<2, NCH>;
-            launch_prof(prof, kern, dim3(2 * W.nt), stream,
+            const bool own = lz_fop_owner(W);
+            auto kern = own ? ((W.F_r <= 64) ? dev::k_fop_finish<1, NCH, true> : dev::k_fop_finish<2, NCH, true>)
+                            : ((W.F_r <= 64) ? dev::k_fop_finish<1, NCH> : dev::k_fop_finish<2, NCH>);
+            launch_prof(prof, kern, dim3((own ? 3 : 2) * W.nt), stream,
                         (const double*)W.w.p, W.V.p, W.npad, kclose, (const double*)lz_hpart(W, kclose), W.pld,
                         (const double*)W.hsum1.p, W.alphas_p, W.betas_p, W.ctl_p, tol, use_carry ? 1 : 0, W.nt,
                         W.prev_factors().V, W.F_r,
-                        (const int*)W.ell_col.p, (const int*)W.ell_sidx.p, W.ell_w, W.npad, W.esv, W.tpart.p, W.ebuf.p,
-                        W.apartf.p, W.hred.p, W.ov);
+                        (const int*)W.ell_col.p, (const int*)W.ell_sidx.p, W.ell_w, W.npad, W.esv, W.tpart.p,
+                        W.ebuf.p, W.apartf.p, W.hred.p, W.ov, W.tred.p);
         } else {
             launch_prof(prof, dev::k_symv_finish<NCH>, dim3(W.nt + W.napart), stream,
                         xp, W.n, W.nt, W.npad, W.Ppart.p, (const double*)W.w.p, W.V.p, W.npad, kclose,
@@ -92,8 +103,10 @@ inline void Solver::lz_launch_orth(EigWork& W, int k, int first, int keep, EigEv
     if (W.use_fop) {
         const EigWork::Factors F = W.prev_factors();
         fo.Vp = F.V; fo.lam = F.lam; fo.rp = F.r;
-        fo.tpart = W.tpart.p; fo.ebuf = W.ebuf.p; fo.apart = W.apartf.p;
+        fo.tpart = W.tpart.p; fo.tred = W.tred.p; fo.ebuf = W.ebuf.p; fo.apart = W.apartf.p;
     }
+    const bool own = lz_fop_owner(W);
+    if (own) W.lst.reserved_s[PROXSDP_STATS_FOP_OWNER_STEPS]++;
     auto launch_orth = [&](auto kern) {
         launch_prof(prof, kern, dim3(W.nt), stream,
                     (const double*)W.Ppart.p, W.nt, W.npad, (const double*)W.V.p, W.npad, k, W.w.p,
@@ -101,11 +114,11 @@ inline void Solver::lz_launch_orth(EigWork& W, int k, int first, int keep, EigEv
                     (const dev::LanczosCtl*)W.ctl_p, (const double*)W.alphas_p, (const double*)W.betas_p,
                     (const double*)W.Apart.p, W.napart, first, (const double*)W.arrow_p, keep, fo);
     };
-    with_nch(k + 1, [&](auto nch) {                  // <NCH, NCHP>: NCHP = 0 packed operator, 1 / 2 operator form (factor rank <= 64 / more)
+    with_nch(k + 1, [&](auto nch) {                  // <NCH, NCHP, OWN>: NCHP = 0 packed operator, 1 / 2 operator form (factor rank <= 64 / more)
         constexpr int NCH = decltype(nch)::value;
         if (!W.use_fop) launch_orth(dev::k_lz_orth<NCH, 0>);
-        else if (W.F_r <= 64) launch_orth(dev::k_lz_orth<NCH, 1>);
-        else launch_orth(dev::k_lz_orth<NCH, 2>);
+        else if (W.F_r <= 64) { if (own) launch_orth(dev::k_lz_orth<NCH, 1, true>); else launch_orth(dev::k_lz_orth<NCH, 1>); }
+        else { if (own) launch_orth(dev::k_lz_orth<NCH, 2, true>); else launch_orth(dev::k_lz_orth<NCH, 2>); }
     });
 }
 
@@ -381,6 +394,12 @@ inline void Solver::lz_plan(EigWork& W, LzRun& R, bool single_block) {
     // thread; a batched run has no split, a block worker thread keeps the host merge (counted as a fallback)
     p.dev_wanted = p.split && (opt.device_eig_merge == 1 || (opt.device_eig_merge < 0 && krylovdim >= 64));
     p.dev_merge = p.dev_wanted && rot_sink == nullptr && StreamRef::tl == nullptr && DeviceMerge::eligible(krylovdim);
+    // owner form of the operator-form step (kernels.hip.hpp fop_owner_body): one workgroup per factor column finishes t = Vp'v.
+    // Needs the 64 row blocks of a column in one workgroup's registers and a column (or two) per workgroup -- and a column at
+    // all (x_prev = 0 off the support has none); lanczos()'s runs only (lanczos_eager runs the packed operator, a batched
+    // run the packed kernels)
+    p.fop_owner = single_block && fop_owner_knob != 0 && W.use_fop && p.engine == LzEngine::step && W.tred.n > 0 &&
+                  W.pld <= dev::WAVE && W.F_r > 0 && W.F_r <= 2 * W.nt;
 }
 
 // while the GPU works through the enqueued steps: reduce the arrow part [diag(D) f; f' .] of this cycle's

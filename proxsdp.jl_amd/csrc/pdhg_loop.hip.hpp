@@ -970,6 +970,7 @@ inline void Solver::setup_support() {
             W.F.alloc((size_t)W.npad * W.cap); W.F.zero(stream);
             W.Flam.alloc(std::max(W.n, dev::MAXK)); W.Flam.zero(stream);
             W.tpart.alloc((size_t)dev::MAXK * W.pld); W.tpart.zero(stream);
+            W.tred.alloc(dev::RLD); W.tred.zero(stream);
             W.ebuf.alloc(W.npad); W.ebuf.zero(stream);
             W.apartf.alloc(W.pld); W.apartf.zero(stream);
             W.warm_part.alloc(ceil_div(W.npad, dev::TPB)); W.warm_part.zero(stream);

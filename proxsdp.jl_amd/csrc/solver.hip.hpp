@@ -238,6 +238,7 @@ struct LzPlan {
     bool split = false;               // split + rank-one merge of the K x K eigensolve (host_eig_merge.hpp), first part under the cycle
     bool dev_wanted = false;          // options.device_eig_merge asks for the merge on the device (one on the host is a fallback) ...
     bool dev_merge = false;           // ... and the run is one merge_device.hip.hpp serves: this run's merges go there
+    bool fop_owner = false;           // operator form: t = Vp'v finished by column owners in the mat-vec launch (fop_owner_body)
 };
 // Host state of ONE thick-restart Lanczos run (one PSD block): what KrylovKit keeps between the restarts of an
 // eigsolve call.  The single-block driver and the batched multi-block driver (lanczos_batch: one launch per step for
@@ -300,7 +301,7 @@ struct EigWork {
     int count = 0, converged_eigs = 0, numiter = 0, prev_numiter = 1;
     bool converged = false;
     // operator-form mat-vec (kernels.hip.hpp "Operator-form mat-vec")
-    DevBuf<double> F, Flam, tpart, ebuf, apartf;   // (lam / Flam swap roles every projection)   // F: npad x cap, the previous projection's Ritz vectors (swapped with Z)
+    DevBuf<double> F, Flam, tpart, tred, ebuf, apartf;   // (lam / Flam swap roles every projection)   // F: npad x cap, the previous projection's Ritz vectors (swapped with Z)
     DevBuf<int> ell_col, ell_sidx;                 // E in ELL form, [k * npad + row]
     DevBuf<int> wr_ptr, wr_row, wr_lo, wr_hi, ov_col, ov_sidx;   // entries beyond the ELL width (hub rows)
     dev::EllOverflow ov{};
@@ -496,6 +497,7 @@ public:
     int block1_lds_cap = 0;                       // dynamic LDS granted to k_lz_block1 (setup_device)
     DevBuf<long long> b1_dbg;                     // PROXSDP_HIP_DEBUG_B1: tick sums of k_lz_block1 (prologue | loop | epilogue | steps | launches)
     bool sg48_ok = false;                         // 72 KiB of dynamic LDS granted to k_sym_gemm48 (setup_device)
+    int fop_owner_knob = -1;                      // PROXSDP_HIP_FOP_OWNER (setup_device): 0 = records form always, unset = auto
     // the host driver of the Lanczos engine (lanczos.hip.hpp), in its order: launches, rotations, a run, the drivers
     EigEvents* profiled_launch(EigWork& W, int phase) const;
     void launch_symv(EigWork& W, const double* xp, const double* v, bool use_ctl, dev::LanczosCtl* ctl = nullptr);
@@ -911,6 +913,8 @@ inline void Solver::setup_device() {
         (void)hipGetLastError();
     }
     if (std::getenv("PROXSDP_HIP_DEBUG_B1") != nullptr) { b1_dbg.alloc(8); b1_dbg.zero(stream); }
+    // PROXSDP_HIP_FOP_OWNER = 0: the operator-form step stays on the records form (A/B measurement); unset: lz_plan decides
+    if (const char* env = std::getenv("PROXSDP_HIP_FOP_OWNER")) fop_owner_knob = (env[0] == '0' && env[1] == 0) ? 0 : -1;
     block1_lds_cap = 0;
     for (int kb : {160, 144, 128, 112, 96}) {
         bool ok = true;
@@ -1300,6 +1304,7 @@ inline void Solver::merge_block_stats() {
         PX_MERGE(batched_block_steps);
         PX_MERGE(host_eigs); PX_MERGE(host_eig_time); PX_MERGE(host_eig_merges); PX_MERGE(host_eig_overlap_time);
         PX_MERGE(reserved_s[PROXSDP_STATS_DEVICE_EIG_MERGES]); PX_MERGE(reserved_s[PROXSDP_STATS_DEVICE_EIG_MERGE_FALLBACKS]);
+        PX_MERGE(reserved_s[PROXSDP_STATS_FOP_OWNER_STEPS]);
         PX_MERGE(warm_starts); PX_MERGE(device_eigs); PX_MERGE(mfma_reconstructions);
         PX_MERGE(cycle_launches); PX_MERGE(cycle_steps); PX_MERGE(cycle_ms);
         PX_MERGE(fop_projections);
