@@ -728,6 +728,52 @@ int  proxsdp_hip_solve_from(const proxsdp_problem* prob, const proxsdp_options* 
 int  proxsdp_hip_start_point(const proxsdp_problem* prob, const proxsdp_options* opt, const proxsdp_start* start,
                              proxsdp_state* out);
 
+/* ------------------------------------------- solution vectors on the device: out of a solve, and back into the next
+ * proxsdp_hip_solve_device is proxsdp_hip_solve_from bit for bit -- iterates, counts, trace, res, factors -- with two
+ * differences in where vectors live:
+ *   out_dev    the six solution vectors are written into DEVICE buffers of the caller, in the caller's variable order and in
+ *              the units a result holds: exactly the values res->primal ... res->slack_in would hold.  A NULL member is not
+ *              wanted.  Host arrays in `res` may be given as well; they receive the same values, each as ONE contiguous
+ *              download of the vector the device formed.
+ *   start_dev  primal, dual_eq and dual_in of the start point as DEVICE buffers, in the units a result holds (so out_dev of one
+ *              solve is start_dev of the next); k_start_gather reads them where they are, no host copy and no upload.  Factors,
+ *              target_rank, primal_step and beta still come from `start` (they are small).  dual_cone, slack_eq and slack_in
+ *              must be NULL here.
+ * The exit path of this entry runs on the device (csrc/exit_device.hip.hpp, Solver::cache_solution_device): M x, c + M'y, the
+ * slacks, the scatter to the caller's order and the cone reductions of the dual feasibility are kernels compiled with
+ * floating-point contraction off, every sum in the host path's order, so every output equals proxsdp_hip_solve_from's bit for
+ * bit; the iterate never visits the host.  stats.exit_time is that path's time.
+ * Device pointers are BORROWED and TRUSTED, exactly as M_dense with M_dense_on_device = 1 is: they must be valid on device
+ * options.device_id for n / p / m doubles, must not overlap each other, and are not probed.  The library works on a stream of
+ * its own: the caller finishes its own work on the buffers before the call (a device synchronisation, or its streams'), and
+ * the call returns after every write has completed (it synchronises its stream).  There is no stream argument.
+ * PROXSDP_E_INVALID on the host, before any device call: a wrong struct_size; device_id != options.device_id; a non-NULL
+ * dual_cone, slack_eq or slack_in in start_dev; a vector given both in `start` and in `start_dev`; everything
+ * proxsdp_hip_solve_from refuses.  ONE check happens after the device exists: that primal, dual_eq and dual_in of start_dev
+ * hold finite numbers is a reduction on the device after set-up; a non-finite entry returns PROXSDP_E_INVALID before
+ * iteration 1, and the message names the vector.  PROXSDP_E_UNSUPP: prob is a shard (as proxsdp_hip_solve_factored).
+ * With start, start_dev, fac and out_dev all NULL the call is proxsdp_hip_solve_from with the device exit path. */
+typedef struct proxsdp_device_vectors {
+    int64_t struct_size;    /* = sizeof(proxsdp_device_vectors) */
+    int32_t device_id;      /* must equal options.device_id */
+    int32_t reserved;
+    double* primal;  double* dual_cone;      /* n each,  DEVICE pointers, NULL = not wanted / not given */
+    double* dual_eq; double* slack_eq;       /* p each */
+    double* dual_in; double* slack_in;       /* m each */
+} proxsdp_device_vectors;
+int  proxsdp_hip_solve_device(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                              const proxsdp_start* start /* may be NULL */, const proxsdp_device_vectors* start_dev /* may be NULL */,
+                              proxsdp_psd_factors* fac /* may be NULL */, proxsdp_device_vectors* out_dev /* may be NULL */);
+/* test entry: the device exit path alone (Solver::cache_solution_device's launches) on host data.  x (n) is an internal iterate
+ * in the solver's order and scale as the loop leaves it, y (p + m) the internal dual; zero_c != 0 takes c = 0 (the certificate
+ * snapshot).  Out, on the host: the six vectors in the caller's order (any may be NULL); viol[4] = the violations of the
+ * inequality duals, of the 1x1 cones, of the second-order cones and of the free variables; neg = minus the dual-cone block of
+ * every PSD cone of side >= 2, one after the other in cone order, as the lambda_min run reads it (neg_cap doubles of room;
+ * PROXSDP_E_INVALID when that is too little). */
+int  proxsdp_hip_exit_vectors(const proxsdp_problem* prob, const proxsdp_options* opt, const double* x, const double* y,
+                              int32_t zero_c, double* primal, double* dual_cone, double* dual_eq, double* dual_in,
+                              double* slack_eq, double* slack_in, double* viol, double* neg, int64_t neg_cap);
+
 /* ------------------------------------------- RCCL communicator helpers (block-sharded solves)
  * The library loads librccl at run time (dlopen; it does not link it).  One rank calls _unique_id and
  * ships the 128 bytes to the others by any means (MPI, torch.distributed, a file); every rank then calls

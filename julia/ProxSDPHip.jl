@@ -192,6 +192,23 @@ struct Start                     # proxsdp_start
     beta::Float64
 end
 
+struct DeviceVectors             # proxsdp_device_vectors: DEVICE pointers, borrowed and trusted (C_NULL = not wanted / not given)
+    struct_size::Int64
+    device_id::Int32
+    reserved::Int32
+    primal::Ptr{Float64}
+    dual_cone::Ptr{Float64}
+    dual_eq::Ptr{Float64}
+    slack_eq::Ptr{Float64}
+    dual_in::Ptr{Float64}
+    slack_in::Ptr{Float64}
+end
+function _device_vectors(nt::NamedTuple)
+    g(name) = haskey(nt, name) ? Ptr{Float64}(getfield(nt, name)) : Ptr{Float64}(C_NULL)
+    DeviceVectors(sizeof(DeviceVectors), Int32(haskey(nt, :device_id) ? nt.device_id : 0), Int32(0),
+                  g(:primal), g(:dual_cone), g(:dual_eq), g(:slack_eq), g(:dual_in), g(:slack_in))
+end
+
 # proxsdp_options is filled by name, exactly like MOI.RawOptimizerAttribute does for the
 # reference (src/MOI_wrapper.jl:84-93): an opaque, suitably large and aligned buffer plus
 # proxsdp_hip_default_options / proxsdp_hip_set_option keeps this file independent of the C
@@ -236,13 +253,25 @@ what a previous `Result` holds; `factors[k] = (values, vectors)` or `nothing` pe
 `factors = true` solve returned: that cone then starts at `vectors * Diagonal(values) * vectors'` and at target rank
 `length(values) + 1`); `target_rank[k] > 0` overrides the target rank of cone k.  Combines with `factors`, not with
 `n_shards > 1`.
+`device_out = (device_id = 0, primal = ptr, dual_cone = ptr, dual_eq = ptr, slack_eq = ptr, dual_in = ptr, slack_in = ptr)`
+and / or `start_dev = (device_id = 0, primal = ptr, dual_eq = ptr, dual_in = ptr)` (NamedTuples of DEVICE pointers, e.g.
+`pointer(::ROCArray{Float64})`; every field optional): the solve through `proxsdp_hip_solve_device`.  The six vectors of
+the result are written into the caller's device buffers, in the caller's order and in the units of a `Result` (the host
+vectors of the returned `Result` receive the same values), and the start point's `primal`, `dual_eq`, `dual_in` are read
+from device buffers in those same units (a vector may be given in `start` or in `start_dev`, not both; factors, target
+ranks and steps stay in `start`).  `device_id` must be the device the options name.  The pointers are borrowed and
+trusted, as a device `M_dense` is; the library runs on its own stream, so synchronise the device before the call -- it
+returns after its writes have completed.  Not with `n_shards > 1`.  (Like the rest of this wrapper the two keywords cannot
+be run where the library is tested; the struct is checked against the header, the entry through the ctypes binding.)
 (This wrapper cannot be executed where the library is tested: there is no Julia there.  Its struct is checked against the
 header field by field, the call itself is exercised through the ctypes binding.)
 """
 function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
                             n_shards::Integer = 1, device_ids::Union{Nothing,AbstractVector{<:Integer}} = nothing,
                             factors::Union{Nothing,Bool,AbstractVector{<:Integer}} = nothing,
-                            start::Union{Nothing,NamedTuple} = nothing)
+                            start::Union{Nothing,NamedTuple} = nothing,
+                            device_out::Union{Nothing,NamedTuple} = nothing,
+                            start_dev::Union{Nothing,NamedTuple} = nothing)
     psd_ptr = Int64[0]; psd_idx = Int64[]
     for s in con.sdpcone
         append!(psd_idx, s.vec_i); push!(psd_ptr, length(psd_idx))
@@ -275,6 +304,8 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
     fresid = zeros(max(nb, 1)); fxnorm = zeros(max(nb, 1))
     # warm start: the caller's arrays as Float64 / Int64 vectors, the factors of every cone concatenated column-major
     (start !== nothing && sharded) && error("start: not available in a block-sharded solve")
+    on_device = device_out !== nothing || start_dev !== nothing
+    (on_device && sharded) && error("device_out / start_dev: not available in a block-sharded solve")
     sget(name) = (start !== nothing && haskey(start, name)) ? getfield(start, name) : nothing
     s_primal = sget(:primal) === nothing ? Float64[] : Vector{Float64}(sget(:primal))
     s_deq = sget(:dual_eq) === nothing ? Float64[] : Vector{Float64}(sget(:dual_eq))
@@ -317,6 +348,22 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
                   (Ref{Problem}, Ptr{UInt64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ref{CResult}, Ptr{Stats}),
                   prob, opt, Int32(n_shards), device_ids === nothing ? Ptr{Int32}(C_NULL) : pointer(devs),
                   C_NULL, C_NULL, C_NULL, res, C_NULL)                # default owners, no per-shard stats
+        elseif on_device
+            st = Start(sizeof(Start), ptr_or_null(s_primal, sget(:primal) !== nothing),
+                       ptr_or_null(s_deq, sget(:dual_eq) !== nothing && p > 0), ptr_or_null(s_din, sget(:dual_in) !== nothing && m > 0),
+                       s_fac === nothing ? 0 : nb, pointer(s_rank), pointer(s_vec_ptr), pointer(s_val_ptr),
+                       pointer(s_vectors), pointer(s_values), ptr_or_null(s_tr, sget(:target_rank) !== nothing && nb > 0),
+                       sget(:primal_step) === nothing ? 0.0 : Float64(sget(:primal_step)),
+                       sget(:beta) === nothing ? 0.0 : Float64(sget(:beta)))
+            fac = PsdFactors(sizeof(PsdFactors), nb, pointer(caps), pointer(fvec_ptr), pointer(fval_ptr),
+                             pointer(fvectors), pointer(fvalues), pointer(frank), pointer(ffound), pointer(fsource),
+                             pointer(fresid), pointer(fxnorm))
+            sdv = start_dev === nothing ? nothing : _device_vectors(start_dev)
+            odv = device_out === nothing ? nothing : _device_vectors(device_out)
+            ccall((:proxsdp_hip_solve_device, libproxsdp_hip), Cint,
+                  (Ref{Problem}, Ptr{UInt64}, Ref{CResult}, Ptr{Start}, Ptr{DeviceVectors}, Ptr{PsdFactors}, Ptr{DeviceVectors}),
+                  prob, opt, res, start === nothing ? C_NULL : Ref(st), sdv === nothing ? C_NULL : Ref(sdv),
+                  want_factors ? Ref(fac) : C_NULL, odv === nothing ? C_NULL : Ref(odv))
         elseif start !== nothing
             st = Start(sizeof(Start), ptr_or_null(s_primal, sget(:primal) !== nothing),
                        ptr_or_null(s_deq, sget(:dual_eq) !== nothing && p > 0), ptr_or_null(s_din, sget(:dual_in) !== nothing && m > 0),

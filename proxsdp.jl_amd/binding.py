@@ -196,6 +196,13 @@ class Start(C.Structure):
                 ("target_rank", pi64), ("primal_step", f64), ("beta", f64)]
 
 
+class DeviceVectors(C.Structure):
+    """proxsdp_device_vectors (include/proxsdp_hip.h): device pointers, borrowed and trusted"""
+    _fields_ = [("struct_size", i64), ("device_id", i32), ("reserved", i32),
+                ("primal", pf64), ("dual_cone", pf64), ("dual_eq", pf64), ("slack_eq", pf64),
+                ("dual_in", pf64), ("slack_in", pf64)]
+
+
 FACTOR_NONE, FACTOR_RITZ, FACTOR_EIG = 0, 1, 2
 FACTOR_SOURCE_NAMES = {FACTOR_NONE: "NONE", FACTOR_RITZ: "RITZ", FACTOR_EIG: "EIG"}
 
@@ -246,6 +253,9 @@ def lib():
     L.proxsdp_hip_solve_from.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Result),
                                          C.POINTER(Start), C.POINTER(PsdFactors)]
     L.proxsdp_hip_start_point.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Start), C.POINTER(State)]
+    L.proxsdp_hip_solve_device.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Result), C.POINTER(Start),
+                                           C.POINTER(DeviceVectors), C.POINTER(PsdFactors), C.POINTER(DeviceVectors)]
+    L.proxsdp_hip_exit_vectors.argtypes = [C.POINTER(Problem), C.POINTER(Options), pf64, pf64, i32] + [pf64] * 8 + [i64]
     L.proxsdp_hip_factor_residual.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64]
     L.proxsdp_hip_factor_residual_kernel.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64, i32, pf64]
     L.proxsdp_hip_psd_project.argtypes = [pf64, i64, i32, i32, C.POINTER(Options), pf64, pf64,
@@ -528,14 +538,68 @@ def _factors_list(sides, arr):
 
 
 START_KEYS = ("primal", "dual_eq", "dual_in", "factors", "target_rank", "primal_step", "beta")
+DEVICE_START_KEYS = ("primal", "dual_eq", "dual_in")
+
+
+def _is_tensor(v):
+    """a torch tensor (torch is imported only by callers who hand one in, or who ask for device_out)"""
+    return hasattr(v, "data_ptr") and hasattr(v, "is_cuda")
+
+
+def _start_on_device(start):
+    """does this start (None, a dict or a SolveResult) hold a CUDA tensor?"""
+    if start is None:
+        return False
+    get = (lambda k: getattr(start, k, None)) if isinstance(start, SolveResult) else dict(start).get
+    return any(_is_tensor(get(k)) and get(k).is_cuda for k in DEVICE_START_KEYS)
+
+
+def _device_ptr(t, length, device_id, what):
+    """the device pointer of a float64 CUDA tensor of `length` entries on cuda:device_id, as a POINTER(c_double)"""
+    if not (t.is_cuda and t.is_contiguous() and t.dtype.is_floating_point and t.element_size() == 8):
+        raise ValueError(f"{what} must be a contiguous float64 CUDA tensor")
+    if t.numel() != length:
+        raise ValueError(f"{what} must have length {length}")
+    if t.device.index != device_id:
+        raise ValueError(f"{what} is on {t.device}, the solve runs on cuda:{device_id}")
+    return C.cast(C.c_void_p(t.data_ptr() if length else 0), pf64)
+
+
+def _device_vectors(device_id, **tensors):
+    """proxsdp_device_vectors over (tensor, length) pairs; the tensors must outlive the call"""
+    D = DeviceVectors()
+    D.struct_size = C.sizeof(DeviceVectors)
+    D.device_id = device_id
+    for k, (t, ln) in tensors.items():
+        if t is not None and ln > 0:
+            setattr(D, k, _device_ptr(t, ln, device_id, k))
+    return D
+
+
+def _split_device_start(start, n, p, m, device_id):
+    """(host part of a start, proxsdp_device_vectors of its CUDA tensors or None, the tensors)"""
+    if isinstance(start, SolveResult):
+        start = start_from_result(start)
+    start = dict(start)
+    dev = {k: start.pop(k) for k in DEVICE_START_KEYS if _is_tensor(start.get(k)) and start[k].is_cuda}
+    for k in DEVICE_START_KEYS:                              # (a CPU tensor is a host array)
+        if _is_tensor(start.get(k)):
+            start[k] = start[k].numpy()
+    if not dev:
+        return start, None, dev
+    ln = dict(primal=n, dual_eq=p, dual_in=m)
+    return start, _device_vectors(device_id, **{k: (v, ln[k]) for k, v in dev.items()}), dev
 
 
 def start_from_result(res):
     """The start dictionary of a previous SolveResult: its primal and duals, and -- when the solve returned them
     (solve(factors=...)) -- the factors of every PSD cone.  A cone whose factors were cut by `cap` (info["rank_found"] >
     info["rank"]) or that asked for none (cap 0) gets None: it starts from its entries of `primal`."""
-    d = dict(primal=None if res.primal is None else np.array(res.primal, dtype=np.float64),
-             dual_eq=np.array(res.dual_eq, dtype=np.float64), dual_in=np.array(res.dual_in, dtype=np.float64))
+    if _is_tensor(res.dual_eq):                              # a device result (solve(device_out=True)): the tensors as they are
+        d = dict(primal=res.primal, dual_eq=res.dual_eq, dual_in=res.dual_in)
+    else:
+        d = dict(primal=None if res.primal is None else np.array(res.primal, dtype=np.float64),
+                 dual_eq=np.array(res.dual_eq, dtype=np.float64), dual_in=np.array(res.dual_in, dtype=np.float64))
     fl = getattr(res, "psd_factors", None)
     if fl is not None:
         fac = []
@@ -627,7 +691,7 @@ def start_point(prob, options=None, start=None, index_base=0, eig_resid=None):
 
 
 def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, coupling=None, index_base=0, nccl_comm=None,
-          resume=None, capture_iteration=None, factors=False, primal=True, start=None):
+          resume=None, capture_iteration=None, factors=False, primal=True, start=None, device_out=False):
     """proxsdp_hip_solve: replaces chambolle_pock(aff, con, options) (MOI_wrapper.jl:310).
     Returns the minimisation objective; sign/constant fix-up is the caller's
     (MOI_wrapper.jl:336-337), see optimizer.Optimizer.
@@ -650,7 +714,17 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
     factors = [(values, vectors) | None per PSD cone], target_rank (per cone, 0 = derive), primal_step, beta; or a previous
     SolveResult, whose psd_factors are used when it has them (a cone cut by `cap` starts from its primal entries).  The
     loop is entered at iteration 1 from that point, each factored cone at target rank rank + 1 unless target_rank says
-    otherwise.  Combines with factors=; not with resume / capture_iteration / reduce / coupling / nccl_comm."""
+    otherwise.  Combines with factors=; not with resume / capture_iteration / reduce / coupling / nccl_comm.
+    device_out = True: proxsdp_hip_solve_device -- the same solve with the exit path on the device; the six vectors of the
+    result are float64 torch tensors on cuda:<options.device_id> (in the caller's order and units, the values the arrays
+    would hold).  start= then also takes CUDA tensors for primal, dual_eq, dual_in, and a device result as it is, so
+    solve(p2, start=solve(p1, device_out=True, factors=True), device_out=True) chains with no n-vector on the host.  The
+    library works on its own stream: the device is synchronised before tensors are handed in, and the call returns after
+    its writes have completed.  Not with resume / capture_iteration / reduce / coupling / nccl_comm."""
+    if device_out or _start_on_device(start):
+        if resume is not None or capture_iteration is not None or reduce is not None or coupling is not None or nccl_comm:
+            raise ValueError("device vectors cannot be combined with the state seam or a block-sharded solve")
+        return _solve_device(prob, options, eig_resid, trace_capacity, index_base, factors, primal, start, device_out)
     L = lib()
     if start is not None and (resume is not None or capture_iteration is not None or reduce is not None or
                               coupling is not None or nccl_comm):
@@ -745,6 +819,80 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
     out = SolveResult(R, n, p, m, arrays, trace)
     out.state = _state_dict(cs, carr, n, Q, nb) if (cs is not None and cs.ints[3] == 1) else None
     return out
+
+
+def _solve_device(prob, options, eig_resid, trace_capacity, index_base, factors, primal, start, device_out):
+    """solve() through proxsdp_hip_solve_device: device tensors out (device_out) and / or in (CUDA tensors in start)"""
+    import torch                                             # (lazily: the host paths do not need it; before lib(), see there)
+    L = lib()
+    if not torch.cuda.is_available():
+        raise RuntimeError("torch sees no GPU: import torch before the first call into the library (see binding.lib)")
+    o = options if options is not None else default_options()
+    if trace_capacity:
+        o.trace_capacity = int(trace_capacity)
+    M = _Marshalled(prob, eig_resid, index_base)
+    n, p, m = int(M.P.n), int(M.P.p), int(M.P.m)
+    dev_id = int(o.device_id)
+    lens = (n, n, p, m, p, m)
+    names = ("primal", "dual_cone", "dual_eq", "dual_in", "slack_eq", "slack_in")
+    trace = np.zeros((max(o.trace_capacity, 1), TRACE_COLS))
+    R = Result()
+    R.trace = _p(trace)
+    out = None
+    if device_out:
+        tens = [torch.empty(k, dtype=torch.float64, device=f"cuda:{dev_id}") for k in lens]
+        if not primal:
+            tens[0] = None
+        out = _device_vectors(dev_id, **{nm: (t, k) for nm, t, k in zip(names, tens, lens)})
+        arrays = tens
+    else:
+        host = [np.zeros(max(k, 1)) for k in lens]
+        R.primal, R.dual_cone, R.dual_eq, R.dual_in, R.slack_eq, R.slack_in = [_p(a) for a in host]
+        if not primal:
+            R.primal = None
+        arrays = [a[:k] for a, k in zip(host, lens)]
+        if not primal:
+            arrays[0] = None
+    st = sd = None
+    if start is not None:
+        hstart, sd, keep_dev = _split_device_start(start, n, p, m, dev_id)
+        st, sarr = _start_struct(n, p, m, psd_sides(prob), hstart)
+    F = None
+    if factors is not False and factors is not None:
+        sides = psd_sides(prob)
+        F, farr = _factors_struct(sides, factors)
+    torch.cuda.synchronize(dev_id)                           # the library runs on its own stream
+    _check(L.proxsdp_hip_solve_device(C.byref(M.P), C.byref(o), C.byref(R), C.byref(st) if st is not None else None,
+                                      C.byref(sd) if sd is not None else None, C.byref(F) if F is not None else None,
+                                      C.byref(out) if out is not None else None))
+    res = SolveResult(R, n, p, m, arrays, trace)
+    if F is not None:
+        res.psd_factors = _factors_list(sides, farr)
+    return res
+
+
+def exit_vectors(prob, x, y, zero_c=False, options=None, index_base=0):
+    """proxsdp_hip_exit_vectors: the device exit path alone on a host iterate (x: n, solver order and scale as the loop leaves
+    it; y: p + m).  Returns dict(primal, dual_cone, dual_eq, dual_in, slack_eq, slack_in, viol (4: inequality duals, 1x1 cones,
+    second-order cones, free variables), neg (minus the dual-cone block of every PSD cone of side >= 2, in cone order))."""
+    L = lib()
+    o = options if options is not None else default_options()
+    M = _Marshalled(prob, None, index_base)
+    n, p, m = int(M.P.n), int(M.P.p), int(M.P.m)
+    x, y = _f(x).ravel(), _f(y).ravel()
+    if len(x) != n or len(y) != p + m:
+        raise ValueError("exit_vectors: x must have n entries and y p + m")
+    lens = dict(primal=n, dual_cone=n, dual_eq=p, dual_in=m, slack_eq=p, slack_in=m)
+    out = {k: np.full(max(v, 1), np.nan) for k, v in lens.items()}
+    nneg = sum(len(v) for v, sd in zip(prob.psd, psd_sides(prob)) if sd >= 2)
+    viol, neg = np.full(4, np.nan), np.full(max(nneg, 1), np.nan)
+    xs, ys = (x if n else np.zeros(1)), (y if p + m else np.zeros(1))
+    _check(L.proxsdp_hip_exit_vectors(C.byref(M.P), C.byref(o), _p(xs), _p(ys), 1 if zero_c else 0,
+                                      *[_p(out[k]) for k in ("primal", "dual_cone", "dual_eq", "dual_in", "slack_eq", "slack_in")],
+                                      _p(viol), _p(neg), nneg))
+    d = {k: out[k][:v] for k, v in lens.items()}
+    d.update(viol=viol, neg=neg[:nneg])
+    return d
 
 
 def _owner_arrays(owners, soc_owners, free_owners):

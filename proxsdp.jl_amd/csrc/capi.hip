@@ -10,6 +10,7 @@
 #include "lanczos.hip.hpp"
 #include "pdhg_loop.hip.hpp"
 #include "projection.hip.hpp"
+#include "exit_device.hip.hpp"
 #include "test_hooks.hip.hpp"
 #include "shard_split.hpp"
 
@@ -162,7 +163,8 @@ static proxsdp_options begin_solve(const proxsdp_options* opt, proxsdp_result* r
 // the solve behind proxsdp_hip_solve_ex and proxsdp_hip_solve_factored (fac: validated by the caller, or NULL)
 static int solve_impl(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
                       const proxsdp_state* resume, proxsdp_state* capture, proxsdp_psd_factors* fac,
-                      const proxsdp_start* start = nullptr) {
+                      const proxsdp_start* start = nullptr, bool device_exit = false,
+                      const proxsdp_device_vectors* start_dev = nullptr, proxsdp_device_vectors* out_dev = nullptr) {
     bool comm_aborted = false;
     const int rc = guarded([&]() -> int {
         if (!prob || !res) throw std::invalid_argument("NULL problem or result");
@@ -172,6 +174,9 @@ static int solve_impl(const proxsdp_problem* prob, const proxsdp_options* opt, p
         S.capture_state = capture;
         S.factors_out = fac;
         S.start = start;
+        S.device_exit = device_exit;
+        S.start_dev = start_dev;
+        S.out_dev = out_dev;
         try {
             S.run();
         } catch (...) {
@@ -291,6 +296,60 @@ int proxsdp_hip_solve_from(const proxsdp_problem* prob, const proxsdp_options* o
     });
     if (rc != 0) return rc;
     return solve_impl(prob, opt, res, nullptr, nullptr, fac, start);
+}
+
+// ---- solution vectors on the device (proxsdp_device_vectors): checked on the host, before a solver exists, except that the
+// start vectors hold finite numbers (Solver::check_start_dev, a device reduction after set-up)
+static void check_device_vectors(const proxsdp_device_vectors* v, int32_t device_id, const char* what) {
+    if (!v) return;
+    if (v->struct_size != (int64_t)sizeof(proxsdp_device_vectors))
+        throw std::invalid_argument(std::string("proxsdp_device_vectors (") + what + "): struct_size mismatch");
+    if (v->device_id != device_id)
+        throw std::invalid_argument(std::string("proxsdp_device_vectors (") + what + "): device_id is not options.device_id");
+}
+
+int proxsdp_hip_solve_device(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                             const proxsdp_start* start, const proxsdp_device_vectors* start_dev,
+                             proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev) {
+    proxsdp_start none{};                                 // start_dev without a start: no factors, cold steps
+    none.struct_size = (int64_t)sizeof(proxsdp_start);
+    const int rc = guarded([&]() -> int {
+        if (!prob || !res) throw std::invalid_argument("NULL problem or result");
+        check_start_arg(prob, start);
+        if (fac) check_factors_arg(prob, res, fac);
+        const int32_t dev_id = Engine::fix(opt).device_id;
+        check_device_vectors(start_dev, dev_id, "start");
+        check_device_vectors(out_dev, dev_id, "out");
+        if (start_dev) {
+            if (start_dev->dual_cone || start_dev->slack_eq || start_dev->slack_in)
+                throw std::invalid_argument("proxsdp_device_vectors (start): dual_cone, slack_eq and slack_in must be NULL");
+            if (start && ((start->primal && start_dev->primal) || (start->dual_eq && start_dev->dual_eq) ||
+                          (start->dual_in && start_dev->dual_in)))
+                throw std::invalid_argument("a start vector is given both on the host (proxsdp_start) and on the device");
+            if (prob->n < 0 || prob->p < 0 || prob->m < 0) throw std::invalid_argument("negative dimension");
+        }
+        if (prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0)
+            throw std::domain_error("proxsdp_hip_solve_device does not serve a shard of a block-sharded solve");
+        return 0;
+    });
+    if (rc != 0) return rc;
+    return solve_impl(prob, opt, res, nullptr, nullptr, fac, (!start && start_dev) ? &none : start, true, start_dev, out_dev);
+}
+
+int proxsdp_hip_exit_vectors(const proxsdp_problem* prob, const proxsdp_options* opt, const double* x, const double* y,
+                             int32_t zero_c, double* primal, double* dual_cone, double* dual_eq, double* dual_in,
+                             double* slack_eq, double* slack_in, double* viol, double* neg, int64_t neg_cap) {
+    return guarded([&]() -> int {
+        if (!prob) throw std::invalid_argument("NULL problem");
+        if ((prob->n > 0 && !x) || (prob->p + prob->m > 0 && !y)) throw std::invalid_argument("exit vectors: NULL iterate");
+        if (prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0)
+            throw std::domain_error("proxsdp_hip_exit_vectors does not serve a shard of a block-sharded solve");
+        proxsdp_result dummy{};
+        const proxsdp_options o = begin_solve(opt, &dummy);
+        proxsdp::Solver S(*prob, o, dummy);
+        S.test_exit_vectors(x, y, zero_c != 0, primal, dual_cone, dual_eq, dual_in, slack_eq, slack_in, viol, neg, neg_cap);
+        return 0;
+    });
 }
 
 int proxsdp_hip_start_point(const proxsdp_problem* prob, const proxsdp_options* opt, const proxsdp_start* start,

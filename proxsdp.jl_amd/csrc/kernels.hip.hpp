@@ -2664,16 +2664,17 @@ k_scale_offdiag(double* __restrict__ xp, int n, double s) {
 // A caller's start point into the solver's order and scale (proxsdp_hip_solve_from), entries k0 .. k1 - 1:
 //   out[k] = src[ord[k]] * (offdiag[k] ? sqrt2 : 1) / D[k]
 // the inverse of what the exit path applies (k_scale_offdiag by 1 / sqrt(2), k_scale_by D or E, the scatter to the
-// caller's order).  ord == NULL: src is in solver order already (the duals); offdiag == NULL: no sqrt(2) factor;
-// D == NULL: not equilibrated.  One multiply and one divide at the most per entry, each rounded on its own.
+// caller's order).  ord == NULL: src is in solver order already (the duals), entry k at src[k - s0] (s0 = p for a dual_in
+// vector read where the caller holds it); offdiag == NULL: no sqrt(2) factor; D == NULL: not equilibrated.  One multiply and
+// one divide at the most per entry, each rounded on its own.
 #pragma clang fp contract(off)
 __global__ void __launch_bounds__(TPB)
-k_start_gather(const double* __restrict__ src, const long long* __restrict__ ord,
+k_start_gather(const double* __restrict__ src, long long s0, const long long* __restrict__ ord,
                const unsigned char* __restrict__ offdiag, const double* __restrict__ D, double sqrt2,
                double* __restrict__ out, long long k0, long long k1) {
     const long long stride = (long long)gridDim.x * TPB;
     for (long long k = k0 + (long long)blockIdx.x * TPB + threadIdx.x; k < k1; k += stride) {
-        double v = src[ord ? ord[k] : k];
+        double v = src[ord ? ord[k] : k - s0];
         if (offdiag && offdiag[k]) v = v * sqrt2;
         if (D) v = v / D[k];
         out[k] = v;

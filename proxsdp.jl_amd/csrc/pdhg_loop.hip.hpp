@@ -407,6 +407,48 @@ inline void Solver::bump_rank(int idx) {
     }
 }
 
+// lambda_min of smat(dc_k) for the dual-cone block of PSD cone idx (side >= 2).  fill(tmp, negated) puts the packed block -- or
+// minus it -- into the device buffer tmp on the solver's stream: from a host vector (dual_feas_host) or by a kernel
+// (cache_solution_device).
+// psd_vec_to_square(v, a, cones, sqrt(2)): off-diagonals / sqrt(2), i.e. smat(dc).
+// The reference takes minimum(eigen!(...)) of the full spectrum (pdhg.jl:685, one
+// O(n^3) dsyevr inside SolveTimeSec); only lambda_min is used, so for Lanczos-sized
+// blocks it is computed as -lambda_max(-smat(dc)) with the projection's own Lanczos
+// (a few hundred mat-vecs), falling back to the dense eigensolver if that does not
+// converge.  This also keeps rocSOLVER's 3-5 s one-off code-object load out of
+// solves that never take the full_eig! path.
+template <typename Fill>
+inline double Solver::dual_block_min_eig(size_t idx, Fill&& fill) {
+    const BlockInfo& B = P.blocks[idx];
+    EigWork& W = eig[idx];
+    DevBuf<double> tmp(B.N);
+    double mn = 0.0;
+    bool have_mn = false;
+    if (B.n > opt.min_size_krylov_eigs && opt.eigsolver != 1 && W.cap >= 26 && krylovdim_fits(1)) {
+        fill(tmp.p, true);
+        const proxsdp_stats keep_st = W.lst;
+        const long long keep_mv = W.mv_iter;
+        const int keep_prev = W.prev_numiter, keep_num = W.numiter;
+        W.use_fop = false;
+        lanczos(W, tmp.p, 1);
+        if (W.converged && W.converged_eigs >= 1 && !W.vals.empty()) { mn = -W.vals[0]; have_mn = true; }
+        const long long mv = W.lst.lanczos_matvecs - keep_st.lanczos_matvecs;
+        W.lst = keep_st;                               // exit-path work is not a projection
+        st.exit_matvecs += mv;
+        W.mv_iter = keep_mv;
+        W.prev_numiter = keep_prev; W.numiter = keep_num;
+        PX_HIP(hipStreamSynchronize(stream));          // (the host vector behind fill may go now)
+    }
+    if (!have_mn) {
+        fill(tmp.p, false);
+        std::vector<double> D;
+        full_eig_values(W, tmp.p, dev::INV_SQRT2, false, D);
+        mn = D[0];
+        for (double v : D) mn = std::min(mn, v);
+    }
+    return mn;
+}
+
 // get_duals + dual_feas + cone_feas (pdhg.jl:678-732) on host vectors; the
 // dual-cone eigenvalues come from the device (rocSOLVER, values only).
 inline double Solver::dual_feas_host(const std::vector<double>& y, const std::vector<double>& cvec,
@@ -438,41 +480,12 @@ inline double Solver::dual_feas_host(const std::vector<double>& y, const std::ve
         if (B.n == 1) {
             sdp_viol = std::max(sdp_viol, -std::min(0.0, dc[B.off]));
         } else {
-            EigWork& W = eig[idx];
-            // psd_vec_to_square(v, a, cones, sqrt(2)): off-diagonals / sqrt(2), i.e. smat(dc).
-            // The reference takes minimum(eigen!(...)) of the full spectrum (pdhg.jl:685, one
-            // O(n^3) dsyevr inside SolveTimeSec); only lambda_min is used, so for Lanczos-sized
-            // blocks it is computed as -lambda_max(-smat(dc)) with the projection's own Lanczos
-            // (a few hundred mat-vecs), falling back to the dense eigensolver if that does not
-            // converge.  This also keeps rocSOLVER's 3-5 s one-off code-object load out of
-            // solves that never take the full_eig! path.
-            DevBuf<double> tmp(B.N);
-            double mn = 0.0;
-            bool have_mn = false;
-            if (B.n > opt.min_size_krylov_eigs && opt.eigsolver != 1 && W.cap >= 26 && krylovdim_fits(1)) {
-                std::vector<double> neg(dc.begin() + B.off, dc.begin() + B.off + B.N);
-                for (double& v : neg) v = -v;
-                tmp.upload(neg.data(), B.N, stream);
-                const proxsdp_stats keep_st = W.lst;
-                const long long keep_mv = W.mv_iter;
-                const int keep_prev = W.prev_numiter, keep_num = W.numiter;
-                W.use_fop = false;
-                lanczos(W, tmp.p, 1);
-                if (W.converged && W.converged_eigs >= 1 && !W.vals.empty()) { mn = -W.vals[0]; have_mn = true; }
-                const long long mv = W.lst.lanczos_matvecs - keep_st.lanczos_matvecs;
-                W.lst = keep_st;                               // exit-path work is not a projection
-                st.exit_matvecs += mv;
-                W.mv_iter = keep_mv;
-                W.prev_numiter = keep_prev; W.numiter = keep_num;
-                PX_HIP(hipStreamSynchronize(stream));          // `neg` goes out of scope
-            }
-            if (!have_mn) {
-                tmp.upload(dc.data() + B.off, B.N, stream);
-                std::vector<double> D;
-                full_eig_values(W, tmp.p, dev::INV_SQRT2, false, D);
-                mn = D[0];
-                for (double v : D) mn = std::min(mn, v);
-            }
+            std::vector<double> stage;                         // (outlives the upload: the helper synchronises)
+            const double mn = dual_block_min_eig(idx, [&](double* tmp, bool negated) {
+                stage.assign(dc.begin() + B.off, dc.begin() + B.off + B.N);
+                if (negated) for (double& v : stage) v = -v;
+                PX_HIP(hipMemcpyAsync(tmp, stage.data(), (size_t)B.N * sizeof(double), hipMemcpyHostToDevice, stream));
+            });
             sdp_viol = std::max(sdp_viol, -std::min(0.0, mn));
         }
     }
@@ -489,28 +502,50 @@ inline double Solver::dual_feas_host(const std::vector<double>& y, const std::ve
     return std::max({sdp_viol, ineq_viol, zero_viol});
 }
 
+// what a snapshot leaves beside its vectors: the scalar fields of the result, and the workspaces' bookkeeping
+inline void Solver::finish_snapshot(double dfeas) {
+    harvest_small_ranks();
+    long long fr = 0;
+    for (long long r : current_rank) fr += r;
+    if (sharded()) {                         // dual feasibility and rank over all shards
+        std::vector<double> sums = {(double)fr}, maxs = {dfeas};
+        reduce(sums, maxs);
+        fr = (long long)std::llround(sums[0]);
+        dfeas = maxs[0];
+    }
+    res.status = stop_reason;
+    merge_block_stats();
+    // (ADVICE r5: a caller who forces equilibration gets the reference's aliased -- not contractive -- scaling iteration by default: say so)
+    std::snprintf(res.status_string, sizeof(res.status_string), "%s%s%s", stop_reason_string.c_str(),
+                  st.dense_truncated_projections > 0 ? " [Krylov dimension > 255: dense eigensolver served those projections]" : "",
+                  (P.equilibrated && opt.equilibration_reference_aliasing) ? " [equilibration: the reference's aliased scaling, equilibration_reference_aliasing = 1]" : "");
+    res.primal_residual = equa_feasibility;
+    res.dual_residual = ineq_feasibility;
+    res.objval = h_pobj.at(iter);
+    res.dual_objval = h_dobj.at(iter);
+    res.gap = h_gap.at(iter);
+    res.iter = iter;
+    res.final_rank = (int32_t)fr;
+    res.primal_feasible_user_tol = h_feas.at(iter) <= opt.tol_feasibility;
+    res.dual_feasible_user_tol = dfeas <= opt.tol_feasibility_dual;
+    res.dual_feasibility = dfeas;
+    res.certificate_found = certificate_found;
+    res.result_count = 1;
+    res.time = now_s() - time0;
+    have_snapshot = true;
+    // x was rescaled IN PLACE above (the reference quirk, pdhg.jl:749-755).  When a certificate
+    // search continues from here, the operator-form factors F diag(Flam) F' still describe the
+    // UNscaled iterate: drop them so the next projection reads the (rescaled) packed buffer, as the
+    // fused residual and the dense / full-eig paths do.
+    for (EigWork& W : eig) { W.have_factors = false; W.xprev.sparse = false; W.ritz_ok = false; }
+}
+
 // cache_solution (pdhg.jl:745-787).  NB the reference rescales pair.x IN PLACE
 // (fix_diag_scaling on pair.x, :749); when a certificate search continues after
 // this snapshot the iterate stays rescaled -- reproduced here on the device.
 inline void Solver::cache_solution(const std::vector<double>& cvec) {
     double t0 = now_s();
-    const double inv = 1.0 / std::sqrt(2.0);
-    for (size_t idx = 0; idx < P.blocks.size(); ++idx) {
-        const BlockInfo& B = P.blocks[idx];
-        if (B.n < 2) continue;
-        const int nt = ceil_div(B.n, dev::TILE);
-        hipLaunchKernelGGL(dev::k_scale_offdiag, dim3(nt * (nt + 1) / 2), dim3(dev::TPB), 0, stream,
-                           xbuf[xc].p + B.off, B.n, inv);
-    }
-    if (P.equilibrated) {                                    // pair.x = D*pair.x; pair.y = E*pair.y (pdhg.jl:751-755)
-        if (Ddiag_d.n == 0) {
-            Ddiag_d.alloc(P.n); Ediag_d.alloc(std::max<int64_t>(P.Q, 1));
-            Ddiag_d.upload(P.Ddiag.data(), P.n, stream); Ediag_d.upload(P.Ediag.data(), P.Q, stream);
-        }
-        hipLaunchKernelGGL(dev::k_scale_by, dim3(grid_for(P.n)), dim3(dev::TPB), 0, stream, xbuf[xc].p, Ddiag_d.p, (long long)P.n);
-        hipLaunchKernelGGL(dev::k_scale_by, dim3(grid_for(std::max<int64_t>(P.Q, 1))), dim3(dev::TPB), 0, stream,
-                           ybuf[yc].p, Ediag_d.p, (long long)P.Q);
-    }
+    exit_rescale_iterate();                                  // (exit_device.hip.hpp: the two exit paths share it)
     std::vector<double> x(P.n), y(P.Q);
     xbuf[xc].download(x.data(), P.n, stream);
     ybuf[yc].download(y.data(), P.Q, stream);
@@ -533,61 +568,32 @@ inline void Solver::cache_solution(const std::vector<double>& cvec) {
         for (size_t k = 0; k < coup_rows.size(); ++k) slack[coup_rows[k]] = part_[k];
     }
     // the factors of this snapshot's PSD blocks, before the lambda_min Lanczos below reuses the blocks' workspaces
-    if (factors_out) extract_factors(x);
-    std::vector<double> deq, din, dcone;
-    double dfeas = dual_feas_host(y, cvec, &deq, &din, &dcone);
-    harvest_small_ranks();
-    long long fr = 0;
-    for (long long r : current_rank) fr += r;
-    if (sharded()) {                         // dual feasibility and rank over all shards
-        std::vector<double> sums = {(double)fr}, maxs = {dfeas};
-        reduce(sums, maxs);
-        fr = (long long)std::llround(sums[0]);
-        dfeas = maxs[0];
+    if (factors_out) {
+        std::vector<double> one_vals(P.blocks.size(), 0.0);
+        for (size_t idx = 0; idx < P.blocks.size(); ++idx) if (P.blocks[idx].n == 1) one_vals[idx] = x[P.blocks[idx].off];
+        extract_factors(one_vals);
     }
-    res.status = stop_reason;
-    merge_block_stats();
-    // (ADVICE r5: a caller who forces equilibration gets the reference's aliased -- not contractive -- scaling iteration by default: say so)
-    std::snprintf(res.status_string, sizeof(res.status_string), "%s%s%s", stop_reason_string.c_str(),
-                  st.dense_truncated_projections > 0 ? " [Krylov dimension > 255: dense eigensolver served those projections]" : "",
-                  (P.equilibrated && opt.equilibration_reference_aliasing) ? " [equilibration: the reference's aliased scaling, equilibration_reference_aliasing = 1]" : "");
+    std::vector<double> deq, din, dcone;
+    const double dfeas = dual_feas_host(y, cvec, &deq, &din, &dcone);
     if (res.primal)    for (int64_t i = 0; i < P.n; ++i) res.primal[i] = x[P.inv[i]];
     if (res.dual_cone) for (int64_t i = 0; i < P.n; ++i) res.dual_cone[i] = dcone[P.inv[i]];
     if (res.dual_eq)   for (int64_t i = 0; i < P.p; ++i) res.dual_eq[i] = deq[i];
     if (res.dual_in)   for (int64_t i = 0; i < P.m; ++i) res.dual_in[i] = din[i];
     if (res.slack_eq)  for (int64_t i = 0; i < P.p; ++i) res.slack_eq[i] = slack[i] - P.b_orig[i];
     if (res.slack_in)  for (int64_t i = 0; i < P.m; ++i) res.slack_in[i] = slack[P.p + i] - P.h_orig[i];
-    res.primal_residual = equa_feasibility;
-    res.dual_residual = ineq_feasibility;
-    res.objval = h_pobj.at(iter);
-    res.dual_objval = h_dobj.at(iter);
-    res.gap = h_gap.at(iter);
-    res.iter = iter;
-    res.final_rank = (int32_t)fr;
-    res.primal_feasible_user_tol = h_feas.at(iter) <= opt.tol_feasibility;
-    res.dual_feasible_user_tol = dfeas <= opt.tol_feasibility_dual;
-    res.dual_feasibility = dfeas;
-    res.certificate_found = certificate_found;
-    res.result_count = 1;
-    res.time = now_s() - time0;
-    have_snapshot = true;
-    // x was rescaled IN PLACE above (the reference quirk, pdhg.jl:749-755).  When a certificate
-    // search continues from here, the operator-form factors F diag(Flam) F' still describe the
-    // UNscaled iterate: drop them so the next projection reads the (rescaled) packed buffer, as the
-    // fused residual and the dense / full-eig paths do.
-    for (EigWork& W : eig) { W.have_factors = false; W.xprev.sparse = false; W.ritz_ok = false; }
+    finish_snapshot(dfeas);
     st.exit_time += now_s() - t0;
 }
 
 // The low-rank factors of the PSD blocks of the snapshot cache_solution is taking (proxsdp_hip_solve_factored): for cone k
 // the positive eigenpairs of the block exactly as it sits in xbuf[xc] -- plain entries in the caller's scale, what is
-// downloaded into res->primal (x is that download).  Where the block still IS the reconstruction of the last projection's
-// Ritz pairs (the operator form's factors F / Flam, or the pairs a converged Krylov projection left in Z / vals) those pairs
+// downloaded into res->primal (one_vals[k]: that entry of a 1x1 cone k, all the host needs of the iterate).
+// Where the block still IS the reconstruction of the last projection's Ritz pairs (the operator form's factors F / Flam, or the pairs a converged Krylov projection left in Z / vals) those pairs
 // are handed out: a gather and a download, no eigensolve.  Any other block of side >= 2 -- full_eig! engines, equilibrated
 // solves (the rescale by D is not a congruence the pairs survive), a snapshot taken before any projection -- gets one
 // dsyevd of the block, pairs with lambda > 0 kept.  Either way the cap[k] largest pairs go out, descending, and
 // k_factor_residual measures them against the block: resid reports what the pairs miss, truncation included.
-inline void Solver::extract_factors(const std::vector<double>& x) {
+inline void Solver::extract_factors(const std::vector<double>& one_vals) {
     proxsdp_psd_factors& F = *factors_out;
     for (size_t idx = 0; idx < P.blocks.size(); ++idx) {
         const BlockInfo& B = P.blocks[idx];
@@ -598,7 +604,7 @@ inline void Solver::extract_factors(const std::vector<double>& x) {
         F.resid[idx] = 0.0; F.xnorm[idx] = 0.0;
         if (cap <= 0) continue;                               // nothing wanted for this cone: nothing computed
         if (B.n == 1) {
-            const double xv = x[B.off];
+            const double xv = one_vals[idx];
             F.xnorm[idx] = std::fabs(xv);
             if (xv > 0.0) { vout[0] = 1.0; lout[0] = xv; F.rank[idx] = 1; F.rank_found[idx] = 1; }
             else F.resid[idx] = std::fabs(xv);
@@ -1066,7 +1072,13 @@ inline void Solver::apply_start() {
     }
     if (s.primal_step > 0.0) { primal_step = s.primal_step; primal_step_old = primal_step; dual_step = primal_step; }
     if (s.beta > 0.0) beta = s.beta;
-    if (!s.primal && !s.dual_eq && !s.dual_in && !any_fac) return;      // no point given: the cold vectors stay (x_old = 0)
+    // vectors the caller holds on the device (proxsdp_hip_solve_device): read where they are
+    const double* d_primal = start_dev ? start_dev->primal : nullptr;
+    const double* d_eq = start_dev ? start_dev->dual_eq : nullptr;
+    const double* d_in = start_dev ? start_dev->dual_in : nullptr;
+    if (start_dev) check_start_dev();
+    // no point given: the cold vectors stay (x_old = 0)
+    if (!s.primal && !s.dual_eq && !s.dual_in && !d_primal && !d_eq && !d_in && !any_fac) return;
     start_active = true;
     if (P.equilibrated && Ddiag_d.n == 0) {                              // (the exit path finds them uploaded)
         Ddiag_d.alloc(P.n); Ediag_d.alloc(std::max<int64_t>(P.Q, 1));
@@ -1074,25 +1086,27 @@ inline void Solver::apply_start() {
     }
     const double sqrt2 = std::sqrt(2.0);
     start_src_d.alloc((size_t)std::max<int64_t>(std::max(P.n, P.Q), 1));
-    auto gather = [&](const long long* ord, const unsigned char* od, const double* D, double* out, long long k0, long long k1) {
+    auto gather = [&](const double* src, long long s0, const long long* ord, const unsigned char* od, const double* D,
+                      double* out, long long k0, long long k1) {
         if (k1 <= k0) return;
         hipLaunchKernelGGL(dev::k_start_gather, dim3(grid_for(k1 - k0)), dim3(dev::TPB), 0, stream,
-                           (const double*)start_src_d.p, ord, od, D, sqrt2, out, k0, k1);
+                           src, s0, ord, od, D, sqrt2, out, k0, k1);
     };
-    if (s.primal) {                                      // every entry outside the factored cones
+    if (s.primal || d_primal) {                          // every entry outside the factored cones
         static_assert(sizeof(long long) == sizeof(int64_t), "variable order is uploaded as it is");
         start_ord_d.alloc(P.n);
         start_ord_d.upload(reinterpret_cast<const long long*>(P.ord.data()), P.n, stream);
         if (offdiag_d.n == 0) { offdiag_d.alloc(P.n); offdiag_d.upload(P.offdiag.data(), P.n, stream); }
-        start_src_d.upload(s.primal, P.n, stream);
+        const double* src = d_primal;
+        if (!src) { start_src_d.upload(s.primal, P.n, stream); src = start_src_d.p; }
         const double* Dd = P.equilibrated ? Ddiag_d.p : nullptr;
         long long k = 0;
         for (size_t idx = 0; idx < nb; ++idx) {
             if (given(idx) < 0) continue;
-            gather(start_ord_d.p, offdiag_d.p, Dd, xbuf[xc].p, k, P.blocks[idx].off);
+            gather(src, 0, start_ord_d.p, offdiag_d.p, Dd, xbuf[xc].p, k, P.blocks[idx].off);
             k = P.blocks[idx].off + P.blocks[idx].N;
         }
-        gather(start_ord_d.p, offdiag_d.p, Dd, xbuf[xc].p, k, P.n);
+        gather(src, 0, start_ord_d.p, offdiag_d.p, Dd, xbuf[xc].p, k, P.n);
         PX_HIP(hipGetLastError());
         PX_HIP(hipStreamSynchronize(stream));            // (start_src_d takes the duals next)
     }
@@ -1121,12 +1135,19 @@ inline void Solver::apply_start() {
         PX_HIP(hipGetLastError());
         PX_HIP(hipStreamSynchronize(stream));            // (the staging buffers serve the next cone)
     }
-    if (P.Q > 0 && (s.dual_eq || s.dual_in)) {           // y = [dual_eq; dual_in] / E, then M'y
+    if (P.Q > 0 && (s.dual_eq || s.dual_in || d_eq || d_in)) {   // y = [dual_eq; dual_in] / E, then M'y
+        // a half given on the host, or not at all, is staged in start_src_d; one on the device is read where it is
         if (s.dual_eq) start_src_d.upload(s.dual_eq, P.p, stream);
-        else if (P.p > 0) PX_HIP(hipMemsetAsync(start_src_d.p, 0, (size_t)P.p * sizeof(double), stream));
+        else if (!d_eq && P.p > 0) PX_HIP(hipMemsetAsync(start_src_d.p, 0, (size_t)P.p * sizeof(double), stream));
         if (s.dual_in) PX_HIP(hipMemcpyAsync(start_src_d.p + P.p, s.dual_in, (size_t)P.m * sizeof(double), hipMemcpyHostToDevice, stream));
-        else if (P.m > 0) PX_HIP(hipMemsetAsync(start_src_d.p + P.p, 0, (size_t)P.m * sizeof(double), stream));
-        gather(nullptr, nullptr, P.equilibrated ? Ediag_d.p : nullptr, ybuf[yc].p, 0, P.Q);
+        else if (!d_in && P.m > 0) PX_HIP(hipMemsetAsync(start_src_d.p + P.p, 0, (size_t)P.m * sizeof(double), stream));
+        const double* Ed = P.equilibrated ? Ediag_d.p : nullptr;
+        if (!d_eq && !d_in) {
+            gather(start_src_d.p, 0, nullptr, nullptr, Ed, ybuf[yc].p, 0, P.Q);
+        } else {
+            gather(d_eq ? d_eq : start_src_d.p, 0, nullptr, nullptr, Ed, ybuf[yc].p, 0, P.p);
+            gather(d_in ? d_in : start_src_d.p, d_in ? P.p : 0, nullptr, nullptr, Ed, ybuf[yc].p, P.p, P.Q);
+        }
         const BatchShape b = batch_shape();
         PX_HIP(hipMemcpyAsync(ycand_d.p, ybuf[yc].p, (size_t)P.Q * sizeof(double), hipMemcpyDeviceToDevice, stream));
         dev::TrialBatch tb{};                            // ONE plain candidate: M'y as computed (on the support, or every column)
@@ -1450,7 +1471,7 @@ inline void Solver::cert_dual_infeas() {
     bh_d.zero(stream);
     certificate_parameters();
 }
-inline void Solver::snapshot() { cache_solution(P.c_orig); }
+inline void Solver::snapshot() { if (device_exit) cache_solution_device(false); else cache_solution(P.c_orig); }
 
 // A stop rule fired: record its reason.  True: the loop stops.  False: it goes on -- with certificate search on and no
 // search running yet, the search for a certificate of `kind` starts here (data zeroed, limits raised, the point
@@ -1675,10 +1696,16 @@ inline void Solver::finish() {
     // ---- results (pdhg.jl:486-529)
     if (opt.certificate_search && certificate_search) {
         if (certificate_found) {
-            std::vector<double> cc(P.c_orig);
-            if (stop_reason == 6) std::fill(cc.begin(), cc.end(), 0.0);
-            cache_solution(cc);
+            if (device_exit) {
+                cache_solution_device(stop_reason == 6);
+            } else {
+                std::vector<double> cc(P.c_orig);
+                if (stop_reason == 6) std::fill(cc.begin(), cc.end(), 0.0);
+                cache_solution(cc);
+            }
         }
+    } else if (device_exit) {
+        cache_solution_device(false);
     } else {
         cache_solution(P.c_orig);
     }

@@ -544,7 +544,7 @@ public:
     DevBuf<double> fac_V, fac_lam, fac_part;
     void factor_residual(const double* xp, int n, const double* V, int ldv, const double* lam, int r,
                          double& resid2, double& xnorm2);
-    void extract_factors(const std::vector<double>& x);
+    void extract_factors(const std::vector<double>& one_vals);
 
     // hooks of the kernel-level test entry points (test_hooks.hip.hpp)
     void test_project(int idx, double* xp, int tr);
@@ -604,6 +604,15 @@ public:
     DevBuf<double> start_src_d, start_V, start_lam;
     void apply_start();
     void write_start_point();
+    // solution vectors on the device (proxsdp_hip_solve_device; exit_device.hip.hpp): the exit path as kernels, the caller's
+    // device buffers for the result (out_dev) and for the start point (start_dev); all off in every other entry
+    bool device_exit = false;
+    const proxsdp_device_vectors* start_dev = nullptr;
+    proxsdp_device_vectors* out_dev = nullptr;
+    void check_start_dev();
+    void cache_solution_device(bool zero_c);
+    void test_exit_vectors(const double* x, const double* y, bool zero_c, double* primal, double* dual_cone, double* dual_eq,
+                           double* dual_in, double* slack_eq, double* slack_in, double* viol, double* neg, int64_t neg_cap);
     int ada_count = 0;                    // pdhg.jl:306-332 (a local of chambolle_pock)
     void wait_event(hipEvent_t ev) {
         if (opt.host_wait_spin == 0) PX_HIP(hipEventSynchronize(ev));
@@ -763,6 +772,27 @@ private:
     double dual_feas_host(const std::vector<double>& y, const std::vector<double>& cvec,
                           std::vector<double>* dual_eq, std::vector<double>* dual_in, std::vector<double>* dual_cone);
     void cache_solution(const std::vector<double>& cvec);
+    template <typename Fill> double dual_block_min_eig(size_t idx, Fill&& fill);
+    void finish_snapshot(double dfeas);
+    // the device exit path's pieces and what they read (exit_device.hip.hpp)
+    struct ExitDev {
+        bool ready = false;
+        DevBuf<double> cval, rval;             // the caller's unscaled values in CSC / CSR storage order
+        DevBuf<double> c, zero, bh;            // c_orig; zeros (dense A with c = 0); [b_orig; h_orig]
+        DevBuf<long long> inv, one_off, soc_off;
+        DevBuf<int> soc_len;
+        std::vector<int> ones;                 // the 1x1 PSD cones, in cone order
+        DevBuf<double> slack, dc, base;        // M x - [b; h]; the dual cone; c + A'y of a dense A
+        DevBuf<double> prim, dcone, onev;      // staging where the caller gave no device buffer; the 1x1 cones' x
+        DevBuf<double> part, scal;
+        int feas_wg = 1;
+    } xd;
+    void exit_rescale_iterate();
+    void exit_device_setup();
+    void exit_form_vectors(bool zero_c);
+    void exit_cone_violations(double viol[4]);
+    void exit_write_vectors(const proxsdp_device_vectors* dv, double* primal, double* dual_cone, double* dual_eq,
+                            double* dual_in, double* slack_eq, double* slack_in);
     void certificate_parameters();
     void bump_rank(int idx);
     std::vector<double> b_host, h_host, c_host;   // current (possibly zeroed by a certificate search)

@@ -66,7 +66,7 @@ class Optimizer:
     # -- _optimize!
     def optimize(self, problem, eig_resid=None, trace_capacity=0, reduce=None, coupling=None, index_base=0,
                  nccl_comm=None, resume=None, capture_iteration=None, shards=None, device_ids=None, owners=None,
-                 soc_owners=None, free_owners=None, factors=False, start=None):
+                 soc_owners=None, free_owners=None, factors=False, start=None, device_out=False):
         """start: warm start (binding.solve: proxsdp_hip_solve_from) -- a dict (primal, dual_eq, dual_in, factors,
         target_rank, primal_step, beta; all in the units of a result) or a previous result of this optimizer; combines with
         factors=, not with shards=k, the state seam or a shard.
@@ -74,7 +74,10 @@ class Optimizer:
         (binding.solve: proxsdp_hip_solve_factored; `sol.psd_factors`, constraint_primal_psd_factor); not with shards=k.
         shards=k: the block-sharded solve from one call (binding.solve_sharded_inprocess) -- the library splits the model
         into k shards and runs them as host threads of this process, shard s on device_ids[s] (default: all on
-        options.device_id); the result is the whole model's, the per-shard stats are kept in `self.shard_stats`."""
+        options.device_id); the result is the whole model's, the per-shard stats are kept in `self.shard_stats`.
+        device_out=True: the result's vectors are float64 torch tensors on the solve's device (binding.solve:
+        proxsdp_hip_solve_device), and the getters return what the result holds; start= then also takes CUDA tensors or a
+        device result.  Not with shards=k, the state seam or a shard."""
         self.empty()
         self.problem = problem
         self.shard_stats = None
@@ -85,13 +88,16 @@ class Optimizer:
                 raise ValueError("shards=...: the block-sharded solve does not return factors")
             if start is not None:
                 raise ValueError("shards=...: the block-sharded solve has no warm start")
+            if device_out:
+                raise ValueError("shards=...: the block-sharded solve returns host arrays")
             sol, self.shard_stats = binding.solve_sharded_inprocess(
                 problem, shards, device_ids=device_ids, owners=owners, soc_owners=soc_owners, free_owners=free_owners,
                 options=self.options, trace_capacity=trace_capacity, eig_resid=eig_resid, index_base=index_base)
         else:
             sol = binding.solve(problem, self.options, eig_resid=eig_resid, trace_capacity=trace_capacity,
                                 reduce=reduce, coupling=coupling, index_base=index_base, nccl_comm=nccl_comm,
-                                resume=resume, capture_iteration=capture_iteration, factors=factors, start=start)
+                                resume=resume, capture_iteration=capture_iteration, factors=factors, start=start,
+                                device_out=device_out)
         sign = -1.0 if problem.max_sense else 1.0          # :336-337
         sol.objval = sign * sol.objval + problem.objective_constant
         sol.dual_objval = sign * sol.dual_objval + problem.objective_constant
