@@ -69,7 +69,11 @@ extern "C" {
  * later: proxsdp_hip_solve_from (warm start from a previous solution's primal / duals / factors) with the new struct
  * proxsdp_start and the test entry proxsdp_hip_start_point: functions and one new struct, the version stays;
  * later: the test entries proxsdp_hip_reconstruct_fused, proxsdp_hip_rotate and proxsdp_hip_tail_copy with their own structs:
- * functions and new structs, no existing struct changed: the version stays */
+ * functions and new structs, no existing struct changed: the version stays;
+ * later: the model handle (proxsdp_hip_model_create / _update / _solve / _info / _destroy: a model that stays set up on the
+ * device between solves) with the new structs proxsdp_model_data, proxsdp_model_info and proxsdp_model_dump and the test
+ * entries proxsdp_hip_model_dump, proxsdp_hip_model_norm2 and proxsdp_host_model_prepare: functions and new structs, no
+ * existing struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -764,6 +768,97 @@ typedef struct proxsdp_device_vectors {
 int  proxsdp_hip_solve_device(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
                               const proxsdp_start* start /* may be NULL */, const proxsdp_device_vectors* start_dev /* may be NULL */,
                               proxsdp_psd_factors* fac /* may be NULL */, proxsdp_device_vectors* out_dev /* may be NULL */);
+/* ------------------------------------------- a model that stays on the device between solves: handle, updates, re-solve
+ * No call of the reference stands behind this section: ProxSDP rebuilds AffineSets, ConicSets, the operator and every
+ * workspace in each optimize! (/root/reference/src/MOI_wrapper.jl:220-342).  A handle does that work ONCE:
+ *   create   everything proxsdp_hip_solve_device does before its first step size -- validation, variable order, scaling, the
+ *            operator in both orientations, block classification, workspaces, support set, ELL structures, candidates, the
+ *            device exit path's arrays -- and copies what it needs: no pointer of `prob` (eig_resid included) is used after
+ *            it returns.  Every argument check of proxsdp_hip_solve applies, with the same codes and texts.  Equilibration
+ *            and approx_norm = 0 are served as proxsdp_hip_solve serves them.  PROXSDP_E_UNSUPP, decided on the host before
+ *            any device call: prob is a shard of a block-sharded solve; M_dense != NULL (the matrix is borrowed, a handle
+ *            would outlive the loan); options.rocsolver_warmup != 0.
+ *   solve    proxsdp_hip_solve_device on the model's current data, BIT FOR BIT -- iterates, iteration and trial counts,
+ *            trace, res, factors, the six vectors, every counter of stats -- on the first solve of a handle and on every later
+ *            one, whatever ran on the handle before.  Only the clocks differ (res->time, trace column 12, the *_time, t_* and
+ *            *_ms members of stats): res->time and options.time_limit count from the entry into proxsdp_hip_model_solve,
+ *            stats.init_time is what this solve spent before iteration 1 (the reset and the start path).  start, start_dev,
+ *            fac and out_dev are checked as proxsdp_hip_solve_device checks them, against the model's dimensions and cones.
+ *            run_opt = NULL: the options of create.  Otherwise every field must equal create's except time_limit, max_iter,
+ *            log_verbose, log_freq, warn_on_limit and trace_capacity, which shape nothing in the set-up; a difference in any
+ *            other field (the tolerances included: small_block_batch and full_eig_sign read them in auto mode) returns
+ *            PROXSDP_E_INVALID and names the field.  A solve that fails -- a non-finite device start (PROXSDP_E_INVALID
+ *            before iteration 1), an error out of the loop -- or stops at its time limit leaves the handle usable: the next
+ *            solve is again the fresh solve bit for bit.  The block workers and the merge helpers are started per solve and
+ *            joined at its end: a handle holds no thread between calls.
+ *   update   replaces data of the same shape (proxsdp_model_data): c, b, h in the caller's order, A_nzval / G_nzval in the
+ *            storage order create() was given; the sparsity pattern stays; a NULL member is unchanged.  on_device = 0: host
+ *            pointers; 1: DEVICE pointers on the model's device, borrowed and trusted as proxsdp_device_vectors are (finish
+ *            your own work on them before the call; the call returns after its reads have completed).
+ *            PROXSDP_E_INVALID on the host: a NULL handle, a wrong struct_size, every pointer NULL.  Non-finite values are
+ *            refused (PROXSDP_E_INVALID) before anything is written -- host arrays by a host loop, device arrays by a
+ *            reduction on the device -- and the model keeps its previous data.  PROXSDP_E_UNSUPP: any update of an
+ *            equilibrated model (E and D depend on the values); A_nzval / G_nzval with approx_norm = 0 (sigma_max depends on
+ *            them).  The four scalars that feed the step size follow the data: ||b||, ||h||, ||c||, ||M||_F.
+ *              host pointers    the host recomputes them in the order prepare() uses (the norms over the caller's arrays, the
+ *                               Frobenius norm over the scaled values in reordered CSC order): a solve after a host update
+ *                               EQUALS a fresh solve of the updated problem bit for bit.
+ *              device pointers  they come from a device reduction in a fixed order (one partial per chunk of 4096 entries,
+ *                               the partials added in chunk order by one thread): reproducible from run to run and
+ *                               independent of the launch width, but NOT guaranteed equal to the host's last bit.
+ *            An update of c may change which entries are zero and with them the support set {column non-empty or c_i != 0}
+ *            of the support-aware vector path: the update then rebuilds what the set-up built from it (the auto rule may
+ *            switch that path on or off, as it would in a fresh solve) and counts it in proxsdp_model_info.support_rebuilds.
+ *   info     dimensions, counters, use_support, device_bytes (the handle's live device allocations), setup_time (seconds
+ *            create took).
+ *   destroy  frees everything; NULL is fine.
+ * One handle serves one caller at a time. */
+typedef struct proxsdp_model proxsdp_model;               /* opaque */
+typedef struct proxsdp_model_data {
+    int64_t struct_size;     /* = sizeof(proxsdp_model_data) */
+    int32_t on_device;       /* 0: host pointers; 1: DEVICE pointers on the model's device, borrowed and trusted */
+    int32_t reserved;
+    const double* c;         /* n, caller's variable order, or NULL = unchanged */
+    const double* b;         /* p */
+    const double* h;         /* m */
+    const double* A_nzval;   /* nnz(A) in the storage order create() was given; the pattern stays */
+    const double* G_nzval;   /* nnz(G) */
+} proxsdp_model_data;
+typedef struct proxsdp_model_info {
+    int64_t struct_size;     /* = sizeof(proxsdp_model_info) */
+    int64_t n, p, m, n_psd, nnz;
+    int32_t device_id;
+    int32_t use_support;     /* 1: the support-aware vector path is on */
+    int64_t solves, updates, support_rebuilds;
+    int64_t device_bytes;
+    double setup_time;
+} proxsdp_model_info;
+int  proxsdp_hip_model_create(const proxsdp_problem* prob, const proxsdp_options* opt /* NULL: defaults */, proxsdp_model** out);
+int  proxsdp_hip_model_update(proxsdp_model* mdl, const proxsdp_model_data* upd);
+int  proxsdp_hip_model_solve(proxsdp_model* mdl, const proxsdp_options* run_opt /* may be NULL */, proxsdp_result* res,
+                             const proxsdp_start* start, const proxsdp_device_vectors* start_dev,
+                             proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev);   /* the last four may be NULL */
+int  proxsdp_hip_model_info(const proxsdp_model* mdl, proxsdp_model_info* info);
+int  proxsdp_hip_model_destroy(proxsdp_model* mdl);       /* NULL is fine */
+/* test entry: the model's current internal data, downloaded into caller-allocated host arrays.  The sizes (n, Q = p + m, nnz,
+ * ns = length of the support list, 0 when the support path is off) and the four norms (||b||, ||h||, ||c||, ||M||_F) are always
+ * written; an array is written when its pointer is not NULL (call once with every pointer NULL for the sizes, allocate, call
+ * again). */
+typedef struct proxsdp_model_dump {
+    int64_t struct_size;     /* = sizeof(proxsdp_model_dump) */
+    int64_t n, Q, nnz, ns;                          /* out */
+    double* csc_val; double* csr_val;               /* nnz each: the loop's scaled values, CSC / CSR */
+    double* csc_val_orig; double* csr_val_orig;     /* nnz each: the exit path's unscaled values */
+    double* c; double* c_orig;                      /* n each: c in solver order and scale; in solver order, unscaled */
+    double* bh;                                     /* Q: [b; h] */
+    int32_t* support; double* cS;                   /* ns each: the support list, c on it */
+    double norms[4];                                /* out */
+} proxsdp_model_dump;
+int  proxsdp_hip_model_dump(proxsdp_model* mdl, proxsdp_model_dump* out);
+/* test entry: ||v||_2 of n host doubles by the device route's reduction (k_model_norm2) with `grid` workgroups (<= 0: the
+ * width an update uses).  The result does not depend on grid. */
+int  proxsdp_hip_model_norm2(const double* v, int64_t n, int32_t grid, double* out);
+
 /* test entry: the device exit path alone (Solver::cache_solution_device's launches) on host data.  x (n) is an internal iterate
  * in the solver's order and scale as the loop leaves it, y (p + m) the internal dual; zero_c != 0 takes c = 0 (the certificate
  * snapshot).  Out, on the host: the six vectors in the caller's order (any may be NULL); viol[4] = the violations of the
@@ -1124,6 +1219,13 @@ int proxsdp_host_start_vector(int64_t n, int64_t seed, int32_t init, double* out
  * inverse permutation and the scaled c; for layout tests */
 int proxsdp_host_preprocess(const proxsdp_problem* prob, int64_t* order, int64_t* var_ordering,
                             double* c_scaled, double* frobenius_norm_M);
+/* prepare() as proxsdp_hip_model_create runs it, with the position maps it records, and no device: the dump's sizes, norms
+ * and arrays as proxsdp_hip_model_dump gives them for a fresh model without equilibration (support = every position whose
+ * column is non-empty or whose c is not zero, whatever the auto rule of the support path would decide; ns its length), and
+ * for entry q of [A.nzval; G.nzval] its position in csc_val (csc_pos[q]) and in csr_val (csr_pos[q]); nnz_A = entries of A.
+ * An array is written when its pointer is not NULL. */
+int proxsdp_host_model_prepare(const proxsdp_problem* prob, proxsdp_model_dump* out, int64_t* nnz_A, int32_t* csc_pos,
+                               int32_t* csr_pos);
 /* equilibrate! (equilibration.jl) from the row sums alone: rowsums[r] = sum_j M[r,j]^2 of a Q x n matrix in, E (Q) and
  * the scalar d (D = d I: the reference replaces v by its mean in every iteration) out -- the iteration a dense A takes,
  * where M is only streamed.  Uses opt's equilibration_iters / _lb / _ub / _reference_aliasing (NULL: the defaults). */

@@ -203,6 +203,31 @@ class DeviceVectors(C.Structure):
                 ("dual_in", pf64), ("slack_in", pf64)]
 
 
+class ModelData(C.Structure):
+    """proxsdp_model_data (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("on_device", i32), ("reserved", i32),
+                ("c", pf64), ("b", pf64), ("h", pf64), ("A_nzval", pf64), ("G_nzval", pf64)]
+
+
+class ModelInfo(C.Structure):
+    """proxsdp_model_info (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("n", i64), ("p", i64), ("m", i64), ("n_psd", i64), ("nnz", i64),
+                ("device_id", i32), ("use_support", i32), ("solves", i64), ("updates", i64), ("support_rebuilds", i64),
+                ("device_bytes", i64), ("setup_time", f64)]
+
+
+class ModelDump(C.Structure):
+    """proxsdp_model_dump (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("n", i64), ("Q", i64), ("nnz", i64), ("ns", i64),
+                ("csc_val", pf64), ("csr_val", pf64), ("csc_val_orig", pf64), ("csr_val_orig", pf64),
+                ("c", pf64), ("c_orig", pf64), ("bh", pf64), ("support", C.POINTER(i32)), ("cS", pf64),
+                ("norms", f64 * 4)]
+
+
+MODEL_DUMP_ARRAYS = (("csc_val", "nnz"), ("csr_val", "nnz"), ("csc_val_orig", "nnz"), ("csr_val_orig", "nnz"),
+                     ("c", "n"), ("c_orig", "n"), ("bh", "Q"), ("support", "ns"), ("cS", "ns"))
+MODEL_NORM_NAMES = ("norm_b", "norm_h", "norm_c", "frob")
+
 FACTOR_NONE, FACTOR_RITZ, FACTOR_EIG = 0, 1, 2
 FACTOR_SOURCE_NAMES = {FACTOR_NONE: "NONE", FACTOR_RITZ: "RITZ", FACTOR_EIG: "EIG"}
 
@@ -256,6 +281,15 @@ def lib():
     L.proxsdp_hip_solve_device.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Result), C.POINTER(Start),
                                            C.POINTER(DeviceVectors), C.POINTER(PsdFactors), C.POINTER(DeviceVectors)]
     L.proxsdp_hip_exit_vectors.argtypes = [C.POINTER(Problem), C.POINTER(Options), pf64, pf64, i32] + [pf64] * 8 + [i64]
+    L.proxsdp_hip_model_create.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(C.c_void_p)]
+    L.proxsdp_hip_model_update.argtypes = [C.c_void_p, C.POINTER(ModelData)]
+    L.proxsdp_hip_model_solve.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(Result), C.POINTER(Start),
+                                          C.POINTER(DeviceVectors), C.POINTER(PsdFactors), C.POINTER(DeviceVectors)]
+    L.proxsdp_hip_model_info.argtypes = [C.c_void_p, C.POINTER(ModelInfo)]
+    L.proxsdp_hip_model_destroy.argtypes = [C.c_void_p]
+    L.proxsdp_hip_model_dump.argtypes = [C.c_void_p, C.POINTER(ModelDump)]
+    L.proxsdp_hip_model_norm2.argtypes = [pf64, i64, i32, pf64]
+    L.proxsdp_host_model_prepare.argtypes = [C.POINTER(Problem), C.POINTER(ModelDump), pi64, C.POINTER(i32), C.POINTER(i32)]
     L.proxsdp_hip_factor_residual.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64]
     L.proxsdp_hip_factor_residual_kernel.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64, i32, pf64]
     L.proxsdp_hip_psd_project.argtypes = [pf64, i64, i32, i32, C.POINTER(Options), pf64, pf64,
@@ -869,6 +903,203 @@ def _solve_device(prob, options, eig_resid, trace_capacity, index_base, factors,
     if F is not None:
         res.psd_factors = _factors_list(sides, farr)
     return res
+
+
+def _dump_arrays(D, fill):
+    """the arrays of a proxsdp_model_dump whose sizes are known, allocated and bound (fill(D) is then called again)"""
+    sizes = dict(n=int(D.n), Q=int(D.Q), nnz=int(D.nnz), ns=int(D.ns))
+    arr = {}
+    for name, sz in MODEL_DUMP_ARRAYS:
+        a = np.zeros(max(sizes[sz], 1), dtype=np.int32 if name == "support" else np.float64)
+        arr[name] = a
+        setattr(D, name, a.ctypes.data_as(C.POINTER(i32)) if name == "support" else _p(a))
+    fill(D)
+    out = {name: arr[name][:sizes[sz]].copy() for name, sz in MODEL_DUMP_ARRAYS}
+    out.update(sizes)
+    out.update({k: float(D.norms[q]) for q, k in enumerate(MODEL_NORM_NAMES)})
+    return out
+
+
+def host_model_prepare(prob, index_base=0):
+    """proxsdp_host_model_prepare: what a fresh Model of `prob` holds, computed on the host (no device), and the position maps:
+    the dump's dictionary plus nnz_A, csc_pos, csr_pos (entry q of [A.data; G.data] in sorted CSC storage)."""
+    L = lib()
+    M = _Marshalled(prob, None, index_base)
+    D = ModelDump()
+    D.struct_size = C.sizeof(ModelDump)
+    nnz_A = i64(0)
+    _check(L.proxsdp_host_model_prepare(C.byref(M.P), C.byref(D), C.byref(nnz_A), None, None))
+    cpos, rpos = np.zeros(max(int(D.nnz), 1), dtype=np.int32), np.zeros(max(int(D.nnz), 1), dtype=np.int32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(i32))
+    out = _dump_arrays(D, lambda d: _check(L.proxsdp_host_model_prepare(C.byref(M.P), C.byref(d), C.byref(nnz_A), ip(cpos), ip(rpos))))
+    out.update(nnz_A=int(nnz_A.value), csc_pos=cpos[:out["nnz"]].copy(), csr_pos=rpos[:out["nnz"]].copy())
+    return out
+
+
+def model_norm2(v, grid=0):
+    """proxsdp_hip_model_norm2: ||v||_2 by the reduction a device-route Model.update uses, with `grid` workgroups"""
+    v = _f(v).ravel()
+    out = f64()
+    _check(lib().proxsdp_hip_model_norm2(_p(v if len(v) else np.zeros(1)), len(v), int(grid), C.byref(out)))
+    return out.value
+
+
+class Model:
+    """A model that stays set up on the device between solves (proxsdp_hip_model_*, include/proxsdp_hip.h).
+
+        with Model(prob, options) as mdl:
+            r0 = mdl.solve(factors=True, device_out=True)
+            mdl.update(c=new_c)                      # same shape, new numbers
+            r1 = mdl.solve(start=r0, factors=True, device_out=True)
+
+    The set-up of solve() -- validation, ordering, scaling, the operator, the workspaces -- runs once, in the constructor;
+    solve() is solve(prob, options, ..., device_out=...) on the model's current data bit for bit (only the clocks differ).
+    The ctypes problem is built once, here; nothing of `prob` is referenced afterwards."""
+
+    def __init__(self, prob, options=None, eig_resid=None, index_base=0):
+        L = lib()
+        o = options if options is not None else default_options()
+        self._options = Options.from_buffer_copy(o)
+        M = _Marshalled(prob, eig_resid, index_base)
+        self.n, self.p, self.m = int(M.P.n), int(M.P.p), int(M.P.m)
+        self._sides = psd_sides(prob)
+        self._nnz = (int(sp.csc_matrix(prob.A).nnz), int(sp.csc_matrix(prob.G).nnz))
+        self._h = C.c_void_p()
+        _check(L.proxsdp_hip_model_create(C.byref(M.P), C.byref(self._options), C.byref(self._h)))
+
+    # ---- lifetime
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _check(lib().proxsdp_hip_model_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the model is closed")
+        return self._h
+
+    # ---- data
+    def update(self, c=None, b=None, h=None, A_values=None, G_values=None):
+        """Replace data of the same shape: c (n), b (p), h (m) in the caller's order; A_values / G_values = the stored entries
+        of A / G in sorted CSC order (scipy's .data after sort_indices), or a sparse matrix with the pattern the model was
+        built with.  NumPy arrays go the host route, CUDA float64 tensors the device route (proxsdp_model_data.on_device);
+        mixing the two in one call is a ValueError."""
+        given = dict(c=(c, self.n), b=(b, self.p), h=(h, self.m), A_nzval=(A_values, self._nnz[0]),
+                     G_nzval=(G_values, self._nnz[1]))
+        given = {k: v for k, v in given.items() if v[0] is not None}
+        on_dev = [_is_tensor(v) and v.is_cuda for v, _ in given.values()]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("Model.update: host arrays and CUDA tensors cannot be mixed in one call")
+        D = ModelData()
+        D.struct_size = C.sizeof(ModelData)
+        keep = []
+        if given and all(on_dev):
+            import torch
+            dev_id = int(self._options.device_id)
+            D.on_device = 1
+            for k, (v, ln) in given.items():
+                setattr(D, k, _device_ptr(v, ln, dev_id, k))
+            keep = [v for v, _ in given.values()]
+            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
+        else:
+            for k, (v, ln) in given.items():
+                if _is_tensor(v):
+                    v = v.numpy()
+                if sp.issparse(v):
+                    v = sp.csc_matrix(v, dtype=np.float64)
+                    v.sort_indices()
+                    v = v.data
+                a = _f(v).ravel()
+                if len(a) != ln:
+                    raise ValueError(f"Model.update: {k} must have {ln} entries")
+                keep.append(a if len(a) else np.zeros(1))
+                setattr(D, k, _p(keep[-1]))
+        _check(lib().proxsdp_hip_model_update(self._handle(), C.byref(D)))
+        del keep
+
+    # ---- solve
+    def solve(self, start=None, factors=False, primal=True, device_out=False, trace_capacity=0, time_limit=None,
+              max_iter=None):
+        """proxsdp_hip_model_solve: the SolveResult solve(prob, options, start=..., factors=..., primal=..., device_out=...)
+        returns for the model's current data.  trace_capacity, time_limit and max_iter override the model's options for this
+        solve (they shape nothing in the set-up)."""
+        L = lib()
+        o = Options.from_buffer_copy(self._options)
+        if trace_capacity:
+            o.trace_capacity = int(trace_capacity)
+        if time_limit is not None:
+            o.time_limit = float(time_limit)
+        if max_iter is not None:
+            o.max_iter = int(max_iter)
+        n, p, m = self.n, self.p, self.m
+        dev_id = int(o.device_id)
+        lens = (n, n, p, m, p, m)
+        names = ("primal", "dual_cone", "dual_eq", "dual_in", "slack_eq", "slack_in")
+        trace = np.zeros((max(o.trace_capacity, 1), TRACE_COLS))
+        R = Result()
+        R.trace = _p(trace)
+        out = None
+        use_torch = device_out or _start_on_device(start)
+        if use_torch:
+            import torch
+        if device_out:
+            tens = [torch.empty(k, dtype=torch.float64, device=f"cuda:{dev_id}") for k in lens]
+            if not primal:
+                tens[0] = None
+            out = _device_vectors(dev_id, **{nm: (t, k) for nm, t, k in zip(names, tens, lens)})
+            arrays = tens
+        else:
+            host = [np.zeros(max(k, 1)) for k in lens]
+            R.primal, R.dual_cone, R.dual_eq, R.dual_in, R.slack_eq, R.slack_in = [_p(a) for a in host]
+            if not primal:
+                R.primal = None
+            arrays = [a[:k] for a, k in zip(host, lens)]
+            if not primal:
+                arrays[0] = None
+        st = sd = None
+        if start is not None:
+            hstart, sd, keep_dev = _split_device_start(start, n, p, m, dev_id)
+            st, sarr = _start_struct(n, p, m, self._sides, hstart)
+        F = None
+        if factors is not False and factors is not None:
+            F, farr = _factors_struct(self._sides, factors)
+        if use_torch:
+            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
+        _check(L.proxsdp_hip_model_solve(self._handle(), C.byref(o), C.byref(R), C.byref(st) if st is not None else None,
+                                         C.byref(sd) if sd is not None else None, C.byref(F) if F is not None else None,
+                                         C.byref(out) if out is not None else None))
+        res = SolveResult(R, n, p, m, arrays, trace)
+        if F is not None:
+            res.psd_factors = _factors_list(self._sides, farr)
+        return res
+
+    # ---- what it holds
+    def info(self):
+        I = ModelInfo()
+        I.struct_size = C.sizeof(ModelInfo)
+        _check(lib().proxsdp_hip_model_info(self._handle(), C.byref(I)))
+        return {k: getattr(I, k) for k, _ in ModelInfo._fields_ if k != "struct_size"}
+
+    def dump(self):
+        """proxsdp_hip_model_dump: the model's internal data as a dictionary (test entry)"""
+        L = lib()
+        D = ModelDump()
+        D.struct_size = C.sizeof(ModelDump)
+        _check(L.proxsdp_hip_model_dump(self._handle(), C.byref(D)))
+        return _dump_arrays(D, lambda d: _check(L.proxsdp_hip_model_dump(self._handle(), C.byref(d))))
 
 
 def exit_vectors(prob, x, y, zero_c=False, options=None, index_base=0):

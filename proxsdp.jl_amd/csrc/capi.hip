@@ -13,6 +13,7 @@
 #include "exit_device.hip.hpp"
 #include "test_hooks.hip.hpp"
 #include "shard_split.hpp"
+#include "model.hip.hpp"
 
 namespace {
 thread_local std::string g_last_error;
@@ -334,6 +335,132 @@ int proxsdp_hip_solve_device(const proxsdp_problem* prob, const proxsdp_options*
     });
     if (rc != 0) return rc;
     return solve_impl(prob, opt, res, nullptr, nullptr, fac, (!start && start_dev) ? &none : start, true, start_dev, out_dev);
+}
+
+// ---- a model that stays set up on the device (model.hip.hpp): what is decided on the host is decided here, before a device call
+static bool is_shard(const proxsdp_problem* prob) {
+    return prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0;
+}
+
+int proxsdp_hip_model_create(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_model** out) {
+    return guarded([&]() -> int {
+        if (!prob || !out) throw std::invalid_argument("NULL problem or handle");
+        *out = nullptr;
+        const proxsdp_options o = Engine::fix(opt);
+        if (is_shard(prob)) throw std::domain_error("proxsdp_hip_model_create does not serve a shard of a block-sharded solve");
+        if (prob->M_dense != nullptr)
+            throw std::domain_error("proxsdp_hip_model_create does not serve M_dense: the matrix is borrowed, a handle would outlive the loan");
+        if (o.rocsolver_warmup != 0) throw std::domain_error("proxsdp_hip_model_create does not serve rocsolver_warmup");
+        *out = new proxsdp_model(*prob, o);
+        return 0;
+    });
+}
+
+int proxsdp_hip_model_destroy(proxsdp_model* mdl) {
+    return guarded([&]() -> int {
+        if (!mdl) return 0;
+        (void)hipSetDevice(mdl->opt0.device_id);
+        mdl->drain();
+        delete mdl;
+        return 0;
+    });
+}
+
+int proxsdp_hip_model_info(const proxsdp_model* mdl, proxsdp_model_info* info) {
+    return guarded([&]() -> int {
+        if (!info) throw std::invalid_argument("NULL info");
+        if (info->struct_size != (int64_t)sizeof(proxsdp_model_info)) throw std::invalid_argument("proxsdp_model_info.struct_size mismatch");
+        if (!mdl) throw std::invalid_argument("NULL handle");
+        mdl->info(*info);
+        return 0;
+    });
+}
+
+int proxsdp_hip_model_dump(proxsdp_model* mdl, proxsdp_model_dump* out) {
+    return guarded([&]() -> int {
+        if (!out) throw std::invalid_argument("NULL dump");
+        if (out->struct_size != (int64_t)sizeof(proxsdp_model_dump)) throw std::invalid_argument("proxsdp_model_dump.struct_size mismatch");
+        if (!mdl) throw std::invalid_argument("NULL handle");
+        mdl->dump(*out);
+        return 0;
+    });
+}
+
+int proxsdp_hip_model_update(proxsdp_model* mdl, const proxsdp_model_data* upd) {
+    return guarded([&]() -> int {
+        if (!upd) throw std::invalid_argument("NULL data");
+        if (upd->struct_size != (int64_t)sizeof(proxsdp_model_data)) throw std::invalid_argument("proxsdp_model_data.struct_size mismatch");
+        if (upd->on_device != 0 && upd->on_device != 1) throw std::invalid_argument("proxsdp_model_data.on_device must be 0 or 1");
+        if (!upd->c && !upd->b && !upd->h && !upd->A_nzval && !upd->G_nzval) throw std::invalid_argument("proxsdp_model_data: every pointer is NULL");
+        if (!mdl) throw std::invalid_argument("NULL handle");
+        const proxsdp::Prep& P = mdl->S->P;
+        if (P.equilibrated) throw std::domain_error("proxsdp_hip_model_update does not serve an equilibrated model: E and D depend on the values");
+        if ((upd->A_nzval || upd->G_nzval) && !mdl->opt0.approx_norm)
+            throw std::domain_error("proxsdp_hip_model_update does not serve A_nzval / G_nzval with approx_norm = 0: sigma_max depends on them");
+        if (upd->on_device == 0) {
+            const double* src[5] = {upd->c, upd->b, upd->h, upd->A_nzval, upd->G_nzval};
+            const int64_t len[5] = {P.n, P.p, P.m, P.nnzA, P.nnz - P.nnzA};
+            const char* name[5] = {"c", "b", "h", "A_nzval", "G_nzval"};
+            for (int q = 0; q < 5; ++q)
+                for (int64_t i = 0; src[q] && i < len[q]; ++i)
+                    if (!std::isfinite(src[q][i])) throw std::invalid_argument(std::string("proxsdp_model_data: non-finite entry in ") + name[q]);
+        }
+        mdl->update(*upd);
+        return 0;
+    });
+}
+
+int proxsdp_hip_model_solve(proxsdp_model* mdl, const proxsdp_options* run_opt, proxsdp_result* res,
+                            const proxsdp_start* start, const proxsdp_device_vectors* start_dev,
+                            proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev) {
+    const double t_entry = proxsdp::now_s();
+    return guarded([&]() -> int {
+        if (!mdl || !res) throw std::invalid_argument("NULL handle or result");
+        proxsdp_options run;
+        if (run_opt) {
+            run = Engine::fix(run_opt);
+            // every option but the ones that shape nothing in the set-up must be create's
+            static const char* const free_fields[] = {"time_limit", "max_iter", "log_verbose", "log_freq", "warn_on_limit", "trace_capacity"};
+            for (const proxsdp::OptEntry& e : proxsdp::option_table()) {
+                bool is_free = false;
+                for (const char* f : free_fields) is_free = is_free || std::strcmp(f, e.name) == 0;
+                if (is_free) continue;
+                const size_t w = e.type == proxsdp::OT_I32 ? 4 : 8;
+                if (std::memcmp(reinterpret_cast<const char*>(&run) + e.offset, reinterpret_cast<const char*>(&mdl->opt0) + e.offset, w) != 0)
+                    throw std::invalid_argument(std::string("proxsdp_hip_model_solve: run_opt.") + e.name +
+                                                " differs from the options of proxsdp_hip_model_create");
+            }
+        }
+        const proxsdp_problem* shape = &mdl->shape;
+        check_start_arg(shape, start);
+        if (fac) check_factors_arg(shape, res, fac);
+        check_device_vectors(start_dev, mdl->opt0.device_id, "start");
+        check_device_vectors(out_dev, mdl->opt0.device_id, "out");
+        if (start_dev) {
+            if (start_dev->dual_cone || start_dev->slack_eq || start_dev->slack_in)
+                throw std::invalid_argument("proxsdp_device_vectors (start): dual_cone, slack_eq and slack_in must be NULL");
+            if (start && ((start->primal && start_dev->primal) || (start->dual_eq && start_dev->dual_eq) ||
+                          (start->dual_in && start_dev->dual_in)))
+                throw std::invalid_argument("a start vector is given both on the host (proxsdp_start) and on the device");
+        }
+        res->status = PROXSDP_STATUS_NOT_CALLED;
+        res->trace_rows = 0; res->result_count = 0; res->certificate_found = 0;
+        res->status_string[0] = 0;
+        mdl->solve(t_entry, run_opt ? &run : nullptr, res, start, start_dev, fac, out_dev);
+        return 0;
+    });
+}
+
+int proxsdp_hip_model_norm2(const double* v, int64_t n, int32_t grid, double* out) {
+    return guarded([&]() -> int {
+        if ((n > 0 && !v) || !out || n < 0 || grid > 65535) throw std::invalid_argument("invalid argument");
+        Engine E(nullptr, 2, 2);
+        proxsdp::Solver& S = E.S;
+        proxsdp::DevBuf<double> d((size_t)std::max<int64_t>(n, 1)), part, sum;
+        d.upload(v, (size_t)n, S.stream);
+        *out = proxsdp::model_norm2(S.stream, d.p, n, part, sum, grid);
+        return 0;
+    });
 }
 
 int proxsdp_hip_exit_vectors(const proxsdp_problem* prob, const proxsdp_options* opt, const double* x, const double* y,
@@ -1194,6 +1321,40 @@ int proxsdp_host_preprocess(const proxsdp_problem* prob, int64_t* order, int64_t
             if (c_scaled) c_scaled[i] = R.c[i];
         }
         if (frobenius_norm_M) *frobenius_norm_M = R.frob;
+        return 0;
+    });
+}
+
+int proxsdp_host_model_prepare(const proxsdp_problem* prob, proxsdp_model_dump* out, int64_t* nnz_A, int32_t* csc_pos,
+                               int32_t* csr_pos) {
+    return guarded([&]() -> int {
+        if (!prob || !out) throw std::invalid_argument("NULL problem or dump");
+        if (out->struct_size != (int64_t)sizeof(proxsdp_model_dump)) throw std::invalid_argument("proxsdp_model_dump.struct_size mismatch");
+        if (is_shard(prob) || prob->M_dense) throw std::domain_error("proxsdp_host_model_prepare does not serve a shard of a block-sharded solve or M_dense");
+        const proxsdp::Prep R = proxsdp::prepare(*prob, nullptr, false, true);
+        std::vector<int32_t> supp;
+        for (int64_t k = 0; k < R.n; ++k)
+            if (R.colptr[k + 1] > R.colptr[k] || R.c[k] != 0.0) supp.push_back((int32_t)k);
+        out->n = R.n; out->Q = R.Q; out->nnz = R.nnz; out->ns = (int64_t)supp.size();
+        out->norms[0] = R.norm_b; out->norms[1] = R.norm_h; out->norms[2] = R.norm_c; out->norms[3] = R.frob;
+        if (nnz_A) *nnz_A = R.nnzA;
+        for (int64_t q = 0; q < R.nnz; ++q) {
+            if (out->csc_val) out->csc_val[q] = R.val[q];
+            if (out->csr_val) out->csr_val[q] = R.rval[q];
+            if (out->csc_val_orig) out->csc_val_orig[q] = R.val_orig[q];
+            if (out->csr_val_orig) out->csr_val_orig[R.csr_pos[q]] = R.val_orig[R.csc_pos[q]];
+            if (csc_pos) csc_pos[q] = R.csc_pos[q];
+            if (csr_pos) csr_pos[q] = R.csr_pos[q];
+        }
+        for (int64_t k = 0; k < R.n; ++k) {
+            if (out->c) out->c[k] = R.c[k];
+            if (out->c_orig) out->c_orig[k] = R.c_orig[k];
+        }
+        for (int64_t i = 0; i < R.Q && out->bh; ++i) out->bh[i] = i < R.p ? R.b[i] : R.h[i - R.p];
+        for (size_t q = 0; q < supp.size(); ++q) {
+            if (out->support) out->support[q] = supp[q];
+            if (out->cS) out->cS[q] = R.c[supp[q]];
+        }
         return 0;
     });
 }

@@ -1,0 +1,265 @@
+// A model that stays set up on the device between solves (include/proxsdp_hip.h "model handle"): one live Solver on storage
+// of its own, the index maps its data is replaced through (model_update.hip.hpp), and the counters proxsdp_hip_model_info
+// reports.  No line of the reference stands behind this file: ProxSDP builds AffineSets, ConicSets, the operator and every
+// workspace anew in each optimize! (/root/reference/src/MOI_wrapper.jl:220-342).
+//
+// create  = everything Solver::run does before initial_steps() (Solver::setup) + the device exit path's set-up, once
+// solve   = Solver::reset_for_solve() + Solver::solve(): proxsdp_hip_solve_device on the model's current data, bit for bit
+// update  = the caller's new numbers through the recorded maps into the device arrays, the four norms, and -- when the zero
+//           pattern of c moved the support set -- setup_support() / alloc_candidates() once more
+// The entry points (argument checks, error codes) are in capi.hip.
+#pragma once
+#include "exit_device.hip.hpp"
+#include "model_update.hip.hpp"
+
+struct proxsdp_model {
+    std::atomic<long long> bytes{0};            // live device bytes (DevAccount); first member: outlives every buffer below
+    proxsdp_options opt0{};                     // create's options, as given
+    proxsdp_result scratch{};                   // the result the solver writes: rebound to the caller's arrays per solve
+    std::vector<double> resid;                  // copy of proxsdp_problem.eig_resid
+    std::vector<int64_t> psd_ptr;               // the cone lists' offsets, for the argument checks of a solve
+    proxsdp_problem shape{};                    // n, p, m, n_psd, psd_ptr: what those checks read of a problem
+    int64_t solves = 0, updates = 0, support_rebuilds = 0;
+    double setup_time = 0.0;
+    std::unique_ptr<proxsdp::Solver> S;
+    proxsdp::DevBuf<int> csc_pos_d, csr_pos_d, sinv_d, flag_d;
+    proxsdp::DevBuf<long long> ord_d;
+    proxsdp::DevBuf<double> stage, npart, nout;
+
+    // device allocations of this thread (and of the block workers started under it) count for this model while one lives
+    struct Accounting {
+        std::atomic<long long>* prev;
+        explicit Accounting(proxsdp_model& m) : prev(proxsdp::DevAccount::sink) { proxsdp::DevAccount::sink = &m.bytes; }
+        ~Accounting() { proxsdp::DevAccount::sink = prev; }
+    };
+
+    // o: validated options; the caller has refused what a handle does not serve
+    proxsdp_model(const proxsdp_problem& prob, const proxsdp_options& o) : opt0(o) {
+        using namespace proxsdp;
+        const double t0 = now_s();
+        Accounting acct(*this);
+        S.reset(new Solver(prob, o, scratch, nullptr, 0, true));      // prepare(): every check of proxsdp_hip_solve, on the host
+        Solver& s = *S;
+        size_t rlen = 0;
+        for (const BlockInfo& B : s.P.blocks) rlen += (size_t)B.n;
+        if (prob.eig_resid) { resid.assign(prob.eig_resid, prob.eig_resid + rlen); s.user_resid = resid.data(); }
+        psd_ptr.assign(1, 0);
+        for (const BlockInfo& B : s.P.blocks) psd_ptr.push_back(psd_ptr.back() + B.N);
+        shape.n = s.P.n; shape.p = s.P.p; shape.m = s.P.m;
+        shape.n_psd = (int64_t)s.P.blocks.size(); shape.psd_ptr = psd_ptr.data();
+        s.device_exit = true;
+        s.setup();
+        s.exit_device_setup();
+        const Prep& P = s.P;
+        const size_t nz = (size_t)std::max<int64_t>(P.nnz, 1), n1 = (size_t)std::max<int64_t>(P.n, 1);
+        csc_pos_d.alloc(nz); csc_pos_d.upload(P.csc_pos.data(), P.nnz, s.stream);
+        csr_pos_d.alloc(nz); csr_pos_d.upload(P.csr_pos.data(), P.nnz, s.stream);
+        static_assert(sizeof(long long) == sizeof(int64_t), "the variable order is uploaded as it is");
+        ord_d.alloc(n1); ord_d.upload(reinterpret_cast<const long long*>(P.ord.data()), P.n, s.stream);
+        flag_d.alloc(8);
+        upload_support_map();
+        PX_HIP(hipStreamSynchronize(s.stream));
+        s.release_host_threads();
+        setup_time = now_s() - t0;
+    }
+
+    // position in the support list of every variable (-1: outside), for k_model_c's store into the compact cS
+    void upload_support_map() {
+        using namespace proxsdp;
+        Solver& s = *S;
+        if (!s.use_support) return;
+        std::vector<int> sinv((size_t)std::max<int64_t>(s.P.n, 1), -1);
+        for (int q = 0; q < s.ns; ++q) sinv[s.supp_h[q]] = q;
+        sinv_d.alloc(sinv.size());
+        sinv_d.upload(sinv.data(), sinv.size(), s.stream);
+        PX_HIP(hipStreamSynchronize(s.stream));
+    }
+
+    // every stream of the solver idle (after a solve that ended in an exception: launches may still be in flight)
+    void drain() {
+        proxsdp::Solver& s = *S;
+        if (s.stream.main) (void)hipStreamSynchronize(s.stream.main);
+        for (proxsdp::EigWork& W : s.eig) {
+            if (W.stream) (void)hipStreamSynchronize(W.stream);
+            if (W.side) (void)hipStreamSynchronize(W.side);
+        }
+        (void)hipGetLastError();
+    }
+
+    // run: the fields of the options a solve may change, already validated against opt0 (null: opt0's)
+    void solve(double t_entry, const proxsdp_options* run, proxsdp_result* res, const proxsdp_start* start,
+               const proxsdp_device_vectors* start_dev, proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev) {
+        using namespace proxsdp;
+        Solver& s = *S;
+        PX_HIP(hipSetDevice(opt0.device_id));
+        Accounting acct(*this);
+        const proxsdp_options& r = run ? *run : opt0;
+        s.opt.time_limit = r.time_limit; s.opt.max_iter = r.max_iter; s.opt.log_verbose = r.log_verbose;
+        s.opt.log_freq = r.log_freq; s.opt.warn_on_limit = r.warn_on_limit; s.opt.trace_capacity = r.trace_capacity;
+        if (s.opt.trace_capacity > 0 && !res->trace) s.opt.trace_capacity = 0;
+        scratch = *res;
+        s.time0 = t_entry; s.t_init0 = t_entry;
+        proxsdp_start none{};                               // start_dev without a start: no factors, cold steps
+        none.struct_size = (int64_t)sizeof(proxsdp_start);
+        struct Leave {                                      // no thread of the handle outlives the call
+            proxsdp_model& m; bool ok = false;
+            ~Leave() { if (!ok) m.drain(); m.S->release_host_threads(); }
+        } leave{*this};
+        s.reset_for_solve();
+        s.factors_out = fac;
+        s.start = (!start && start_dev) ? &none : start;
+        s.start_dev = start_dev;
+        s.out_dev = out_dev;
+        s.device_exit = true;
+        s.start_block_workers();
+        s.solve();
+        PX_HIP(hipStreamSynchronize(s.stream));
+        s.start = nullptr; s.start_dev = nullptr; s.factors_out = nullptr; s.out_dev = nullptr;
+        leave.ok = true;
+        *res = scratch;
+        ++solves;
+    }
+
+    // upd: validated on the host (struct_size, some pointer given, host values finite, what the model does not serve)
+    void update(const proxsdp_model_data& u) {
+        using namespace proxsdp;
+        Solver& s = *S;
+        Prep& P = s.P;
+        PX_HIP(hipSetDevice(opt0.device_id));
+        Accounting acct(*this);
+        hipStream_t st = s.stream;
+        const bool on_dev = u.on_device != 0;
+        const int64_t nnzA = P.nnzA, nnzG = P.nnz - P.nnzA;
+        const double* src[5] = {u.c, u.b, u.h, u.A_nzval, u.G_nzval};
+        const int64_t len[5] = {P.n, P.p, P.m, nnzA, nnzG};
+        const char* name[5] = {"c", "b", "h", "A_nzval", "G_nzval"};
+        if (on_dev) {                                       // the finite check of device data: a reduction, before any write
+            flag_d.zero(st);
+            for (int q = 0; q < 5; ++q)
+                if (src[q] && len[q] > 0)
+                    hipLaunchKernelGGL(dev::k_exit_nonfinite, dim3(grid_for(len[q])), dim3(dev::TPB), 0, st, src[q],
+                                       (long long)len[q], flag_d.p + q);
+            PX_HIP(hipGetLastError());
+            int h[5] = {0, 0, 0, 0, 0};
+            flag_d.download(h, 5, st);
+            PX_HIP(hipStreamSynchronize(st));
+            for (int q = 0; q < 5; ++q)
+                if (h[q]) throw std::invalid_argument(std::string("proxsdp_model_data: non-finite entry in ") + name[q]);
+        }
+        s.restore_cert_data();                              // (a certificate search of the last solve zeroed c or [b; h])
+        // a host array goes through the staging buffer; the stream orders its reuse
+        auto on_device = [&](int q) -> const double* {
+            if (on_dev || !src[q] || len[q] == 0) return src[q];
+            if (stage.n < (size_t)len[q]) stage.alloc((size_t)std::max<int64_t>(std::max(P.n, P.Q), std::max<int64_t>(P.nnz, 1)));
+            stage.upload(src[q], (size_t)len[q], st);
+            return stage.p;
+        };
+        const double cte = std::sqrt(2.0) / 2.0;
+        int moved = 0;
+        if (u.c && P.n > 0) {
+            const double* d = on_device(0);
+            PX_HIP(hipMemsetAsync(flag_d.p + 5, 0, sizeof(int), st));
+            hipLaunchKernelGGL(dev::k_model_c, dim3(grid_for(P.n)), dim3(dev::TPB), 0, st, d, (const long long*)ord_d.p,
+                               (const unsigned char*)s.offdiag_d.p, cte, (const int*)s.csc_ptr.p,
+                               s.use_support ? (const int*)sinv_d.p : (const int*)nullptr, s.c_d.p, s.xd.c.p,
+                               s.use_support ? s.cS_d.p : (double*)nullptr, flag_d.p + 5, (long long)P.n);
+            PX_HIP(hipGetLastError());
+            if (on_dev) P.norm_c = model_norm2(st, d, P.n, npart, nout);
+            else P.norm_c = norm2(u.c, P.n);
+            PX_HIP(hipMemcpyAsync(&moved, flag_d.p + 5, sizeof(int), hipMemcpyDeviceToHost, st));
+            s.c_d.download(P.c.data(), P.n, st);
+            s.xd.c.download(P.c_orig.data(), P.n, st);
+            PX_HIP(hipStreamSynchronize(st));
+            s.c_host = P.c;
+        }
+        for (int q = 3; q < 5; ++q) {
+            if (!src[q] || len[q] == 0) continue;
+            const int64_t off = q == 3 ? 0 : nnzA;
+            const double* d = on_device(q);
+            hipLaunchKernelGGL(dev::k_model_values, dim3(grid_for(len[q])), dim3(dev::TPB), 0, st, d, (long long)len[q],
+                               (const int*)csc_pos_d.p + off, (const int*)csr_pos_d.p + off, (const int*)s.csr_col.p,
+                               (const unsigned char*)s.offdiag_d.p, cte, s.xd.cval.p, s.xd.rval.p, s.csc_val.p, s.csr_val.p);
+            PX_HIP(hipGetLastError());
+        }
+        if ((u.A_nzval && nnzA > 0) || (u.G_nzval && nnzG > 0)) {
+            s.csc_val.download(P.val.data(), P.nnz, st);
+            s.csr_val.download(P.rval.data(), P.nnz, st);
+            s.xd.cval.download(P.val_orig.data(), P.nnz, st);
+            PX_HIP(hipStreamSynchronize(st));
+            if (on_dev) {
+                P.frob = model_norm2(st, s.csc_val.p, P.nnz, npart, nout);
+            } else {                                        // finish_matrix's sum: the scaled values in reordered CSC order
+                double ss = 0.0;
+                for (int64_t q = 0; q < P.nnz; ++q) ss += P.val[q] * P.val[q];
+                P.frob = std::sqrt(ss);
+            }
+        }
+        if ((u.b && P.p > 0) || (u.h && P.m > 0)) {
+            const double* db = nullptr;
+            const double* dh = nullptr;
+            if (u.b && P.p > 0) {
+                db = on_device(1);
+                if (!on_dev) {                              // (the staging buffer takes h next: b's launch goes first)
+                    hipLaunchKernelGGL(dev::k_model_bh, dim3(grid_for(P.Q)), dim3(dev::TPB), 0, st, db, (long long)P.p,
+                                       (const double*)nullptr, (long long)P.m, s.bh_d.p, s.xd.bh.p);
+                    db = nullptr;
+                }
+            }
+            if (u.h && P.m > 0) dh = on_device(2);
+            if (db || dh)
+                hipLaunchKernelGGL(dev::k_model_bh, dim3(grid_for(P.Q)), dim3(dev::TPB), 0, st, db, (long long)P.p, dh,
+                                   (long long)P.m, s.bh_d.p, s.xd.bh.p);
+            PX_HIP(hipGetLastError());
+            if (u.b && P.p > 0) P.norm_b = on_dev ? model_norm2(st, u.b, P.p, npart, nout) : norm2(u.b, P.p);
+            if (u.h && P.m > 0) P.norm_h = on_dev ? model_norm2(st, u.h, P.m, npart, nout) : norm2(u.h, P.m);
+            std::vector<double> bh((size_t)P.Q);
+            s.bh_d.download(bh.data(), P.Q, st);
+            PX_HIP(hipStreamSynchronize(st));
+            std::copy(bh.begin(), bh.begin() + P.p, P.b.begin());
+            std::copy(bh.begin() + P.p, bh.end(), P.h.begin());
+            P.b_orig = P.b; P.h_orig = P.h;
+            s.b_host = P.b; s.h_host = P.h;
+        }
+        PX_HIP(hipStreamSynchronize(st));
+        if (moved != 0) {                                   // the support set changed: what setup_support() and alloc_candidates() built, again
+            for (EigWork& W : s.eig) { W.fop_ok = false; W.ell_w = 0; W.ov = dev::EllOverflow{}; }
+            s.ns = 0; s.rstride = 0; s.n_res_wg = 0; s.tile_base.clear(); s.supp_h.clear();
+            s.setup_support();
+            s.alloc_candidates();
+            upload_support_map();
+            ++support_rebuilds;
+        }
+        ++updates;
+    }
+
+    void info(proxsdp_model_info& out) const {
+        const proxsdp::Solver& s = *S;
+        out.n = s.P.n; out.p = s.P.p; out.m = s.P.m; out.n_psd = (int64_t)s.P.blocks.size(); out.nnz = s.P.nnz;
+        out.device_id = opt0.device_id; out.use_support = s.use_support ? 1 : 0;
+        out.solves = solves; out.updates = updates; out.support_rebuilds = support_rebuilds;
+        out.device_bytes = bytes.load();
+        out.setup_time = setup_time;
+    }
+
+    // sizes always; an array when its pointer is given
+    void dump(proxsdp_model_dump& out) {
+        using namespace proxsdp;
+        Solver& s = *S;
+        const Prep& P = s.P;
+        PX_HIP(hipSetDevice(opt0.device_id));
+        s.restore_cert_data();
+        hipStream_t st = s.stream;
+        out.n = P.n; out.Q = P.Q; out.nnz = P.nnz; out.ns = s.use_support ? s.ns : 0;
+        out.norms[0] = P.norm_b; out.norms[1] = P.norm_h; out.norms[2] = P.norm_c; out.norms[3] = P.frob;
+        if (out.csc_val) s.csc_val.download(out.csc_val, P.nnz, st);
+        if (out.csr_val) s.csr_val.download(out.csr_val, P.nnz, st);
+        if (out.csc_val_orig) s.xd.cval.download(out.csc_val_orig, P.nnz, st);
+        if (out.csr_val_orig) s.xd.rval.download(out.csr_val_orig, P.nnz, st);
+        if (out.c) s.c_d.download(out.c, P.n, st);
+        if (out.c_orig) s.xd.c.download(out.c_orig, P.n, st);
+        if (out.bh) s.bh_d.download(out.bh, P.Q, st);
+        if (out.support && out.ns > 0) PX_HIP(hipMemcpyAsync(out.support, s.supp_d.p, (size_t)out.ns * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (out.cS && out.ns > 0) s.cS_d.download(out.cS, out.ns, st);
+        PX_HIP(hipStreamSynchronize(st));
+    }
+};

@@ -876,6 +876,7 @@ inline std::vector<int> Solver::support_list() const {
 // the support's device vectors: the list, its bit mask, c on S, and the buffers k_primal_update_S writes
 inline void Solver::upload_support(const std::vector<int>& supp) {
     ns = (int)supp.size();
+    supp_h = supp;
     std::vector<unsigned> mask((size_t)(P.n + 31) / 32 + 1, 0u);
     std::vector<double> cS(std::max(ns, 1), 0.0);
     for (int s = 0; s < ns; ++s) { mask[supp[s] >> 5] |= 1u << (supp[s] & 31); cS[s] = P.c[supp[s]]; }
@@ -1094,8 +1095,10 @@ inline void Solver::apply_start() {
     };
     if (s.primal || d_primal) {                          // every entry outside the factored cones
         static_assert(sizeof(long long) == sizeof(int64_t), "variable order is uploaded as it is");
-        start_ord_d.alloc(P.n);
-        start_ord_d.upload(reinterpret_cast<const long long*>(P.ord.data()), P.n, stream);
+        if (start_ord_d.n != (size_t)P.n) {               // (a model handle's later solves find it uploaded)
+            start_ord_d.alloc(P.n);
+            start_ord_d.upload(reinterpret_cast<const long long*>(P.ord.data()), P.n, stream);
+        }
         if (offdiag_d.n == 0) { offdiag_d.alloc(P.n); offdiag_d.upload(P.offdiag.data(), P.n, stream); }
         const double* src = d_primal;
         if (!src) { start_src_d.upload(s.primal, P.n, stream); src = start_src_d.p; }
@@ -1381,6 +1384,7 @@ inline void Solver::classify_blocks() {
 // stream per block (the per-block Lanczos chains are launch-latency-bound, so they overlap
 // almost perfectly: MIMO n=512 x 8 on one GPU).  options.block_threads = 0 disables.
 inline void Solver::start_block_workers() {
+    if (block_pool) return;                              // (a model handle calls this before every solve)
     int nthreads = opt.block_threads < 0 ? 8 : std::min(opt.block_threads, 64);
     // (blocks handled by the batched small-block kernel need no worker / stream of their own)
     const std::vector<int>& pool_blocks = small_blocks.empty() ? big_blocks : large_blocks;
@@ -1393,7 +1397,8 @@ inline void Solver::start_block_workers() {
     ev_main.create(hipEventDisableTiming);
     PX_HIP(hipStreamSynchronize(stream));           // workspace zero-fills precede any block-stream work
     const int dev_id = opt.device_id;
-    block_pool.reset(new BlockPool(nthreads, [dev_id]() { (void)hipSetDevice(dev_id); }));
+    std::atomic<long long>* const sink = DevAccount::sink;
+    block_pool.reset(new BlockPool(nthreads, [dev_id, sink]() { (void)hipSetDevice(dev_id); DevAccount::sink = sink; }));
 }
 
 // the batched small-block launch: offsets, sides and rank records of its blocks, and the kernels' LDS grants
@@ -1463,12 +1468,14 @@ inline void Solver::cert_infeas() {
     std::fill(c_host.begin(), c_host.end(), 0.0);
     c_d.zero(stream);
     if (use_support) cS_d.zero(stream);
+    cert_zeroed_c = true;
     certificate_parameters();
 }
 inline void Solver::cert_dual_infeas() {
     std::fill(b_host.begin(), b_host.end(), 0.0);
     std::fill(h_host.begin(), h_host.end(), 0.0);
     bh_d.zero(stream);
+    cert_zeroed_bh = true;
     certificate_parameters();
 }
 inline void Solver::snapshot() { if (device_exit) cache_solution_device(false); else cache_solution(P.c_orig); }
@@ -1729,7 +1736,13 @@ inline void Solver::finish() {
 }
 
 inline void Solver::run() {
-    const double t_init0 = now_s();
+    setup();
+    solve();
+}
+
+// everything before the first step size: what a model handle (model.hip.hpp) runs once
+inline void Solver::setup() {
+    t_init0 = now_s();
     check_run_options();
     init_parameters();
     reduce_global_constants();
@@ -1751,6 +1764,10 @@ inline void Solver::run() {
     alloc_candidates();
     if (sharded() && use_support == shard_general)
         throw std::logic_error("block-sharded solve: the shard's vector path is not the one chosen for it");
+}
+
+// the steps, the start path, the loop and the exit: what a model handle runs per solve
+inline void Solver::solve() {
     if (!initial_steps()) return;
 
     // ---- where the loop enters: cold, resumed (proxsdp_hip_solve_ex) or from the caller's point (proxsdp_hip_solve_from)
@@ -1770,6 +1787,109 @@ inline void Solver::run() {
         if (after_iteration(k) == Loop::stop) break;
     }
     finish();
+}
+
+// ---- a solver kept set up between solves (model.hip.hpp)
+// One block's workspace as classify_blocks() and setup_support() left it: the buffers they zeroed are zero again (and the
+// ones a run fills before it reads them as well: the same launch costs nothing more), the start vector is uploaded again,
+// every host member a projection writes has its initial value.  What the set-up built stays: sizes, the record pointers,
+// the ELL structures with fop_ok, the streams and events, the sign projection's work matrices with their tile shape
+// (allocated on first use; sgA's padding is zero and stays zero, as the rows the 48-tiles never write).
+inline void Solver::reset_eigwork(EigWork& W) {
+    for (DevBuf<double>* b : {&W.V, &W.Z, &W.w, &W.Ppart, &W.hpart1, &W.hpart2, &W.hsum1, &W.hred, &W.U, &W.lam, &W.Apart,
+                              &W.arrow, &W.rec, &W.hpw1, &W.hpw2, &W.hsw1, &W.hsw2, &W.recw, &W.F, &W.Flam, &W.tpart, &W.tred,
+                              &W.ebuf, &W.apartf, &W.warm_part, &W.sg_sc, &W.sg_part, &W.sg_part2})
+        b->zero(stream);
+    if (W.resid.n > 0) W.resid.upload(W.resid_host.data(), W.npad, stream);
+    if (W.arrow_host.p) std::fill(W.arrow_host.p, W.arrow_host.p + 2 * dev::MAXK, 0.0);
+    W.arrow_p = W.arrow.p;
+    W.ustage_next = 0; W.rot_form = 0; W.rot_launches = 0;
+    W.vals.clear();
+    W.count = 0; W.converged_eigs = 0; W.numiter = 0; W.prev_numiter = 1; W.converged = false;
+    W.F_first = 0; W.F_r = 0;
+    W.have_factors = false; W.use_fop = false;
+    W.xprev = EigWork::XPrev{};
+    W.ritz_ok = false; W.ritz_first = 0; W.ritz_r = 0;
+    W.split.k1 = 0; W.split.K = 0; W.split.beta = 0.0; W.split.have_first = false; W.split.M.par = nullptr;
+    W.batch_slot = 0;
+    W.b1_rot_K = 0; W.b1_rot_U = nullptr;
+    W.lzrun = LzRun{};
+    W.fel = EigWork::LanczosFullEig{};
+    W.cye_pending = false; W.esv = nullptr;
+    W.lst = proxsdp_stats{};
+    W.mv_iter = 0; W.recon_r = 0;
+    W.fe_pending = false;
+    W.sg_row = -1; W.sg_ok = 16; W.sg_idle = 0; W.sg_hold = 0; W.sg_pending = false;
+    W.sign = EigWork::SignStandIn{};
+    W.ev.used = 0; W.evo.used = 0;
+}
+
+// c and [b; h] on the device after a certificate search zeroed them (cert_infeas, cert_dual_infeas): from the Prep again
+inline void Solver::restore_cert_data() {
+    if (cert_zeroed_c) {
+        c_host = P.c;
+        c_d.upload(P.c.data(), P.n, stream);
+        if (use_support) {
+            std::vector<double> cS(std::max(ns, 1), 0.0);
+            for (int s = 0; s < ns; ++s) cS[s] = P.c[supp_h[s]];
+            cS_d.upload(cS.data(), ns, stream);
+            PX_HIP(hipStreamSynchronize(stream));        // (cS goes out of scope)
+        }
+        cert_zeroed_c = false;
+    }
+    if (cert_zeroed_bh) {
+        b_host = P.b; h_host = P.h;
+        std::vector<double> bh(P.Q);
+        std::copy(P.b.begin(), P.b.end(), bh.begin());
+        std::copy(P.h.begin(), P.h.end(), bh.begin() + P.p);
+        bh_d.upload(bh.data(), P.Q, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+        cert_zeroed_bh = false;
+    }
+}
+
+// Every member a solve writes, back at the value it has after setup().  The data vectors a certificate search zeroes
+// (cert_infeas, cert_dual_infeas) come back from the Prep, which a model handle keeps current.
+inline void Solver::reset_for_solve() {
+    PX_HIP(hipStreamSynchronize(stream));
+    init_parameters();                                   // Params, target ranks, histories, time_limit
+    reduce_global_constants();                           // the norms may have changed (proxsdp_hip_model_update); max_iter_local
+    primal_step = 0; primal_step_old = 0; dual_step = 0;
+    iter = 0; rank_update = 0; update_cont = 0; stop_reason = 0;
+    stop_reason_string = "Not optimized";
+    dual_feasibility = -1.0;
+    certificate_search = false; certificate_found = false; certificate_search_min_iter = 0;
+    last_trials = 0; lz_matvec_iter = 0; recon_r_iter = 0;
+    equa_feasibility = 0; ineq_feasibility = 0;
+    have_snapshot = false; start_active = false;
+    st = proxsdp_stats{};
+    shard_error = nullptr;
+    dense_ev_used = 0; dense_passes_seen = 0;
+    dbg_batch = BatchDebug{}; dbg_lz = LzDebug{};
+    sigma_max = 0.0; loop_t0 = 0; g_elapsed = 0;
+    g_not_converged_rank = false; g_any_below_full = false;
+    small_pending = false;
+    for (int k = 0; k < 2; ++k) { xbuf[k].zero(stream); Mtybuf[k].zero(stream); ybuf[k].zero(stream); Mxbuf[k].zero(stream); }
+    xc = yc = mxc = mtyc = 0;
+    restore_cert_data();
+    part.zero(stream); scal.zero(stream);
+    small_rank.zero(stream);
+    if (small_rank_host.p) std::fill(small_rank_host.p, small_rank_host.p + 2 * small_blocks.size() + 2, 0.0);
+    if (use_support) { MtyS_cur.zero(stream); xsave_d.zero(stream); esv_d.zero(stream); respart_d.zero(stream); }
+    ycand_d.zero(stream); Mtycand_d.zero(stream); bpart.zero(stream); bscal.zero(stream);
+    hbscal.assign(64, 0.0);
+    if (hscal_pin.p) std::fill(hscal_pin.p, hscal_pin.p + 64, 0.0);
+    for (int idx : big_blocks) reset_eigwork(eig[idx]);
+    batch_ctx.clear();                                   // (the batched runs' buffers come on first use, as in a fresh solve)
+    factors_out = nullptr; start = nullptr; start_dev = nullptr; out_dev = nullptr;
+    PX_HIP(hipStreamSynchronize(stream));
+}
+
+// the block workers and the merge helpers end with a solve: a model handle keeps no thread between calls
+inline void Solver::release_host_threads() {
+    block_pool.reset();
+    merge_pool.reset();
+    for (auto& c : batch_ctx) if (c) c->pool.reset();
 }
 
 }  // namespace proxsdp

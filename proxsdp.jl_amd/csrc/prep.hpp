@@ -48,6 +48,11 @@ struct Prep {
     // equilibration asked for on a dense A: the limit check and the scaling need one device pass over the
     // borrowed matrix, so prepare() leaves them to the solver (finish_dense_equilibration)
     bool equil_deferred = false;
+    // position maps of a model handle (model.hip.hpp; prepare(..., record_maps = true)): entry q of the caller's A.nzval
+    // followed by G.nzval sits at csc_pos[q] of val / val_orig and at csr_pos[q] of rval.  Recording them changes nothing else.
+    bool record_maps = false;
+    int64_t nnzA = 0;
+    std::vector<int32_t> csc_pos, csr_pos;
 };
 
 inline double norm2(const double* v, int64_t n) {
@@ -152,8 +157,8 @@ inline void equilibrate_rowsums(const double* rs, int64_t nQ, int64_t n, const p
     d = std::exp(v_);
 }
 
-// values of the solver's M (E M D when equilibrated, then the sqrt(2)/2 column factor), its Frobenius norm, its CSR
-inline void finish_matrix(Prep& R) {
+// values of the solver's M (E M D when equilibrated, then the sqrt(2)/2 column factor) and its Frobenius norm
+inline void scale_values(Prep& R) {
     const double cte = std::sqrt(2.0) / 2.0;
     const bool equil = R.equilibrated;
     double ss = 0.0;
@@ -167,8 +172,13 @@ inline void finish_matrix(Prep& R) {
         }
     }
     R.frob = std::sqrt(ss);
+}
 
-    // ---- CSR of the scaled M (counting sort; column order inside a row ascending)
+// ... and its CSR (counting sort; column order inside a row ascending)
+inline void finish_matrix(Prep& R) {
+    scale_values(R);
+    std::vector<int32_t> to_csr;                         // CSC position -> CSR position, for the position maps only
+    if (R.record_maps) to_csr.resize(R.nnz);
     R.rowptr.assign(R.Q + 1, 0);
     for (int64_t q = 0; q < R.nnz; ++q) R.rowptr[R.rowidx[q] + 1]++;
     for (int64_t r = 0; r < R.Q; ++r) R.rowptr[r + 1] += R.rowptr[r];
@@ -179,7 +189,12 @@ inline void finish_matrix(Prep& R) {
             int64_t d = cur[R.rowidx[q]]++;
             R.colidx[d] = (int32_t)k;
             R.rval[d] = R.val[q];
+            if (R.record_maps) to_csr[q] = (int32_t)d;
         }
+    if (R.record_maps) {
+        R.csr_pos.resize(R.nnz);
+        for (int64_t q = 0; q < R.nnz; ++q) R.csr_pos[q] = to_csr[R.csc_pos[q]];
+    }
 }
 
 // [b;h] <- E [b;h], c <- D c (pdhg.jl:74-92)
@@ -235,8 +250,10 @@ inline int64_t psd_side(int64_t len) {
     return side * (side + 1) / 2 == len ? side : -1;
 }
 
-inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullptr, bool shard = false) {
+inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullptr, bool shard = false,
+                    bool record_maps = false) {
     Prep R;
+    R.record_maps = record_maps;
     const int base = P.index_base;
     if (base != 0 && base != 1) throw std::invalid_argument("index_base must be 0 or 1");
     if (P.n < 0 || P.p < 0 || P.m < 0) throw std::invalid_argument("negative dimension");
@@ -324,6 +341,8 @@ inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullp
     if (R.nnz >= ((int64_t)1 << 31) - 1) throw std::invalid_argument("nnz(M) >= 2^31 not supported by the sparse path");
     R.colptr.assign(P.n + 1, 0);
     R.rowidx.resize(R.nnz); R.val.resize(R.nnz); R.val_orig.resize(R.nnz);
+    R.nnzA = nnzA;
+    if (record_maps) R.csc_pos.resize(R.nnz);
     int64_t w = 0;
     for (int64_t k = 0; k < P.n; ++k) {
         const int64_t j = R.ord[k];
@@ -331,10 +350,12 @@ inline Prep prepare(const proxsdp_problem& P, const proxsdp_options* opt = nullp
         for (int64_t q = dense ? 0 : P.A.colptr[j] - base; q < (dense ? 0 : P.A.colptr[j + 1] - base); ++q, ++w) {
             R.rowidx[w] = (int32_t)(P.A.rowval[q] - base);
             R.val_orig[w] = P.A.nzval[q];
+            if (record_maps) R.csc_pos[q] = (int32_t)w;
         }
         for (int64_t q = P.G.colptr[j] - base; q < P.G.colptr[j + 1] - base; ++q, ++w) {
             R.rowidx[w] = (int32_t)(P.G.rowval[q] - base + P.p);
             R.val_orig[w] = P.G.nzval[q];
+            if (record_maps) R.csc_pos[nnzA + q] = (int32_t)w;
         }
     }
     R.colptr[P.n] = w;

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <array>
+#include <atomic>
 #include <memory>
 #include <mutex>
 #include <condition_variable>
@@ -46,6 +47,8 @@
 #include "shard_group.hpp"
 #include "prep.hpp"
 
+struct proxsdp_model;               // (model.hip.hpp: a Solver kept set up between solves)
+
 namespace proxsdp {
 
 struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -64,17 +67,27 @@ struct HipError : std::runtime_error { using std::runtime_error::runtime_error; 
             throw ::proxsdp::HipError(std::string(#call) + ": rocblas status " + std::to_string((int)s_)); \
     } while (0)
 
+// Where the device buffers allocated on this thread are counted (proxsdp_model_info.device_bytes): a model handle points it
+// at its own counter for the length of a call, the block workers inherit it (start_block_workers); null everywhere else.
+struct DevAccount { static inline thread_local std::atomic<long long>* sink = nullptr; };
+
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    std::atomic<long long>* acct = nullptr;     // the counter this allocation was added to, with `held` bytes
+    size_t held = 0;
     DevBuf() = default;
     explicit DevBuf(size_t count) { alloc(count); }
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n), acct(o.acct), held(o.held) { o.p = nullptr; o.n = 0; o.acct = nullptr; o.held = 0; }
     DevBuf& operator=(DevBuf&& o) noexcept {
-        if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        if (this != &o) {
+            release();
+            p = o.p; n = o.n; acct = o.acct; held = o.held;
+            o.p = nullptr; o.n = 0; o.acct = nullptr; o.held = 0;
+        }
         return *this;
     }
     ~DevBuf() { release(); }
@@ -84,8 +97,14 @@ struct DevBuf {
         if (count == 0) return;
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
         if (e != hipSuccess) { p = nullptr; throw std::bad_alloc(); }
+        acct = DevAccount::sink;
+        held = count * sizeof(T);
+        if (acct) acct->fetch_add((long long)held);
     }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; } n = 0; }
+    void release() {
+        if (p) { (void)hipFree(p); p = nullptr; if (acct) acct->fetch_sub((long long)held); }
+        n = 0; acct = nullptr; held = 0;
+    }
     void zero(hipStream_t s) { if (n) PX_HIP(hipMemsetAsync(p, 0, n * sizeof(T), s)); }
     void upload(const T* h, size_t count, hipStream_t s) {
         if (count) PX_HIP(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s));
@@ -411,9 +430,11 @@ public:
     // time0 is stamped BEFORE prepare(): the reference's clock starts at the top of chambolle_pock
     // (pdhg.jl:13), so preprocessing and equilibration count towards Result.time and time_limit
     // grp / grp_rank: this solver is shard grp_rank of an in-process shard group (proxsdp_hip_solve_sharded)
+    // record_maps: prepare() keeps the position maps a model handle updates its values through (Prep::csc_pos / csr_pos)
     Solver(const proxsdp_problem& prob, const proxsdp_options& opt_in, proxsdp_result& res_out,
-           ShardGroup* grp = nullptr, int grp_rank = 0)
-        : opt(opt_in), res(res_out), time0(now_s()), P(prepare(prob, &opt_in, grp != nullptr || prob.reduce_fn != nullptr || prob.nccl_comm != nullptr)) {
+           ShardGroup* grp = nullptr, int grp_rank = 0, bool record_maps = false)
+        : opt(opt_in), res(res_out), time0(now_s()),
+          P(prepare(prob, &opt_in, grp != nullptr || prob.reduce_fn != nullptr || prob.nccl_comm != nullptr, record_maps)) {
         user_resid = prob.eig_resid;
         // the transport: the group, else the communicator (reduce_fn is ignored beside one), else the callbacks
         if (grp) comm.reset(new GroupComm(*grp, grp_rank, opt.host_wait_spin != 0));
@@ -442,6 +463,15 @@ public:
         block_pool.reset();
     }
     void run();
+    // run() = setup(); solve().  A model handle (model.hip.hpp) calls setup() once and then, per solve, reset_for_solve() --
+    // every member a solve writes back at the value setup() left -- and solve()
+    void setup();
+    void solve();
+    void reset_for_solve();
+    void reset_eigwork(EigWork& W);
+    void restore_cert_data();
+    void release_host_threads();
+    double t_init0 = 0;             // start of what stats.init_time counts
     // the phases of run(), in its order (pdhg_loop.hip.hpp)
     void check_run_options();
     void init_parameters();
@@ -635,6 +665,7 @@ public:
     void start_rocsolver_warmup();
 
 private:
+    friend struct ::proxsdp_model;
     // device state
     DevBuf<double> xbuf[2], Mtybuf[2], ybuf[2], Mxbuf[2], c_d, bh_d, part, scal;
     DevBuf<int> csr_ptr, csr_col, csc_ptr, csc_row;
@@ -796,6 +827,7 @@ private:
     void certificate_parameters();
     void bump_rank(int idx);
     std::vector<double> b_host, h_host, c_host;   // current (possibly zeroed by a certificate search)
+    bool cert_zeroed_c = false, cert_zeroed_bh = false;   // ... and with them c_d / cS_d, bh_d: reset_for_solve uploads them again
     bool have_snapshot = false;
     // support-aware vector passes
     bool use_support = false;
@@ -803,6 +835,7 @@ private:
     // row on its owner only), as the support path's always does; a solve that is not sharded keeps the null pointer
     bool general_row_weights = false;
     int ns = 0, rstride = 0, n_res_wg = 0;
+    std::vector<int> supp_h;                    // the support list as uploaded (upload_support)
     std::vector<int> tile_base;                 // first residual-partial slot of each PSD block
     DevBuf<int> supp_d;
     DevBuf<unsigned> mask_d;

@@ -29,6 +29,7 @@ class Optimizer:
         self.options = binding.default_options()
         self.sol = None
         self.problem = None
+        self.model = None                  # binding.Model kept by optimize(..., keep_model=True)
         for k, v in kwargs.items():
             self.set_attribute(k, v)
 
@@ -66,7 +67,7 @@ class Optimizer:
     # -- _optimize!
     def optimize(self, problem, eig_resid=None, trace_capacity=0, reduce=None, coupling=None, index_base=0,
                  nccl_comm=None, resume=None, capture_iteration=None, shards=None, device_ids=None, owners=None,
-                 soc_owners=None, free_owners=None, factors=False, start=None, device_out=False):
+                 soc_owners=None, free_owners=None, factors=False, start=None, device_out=False, keep_model=False):
         """start: warm start (binding.solve: proxsdp_hip_solve_from) -- a dict (primal, dual_eq, dual_in, factors,
         target_rank, primal_step, beta; all in the units of a result) or a previous result of this optimizer; combines with
         factors=, not with shards=k, the state seam or a shard.
@@ -77,11 +78,23 @@ class Optimizer:
         options.device_id); the result is the whole model's, the per-shard stats are kept in `self.shard_stats`.
         device_out=True: the result's vectors are float64 torch tensors on the solve's device (binding.solve:
         proxsdp_hip_solve_device), and the getters return what the result holds; start= then also takes CUDA tensors or a
-        device result.  Not with shards=k, the state seam or a shard."""
+        device result.  Not with shards=k, the state seam or a shard.
+        keep_model=True: the solve runs on a binding.Model that stays on this optimizer (`self.model`), set up on the
+        device; reoptimize() then replaces data of the same shape and solves again without that set-up.  The result is the
+        one optimize() returns without the keyword.  Not with shards=k, the state seam or a shard."""
         self.empty()
         self.problem = problem
         self.shard_stats = None
-        if shards is not None:
+        if self.model is not None:                         # (a kept model belongs to the problem it was built for)
+            self.model.close()
+            self.model = None
+        if keep_model:
+            if (shards is not None or reduce is not None or coupling is not None or nccl_comm or resume is not None or
+                    capture_iteration is not None):
+                raise ValueError("keep_model=True: the model must be whole, and there is no state seam")
+            self.model = binding.Model(problem, self.options, eig_resid=eig_resid, index_base=index_base)
+            sol = self.model.solve(start=start, factors=factors, device_out=device_out, trace_capacity=trace_capacity)
+        elif shards is not None:
             if reduce is not None or coupling is not None or nccl_comm or resume is not None or capture_iteration is not None:
                 raise ValueError("shards=...: the model must be whole (no reduce / coupling / nccl_comm) and there is no state seam")
             if factors is not False and factors is not None:
@@ -101,6 +114,23 @@ class Optimizer:
         sign = -1.0 if problem.max_sense else 1.0          # :336-337
         sol.objval = sign * sol.objval + problem.objective_constant
         sol.dual_objval = sign * sol.dual_objval + problem.objective_constant
+        self.sol = sol
+        return sol
+
+    def reoptimize(self, c=None, b=None, h=None, A_values=None, G_values=None, start=None, factors=False, device_out=False,
+                   trace_capacity=0):
+        """After optimize(..., keep_model=True): replace data of the same shape (binding.Model.update: c, b, h as
+        problem.c / .b / .h hold them -- c in the minimisation form, already sign-flipped for a max_sense problem --,
+        A_values / G_values = the stored entries in sorted CSC order) and solve again on the kept model.  The sign and
+        constant fix-up of optimize() applies: a max_sense problem keeps its sign."""
+        if getattr(self, "model", None) is None:
+            raise ValueError("reoptimize() needs optimize(..., keep_model=True) first")
+        if any(v is not None for v in (c, b, h, A_values, G_values)):
+            self.model.update(c=c, b=b, h=h, A_values=A_values, G_values=G_values)
+        sol = self.model.solve(start=start, factors=factors, device_out=device_out, trace_capacity=trace_capacity)
+        sign = -1.0 if self.problem.max_sense else 1.0
+        sol.objval = sign * sol.objval + self.problem.objective_constant
+        sol.dual_objval = sign * sol.dual_objval + self.problem.objective_constant
         self.sol = sol
         return sol
 
