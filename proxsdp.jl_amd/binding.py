@@ -704,6 +704,61 @@ def _start_struct(n, p, m, sides, start):
     return S, arr
 
 
+def _ref(x):
+    return C.byref(x) if x is not None else None
+
+
+class _SolveCall:
+    """What ONE call into a solve entry marshals beside problem and options, and the SolveResult made of it afterwards: the
+    proxsdp_result with its trace, the six vectors as host arrays or (device_out) as tensors on cuda:<o.device_id>, the start
+    split into its host part and its CUDA tensors, the factors struct.  R, st, sd, F, out are what the entry takes (byref,
+    or None where nothing was asked for); run() makes the call.  torch is imported only when tensors are involved."""
+
+    def __init__(self, n, p, m, sides, o, start=None, factors=False, primal=True, device_out=False):
+        self.dims, self.sides, self.dev_id = (n, p, m), sides, int(o.device_id)
+        lens = (n, n, p, m, p, m)
+        self.trace = np.zeros((max(o.trace_capacity, 1), TRACE_COLS))
+        self._R = Result()
+        self._R.trace = _p(self.trace)
+        self.torch = None
+        if device_out or _start_on_device(start):
+            import torch
+            self.torch = torch
+        self._keep = []                                      # what the structs point to
+        out = None
+        if device_out:
+            self.arrays = [self.torch.empty(k, dtype=self.torch.float64, device=f"cuda:{self.dev_id}") for k in lens]
+            if not primal:
+                self.arrays[0] = None
+            names = ("primal", "dual_cone", "dual_eq", "dual_in", "slack_eq", "slack_in")
+            out = _device_vectors(self.dev_id, **{nm: (t, k) for nm, t, k in zip(names, self.arrays, lens)})
+        else:
+            host = [np.zeros(max(k, 1)) for k in lens]
+            R = self._R
+            R.primal, R.dual_cone, R.dual_eq, R.dual_in, R.slack_eq, R.slack_in = [_p(a) for a in host]
+            self.arrays = [a[:k] for a, k in zip(host, lens)]
+            if not primal:
+                R.primal = self.arrays[0] = None
+        st = sd = F = self._farr = None
+        if start is not None:
+            hstart, sd, dev = _split_device_start(start, n, p, m, self.dev_id)
+            st, sarr = _start_struct(n, p, m, sides, hstart)
+            self._keep += [dev, sarr]
+        if factors is not False and factors is not None:
+            F, self._farr = _factors_struct(sides, factors)
+        self._structs = (st, sd, F, out)
+        self.R, self.st, self.sd, self.F, self.out = C.byref(self._R), _ref(st), _ref(sd), _ref(F), _ref(out)
+
+    def run(self, entry, *args):
+        if self.torch is not None:
+            self.torch.cuda.synchronize(self.dev_id)         # the library runs on its own stream
+        _check(entry(*args))
+        res = SolveResult(self._R, *self.dims, self.arrays, self.trace)
+        if self._farr is not None:
+            res.psd_factors = _factors_list(self.sides, self._farr)
+        return res
+
+
 def start_point(prob, options=None, start=None, index_base=0, eig_resid=None):
     """proxsdp_hip_start_point: the "Init" section and the start path of a warm-started solve, nothing more.  Returns the
     solver's internal x, Mty (n), y, Mx (p + m), target_rank, the scalars primal_step, primal_step_old, dual_step, beta,
@@ -755,11 +810,14 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
     solve(p2, start=solve(p1, device_out=True, factors=True), device_out=True) chains with no n-vector on the host.  The
     library works on its own stream: the device is synchronised before tensors are handed in, and the call returns after
     its writes have completed.  Not with resume / capture_iteration / reduce / coupling / nccl_comm."""
-    if device_out or _start_on_device(start):
+    on_device = device_out or _start_on_device(start)        # proxsdp_hip_solve_device: tensors out and / or in
+    if on_device:
         if resume is not None or capture_iteration is not None or reduce is not None or coupling is not None or nccl_comm:
             raise ValueError("device vectors cannot be combined with the state seam or a block-sharded solve")
-        return _solve_device(prob, options, eig_resid, trace_capacity, index_base, factors, primal, start, device_out)
+        import torch                                         # (lazily: the host paths do not need it; before lib(), see there)
     L = lib()
+    if on_device and not torch.cuda.is_available():
+        raise RuntimeError("torch sees no GPU: import torch before the first call into the library (see binding.lib)")
     if start is not None and (resume is not None or capture_iteration is not None or reduce is not None or
                               coupling is not None or nccl_comm):
         raise ValueError("start cannot be combined with the state seam or a block-sharded solve")
@@ -808,101 +866,24 @@ def solve(prob, options=None, eig_resid=None, trace_capacity=0, reduce=None, cou
             M.keep.append(cbv)
             M.P.reduce_vec_fn = C.cast(cbv, C.c_void_p)
             M.P.reduce_vec_on_device = 1 if coupling.get("on_device") else 0
-    n, p, m = M.P.n, M.P.p, M.P.m
-    arrays = [np.zeros(max(k, 1)) for k in (n, n, p, m, p, m)]
-    trace = np.zeros((max(o.trace_capacity, 1), TRACE_COLS))
-    R = Result()
-    R.primal, R.dual_cone, R.dual_eq, R.dual_in, R.slack_eq, R.slack_in = [_p(a) for a in arrays]
-    R.trace = _p(trace)
-    if not primal:
-        R.primal = None
-    st = None
-    if start is not None:
-        st, sarr = _start_struct(n, p, m, psd_sides(prob), start)
-    if factors is not False and factors is not None:
-        sides = psd_sides(prob)
-        F, farr = _factors_struct(sides, factors)
-        if st is not None:
-            _check(L.proxsdp_hip_solve_from(C.byref(M.P), C.byref(o), C.byref(R), C.byref(st), C.byref(F)))
-        else:
-            _check(L.proxsdp_hip_solve_factored(C.byref(M.P), C.byref(o), C.byref(R), C.byref(F)))
-        arrays = [a[:k] for a, k in zip(arrays, (n, n, p, m, p, m))]
-        if not primal:
-            arrays[0] = None
-        out = SolveResult(R, n, p, m, arrays, trace)
-        out.psd_factors = _factors_list(sides, farr)
-        return out
+    K = _SolveCall(int(M.P.n), int(M.P.p), int(M.P.m), psd_sides(prob), o, start, factors, primal, device_out)
+    if on_device:
+        return K.run(L.proxsdp_hip_solve_device, C.byref(M.P), C.byref(o), K.R, K.st, K.sd, K.F, K.out)
+    if K.F is not None and K.st is None:
+        return K.run(L.proxsdp_hip_solve_factored, C.byref(M.P), C.byref(o), K.R, K.F)
+    if K.st is not None:
+        return K.run(L.proxsdp_hip_solve_from, C.byref(M.P), C.byref(o), K.R, K.st, K.F)
     if resume is None and capture_iteration is None:
-        if st is not None:
-            _check(L.proxsdp_hip_solve_from(C.byref(M.P), C.byref(o), C.byref(R), C.byref(st), None))
-        else:
-            _check(L.proxsdp_hip_solve(C.byref(M.P), C.byref(o), C.byref(R)))
-        arrays = [a[:k] for a, k in zip(arrays, (n, n, p, m, p, m))]
-        if not primal:
-            arrays[0] = None
-        return SolveResult(R, n, p, m, arrays, trace)
-    Q, nb = p + m, int(M.P.n_psd)
-    rs = cs = None
+        return K.run(L.proxsdp_hip_solve, C.byref(M.P), C.byref(o), K.R)
+    n, Q, nb = int(M.P.n), int(M.P.p + M.P.m), int(M.P.n_psd)
+    rs = cs = carr = None
     if resume is not None:
         rs, rarr = _state_struct(n, Q, nb, o.convergence_window, state=resume)
     if capture_iteration is not None:
         cs, carr = _state_struct(n, Q, nb, o.convergence_window, iteration=capture_iteration)
-    _check(L.proxsdp_hip_solve_ex(C.byref(M.P), C.byref(o), C.byref(R),
-                                  C.byref(rs) if rs is not None else None, C.byref(cs) if cs is not None else None))
-    arrays = [a[:k] for a, k in zip(arrays, (n, n, p, m, p, m))]
-    out = SolveResult(R, n, p, m, arrays, trace)
+    out = K.run(L.proxsdp_hip_solve_ex, C.byref(M.P), C.byref(o), K.R, _ref(rs), _ref(cs))
     out.state = _state_dict(cs, carr, n, Q, nb) if (cs is not None and cs.ints[3] == 1) else None
     return out
-
-
-def _solve_device(prob, options, eig_resid, trace_capacity, index_base, factors, primal, start, device_out):
-    """solve() through proxsdp_hip_solve_device: device tensors out (device_out) and / or in (CUDA tensors in start)"""
-    import torch                                             # (lazily: the host paths do not need it; before lib(), see there)
-    L = lib()
-    if not torch.cuda.is_available():
-        raise RuntimeError("torch sees no GPU: import torch before the first call into the library (see binding.lib)")
-    o = options if options is not None else default_options()
-    if trace_capacity:
-        o.trace_capacity = int(trace_capacity)
-    M = _Marshalled(prob, eig_resid, index_base)
-    n, p, m = int(M.P.n), int(M.P.p), int(M.P.m)
-    dev_id = int(o.device_id)
-    lens = (n, n, p, m, p, m)
-    names = ("primal", "dual_cone", "dual_eq", "dual_in", "slack_eq", "slack_in")
-    trace = np.zeros((max(o.trace_capacity, 1), TRACE_COLS))
-    R = Result()
-    R.trace = _p(trace)
-    out = None
-    if device_out:
-        tens = [torch.empty(k, dtype=torch.float64, device=f"cuda:{dev_id}") for k in lens]
-        if not primal:
-            tens[0] = None
-        out = _device_vectors(dev_id, **{nm: (t, k) for nm, t, k in zip(names, tens, lens)})
-        arrays = tens
-    else:
-        host = [np.zeros(max(k, 1)) for k in lens]
-        R.primal, R.dual_cone, R.dual_eq, R.dual_in, R.slack_eq, R.slack_in = [_p(a) for a in host]
-        if not primal:
-            R.primal = None
-        arrays = [a[:k] for a, k in zip(host, lens)]
-        if not primal:
-            arrays[0] = None
-    st = sd = None
-    if start is not None:
-        hstart, sd, keep_dev = _split_device_start(start, n, p, m, dev_id)
-        st, sarr = _start_struct(n, p, m, psd_sides(prob), hstart)
-    F = None
-    if factors is not False and factors is not None:
-        sides = psd_sides(prob)
-        F, farr = _factors_struct(sides, factors)
-    torch.cuda.synchronize(dev_id)                           # the library runs on its own stream
-    _check(L.proxsdp_hip_solve_device(C.byref(M.P), C.byref(o), C.byref(R), C.byref(st) if st is not None else None,
-                                      C.byref(sd) if sd is not None else None, C.byref(F) if F is not None else None,
-                                      C.byref(out) if out is not None else None))
-    res = SolveResult(R, n, p, m, arrays, trace)
-    if F is not None:
-        res.psd_factors = _factors_list(sides, farr)
-    return res
 
 
 def _dump_arrays(D, fill):
@@ -1044,47 +1025,8 @@ class Model:
             o.time_limit = float(time_limit)
         if max_iter is not None:
             o.max_iter = int(max_iter)
-        n, p, m = self.n, self.p, self.m
-        dev_id = int(o.device_id)
-        lens = (n, n, p, m, p, m)
-        names = ("primal", "dual_cone", "dual_eq", "dual_in", "slack_eq", "slack_in")
-        trace = np.zeros((max(o.trace_capacity, 1), TRACE_COLS))
-        R = Result()
-        R.trace = _p(trace)
-        out = None
-        use_torch = device_out or _start_on_device(start)
-        if use_torch:
-            import torch
-        if device_out:
-            tens = [torch.empty(k, dtype=torch.float64, device=f"cuda:{dev_id}") for k in lens]
-            if not primal:
-                tens[0] = None
-            out = _device_vectors(dev_id, **{nm: (t, k) for nm, t, k in zip(names, tens, lens)})
-            arrays = tens
-        else:
-            host = [np.zeros(max(k, 1)) for k in lens]
-            R.primal, R.dual_cone, R.dual_eq, R.dual_in, R.slack_eq, R.slack_in = [_p(a) for a in host]
-            if not primal:
-                R.primal = None
-            arrays = [a[:k] for a, k in zip(host, lens)]
-            if not primal:
-                arrays[0] = None
-        st = sd = None
-        if start is not None:
-            hstart, sd, keep_dev = _split_device_start(start, n, p, m, dev_id)
-            st, sarr = _start_struct(n, p, m, self._sides, hstart)
-        F = None
-        if factors is not False and factors is not None:
-            F, farr = _factors_struct(self._sides, factors)
-        if use_torch:
-            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
-        _check(L.proxsdp_hip_model_solve(self._handle(), C.byref(o), C.byref(R), C.byref(st) if st is not None else None,
-                                         C.byref(sd) if sd is not None else None, C.byref(F) if F is not None else None,
-                                         C.byref(out) if out is not None else None))
-        res = SolveResult(R, n, p, m, arrays, trace)
-        if F is not None:
-            res.psd_factors = _factors_list(self._sides, farr)
-        return res
+        K = _SolveCall(self.n, self.p, self.m, self._sides, o, start, factors, primal, device_out)
+        return K.run(L.proxsdp_hip_model_solve, self._handle(), C.byref(o), K.R, K.st, K.sd, K.F, K.out)
 
     # ---- what it holds
     def info(self):

@@ -44,26 +44,28 @@ int guarded(F&& f) {
     }
 }
 
+// the caller's options (NULL: the defaults), refused when they are not this ABI's struct
+proxsdp_options checked_options(const proxsdp_options* o) {
+    proxsdp_options d;
+    proxsdp::default_options(&d);
+    if (o) {
+        if (o->struct_size != (int64_t)sizeof(proxsdp_options))
+            throw std::invalid_argument("proxsdp_options.struct_size mismatch (ABI version?)");
+        d = *o;
+    }
+    return d;
+}
+
 // engine-only solver for the kernel-level entry points: one block of side n
 struct Engine {
     proxsdp_result dummy{};
     proxsdp::Solver S;
     Engine(const proxsdp_options* opt, int64_t n, int max_nev)
-        : S(fix(opt), dummy) {
+        : S(checked_options(opt), dummy) {
         if (n < 1 || n > 46340) throw std::invalid_argument("n out of range");
         S.setup_device();
         S.eig.resize(1);
         S.alloc_eigwork(S.eig[0], (int)n, std::min<int>(std::max(max_nev, 2), (int)n));
-    }
-    static proxsdp_options fix(const proxsdp_options* o) {
-        proxsdp_options d;
-        proxsdp::default_options(&d);
-        if (o) {
-            if (o->struct_size != (int64_t)sizeof(proxsdp_options))
-                throw std::invalid_argument("proxsdp_options.struct_size mismatch (ABI version?)");
-            d = *o;
-        }
-        return d;
     }
     void set_resid(const double* resid) {
         proxsdp::EigWork& W = S.eig[0];
@@ -151,33 +153,29 @@ int proxsdp_hip_solve(const proxsdp_problem* prob, const proxsdp_options* opt, p
     return proxsdp_hip_solve_ex(prob, opt, res, nullptr, nullptr);
 }
 
-// both solve entry points: the result before the solve; a trace the caller gave no buffer for is not written
-static proxsdp_options begin_solve(const proxsdp_options* opt, proxsdp_result* res) {
-    proxsdp_options o = Engine::fix(opt);
+// every solve entry point: the result before the solve (begin_solve: with the options; a trace the caller gave no buffer
+// for is not written)
+static void reset_result(proxsdp_result* res) {
     res->status = PROXSDP_STATUS_NOT_CALLED;
     res->trace_rows = 0; res->result_count = 0; res->certificate_found = 0;
     res->status_string[0] = 0;
+}
+static proxsdp_options begin_solve(const proxsdp_options* opt, proxsdp_result* res) {
+    proxsdp_options o = checked_options(opt);
+    reset_result(res);
     if (o.trace_capacity > 0 && !res->trace) o.trace_capacity = 0;
     return o;
 }
 
-// the solve behind proxsdp_hip_solve_ex and proxsdp_hip_solve_factored (fac: validated by the caller, or NULL)
+// the solve behind every one-call entry (req: validated by the caller through check_request, or empty)
 static int solve_impl(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
-                      const proxsdp_state* resume, proxsdp_state* capture, proxsdp_psd_factors* fac,
-                      const proxsdp_start* start = nullptr, bool device_exit = false,
-                      const proxsdp_device_vectors* start_dev = nullptr, proxsdp_device_vectors* out_dev = nullptr) {
+                      const proxsdp::SolveRequest& req) {
     bool comm_aborted = false;
     const int rc = guarded([&]() -> int {
         if (!prob || !res) throw std::invalid_argument("NULL problem or result");
         const proxsdp_options o = begin_solve(opt, res);
         proxsdp::Solver S(*prob, o, *res);
-        S.resume_state = resume;
-        S.capture_state = capture;
-        S.factors_out = fac;
-        S.start = start;
-        S.device_exit = device_exit;
-        S.start_dev = start_dev;
-        S.out_dev = out_dev;
+        S.req = req;
         try {
             S.run();
         } catch (...) {
@@ -198,11 +196,17 @@ static int solve_impl(const proxsdp_problem* prob, const proxsdp_options* opt, p
 
 int proxsdp_hip_solve_ex(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
                          const proxsdp_state* resume, proxsdp_state* capture) {
-    return solve_impl(prob, opt, res, resume, capture, nullptr);
+    proxsdp::SolveRequest req;
+    req.resume_state = resume; req.capture_state = capture;
+    return solve_impl(prob, opt, res, req);
 }
 
-// the solve with the factors of its PSD solution (Solver::extract_factors): every argument is checked here, on the host,
-// before a solver -- and with it the device -- exists
+// ---- what a request carries is checked here, on the host, before a solver -- and with it the device -- exists
+static bool is_shard(const proxsdp_problem* prob) {
+    return prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0;
+}
+
+// the factors of the PSD solution (proxsdp_psd_factors; Solver::extract_factors)
 static void check_factors_arg(const proxsdp_problem* prob, const proxsdp_result* res, const proxsdp_psd_factors* fac) {
         if (!prob || !res || !fac) throw std::invalid_argument("NULL problem, result or factors");
         if (fac->struct_size != (int64_t)sizeof(proxsdp_psd_factors))
@@ -227,18 +231,9 @@ static void check_factors_arg(const proxsdp_problem* prob, const proxsdp_result*
                 throw std::invalid_argument("proxsdp_psd_factors: vec_ptr / val_ptr span too small for cap");
         }
         if (any && (!fac->vectors || !fac->values)) throw std::invalid_argument("proxsdp_psd_factors: NULL vectors / values");
-        if (prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0)
-            throw std::domain_error("proxsdp_hip_solve_factored does not serve a shard of a block-sharded solve");
 }
 
-int proxsdp_hip_solve_factored(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
-                               proxsdp_psd_factors* fac) {
-    const int rc = guarded([&]() -> int { check_factors_arg(prob, res, fac); return 0; });
-    if (rc != 0) return rc;
-    return solve_impl(prob, opt, res, nullptr, nullptr, fac);
-}
-
-// ---- warm start (proxsdp_start): every argument is checked here, on the host, before a solver -- and with it the device -- exists
+// the warm start (proxsdp_start)
 static void check_start_arg(const proxsdp_problem* prob, const proxsdp_start* st) {
     if (!prob) throw std::invalid_argument("NULL problem");
     if (!st) return;
@@ -283,24 +278,11 @@ static void check_start_arg(const proxsdp_problem* prob, const proxsdp_start* st
     if ((st->primal && !all_finite(st->primal, prob->n)) || (st->dual_eq && !all_finite(st->dual_eq, prob->p)) ||
         (st->dual_in && !all_finite(st->dual_in, prob->m)))
         throw std::invalid_argument("proxsdp_start: non-finite entry in primal / dual_eq / dual_in");
-    if (prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0)
-        throw std::domain_error("a warm start does not serve a shard of a block-sharded solve");
+    if (is_shard(prob)) throw std::domain_error("a warm start does not serve a shard of a block-sharded solve");
 }
 
-int proxsdp_hip_solve_from(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
-                           const proxsdp_start* start, proxsdp_psd_factors* fac) {
-    const int rc = guarded([&]() -> int {
-        if (!prob || !res) throw std::invalid_argument("NULL problem or result");
-        check_start_arg(prob, start);
-        if (fac) check_factors_arg(prob, res, fac);
-        return 0;
-    });
-    if (rc != 0) return rc;
-    return solve_impl(prob, opt, res, nullptr, nullptr, fac, start);
-}
-
-// ---- solution vectors on the device (proxsdp_device_vectors): checked on the host, before a solver exists, except that the
-// start vectors hold finite numbers (Solver::check_start_dev, a device reduction after set-up)
+// solution vectors on the device (proxsdp_device_vectors): all but that the start vectors hold finite numbers
+// (Solver::check_start_dev, a device reduction after set-up)
 static void check_device_vectors(const proxsdp_device_vectors* v, int32_t device_id, const char* what) {
     if (!v) return;
     if (v->struct_size != (int64_t)sizeof(proxsdp_device_vectors))
@@ -309,44 +291,70 @@ static void check_device_vectors(const proxsdp_device_vectors* v, int32_t device
         throw std::invalid_argument(std::string("proxsdp_device_vectors (") + what + "): device_id is not options.device_id");
 }
 
+// One request against the problem it is for (shape: the problem, or a handle's dimensions and cones): each entry sets the
+// fields it accepts, so one damaged argument is refused with the same code and message at every entry that takes it.
+// device_id: the options' (read only when device vectors are given); entry: named when the problem is a shard.
+static void check_request(const proxsdp_problem* shape, const proxsdp_result* res, int32_t device_id,
+                          const proxsdp::SolveRequest& q, const char* entry) {
+    check_start_arg(shape, q.start);
+    if (q.factors_out) check_factors_arg(shape, res, q.factors_out);
+    check_device_vectors(q.start_dev, device_id, "start");
+    check_device_vectors(q.out_dev, device_id, "out");
+    if (const proxsdp_device_vectors* d = q.start_dev) {
+        if (d->dual_cone || d->slack_eq || d->slack_in)
+            throw std::invalid_argument("proxsdp_device_vectors (start): dual_cone, slack_eq and slack_in must be NULL");
+        if (q.start && ((q.start->primal && d->primal) || (q.start->dual_eq && d->dual_eq) || (q.start->dual_in && d->dual_in)))
+            throw std::invalid_argument("a start vector is given both on the host (proxsdp_start) and on the device");
+        if (shape->n < 0 || shape->p < 0 || shape->m < 0) throw std::invalid_argument("negative dimension");
+    }
+    if (is_shard(shape)) throw std::domain_error(std::string(entry) + " does not serve a shard of a block-sharded solve");
+}
+
+int proxsdp_hip_solve_factored(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                               proxsdp_psd_factors* fac) {
+    proxsdp::SolveRequest req;
+    req.factors_out = fac;
+    const int rc = guarded([&]() -> int {
+        if (!prob || !res || !fac) throw std::invalid_argument("NULL problem, result or factors");
+        check_request(prob, res, 0, req, "proxsdp_hip_solve_factored");
+        return 0;
+    });
+    return rc != 0 ? rc : solve_impl(prob, opt, res, req);
+}
+
+int proxsdp_hip_solve_from(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
+                           const proxsdp_start* start, proxsdp_psd_factors* fac) {
+    proxsdp::SolveRequest req;
+    req.start = start; req.factors_out = fac;
+    const int rc = guarded([&]() -> int {
+        if (!prob || !res) throw std::invalid_argument("NULL problem or result");
+        check_request(prob, res, 0, req, "proxsdp_hip_solve_from");
+        return 0;
+    });
+    return rc != 0 ? rc : solve_impl(prob, opt, res, req);
+}
+
 int proxsdp_hip_solve_device(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_result* res,
                              const proxsdp_start* start, const proxsdp_device_vectors* start_dev,
                              proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev) {
-    proxsdp_start none{};                                 // start_dev without a start: no factors, cold steps
-    none.struct_size = (int64_t)sizeof(proxsdp_start);
+    proxsdp::SolveRequest req;
+    req.start = start; req.start_dev = start_dev; req.factors_out = fac; req.out_dev = out_dev;
+    req.device_exit = true;
     const int rc = guarded([&]() -> int {
         if (!prob || !res) throw std::invalid_argument("NULL problem or result");
-        check_start_arg(prob, start);
-        if (fac) check_factors_arg(prob, res, fac);
-        const int32_t dev_id = Engine::fix(opt).device_id;
-        check_device_vectors(start_dev, dev_id, "start");
-        check_device_vectors(out_dev, dev_id, "out");
-        if (start_dev) {
-            if (start_dev->dual_cone || start_dev->slack_eq || start_dev->slack_in)
-                throw std::invalid_argument("proxsdp_device_vectors (start): dual_cone, slack_eq and slack_in must be NULL");
-            if (start && ((start->primal && start_dev->primal) || (start->dual_eq && start_dev->dual_eq) ||
-                          (start->dual_in && start_dev->dual_in)))
-                throw std::invalid_argument("a start vector is given both on the host (proxsdp_start) and on the device");
-            if (prob->n < 0 || prob->p < 0 || prob->m < 0) throw std::invalid_argument("negative dimension");
-        }
-        if (prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0)
-            throw std::domain_error("proxsdp_hip_solve_device does not serve a shard of a block-sharded solve");
+        check_request(prob, res, checked_options(opt).device_id, req, "proxsdp_hip_solve_device");
         return 0;
     });
-    if (rc != 0) return rc;
-    return solve_impl(prob, opt, res, nullptr, nullptr, fac, (!start && start_dev) ? &none : start, true, start_dev, out_dev);
+    return rc != 0 ? rc : solve_impl(prob, opt, res, req);
 }
 
 // ---- a model that stays set up on the device (model.hip.hpp): what is decided on the host is decided here, before a device call
-static bool is_shard(const proxsdp_problem* prob) {
-    return prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0;
-}
 
 int proxsdp_hip_model_create(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_model** out) {
     return guarded([&]() -> int {
         if (!prob || !out) throw std::invalid_argument("NULL problem or handle");
         *out = nullptr;
-        const proxsdp_options o = Engine::fix(opt);
+        const proxsdp_options o = checked_options(opt);
         if (is_shard(prob)) throw std::domain_error("proxsdp_hip_model_create does not serve a shard of a block-sharded solve");
         if (prob->M_dense != nullptr)
             throw std::domain_error("proxsdp_hip_model_create does not serve M_dense: the matrix is borrowed, a handle would outlive the loan");
@@ -418,7 +426,7 @@ int proxsdp_hip_model_solve(proxsdp_model* mdl, const proxsdp_options* run_opt, 
         if (!mdl || !res) throw std::invalid_argument("NULL handle or result");
         proxsdp_options run;
         if (run_opt) {
-            run = Engine::fix(run_opt);
+            run = checked_options(run_opt);
             // every option but the ones that shape nothing in the set-up must be create's
             static const char* const free_fields[] = {"time_limit", "max_iter", "log_verbose", "log_freq", "warn_on_limit", "trace_capacity"};
             for (const proxsdp::OptEntry& e : proxsdp::option_table()) {
@@ -431,22 +439,12 @@ int proxsdp_hip_model_solve(proxsdp_model* mdl, const proxsdp_options* run_opt, 
                                                 " differs from the options of proxsdp_hip_model_create");
             }
         }
-        const proxsdp_problem* shape = &mdl->shape;
-        check_start_arg(shape, start);
-        if (fac) check_factors_arg(shape, res, fac);
-        check_device_vectors(start_dev, mdl->opt0.device_id, "start");
-        check_device_vectors(out_dev, mdl->opt0.device_id, "out");
-        if (start_dev) {
-            if (start_dev->dual_cone || start_dev->slack_eq || start_dev->slack_in)
-                throw std::invalid_argument("proxsdp_device_vectors (start): dual_cone, slack_eq and slack_in must be NULL");
-            if (start && ((start->primal && start_dev->primal) || (start->dual_eq && start_dev->dual_eq) ||
-                          (start->dual_in && start_dev->dual_in)))
-                throw std::invalid_argument("a start vector is given both on the host (proxsdp_start) and on the device");
-        }
-        res->status = PROXSDP_STATUS_NOT_CALLED;
-        res->trace_rows = 0; res->result_count = 0; res->certificate_found = 0;
-        res->status_string[0] = 0;
-        mdl->solve(t_entry, run_opt ? &run : nullptr, res, start, start_dev, fac, out_dev);
+        proxsdp::SolveRequest req;
+        req.start = start; req.start_dev = start_dev; req.factors_out = fac; req.out_dev = out_dev;
+        req.device_exit = true;
+        check_request(&mdl->shape, res, mdl->opt0.device_id, req, "proxsdp_hip_model_solve");
+        reset_result(res);
+        mdl->solve(t_entry, run_opt ? &run : nullptr, res, req);
         return 0;
     });
 }
@@ -469,8 +467,7 @@ int proxsdp_hip_exit_vectors(const proxsdp_problem* prob, const proxsdp_options*
     return guarded([&]() -> int {
         if (!prob) throw std::invalid_argument("NULL problem");
         if ((prob->n > 0 && !x) || (prob->p + prob->m > 0 && !y)) throw std::invalid_argument("exit vectors: NULL iterate");
-        if (prob->reduce_fn || prob->reduce_vec_fn || prob->nccl_comm || prob->n_coupling != 0)
-            throw std::domain_error("proxsdp_hip_exit_vectors does not serve a shard of a block-sharded solve");
+        check_request(prob, nullptr, 0, proxsdp::SolveRequest{}, "proxsdp_hip_exit_vectors");
         proxsdp_result dummy{};
         const proxsdp_options o = begin_solve(opt, &dummy);
         proxsdp::Solver S(*prob, o, dummy);
@@ -483,7 +480,9 @@ int proxsdp_hip_start_point(const proxsdp_problem* prob, const proxsdp_options* 
                             proxsdp_state* out) {
     return guarded([&]() -> int {
         if (!prob || !out) throw std::invalid_argument("NULL problem or state");
-        check_start_arg(prob, start);
+        proxsdp::SolveRequest req;
+        req.start = start; req.start_out = out;
+        check_request(prob, nullptr, 0, req, "proxsdp_hip_start_point");
         if (out->struct_size != (int64_t)sizeof(proxsdp_state)) throw std::invalid_argument("proxsdp_state.struct_size mismatch");
         if (out->n != prob->n || out->Q != prob->p + prob->m || out->n_psd != prob->n_psd)
             throw std::invalid_argument("start point: n / Q / n_psd do not match the problem");
@@ -492,8 +491,7 @@ int proxsdp_hip_start_point(const proxsdp_problem* prob, const proxsdp_options* 
         proxsdp_result dummy{};
         const proxsdp_options o = begin_solve(opt, &dummy);
         proxsdp::Solver S(*prob, o, dummy);
-        S.start = start;
-        S.start_out = out;
+        S.req = req;
         S.run();
         return 0;
     });
@@ -739,7 +737,7 @@ int proxsdp_hip_psd_project(const double* packed_in, int64_t n, int32_t target_r
     return guarded([&]() -> int {
         if (!packed_in || !packed_out) throw std::invalid_argument("NULL buffer");
         if (target_rank < 1) throw std::invalid_argument("target_rank < 1");
-        proxsdp_options o = Engine::fix(opt);
+        proxsdp_options o = checked_options(opt);
         if (mode == 1) { o.full_eig_decomp = 1; o.full_eig_lanczos = 0; o.full_eig_sign = 0; }
         // mode 4: full_eig! by the sign-function projection (fp64 MFMA products)
         if (mode == 4) { o.full_eig_decomp = 1; o.full_eig_lanczos = 0; o.full_eig_sign = 1; }
@@ -808,7 +806,7 @@ int proxsdp_hip_full_eig_kernel(const double* packed_in, int64_t n, int32_t sign
                                 int32_t repeat, double* ms, int32_t* out_rank, int64_t* out_products) {
     return guarded([&]() -> int {
         if (!packed_in || !packed_out) throw std::invalid_argument("NULL buffer");
-        proxsdp_options o = Engine::fix(nullptr);
+        proxsdp_options o = checked_options(nullptr);
         o.full_eig_decomp = 1; o.full_eig_lanczos = 0; o.full_eig_sign = sign < 0 ? -1 : (sign ? 1 : 0);   // (-1: the solver's own choice of engine)
         if (sign >= 100) o.sign_start_row = sign - 100;
         Engine E(&o, n, 2);
@@ -900,7 +898,7 @@ int proxsdp_hip_reconstruct_kernel(const double* Z, const double* lambda, int64_
     return guarded([&]() -> int {
         if ((r > 0 && (!Z || !lambda)) || !packed_out) throw std::invalid_argument("NULL buffer");
         if (r < 0) throw std::invalid_argument("r < 0");
-        proxsdp_options o = Engine::fix(nullptr);
+        proxsdp_options o = checked_options(nullptr);
         o.reconstruct_mfma = mfma;
         Engine E(&o, n, 2);
         proxsdp::Solver& S = E.S;
@@ -1041,7 +1039,7 @@ int proxsdp_hip_reconstruct_fused(proxsdp_reconstruct_fused* t) {
             throw std::invalid_argument("reconstruct: the mask does not cover the block");
         const int nt = proxsdp::ceil_div(t->n, proxsdp::dev::TILE);
         if (t->respart_cap < 2 * (int64_t)proxsdp::tile_grid(nt)) throw std::invalid_argument("reconstruct: respart_cap < 2 grid");
-        proxsdp_options o = Engine::fix(nullptr);
+        proxsdp_options o = checked_options(nullptr);
         o.reconstruct_mfma = t->mfma;
         Engine E(&o, t->n, 2);
         E.S.test_reconstruct_fused(*t);
@@ -1065,7 +1063,7 @@ int proxsdp_hip_rotate(proxsdp_rotation* t) {
         const int kd = std::max(t->K, std::max(t->Kv, t->out_cols) - 1);
         if (t->wide && kd <= proxsdp::dev::LZ_KMAX) throw std::invalid_argument("rotation: wide = 1 needs the wide workspace (Krylov dimension > 255)");
         if (kd > (t->wide ? proxsdp::dev::LZW_MAXK - 1 : proxsdp::dev::LZ_KMAX)) throw std::invalid_argument("rotation: Krylov dimension out of range");
-        proxsdp_options o = Engine::fix(nullptr);
+        proxsdp_options o = checked_options(nullptr);
         o.lanczos_wide_krylov = t->wide;
         o.eigsolver_min_lanczos = kd;
         Engine E(&o, t->n, 2);
@@ -1102,7 +1100,7 @@ int proxsdp_hip_dense_scaling(const proxsdp_problem* prob, const proxsdp_options
     return guarded([&]() -> int {
         if (!prob) throw std::invalid_argument("NULL problem");
         if (!prob->M_dense) throw std::invalid_argument("proxsdp_hip_dense_scaling needs a dense A (M_dense)");
-        proxsdp_options o = Engine::fix(opt);
+        proxsdp_options o = checked_options(opt);
         o.trace_capacity = 0;
         proxsdp_result dummy{};
         proxsdp::Solver S(*prob, o, dummy);
@@ -1420,7 +1418,7 @@ int proxsdp_host_equilibrate_rowsums(const double* rowsums, int64_t Q, int64_t n
                                      double* E, double* d) {
     return guarded([&]() -> int {
         if (Q <= 0 || n <= 0 || !rowsums || !E || !d) throw std::invalid_argument("invalid argument");
-        const proxsdp_options o = Engine::fix(opt);
+        const proxsdp_options o = checked_options(opt);
         std::vector<double> Ed;
         proxsdp::equilibrate_rowsums(rowsums, Q, n, o, Ed, *d);
         std::copy(Ed.begin(), Ed.end(), E);

@@ -262,7 +262,7 @@ inline void Solver::cache_solution_device(bool zero_c) {
     exit_device_setup();
     exit_form_vectors(zero_c);
     // the factors of this snapshot's PSD blocks, before the lambda_min Lanczos below reuses the blocks' workspaces
-    if (factors_out) {
+    if (req.factors_out) {
         std::vector<double> one_vals(P.blocks.size(), 0.0);
         if (!xd.ones.empty()) {
             const int cnt = (int)xd.ones.size();
@@ -292,7 +292,7 @@ inline void Solver::cache_solution_device(bool zero_c) {
         sdp_viol = std::max(sdp_viol, -std::min(0.0, mn));
     }
     const double dfeas = std::max({sdp_viol, viol[0], viol[3]});
-    exit_write_vectors(out_dev, res.primal, res.dual_cone, res.dual_eq, res.dual_in, res.slack_eq, res.slack_in);
+    exit_write_vectors(req.out_dev, res.primal, res.dual_cone, res.dual_eq, res.dual_in, res.slack_eq, res.slack_in);
     finish_snapshot(dfeas);
     st.exit_time += now_s() - t0;
 }
@@ -300,7 +300,7 @@ inline void Solver::cache_solution_device(bool zero_c) {
 // proxsdp_hip_solve_device: the finite check of the start vectors the caller holds on the device (the host entry checks
 // every host array before the device exists; this one check needs it)
 inline void Solver::check_start_dev() {
-    const proxsdp_device_vectors& d = *start_dev;
+    const proxsdp_device_vectors& d = *req.start_dev;
     const double* v[3] = {d.primal, d.dual_eq, d.dual_in};
     const int64_t len[3] = {P.n, P.p, P.m};
     const char* name[3] = {"primal", "dual_eq", "dual_in"};

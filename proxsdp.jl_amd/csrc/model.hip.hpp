@@ -47,7 +47,7 @@ struct proxsdp_model {
         for (const BlockInfo& B : s.P.blocks) psd_ptr.push_back(psd_ptr.back() + B.N);
         shape.n = s.P.n; shape.p = s.P.p; shape.m = s.P.m;
         shape.n_psd = (int64_t)s.P.blocks.size(); shape.psd_ptr = psd_ptr.data();
-        s.device_exit = true;
+        s.req.device_exit = true;
         s.setup();
         s.exit_device_setup();
         const Prep& P = s.P;
@@ -86,9 +86,9 @@ struct proxsdp_model {
         (void)hipGetLastError();
     }
 
-    // run: the fields of the options a solve may change, already validated against opt0 (null: opt0's)
-    void solve(double t_entry, const proxsdp_options* run, proxsdp_result* res, const proxsdp_start* start,
-               const proxsdp_device_vectors* start_dev, proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev) {
+    // run: the fields of the options a solve may change, already validated against opt0 (null: opt0's); request: checked
+    // by the entry, device_exit set
+    void solve(double t_entry, const proxsdp_options* run, proxsdp_result* res, const proxsdp::SolveRequest& request) {
         using namespace proxsdp;
         Solver& s = *S;
         PX_HIP(hipSetDevice(opt0.device_id));
@@ -99,22 +99,15 @@ struct proxsdp_model {
         if (s.opt.trace_capacity > 0 && !res->trace) s.opt.trace_capacity = 0;
         scratch = *res;
         s.time0 = t_entry; s.t_init0 = t_entry;
-        proxsdp_start none{};                               // start_dev without a start: no factors, cold steps
-        none.struct_size = (int64_t)sizeof(proxsdp_start);
         struct Leave {                                      // no thread of the handle outlives the call
             proxsdp_model& m; bool ok = false;
             ~Leave() { if (!ok) m.drain(); m.S->release_host_threads(); }
         } leave{*this};
         s.reset_for_solve();
-        s.factors_out = fac;
-        s.start = (!start && start_dev) ? &none : start;
-        s.start_dev = start_dev;
-        s.out_dev = out_dev;
-        s.device_exit = true;
+        s.req = request;
         s.start_block_workers();
         s.solve();
         PX_HIP(hipStreamSynchronize(s.stream));
-        s.start = nullptr; s.start_dev = nullptr; s.factors_out = nullptr; s.out_dev = nullptr;
         leave.ok = true;
         *res = scratch;
         ++solves;

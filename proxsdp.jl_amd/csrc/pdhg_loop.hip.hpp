@@ -568,7 +568,7 @@ inline void Solver::cache_solution(const std::vector<double>& cvec) {
         for (size_t k = 0; k < coup_rows.size(); ++k) slack[coup_rows[k]] = part_[k];
     }
     // the factors of this snapshot's PSD blocks, before the lambda_min Lanczos below reuses the blocks' workspaces
-    if (factors_out) {
+    if (req.factors_out) {
         std::vector<double> one_vals(P.blocks.size(), 0.0);
         for (size_t idx = 0; idx < P.blocks.size(); ++idx) if (P.blocks[idx].n == 1) one_vals[idx] = x[P.blocks[idx].off];
         extract_factors(one_vals);
@@ -594,7 +594,7 @@ inline void Solver::cache_solution(const std::vector<double>& cvec) {
 // dsyevd of the block, pairs with lambda > 0 kept.  Either way the cap[k] largest pairs go out, descending, and
 // k_factor_residual measures them against the block: resid reports what the pairs miss, truncation included.
 inline void Solver::extract_factors(const std::vector<double>& one_vals) {
-    proxsdp_psd_factors& F = *factors_out;
+    proxsdp_psd_factors& F = *req.factors_out;
     for (size_t idx = 0; idx < P.blocks.size(); ++idx) {
         const BlockInfo& B = P.blocks[idx];
         const int64_t cap = F.cap[idx];
@@ -1020,9 +1020,9 @@ inline void Solver::check_state_shape(const proxsdp_state& s, const char* what) 
     if (sharded() || P.equilibrated) throw std::domain_error("state capture / resume: not with a block-sharded solve or equilibration");
 }
 
-// continue from resume_state: called after the "Init" section built every buffer; overwrites the initial point
+// continue from req.resume_state: called after the "Init" section built every buffer; overwrites the initial point
 inline void Solver::apply_resume() {
-    const proxsdp_state& s = *resume_state;
+    const proxsdp_state& s = *req.resume_state;
     check_state_shape(s, "resume");
     xbuf[xc].upload(s.x, P.n, stream);
     ybuf[yc].upload(s.y, P.Q, stream);
@@ -1060,7 +1060,7 @@ inline void Solver::apply_resume() {
 // as the caller holds it and brought into the solver's order and scale by k_start_gather; a factored cone goes through the
 // solver's own reconstruction launch straight into the iterate; M x and M'y come from the solver's product launches.
 inline void Solver::apply_start() {
-    const proxsdp_start& s = *start;
+    const proxsdp_start& s = *req.start_point();
     const size_t nb = P.blocks.size();
     auto given = [&](size_t idx) -> long long { return s.n_psd > 0 ? (long long)s.rank[idx] : -1; };
     // target ranks and step scalars: they hold for a start without a point as well
@@ -1074,10 +1074,11 @@ inline void Solver::apply_start() {
     if (s.primal_step > 0.0) { primal_step = s.primal_step; primal_step_old = primal_step; dual_step = primal_step; }
     if (s.beta > 0.0) beta = s.beta;
     // vectors the caller holds on the device (proxsdp_hip_solve_device): read where they are
-    const double* d_primal = start_dev ? start_dev->primal : nullptr;
-    const double* d_eq = start_dev ? start_dev->dual_eq : nullptr;
-    const double* d_in = start_dev ? start_dev->dual_in : nullptr;
-    if (start_dev) check_start_dev();
+    const proxsdp_device_vectors* sd = req.start_dev;
+    const double* d_primal = sd ? sd->primal : nullptr;
+    const double* d_eq = sd ? sd->dual_eq : nullptr;
+    const double* d_in = sd ? sd->dual_in : nullptr;
+    if (sd) check_start_dev();
     // no point given: the cold vectors stay (x_old = 0)
     if (!s.primal && !s.dual_eq && !s.dual_in && !d_primal && !d_eq && !d_in && !any_fac) return;
     start_active = true;
@@ -1169,7 +1170,7 @@ inline void Solver::apply_start() {
 
 // proxsdp_hip_start_point: the internal vectors after the start path
 inline void Solver::write_start_point() {
-    proxsdp_state& s = *start_out;
+    proxsdp_state& s = *req.start_out;
     PX_HIP(hipStreamSynchronize(stream));
     xbuf[xc].download(s.x, P.n, stream);
     if (P.Q > 0) { ybuf[yc].download(s.y, P.Q, stream); Mxbuf[mxc].download(s.Mx, P.Q, stream); }
@@ -1191,9 +1192,9 @@ inline void Solver::write_start_point() {
     s.iteration = 0;
 }
 
-// write capture_state: the stream is idle (every iteration ends with a synchronisation)
+// write req.capture_state: the stream is idle (every iteration ends with a synchronisation)
 inline void Solver::write_capture() {
-    proxsdp_state& s = *capture_state;
+    proxsdp_state& s = *req.capture_state;
     if (certificate_search) return;          // (the seam does not carry a certificate search: ints[3] stays 0, the solve goes on)
     PX_HIP(hipStreamSynchronize(stream));
     harvest_small_ranks();
@@ -1478,7 +1479,7 @@ inline void Solver::cert_dual_infeas() {
     cert_zeroed_bh = true;
     certificate_parameters();
 }
-inline void Solver::snapshot() { if (device_exit) cache_solution_device(false); else cache_solution(P.c_orig); }
+inline void Solver::snapshot() { if (req.device_exit) cache_solution_device(false); else cache_solution(P.c_orig); }
 
 // A stop rule fired: record its reason.  True: the loop stops.  False: it goes on -- with certificate search on and no
 // search running yet, the search for a certificate of `kind` starts here (data zeroed, limits raised, the point
@@ -1694,7 +1695,7 @@ inline Solver::Loop Solver::after_iteration(long long k) {
 // after the loop: pending capture, event harvest, the solution (pdhg.jl:486-529), debug summaries
 inline void Solver::finish() {
     PX_HIP(hipStreamSynchronize(stream));
-    if (capture_state && capture_state->ints[3] == 0 && iter == capture_state->iteration) write_capture();
+    if (req.capture_state && req.capture_state->ints[3] == 0 && iter == req.capture_state->iteration) write_capture();
     for (EigWork& W : eig) harvest_full_eig_events(W);
     merge_block_stats();
     st.loop_time = now_s() - loop_t0;
@@ -1703,7 +1704,7 @@ inline void Solver::finish() {
     // ---- results (pdhg.jl:486-529)
     if (opt.certificate_search && certificate_search) {
         if (certificate_found) {
-            if (device_exit) {
+            if (req.device_exit) {
                 cache_solution_device(stop_reason == 6);
             } else {
                 std::vector<double> cc(P.c_orig);
@@ -1711,7 +1712,7 @@ inline void Solver::finish() {
                 cache_solution(cc);
             }
         }
-    } else if (device_exit) {
+    } else if (req.device_exit) {
         cache_solution_device(false);
     } else {
         cache_solution(P.c_orig);
@@ -1772,17 +1773,17 @@ inline void Solver::solve() {
 
     // ---- where the loop enters: cold, resumed (proxsdp_hip_solve_ex) or from the caller's point (proxsdp_hip_solve_from)
     long long k_first = 1;
-    if (resume_state) { apply_resume(); k_first = resume_state->iteration + 1; }
-    if (start) apply_start();
-    if (start_out) { write_start_point(); return; }
-    if (capture_state) { check_state_shape(*capture_state, "capture"); capture_state->ints[3] = 0; }
+    if (req.resume_state) { apply_resume(); k_first = req.resume_state->iteration + 1; }
+    if (req.start_point()) apply_start();
+    if (req.start_out) { write_start_point(); return; }
+    if (req.capture_state) { check_state_shape(*req.capture_state, "capture"); req.capture_state->ints[3] = 0; }
     st.init_time = now_s() - t_init0;
 
     // ---- "CP loop" (pdhg.jl:145-484)
     loop_t0 = now_s();
     const long long kmax = 2 * max_iter_local;
     for (long long k = k_first; k <= kmax; ++k) {
-        if (capture_state && k == capture_state->iteration + 1 && k > k_first) write_capture();
+        if (req.capture_state && k == req.capture_state->iteration + 1 && k > k_first) write_capture();
         iterate(k);
         if (after_iteration(k) == Loop::stop) break;
     }
@@ -1802,25 +1803,10 @@ inline void Solver::reset_eigwork(EigWork& W) {
         b->zero(stream);
     if (W.resid.n > 0) W.resid.upload(W.resid_host.data(), W.npad, stream);
     if (W.arrow_host.p) std::fill(W.arrow_host.p, W.arrow_host.p + 2 * dev::MAXK, 0.0);
-    W.arrow_p = W.arrow.p;
-    W.ustage_next = 0; W.rot_form = 0; W.rot_launches = 0;
-    W.vals.clear();
-    W.count = 0; W.converged_eigs = 0; W.numiter = 0; W.prev_numiter = 1; W.converged = false;
-    W.F_first = 0; W.F_r = 0;
-    W.have_factors = false; W.use_fop = false;
-    W.xprev = EigWork::XPrev{};
-    W.ritz_ok = false; W.ritz_first = 0; W.ritz_r = 0;
+    static_cast<EigSolveState&>(W) = EigSolveState{};    // every per-solve host member (the rule is at the struct)
+    W.arrow_p = W.arrow.p;                               // (its value comes from the set-up)
+    // owners of buffers, events and a helper pool that stay: only their per-solve fields
     W.split.k1 = 0; W.split.K = 0; W.split.beta = 0.0; W.split.have_first = false; W.split.M.par = nullptr;
-    W.batch_slot = 0;
-    W.b1_rot_K = 0; W.b1_rot_U = nullptr;
-    W.lzrun = LzRun{};
-    W.fel = EigWork::LanczosFullEig{};
-    W.cye_pending = false; W.esv = nullptr;
-    W.lst = proxsdp_stats{};
-    W.mv_iter = 0; W.recon_r = 0;
-    W.fe_pending = false;
-    W.sg_row = -1; W.sg_ok = 16; W.sg_idle = 0; W.sg_hold = 0; W.sg_pending = false;
-    W.sign = EigWork::SignStandIn{};
     W.ev.used = 0; W.evo.used = 0;
 }
 
@@ -1852,25 +1838,11 @@ inline void Solver::restore_cert_data() {
 // (cert_infeas, cert_dual_infeas) come back from the Prep, which a model handle keeps current.
 inline void Solver::reset_for_solve() {
     PX_HIP(hipStreamSynchronize(stream));
+    static_cast<SolveState&>(*this) = SolveState{};      // every per-solve host scalar (the rule is at the struct)
+    req = SolveRequest{};                                // the one place a request is cleared
     init_parameters();                                   // Params, target ranks, histories, time_limit
     reduce_global_constants();                           // the norms may have changed (proxsdp_hip_model_update); max_iter_local
-    primal_step = 0; primal_step_old = 0; dual_step = 0;
-    iter = 0; rank_update = 0; update_cont = 0; stop_reason = 0;
-    stop_reason_string = "Not optimized";
-    dual_feasibility = -1.0;
-    certificate_search = false; certificate_found = false; certificate_search_min_iter = 0;
-    last_trials = 0; lz_matvec_iter = 0; recon_r_iter = 0;
-    equa_feasibility = 0; ineq_feasibility = 0;
-    have_snapshot = false; start_active = false;
-    st = proxsdp_stats{};
-    shard_error = nullptr;
-    dense_ev_used = 0; dense_passes_seen = 0;
-    dbg_batch = BatchDebug{}; dbg_lz = LzDebug{};
-    sigma_max = 0.0; loop_t0 = 0; g_elapsed = 0;
-    g_not_converged_rank = false; g_any_below_full = false;
-    small_pending = false;
     for (int k = 0; k < 2; ++k) { xbuf[k].zero(stream); Mtybuf[k].zero(stream); ybuf[k].zero(stream); Mxbuf[k].zero(stream); }
-    xc = yc = mxc = mtyc = 0;
     restore_cert_data();
     part.zero(stream); scal.zero(stream);
     small_rank.zero(stream);
@@ -1881,7 +1853,6 @@ inline void Solver::reset_for_solve() {
     if (hscal_pin.p) std::fill(hscal_pin.p, hscal_pin.p + 64, 0.0);
     for (int idx : big_blocks) reset_eigwork(eig[idx]);
     batch_ctx.clear();                                   // (the batched runs' buffers come on first use, as in a fresh solve)
-    factors_out = nullptr; start = nullptr; start_dev = nullptr; out_dev = nullptr;
     PX_HIP(hipStreamSynchronize(stream));
 }
 

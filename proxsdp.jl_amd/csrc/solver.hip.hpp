@@ -280,7 +280,61 @@ struct LzRun {
     std::vector<double> erow;
 };
 
-struct EigWork {
+// The host members of a block's workspace that a solve writes.  RULE: declare a per-solve host member of EigWork here, with
+// the value a fresh workspace has as its initialiser, and Solver::reset_eigwork puts it back by assigning a default-constructed
+// EigSolveState.  What the set-up computes (sizes, record pointers, ELL structures, fop_ok, the sign projection's tile shape)
+// belongs in EigWork itself; so does a member whose reset value comes from the set-up (arrow_p), which reset_eigwork names.
+struct EigSolveState {
+    int ustage_next = 0;
+    int rot_form = 0, rot_launches = 0;   // the last rotate_launch: PROXSDP_ROTATE_SCALAR / _MFMA / _WIDE (0: nothing launched), its launches
+    // results of the last call
+    std::vector<double> vals;
+    int count = 0, converged_eigs = 0, numiter = 0, prev_numiter = 1;
+    bool converged = false;
+    int F_first = 0, F_r = 0;
+    bool have_factors = false;                     // x_prev of this block is F[:, F_first .. +F_r) diag(Flam) F'
+    bool use_fop = false;                          // the projection in progress uses the operator form
+    // what else the dispatch (projection.hip.hpp) knows of x_prev; have_factors, F_first / F_r and ritz_ok stay beside the
+    // buffers they describe: the Lanczos drivers read or drop them
+    struct XPrev {
+        bool sparse = true;                        // x_prev is zero off the support (initial iterate)
+        int last_npos = -1;                        // positive eigenvalues found by the last projection of this block
+    } xprev;
+    // a block without the operator form's structures keeps no F: there the last converged Krylov projection's pairs stay
+    // where the run left them -- Z[:, ritz_first .. +ritz_r) and vals[ritz_first ..) -- and ritz_ok says that x_prev of this
+    // block is still their reconstruction: set at the end of that projection, dropped by whatever writes Z / vals (lanczos,
+    // lanczos_batch) or the block (project_block, project_blocks, the exit path's rescale).  Read by extract_factors only.
+    bool ritz_ok = false;
+    int ritz_first = 0, ritz_r = 0;
+    int batch_slot = 0;                            // position of this block in the batched run in progress
+    // one-workgroup cycle kernel (lanczos_block1.hip.hpp): the restart rotation is deferred into the next cycle's launch
+    int b1_rot_K = 0;                             // > 0: a rotation is pending, U (K x kfirst, compact) at b1_rot_U (pinned staging)
+    const double* b1_rot_U = nullptr;
+    LzRun lzrun;                                   // host state of the run in progress (buffers reused across projections)
+    struct LanczosFullEig {                        // full_eig! served by the Lanczos engine (full_eig_by_lanczos)
+        long long served = 0;                      // calls of this block it served
+        bool disabled = false;                     // ... switched off after a failed verification (full_eig_lanczos_verify)
+        int cert_fails = 0;                        // failed certificates of this block (full_eig_lanczos_certify)
+    } fel;
+    bool cye_pending = false;                      // cye[] hold a profiled k_lz_block1 launch
+    const double* esv = nullptr;                   // support values of E for the projection in progress
+    // per-block execution context: counters are merged into the solver's after the projections
+    proxsdp_stats lst{};
+    long long mv_iter = 0, recon_r = 0;
+    bool fe_pending = false;
+    int sg_row = -1, sg_ok = 16, sg_idle = 0, sg_hold = 0;   // shortened schedule of the sign iteration (full_eig_by_sign)
+    bool sg_pending = false;                       // fe[] hold a sign projection's events (all of it is "solver")
+    // cost-based engine choice on the Krylov branch (psd_sign_engine, exact_projection_by_sign): wall-clock averages of this
+    // block's Lanczos and sign projections, projections since the last Lanczos probe
+    struct SignStandIn {
+        double kry_ms = -1.0, sign_ms = -1.0;
+        int streak = 0, backoff = 0;
+        int verified_left = 0;                     // projections the engine may still serve before it is checked again
+        bool disabled = false, check_pending = false;
+    } sign;
+};
+
+struct EigWork : EigSolveState {
     int n = 0, nt = 0, npad = 0, nwg = 0, cap = 0, pld = 0;   // cap = columns of V (krylovdim_max + 1)
     int64_t N = 0;
     DevBuf<double> V, Z;            // npad x cap each (V: Krylov basis, Z: rotation target / Ritz vectors)
@@ -313,75 +367,30 @@ struct EigWork {
     DevBuf<rocblas_int> info;
     std::vector<double> resid_host;
     PinnedBuf Ustage[2];            // pinned: the upload is a truly asynchronous copy (a pageable source makes the runtime stage and wait)
-    int ustage_next = 0;
-    int rot_form = 0, rot_launches = 0;   // the last rotate_launch: PROXSDP_ROTATE_SCALAR / _MFMA / _WIDE (0: nothing launched), its launches
-    // results of the last call
-    std::vector<double> vals;
-    int count = 0, converged_eigs = 0, numiter = 0, prev_numiter = 1;
-    bool converged = false;
     // operator-form mat-vec (kernels.hip.hpp "Operator-form mat-vec")
     DevBuf<double> F, Flam, tpart, tred, ebuf, apartf;   // (lam / Flam swap roles every projection)   // F: npad x cap, the previous projection's Ritz vectors (swapped with Z)
     DevBuf<int> ell_col, ell_sidx;                 // E in ELL form, [k * npad + row]
     DevBuf<int> wr_ptr, wr_row, wr_lo, wr_hi, ov_col, ov_sidx;   // entries beyond the ELL width (hub rows)
     dev::EllOverflow ov{};
-    int ell_w = 0, F_first = 0, F_r = 0;
+    int ell_w = 0;
     bool fop_ok = false;                           // structures built (support path, narrow rows)
-    bool have_factors = false;                     // x_prev of this block is F[:, F_first .. +F_r) diag(Flam) F'
-    bool use_fop = false;                          // the projection in progress uses the operator form
-    // what else the dispatch (projection.hip.hpp) knows of x_prev; have_factors, F_first / F_r and ritz_ok stay beside the
-    // buffers they describe: the Lanczos drivers read or drop them
-    struct XPrev {
-        bool sparse = true;                        // x_prev is zero off the support (initial iterate)
-        int last_npos = -1;                        // positive eigenvalues found by the last projection of this block
-    } xprev;
     // the previous projection's factors (valid while have_factors, or use_fop for the projection in progress)
     struct Factors { const double* V; const double* lam; int r; };
     Factors prev_factors() const { return {F.p + (size_t)F_first * npad, Flam.p, F_r}; }
     void forget_factors() { have_factors = false; xprev.sparse = false; use_fop = false; }   // x_prev is only the packed block now
-    // a block without the operator form's structures keeps no F: there the last converged Krylov projection's pairs stay
-    // where the run left them -- Z[:, ritz_first .. +ritz_r) and vals[ritz_first ..) -- and ritz_ok says that x_prev of this
-    // block is still their reconstruction: set at the end of that projection, dropped by whatever writes Z / vals (lanczos,
-    // lanczos_batch) or the block (project_block, project_blocks, the exit path's rescale).  Read by extract_factors only.
-    bool ritz_ok = false;
-    int ritz_first = 0, ritz_r = 0;
     // early read-back of the recurrence coefficients (host_eig_merge): side stream + events (below) + pinned mirror
     PinnedBuf rec_early;
     SplitEig split;
     DeviceMerge dmerge;                            // buffers of the device merge (allocated on first use)
-    int batch_slot = 0;                            // position of this block in the batched run in progress
-    // one-workgroup cycle kernel (lanczos_block1.hip.hpp): the restart rotation is deferred into the next cycle's launch
-    int b1_rot_K = 0;                             // > 0: a rotation is pending, U (K x kfirst, compact) at b1_rot_U (pinned staging)
-    const double* b1_rot_U = nullptr;
-    LzRun lzrun;                                   // host state of the run in progress (buffers reused across projections)
-    struct LanczosFullEig {                        // full_eig! served by the Lanczos engine (full_eig_by_lanczos)
-        long long served = 0;                      // calls of this block it served
-        bool disabled = false;                     // ... switched off after a failed verification (full_eig_lanczos_verify)
-        int cert_fails = 0;                        // failed certificates of this block (full_eig_lanczos_certify)
-    } fel;
     DevBuf<double> warm_part;                      // partial sums of the warm start (k_lz_warm_sum)
-    bool cye_pending = false;                      // cye[] hold a profiled k_lz_block1 launch
-    const double* esv = nullptr;                   // support values of E for the projection in progress
-    // per-block execution context: counters are merged into the solver's after the projections
-    proxsdp_stats lst{};
-    long long mv_iter = 0, recon_r = 0;
-    bool fe_pending = false;
     // full_eig! by the matrix sign function (sign_project.hip.hpp): A | X | X' | Y | Q, ld x ld each
     DevBuf<double> sgA, sgX, sgX2, sgY, sgQ, sg_part, sg_part2, sg_sc;
     PinnedBuf sg_host;
     int sg_ld = 0;
     int sg_npart = 0;
-    int sg_row = -1, sg_ok = 16, sg_idle = 0, sg_hold = 0;   // shortened schedule of the sign iteration (full_eig_by_sign)
     bool sg_small = false;                         // products on 32 x 32 tiles (blocks up to side 3072)
     int sg_nt48 = 0;                               // > 0: products on 48 x 48 tiles, this many per side (chosen by makespan)
-    bool sg_pending = false;                       // fe[] hold a sign projection's events (all of it is "solver")
-    // cost-based engine choice on the Krylov branch (psd_sign_engine, exact_projection_by_sign): wall-clock averages of this
-    // block's Lanczos and sign projections, projections since the last Lanczos probe; below it the scratch for in-place calls
-    struct SignStandIn {
-        double kry_ms = -1.0, sign_ms = -1.0;
-        int streak = 0, backoff = 0;
-        int verified_left = 0;                     // projections the engine may still serve before it is checked again
-        bool disabled = false, check_pending = false;
-    } sign;
+    // the sign engine's verification (EigSolveState::sign) and the scratch for in-place calls
     DevBuf<double> sg_cmp;                         // max |difference|, max |value| of a verification
     DevBuf<double> sg_out;
     // streams and events last: destroyed before the buffers above
@@ -425,7 +434,66 @@ struct RotSink {
     std::array<Req, dev::LZB_MAX> slot;
 };
 
-class Solver {
+// What a caller may ask of ONE solve beyond problem and options.  The C entries (capi.hip) fill one and check it there
+// (check_request); Solver::req carries it through the run; clearing it is `req = SolveRequest{}`.  All null / false: a plain
+// proxsdp_hip_solve, no code of the features below runs.
+struct SolveRequest {
+    // state seam (proxsdp_hip_solve_ex): continue from / write out the iterate at an iteration boundary
+    const proxsdp_state* resume_state = nullptr;
+    proxsdp_state* capture_state = nullptr;
+    // factors of the PSD solution (proxsdp_hip_solve_factored): where the caller wants them
+    proxsdp_psd_factors* factors_out = nullptr;
+    // warm start (proxsdp_hip_solve_from): the caller's point, validated by the entry; start_out: proxsdp_hip_start_point
+    // (the solve returns after the start path and writes the internal vectors there)
+    const proxsdp_start* start = nullptr;
+    proxsdp_state* start_out = nullptr;
+    // solution vectors on the device (proxsdp_hip_solve_device; exit_device.hip.hpp): the exit path as kernels, the caller's
+    // device buffers for the result (out_dev) and for the start point (start_dev)
+    bool device_exit = false;
+    const proxsdp_device_vectors* start_dev = nullptr;
+    proxsdp_device_vectors* out_dev = nullptr;
+    // the start the solver enters from: start_dev without a start stands for one with no factors and cold steps
+    const proxsdp_start* start_point() const { return (!start && start_dev) ? &none : start; }
+private:
+    proxsdp_start none = [] { proxsdp_start s{}; s.struct_size = (int64_t)sizeof(proxsdp_start); return s; }();
+};
+
+// The host scalars of a Solver that a solve writes.  RULE: declare a per-solve host member here, with the value it has after
+// setup() as its initialiser, and Solver::reset_for_solve puts it back by assigning a default-constructed SolveState: the
+// second solve on a model handle then starts from what a fresh solver has.  What comes from the options or the problem
+// (init_parameters, reduce_global_constants), what the set-up built, and the certificate flags (restore_cert_data owns them)
+// stay in Solver.  (A plain struct: the members that were private to Solver are reachable through it; nothing outside
+// Solver and the model handle uses them.)
+struct SolveState {
+    // scalar state (Params, structs.jl:159-192); theta, beta and adapt_level come from the options (init_parameters)
+    double primal_step = 0, primal_step_old = 0, dual_step = 0;
+    long long iter = 0;
+    int rank_update = 0, update_cont = 0, stop_reason = 0;
+    std::string stop_reason_string = "Not optimized";
+    double dual_feasibility = -1.0;
+    bool certificate_search = false, certificate_found = false;
+    long long certificate_search_min_iter = 0;
+    int last_trials = 0;
+    long long lz_matvec_iter = 0; long long recon_r_iter = 0;
+    double equa_feasibility = 0, ineq_feasibility = 0;
+    bool have_snapshot = false;
+    bool start_active = false;            // the start gave a point: x_old = x at iteration 1 (a cold solve has x_old = 0)
+    proxsdp_stats st{};
+    std::exception_ptr shard_error;       // this shard's projection failed in the current iteration (see primal_step_dev)
+    size_t dense_ev_used = 0;             // (Solver::dense_ev: one pair of events per pass of the current iteration)
+    long long dense_passes_seen = 0;
+    // PROXSDP_HIP_DEBUG: host seconds of the batched and of the single-block runs, and their cycles
+    struct BatchDebug { double enqueue = 0, wait = 0, restart = 0, flush = 0, cycles = 0; } dbg_batch;
+    struct LzDebug { double wait = 0, after_cycle = 0, results = 0, cycles = 0; } dbg_lz;
+    double sigma_max = 0.0;               // what approx_norm = false computed (0 otherwise)
+    double loop_t0 = 0;                   // start of the loop (trace column 12, stats.loop_time)
+    double g_elapsed = 0;
+    bool g_not_converged_rank = false, g_any_below_full = false;
+    bool small_pending = false;
+    int xc = 0, mtyc = 0, yc = 0, mxc = 0;     // index of the "current" buffer of each ping-pong pair
+};
+
+class Solver : public SolveState {
 public:
     // time0 is stamped BEFORE prepare(): the reference's clock starts at the top of chambolle_pock
     // (pdhg.jl:13), so preprocessing and equilibration count towards Result.time and time_limit
@@ -495,16 +563,12 @@ public:
     void cert_dual_infeas();
     void snapshot();
     void update_dual_feasibility(const std::vector<double>& cvec);
-    double loop_t0 = 0;             // start of the loop (trace column 12, stats.loop_time)
     bool shard_general = false;     // block-sharded solve: this shard runs the general vector path (classify_blocks)
 
     // pieces also used by the kernel-level test entry points
     void setup_device();
     void alloc_eigwork(EigWork& W, int n, int max_nev);
     void lanczos_start_vector(EigWork& W, const double* user);
-    // PROXSDP_HIP_DEBUG: host seconds of the batched and of the single-block runs, and their cycles
-    struct BatchDebug { double enqueue = 0, wait = 0, restart = 0, flush = 0, cycles = 0; } dbg_batch;
-    struct LzDebug { double wait = 0, after_cycle = 0, results = 0, cycles = 0; } dbg_lz;
     // (thread-local: several batched runs may be in progress at once, one per group of blocks, each on its own worker thread)
     static inline thread_local RotSink* rot_sink = nullptr;
     // per-GROUP state of a batched run (round 5: equal-side blocks are split into groups that run CONCURRENTLY, each on its own
@@ -568,9 +632,8 @@ public:
     void harvest_full_eig_events(EigWork& W);
     void launch_reconstruct(EigWork& W, const double* Z, int ldz, const double* lam, int r, double* xp_out,
                             const double* xp_old = nullptr, int blk = -1);
-    // factors of the PSD solution (proxsdp_hip_solve_factored): where the caller wants them (null: a plain solve, no new
-    // code runs), the residual kernel's launch, and the extraction at the snapshot that fills `res`
-    proxsdp_psd_factors* factors_out = nullptr;
+    // factors of the PSD solution (req.factors_out; null: a plain solve, no new code runs): the residual kernel's launch,
+    // and the extraction at the snapshot that fills `res`
     DevBuf<double> fac_V, fac_lam, fac_part;
     void factor_residual(const double* xp, int n, const double* V, int ldv, const double* lam, int r,
                          double& resid2, double& xnorm2);
@@ -598,13 +661,12 @@ public:
     proxsdp_result& res;
     double time0 = 0;               // (declared before P: initialised first)
     Prep P;
-    proxsdp_stats st{};
+    SolveRequest req;               // what this solve was asked for beyond problem and options
     const double* user_resid = nullptr;
     // block-sharded solve: how this shard reaches the others (shard_comm.hip.hpp); none when the solve is not sharded
     std::unique_ptr<ShardComm> comm;
     bool sharded() const { return comm != nullptr; }
     long long current_iteration() const { return iter; }   // (the iteration a failed shard stopped in: proxsdp_hip_solve_sharded)
-    std::exception_ptr shard_error;                 // this shard's projection failed in the current iteration (see primal_step_dev)
     void reduce(std::vector<double>& sums, std::vector<double>& maxs) { if (comm) comm->reduce(stream, sums, maxs); }
     void reduce_vec_host(std::vector<double>& v) { if (!v.empty()) comm->reduce_vec_host(stream, v); }
     // coupling rows of a block-sharded solve (include/proxsdp_hip.h): partial M x summed over the shards
@@ -619,26 +681,16 @@ public:
     void wait_stream() {
         if (!comm || !comm->bounded_wait(stream)) wait_for_stream(stream, opt.host_wait_spin != 0);
     }
-    // state seam (proxsdp_hip_solve_ex): continue from / write out the iterate at an iteration boundary
-    const proxsdp_state* resume_state = nullptr;
-    proxsdp_state* capture_state = nullptr;
+    // state seam (req.resume_state, req.capture_state)
     void check_state_shape(const proxsdp_state& s, const char* what) const;
     void apply_resume();
     void write_capture();
-    // warm start (proxsdp_hip_solve_from): the caller's point, validated by the entry; start_out: proxsdp_hip_start_point
-    // (run() returns after the start path and writes the internal vectors there)
-    const proxsdp_start* start = nullptr;
-    proxsdp_state* start_out = nullptr;
-    bool start_active = false;            // the start gave a point: x_old = x at iteration 1 (a cold solve has x_old = 0)
+    // warm start (req.start_point(), req.start_out)
     DevBuf<long long> start_ord_d;
     DevBuf<double> start_src_d, start_V, start_lam;
     void apply_start();
     void write_start_point();
-    // solution vectors on the device (proxsdp_hip_solve_device; exit_device.hip.hpp): the exit path as kernels, the caller's
-    // device buffers for the result (out_dev) and for the start point (start_dev); all off in every other entry
-    bool device_exit = false;
-    const proxsdp_device_vectors* start_dev = nullptr;
-    proxsdp_device_vectors* out_dev = nullptr;
+    // solution vectors on the device (req.device_exit, req.start_dev, req.out_dev; exit_device.hip.hpp)
     void check_start_dev();
     void cache_solution_device(bool zero_c);
     void test_exit_vectors(const double* x, const double* y, bool zero_c, double* primal, double* dual_cone, double* dual_eq,
@@ -650,10 +702,8 @@ public:
     }
     // global (all-shard) problem constants; equal to the local ones when not sharded
     double g_n = 0, g_Q = 0, g_p = 0, g_m = 0, g_norm_b = 0, g_norm_h = 0, g_norm_c = 0, g_frob = 0;
-    bool g_conic = false, g_not_converged_rank = false, g_any_below_full = false;
-    double g_elapsed = 0;
+    bool g_conic = false;
     bool init_only = false;         // proxsdp_hip_dense_scaling: run() returns after the "Init" section
-    double sigma_max = 0.0;         // what approx_norm = false computed (0 otherwise)
     std::thread warm;               // loads rocSOLVER's code objects while the loop runs
     // concurrent block projections: one worker thread per PSD block (up to 8), each driving its
     // block's Lanczos on the block's own stream
@@ -673,7 +723,6 @@ private:
     DevBuf<long long> one_off, soc_off;
     DevBuf<int> soc_len;
     DevBuf<double> one_min, soc_gap_d;
-    int xc = 0, mtyc = 0, yc = 0, mxc = 0;     // index of the "current" buffer of each ping-pong pair
     std::vector<int> one_blocks;               // indices of 1x1 PSD blocks
     std::vector<int> big_blocks;               // indices of the blocks that are projected by an eigensolver
     // blocks of side 2..64 below min_size_krylov_eigs: one batched Jacobi launch on the dense vector path
@@ -688,7 +737,6 @@ private:
     // per-iteration read-backs written by the kernels straight into pinned host memory: only where the iteration leaves little
     // dirty data behind (a kernel that stores to host memory ends with a system-scope release)
     bool zero_copy_small() const { return P.n <= (1 << 16); }
-    bool small_pending = false;
     void project_small_blocks(double* x);
     void harvest_small_ranks();
     bool csr_wave = false;
@@ -701,23 +749,14 @@ private:
     int n_seg = 0, n_long = 0;
     void setup_long_rows(const std::vector<int>& rp);
 
-    // scalar state (Params, structs.jl:159-192)
-    double theta = 1, beta = 1, adapt_level = 0.9, primal_step = 0, primal_step_old = 0, dual_step = 0;
-    long long iter = 0;
-    int rank_update = 0, update_cont = 0, stop_reason = 0;
-    std::string stop_reason_string = "Not optimized";
+    // scalar state (Params, structs.jl:159-192) that init_parameters() and reduce_global_constants() set; the rest is SolveState's
+    double theta = 1, beta = 1, adapt_level = 0.9;
     std::vector<long long> target_rank, current_rank;
     std::vector<double> min_eig;
-    double dual_feasibility = -1.0;
-    bool certificate_search = false, certificate_found = false;
-    long long certificate_search_min_iter = 0;
     long long max_iter_local = 0;
     double time_limit = 0;
-    int last_trials = 0;
-    long long lz_matvec_iter = 0; long long recon_r_iter = 0;
     // histories (Residuals, structs.jl:100-125)
     CircularVector h_gap, h_pobj, h_dobj, h_feas, h_pres, h_dres, h_comb;
-    double equa_feasibility = 0, ineq_feasibility = 0;
 
     void primal_step_dev();
     void psd_projection(double* x);
@@ -828,7 +867,6 @@ private:
     void bump_rank(int idx);
     std::vector<double> b_host, h_host, c_host;   // current (possibly zeroed by a certificate search)
     bool cert_zeroed_c = false, cert_zeroed_bh = false;   // ... and with them c_d / cS_d, bh_d: reset_for_solve uploads them again
-    bool have_snapshot = false;
     // support-aware vector passes
     bool use_support = false;
     // the general path inside a block-sharded solve: its residual pass takes the row weights (b'y and h'y count a coupling
@@ -848,7 +886,6 @@ private:
     DevBuf<unsigned char> offdiag_d;
     int dmv_slices = 1, dmv_qpad = 0;
     static constexpr int DMV_ROWS = 8, DMV_UNR = 4;       // k_dense_mv shape (rows per workgroup, strips in flight)
-    long long dense_passes_seen = 0;
     // equilibration / approx_norm = false on a dense A: set-up on the device (one pass over M: row sums + extrema), scale
     // vectors E (rows of the dense block) and D o s (columns) for the products, Lanczos for sigma_max
     void upload_dense();
@@ -856,7 +893,6 @@ private:
     double spectral_norm_device();
     DevBuf<double> drow_d, dcol_d;   // E[0..p), D o s
     double dense_frob2 = 0.0;        // ||E A D S||_F^2 of the dense block, from the set-up pass's row sums
-    size_t dense_ev_used = 0;                // (dense_ev, below: one pair of events per pass of the current iteration)
     void dense_ev_begin();
     void dense_ev_end();
     void dense_ev_harvest();

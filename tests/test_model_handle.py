@@ -14,6 +14,7 @@ from proxsdp_jl_amd import problems as P
 from proxsdp_jl_amd.optimizer import Optimizer
 
 import kat_problems as K
+import solve_request_cases as Q
 
 pytestmark = pytest.mark.gpu
 
@@ -342,6 +343,25 @@ def test_a_value_update_needs_the_approximate_norm():
         _assert_equal(_on_model(mdl), want, "approx_norm = 0")
         mdl.update(c=pr.c * 2.0)                                      # (c does not enter sigma_max)
         _assert_equal(_on_model(mdl), _fresh(_with(pr, c=pr.c * 2.0), okw), "approx_norm = 0, new c")
+
+
+def test_a_handle_refuses_a_damaged_request_as_solve_device_does():
+    """every case of the start table and of the device-vector table (solve_request_cases; the shard cases do not apply: a
+    handle has no shard fields) against proxsdp_hip_model_solve: refused on the host -- the fake device pointers of the table
+    are never read -- with the code and the message proxsdp_hip_solve_device gives for the same damage; no solve is counted,
+    and the handle then solves as a fresh call does"""
+    pr = K.sdp_wiki(False)
+    want = _fresh(pr, {})
+    with B.Model(pr, _opts()) as mdl:
+        for table, cases in (("start", Q.START_CASES), ("device", Q.DEVICE_CASES)):
+            for case in cases:
+                rc, msg = Q.request_call("model_solve", table, case, handle=mdl._h)
+                rc_dev, msg_dev = Q.request_call("solve_device", table, case)
+                assert rc == E_INVALID and rc_dev == E_INVALID, (table, case, rc, rc_dev, msg, msg_dev)
+                assert msg and msg == msg_dev, (table, case, msg, msg_dev)
+        assert mdl.info()["solves"] == 0
+        _assert_equal(_on_model(mdl), want, "after the refused requests")
+        assert mdl.info()["solves"] == 1
 
 
 # ----------------------------------------------------------------- 8. the Python surface
