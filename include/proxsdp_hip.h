@@ -73,7 +73,10 @@ extern "C" {
  * later: the model handle (proxsdp_hip_model_create / _update / _solve / _info / _destroy: a model that stays set up on the
  * device between solves) with the new structs proxsdp_model_data, proxsdp_model_info and proxsdp_model_dump and the test
  * entries proxsdp_hip_model_dump, proxsdp_hip_model_norm2 and proxsdp_host_model_prepare: functions and new structs, no
- * existing struct changed: the version stays */
+ * existing struct changed: the version stays;
+ * later: proxsdp_hip_model_rows (inequality rows of a model handle added and dropped in place) with the new struct
+ * proxsdp_model_rows and the test entry proxsdp_host_model_rows_plan: functions and one new struct, no existing struct
+ * changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -840,6 +843,61 @@ int  proxsdp_hip_model_solve(proxsdp_model* mdl, const proxsdp_options* run_opt 
                              proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev);   /* the last four may be NULL */
 int  proxsdp_hip_model_info(const proxsdp_model* mdl, proxsdp_model_info* info);
 int  proxsdp_hip_model_destroy(proxsdp_model* mdl);       /* NULL is fine */
+/* ------------------------------------------- inequality rows of a model handle added and dropped in place
+ * The structural change of a cutting-plane loop: solve, separate violated inequalities, add them as rows of G x <= h, drop
+ * the rows that went slack, re-solve from the previous point -- without destroy + create.  The reference has no counterpart
+ * (it rebuilds everything per optimize!, as the section above says).
+ *   G' = [the rows of G not in `drop`, in their old order; then the n_add new rows in the order given], h' likewise.
+ * A, b, c and the cones are untouched; equality rows, new variables and new cones are out of scope.  m = 0 before and m' = 0
+ * after are both valid; a new row may be empty; a new row may list a column twice (both stored entries are kept, as create
+ * keeps duplicates).
+ * STORAGE ORDER of G' -- the order a later proxsdp_hip_model_update(G_nzval) follows: column by column; inside a column its
+ * kept entries in the order they are stored now, then its new entries by ascending new row; the entries of one row and
+ * column in the order the row lists them.  For sorted, duplicate-free input this is the sorted CSC of the stacked matrix.
+ * CONTRACT, the one every handle operation has: after the call proxsdp_hip_model_solve is proxsdp_hip_solve_device on the
+ * problem with G', h' (stored in that order) BIT FOR BIT, and proxsdp_hip_model_dump equals the dump of a fresh model of it:
+ * every decision a set-up derives from the matrix is taken again (the support path's auto rule, the wave-per-row mat-vec,
+ * the long rows, the ELL structures of the operator form, general path versus support path).
+ * The four norms follow the data as in update: on the host route (on_device = 0) ||h'|| and ||M'||_F are recomputed on the
+ * host in prepare()'s order and equal a fresh model's to the last bit; on the device route they come from the fixed-order
+ * device reduction update uses: reproducible, not guaranteed equal to the host's last bit.
+ * What is rebuilt: everything sized by Q = p + m or by nnz -- y, M x and the candidates' y, [b; h], the operator's index and
+ * value arrays in both orientations with its launch shapes, the exit path's value arrays and slack, the handle's position
+ * maps -- and, ONLY when the set {column non-empty or c_i != 0} changed, the support set with what update rebuilds from it
+ * (support_rebuilt = 1, counted in proxsdp_model_info.support_rebuilds).  What stays: everything sized by n or by a cone
+ * side alone -- the Lanczos workspaces, the sign projection's work matrices, x and M'y, the small-block and SOC set-ups,
+ * streams, events, the rocBLAS handle.  The values of kept entries do not visit the host on either route.
+ * PROXSDP_E_INVALID, decided on the host before anything is written: a NULL handle; a wrong struct_size; n_drop and n_add
+ * both 0 (or one negative); on_device other than 0 or 1; a NULL array that is needed; a drop number outside 0 .. m-1 or
+ * repeated; add_ptr[0] != 0 or add_ptr not monotone; a column outside the model's variables; non-finite host values; Q' or
+ * nnz' >= 2^31 (as create refuses them).  Device values are checked by a reduction on the device before anything is written;
+ * the message names the array.  PROXSDP_E_UNSUPP: an equilibrated model (E and D depend on the rows); a model created with
+ * approx_norm = 0 (sigma_max depends on them).  After a refused call the handle holds its previous data and solves as before.
+ * ALLOCATION: every buffer of the new operator, of [b; h'], of the Q-sized vectors and of the maps is allocated BEFORE the
+ * first write and before an old one is released: PROXSDP_E_NOMEM out of that phase leaves the old model in place.  The
+ * segment lists of rows longer than 8192 entries and the support rebuild allocate after the new operator is in place; a
+ * failure there leaves a handle that must be destroyed. */
+typedef struct proxsdp_model_rows {
+    int64_t struct_size;      /* = sizeof(proxsdp_model_rows) */
+    int32_t on_device;        /* where add_val and add_h live: 0 host, 1 DEVICE pointers on the model's device, borrowed and
+                               * trusted as proxsdp_model_data's are.  Index arrays are always HOST. */
+    int32_t reserved;
+    int64_t n_drop;  const int64_t* drop;     /* inequality rows to remove: 0-BASED numbers into the model's CURRENT G
+                                               * (0 .. m-1), whatever index base, any order, no repeats */
+    int64_t n_add;   const int64_t* add_ptr;  /* n_add + 1 offsets (0-based) into add_col / add_val: CSR of the new rows */
+    const int64_t* add_col;                   /* variable numbers in the caller's numbering and the index base of create */
+    const double*  add_val;                   /* host or device (on_device) */
+    const double*  add_h;                     /* n_add right-hand sides, host or device (on_device) */
+    /* out */
+    int64_t m_new, nnz_new;
+    int64_t* kept;            /* optional, caller-allocated, m - n_drop + n_add entries: new inequality row r was old row
+                               * kept[r], -1 for an added row */
+    int32_t support_rebuilt;  /* the support set or the vector path changed and was rebuilt */
+    int32_t reserved2;
+    int64_t bytes_allocated;  /* device bytes this call allocated (new buffers, whatever it freed) */
+    double  seconds;          /* wall time of the call */
+} proxsdp_model_rows;
+int  proxsdp_hip_model_rows(proxsdp_model* mdl, proxsdp_model_rows* ch);
 /* test entry: the model's current internal data, downloaded into caller-allocated host arrays.  The sizes (n, Q = p + m, nnz,
  * ns = length of the support list, 0 when the support path is off) and the four norms (||b||, ||h||, ||c||, ||M||_F) are always
  * written; an array is written when its pointer is not NULL (call once with every pointer NULL for the sizes, allocate, call
@@ -1226,6 +1284,14 @@ int proxsdp_host_preprocess(const proxsdp_problem* prob, int64_t* order, int64_t
  * An array is written when its pointer is not NULL. */
 int proxsdp_host_model_prepare(const proxsdp_problem* prob, proxsdp_model_dump* out, int64_t* nnz_A, int32_t* csc_pos,
                                int32_t* csr_pos);
+/* the planner proxsdp_hip_model_rows runs, with no device: prob is the model BEFORE the change (as create was given it), ch
+ * the change with HOST add_val / add_h.  Out: the dump of the changed model exactly as proxsdp_host_model_prepare gives it
+ * for the changed problem; for every position of the new csc_val / csr_val where its value comes from (csc_src / csr_src:
+ * q >= 0 = position q of the old array, -1 - t = entry t of add_val); the same map for [b; h'] (bh_src, -1 - t = entry t of
+ * add_h); the new position maps csc_pos / csr_pos; ch->kept, m_new, nnz_new.  An array is written when its pointer is not
+ * NULL.  Every refusal of proxsdp_hip_model_rows that needs no device applies, with the same codes. */
+int proxsdp_host_model_rows_plan(const proxsdp_problem* prob, proxsdp_model_rows* ch, proxsdp_model_dump* out,
+                                 int32_t* csc_src, int32_t* csr_src, int32_t* bh_src, int32_t* csc_pos, int32_t* csr_pos);
 /* equilibrate! (equilibration.jl) from the row sums alone: rowsums[r] = sum_j M[r,j]^2 of a Q x n matrix in, E (Q) and
  * the scalar d (D = d I: the reference replaces v by its mean in every iteration) out -- the iteration a dense A takes,
  * where M is only streamed.  Uses opt's equilibration_iters / _lb / _ub / _reference_aliasing (NULL: the defaults). */

@@ -224,6 +224,15 @@ class ModelDump(C.Structure):
                 ("norms", f64 * 4)]
 
 
+class ModelRows(C.Structure):
+    """proxsdp_model_rows (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("on_device", i32), ("reserved", i32),
+                ("n_drop", i64), ("drop", pi64), ("n_add", i64), ("add_ptr", pi64), ("add_col", pi64),
+                ("add_val", pf64), ("add_h", pf64),
+                ("m_new", i64), ("nnz_new", i64), ("kept", pi64), ("support_rebuilt", i32), ("reserved2", i32),
+                ("bytes_allocated", i64), ("seconds", f64)]
+
+
 MODEL_DUMP_ARRAYS = (("csc_val", "nnz"), ("csr_val", "nnz"), ("csc_val_orig", "nnz"), ("csr_val_orig", "nnz"),
                      ("c", "n"), ("c_orig", "n"), ("bh", "Q"), ("support", "ns"), ("cS", "ns"))
 MODEL_NORM_NAMES = ("norm_b", "norm_h", "norm_c", "frob")
@@ -290,6 +299,8 @@ def lib():
     L.proxsdp_hip_model_dump.argtypes = [C.c_void_p, C.POINTER(ModelDump)]
     L.proxsdp_hip_model_norm2.argtypes = [pf64, i64, i32, pf64]
     L.proxsdp_host_model_prepare.argtypes = [C.POINTER(Problem), C.POINTER(ModelDump), pi64, C.POINTER(i32), C.POINTER(i32)]
+    L.proxsdp_hip_model_rows.argtypes = [C.c_void_p, C.POINTER(ModelRows)]
+    L.proxsdp_host_model_rows_plan.argtypes = [C.POINTER(Problem), C.POINTER(ModelRows), C.POINTER(ModelDump)] + [C.POINTER(i32)] * 5
     L.proxsdp_hip_factor_residual.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64]
     L.proxsdp_hip_factor_residual_kernel.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64, i32, pf64]
     L.proxsdp_hip_psd_project.argtypes = [pf64, i64, i32, i32, C.POINTER(Options), pf64, pf64,
@@ -917,6 +928,106 @@ def host_model_prepare(prob, index_base=0):
     return out
 
 
+def _host_index(a):
+    """an index array as a contiguous int64 NumPy array (a tensor, CUDA included, is copied to the host)"""
+    if _is_tensor(a):
+        a = a.detach().cpu().numpy()
+    return _i(np.asarray(a).ravel())
+
+
+def _rows_arguments(add, drop, n, index_base=0):
+    """(drop, rowptr, cols, values, h_new) of a row change, the index arrays as int64 NumPy arrays (cols in `index_base`),
+    values and h_new as given (NumPy or tensors); None where nothing is added / dropped.  add = (G_new, h_new) with G_new
+    a scipy sparse k x n matrix or a triple (rowptr, cols, values) of CSR arrays with 0-based cols."""
+    d = None if drop is None else _host_index(drop)
+    if add is None:
+        return d, None, None, None, None
+    G_new, h_new = add
+    if sp.issparse(G_new):
+        G_new = sp.csr_matrix(G_new, dtype=np.float64)
+        if G_new.shape[1] != n:
+            raise ValueError(f"change_rows: the new rows must have {n} columns")
+        ptr, cols, vals = G_new.indptr, G_new.indices, G_new.data
+    else:
+        ptr, cols, vals = G_new
+    return d, _host_index(ptr), _host_index(cols) + index_base, vals, h_new
+
+
+def _rows_struct(d, ptr, cols, vals, h_new, keep):
+    """proxsdp_model_rows over HOST arrays (vals, h_new float64 NumPy or None); keep collects what it points to"""
+    R = ModelRows()
+    R.struct_size = C.sizeof(ModelRows)
+    if d is not None and len(d):
+        keep.append(d)
+        R.n_drop, R.drop = len(d), _p(d, pi64)
+    if ptr is not None and len(ptr) > 1:
+        keep += [ptr, cols if len(cols) else np.zeros(1, dtype=np.int64)]
+        R.n_add, R.add_ptr, R.add_col = len(ptr) - 1, _p(ptr, pi64), _p(keep[-1], pi64)
+        if vals is not None:
+            keep += [vals if len(vals) else np.zeros(1), h_new]
+            R.add_val, R.add_h = _p(keep[-2]), _p(keep[-1])
+    return R
+
+
+def host_model_rows_plan(prob, add=None, drop=None, index_base=0):
+    """proxsdp_host_model_rows_plan: the planner Model.change_rows runs, on the host (no device).  prob: the model before
+    the change.  Returns the dump's dictionary of the changed model plus csc_src, csr_src, bh_src (q >= 0: position q of
+    the old array; -1 - t: entry t of the new values / right-hand sides), csc_pos, csr_pos, kept, m, nnz."""
+    L = lib()
+    M = _Marshalled(prob, None, index_base)
+    d, ptr, cols, vals, h_new = _rows_arguments(add, drop, int(M.P.n), index_base)
+    keep = []
+    R = _rows_struct(d, ptr, cols, None if vals is None else _f(vals).ravel(), None if h_new is None else _f(h_new).ravel(), keep)
+    kept = np.zeros(max(int(M.P.m) - int(R.n_drop) + int(R.n_add), 1), dtype=np.int64)
+    R.kept = _p(kept, pi64)
+    D = ModelDump()
+    D.struct_size = C.sizeof(ModelDump)
+    _check(L.proxsdp_host_model_rows_plan(C.byref(M.P), C.byref(R), C.byref(D), None, None, None, None, None))
+    nz, Q = max(int(D.nnz), 1), max(int(D.Q), 1)
+    maps = {k: np.zeros(Q if k == "bh_src" else nz, dtype=np.int32) for k in ("csc_src", "csr_src", "bh_src", "csc_pos", "csr_pos")}
+    ip = lambda a: a.ctypes.data_as(C.POINTER(i32))
+    out = _dump_arrays(D, lambda dd: _check(L.proxsdp_host_model_rows_plan(
+        C.byref(M.P), C.byref(R), C.byref(dd), *[ip(maps[k]) for k in ("csc_src", "csr_src", "bh_src", "csc_pos", "csr_pos")])))
+    out.update({k: v[:out["Q" if k == "bh_src" else "nnz"]].copy() for k, v in maps.items()})
+    out.update(kept=kept[:int(R.m_new)].copy(), m=int(R.m_new))
+    return out
+
+
+class RowsChange:
+    """What Model.change_rows did: kept (new inequality row r was old row kept[r], -1 for an added row), m, nnz,
+    support_rebuilt, bytes_allocated, seconds."""
+
+    def __init__(self, R, kept):
+        self.kept = kept
+        self.m, self.nnz = int(R.m_new), int(R.nnz_new)
+        self.support_rebuilt = int(R.support_rebuilt)
+        self.bytes_allocated, self.seconds = int(R.bytes_allocated), float(R.seconds)
+
+    def carry(self, prev):
+        """The start= dictionary of a previous result (or start dictionary) of the OLD shape for the changed model: dual_in
+        re-indexed through `kept`, zeros on the new rows -- a NumPy array stays NumPy, a CUDA tensor stays on its device;
+        everything else is passed through."""
+        d = start_from_result(prev) if isinstance(prev, SolveResult) else dict(prev)
+        v = d.get("dual_in")
+        if v is None:
+            return d
+        old = np.maximum(self.kept, 0)
+        if _is_tensor(v):
+            import torch
+            new = torch.zeros(len(self.kept), dtype=v.dtype, device=v.device)
+            if len(self.kept) and v.numel():
+                idx = torch.as_tensor(old, device=v.device)
+                mask = torch.as_tensor(self.kept >= 0, device=v.device)
+                new = torch.where(mask, v[idx], new)
+        else:
+            v = np.asarray(v, dtype=np.float64)
+            new = np.zeros(len(self.kept))
+            if len(self.kept) and len(v):
+                new = np.where(self.kept >= 0, v[old], 0.0)
+        d["dual_in"] = new
+        return d
+
+
 def model_norm2(v, grid=0):
     """proxsdp_hip_model_norm2: ||v||_2 by the reduction a device-route Model.update uses, with `grid` workgroups"""
     v = _f(v).ravel()
@@ -945,6 +1056,7 @@ class Model:
         self.n, self.p, self.m = int(M.P.n), int(M.P.p), int(M.P.m)
         self._sides = psd_sides(prob)
         self._nnz = (int(sp.csc_matrix(prob.A).nnz), int(sp.csc_matrix(prob.G).nnz))
+        self._index_base = index_base
         self._h = C.c_void_p()
         _check(L.proxsdp_hip_model_create(C.byref(M.P), C.byref(self._options), C.byref(self._h)))
 
@@ -1010,6 +1122,48 @@ class Model:
                 setattr(D, k, _p(keep[-1]))
         _check(lib().proxsdp_hip_model_update(self._handle(), C.byref(D)))
         del keep
+
+    def change_rows(self, add=None, drop=None):
+        """proxsdp_hip_model_rows: add and drop inequality rows in place.  drop: numbers (0-based) into the model's current
+        G.  add = (G_new, h_new): G_new a scipy sparse k x n matrix or a triple (rowptr, cols, values) of CSR arrays
+        (0-based cols), h_new the k right-hand sides.  G' = [kept rows in their old order; the new rows], stored column by
+        column: kept entries first, then the new ones by ascending row -- the order a later update(G_values=...) follows.
+        values / h_new as CUDA float64 tensors take the device route, NumPy arrays the host route; mixing the two is a
+        ValueError.  Index arrays that arrive as tensors are copied to the host.  Returns a RowsChange; carry(prev) of it
+        re-indexes a previous result's dual_in for start=."""
+        d, ptr, cols, vals, h_new = _rows_arguments(add, drop, self.n, getattr(self, "_index_base", 0))
+        k = 0 if ptr is None else len(ptr) - 1
+        on_dev = [_is_tensor(v) and v.is_cuda for v in (vals, h_new) if v is not None]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("Model.change_rows: host arrays and CUDA tensors cannot be mixed in one call")
+        keep = []
+        if k > 0 and all(on_dev):
+            import torch
+            dev_id = int(self._options.device_id)
+            R = _rows_struct(d, ptr, cols, None, None, keep)
+            R.on_device = 1
+            R.add_val = _device_ptr(vals, int(ptr[-1]), dev_id, "values")
+            R.add_h = _device_ptr(h_new, k, dev_id, "h_new")
+            keep += [vals, h_new]
+            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
+        else:
+            host = []
+            for v, ln, what in ((vals, 0 if ptr is None else int(ptr[-1]), "values"), (h_new, k, "h_new")):
+                if v is None:
+                    host.append(None)
+                    continue
+                a = _f(v.numpy() if _is_tensor(v) else v).ravel()
+                if len(a) != ln:
+                    raise ValueError(f"Model.change_rows: {what} must have {ln} entries")
+                host.append(a if len(a) else np.zeros(1))
+            R = _rows_struct(d, ptr, cols, host[0], host[1], keep)
+        kept = np.zeros(max(self.m - int(R.n_drop) + int(R.n_add), 1), dtype=np.int64)
+        R.kept = _p(kept, pi64)
+        _check(lib().proxsdp_hip_model_rows(self._handle(), C.byref(R)))
+        del keep
+        self.m = int(R.m_new)
+        self._nnz = (self._nnz[0], int(R.nnz_new) - self._nnz[0])
+        return RowsChange(R, kept[:self.m].copy())
 
     # ---- solve
     def solve(self, start=None, factors=False, primal=True, device_out=False, trace_capacity=0, time_limit=None,

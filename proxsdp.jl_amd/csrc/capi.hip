@@ -418,6 +418,17 @@ int proxsdp_hip_model_update(proxsdp_model* mdl, const proxsdp_model_data* upd) 
     });
 }
 
+int proxsdp_hip_model_rows(proxsdp_model* mdl, proxsdp_model_rows* ch) {
+    return guarded([&]() -> int {
+        proxsdp::check_rows_struct(ch);
+        if (!mdl) throw std::invalid_argument("NULL handle");
+        if (mdl->S->P.equilibrated) throw std::domain_error("proxsdp_hip_model_rows does not serve an equilibrated model: E and D depend on the rows");
+        if (!mdl->opt0.approx_norm) throw std::domain_error("proxsdp_hip_model_rows does not serve approx_norm = 0: sigma_max depends on the rows");
+        mdl->change_rows(*ch);
+        return 0;
+    });
+}
+
 int proxsdp_hip_model_solve(proxsdp_model* mdl, const proxsdp_options* run_opt, proxsdp_result* res,
                             const proxsdp_start* start, const proxsdp_device_vectors* start_dev,
                             proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev) {
@@ -1353,6 +1364,52 @@ int proxsdp_host_model_prepare(const proxsdp_problem* prob, proxsdp_model_dump* 
             if (out->support) out->support[q] = supp[q];
             if (out->cS) out->cS[q] = R.c[supp[q]];
         }
+        return 0;
+    });
+}
+
+int proxsdp_host_model_rows_plan(const proxsdp_problem* prob, proxsdp_model_rows* ch, proxsdp_model_dump* out,
+                                 int32_t* csc_src, int32_t* csr_src, int32_t* bh_src, int32_t* csc_pos, int32_t* csr_pos) {
+    return guarded([&]() -> int {
+        proxsdp::check_rows_struct(ch);
+        if (ch->on_device != 0) throw std::invalid_argument("proxsdp_host_model_rows_plan takes host values (on_device = 0)");
+        if (!prob || !out) throw std::invalid_argument("NULL problem or dump");
+        if (out->struct_size != (int64_t)sizeof(proxsdp_model_dump)) throw std::invalid_argument("proxsdp_model_dump.struct_size mismatch");
+        if (is_shard(prob) || prob->M_dense) throw std::domain_error("proxsdp_host_model_rows_plan does not serve a shard of a block-sharded solve or M_dense");
+        const proxsdp::Prep P = proxsdp::prepare(*prob, nullptr, false, true);
+        proxsdp::RowsPlan pl = proxsdp::plan_rows(P, prob->index_base, *ch);
+        std::vector<double> rorig;
+        proxsdp::apply_rows_host(P, pl, ch->add_val, ch->add_h, rorig);
+        const proxsdp::Prep& R = pl.R;
+        std::vector<int32_t> supp;
+        for (int64_t k = 0; k < R.n; ++k)
+            if (R.colptr[k + 1] > R.colptr[k] || P.c[k] != 0.0) supp.push_back((int32_t)k);
+        out->n = R.n; out->Q = R.Q; out->nnz = R.nnz; out->ns = (int64_t)supp.size();
+        out->norms[0] = P.norm_b; out->norms[1] = R.norm_h; out->norms[2] = P.norm_c; out->norms[3] = R.frob;
+        for (int64_t q = 0; q < R.nnz; ++q) {
+            if (out->csc_val) out->csc_val[q] = R.val[q];
+            if (out->csr_val) out->csr_val[q] = R.rval[q];
+            if (out->csc_val_orig) out->csc_val_orig[q] = R.val_orig[q];
+            if (out->csr_val_orig) out->csr_val_orig[q] = rorig[q];
+            if (csc_src) csc_src[q] = pl.csc_src[q];
+            if (csr_src) csr_src[q] = pl.csr_src[q];
+            if (csc_pos) csc_pos[q] = R.csc_pos[q];
+            if (csr_pos) csr_pos[q] = R.csr_pos[q];
+        }
+        for (int64_t k = 0; k < R.n; ++k) {
+            if (out->c) out->c[k] = P.c[k];
+            if (out->c_orig) out->c_orig[k] = P.c_orig[k];
+        }
+        for (int64_t i = 0; i < R.Q; ++i) {
+            if (out->bh) out->bh[i] = i < R.p ? P.b[i] : R.h[i - R.p];
+            if (bh_src) bh_src[i] = pl.bh_src[i];
+        }
+        for (size_t q = 0; q < supp.size(); ++q) {
+            if (out->support) out->support[q] = supp[q];
+            if (out->cS) out->cS[q] = P.c[supp[q]];
+        }
+        ch->m_new = R.m; ch->nnz_new = R.nnz; ch->support_rebuilt = 0; ch->bytes_allocated = 0; ch->seconds = 0.0;
+        if (ch->kept) std::copy(pl.kept.begin(), pl.kept.end(), ch->kept);
         return 0;
     });
 }

@@ -148,6 +148,13 @@ inline void Solver::exit_rescale_iterate() {
     }
 }
 
+// workgroups of the feasibility reductions: the longest of the free tail, m inequality rows, the 1x1 cones and the SOCs
+inline int Solver::exit_feas_grid(int64_t m) const {
+    size_t ones = 0;
+    for (const BlockInfo& B : P.blocks) ones += B.n == 1 ? 1 : 0;
+    return grid_for(std::max<int64_t>(std::max(P.n - P.conelen, m), (int64_t)std::max(ones, P.socs.size())));
+}
+
 // what the exit kernels read beside the operator's pattern (csc_ptr / csc_row, csr_ptr / csr_col: upload_sparse_operator):
 // uploaded once, at the first exit
 inline void Solver::exit_device_setup() {
@@ -179,7 +186,7 @@ inline void Solver::exit_device_setup() {
     xd.soc_len.alloc(std::max<size_t>(sl.size(), 1)); xd.soc_len.upload(sl.data(), sl.size(), stream);
     xd.slack.alloc(q1); xd.dc.alloc(n1);
     if (P.dense()) { xd.base.alloc(n1); xd.zero.alloc(n1); xd.zero.zero(stream); }
-    xd.feas_wg = grid_for(std::max<int64_t>(std::max(P.n - P.conelen, P.m), (int64_t)std::max(ones.size(), so.size())));
+    xd.feas_wg = exit_feas_grid(P.m);
     xd.part.alloc((size_t)4 * xd.feas_wg); xd.scal.alloc(4);
     PX_HIP(hipStreamSynchronize(stream));                    // (the host vectors above go out of scope)
     xd.ready = true;

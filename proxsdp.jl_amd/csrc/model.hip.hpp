@@ -7,10 +7,13 @@
 // solve   = Solver::reset_for_solve() + Solver::solve(): proxsdp_hip_solve_device on the model's current data, bit for bit
 // update  = the caller's new numbers through the recorded maps into the device arrays, the four norms, and -- when the zero
 //           pattern of c moved the support set -- setup_support() / alloc_candidates() once more
+// rows    = inequality rows added and dropped (model_rows.hip.hpp): the stages of the set-up that read Q, nnz or the pattern,
+//           again, on new buffers; everything sized by n or a cone side stays
 // The entry points (argument checks, error codes) are in capi.hip.
 #pragma once
 #include "exit_device.hip.hpp"
 #include "model_update.hip.hpp"
+#include "model_rows.hip.hpp"
 
 struct proxsdp_model {
     std::atomic<long long> bytes{0};            // live device bytes (DevAccount); first member: outlives every buffer below
@@ -21,6 +24,7 @@ struct proxsdp_model {
     proxsdp_problem shape{};                    // n, p, m, n_psd, psd_ptr: what those checks read of a problem
     int64_t solves = 0, updates = 0, support_rebuilds = 0;
     double setup_time = 0.0;
+    int index_base = 0;                         // of create: the columns of added rows follow it
     std::unique_ptr<proxsdp::Solver> S;
     proxsdp::DevBuf<int> csc_pos_d, csr_pos_d, sinv_d, flag_d;
     proxsdp::DevBuf<long long> ord_d;
@@ -34,7 +38,7 @@ struct proxsdp_model {
     };
 
     // o: validated options; the caller has refused what a handle does not serve
-    proxsdp_model(const proxsdp_problem& prob, const proxsdp_options& o) : opt0(o) {
+    proxsdp_model(const proxsdp_problem& prob, const proxsdp_options& o) : opt0(o), index_base(prob.index_base) {
         using namespace proxsdp;
         const double t0 = now_s();
         Accounting acct(*this);
@@ -214,15 +218,147 @@ struct proxsdp_model {
             s.b_host = P.b; s.h_host = P.h;
         }
         PX_HIP(hipStreamSynchronize(st));
-        if (moved != 0) {                                   // the support set changed: what setup_support() and alloc_candidates() built, again
-            for (EigWork& W : s.eig) { W.fop_ok = false; W.ell_w = 0; W.ov = dev::EllOverflow{}; }
-            s.ns = 0; s.rstride = 0; s.n_res_wg = 0; s.tile_base.clear(); s.supp_h.clear();
-            s.setup_support();
-            s.alloc_candidates();
-            upload_support_map();
-            ++support_rebuilds;
-        }
+        if (moved != 0) rebuild_support();
         ++updates;
+    }
+
+    // the support set changed: what setup_support() and alloc_candidates() built, again
+    void rebuild_support() {
+        using namespace proxsdp;
+        Solver& s = *S;
+        for (EigWork& W : s.eig) { W.fop_ok = false; W.ell_w = 0; W.ov = dev::EllOverflow{}; }
+        s.ns = 0; s.rstride = 0; s.n_res_wg = 0; s.tile_base.clear(); s.supp_h.clear();
+        s.setup_support();
+        s.alloc_candidates();
+        upload_support_map();
+        ++support_rebuilds;
+    }
+
+    // ch: validated on the host as far as no model is needed (check_rows_struct); the model's own refusals are the caller's.
+    // Order: plan (host; the last refusals) -> the finite check of device values -> every new buffer -> index uploads, the
+    // gathers, the host mirrors downloaded -> the new buffers and the Prep's changed members take the old ones' places ->
+    // the two norms, the mat-vec's launch shape, the support set.
+    void change_rows(proxsdp_model_rows& ch) {
+        using namespace proxsdp;
+        const double t0 = now_s();
+        Solver& s = *S;
+        Prep& P = s.P;
+        RowsPlan pl = plan_rows(P, index_base, ch);
+        PX_HIP(hipSetDevice(opt0.device_id));
+        Accounting acct(*this);
+        long long allocated = 0;
+        struct Count {
+            long long* prev;
+            explicit Count(long long* c) : prev(DevAccount::allocated) { DevAccount::allocated = c; }
+            ~Count() { DevAccount::allocated = prev; }
+        } count(&allocated);
+        hipStream_t st = s.stream;
+        const bool on_dev = ch.on_device != 0;
+        const int64_t na = ch.n_add, nnz_add = pl.nnz_add;
+        if (on_dev && na > 0) {                             // the finite check of device data: a reduction, before any write
+            flag_d.zero(st);
+            const double* src[2] = {ch.add_val, ch.add_h};
+            const int64_t len[2] = {nnz_add, na};
+            const char* name[2] = {"add_val", "add_h"};
+            for (int q = 0; q < 2; ++q)
+                if (len[q] > 0)
+                    hipLaunchKernelGGL(dev::k_exit_nonfinite, dim3(grid_for(len[q])), dim3(dev::TPB), 0, st, src[q],
+                                       (long long)len[q], flag_d.p + q);
+            PX_HIP(hipGetLastError());
+            int h[2] = {0, 0};
+            flag_d.download(h, 2, st);
+            PX_HIP(hipStreamSynchronize(st));
+            for (int q = 0; q < 2; ++q)
+                if (h[q]) throw std::invalid_argument(std::string("proxsdp_model_rows: non-finite entry in ") + name[q]);
+        }
+        s.restore_cert_data();                              // (a certificate search of the last solve zeroed c or [b; h])
+        bool supp_moved = false;                            // only a column that lost or gained an entry can enter or leave the set
+        for (int32_t k : pl.touched) supp_moved = supp_moved || in_support(P.colptr, P.c, k) != in_support(pl.R.colptr, P.c, k);
+        const Prep& R = pl.R;
+        const size_t nz = (size_t)std::max<int64_t>(R.nnz, 1), q1 = (size_t)std::max<int64_t>(R.Q, 1);
+        // ---- every new buffer, before the first write and before an old one goes
+        DevBuf<int> csr_ptr(R.Q + 1), csr_col(nz), csc_row(nz), cpos(nz), rpos(nz);
+        DevBuf<int> csc_src(nz), csr_src(nz), bh_src(q1), add_k((size_t)std::max<int64_t>(nnz_add, 1));
+        DevBuf<int> csc_ptr(R.n + 1);
+        DevBuf<double> csr_val(nz), csc_val(nz), cval(nz), rval(nz), bh(q1), xbh(q1), slack(q1);
+        DevBuf<double> ybuf[2], Mxbuf[2], ycand((size_t)NCAND * q1), xpart;
+        for (int k = 0; k < 2; ++k) { ybuf[k].alloc(q1); Mxbuf[k].alloc(q1); }
+        const int feas_old = s.xd.feas_wg;
+        const int feas_new = s.exit_feas_grid(R.m);
+        if (feas_new != feas_old) xpart.alloc((size_t)4 * feas_new);
+        const double* d_val = ch.add_val;
+        const double* d_h = ch.add_h;
+        if (!on_dev && na > 0) {                            // host values: through the staging buffer, the two arrays side by side
+            const size_t need = (size_t)(nnz_add + na);
+            if (stage.n < need) stage.alloc(std::max(need, (size_t)std::max<int64_t>(std::max(R.n, R.Q), std::max<int64_t>(R.nnz, 1))));
+        }
+        // ---- the index arrays from the plan, the numbers through the source maps
+        std::vector<int> rp((size_t)R.Q + 1), cp((size_t)R.n + 1);
+        for (int64_t i = 0; i <= R.Q; ++i) rp[i] = (int)R.rowptr[i];
+        for (int64_t i = 0; i <= R.n; ++i) cp[i] = (int)R.colptr[i];
+        csr_ptr.upload(rp.data(), rp.size(), st); csc_ptr.upload(cp.data(), cp.size(), st);
+        csr_col.upload(R.colidx.data(), R.nnz, st); csc_row.upload(R.rowidx.data(), R.nnz, st);
+        cpos.upload(R.csc_pos.data(), R.nnz, st); rpos.upload(R.csr_pos.data(), R.nnz, st);
+        csc_src.upload(pl.csc_src.data(), R.nnz, st); csr_src.upload(pl.csr_src.data(), R.nnz, st);
+        bh_src.upload(pl.bh_src.data(), R.Q, st); add_k.upload(pl.add_k.data(), nnz_add, st);
+        if (!on_dev && na > 0) {
+            stage.upload(ch.add_val, (size_t)nnz_add, st);
+            PX_HIP(hipMemcpyAsync(stage.p + nnz_add, ch.add_h, (size_t)na * sizeof(double), hipMemcpyHostToDevice, st));
+            d_val = stage.p; d_h = stage.p + nnz_add;
+        }
+        const double cte = std::sqrt(2.0) / 2.0;
+        if (R.nnz > 0) {
+            hipLaunchKernelGGL(dev::k_rows_values, dim3(grid_for(R.nnz)), dim3(dev::TPB), 0, st, (const int*)csc_src.p, (long long)R.nnz,
+                               (const double*)s.xd.cval.p, (const double*)s.csc_val.p, d_val, (const int*)add_k.p,
+                               (const unsigned char*)s.offdiag_d.p, cte, cval.p, csc_val.p);
+            hipLaunchKernelGGL(dev::k_rows_values, dim3(grid_for(R.nnz)), dim3(dev::TPB), 0, st, (const int*)csr_src.p, (long long)R.nnz,
+                               (const double*)s.xd.rval.p, (const double*)s.csr_val.p, d_val, (const int*)add_k.p,
+                               (const unsigned char*)s.offdiag_d.p, cte, rval.p, csr_val.p);
+        }
+        if (R.Q > 0)
+            hipLaunchKernelGGL(dev::k_rows_bh, dim3(grid_for(R.Q)), dim3(dev::TPB), 0, st, (const int*)bh_src.p, (long long)R.Q,
+                               (const double*)s.bh_d.p, d_h, bh.p, xbh.p);
+        PX_HIP(hipGetLastError());
+        for (int k = 0; k < 2; ++k) { ybuf[k].zero(st); Mxbuf[k].zero(st); }
+        ycand.zero(st); slack.zero(st);
+        // the host mirrors, the way update brings them up to date: from the device arrays
+        csc_val.download(pl.R.val.data(), R.nnz, st);
+        csr_val.download(pl.R.rval.data(), R.nnz, st);
+        cval.download(pl.R.val_orig.data(), R.nnz, st);
+        std::vector<double> bhh((size_t)R.Q);
+        bh.download(bhh.data(), R.Q, st);
+        PX_HIP(hipStreamSynchronize(st));
+        // ---- the new buffers take the old ones' places (nothing below this line throws before the Prep is the new one)
+        s.csr_ptr = std::move(csr_ptr); s.csr_col = std::move(csr_col); s.csr_val = std::move(csr_val);
+        s.csc_ptr = std::move(csc_ptr); s.csc_row = std::move(csc_row); s.csc_val = std::move(csc_val);
+        s.xd.cval = std::move(cval); s.xd.rval = std::move(rval); s.xd.bh = std::move(xbh); s.xd.slack = std::move(slack);
+        s.bh_d = std::move(bh);
+        for (int k = 0; k < 2; ++k) { s.ybuf[k] = std::move(ybuf[k]); s.Mxbuf[k] = std::move(Mxbuf[k]); }
+        s.ycand_d = std::move(ycand);
+        if (feas_new != feas_old) { s.xd.part = std::move(xpart); s.xd.feas_wg = feas_new; }
+        csc_pos_d = std::move(cpos); csr_pos_d = std::move(rpos);
+        std::copy(bhh.begin() + R.p, bhh.end(), pl.R.h.begin());
+        pl.R.h_orig = pl.R.h;
+        commit_rows(P, pl);
+        s.b_host = P.b; s.h_host = P.h;
+        shape.m = P.m;
+        if (on_dev) {
+            P.norm_h = model_norm2(st, s.bh_d.p + P.p, P.m, npart, nout);
+            P.frob = model_norm2(st, s.csc_val.p, P.nnz, npart, nout);
+        } else {
+            rows_host_norms(P);
+        }
+        // ---- what the set-up derives from the pattern: the mat-vec's shape, the support set
+        s.n_seg = 0; s.n_long = 0;
+        s.choose_spmv_shape(rp);
+        ch.support_rebuilt = 0;
+        // a changed set matters where the support path runs, or would now (the auto rule reads the set's size)
+        if (supp_moved && (s.use_support || s.support_path_wanted(s.support_list().size()))) { rebuild_support(); ch.support_rebuilt = 1; }
+        PX_HIP(hipStreamSynchronize(st));
+        ch.m_new = P.m; ch.nnz_new = P.nnz;
+        if (ch.kept) std::copy(pl.kept.begin(), pl.kept.end(), ch.kept);
+        ch.bytes_allocated = allocated;
+        ch.seconds = now_s() - t0;
     }
 
     void info(proxsdp_model_info& out) const {

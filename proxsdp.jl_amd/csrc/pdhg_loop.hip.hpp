@@ -888,13 +888,18 @@ inline void Solver::upload_support(const std::vector<int>& supp) {
     esv_d.alloc((size_t)2 * std::max(ns, 1)); esv_d.zero(stream);
     PX_HIP(hipStreamSynchronize(stream));                 // host vectors go out of scope
 }
+// does a model whose support list has `ns` entries run the support path (the options, the cones, the auto rule)
+inline bool Solver::support_path_wanted(size_t ns) const {
+    // (without linesearch the support path runs on request -- support_path = 1 -- and inside a block-sharded solve, which is built on it)
+    if (opt.support_path == 0 || (!opt.line_search_flag && opt.support_path < 0)) return false;
+    if (!P.socs.empty() || !one_blocks.empty() || P.blocks.empty()) return false;
+    if (opt.support_path < 0 && (8 * (int64_t)ns > P.n || P.n < 4096)) return false;   // auto: only when it pays
+    return true;
+}
 inline void Solver::setup_support() {
     use_support = false;
-    // (without linesearch the support path runs on request -- support_path = 1 -- and inside a block-sharded solve, which is built on it)
-    if (opt.support_path == 0 || (!opt.line_search_flag && opt.support_path < 0)) return;
-    if (!P.socs.empty() || !one_blocks.empty() || P.blocks.empty()) return;
     const std::vector<int> supp = support_list();
-    if (opt.support_path < 0 && (8 * (int64_t)supp.size() > P.n || P.n < 4096)) return;   // auto: only when it pays
+    if (!support_path_wanted(supp.size())) return;
     upload_support(supp);
     // residual partial slots: one per reconstruction tile of every block + the tail workgroups
     tile_base.clear();
@@ -1001,6 +1006,11 @@ inline void Solver::upload_sparse_operator() {
     csr_col.upload(P.colidx.data(), P.nnz, stream); csr_val.upload(P.rval.data(), P.nnz, stream);
     csc_row.upload(P.rowidx.data(), P.nnz, stream); csc_val.upload(P.val.data(), P.nnz, stream);
     PX_HIP(hipStreamSynchronize(stream));
+    choose_spmv_shape(rp);
+}
+// what M x derives from the row pointers rp: a wave per row above 8 entries a row on average, and the segments of the long
+// rows (a model handle takes both again when its rows change)
+inline void Solver::choose_spmv_shape(const std::vector<int>& rp) {
     csr_wave = P.Q > 0 && (double)P.nnz / (double)P.Q > 8.0;
     setup_long_rows(rp);
 }

@@ -69,7 +69,11 @@ struct HipError : std::runtime_error { using std::runtime_error::runtime_error; 
 
 // Where the device buffers allocated on this thread are counted (proxsdp_model_info.device_bytes): a model handle points it
 // at its own counter for the length of a call, the block workers inherit it (start_block_workers); null everywhere else.
-struct DevAccount { static inline thread_local std::atomic<long long>* sink = nullptr; };
+// `allocated`: where a call that wants to know what IT allocated (proxsdp_model_rows.bytes_allocated) has the bytes added up.
+struct DevAccount {
+    static inline thread_local std::atomic<long long>* sink = nullptr;
+    static inline thread_local long long* allocated = nullptr;
+};
 
 template <typename T>
 struct DevBuf {
@@ -100,6 +104,7 @@ struct DevBuf {
         acct = DevAccount::sink;
         held = count * sizeof(T);
         if (acct) acct->fetch_add((long long)held);
+        if (DevAccount::allocated) *DevAccount::allocated += (long long)held;
     }
     void release() {
         if (p) { (void)hipFree(p); p = nullptr; if (acct) acct->fetch_sub((long long)held); }
@@ -748,6 +753,7 @@ private:
     DevBuf<double> segpart_d;
     int n_seg = 0, n_long = 0;
     void setup_long_rows(const std::vector<int>& rp);
+    void choose_spmv_shape(const std::vector<int>& rp);
 
     // scalar state (Params, structs.jl:159-192) that init_parameters() and reduce_global_constants() set; the rest is SolveState's
     double theta = 1, beta = 1, adapt_level = 0.9;
@@ -777,6 +783,7 @@ private:
     void setup_support();
     void setup_dense();
     std::vector<int> support_list() const;
+    bool support_path_wanted(size_t ns) const;
     void upload_support(const std::vector<int>& supp);
     void upload_sparse_operator();
     void launch_clamp_scalars(double* x, int cnt);
@@ -859,6 +866,7 @@ private:
     } xd;
     void exit_rescale_iterate();
     void exit_device_setup();
+    int exit_feas_grid(int64_t m) const;
     void exit_form_vectors(bool zero_c);
     void exit_cone_violations(double viol[4]);
     void exit_write_vectors(const proxsdp_device_vectors* dv, double* primal, double* dual_cone, double* dual_eq,

@@ -118,13 +118,26 @@ class Optimizer:
         return sol
 
     def reoptimize(self, c=None, b=None, h=None, A_values=None, G_values=None, start=None, factors=False, device_out=False,
-                   trace_capacity=0):
+                   trace_capacity=0, add_rows=None, drop_rows=None):
         """After optimize(..., keep_model=True): replace data of the same shape (binding.Model.update: c, b, h as
         problem.c / .b / .h hold them -- c in the minimisation form, already sign-flipped for a max_sense problem --,
         A_values / G_values = the stored entries in sorted CSC order) and solve again on the kept model.  The sign and
-        constant fix-up of optimize() applies: a max_sense problem keeps its sign."""
+        constant fix-up of optimize() applies: a max_sense problem keeps its sign.
+        add_rows = (G_new, h_new) / drop_rows = row numbers: inequality rows added and dropped first
+        (binding.Model.change_rows), before any value update; the optimizer's own problem (self.problem.G, .h) follows, so
+        the getters and a later reoptimize(h=...) see the new shape; a start= that is a previous result of the old shape is
+        carried over (its dual_in re-indexed, zeros on the new rows)."""
         if getattr(self, "model", None) is None:
             raise ValueError("reoptimize() needs optimize(..., keep_model=True) first")
+        if add_rows is not None or drop_rows is not None:
+            m_old = self.problem.G.shape[0]
+            ch = self.model.change_rows(add=add_rows, drop=drop_rows)
+            self._follow_rows(ch, add_rows)
+            # a previous result can only be of the old shape; a dictionary is carried when its dual_in says so
+            if isinstance(start, binding.SolveResult):
+                start = ch.carry(start)
+            elif start is not None and start.get("dual_in") is not None and len(start["dual_in"]) == m_old != ch.m:
+                start = ch.carry(start)
         if any(v is not None for v in (c, b, h, A_values, G_values)):
             self.model.update(c=c, b=b, h=h, A_values=A_values, G_values=G_values)
         sol = self.model.solve(start=start, factors=factors, device_out=device_out, trace_capacity=trace_capacity)
@@ -133,6 +146,23 @@ class Optimizer:
         sol.dual_objval = sign * sol.dual_objval + self.problem.objective_constant
         self.sol = sol
         return sol
+
+    def _follow_rows(self, ch, add_rows):
+        """self.problem with the rows of the kept model: G' = [kept rows; new rows], h' likewise (host copies)"""
+        import dataclasses
+        import numpy as np
+        import scipy.sparse as sp
+        pr = self.problem
+        k_old = ch.kept[ch.kept >= 0]
+        G = sp.csr_matrix(pr.G, dtype=np.float64)[k_old, :]
+        hh = np.asarray(pr.h, dtype=np.float64)[k_old]
+        if add_rows is not None:
+            _, ptr, cols, vals, h_new = binding._rows_arguments(add_rows, None, pr.n)
+            to_np = lambda v: v.detach().cpu().numpy() if binding._is_tensor(v) else np.asarray(v, dtype=np.float64)
+            Gn = sp.csr_matrix((to_np(vals).ravel(), cols, ptr), shape=(len(ptr) - 1, pr.n))
+            G = sp.vstack([G, Gn], format="csr")
+            hh = np.concatenate([hh, to_np(h_new).ravel()])
+        self.problem = dataclasses.replace(pr, G=sp.csc_matrix(G), h=hh)
 
     # -- attributes set by optimize
     def termination_status(self):
