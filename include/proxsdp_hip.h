@@ -76,7 +76,11 @@ extern "C" {
  * existing struct changed: the version stays;
  * later: proxsdp_hip_model_rows (inequality rows of a model handle added and dropped in place) with the new struct
  * proxsdp_model_rows and the test entry proxsdp_host_model_rows_plan: functions and one new struct, no existing struct
- * changed: the version stays */
+ * changed: the version stays;
+ * later: proxsdp_hip_model_triangles (the most violated triangle inequalities of a PSD cone of a model handle, separated on
+ * the device) with its host restatement proxsdp_host_triangle_cuts, and proxsdp_hip_model_inactive_rows (the inequality rows
+ * that went slack), with the new structs proxsdp_triangle_cuts and proxsdp_inactive_rows: functions and two new structs, no
+ * existing struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -898,6 +902,85 @@ typedef struct proxsdp_model_rows {
     double  seconds;          /* wall time of the call */
 } proxsdp_model_rows;
 int  proxsdp_hip_model_rows(proxsdp_model* mdl, proxsdp_model_rows* ch);
+/* ------------------------------------------- separation on a model handle: violated triangle inequalities, slack rows
+ * The other two verbs of the loop above.  The reference has no counterpart.
+ * TRIANGLES.  For PSD cone `cone` of the handle (side s >= 3), X = the symmetric matrix of the cone's entries of `primal`
+ * (n doubles, the caller's variable order, the units a result holds; the cone's variable list is its upper triangle, column
+ * by column).  For 0 <= i < j < k < s and the patterns
+ *     0: (-1, -1, -1)    1: (-1, +1, +1)    2: (+1, -1, +1)    3: (+1, +1, -1)
+ * the inequality s1 X_ij + s2 X_ik + s3 X_jk <= rhs has the violation
+ *     v = ((s1 * X_ij + s2 * X_ik) + s3 * X_jk) - rhs      fp64, left to right in this association, no contraction
+ * (a product with +-1 is exact: any IEEE restatement gives the same bits).  The call returns the min(count, violated) rows
+ * with the largest v among those with v > min_violation, ordered by v descending, equal v by (i, j, k, pattern) ascending;
+ * that order also decides which rows of equal violation survive the cut-off.  `violated` counts ALL rows with
+ * v > min_violation.  The result is a pure function of the inputs: the same rows and bits on every run, whatever the launch.
+ * Outputs are HOST arrays, caller-allocated for `count` rows; entries past n_rows are not written.  add_col / add_val / add_h
+ * with add_ptr = 0, 3, 6, ... are a proxsdp_model_rows change as they stand (add_col: the variables of X_ij, X_ik, X_jk in the
+ * caller's numbering and the index base of create; add_val: the signs; add_h: rhs).
+ * The handle's data is not touched: a solve after the call equals a solve before it bit for bit.  Scratch (the dense X of
+ * 8 s^2 bytes, 2^12 counters, 16 cand_cap bytes of candidates) is allocated in the call, released before it returns and
+ * reported in bytes_allocated, not in proxsdp_model_info.device_bytes; a host `primal` is expanded to X on the host.
+ * How: a sweep over all C(s, 3) triples, once per pass of a radix select on the key (bits of v, then the index of
+ * (i, j, k, pattern)) in digits of 12 bits -- a histogram pass per digit until at most cand_cap rows lie at or above the
+ * prefix, then one pass that emits those; the host sorts them.  cand_cap = 0: max(4 count, 65536); a smaller value (at
+ * least count is used) only forces more passes -- a test knob.
+ * PROXSDP_E_INVALID, decided on the host before any device call: a NULL struct or handle; a wrong struct_size; on_device
+ * other than 0 or 1; count < 1 or > 2^20; min_violation negative or not finite; rhs not finite; cand_cap < 0 or > 2^24; a
+ * NULL primal; a NULL output array; a cone number outside the model; a cone of side < 3.  A non-finite entry of the cone's
+ * part of primal: a host primal is checked by a host loop, a device primal by a reduction on the device before the sweep;
+ * the message names the cone. */
+typedef struct proxsdp_triangle_cuts {
+    int64_t struct_size;      /* = sizeof(proxsdp_triangle_cuts) */
+    int32_t on_device;        /* where primal lives: 0 host, 1 DEVICE pointer on the model's device, borrowed and trusted as
+                               * proxsdp_model_data's are (proxsdp_host_triangle_cuts ignores it) */
+    int32_t cone;             /* PSD cone of the model, 0-based in cone order (proxsdp_host_triangle_cuts ignores it) */
+    int64_t count;            /* rows wanted: 1 .. 2^20 */
+    double  min_violation;    /* >= 0 */
+    double  rhs;
+    int64_t cand_cap;         /* 0 = default; test knob */
+    const double* primal;     /* n doubles (proxsdp_host_triangle_cuts ignores it: it is given X) */
+    /* out: caller-allocated HOST arrays for `count` rows */
+    int64_t* tri;             /* 3 per row: 0-based i < j < k */
+    int32_t* pattern;
+    double*  violation;
+    int64_t* add_col;         /* 3 per row */
+    double*  add_val;         /* 3 per row */
+    double*  add_h;
+    int64_t n_rows;           /* rows written: min(count, violated) */
+    int64_t violated;         /* all rows with v > min_violation */
+    int64_t scanned;          /* 4 C(s, 3) */
+    int32_t passes;           /* sweeps over the triples (0 on the host) */
+    int32_t reserved;
+    int64_t bytes_allocated;  /* device bytes this call allocated (and released) */
+    double  seconds;          /* wall time of the call */
+    double  sweep_seconds;    /* the first sweep alone, between two device events */
+} proxsdp_triangle_cuts;
+int  proxsdp_hip_model_triangles(proxsdp_model* mdl, proxsdp_triangle_cuts* tc);
+/* The same contract with no device and no handle: a serial enumeration with the expression above and a partial sort under the
+ * same order.  X: the side x side matrix itself, row-major, symmetric, only i < j read.  cone_idx: the cone's variable list
+ * (side (side + 1) / 2 numbers, upper triangle column by column) as add_col shall report it, or NULL = tri_index(i, j) +
+ * index_base with tri_index(i, j) = j (j + 1) / 2 + i.  PROXSDP_E_INVALID: as above where it applies; NULL X; side < 3 or
+ * > 46340; index_base other than 0 or 1; a non-finite X_ij, i < j. */
+int  proxsdp_host_triangle_cuts(const double* X, int64_t side, const int64_t* cone_idx, int32_t index_base,
+                                proxsdp_triangle_cuts* tc);
+/* SLACK ROWS.  Given dual_in and slack_in of a result of the handle's current model (m doubles each, both host or both
+ * device; slack_in = G x - h), the inequality rows r with |dual_in[r]| <= dual_tol and slack_in[r] < -slack_tol, as ascending
+ * 0-based numbers in `rows` (HOST, caller-allocated, m entries; n_rows of them written): a `drop` list for
+ * proxsdp_hip_model_rows.  A NaN in either vector fails its comparison: such a row is "not inactive"; it is not refused.
+ * m = 0 gives 0 rows.  Device vectors are flagged and compacted by one kernel whose output order is the rows' own; its
+ * scratch (8 m bytes) is released before the call returns.  PROXSDP_E_INVALID, on the host: a NULL struct, handle or array;
+ * a wrong struct_size; on_device other than 0 or 1; a negative or non-finite tolerance. */
+typedef struct proxsdp_inactive_rows {
+    int64_t struct_size;      /* = sizeof(proxsdp_inactive_rows) */
+    int32_t on_device;        /* dual_in and slack_in: 0 host, 1 DEVICE pointers on the model's device */
+    int32_t reserved;
+    const double* dual_in;    /* m */
+    const double* slack_in;   /* m */
+    double dual_tol, slack_tol;
+    int64_t* rows;            /* out: HOST, m entries */
+    int64_t n_rows;           /* out */
+} proxsdp_inactive_rows;
+int  proxsdp_hip_model_inactive_rows(proxsdp_model* mdl, proxsdp_inactive_rows* q);
 /* test entry: the model's current internal data, downloaded into caller-allocated host arrays.  The sizes (n, Q = p + m, nnz,
  * ns = length of the support list, 0 when the support path is off) and the four norms (||b||, ||h||, ||c||, ||M||_F) are always
  * written; an array is written when its pointer is not NULL (call once with every pointer NULL for the sizes, allocate, call

@@ -410,4 +410,123 @@ function chambolle_pock_hip(aff, con, options; ResultType = Main.ProxSDP.Result,
     return result, out
 end
 
+# ---- separation on a kept model (include/proxsdp_hip.h, "separation on a model handle").  `mdl` is the opaque handle of
+# proxsdp_hip_model_create as a Ptr{Cvoid}.  (Like the rest of this file these cannot be executed where the library is tested;
+# the structs are checked against the header field by field, the entries through the ctypes binding.)
+mutable struct TriangleCuts      # proxsdp_triangle_cuts
+    struct_size::Int64
+    on_device::Int32
+    cone::Int32
+    count::Int64
+    min_violation::Float64
+    rhs::Float64
+    cand_cap::Int64
+    primal::Ptr{Float64}
+    tri::Ptr{Int64}
+    pattern::Ptr{Int32}
+    violation::Ptr{Float64}
+    add_col::Ptr{Int64}
+    add_val::Ptr{Float64}
+    add_h::Ptr{Float64}
+    n_rows::Int64
+    violated::Int64
+    scanned::Int64
+    passes::Int32
+    reserved::Int32
+    bytes_allocated::Int64
+    seconds::Float64
+    sweep_seconds::Float64
+end
+
+mutable struct InactiveRows      # proxsdp_inactive_rows
+    struct_size::Int64
+    on_device::Int32
+    reserved::Int32
+    dual_in::Ptr{Float64}
+    slack_in::Ptr{Float64}
+    dual_tol::Float64
+    slack_tol::Float64
+    rows::Ptr{Int64}
+    n_rows::Int64
+end
+
+function _check_rc(rc)
+    rc == 0 && return
+    msg = unsafe_string(ccall((:proxsdp_hip_last_error, libproxsdp_hip), Cstring, ()))
+    error("libproxsdp_hip: error $(rc): $(msg)")
+end
+
+function _triangle_result(tc::TriangleCuts, tri, pattern, violation, add_col, add_val, add_h)
+    k = Int(tc.n_rows)
+    (triples = permutedims(reshape(tri[1:3k], 3, k)), patterns = pattern[1:k], violations = violation[1:k],
+     add_ptr = collect(Int64(0):Int64(3):Int64(3k)), add_col = add_col[1:3k], add_val = add_val[1:3k], add_h = add_h[1:k],
+     violated = tc.violated, scanned = tc.scanned, passes = tc.passes, seconds = tc.seconds)
+end
+
+"""
+    model_triangles(mdl, primal; cone = 1, count = 1000, min_violation = 1e-3, rhs = 1.0, cand_cap = 0, on_device = false)
+
+The `count` most violated triangle inequalities of PSD cone `cone` (1-based here, in cone order) of the kept model `mdl` at
+`primal`: a `Vector{Float64}` of n entries, or with `on_device = true` a DEVICE pointer (`Ptr{Float64}`) on the model's
+device.  Returns a NamedTuple; `triples` are 0-based `i < j < k` as the library reports them, `add_ptr` / `add_col` /
+`add_val` / `add_h` are a `proxsdp_model_rows` change as they stand (`add_col` in the index base of create: 1-based for a
+model created from Julia data).
+"""
+function model_triangles(mdl::Ptr{Cvoid}, primal; cone::Integer = 1, count::Integer = 1000, min_violation::Real = 1e-3,
+                         rhs::Real = 1.0, cand_cap::Integer = 0, on_device::Bool = false)
+    tri = zeros(Int64, 3count); pattern = zeros(Int32, count); violation = zeros(count)
+    add_col = zeros(Int64, 3count); add_val = zeros(3count); add_h = zeros(count)
+    GC.@preserve primal tri pattern violation add_col add_val add_h begin
+        tc = TriangleCuts(sizeof(TriangleCuts), Int32(on_device), Int32(cone - 1), count, min_violation, rhs, cand_cap,
+                          on_device ? Ptr{Float64}(primal) : pointer(primal), pointer(tri), pointer(pattern), pointer(violation),
+                          pointer(add_col), pointer(add_val), pointer(add_h), 0, 0, 0, Int32(0), Int32(0), 0, 0.0, 0.0)
+        _check_rc(ccall((:proxsdp_hip_model_triangles, libproxsdp_hip), Cint, (Ptr{Cvoid}, Ref{TriangleCuts}), mdl, tc))
+    end
+    return _triangle_result(tc, tri, pattern, violation, add_col, add_val, add_h)
+end
+
+"""
+    host_triangle_cuts(X; count = 1000, min_violation = 1e-3, rhs = 1.0, cone_idx = nothing, index_base = 1)
+
+The same separation on the host, serially, for a symmetric `Matrix{Float64}` (no device, no handle).  `cone_idx`: the cone's
+variable list (upper triangle column by column, `SDPSet.vec_i`) as `add_col` shall report it; `nothing`: the position in that
+list plus `index_base`.
+"""
+function host_triangle_cuts(X::Matrix{Float64}; count::Integer = 1000, min_violation::Real = 1e-3, rhs::Real = 1.0,
+                            cone_idx::Union{Nothing,Vector{Int64}} = nothing, index_base::Integer = 1)
+    side = size(X, 1)
+    size(X, 2) == side || error("X must be square")
+    tri = zeros(Int64, 3count); pattern = zeros(Int32, count); violation = zeros(count)
+    add_col = zeros(Int64, 3count); add_val = zeros(3count); add_h = zeros(count)
+    GC.@preserve X cone_idx tri pattern violation add_col add_val add_h begin
+        tc = TriangleCuts(sizeof(TriangleCuts), Int32(0), Int32(0), count, min_violation, rhs, 0, Ptr{Float64}(C_NULL),
+                          pointer(tri), pointer(pattern), pointer(violation), pointer(add_col), pointer(add_val), pointer(add_h),
+                          0, 0, 0, Int32(0), Int32(0), 0, 0.0, 0.0)
+        # (a symmetric matrix is its own transpose: Julia's column-major storage is the row-major X the entry reads)
+        _check_rc(ccall((:proxsdp_host_triangle_cuts, libproxsdp_hip), Cint,
+                        (Ptr{Float64}, Int64, Ptr{Int64}, Int32, Ref{TriangleCuts}),
+                        X, side, cone_idx === nothing ? Ptr{Int64}(C_NULL) : pointer(cone_idx), Int32(index_base), tc))
+    end
+    return _triangle_result(tc, tri, pattern, violation, add_col, add_val, add_h)
+end
+
+"""
+    model_inactive_rows(mdl, dual_in, slack_in, m; dual_tol = 0.0, slack_tol = 1e-6, on_device = false)
+
+The inequality rows of the kept model `mdl` (m of them) with `|dual_in[r]| <= dual_tol` and `slack_in[r] < -slack_tol`, as
+ascending 0-BASED numbers: the `drop` list of `proxsdp_hip_model_rows`.  `dual_in` / `slack_in`: `Vector{Float64}`s of a
+`Result`, or with `on_device = true` DEVICE pointers.  A NaN row is not inactive.
+"""
+function model_inactive_rows(mdl::Ptr{Cvoid}, dual_in, slack_in, m::Integer; dual_tol::Real = 0.0, slack_tol::Real = 1e-6,
+                             on_device::Bool = false)
+    rows = zeros(Int64, max(m, 1))
+    GC.@preserve dual_in slack_in rows begin
+        q = InactiveRows(sizeof(InactiveRows), Int32(on_device), Int32(0),
+                         on_device ? Ptr{Float64}(dual_in) : pointer(dual_in), on_device ? Ptr{Float64}(slack_in) : pointer(slack_in),
+                         dual_tol, slack_tol, pointer(rows), 0)
+        _check_rc(ccall((:proxsdp_hip_model_inactive_rows, libproxsdp_hip), Cint, (Ptr{Cvoid}, Ref{InactiveRows}), mdl, q))
+    end
+    return rows[1:Int(q.n_rows)]
+end
+
 end # module

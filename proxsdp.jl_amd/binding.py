@@ -233,6 +233,22 @@ class ModelRows(C.Structure):
                 ("bytes_allocated", i64), ("seconds", f64)]
 
 
+class TriangleCutsIO(C.Structure):
+    """proxsdp_triangle_cuts (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("on_device", i32), ("cone", i32), ("count", i64), ("min_violation", f64),
+                ("rhs", f64), ("cand_cap", i64), ("primal", pf64),
+                ("tri", pi64), ("pattern", C.POINTER(i32)), ("violation", pf64), ("add_col", pi64), ("add_val", pf64),
+                ("add_h", pf64),
+                ("n_rows", i64), ("violated", i64), ("scanned", i64), ("passes", i32), ("reserved", i32),
+                ("bytes_allocated", i64), ("seconds", f64), ("sweep_seconds", f64)]
+
+
+class InactiveRowsIO(C.Structure):
+    """proxsdp_inactive_rows (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("on_device", i32), ("reserved", i32), ("dual_in", pf64), ("slack_in", pf64),
+                ("dual_tol", f64), ("slack_tol", f64), ("rows", pi64), ("n_rows", i64)]
+
+
 MODEL_DUMP_ARRAYS = (("csc_val", "nnz"), ("csr_val", "nnz"), ("csc_val_orig", "nnz"), ("csr_val_orig", "nnz"),
                      ("c", "n"), ("c_orig", "n"), ("bh", "Q"), ("support", "ns"), ("cS", "ns"))
 MODEL_NORM_NAMES = ("norm_b", "norm_h", "norm_c", "frob")
@@ -301,6 +317,9 @@ def lib():
     L.proxsdp_host_model_prepare.argtypes = [C.POINTER(Problem), C.POINTER(ModelDump), pi64, C.POINTER(i32), C.POINTER(i32)]
     L.proxsdp_hip_model_rows.argtypes = [C.c_void_p, C.POINTER(ModelRows)]
     L.proxsdp_host_model_rows_plan.argtypes = [C.POINTER(Problem), C.POINTER(ModelRows), C.POINTER(ModelDump)] + [C.POINTER(i32)] * 5
+    L.proxsdp_hip_model_triangles.argtypes = [C.c_void_p, C.POINTER(TriangleCutsIO)]
+    L.proxsdp_host_triangle_cuts.argtypes = [pf64, i64, pi64, i32, C.POINTER(TriangleCutsIO)]
+    L.proxsdp_hip_model_inactive_rows.argtypes = [C.c_void_p, C.POINTER(InactiveRowsIO)]
     L.proxsdp_hip_factor_residual.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64]
     L.proxsdp_hip_factor_residual_kernel.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64, i32, pf64]
     L.proxsdp_hip_psd_project.argtypes = [pf64, i64, i32, i32, C.POINTER(Options), pf64, pf64,
@@ -1028,6 +1047,64 @@ class RowsChange:
         return d
 
 
+class TriangleCuts:
+    """What a triangle separation returned (proxsdp_triangle_cuts): triples (rows x 3, 0-based i < j < k), patterns,
+    violations (descending; equal ones by (i, j, k, pattern)), violated (all rows above min_violation), scanned, passes,
+    seconds, sweep_seconds, bytes_allocated, and add = ((rowptr, cols, values), h) with 0-based cols: what
+    Model.change_rows(add=...) and Optimizer.reoptimize(add_rows=...) take.  raw: add_col / add_val / add_h as the library
+    wrote them (add_col in the index base of the model); arrays: every output array at its full length of `count` rows."""
+
+    def __init__(self, T, arr, index_base):
+        k = int(T.n_rows)
+        self.arrays = arr
+        self.triples = arr["tri"].reshape(-1, 3)[:k].copy()
+        self.patterns = arr["pattern"][:k].copy()
+        self.violations = arr["violation"][:k].copy()
+        self.violated, self.scanned, self.passes = int(T.violated), int(T.scanned), int(T.passes)
+        self.seconds, self.sweep_seconds = float(T.seconds), float(T.sweep_seconds)
+        self.bytes_allocated = int(T.bytes_allocated)
+        self.raw = dict(add_col=arr["add_col"][:3 * k].copy(), add_val=arr["add_val"][:3 * k].copy(), add_h=arr["add_h"][:k].copy())
+        self.add = ((3 * np.arange(k + 1, dtype=np.int64), self.raw["add_col"] - index_base, self.raw["add_val"]),
+                    self.raw["add_h"])
+
+    def __len__(self):
+        return len(self.patterns)
+
+
+def _triangle_struct(count, min_violation, rhs, cand_cap, sentinel=None):
+    """proxsdp_triangle_cuts with output arrays for `count` rows (prefilled with `sentinel` when given), and the arrays"""
+    n = max(int(count), 1) if -(1 << 40) < int(count) < (1 << 24) else 1      # (an absurd count is the library's to refuse)
+    arr = dict(tri=np.zeros(3 * n, dtype=np.int64), pattern=np.zeros(n, dtype=np.int32), violation=np.zeros(n),
+               add_col=np.zeros(3 * n, dtype=np.int64), add_val=np.zeros(3 * n), add_h=np.zeros(n))
+    if sentinel is not None:
+        for a in arr.values():
+            a[:] = sentinel
+    T = TriangleCutsIO()
+    T.struct_size = C.sizeof(TriangleCutsIO)
+    T.count, T.min_violation, T.rhs, T.cand_cap = int(count), float(min_violation), float(rhs), int(cand_cap)
+    T.tri, T.add_col = _p(arr["tri"], pi64), _p(arr["add_col"], pi64)
+    T.pattern = arr["pattern"].ctypes.data_as(C.POINTER(i32))
+    T.violation, T.add_val, T.add_h = _p(arr["violation"]), _p(arr["add_val"]), _p(arr["add_h"])
+    return T, arr
+
+
+def host_triangle_cuts(X, count=1000, min_violation=1e-3, rhs=1.0, cone_idx=None, index_base=0, sentinel=None):
+    """proxsdp_host_triangle_cuts: the separation of Model.separate_triangles on the host, serially (no device, no handle).
+    X: the symmetric side x side matrix; cone_idx: the cone's variable list as add_col shall report it (None: tri_index +
+    index_base).  Returns a TriangleCuts; its `arrays` are the output arrays at full length (entries past the rows returned
+    keep `sentinel`)."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != X.shape[1]:
+        raise ValueError("host_triangle_cuts: X must be square")
+    T, arr = _triangle_struct(count, min_violation, rhs, 0, sentinel)
+    idx = None if cone_idx is None else _i(cone_idx)
+    if idx is not None and len(idx) != X.shape[0] * (X.shape[0] + 1) // 2:
+        raise ValueError("host_triangle_cuts: cone_idx must list the upper triangle")
+    _check(lib().proxsdp_host_triangle_cuts(_p(X if X.size else np.zeros(1)), X.shape[0], None if idx is None else _p(idx, pi64),
+                                            int(index_base), C.byref(T)))
+    return TriangleCuts(T, arr, index_base)
+
+
 def model_norm2(v, grid=0):
     """proxsdp_hip_model_norm2: ||v||_2 by the reduction a device-route Model.update uses, with `grid` workgroups"""
     v = _f(v).ravel()
@@ -1164,6 +1241,69 @@ class Model:
         self.m = int(R.m_new)
         self._nnz = (self._nnz[0], int(R.nnz_new) - self._nnz[0])
         return RowsChange(R, kept[:self.m].copy())
+
+    # ---- separation
+    def separate_triangles(self, primal, cone=0, count=1000, min_violation=1e-3, rhs=1.0, cand_cap=0):
+        """proxsdp_hip_model_triangles: the `count` most violated triangle inequalities of PSD cone `cone` at `primal` -- a
+        NumPy array (host route), a CUDA float64 tensor (device route) or a SolveResult (its primal) of n entries.  Returns a
+        TriangleCuts; change_rows(add=cuts.add) appends the rows.  The model is not touched."""
+        if isinstance(primal, SolveResult):
+            primal = primal.primal
+        if primal is None:
+            raise ValueError("Model.separate_triangles: the result holds no primal (solve(primal=True))")
+        T, arr = _triangle_struct(count, min_violation, rhs, cand_cap)
+        T.cone = int(cone)
+        if _is_tensor(primal) and primal.is_cuda:
+            import torch
+            dev_id = int(self._options.device_id)
+            T.on_device = 1
+            T.primal = _device_ptr(primal, self.n, dev_id, "primal")
+            keep = primal
+            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
+        else:
+            keep = _f(primal.numpy() if _is_tensor(primal) else primal).ravel()
+            if len(keep) != self.n:
+                raise ValueError(f"Model.separate_triangles: primal must have {self.n} entries")
+            T.primal = _p(keep if len(keep) else np.zeros(1))
+        _check(lib().proxsdp_hip_model_triangles(self._handle(), C.byref(T)))
+        del keep
+        return TriangleCuts(T, arr, getattr(self, "_index_base", 0))
+
+    def inactive_rows(self, result_or_pair, dual_tol=0.0, slack_tol=1e-6):
+        """proxsdp_hip_model_inactive_rows: the inequality rows r with |dual_in[r]| <= dual_tol and slack_in[r] < -slack_tol
+        (slack_in = G x - h) as an ascending int64 array of 0-based numbers -- a drop list for change_rows.  result_or_pair: a
+        SolveResult or (dual_in, slack_in), both NumPy or both CUDA float64 tensors.  A NaN row is not inactive."""
+        if isinstance(result_or_pair, SolveResult):
+            dual, slack = result_or_pair.dual_in, result_or_pair.slack_in
+        else:
+            dual, slack = result_or_pair
+        on_dev = [_is_tensor(v) and v.is_cuda for v in (dual, slack)]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("Model.inactive_rows: host arrays and CUDA tensors cannot be mixed in one call")
+        Q = InactiveRowsIO()
+        Q.struct_size = C.sizeof(InactiveRowsIO)
+        Q.dual_tol, Q.slack_tol = float(dual_tol), float(slack_tol)
+        rows = np.zeros(max(self.m, 1), dtype=np.int64)
+        Q.rows = _p(rows, pi64)
+        if all(on_dev):
+            import torch
+            dev_id = int(self._options.device_id)
+            Q.on_device = 1
+            keep = [dual, slack]
+            if self.m:
+                Q.dual_in, Q.slack_in = _device_ptr(dual, self.m, dev_id, "dual_in"), _device_ptr(slack, self.m, dev_id, "slack_in")
+            else:                                            # (no row: any non-NULL address, never read)
+                Q.dual_in = Q.slack_in = _p(np.zeros(1))
+            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
+        else:
+            keep = [_f(v.numpy() if _is_tensor(v) else v).ravel() for v in (dual, slack)]
+            if any(len(a) != self.m for a in keep):
+                raise ValueError(f"Model.inactive_rows: dual_in and slack_in must have {self.m} entries")
+            keep = [a if len(a) else np.zeros(1) for a in keep]
+            Q.dual_in, Q.slack_in = _p(keep[0]), _p(keep[1])
+        _check(lib().proxsdp_hip_model_inactive_rows(self._handle(), C.byref(Q)))
+        del keep
+        return rows[:int(Q.n_rows)].copy()
 
     # ---- solve
     def solve(self, start=None, factors=False, primal=True, device_out=False, trace_capacity=0, time_limit=None,

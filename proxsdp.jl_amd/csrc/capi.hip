@@ -14,6 +14,7 @@
 #include "test_hooks.hip.hpp"
 #include "shard_split.hpp"
 #include "model.hip.hpp"
+#include "triangle_cuts.hip.hpp"
 
 namespace {
 thread_local std::string g_last_error;
@@ -425,6 +426,41 @@ int proxsdp_hip_model_rows(proxsdp_model* mdl, proxsdp_model_rows* ch) {
         if (mdl->S->P.equilibrated) throw std::domain_error("proxsdp_hip_model_rows does not serve an equilibrated model: E and D depend on the rows");
         if (!mdl->opt0.approx_norm) throw std::domain_error("proxsdp_hip_model_rows does not serve approx_norm = 0: sigma_max depends on the rows");
         mdl->change_rows(*ch);
+        return 0;
+    });
+}
+
+int proxsdp_hip_model_triangles(proxsdp_model* mdl, proxsdp_triangle_cuts* tc) {
+    return guarded([&]() -> int {
+        proxsdp::check_triangle_struct(tc, true);
+        if (!mdl) throw std::invalid_argument("NULL handle");
+        const proxsdp::Prep& P = mdl->S->P;
+        if (tc->cone < 0 || tc->cone >= (int64_t)P.blocks.size()) throw std::invalid_argument("proxsdp_triangle_cuts.cone is outside the model's PSD cones");
+        const proxsdp::BlockInfo& B = P.blocks[tc->cone];
+        if (B.n < 3) throw std::invalid_argument("proxsdp_triangle_cuts: cone " + std::to_string(tc->cone) + " has side < 3");
+        PX_HIP(hipSetDevice(mdl->opt0.device_id));
+        proxsdp::device_triangle_cuts(mdl->S->stream, P.ord.data() + B.off, mdl->ord_d.p + B.off, B.n, mdl->index_base, tc->cone, *tc);
+        return 0;
+    });
+}
+
+int proxsdp_host_triangle_cuts(const double* X, int64_t side, const int64_t* cone_idx, int32_t index_base, proxsdp_triangle_cuts* tc) {
+    return guarded([&]() -> int {
+        proxsdp::check_triangle_struct(tc, false);
+        if (!X) throw std::invalid_argument("proxsdp_host_triangle_cuts: X is NULL");
+        if (side < 3 || side > 46340) throw std::invalid_argument("proxsdp_host_triangle_cuts: side must be 3 .. 46340");
+        if (index_base != 0 && index_base != 1) throw std::invalid_argument("index_base must be 0 or 1");
+        proxsdp::host_triangle_cuts(X, side, cone_idx, index_base, *tc);
+        return 0;
+    });
+}
+
+int proxsdp_hip_model_inactive_rows(proxsdp_model* mdl, proxsdp_inactive_rows* q) {
+    return guarded([&]() -> int {
+        proxsdp::check_inactive_struct(q);
+        if (!mdl) throw std::invalid_argument("NULL handle");
+        if (q->on_device) PX_HIP(hipSetDevice(mdl->opt0.device_id));
+        proxsdp::inactive_rows(mdl->S->stream, mdl->S->P.m, *q);
         return 0;
     });
 }

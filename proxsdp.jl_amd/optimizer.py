@@ -147,6 +147,20 @@ class Optimizer:
         self.sol = sol
         return sol
 
+    def separate_triangles(self, result=None, **kw):
+        """After optimize(..., keep_model=True): the most violated triangle inequalities of a PSD cone at `result` (default:
+        the last solution) -- binding.Model.separate_triangles.  reoptimize(add_rows=cuts.add) appends them."""
+        if getattr(self, "model", None) is None:
+            raise ValueError("separate_triangles() needs optimize(..., keep_model=True) first")
+        return self.model.separate_triangles(self.sol if result is None else result, **kw)
+
+    def inactive_rows(self, result=None, **kw):
+        """After optimize(..., keep_model=True): the inequality rows that went slack at `result` (default: the last
+        solution) -- binding.Model.inactive_rows; a drop_rows list for reoptimize()."""
+        if getattr(self, "model", None) is None:
+            raise ValueError("inactive_rows() needs optimize(..., keep_model=True) first")
+        return self.model.inactive_rows(self.sol if result is None else result, **kw)
+
     def _follow_rows(self, ch, add_rows):
         """self.problem with the rows of the kept model: G' = [kept rows; new rows], h' likewise (host copies)"""
         import dataclasses
