@@ -127,6 +127,22 @@ k_exit_feas_fin(const double* __restrict__ part, int nwg, double* __restrict__ o
 
 }  // namespace dev
 
+// The finite check of data the caller holds on the device, before anything is written: one reduction per array src[q] of len[q]
+// doubles (null or empty: skipped) into flag[q] (cnt ints at least), read back together; throws by the first bad array's name
+inline void require_finite_device(hipStream_t st, DevBuf<int>& flag, int cnt, const double* const* src, const int64_t* len,
+                                  const char* const* name, const char* what) {
+    flag.zero(st);
+    for (int q = 0; q < cnt; ++q)
+        if (src[q] && len[q] > 0)
+            hipLaunchKernelGGL(dev::k_exit_nonfinite, dim3(grid_for(len[q])), dim3(dev::TPB), 0, st, src[q], (long long)len[q], flag.p + q);
+    PX_HIP(hipGetLastError());
+    std::vector<int> h((size_t)cnt, 0);
+    flag.download(h.data(), (size_t)cnt, st);
+    PX_HIP(hipStreamSynchronize(st));
+    for (int q = 0; q < cnt; ++q)
+        if (h[q]) throw std::invalid_argument(std::string(what) + ": non-finite entry in " + name[q]);
+}
+
 // the in-place quirks of cache_solution (pdhg.jl:749-755): fix_diag_scaling on pair.x, then x = D x, y = E y
 inline void Solver::exit_rescale_iterate() {
     const double inv = 1.0 / std::sqrt(2.0);
@@ -144,7 +160,7 @@ inline void Solver::exit_rescale_iterate() {
         }
         hipLaunchKernelGGL(dev::k_scale_by, dim3(grid_for(P.n)), dim3(dev::TPB), 0, stream, xbuf[xc].p, Ddiag_d.p, (long long)P.n);
         hipLaunchKernelGGL(dev::k_scale_by, dim3(grid_for(std::max<int64_t>(P.Q, 1))), dim3(dev::TPB), 0, stream,
-                           ybuf[yc].p, Ediag_d.p, (long long)P.Q);
+                           rs.ybuf[yc].p, Ediag_d.p, (long long)P.Q);
     }
 }
 
@@ -156,23 +172,22 @@ inline int Solver::exit_feas_grid(int64_t m) const {
 }
 
 // what the exit kernels read beside the operator's pattern (csc_ptr / csc_row, csr_ptr / csr_col: upload_sparse_operator):
-// uploaded once, at the first exit
+// uploaded once, at the first exit; the row-sized part is the row state's (RowState::build_exit)
 inline void Solver::exit_device_setup() {
     if (xd.ready) return;
-    const size_t nz = (size_t)std::max<int64_t>(P.nnz, 1), n1 = (size_t)std::max<int64_t>(P.n, 1), q1 = (size_t)std::max<int64_t>(P.Q, 1);
+    const size_t nz = (size_t)std::max<int64_t>(P.nnz, 1), n1 = (size_t)std::max<int64_t>(P.n, 1);
+    rs.build_exit(P.p, P.m, P.nnz, exit_feas_grid(P.m));
     std::vector<double> rv(nz, 0.0);                         // the unscaled values in CSR order: prepare()'s counting sort again
     {
         std::vector<int64_t> cur(P.rowptr.begin(), P.rowptr.end() - 1);
         for (int64_t k = 0; k < P.n; ++k)
             for (int64_t q = P.colptr[k]; q < P.colptr[k + 1]; ++q) rv[cur[P.rowidx[q]]++] = P.val_orig[q];
     }
-    xd.cval.alloc(nz); xd.cval.upload(P.val_orig.data(), P.nnz, stream);
-    xd.rval.alloc(nz); xd.rval.upload(rv.data(), P.nnz, stream);
+    rs.exit.cval.upload(P.val_orig.data(), P.nnz, stream);
+    rs.exit.rval.upload(rv.data(), P.nnz, stream);
     xd.c.alloc(n1); xd.c.upload(P.c_orig.data(), P.n, stream);
-    std::vector<double> bh(q1, 0.0);
-    std::copy(P.b_orig.begin(), P.b_orig.begin() + P.p, bh.begin());
-    std::copy(P.h_orig.begin(), P.h_orig.begin() + P.m, bh.begin() + P.p);
-    xd.bh.alloc(q1); xd.bh.upload(bh.data(), P.Q, stream);
+    const std::vector<double> bh = stacked_bh(P.b_orig, P.h_orig);
+    rs.exit.bh.upload(bh.data(), P.Q, stream);
     static_assert(sizeof(long long) == sizeof(int64_t), "the inverse order is uploaded as it is");
     xd.inv.alloc(n1); xd.inv.upload(reinterpret_cast<const long long*>(P.inv.data()), P.n, stream);
     if (offdiag_d.n == 0) { offdiag_d.alloc(n1); offdiag_d.upload(P.offdiag.data(), P.n, stream); }
@@ -184,24 +199,23 @@ inline void Solver::exit_device_setup() {
     xd.one_off.alloc(std::max<size_t>(ones.size(), 1)); xd.one_off.upload(ones.data(), ones.size(), stream);
     xd.soc_off.alloc(std::max<size_t>(so.size(), 1)); xd.soc_off.upload(so.data(), so.size(), stream);
     xd.soc_len.alloc(std::max<size_t>(sl.size(), 1)); xd.soc_len.upload(sl.data(), sl.size(), stream);
-    xd.slack.alloc(q1); xd.dc.alloc(n1);
+    xd.dc.alloc(n1);
     if (P.dense()) { xd.base.alloc(n1); xd.zero.alloc(n1); xd.zero.zero(stream); }
-    xd.feas_wg = exit_feas_grid(P.m);
-    xd.part.alloc((size_t)4 * xd.feas_wg); xd.scal.alloc(4);
+    xd.scal.alloc(4);
     PX_HIP(hipStreamSynchronize(stream));                    // (the host vectors above go out of scope)
     xd.ready = true;
 }
 
-// M x - [b; h] into xd.slack and the dual cone c + M'y (halved off the diagonals) into xd.dc, from the rescaled iterate
+// M x - [b; h] into rs.exit.slack and the dual cone c + M'y (halved off the diagonals) into xd.dc, from the rescaled iterate
 inline void Solver::exit_form_vectors(bool zero_c) {
     const double* x = xbuf[xc].p;
-    const double* y = ybuf[yc].p;
+    const double* y = rs.ybuf[yc].p;
     if (P.Q > 0) {
-        xd.slack.zero(stream);
-        if (P.dense() && P.p > 0) dense_mv(x, xd.slack.p, false);        // A x with the caller's (unscaled) dense A
+        rs.exit.slack.zero(stream);
+        if (P.dense() && P.p > 0) dense_mv(x, rs.exit.slack.p, false);        // A x with the caller's (unscaled) dense A
         hipLaunchKernelGGL(dev::k_exit_slack, dim3(grid_for(P.Q)), dim3(dev::TPB), 0, stream,
-                           (const int*)csr_ptr.p, (const int*)csr_col.p, (const double*)xd.rval.p, x, (const double*)xd.bh.p,
-                           xd.slack.p, (long long)P.Q);
+                           (const int*)rs.csr_ptr.p, (const int*)rs.csr_col.p, (const double*)rs.exit.rval.p, x, (const double*)rs.exit.bh.p,
+                           rs.exit.slack.p, (long long)P.Q);
     }
     if (P.n > 0) {
         const double* base = zero_c ? nullptr : xd.c.p;
@@ -210,7 +224,7 @@ inline void Solver::exit_form_vectors(bool zero_c) {
             base = xd.base.p;
         }
         hipLaunchKernelGGL(dev::k_exit_dual_cone, dim3(grid_for(P.n)), dim3(dev::TPB), 0, stream,
-                           (const int*)csc_ptr.p, (const int*)csc_row.p, (const double*)xd.cval.p, y, base,
+                           (const int*)rs.csc_ptr.p, (const int*)rs.csc_row.p, (const double*)rs.exit.cval.p, y, base,
                            (const unsigned char*)offdiag_d.p, xd.dc.p, (long long)P.n);
     }
     PX_HIP(hipGetLastError());
@@ -219,11 +233,11 @@ inline void Solver::exit_form_vectors(bool zero_c) {
 // the four violations that need no eigenvalue, from xd.dc and the rescaled y: inequality duals, 1x1 cones, second-order
 // cones, free variables -- the host path's expressions on the extrema the device reduced
 inline void Solver::exit_cone_violations(double viol[4]) {
-    hipLaunchKernelGGL(dev::k_exit_feas, dim3(xd.feas_wg), dim3(dev::TPB), 0, stream,
-                       (const double*)ybuf[yc].p + P.p, (long long)P.m, (const double*)xd.dc.p,
+    hipLaunchKernelGGL(dev::k_exit_feas, dim3(rs.exit.feas_wg), dim3(dev::TPB), 0, stream,
+                       (const double*)rs.ybuf[yc].p + P.p, (long long)P.m, (const double*)xd.dc.p,
                        (const long long*)xd.one_off.p, (int)xd.ones.size(), (const long long*)xd.soc_off.p,
-                       (const int*)xd.soc_len.p, (int)P.socs.size(), (long long)P.conelen, (long long)P.n, xd.part.p);
-    hipLaunchKernelGGL(dev::k_exit_feas_fin, dim3(1), dim3(dev::WAVE), 0, stream, (const double*)xd.part.p, xd.feas_wg, xd.scal.p);
+                       (const int*)xd.soc_len.p, (int)P.socs.size(), (long long)P.conelen, (long long)P.n, rs.exit.part.p);
+    hipLaunchKernelGGL(dev::k_exit_feas_fin, dim3(1), dim3(dev::WAVE), 0, stream, (const double*)rs.exit.part.p, rs.exit.feas_wg, xd.scal.p);
     PX_HIP(hipGetLastError());
     double ext[4];
     xd.scal.download(ext, 4, stream);
@@ -254,10 +268,10 @@ inline void Solver::exit_write_vectors(const proxsdp_device_vectors* dv, double*
     };
     scattered(xbuf[xc].p, dv ? dv->primal : nullptr, primal, xd.prim);
     scattered(xd.dc.p, dv ? dv->dual_cone : nullptr, dual_cone, xd.dcone);
-    copied(ybuf[yc].p, P.p, dv ? dv->dual_eq : nullptr, dual_eq);
-    copied(ybuf[yc].p + P.p, P.m, dv ? dv->dual_in : nullptr, dual_in);
-    copied(xd.slack.p, P.p, dv ? dv->slack_eq : nullptr, slack_eq);
-    copied(xd.slack.p + P.p, P.m, dv ? dv->slack_in : nullptr, slack_in);
+    copied(rs.ybuf[yc].p, P.p, dv ? dv->dual_eq : nullptr, dual_eq);
+    copied(rs.ybuf[yc].p + P.p, P.m, dv ? dv->dual_in : nullptr, dual_in);
+    copied(rs.exit.slack.p, P.p, dv ? dv->slack_eq : nullptr, slack_eq);
+    copied(rs.exit.slack.p + P.p, P.m, dv ? dv->slack_in : nullptr, slack_in);
     PX_HIP(hipGetLastError());
     PX_HIP(hipStreamSynchronize(stream));
 }
@@ -312,16 +326,7 @@ inline void Solver::check_start_dev() {
     const int64_t len[3] = {P.n, P.p, P.m};
     const char* name[3] = {"primal", "dual_eq", "dual_in"};
     DevBuf<int> flag(3);
-    flag.zero(stream);
-    for (int q = 0; q < 3; ++q)
-        if (v[q] && len[q] > 0)
-            hipLaunchKernelGGL(dev::k_exit_nonfinite, dim3(grid_for(len[q])), dim3(dev::TPB), 0, stream, v[q], (long long)len[q], flag.p + q);
-    PX_HIP(hipGetLastError());
-    int h[3] = {0, 0, 0};
-    flag.download(h, 3, stream);
-    PX_HIP(hipStreamSynchronize(stream));
-    for (int q = 0; q < 3; ++q)
-        if (h[q]) throw std::invalid_argument(std::string("proxsdp_device_vectors (start): non-finite entry in ") + name[q]);
+    require_finite_device(stream, flag, 3, v, len, name, "proxsdp_device_vectors (start)");
 }
 
 // proxsdp_hip_exit_vectors: the exit path's own launches on a host iterate (include/proxsdp_hip.h)
@@ -337,7 +342,7 @@ inline void Solver::test_exit_vectors(const double* x, const double* y, bool zer
     upload_sparse_operator();
     if (P.dense()) upload_dense();
     xbuf[xc].upload(x, P.n, stream);
-    ybuf[yc].upload(y, P.Q, stream);
+    rs.ybuf[yc].upload(y, P.Q, stream);
     exit_rescale_iterate();
     exit_device_setup();
     exit_form_vectors(zero_c);

@@ -7,8 +7,9 @@
 // solve   = Solver::reset_for_solve() + Solver::solve(): proxsdp_hip_solve_device on the model's current data, bit for bit
 // update  = the caller's new numbers through the recorded maps into the device arrays, the four norms, and -- when the zero
 //           pattern of c moved the support set -- setup_support() / alloc_candidates() once more
-// rows    = inequality rows added and dropped (model_rows.hip.hpp): the stages of the set-up that read Q, nnz or the pattern,
-//           again, on new buffers; everything sized by n or a cone side stays
+// rows    = inequality rows added and dropped (model_rows.hip.hpp): a second RowState (solver.hip.hpp: every buffer sized by Q,
+//           nnz or the pattern) built for the new shape, filled from the live one through the plan's source maps, and exchanged
+//           with it; everything sized by n or a cone side stays
 // The entry points (argument checks, error codes) are in capi.hip.
 #pragma once
 #include "exit_device.hip.hpp"
@@ -26,7 +27,7 @@ struct proxsdp_model {
     double setup_time = 0.0;
     int index_base = 0;                         // of create: the columns of added rows follow it
     std::unique_ptr<proxsdp::Solver> S;
-    proxsdp::DevBuf<int> csc_pos_d, csr_pos_d, sinv_d, flag_d;
+    proxsdp::DevBuf<int> sinv_d, flag_d;
     proxsdp::DevBuf<long long> ord_d;
     proxsdp::DevBuf<double> stage, npart, nout;
 
@@ -55,9 +56,7 @@ struct proxsdp_model {
         s.setup();
         s.exit_device_setup();
         const Prep& P = s.P;
-        const size_t nz = (size_t)std::max<int64_t>(P.nnz, 1), n1 = (size_t)std::max<int64_t>(P.n, 1);
-        csc_pos_d.alloc(nz); csc_pos_d.upload(P.csc_pos.data(), P.nnz, s.stream);
-        csr_pos_d.alloc(nz); csr_pos_d.upload(P.csr_pos.data(), P.nnz, s.stream);
+        const size_t n1 = (size_t)std::max<int64_t>(P.n, 1);
         static_assert(sizeof(long long) == sizeof(int64_t), "the variable order is uploaded as it is");
         ord_d.alloc(n1); ord_d.upload(reinterpret_cast<const long long*>(P.ord.data()), P.n, s.stream);
         flag_d.alloc(8);
@@ -122,6 +121,7 @@ struct proxsdp_model {
         using namespace proxsdp;
         Solver& s = *S;
         Prep& P = s.P;
+        RowState& rs = s.rs;
         PX_HIP(hipSetDevice(opt0.device_id));
         Accounting acct(*this);
         hipStream_t st = s.stream;
@@ -130,19 +130,7 @@ struct proxsdp_model {
         const double* src[5] = {u.c, u.b, u.h, u.A_nzval, u.G_nzval};
         const int64_t len[5] = {P.n, P.p, P.m, nnzA, nnzG};
         const char* name[5] = {"c", "b", "h", "A_nzval", "G_nzval"};
-        if (on_dev) {                                       // the finite check of device data: a reduction, before any write
-            flag_d.zero(st);
-            for (int q = 0; q < 5; ++q)
-                if (src[q] && len[q] > 0)
-                    hipLaunchKernelGGL(dev::k_exit_nonfinite, dim3(grid_for(len[q])), dim3(dev::TPB), 0, st, src[q],
-                                       (long long)len[q], flag_d.p + q);
-            PX_HIP(hipGetLastError());
-            int h[5] = {0, 0, 0, 0, 0};
-            flag_d.download(h, 5, st);
-            PX_HIP(hipStreamSynchronize(st));
-            for (int q = 0; q < 5; ++q)
-                if (h[q]) throw std::invalid_argument(std::string("proxsdp_model_data: non-finite entry in ") + name[q]);
-        }
+        if (on_dev) require_finite_device(st, flag_d, 5, src, len, name, "proxsdp_model_data");
         s.restore_cert_data();                              // (a certificate search of the last solve zeroed c or [b; h])
         // a host array goes through the staging buffer; the stream orders its reuse
         auto on_device = [&](int q) -> const double* {
@@ -157,7 +145,7 @@ struct proxsdp_model {
             const double* d = on_device(0);
             PX_HIP(hipMemsetAsync(flag_d.p + 5, 0, sizeof(int), st));
             hipLaunchKernelGGL(dev::k_model_c, dim3(grid_for(P.n)), dim3(dev::TPB), 0, st, d, (const long long*)ord_d.p,
-                               (const unsigned char*)s.offdiag_d.p, cte, (const int*)s.csc_ptr.p,
+                               (const unsigned char*)s.offdiag_d.p, cte, (const int*)rs.csc_ptr.p,
                                s.use_support ? (const int*)sinv_d.p : (const int*)nullptr, s.c_d.p, s.xd.c.p,
                                s.use_support ? s.cS_d.p : (double*)nullptr, flag_d.p + 5, (long long)P.n);
             PX_HIP(hipGetLastError());
@@ -174,22 +162,16 @@ struct proxsdp_model {
             const int64_t off = q == 3 ? 0 : nnzA;
             const double* d = on_device(q);
             hipLaunchKernelGGL(dev::k_model_values, dim3(grid_for(len[q])), dim3(dev::TPB), 0, st, d, (long long)len[q],
-                               (const int*)csc_pos_d.p + off, (const int*)csr_pos_d.p + off, (const int*)s.csr_col.p,
-                               (const unsigned char*)s.offdiag_d.p, cte, s.xd.cval.p, s.xd.rval.p, s.csc_val.p, s.csr_val.p);
+                               (const int*)rs.csc_pos_d.p + off, (const int*)rs.csr_pos_d.p + off, (const int*)rs.csr_col.p,
+                               (const unsigned char*)s.offdiag_d.p, cte, rs.exit.cval.p, rs.exit.rval.p, rs.csc_val.p, rs.csr_val.p);
             PX_HIP(hipGetLastError());
         }
         if ((u.A_nzval && nnzA > 0) || (u.G_nzval && nnzG > 0)) {
-            s.csc_val.download(P.val.data(), P.nnz, st);
-            s.csr_val.download(P.rval.data(), P.nnz, st);
-            s.xd.cval.download(P.val_orig.data(), P.nnz, st);
+            rs.csc_val.download(P.val.data(), P.nnz, st);
+            rs.csr_val.download(P.rval.data(), P.nnz, st);
+            rs.exit.cval.download(P.val_orig.data(), P.nnz, st);
             PX_HIP(hipStreamSynchronize(st));
-            if (on_dev) {
-                P.frob = model_norm2(st, s.csc_val.p, P.nnz, npart, nout);
-            } else {                                        // finish_matrix's sum: the scaled values in reordered CSC order
-                double ss = 0.0;
-                for (int64_t q = 0; q < P.nnz; ++q) ss += P.val[q] * P.val[q];
-                P.frob = std::sqrt(ss);
-            }
+            P.frob = on_dev ? model_norm2(st, rs.csc_val.p, P.nnz, npart, nout) : host_frob(P);
         }
         if ((u.b && P.p > 0) || (u.h && P.m > 0)) {
             const double* db = nullptr;
@@ -198,19 +180,19 @@ struct proxsdp_model {
                 db = on_device(1);
                 if (!on_dev) {                              // (the staging buffer takes h next: b's launch goes first)
                     hipLaunchKernelGGL(dev::k_model_bh, dim3(grid_for(P.Q)), dim3(dev::TPB), 0, st, db, (long long)P.p,
-                                       (const double*)nullptr, (long long)P.m, s.bh_d.p, s.xd.bh.p);
+                                       (const double*)nullptr, (long long)P.m, rs.bh_d.p, rs.exit.bh.p);
                     db = nullptr;
                 }
             }
             if (u.h && P.m > 0) dh = on_device(2);
             if (db || dh)
                 hipLaunchKernelGGL(dev::k_model_bh, dim3(grid_for(P.Q)), dim3(dev::TPB), 0, st, db, (long long)P.p, dh,
-                                   (long long)P.m, s.bh_d.p, s.xd.bh.p);
+                                   (long long)P.m, rs.bh_d.p, rs.exit.bh.p);
             PX_HIP(hipGetLastError());
             if (u.b && P.p > 0) P.norm_b = on_dev ? model_norm2(st, u.b, P.p, npart, nout) : norm2(u.b, P.p);
             if (u.h && P.m > 0) P.norm_h = on_dev ? model_norm2(st, u.h, P.m, npart, nout) : norm2(u.h, P.m);
             std::vector<double> bh((size_t)P.Q);
-            s.bh_d.download(bh.data(), P.Q, st);
+            rs.bh_d.download(bh.data(), P.Q, st);
             PX_HIP(hipStreamSynchronize(st));
             std::copy(bh.begin(), bh.begin() + P.p, P.b.begin());
             std::copy(bh.begin() + P.p, bh.end(), P.h.begin());
@@ -235,9 +217,9 @@ struct proxsdp_model {
     }
 
     // ch: validated on the host as far as no model is needed (check_rows_struct); the model's own refusals are the caller's.
-    // Order: plan (host; the last refusals) -> the finite check of device values -> every new buffer -> index uploads, the
-    // gathers, the host mirrors downloaded -> the new buffers and the Prep's changed members take the old ones' places ->
-    // the two norms, the mat-vec's launch shape, the support set.
+    // Order: plan (host; the last refusals) -> the finite check of device values -> build: a second RowState for the plan's
+    // shape and the plan's source maps -> fill: the pattern, the gathers from the live state, the host mirrors, the two norms
+    // -> swap: the two states exchanged, the Prep's changed members committed -> the support set, where it moved.
     void change_rows(proxsdp_model_rows& ch) {
         using namespace proxsdp;
         const double t0 = now_s();
@@ -255,102 +237,72 @@ struct proxsdp_model {
         hipStream_t st = s.stream;
         const bool on_dev = ch.on_device != 0;
         const int64_t na = ch.n_add, nnz_add = pl.nnz_add;
-        if (on_dev && na > 0) {                             // the finite check of device data: a reduction, before any write
-            flag_d.zero(st);
+        if (on_dev && na > 0) {
             const double* src[2] = {ch.add_val, ch.add_h};
             const int64_t len[2] = {nnz_add, na};
             const char* name[2] = {"add_val", "add_h"};
-            for (int q = 0; q < 2; ++q)
-                if (len[q] > 0)
-                    hipLaunchKernelGGL(dev::k_exit_nonfinite, dim3(grid_for(len[q])), dim3(dev::TPB), 0, st, src[q],
-                                       (long long)len[q], flag_d.p + q);
-            PX_HIP(hipGetLastError());
-            int h[2] = {0, 0};
-            flag_d.download(h, 2, st);
-            PX_HIP(hipStreamSynchronize(st));
-            for (int q = 0; q < 2; ++q)
-                if (h[q]) throw std::invalid_argument(std::string("proxsdp_model_rows: non-finite entry in ") + name[q]);
+            require_finite_device(st, flag_d, 2, src, len, name, "proxsdp_model_rows");
         }
         s.restore_cert_data();                              // (a certificate search of the last solve zeroed c or [b; h])
         bool supp_moved = false;                            // only a column that lost or gained an entry can enter or leave the set
         for (int32_t k : pl.touched) supp_moved = supp_moved || in_support(P.colptr, P.c, k) != in_support(pl.R.colptr, P.c, k);
-        const Prep& R = pl.R;
+        Prep& R = pl.R;
+        const RowState& old = s.rs;
+        // ---- build: the next row state and the source maps, before the first write and before an old buffer goes
         const size_t nz = (size_t)std::max<int64_t>(R.nnz, 1), q1 = (size_t)std::max<int64_t>(R.Q, 1);
-        // ---- every new buffer, before the first write and before an old one goes
-        DevBuf<int> csr_ptr(R.Q + 1), csr_col(nz), csc_row(nz), cpos(nz), rpos(nz);
+        RowState next;
+        next.build(R.n, R.p, R.m, R.nnz, true);
+        next.build_exit(R.p, R.m, R.nnz, s.exit_feas_grid(R.m));
         DevBuf<int> csc_src(nz), csr_src(nz), bh_src(q1), add_k((size_t)std::max<int64_t>(nnz_add, 1));
-        DevBuf<int> csc_ptr(R.n + 1);
-        DevBuf<double> csr_val(nz), csc_val(nz), cval(nz), rval(nz), bh(q1), xbh(q1), slack(q1);
-        DevBuf<double> ybuf[2], Mxbuf[2], ycand((size_t)NCAND * q1), xpart;
-        for (int k = 0; k < 2; ++k) { ybuf[k].alloc(q1); Mxbuf[k].alloc(q1); }
-        const int feas_old = s.xd.feas_wg;
-        const int feas_new = s.exit_feas_grid(R.m);
-        if (feas_new != feas_old) xpart.alloc((size_t)4 * feas_new);
         const double* d_val = ch.add_val;
         const double* d_h = ch.add_h;
         if (!on_dev && na > 0) {                            // host values: through the staging buffer, the two arrays side by side
             const size_t need = (size_t)(nnz_add + na);
             if (stage.n < need) stage.alloc(std::max(need, (size_t)std::max<int64_t>(std::max(R.n, R.Q), std::max<int64_t>(R.nnz, 1))));
-        }
-        // ---- the index arrays from the plan, the numbers through the source maps
-        std::vector<int> rp((size_t)R.Q + 1), cp((size_t)R.n + 1);
-        for (int64_t i = 0; i <= R.Q; ++i) rp[i] = (int)R.rowptr[i];
-        for (int64_t i = 0; i <= R.n; ++i) cp[i] = (int)R.colptr[i];
-        csr_ptr.upload(rp.data(), rp.size(), st); csc_ptr.upload(cp.data(), cp.size(), st);
-        csr_col.upload(R.colidx.data(), R.nnz, st); csc_row.upload(R.rowidx.data(), R.nnz, st);
-        cpos.upload(R.csc_pos.data(), R.nnz, st); rpos.upload(R.csr_pos.data(), R.nnz, st);
-        csc_src.upload(pl.csc_src.data(), R.nnz, st); csr_src.upload(pl.csr_src.data(), R.nnz, st);
-        bh_src.upload(pl.bh_src.data(), R.Q, st); add_k.upload(pl.add_k.data(), nnz_add, st);
-        if (!on_dev && na > 0) {
             stage.upload(ch.add_val, (size_t)nnz_add, st);
             PX_HIP(hipMemcpyAsync(stage.p + nnz_add, ch.add_h, (size_t)na * sizeof(double), hipMemcpyHostToDevice, st));
             d_val = stage.p; d_h = stage.p + nnz_add;
         }
+        // ---- fill: the pattern and the mat-vec's shape from the plan, the numbers through the source maps
+        s.upload_pattern(next, R);
+        csc_src.upload(pl.csc_src.data(), R.nnz, st); csr_src.upload(pl.csr_src.data(), R.nnz, st);
+        bh_src.upload(pl.bh_src.data(), R.Q, st); add_k.upload(pl.add_k.data(), nnz_add, st);
         const double cte = std::sqrt(2.0) / 2.0;
         if (R.nnz > 0) {
             hipLaunchKernelGGL(dev::k_rows_values, dim3(grid_for(R.nnz)), dim3(dev::TPB), 0, st, (const int*)csc_src.p, (long long)R.nnz,
-                               (const double*)s.xd.cval.p, (const double*)s.csc_val.p, d_val, (const int*)add_k.p,
-                               (const unsigned char*)s.offdiag_d.p, cte, cval.p, csc_val.p);
+                               (const double*)old.exit.cval.p, (const double*)old.csc_val.p, d_val, (const int*)add_k.p,
+                               (const unsigned char*)s.offdiag_d.p, cte, next.exit.cval.p, next.csc_val.p);
             hipLaunchKernelGGL(dev::k_rows_values, dim3(grid_for(R.nnz)), dim3(dev::TPB), 0, st, (const int*)csr_src.p, (long long)R.nnz,
-                               (const double*)s.xd.rval.p, (const double*)s.csr_val.p, d_val, (const int*)add_k.p,
-                               (const unsigned char*)s.offdiag_d.p, cte, rval.p, csr_val.p);
+                               (const double*)old.exit.rval.p, (const double*)old.csr_val.p, d_val, (const int*)add_k.p,
+                               (const unsigned char*)s.offdiag_d.p, cte, next.exit.rval.p, next.csr_val.p);
         }
         if (R.Q > 0)
             hipLaunchKernelGGL(dev::k_rows_bh, dim3(grid_for(R.Q)), dim3(dev::TPB), 0, st, (const int*)bh_src.p, (long long)R.Q,
-                               (const double*)s.bh_d.p, d_h, bh.p, xbh.p);
+                               (const double*)old.bh_d.p, d_h, next.bh_d.p, next.exit.bh.p);
         PX_HIP(hipGetLastError());
-        for (int k = 0; k < 2; ++k) { ybuf[k].zero(st); Mxbuf[k].zero(st); }
-        ycand.zero(st); slack.zero(st);
+        for (int k = 0; k < 2; ++k) { next.ybuf[k].zero(st); next.Mxbuf[k].zero(st); }
+        next.ycand_d.zero(st); next.exit.slack.zero(st);
         // the host mirrors, the way update brings them up to date: from the device arrays
-        csc_val.download(pl.R.val.data(), R.nnz, st);
-        csr_val.download(pl.R.rval.data(), R.nnz, st);
-        cval.download(pl.R.val_orig.data(), R.nnz, st);
+        next.csc_val.download(R.val.data(), R.nnz, st);
+        next.csr_val.download(R.rval.data(), R.nnz, st);
+        next.exit.cval.download(R.val_orig.data(), R.nnz, st);
         std::vector<double> bhh((size_t)R.Q);
-        bh.download(bhh.data(), R.Q, st);
+        next.bh_d.download(bhh.data(), R.Q, st);
         PX_HIP(hipStreamSynchronize(st));
-        // ---- the new buffers take the old ones' places (nothing below this line throws before the Prep is the new one)
-        s.csr_ptr = std::move(csr_ptr); s.csr_col = std::move(csr_col); s.csr_val = std::move(csr_val);
-        s.csc_ptr = std::move(csc_ptr); s.csc_row = std::move(csc_row); s.csc_val = std::move(csc_val);
-        s.xd.cval = std::move(cval); s.xd.rval = std::move(rval); s.xd.bh = std::move(xbh); s.xd.slack = std::move(slack);
-        s.bh_d = std::move(bh);
-        for (int k = 0; k < 2; ++k) { s.ybuf[k] = std::move(ybuf[k]); s.Mxbuf[k] = std::move(Mxbuf[k]); }
-        s.ycand_d = std::move(ycand);
-        if (feas_new != feas_old) { s.xd.part = std::move(xpart); s.xd.feas_wg = feas_new; }
-        csc_pos_d = std::move(cpos); csr_pos_d = std::move(rpos);
-        std::copy(bhh.begin() + R.p, bhh.end(), pl.R.h.begin());
-        pl.R.h_orig = pl.R.h;
+        std::copy(bhh.begin() + R.p, bhh.end(), R.h.begin());
+        R.h_orig = R.h;
+        if (on_dev) {
+            R.norm_h = model_norm2(st, next.bh_d.p + R.p, R.m, npart, nout);
+            R.frob = model_norm2(st, next.csc_val.p, R.nnz, npart, nout);
+        } else {
+            rows_host_norms(R);
+        }
+        // ---- swap (nothing throws until the solver and its Prep describe the new rows, no device allocation until the support rebuild)
+        std::swap(s.rs, next);
+        P.norm_h = R.norm_h; P.frob = R.frob;
         commit_rows(P, pl);
         s.b_host = P.b; s.h_host = P.h;
         shape.m = P.m;
-        if (on_dev) {
-            P.norm_h = model_norm2(st, s.bh_d.p + P.p, P.m, npart, nout);
-            P.frob = model_norm2(st, s.csc_val.p, P.nnz, npart, nout);
-        } else {
-            rows_host_norms(P);
-        }
-        // ---- what the set-up derives from the pattern: the mat-vec's shape, the support set
-        s.n_seg = 0; s.n_long = 0;
-        s.choose_spmv_shape(rp);
         ch.support_rebuilt = 0;
         // a changed set matters where the support path runs, or would now (the auto rule reads the set's size)
         if (supp_moved && (s.use_support || s.support_path_wanted(s.support_list().size()))) { rebuild_support(); ch.support_rebuilt = 1; }
@@ -375,18 +327,19 @@ struct proxsdp_model {
         using namespace proxsdp;
         Solver& s = *S;
         const Prep& P = s.P;
+        const RowState& rs = s.rs;
         PX_HIP(hipSetDevice(opt0.device_id));
         s.restore_cert_data();
         hipStream_t st = s.stream;
         out.n = P.n; out.Q = P.Q; out.nnz = P.nnz; out.ns = s.use_support ? s.ns : 0;
         out.norms[0] = P.norm_b; out.norms[1] = P.norm_h; out.norms[2] = P.norm_c; out.norms[3] = P.frob;
-        if (out.csc_val) s.csc_val.download(out.csc_val, P.nnz, st);
-        if (out.csr_val) s.csr_val.download(out.csr_val, P.nnz, st);
-        if (out.csc_val_orig) s.xd.cval.download(out.csc_val_orig, P.nnz, st);
-        if (out.csr_val_orig) s.xd.rval.download(out.csr_val_orig, P.nnz, st);
+        if (out.csc_val) rs.csc_val.download(out.csc_val, P.nnz, st);
+        if (out.csr_val) rs.csr_val.download(out.csr_val, P.nnz, st);
+        if (out.csc_val_orig) rs.exit.cval.download(out.csc_val_orig, P.nnz, st);
+        if (out.csr_val_orig) rs.exit.rval.download(out.csr_val_orig, P.nnz, st);
         if (out.c) s.c_d.download(out.c, P.n, st);
         if (out.c_orig) s.xd.c.download(out.c_orig, P.n, st);
-        if (out.bh) s.bh_d.download(out.bh, P.Q, st);
+        if (out.bh) rs.bh_d.download(out.bh, P.Q, st);
         if (out.support && out.ns > 0) PX_HIP(hipMemcpyAsync(out.support, s.supp_d.p, (size_t)out.ns * sizeof(int), hipMemcpyDeviceToHost, st));
         if (out.cS && out.ns > 0) s.cS_d.download(out.cS, out.ns, st);
         PX_HIP(hipStreamSynchronize(st));

@@ -218,14 +218,14 @@ inline void commit_rows(Prep& P, RowsPlan& pl) {
 // is position k in the support set {column non-empty or c_k != 0} under the column pointers cp
 inline bool in_support(const std::vector<int64_t>& cp, const std::vector<double>& c, int64_t k) { return cp[k + 1] > cp[k] || c[k] != 0.0; }
 
-// ||h'|| and ||M'||_F from the host mirrors, in prepare()'s order: one running sum over h, one over the scaled values in
-// reordered CSC order
-inline void rows_host_norms(Prep& R) {
-    R.norm_h = norm2(R.h.data(), R.m);
+// ||M||_F from the host mirror, in finish_matrix's order: one running sum over the scaled values in reordered CSC order
+inline double host_frob(const Prep& R) {
     double ss = 0.0;
     for (int64_t q = 0; q < R.nnz; ++q) ss += R.val[q] * R.val[q];
-    R.frob = std::sqrt(ss);
+    return std::sqrt(ss);
 }
+// ||h'|| and ||M'||_F from the host mirrors, in prepare()'s order
+inline void rows_host_norms(Prep& R) { R.norm_h = norm2(R.h.data(), R.m); R.frob = host_frob(R); }
 
 // The planner's values on the host (proxsdp_host_model_rows_plan: no device): the kernels' arithmetic from the old Prep's
 // arrays and HOST add_val / add_h, then the two norms.  rval_orig: the unscaled values in CSR order (the dump's csr_val_orig).

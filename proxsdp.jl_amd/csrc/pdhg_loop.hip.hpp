@@ -16,33 +16,32 @@ inline void Solver::spmv(const double* x, double* y) {
 }
 inline void Solver::spmv_sparse(const double* x, double* y) {
     if (P.Q == 0) return;
-    if (csr_wave)
+    if (rs.csr_wave)
         hipLaunchKernelGGL(dev::k_spmv_csr_wave, dim3(ceil_div(P.Q, dev::NWAVE)), dim3(dev::TPB), 0, stream,
-                           csr_ptr.p, csr_col.p, csr_val.p, x, y, (int)P.Q, LONG_ROW);
+                           rs.csr_ptr.p, rs.csr_col.p, rs.csr_val.p, x, y, (int)P.Q, LONG_ROW);
     else
         hipLaunchKernelGGL(dev::k_spmv_csr_thread, dim3(ceil_div(P.Q, dev::TPB)), dim3(dev::TPB), 0, stream,
-                           csr_ptr.p, csr_col.p, csr_val.p, x, y, (int)P.Q, LONG_ROW);
-    if (n_seg > 0) {
-        hipLaunchKernelGGL(dev::k_spmv_csr_seg, dim3(n_seg), dim3(dev::TPB), 0, stream,
-                           seg_lo_d.p, seg_hi_d.p, csr_col.p, csr_val.p, x, segpart_d.p);
-        hipLaunchKernelGGL(dev::k_spmv_seg_fin, dim3(ceil_div(n_long, dev::TPB)), dim3(dev::TPB), 0, stream,
-                           long_row_d.p, long_ptr_d.p, n_long, segpart_d.p, y);
+                           rs.csr_ptr.p, rs.csr_col.p, rs.csr_val.p, x, y, (int)P.Q, LONG_ROW);
+    if (rs.n_seg > 0) {
+        hipLaunchKernelGGL(dev::k_spmv_csr_seg, dim3(rs.n_seg), dim3(dev::TPB), 0, stream,
+                           rs.seg_lo_d.p, rs.seg_hi_d.p, rs.csr_col.p, rs.csr_val.p, x, rs.segpart_d.p);
+        hipLaunchKernelGGL(dev::k_spmv_seg_fin, dim3(ceil_div(rs.n_long, dev::TPB)), dim3(dev::TPB), 0, stream,
+                           rs.long_row_d.p, rs.long_ptr_d.p, rs.n_long, rs.segpart_d.p, y);
     }
 }
-// rows with more than LONG_ROW entries -> segments of SPMV_SEG entries
-inline void Solver::setup_long_rows(const std::vector<int>& rp) {
+// rows of the row pointers rp with more than LONG_ROW entries -> segments of SPMV_SEG entries, into `to`
+inline void Solver::setup_long_rows(RowState& to, const std::vector<int>& rp) {
     std::vector<int> lo, hi, rows, ptr{0};
-    for (int64_t r = 0; r < P.Q; ++r) {
+    for (size_t r = 0; r + 1 < rp.size(); ++r) {
         if (rp[r + 1] - rp[r] <= LONG_ROW) continue;
         rows.push_back((int)r);
         for (int k = rp[r]; k < rp[r + 1]; k += dev::SPMV_SEG) { lo.push_back(k); hi.push_back(std::min(k + dev::SPMV_SEG, rp[r + 1])); }
         ptr.push_back((int)lo.size());
     }
-    n_seg = (int)lo.size(); n_long = (int)rows.size();
-    if (n_seg == 0) return;
-    seg_lo_d.alloc(n_seg); seg_hi_d.alloc(n_seg); long_row_d.alloc(n_long); long_ptr_d.alloc(n_long + 1); segpart_d.alloc(n_seg);
-    seg_lo_d.upload(lo.data(), n_seg, stream); seg_hi_d.upload(hi.data(), n_seg, stream);
-    long_row_d.upload(rows.data(), n_long, stream); long_ptr_d.upload(ptr.data(), n_long + 1, stream);
+    to.build_segments((int)lo.size(), (int)rows.size());
+    if (to.n_seg == 0) return;
+    to.seg_lo_d.upload(lo.data(), to.n_seg, stream); to.seg_hi_d.upload(hi.data(), to.n_seg, stream);
+    to.long_row_d.upload(rows.data(), to.n_long, stream); to.long_ptr_d.upload(ptr.data(), to.n_long + 1, stream);
     PX_HIP(hipStreamSynchronize(stream));
 }
 
@@ -93,8 +92,8 @@ inline void Solver::primal_step_dev() {
         shard_guard([&]() { project_blocks(big_blocks, xcur, xnew, true); });
         st.t_psd += now_s() - t0;
         if (P.sdplen < P.n) launch_tail_copy(xcur, xnew);
-        spmv(xnew, Mxbuf[1 - mxc].p);
-        reduce_coupling(Mxbuf[1 - mxc].p);
+        spmv(xnew, rs.Mxbuf[1 - mxc].p);
+        reduce_coupling(rs.Mxbuf[1 - mxc].p);
         return;
     }
     const double* xi = xbuf[xc].p;
@@ -111,17 +110,16 @@ inline void Solver::primal_step_dev() {
         }
         if (!P.socs.empty()) launch_soc_project(xo, (int)P.socs.size());
     });
-    spmv(xo, Mxbuf[1 - mxc].p);
-    reduce_coupling(Mxbuf[1 - mxc].p);
+    spmv(xo, rs.Mxbuf[1 - mxc].p);
+    reduce_coupling(rs.Mxbuf[1 - mxc].p);
 }
 
 // ---- linesearch! / dual_step! (pdhg.jl:532-609) + compute_residual! + compute_gap! (residuals.jl:2-71) on every vector path
-constexpr int NCAND = 3;    // candidates per batch (options.general_batch = 0: one); the scalar record always holds NCAND
-constexpr int NSCAL = 11;   // scalars per candidate: q0,q1 sums | q2,q3 max, q4 sum | q5..q8 max, q9,q10 sum
+constexpr int NSCAL = 11;   // scalars per candidate (NCAND of them, solver.hip.hpp): q0,q1 sums | q2,q3 max, q4 sum | q5..q8 max, q9,q10 sum
 
-// the candidates' buffers: y_c, M'y_c (on the support, or every column), their partials and the scalar record
+// the candidates' buffers: y_c (the row state's: zeroed), M'y_c (on the support, or every column), partials, the scalar record
 inline void Solver::alloc_candidates() {
-    ycand_d.alloc((size_t)NCAND * std::max<int64_t>(P.Q, 1)); ycand_d.zero(stream);
+    rs.ycand_d.zero(stream);
     Mtycand_d.alloc((size_t)NCAND * batch_shape().mstride); Mtycand_d.zero(stream);
     bpart.alloc((size_t)NCAND * NSCAL * PSTRIDE); bpart.zero(stream);
     bscal.alloc(64); bscal.zero(stream);
@@ -168,7 +166,7 @@ inline void Solver::reduce_candidates(int nc) {
 
 // ---- one batch of linesearch candidates: the launches (shared with the kernel-level test entry, test_trial_batch)
 // the batch's launch shapes: one workgroup column per 256 entries of y (gq) and of the support or every column (gx), capped at
-// PSTRIDE (the kernels stride over the rest); the candidates' slices of ycand_d / Mtycand_d / bpart; and the one place that
+// PSTRIDE (the kernels stride over the rest); the candidates' slices of rs.ycand_d / Mtycand_d / bpart; and the one place that
 // tells the vector paths apart for the batch (the support path keeps M'y on S in one buffer, which commit overwrites)
 inline Solver::BatchShape Solver::batch_shape() const {
     BatchShape b;
@@ -184,7 +182,7 @@ inline Solver::BatchShape Solver::batch_shape() const {
 // residual / gap reductions of candidates c0 .. c0 + nc - 1 (their partials land in the records 0 .. nc - 1)
 inline void Solver::batch_residuals(const dev::TrialBatch& tb, int nc, int c0, double xold_coef) {
     const BatchShape b = batch_shape();
-    const double* yc0 = ycand_d.p + (size_t)c0 * b.ystride;
+    const double* yc0 = rs.ycand_d.p + (size_t)c0 * b.ystride;
     const double* mc0 = Mtycand_d.p + (size_t)c0 * b.mstride;
     // (outside a block-sharded solve the general path's residuals have never taken the row weights that k_dual_trial_batch
     // gets on both paths: kept as it is, and with it that solve's bits; inside one, b'y and h'y count a coupling row once)
@@ -192,7 +190,7 @@ inline void Solver::batch_residuals(const dev::TrialBatch& tb, int nc, int c0, d
     hipLaunchKernelGGL(b.supp != nullptr ? dev::k_residual_xy<true> : dev::k_residual_xy<false>,
                        dim3(std::max(b.gx, b.gq), nc, 2), dim3(dev::TPB), 0, stream,
                        xbuf[1 - xc].p, b.supp, b.cnt, b.xold, xold_coef, mc0, b.mstride, b.mty_cur, b.cv, b.gx,
-                       yc0, b.ystride, ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, b.gq,
+                       yc0, b.ystride, rs.ybuf[yc].p, rs.Mxbuf[1 - mxc].p, rs.Mxbuf[mxc].p, rs.bh_d.p, (int)P.p, (int)P.Q, b.gq,
                        tb, bpart.p, PSTRIDE, b.cstride, roww);
 }
 // y+, M'y+ and their norms for nc candidates, then their residuals
@@ -202,20 +200,20 @@ inline void Solver::batch_evaluate(const dev::TrialBatch& tb, int nc, double xol
     const int gq = b.gq;
     const long long cstride = b.cstride, ystride = b.ystride;
     hipLaunchKernelGGL(dev::k_dual_trial_batch, dim3(gq, nc), dim3(dev::TPB), 0, stream,
-                       ybuf[yc].p, Mxbuf[1 - mxc].p, Mxbuf[mxc].p, bh_d.p, (int)P.p, (int)P.Q, tb,
-                       ycand_d.p, ystride, bpart.p, cstride, roww_d.p);
+                       rs.ybuf[yc].p, rs.Mxbuf[1 - mxc].p, rs.Mxbuf[mxc].p, rs.bh_d.p, (int)P.p, (int)P.Q, tb,
+                       rs.ycand_d.p, ystride, bpart.p, cstride, roww_d.p);
     batch_mty(tb, nc);
     batch_residuals(tb, nc, 0, xold_coef);
 }
-// M'y_c of the candidates in ycand_d + |M'y_c - M'y_old|^2 partials
+// M'y_c of the candidates in rs.ycand_d + |M'y_c - M'y_old|^2 partials
 inline void Solver::batch_mty(const dev::TrialBatch& tb, int nc) {
     const BatchShape b = batch_shape();
     if (b.supp == nullptr && P.dense())
-        dense_mtv(nc, ycand_d.p, b.ystride, true, Mtycand_d.p, b.mstride, b.mty_cur, nullptr, bpart.p + PSTRIDE, b.cstride, !tb.plain);
+        dense_mtv(nc, rs.ycand_d.p, b.ystride, true, Mtycand_d.p, b.mstride, b.mty_cur, nullptr, bpart.p + PSTRIDE, b.cstride, !tb.plain);
     else
         hipLaunchKernelGGL(b.supp != nullptr ? dev::k_spmvT_batch<true> : dev::k_spmvT_batch<false>,
                            dim3(b.gx, nc), dim3(dev::TPB), 0, stream,
-                           csc_ptr.p, csc_row.p, csc_val.p, b.supp, b.cnt, ycand_d.p, b.ystride,
+                           rs.csc_ptr.p, rs.csc_row.p, rs.csc_val.p, b.supp, b.cnt, rs.ycand_d.p, b.ystride,
                            Mtycand_d.p, b.mstride, b.mty_cur, bpart.p + PSTRIDE, b.cstride, tb.plain);
 }
 // the scalar record: NSCAL per candidate, then (support path) the two off-support residual maxima that the fused
@@ -268,7 +266,7 @@ inline const double* Solver::linesearch_and_residuals() {
     auto commit = [&](int c) {                           // y <- y_c, M'y <- M'y_c (one launch)
         const BatchShape b = batch_shape();
         hipLaunchKernelGGL(dev::k_copy2, dim3(grid_for((long long)P.Q + b.cnt)), dim3(dev::TPB), 0, stream,
-                           ybuf[1 - yc].p, (const double*)(ycand_d.p + (size_t)c * b.ystride), (long long)P.Q,
+                           rs.ybuf[1 - yc].p, (const double*)(rs.ycand_d.p + (size_t)c * b.ystride), (long long)P.Q,
                            b.mty_commit, (const double*)(Mtycand_d.p + (size_t)c * b.mstride), b.cnt);
     };
     const bool ls = opt.line_search_flag;
@@ -548,7 +546,7 @@ inline void Solver::cache_solution(const std::vector<double>& cvec) {
     exit_rescale_iterate();                                  // (exit_device.hip.hpp: the two exit paths share it)
     std::vector<double> x(P.n), y(P.Q);
     xbuf[xc].download(x.data(), P.n, stream);
-    ybuf[yc].download(y.data(), P.Q, stream);
+    rs.ybuf[yc].download(y.data(), P.Q, stream);
     PX_HIP(hipStreamSynchronize(stream));
     std::vector<double> slack(P.Q, 0.0);
     if (P.dense() && P.p > 0) {                              // A x with the caller's (unscaled) dense A
@@ -845,12 +843,12 @@ inline void Solver::dense_mtv(int nc, const double* Y, long long ystride, bool s
     auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(gx), dim3(dev::TPB), 0, stream, Md, (long long)P.n, (int)P.p, (long long)P.n,
                            Y, ystride, od, sc, OUT, ostride, old, addc, normpart, cstride,
-                           scaled && P.nnz > 0 ? csc_ptr.p : nullptr, csc_row.p, csc_val.p, addback ? 1 : 0);
+                           scaled && P.nnz > 0 ? rs.csc_ptr.p : nullptr, rs.csc_row.p, rs.csc_val.p, addback ? 1 : 0);
     };
     auto launch_eq = [&](auto kern) {                    // OUT_c = (D o s) o (M' (E o Y_c)) + the scaled sparse rows
         hipLaunchKernelGGL(kern, dim3(gx), dim3(dev::TPB), 0, stream, Md, (long long)P.n, (int)P.p, (long long)P.n,
                            Y, ystride, (const double*)drow_d.p, (const double*)dcol_d.p, OUT, ostride, old, addc, normpart, cstride,
-                           P.nnz > 0 ? csc_ptr.p : nullptr, csc_row.p, csc_val.p, addback ? 1 : 0);
+                           P.nnz > 0 ? rs.csc_ptr.p : nullptr, rs.csc_row.p, rs.csc_val.p, addback ? 1 : 0);
     };
     dense_ev_begin();
     if (scaled && P.equilibrated) {
@@ -996,23 +994,24 @@ inline void Solver::setup_support() {
 
 // sparse operator on the device, both orientations, int32 indices
 inline void Solver::upload_sparse_operator() {
-    std::vector<int> rp(P.Q + 1), cp(P.n + 1);
-    // (prepare() guarantees n, Q, nnz < 2^31: the casts below cannot truncate)
-    for (int64_t i = 0; i <= P.Q; ++i) rp[i] = (int)P.rowptr[i];
-    for (int64_t i = 0; i <= P.n; ++i) cp[i] = (int)P.colptr[i];
-    csr_ptr.alloc(P.Q + 1); csr_col.alloc(std::max<int64_t>(P.nnz, 1)); csr_val.alloc(std::max<int64_t>(P.nnz, 1));
-    csc_ptr.alloc(P.n + 1); csc_row.alloc(std::max<int64_t>(P.nnz, 1)); csc_val.alloc(std::max<int64_t>(P.nnz, 1));
-    csr_ptr.upload(rp.data(), P.Q + 1, stream); csc_ptr.upload(cp.data(), P.n + 1, stream);
-    csr_col.upload(P.colidx.data(), P.nnz, stream); csr_val.upload(P.rval.data(), P.nnz, stream);
-    csc_row.upload(P.rowidx.data(), P.nnz, stream); csc_val.upload(P.val.data(), P.nnz, stream);
-    PX_HIP(hipStreamSynchronize(stream));
-    choose_spmv_shape(rp);
+    build_rows();
+    rs.csr_val.upload(P.rval.data(), P.nnz, stream); rs.csc_val.upload(P.val.data(), P.nnz, stream);
+    upload_pattern(rs, P);
 }
-// what M x derives from the row pointers rp: a wave per row above 8 entries a row on average, and the segments of the long
-// rows (a model handle takes both again when its rows change)
-inline void Solver::choose_spmv_shape(const std::vector<int>& rp) {
-    csr_wave = P.Q > 0 && (double)P.nnz / (double)P.Q > 8.0;
-    setup_long_rows(rp);
+// The pattern of R's operator into `to`: pointers and indices in both orientations, the position maps where `to` has them, and
+// what M x derives from the row pointers -- a wave per row above 8 entries a row on average, the segments of the long rows.
+// R: the solver's Prep, or the one a row change is about to commit (the next row state is built before it is the solver's).
+inline void Solver::upload_pattern(RowState& to, const Prep& R) {
+    std::vector<int> rp(R.Q + 1), cp(R.n + 1);
+    // (prepare() and plan_rows() guarantee n, Q, nnz < 2^31: the casts below cannot truncate)
+    for (int64_t i = 0; i <= R.Q; ++i) rp[i] = (int)R.rowptr[i];
+    for (int64_t i = 0; i <= R.n; ++i) cp[i] = (int)R.colptr[i];
+    to.csr_ptr.upload(rp.data(), R.Q + 1, stream); to.csc_ptr.upload(cp.data(), R.n + 1, stream);
+    to.csr_col.upload(R.colidx.data(), R.nnz, stream); to.csc_row.upload(R.rowidx.data(), R.nnz, stream);
+    if (to.csc_pos_d.n > 0) { to.csc_pos_d.upload(R.csc_pos.data(), R.nnz, stream); to.csr_pos_d.upload(R.csr_pos.data(), R.nnz, stream); }
+    PX_HIP(hipStreamSynchronize(stream));
+    to.csr_wave = R.Q > 0 && (double)R.nnz / (double)R.Q > 8.0;
+    setup_long_rows(to, rp);
 }
 
 // ---- state seam (include/proxsdp_hip.h proxsdp_state)
@@ -1035,8 +1034,8 @@ inline void Solver::apply_resume() {
     const proxsdp_state& s = *req.resume_state;
     check_state_shape(s, "resume");
     xbuf[xc].upload(s.x, P.n, stream);
-    ybuf[yc].upload(s.y, P.Q, stream);
-    Mxbuf[mxc].upload(s.Mx, P.Q, stream);
+    rs.ybuf[yc].upload(s.y, P.Q, stream);
+    rs.Mxbuf[mxc].upload(s.Mx, P.Q, stream);
     Mtybuf[mtyc].upload(s.Mty, P.n, stream);
     std::vector<double> mtyS;
     if (use_support) {                                   // the support path carries M'y on the support only
@@ -1157,19 +1156,19 @@ inline void Solver::apply_start() {
         else if (!d_in && P.m > 0) PX_HIP(hipMemsetAsync(start_src_d.p + P.p, 0, (size_t)P.m * sizeof(double), stream));
         const double* Ed = P.equilibrated ? Ediag_d.p : nullptr;
         if (!d_eq && !d_in) {
-            gather(start_src_d.p, 0, nullptr, nullptr, Ed, ybuf[yc].p, 0, P.Q);
+            gather(start_src_d.p, 0, nullptr, nullptr, Ed, rs.ybuf[yc].p, 0, P.Q);
         } else {
-            gather(d_eq ? d_eq : start_src_d.p, 0, nullptr, nullptr, Ed, ybuf[yc].p, 0, P.p);
-            gather(d_in ? d_in : start_src_d.p, d_in ? P.p : 0, nullptr, nullptr, Ed, ybuf[yc].p, P.p, P.Q);
+            gather(d_eq ? d_eq : start_src_d.p, 0, nullptr, nullptr, Ed, rs.ybuf[yc].p, 0, P.p);
+            gather(d_in ? d_in : start_src_d.p, d_in ? P.p : 0, nullptr, nullptr, Ed, rs.ybuf[yc].p, P.p, P.Q);
         }
         const BatchShape b = batch_shape();
-        PX_HIP(hipMemcpyAsync(ycand_d.p, ybuf[yc].p, (size_t)P.Q * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        PX_HIP(hipMemcpyAsync(rs.ycand_d.p, rs.ybuf[yc].p, (size_t)P.Q * sizeof(double), hipMemcpyDeviceToDevice, stream));
         dev::TrialBatch tb{};                            // ONE plain candidate: M'y as computed (on the support, or every column)
         tb.nc = 1; tb.plain = 1;
         batch_mty(tb, 1);
         PX_HIP(hipMemcpyAsync(b.mty_cur, Mtycand_d.p, (size_t)b.cnt * sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
-    spmv(xbuf[xc].p, Mxbuf[mxc].p);                      // M x (sparse rows, and the dense block with its scale vectors)
+    spmv(xbuf[xc].p, rs.Mxbuf[mxc].p);                      // M x (sparse rows, and the dense block with its scale vectors)
     PX_HIP(hipGetLastError());
     PX_HIP(hipStreamSynchronize(stream));
     if (P.dense()) { dense_ev_harvest(); dense_passes_seen = st.dense_passes; }   // (set-up work, as the sigma_max passes)
@@ -1183,7 +1182,7 @@ inline void Solver::write_start_point() {
     proxsdp_state& s = *req.start_out;
     PX_HIP(hipStreamSynchronize(stream));
     xbuf[xc].download(s.x, P.n, stream);
-    if (P.Q > 0) { ybuf[yc].download(s.y, P.Q, stream); Mxbuf[mxc].download(s.Mx, P.Q, stream); }
+    if (P.Q > 0) { rs.ybuf[yc].download(s.y, P.Q, stream); rs.Mxbuf[mxc].download(s.Mx, P.Q, stream); }
     if (use_support) {
         std::vector<int> supp(ns);
         std::vector<double> mtyS(std::max(ns, 1), 0.0);
@@ -1209,8 +1208,8 @@ inline void Solver::write_capture() {
     PX_HIP(hipStreamSynchronize(stream));
     harvest_small_ranks();
     xbuf[xc].download(s.x, P.n, stream);
-    ybuf[yc].download(s.y, P.Q, stream);
-    Mxbuf[mxc].download(s.Mx, P.Q, stream);
+    rs.ybuf[yc].download(s.y, P.Q, stream);
+    rs.Mxbuf[mxc].download(s.Mx, P.Q, stream);
     if (use_support) {
         std::vector<int> supp(ns);
         std::vector<double> mtyS(std::max(ns, 1), 0.0);
@@ -1305,10 +1304,10 @@ inline void Solver::start_host_helpers() {
 // the four ping-pong pairs of the iterate, zero (also what the kernel-level test entries start from: they upload their own
 // c and [b; h], so the rest of alloc_iterate is not theirs)
 inline void Solver::alloc_iterate_pairs() {
+    build_rows();
     for (int k = 0; k < 2; ++k) {
         xbuf[k].alloc(P.n); Mtybuf[k].alloc(P.n);
-        ybuf[k].alloc(std::max<int64_t>(P.Q, 1)); Mxbuf[k].alloc(std::max<int64_t>(P.Q, 1));
-        xbuf[k].zero(stream); Mtybuf[k].zero(stream); ybuf[k].zero(stream); Mxbuf[k].zero(stream);
+        xbuf[k].zero(stream); Mtybuf[k].zero(stream); rs.ybuf[k].zero(stream); rs.Mxbuf[k].zero(stream);
     }
     xc = yc = mxc = mtyc = 0;
 }
@@ -1317,12 +1316,9 @@ inline void Solver::alloc_iterate_pairs() {
 inline void Solver::alloc_iterate() {
     alloc_iterate_pairs();
     c_d.alloc(P.n); c_d.upload(P.c.data(), P.n, stream);
-    bh_d.alloc(std::max<int64_t>(P.Q, 1));
     {
-        std::vector<double> bh(P.Q);
-        std::copy(P.b.begin(), P.b.end(), bh.begin());
-        std::copy(P.h.begin(), P.h.end(), bh.begin() + P.p);
-        bh_d.upload(bh.data(), P.Q, stream);
+        const std::vector<double> bh = stacked_bh(P.b, P.h);
+        rs.bh_d.upload(bh.data(), P.Q, stream);
         PX_HIP(hipStreamSynchronize(stream));
     }
     if (!coup_rows.empty()) {
@@ -1485,7 +1481,7 @@ inline void Solver::cert_infeas() {
 inline void Solver::cert_dual_infeas() {
     std::fill(b_host.begin(), b_host.end(), 0.0);
     std::fill(h_host.begin(), h_host.end(), 0.0);
-    bh_d.zero(stream);
+    rs.bh_d.zero(stream);
     cert_zeroed_bh = true;
     certificate_parameters();
 }
@@ -1510,7 +1506,7 @@ inline bool Solver::declare(int reason, const std::string& str, Cert kind, bool 
 // dual feasibility of the current y against the cost vector `cvec`: the largest over the shards
 inline void Solver::update_dual_feasibility(const std::vector<double>& cvec) {
     std::vector<double> y(P.Q);
-    ybuf[yc].download(y.data(), P.Q, stream);
+    rs.ybuf[yc].download(y.data(), P.Q, stream);
     PX_HIP(hipStreamSynchronize(stream));
     dual_feasibility = dual_feas_host(y, cvec, nullptr, nullptr, nullptr);
     if (sharded()) {                                     // every shard tests its own columns: the model's value is the largest
@@ -1820,6 +1816,14 @@ inline void Solver::reset_eigwork(EigWork& W) {
     W.ev.used = 0; W.evo.used = 0;
 }
 
+// [b; h] as one host vector of P.Q entries (scaled or the caller's: the loop's and the exit path's uploads)
+inline std::vector<double> Solver::stacked_bh(const std::vector<double>& b, const std::vector<double>& h) const {
+    std::vector<double> bh((size_t)P.Q);
+    std::copy(b.begin(), b.begin() + P.p, bh.begin());
+    std::copy(h.begin(), h.begin() + P.m, bh.begin() + P.p);
+    return bh;
+}
+
 // c and [b; h] on the device after a certificate search zeroed them (cert_infeas, cert_dual_infeas): from the Prep again
 inline void Solver::restore_cert_data() {
     if (cert_zeroed_c) {
@@ -1835,10 +1839,8 @@ inline void Solver::restore_cert_data() {
     }
     if (cert_zeroed_bh) {
         b_host = P.b; h_host = P.h;
-        std::vector<double> bh(P.Q);
-        std::copy(P.b.begin(), P.b.end(), bh.begin());
-        std::copy(P.h.begin(), P.h.end(), bh.begin() + P.p);
-        bh_d.upload(bh.data(), P.Q, stream);
+        const std::vector<double> bh = stacked_bh(P.b, P.h);
+        rs.bh_d.upload(bh.data(), P.Q, stream);
         PX_HIP(hipStreamSynchronize(stream));
         cert_zeroed_bh = false;
     }
@@ -1852,13 +1854,13 @@ inline void Solver::reset_for_solve() {
     req = SolveRequest{};                                // the one place a request is cleared
     init_parameters();                                   // Params, target ranks, histories, time_limit
     reduce_global_constants();                           // the norms may have changed (proxsdp_hip_model_update); max_iter_local
-    for (int k = 0; k < 2; ++k) { xbuf[k].zero(stream); Mtybuf[k].zero(stream); ybuf[k].zero(stream); Mxbuf[k].zero(stream); }
+    for (int k = 0; k < 2; ++k) { xbuf[k].zero(stream); Mtybuf[k].zero(stream); rs.ybuf[k].zero(stream); rs.Mxbuf[k].zero(stream); }
     restore_cert_data();
     part.zero(stream); scal.zero(stream);
     small_rank.zero(stream);
     if (small_rank_host.p) std::fill(small_rank_host.p, small_rank_host.p + 2 * small_blocks.size() + 2, 0.0);
     if (use_support) { MtyS_cur.zero(stream); xsave_d.zero(stream); esv_d.zero(stream); respart_d.zero(stream); }
-    ycand_d.zero(stream); Mtycand_d.zero(stream); bpart.zero(stream); bscal.zero(stream);
+    rs.ycand_d.zero(stream); Mtycand_d.zero(stream); bpart.zero(stream); bscal.zero(stream);
     hbscal.assign(64, 0.0);
     if (hscal_pin.p) std::fill(hscal_pin.p, hscal_pin.p + 64, 0.0);
     for (int idx : big_blocks) reset_eigwork(eig[idx]);

@@ -498,6 +498,47 @@ struct SolveState {
     int xc = 0, mtyc = 0, yc = 0, mxc = 0;     // index of the "current" buffer of each ping-pong pair
 };
 
+constexpr int NCAND = 3;    // linesearch candidates per batch (options.general_batch = 0: one); the scalar record always holds NCAND
+// The device state of a Solver that follows the rows of M = [A; G]: sized by Q = p + m or by the nnz stored entries, or derived
+// from M's pattern.  RULE: a device member sized by the rows or by the stored entries is declared here and allocated by build()
+// / build_exit() / build_segments(), nowhere else; the set-up stages only fill.  A row change of a model handle
+// (proxsdp_model::change_rows) builds a second RowState for the new shape, fills it from this one and exchanges the two.
+// Not here, because the handle refuses every model whose rows would change them (capi.hip): the equilibration diagonals, the
+// coupling rows' weights, the dense matrix.  The support path's structures are redone as a unit (proxsdp_model::rebuild_support).
+struct RowState {
+    DevBuf<int> csr_ptr, csr_col, csc_ptr, csc_row;      // the operator in both orientations, int32 indices
+    DevBuf<double> csr_val, csc_val;
+    bool csr_wave = false;                               // the launch shape of M x: a wave per row; the rows longer than
+    int n_seg = 0, n_long = 0;                           // Solver::LONG_ROW in segments (k_spmv_csr_seg)
+    DevBuf<int> seg_lo_d, seg_hi_d, long_row_d, long_ptr_d;
+    DevBuf<double> segpart_d;
+    DevBuf<double> bh_d, ybuf[2], Mxbuf[2], ycand_d;    // [b; h], the ping-pong pairs of y and M x, the candidates' y_c
+    struct Exit {                                        // the device exit path's (exit_device.hip.hpp), built on its first use
+        DevBuf<double> cval, rval;                       // the caller's unscaled values in CSC / CSR storage order
+        DevBuf<double> bh, slack, part;                  // [b_orig; h_orig]; M x - [b; h]; the feasibility reductions' shares
+        int feas_wg = 1;
+    } exit;
+    DevBuf<int> csc_pos_d, csr_pos_d;                    // a model handle's position maps (Prep::csc_pos / csr_pos), else empty
+
+    void build(int64_t n, int64_t p, int64_t m, int64_t nnz, bool record_maps) {
+        const size_t nz = (size_t)std::max<int64_t>(nnz, 1), q1 = (size_t)std::max<int64_t>(p + m, 1);
+        csr_ptr.alloc((size_t)(p + m) + 1); csr_col.alloc(nz); csr_val.alloc(nz);
+        csc_ptr.alloc((size_t)n + 1); csc_row.alloc(nz); csc_val.alloc(nz);
+        bh_d.alloc(q1); ycand_d.alloc((size_t)NCAND * q1);
+        for (int k = 0; k < 2; ++k) { ybuf[k].alloc(q1); Mxbuf[k].alloc(q1); }
+        if (record_maps) { csc_pos_d.alloc(nz); csr_pos_d.alloc(nz); }
+    }
+    void build_exit(int64_t p, int64_t m, int64_t nnz, int feas_grid) {
+        const size_t nz = (size_t)std::max<int64_t>(nnz, 1), q1 = (size_t)std::max<int64_t>(p + m, 1);
+        exit.cval.alloc(nz); exit.rval.alloc(nz); exit.bh.alloc(q1); exit.slack.alloc(q1);
+        exit.feas_wg = feas_grid; exit.part.alloc((size_t)4 * feas_grid);
+    }
+    void build_segments(int segments, int long_rows) {
+        n_seg = segments; n_long = long_rows;
+        if (n_seg > 0) { seg_lo_d.alloc(n_seg); seg_hi_d.alloc(n_seg); long_row_d.alloc(n_long); long_ptr_d.alloc(n_long + 1); segpart_d.alloc(n_seg); }
+    }
+};
+
 class Solver : public SolveState {
 public:
     // time0 is stamped BEFORE prepare(): the reference's clock starts at the top of chambolle_pock
@@ -722,9 +763,10 @@ public:
 private:
     friend struct ::proxsdp_model;
     // device state
-    DevBuf<double> xbuf[2], Mtybuf[2], ybuf[2], Mxbuf[2], c_d, bh_d, part, scal;
-    DevBuf<int> csr_ptr, csr_col, csc_ptr, csc_row;
-    DevBuf<double> csr_val, csc_val;
+    DevBuf<double> xbuf[2], Mtybuf[2], c_d, part, scal;
+    RowState rs;                               // the operator, y, M x, [b; h]: everything sized by the rows (the rule is at the struct)
+    void build_rows() { if (rs.csr_ptr.n == 0) rs.build(P.n, P.p, P.m, P.nnz, P.record_maps); }   // (the first set-up stage that needs it)
+    std::vector<double> stacked_bh(const std::vector<double>& b, const std::vector<double>& h) const;
     DevBuf<long long> one_off, soc_off;
     DevBuf<int> soc_len;
     DevBuf<double> one_min, soc_gap_d;
@@ -744,16 +786,11 @@ private:
     bool zero_copy_small() const { return P.n <= (1 << 16); }
     void project_small_blocks(double* x);
     void harvest_small_ranks();
-    bool csr_wave = false;
     int rotate_lds_cap = 60 * 1024;           // dynamic LDS granted to k_lz_rotate (setup_device)
     int rotate_mfma_lds_cap = 0;              // ... to k_lz_rotate_mfma
     // rows longer than LONG_ROW entries: segmented SpMV (kernels.hip.hpp k_spmv_csr_seg)
     static constexpr int LONG_ROW = 8192;
-    DevBuf<int> seg_lo_d, seg_hi_d, long_row_d, long_ptr_d;
-    DevBuf<double> segpart_d;
-    int n_seg = 0, n_long = 0;
-    void setup_long_rows(const std::vector<int>& rp);
-    void choose_spmv_shape(const std::vector<int>& rp);
+    void setup_long_rows(RowState& to, const std::vector<int>& rp);
 
     // scalar state (Params, structs.jl:159-192) that init_parameters() and reduce_global_constants() set; the rest is SolveState's
     double theta = 1, beta = 1, adapt_level = 0.9;
@@ -786,6 +823,7 @@ private:
     bool support_path_wanted(size_t ns) const;
     void upload_support(const std::vector<int>& supp);
     void upload_sparse_operator();
+    void upload_pattern(RowState& to, const Prep& R);
     void launch_clamp_scalars(double* x, int cnt);
     void launch_soc_project(double* x, int nsoc);
     void launch_soc_gap(const double* x, int nsoc);
@@ -853,16 +891,14 @@ private:
     void finish_snapshot(double dfeas);
     // the device exit path's pieces and what they read (exit_device.hip.hpp)
     struct ExitDev {
-        bool ready = false;
-        DevBuf<double> cval, rval;             // the caller's unscaled values in CSC / CSR storage order
-        DevBuf<double> c, zero, bh;            // c_orig; zeros (dense A with c = 0); [b_orig; h_orig]
+        bool ready = false;                    // (with it RowState::exit: the unscaled values, [b_orig; h_orig], the slack)
+        DevBuf<double> c, zero;                // c_orig; zeros (dense A with c = 0)
         DevBuf<long long> inv, one_off, soc_off;
         DevBuf<int> soc_len;
         std::vector<int> ones;                 // the 1x1 PSD cones, in cone order
-        DevBuf<double> slack, dc, base;        // M x - [b; h]; the dual cone; c + A'y of a dense A
+        DevBuf<double> dc, base;               // the dual cone; c + A'y of a dense A
         DevBuf<double> prim, dcone, onev;      // staging where the caller gave no device buffer; the 1x1 cones' x
-        DevBuf<double> part, scal;
-        int feas_wg = 1;
+        DevBuf<double> scal;
     } xd;
     void exit_rescale_iterate();
     void exit_device_setup();
@@ -906,7 +942,7 @@ private:
     void dense_ev_harvest();
     // linesearch candidates (linesearch_and_residuals): y_c, M'y_c, partials, the scalar record on the device and its
     // read-back (support path: hbscal; otherwise the pinned hscal_pin)
-    DevBuf<double> ycand_d, Mtycand_d, bpart, bscal;
+    DevBuf<double> Mtycand_d, bpart, bscal;      // (y_c: RowState::ycand_d)
     std::vector<double> hbscal;
     PinnedBuf hscal_pin;
 

@@ -27,7 +27,7 @@ inline void Solver::test_spmv(bool transpose, const double* in, double* out) {
         alloc_iterate_pairs();
         use_support = false;
         alloc_candidates();
-        ycand_d.upload(in, P.Q, stream);
+        rs.ycand_d.upload(in, P.Q, stream);
         dev::TrialBatch tb{};
         tb.nc = 1; tb.plain = 1;
         batch_mty(tb, 1);
@@ -55,10 +55,10 @@ inline void Solver::test_trial_batch(proxsdp_trial_batch& t) {
     upload_sparse_operator();
     alloc_iterate_pairs();
     c_d.alloc(n); c_d.upload(P.c.data(), n, stream);
-    bh_d.alloc(Q); bh_d.upload(t.bh, Q, stream);
+    rs.bh_d.upload(t.bh, Q, stream);
     if (t.roww) { roww_d.alloc(Q); roww_d.upload(t.roww, Q, stream); }
-    ybuf[yc].upload(t.y, Q, stream);
-    Mxbuf[1 - mxc].upload(t.Mx, Q, stream); Mxbuf[mxc].upload(t.Mx_old, Q, stream);
+    rs.ybuf[yc].upload(t.y, Q, stream);
+    rs.Mxbuf[1 - mxc].upload(t.Mx, Q, stream); rs.Mxbuf[mxc].upload(t.Mx_old, Q, stream);
     xbuf[xc].upload(t.x_old, n, stream);
     PX_HIP(hipStreamSynchronize(stream));
     use_support = t.support == 1;
@@ -93,7 +93,7 @@ inline void Solver::test_trial_batch(proxsdp_trial_batch& t) {
     const BatchShape b = batch_shape();
     t.gq = b.gq; t.gx = b.gx;
     for (int c = 0; c < t.nc; ++c) {
-        PX_HIP(hipMemcpyAsync(t.y_out + (size_t)c * Q, ycand_d.p + (size_t)c * b.ystride, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, stream));
+        PX_HIP(hipMemcpyAsync(t.y_out + (size_t)c * Q, rs.ycand_d.p + (size_t)c * b.ystride, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, stream));
         if (t.ns > 0)
             PX_HIP(hipMemcpyAsync(t.Mty_out + (size_t)c * t.ns, Mtycand_d.p + (size_t)c * b.mstride, (size_t)t.ns * sizeof(double), hipMemcpyDeviceToHost, stream));
     }

@@ -340,7 +340,56 @@ def test_a_change_allocates_less_than_the_model_and_leaks_nothing_per_round():
         assert again.info()["device_bytes"] == whole
 
 
-# ----------------------------------------------------------------- 10. Optimizer
+# ----------------------------------------------------------------- 10. across the long-row limit of M x
+SIDE130 = dict(min_size_krylov_eigs=32, max_iter=30)
+
+
+def _full_rows(n, count, parts=1):
+    """`count` rows with an entry in every one of the n columns -- small integers, so every stored value, product with 1.0 and
+    sum of squares of unscaled values is exact -- each cut into `parts` consecutive pieces (rows of their own); h = 40000 is
+    above 3 n |x| for every x the first iterations reach: the rows are slack"""
+    ptr, cols, vals = [0], [], []
+    for r in range(count):
+        for piece in np.array_split(np.arange(n, dtype=np.int64), parts):
+            cols += piece.tolist()
+            vals += (1.0 + (piece + r) % 3).tolist()
+            ptr.append(len(cols))
+    return (np.array(ptr, dtype=np.int64), np.array(cols, dtype=np.int64), np.array(vals)), np.full(len(ptr) - 1, 40000.0)
+
+
+def test_a_row_longer_than_the_segment_limit_comes_and_goes():
+    """Side 130 has 8515 variables, the smallest side above the 8192 entries from which M x takes a row in segments
+    (Solver::LONG_ROW): a row over every column switches the segmented launches on, dropping it switches them off, two such
+    rows give two long rows.  After every step the handle is a fresh model of the changed problem, and after the drop it holds
+    the bytes it held before the add: the segment buffers went with the last long row.  Before that comparison the handle is
+    warmed with the same entries in two half rows (none above the limit), solved and dropped again: the staging buffer of host
+    values only grows (it is sized by the largest change so far), and a solve allocates some workspaces on first use; neither
+    is what the comparison is about."""
+    pr = P.maxcut(130, seed=0, avg_degree=6.0)
+    assert pr.n == 130 * 131 // 2 == 8515 and pr.n > 8192 and pr.G.shape[0] == 0
+    one, two, halves = _full_rows(pr.n, 1), _full_rows(pr.n, 2), _full_rows(pr.n, 1, parts=2)
+    assert np.diff(halves[0][0]).max() <= 8192 < np.diff(one[0][0]).min()
+    with B.Model(pr, _opts(**SIDE130)) as mdl:
+        mdl.change_rows(add=halves)
+        _assert_is_fresh_model(mdl, _changed(pr, halves)[0], SIDE130, "two half rows")
+        mdl.change_rows(drop=[0, 1])
+        before = mdl.info()["device_bytes"]
+        ch = mdl.change_rows(add=one)
+        assert (ch.m, ch.nnz) == (1, 130 + pr.n)
+        print("device_bytes", before, "with the long row", mdl.info()["device_bytes"])
+        _assert_is_fresh_model(mdl, _changed(pr, one)[0], SIDE130, "one long row")
+        ch = mdl.change_rows(drop=[0])
+        assert (ch.m, ch.nnz) == (0, 130)
+        after = mdl.info()["device_bytes"]
+        print("device_bytes after the drop", after)
+        _assert_is_fresh_model(mdl, pr, SIDE130, "long row dropped")
+        assert after == before, (after, before)
+        ch = mdl.change_rows(add=two)
+        assert (ch.m, ch.nnz) == (2, 130 + 2 * pr.n)
+        _assert_is_fresh_model(mdl, _changed(pr, two)[0], SIDE130, "two long rows")
+
+
+# ----------------------------------------------------------------- 11. Optimizer
 def _assert_same_sol(a, b, what):
     for k in ("status", "iter", "objval", "dual_objval", "gap", "final_rank"):
         assert getattr(a, k) == getattr(b, k), (what, k, getattr(a, k), getattr(b, k))
