@@ -80,6 +80,10 @@ extern "C" {
  * later: proxsdp_hip_model_triangles (the most violated triangle inequalities of a PSD cone of a model handle, separated on
  * the device) with its host restatement proxsdp_host_triangle_cuts, and proxsdp_hip_model_inactive_rows (the inequality rows
  * that went slack), with the new structs proxsdp_triangle_cuts and proxsdp_inactive_rows: functions and two new structs, no
+ * existing struct changed: the version stays;
+ * later: proxsdp_hip_model_round (randomised hyperplane rounding of a PSD cone's factors to +-1 vectors and a one-flip local
+ * search against the handle's current objective, on the device) with its host restatement proxsdp_host_round and the
+ * direction generator proxsdp_host_round_directions, with the new struct proxsdp_rounding: functions and one new struct, no
  * existing struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
@@ -981,6 +985,98 @@ typedef struct proxsdp_inactive_rows {
     int64_t n_rows;           /* out */
 } proxsdp_inactive_rows;
 int  proxsdp_hip_model_inactive_rows(proxsdp_model* mdl, proxsdp_inactive_rows* q);
+/* ------------------------------------------- rounding on a model handle: a +-1 vector from a PSD cone's factors
+ * The verbs above tighten the relaxation's bound; this one produces a feasible point of a +-1 model (Max-Cut and its kin):
+ * randomised hyperplane rounding (Goemans-Williamson) of the factors a solve hands out (proxsdp_psd_factors) to `trials`
+ * sign vectors at once, each improved by a one-flip local search against the objective the handle holds NOW, and the best
+ * one returned with its value.  The reference has no counterpart.  Everything below is fp64, evaluated left to right exactly
+ * as written, with no contraction, on the device and on the host: the result is a pure function of the inputs, the same bits
+ * on every run, whatever the launch and whatever the knobs.
+ * IN.   cone: a PSD cone of the handle, side s >= 2.  V: s x r, column-major, ld = s; values: r numbers, finite and > 0 (the
+ *       units of proxsdp_psd_factors; 1 <= r <= s).  on_device says where V and values live (device pointers are borrowed
+ *       and trusted as proxsdp_model_data's are).  trials: T, a multiple of 64, 64 <= T <= 65536.  max_sweeps: 0 .. 1000,
+ *       0 = rounding only.
+ * WEIGHTS.     w_k = sqrt(values[k]), by std::sqrt on the HOST (device values cost one download of r doubles); no square
+ *              root and no transcendental function runs on the device.
+ * DIRECTIONS.  g(k, t) = (((u_0 + u_1) + ... + u_11) - 6.0), u_q = uniform53(seed, (t r + k) 12 + q): the counter-based
+ *              generator of proxsdp_host_start_vector (integer operations, an exact conversion, twelve additions in order).
+ * EMBEDDING.   y(i, t) = 0.0; for k = 0 .. r-1: y = y + (V[i, k] * w_k) * g(k, t).
+ * SIGNS.       sigma_i = -1 if y < 0, else +1 (a zero row of V gives +1).
+ * OBJECTIVE.   From the handle's CURRENT c in the caller's units (create's, or the last proxsdp_hip_model_update's), the
+ *              cone's entries only: with var(i, j) the cone's variable of X_ij, d_i = c[var(i, i)], w_ij = c[var(i, j)] for
+ *              i != j, adj(i) = the j != i with w_ij != 0, ascending.  The value of a sign vector is the cone's part of c'x
+ *              at x = the triangle of sigma sigma':
+ *                  f = 0.0;  for i ascending: f = f + d_i;
+ *                  for i ascending: u = 0.0; for j in adj(i), j > i, ascending: u = u + w_ij * sigma_j;  f = f + sigma_i * u
+ * SEARCH.      The library minimises (c is already sign-flipped for a MAX model).  A sweep visits i = 0 .. s-1: a = 0.0;
+ *              for j in adj(i) ascending: a = a + w_ij * sigma_j with the signs as they are now; if sigma_i * a > 0, sigma_i
+ *              is flipped at once.  Sweeps repeat until one flips nothing or max_sweeps have run.  The value after the
+ *              search is computed afresh by the expression above, not accumulated from the flips.
+ * ANSWER.      The trial with the smallest final value; among equal values the lowest t.
+ * OUT (HOST arrays, caller-allocated): signs (s entries, +-1), best_trial, value, value_rounded (the smallest value BEFORE
+ *       the search), sweeps (the most any trial ran, counting the sweep that flipped nothing), flips (the total over all
+ *       trials); optional, NULL when not wanted: values_rounded[T], values_final[T], and the adjacency the library derived
+ *       from c: adj_ptr[s + 1], adj_col / adj_val with room for adj_cap entries (adj_nnz written), diag[s] -- asked for by
+ *       a non-NULL adj_ptr, which needs the other three.
+ * The handle's data is not touched: a solve after the call equals a solve before it.  Scratch (the adjacency, 8 r T bytes
+ * of directions, two copies of 8 s T / 64 bytes of sign words, 16 T bytes of values) is allocated in the call, released
+ * before it returns and reported in bytes_allocated, not in proxsdp_model_info.device_bytes.
+ * Other variables of the model are ignored, and the rows of A and G are NOT checked: any +-1 vector satisfies diag(X) = 1
+ * and every triangle inequality at X = sigma sigma'; any other row is the caller's constraint to test.
+ * How: the adjacency is built from the exit path's unscaled c on the device (count, prefix sum, ballot-compacted fill: the
+ * values do not visit the host); k_round_directions writes g; k_round_signs has lane = trial and one ballot of y < 0 per node
+ * and 64 trials gives a 64-bit word, words[i][T / 64]; k_round_search has one wave own 64 trials, walks the nodes in order
+ * with the adjacency wave-uniform, each lane reading its bit, and XORs the ballot of sigma_i a > 0 into the node's word.  The
+ * wave's word column lives in LDS for s <= lds_side (default 4096: 32 KiB), in global memory beyond.
+ * Test knobs (0 = the library's choice; the result does not depend on any): grid_adjacency, grid_directions, grid_signs,
+ * grid_search = workgroups of each launch; lds_side = the largest side whose words are kept in LDS (< 0: none, at most 8192).
+ * PROXSDP_E_INVALID, decided on the host before any device call: a NULL struct or handle; a NULL V, values or signs; a wrong
+ * struct_size; on_device other than 0 or 1; a cone number outside the model; a cone of side < 2; r outside 1 .. s; trials
+ * not a multiple of 64 or outside 64 .. 65536; max_sweeps outside 0 .. 1000; a negative knob other than lds_side; an
+ * adjacency asked for with a NULL adj_col / adj_val / diag or adj_cap smaller than its entries; a host `values` entry that is
+ * not finite or not > 0; a non-finite host V.  Device factors are checked before anything else runs (V by a reduction,
+ * values on their way to the weights); the message names the array. */
+typedef struct proxsdp_rounding {
+    int64_t struct_size;      /* = sizeof(proxsdp_rounding) */
+    int32_t on_device;        /* where V and values live: 0 host, 1 DEVICE pointers on the model's device (proxsdp_host_round
+                               * ignores it) */
+    int32_t cone;             /* PSD cone of the model, 0-based in cone order (proxsdp_host_round ignores it) */
+    int32_t r;                /* columns of V */
+    int32_t trials;           /* T */
+    int64_t seed;
+    int32_t max_sweeps;
+    int32_t grid_adjacency, grid_directions, grid_signs, grid_search, lds_side;   /* test knobs, 0 = default */
+    const double* V;          /* s x r, column-major, ld = s */
+    const double* values;     /* r */
+    /* out: caller-allocated HOST arrays */
+    int8_t*  signs;           /* s */
+    double*  values_rounded;  /* T, or NULL */
+    double*  values_final;    /* T, or NULL */
+    int64_t* adj_ptr;         /* s + 1, or NULL = the adjacency is not wanted (proxsdp_host_round ignores these five) */
+    int64_t* adj_col;         /* adj_cap */
+    double*  adj_val;         /* adj_cap */
+    double*  diag;            /* s */
+    int64_t adj_cap;
+    int64_t adj_nnz;          /* out (written when the adjacency is asked for) */
+    int64_t best_trial;
+    double  value, value_rounded;
+    int64_t flips;
+    int32_t sweeps;
+    int32_t reserved;
+    int64_t bytes_allocated;  /* device bytes this call allocated (and released); 0 on the host */
+    double  seconds;          /* wall time of the call */
+    double  search_seconds;   /* the search kernel alone, between two device events (0 on the host) */
+} proxsdp_rounding;
+int  proxsdp_hip_model_round(proxsdp_model* mdl, proxsdp_rounding* q);
+/* The same contract with no device and no handle: a serial loop over the trials.  The adjacency is an argument: adj_ptr
+ * (side + 1), adj_col / adj_val (adj_ptr[side] entries; per node ascending, none equal to the node, values finite; symmetry is
+ * the caller's to keep) and diag (side).  PROXSDP_E_INVALID: as above where it applies; side < 2 or > 46340; a NULL or
+ * malformed adjacency. */
+int  proxsdp_host_round(int64_t side, const int64_t* adj_ptr, const int64_t* adj_col, const double* adj_val,
+                        const double* diag, proxsdp_rounding* q);
+/* g (r x trials doubles, row k contiguous) = the directions above.  PROXSDP_E_INVALID: NULL g, r < 1 or > 46340, trials as
+ * above. */
+int  proxsdp_host_round_directions(int64_t seed, int32_t r, int32_t trials, double* g);
 /* test entry: the model's current internal data, downloaded into caller-allocated host arrays.  The sizes (n, Q = p + m, nnz,
  * ns = length of the support list, 0 when the support path is off) and the four norms (||b||, ||h||, ||c||, ||M||_F) are always
  * written; an array is written when its pointer is not NULL (call once with every pointer NULL for the sizes, allocate, call

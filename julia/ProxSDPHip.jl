@@ -529,4 +529,64 @@ function model_inactive_rows(mdl::Ptr{Cvoid}, dual_in, slack_in, m::Integer; dua
     return rows[1:Int(q.n_rows)]
 end
 
+# ---- a +-1 vector from a kept model's factors (include/proxsdp_hip.h, "rounding on a model handle")
+mutable struct Rounding          # proxsdp_rounding
+    struct_size::Int64
+    on_device::Int32
+    cone::Int32
+    r::Int32
+    trials::Int32
+    seed::Int64
+    max_sweeps::Int32
+    grid_adjacency::Int32
+    grid_directions::Int32
+    grid_signs::Int32
+    grid_search::Int32
+    lds_side::Int32
+    V::Ptr{Float64}
+    values::Ptr{Float64}
+    signs::Ptr{Int8}
+    values_rounded::Ptr{Float64}
+    values_final::Ptr{Float64}
+    adj_ptr::Ptr{Int64}
+    adj_col::Ptr{Int64}
+    adj_val::Ptr{Float64}
+    diag::Ptr{Float64}
+    adj_cap::Int64
+    adj_nnz::Int64
+    best_trial::Int64
+    value::Float64
+    value_rounded::Float64
+    flips::Int64
+    sweeps::Int32
+    reserved::Int32
+    bytes_allocated::Int64
+    seconds::Float64
+    search_seconds::Float64
+end
+
+"""
+    model_round(mdl, values, V, side; cone = 1, trials = 1024, seed = 0, max_sweeps = 50, on_device = false)
+
+Randomised hyperplane rounding of the factors `V` (`side x r`, a `Matrix{Float64}`: Julia's column-major storage is what the
+entry reads) and `values` (`r`, all > 0) of PSD cone `cone` (1-based here) of the kept model `mdl` to `trials` +-1 vectors, each
+improved by a one-flip local search against the model's current objective; with `on_device = true` both are DEVICE pointers
+and `r = length` must be given as `r`.  Returns a NamedTuple: `signs` (`Vector{Int8}`), `value` (minimisation form),
+`value_rounded`, `best_trial` (0-based), `sweeps`, `flips`, `values_rounded`, `values_final`, `seconds`.
+"""
+function model_round(mdl::Ptr{Cvoid}, values, V, side::Integer; cone::Integer = 1, trials::Integer = 1024, seed::Integer = 0,
+                     max_sweeps::Integer = 50, on_device::Bool = false, r::Integer = on_device ? 0 : length(values))
+    signs = zeros(Int8, side); vr = zeros(trials); vf = zeros(trials)
+    GC.@preserve values V signs vr vf begin
+        q = Rounding(sizeof(Rounding), Int32(on_device), Int32(cone - 1), Int32(r), Int32(trials), Int64(seed), Int32(max_sweeps),
+                     Int32(0), Int32(0), Int32(0), Int32(0), Int32(0),
+                     on_device ? Ptr{Float64}(V) : pointer(V), on_device ? Ptr{Float64}(values) : pointer(values),
+                     pointer(signs), pointer(vr), pointer(vf), Ptr{Int64}(C_NULL), Ptr{Int64}(C_NULL), Ptr{Float64}(C_NULL),
+                     Ptr{Float64}(C_NULL), 0, 0, 0, 0.0, 0.0, 0, Int32(0), Int32(0), 0, 0.0, 0.0)
+        _check_rc(ccall((:proxsdp_hip_model_round, libproxsdp_hip), Cint, (Ptr{Cvoid}, Ref{Rounding}), mdl, q))
+    end
+    return (signs = signs, value = q.value, value_rounded = q.value_rounded, best_trial = q.best_trial, sweeps = q.sweeps,
+            flips = q.flips, values_rounded = vr, values_final = vf, seconds = q.seconds)
+end
+
 end # module

@@ -249,6 +249,18 @@ class InactiveRowsIO(C.Structure):
                 ("dual_tol", f64), ("slack_tol", f64), ("rows", pi64), ("n_rows", i64)]
 
 
+class RoundingIO(C.Structure):
+    """proxsdp_rounding (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("on_device", i32), ("cone", i32), ("r", i32), ("trials", i32), ("seed", i64),
+                ("max_sweeps", i32), ("grid_adjacency", i32), ("grid_directions", i32), ("grid_signs", i32),
+                ("grid_search", i32), ("lds_side", i32),
+                ("V", pf64), ("values", pf64),
+                ("signs", C.POINTER(C.c_int8)), ("values_rounded", pf64), ("values_final", pf64),
+                ("adj_ptr", pi64), ("adj_col", pi64), ("adj_val", pf64), ("diag", pf64), ("adj_cap", i64),
+                ("adj_nnz", i64), ("best_trial", i64), ("value", f64), ("value_rounded", f64), ("flips", i64),
+                ("sweeps", i32), ("reserved", i32), ("bytes_allocated", i64), ("seconds", f64), ("search_seconds", f64)]
+
+
 MODEL_DUMP_ARRAYS = (("csc_val", "nnz"), ("csr_val", "nnz"), ("csc_val_orig", "nnz"), ("csr_val_orig", "nnz"),
                      ("c", "n"), ("c_orig", "n"), ("bh", "Q"), ("support", "ns"), ("cS", "ns"))
 MODEL_NORM_NAMES = ("norm_b", "norm_h", "norm_c", "frob")
@@ -320,6 +332,9 @@ def lib():
     L.proxsdp_hip_model_triangles.argtypes = [C.c_void_p, C.POINTER(TriangleCutsIO)]
     L.proxsdp_host_triangle_cuts.argtypes = [pf64, i64, pi64, i32, C.POINTER(TriangleCutsIO)]
     L.proxsdp_hip_model_inactive_rows.argtypes = [C.c_void_p, C.POINTER(InactiveRowsIO)]
+    L.proxsdp_hip_model_round.argtypes = [C.c_void_p, C.POINTER(RoundingIO)]
+    L.proxsdp_host_round.argtypes = [i64, pi64, pi64, pf64, pf64, C.POINTER(RoundingIO)]
+    L.proxsdp_host_round_directions.argtypes = [i64, i32, i32, pf64]
     L.proxsdp_hip_factor_residual.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64]
     L.proxsdp_hip_factor_residual_kernel.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64, i32, pf64]
     L.proxsdp_hip_psd_project.argtypes = [pf64, i64, i32, i32, C.POINTER(Options), pf64, pf64,
@@ -1105,6 +1120,87 @@ def host_triangle_cuts(X, count=1000, min_violation=1e-3, rhs=1.0, cone_idx=None
     return TriangleCuts(T, arr, index_base)
 
 
+class Rounding:
+    """What a rounding returned (proxsdp_rounding): signs (int8, +-1, one per node of the cone), value (of `signs`, the
+    cone's part of c'x in the units and the minimisation form of the model's c), value_rounded (the smallest value before the
+    local search), best_trial, sweeps, flips, values_rounded / values_final (one per trial), seconds, search_seconds,
+    bytes_allocated, and adjacency = (ptr, cols, values, diag) as the library derived it from c, when asked for (else None).
+    objective: set by Optimizer.round.  arrays: every output array at its full length."""
+
+    def __init__(self, Q, arr):
+        self.arrays = arr
+        self.signs = arr["signs"].copy()
+        self.value, self.value_rounded = float(Q.value), float(Q.value_rounded)
+        self.best_trial, self.sweeps, self.flips = int(Q.best_trial), int(Q.sweeps), int(Q.flips)
+        self.values_rounded, self.values_final = arr["values_rounded"].copy(), arr["values_final"].copy()
+        self.seconds, self.search_seconds = float(Q.seconds), float(Q.search_seconds)
+        self.bytes_allocated = int(Q.bytes_allocated)
+        self.adjacency = None
+        if "adj_ptr" in arr:
+            k = int(Q.adj_nnz)
+            self.adjacency = (arr["adj_ptr"].copy(), arr["adj_col"][:k].copy(), arr["adj_val"][:k].copy(), arr["diag"].copy())
+        self.objective = None
+
+
+def _rounding_struct(side, r, trials, seed, max_sweeps, knobs=None, adj_cap=None, sentinel=None):
+    """proxsdp_rounding with output arrays for a cone of that side (prefilled with `sentinel` when given), and the arrays.
+    knobs: {grid_adjacency, grid_directions, grid_signs, grid_search: workgroups; lds_side: None = the library's choice, 0 =
+    never in LDS}; adj_cap: room for the adjacency (None: not asked for)"""
+    s = max(int(side), 1)
+    nt = int(trials) if 0 < int(trials) <= (1 << 20) else 1         # (an absurd count is the library's to refuse)
+    arr = dict(signs=np.zeros(s, dtype=np.int8), values_rounded=np.zeros(nt), values_final=np.zeros(nt))
+    if adj_cap is not None:
+        cap = max(int(adj_cap), 1)
+        arr.update(adj_ptr=np.zeros(s + 1, dtype=np.int64), adj_col=np.zeros(cap, dtype=np.int64), adj_val=np.zeros(cap),
+                   diag=np.zeros(s))
+    if sentinel is not None:
+        for a in arr.values():
+            a[:] = sentinel
+    Q = RoundingIO()
+    Q.struct_size = C.sizeof(RoundingIO)
+    Q.r, Q.trials, Q.seed, Q.max_sweeps = int(r), int(trials), int(seed), int(max_sweeps)
+    knobs = dict(knobs or {})
+    lds = knobs.pop("lds_side", None)
+    Q.lds_side = 0 if lds is None else (-1 if int(lds) <= 0 else int(lds))
+    for k, v in knobs.items():
+        if k not in ("grid_adjacency", "grid_directions", "grid_signs", "grid_search"):
+            raise ValueError(f"round: no knob {k}")
+        setattr(Q, k, int(v))
+    Q.signs = arr["signs"].ctypes.data_as(C.POINTER(C.c_int8))
+    Q.values_rounded, Q.values_final = _p(arr["values_rounded"]), _p(arr["values_final"])
+    if adj_cap is not None:
+        Q.adj_ptr, Q.adj_col, Q.adj_val, Q.diag = _p(arr["adj_ptr"], pi64), _p(arr["adj_col"], pi64), _p(arr["adj_val"]), _p(arr["diag"])
+        Q.adj_cap = int(adj_cap)
+    return Q, arr
+
+
+def host_round_directions(seed, r, trials):
+    """proxsdp_host_round_directions: the r x trials directions g(k, t) of a rounding with that seed"""
+    g = np.zeros((max(int(r), 1), int(trials) if 0 < int(trials) <= (1 << 20) else 1))
+    _check(lib().proxsdp_host_round_directions(int(seed), int(r), int(trials), _p(g)))
+    return g
+
+
+def host_round(values, vectors, adjacency, trials=1024, seed=0, max_sweeps=50, sentinel=None):
+    """proxsdp_host_round: the rounding of Model.round on the host, serially (no device, no handle).  values (r,) and
+    vectors (side, r): the factors; adjacency = (ptr, cols, values, diag) of the objective.  Returns a Rounding."""
+    vals = _f(values).ravel()
+    V = np.asarray(vectors, dtype=np.float64)
+    if V.ndim != 2 or V.shape[1] != len(vals):
+        raise ValueError("host_round: vectors must be side x len(values)")
+    side = V.shape[0]
+    Vf = np.ascontiguousarray(V.T).ravel()                          # column-major, ld = side
+    ptr, cols, av, diag = adjacency
+    ptr, cols, av, diag = _i(ptr), _i(cols), _f(av), _f(diag)
+    if len(ptr) != side + 1 or len(diag) != side or len(cols) != len(av) or (len(ptr) and len(cols) < ptr[-1]):
+        raise ValueError("host_round: the adjacency does not fit the side")
+    Q, arr = _rounding_struct(side, len(vals), trials, seed, max_sweeps, sentinel=sentinel)
+    Q.V, Q.values = _p(Vf if Vf.size else np.zeros(1)), _p(vals if vals.size else np.zeros(1))
+    _check(lib().proxsdp_host_round(side, _p(ptr, pi64), _p(cols if len(cols) else np.zeros(1, dtype=np.int64), pi64),
+                                    _p(av if len(av) else np.zeros(1)), _p(diag if len(diag) else np.zeros(1)), C.byref(Q)))
+    return Rounding(Q, arr)
+
+
 def model_norm2(v, grid=0):
     """proxsdp_hip_model_norm2: ||v||_2 by the reduction a device-route Model.update uses, with `grid` workgroups"""
     v = _f(v).ravel()
@@ -1304,6 +1400,46 @@ class Model:
         _check(lib().proxsdp_hip_model_inactive_rows(self._handle(), C.byref(Q)))
         del keep
         return rows[:int(Q.n_rows)].copy()
+
+    # ---- a feasible point
+    def round(self, factors, cone=0, trials=1024, seed=0, max_sweeps=50, adjacency=False, knobs=None):
+        """proxsdp_hip_model_round: randomised hyperplane rounding of the factors of PSD cone `cone` to `trials` +-1 vectors
+        and a one-flip local search against the model's current c, on the device; the best vector and its value.  factors:
+        (values, vectors) as NumPy arrays (host route) or as CUDA float64 tensors (device route; mixing the two is a
+        ValueError), vectors of shape (side, r) -- or a SolveResult that carries factors (solve(factors=...)).
+        adjacency=True also returns the objective's adjacency as the library derived it; knobs: test knobs
+        (_rounding_struct).  Returns a Rounding.  The model is not touched."""
+        if isinstance(factors, SolveResult):
+            fl = getattr(factors, "psd_factors", None)
+            if fl is None:
+                raise ValueError("Model.round: the result carries no factors (solve(factors=True))")
+            factors = fl[cone][:2]
+        vals, V = factors[0], factors[1]
+        on_dev = [_is_tensor(v) and v.is_cuda for v in (vals, V)]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("Model.round: host arrays and CUDA tensors cannot be mixed in one call")
+        side = self._sides[cone] if 0 <= int(cone) < len(self._sides) else 1
+        if len(V.shape) != 2 or V.shape[1] != len(vals) or (0 <= int(cone) < len(self._sides) and V.shape[0] != side):
+            raise ValueError("Model.round: vectors must be side x len(values)")
+        Q, arr = _rounding_struct(side, len(vals), trials, seed, max_sweeps, knobs, side * (side - 1) if adjacency else None)
+        Q.cone = int(cone)
+        if all(on_dev):
+            import torch
+            dev_id = int(self._options.device_id)
+            Q.on_device = 1
+            Vt = V.t().contiguous()                                 # column-major, ld = side
+            keep = [Vt, vals]
+            Q.V = _device_ptr(Vt, Vt.numel(), dev_id, "vectors")
+            Q.values = _device_ptr(vals, len(vals), dev_id, "values")
+            torch.cuda.synchronize(dev_id)                          # the library runs on its own stream
+        else:
+            to_np = lambda v: v.numpy() if _is_tensor(v) else v
+            keep = [np.ascontiguousarray(np.asarray(to_np(V), dtype=np.float64).T).ravel(), _f(to_np(vals)).ravel()]
+            keep = [a if a.size else np.zeros(1) for a in keep]
+            Q.V, Q.values = _p(keep[0]), _p(keep[1])
+        _check(lib().proxsdp_hip_model_round(self._handle(), C.byref(Q)))
+        del keep
+        return Rounding(Q, arr)
 
     # ---- solve
     def solve(self, start=None, factors=False, primal=True, device_out=False, trace_capacity=0, time_limit=None,

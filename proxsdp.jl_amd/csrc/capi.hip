@@ -465,6 +465,46 @@ int proxsdp_hip_model_inactive_rows(proxsdp_model* mdl, proxsdp_inactive_rows* q
     });
 }
 
+int proxsdp_hip_model_round(proxsdp_model* mdl, proxsdp_rounding* q) {
+    return guarded([&]() -> int {
+        proxsdp::check_rounding_struct(q, true);
+        if (!mdl) throw std::invalid_argument("NULL handle");
+        proxsdp::Solver& s = *mdl->S;
+        const proxsdp::Prep& P = s.P;
+        if (q->cone < 0 || q->cone >= (int64_t)P.blocks.size()) throw std::invalid_argument("proxsdp_rounding.cone is outside the model's PSD cones");
+        const proxsdp::BlockInfo& B = P.blocks[q->cone];
+        proxsdp::check_rounding_factors(*q, B.n, q->on_device == 0);
+        // (the host mirror of the exit path's c is what the device holds: create and every update leave the two equal)
+        if (q->adj_ptr && proxsdp::round_adjacency_count(P.c_orig.data() + B.off, B.n) > q->adj_cap)
+            throw std::invalid_argument("proxsdp_rounding.adj_cap is smaller than the adjacency");
+        mdl->round(*q);
+        return 0;
+    });
+}
+
+int proxsdp_host_round(int64_t side, const int64_t* adj_ptr, const int64_t* adj_col, const double* adj_val, const double* diag,
+                       proxsdp_rounding* q) {
+    return guarded([&]() -> int {
+        proxsdp::check_rounding_struct(q, false);
+        if (side > proxsdp::ROUND_MAX_SIDE) throw std::invalid_argument("proxsdp_host_round: side must be 2 .. 46340");
+        proxsdp::check_rounding_factors(*q, side, true);
+        proxsdp::check_round_adjacency(side, adj_ptr, adj_col, adj_val, diag);
+        proxsdp::host_round(side, adj_ptr, adj_col, adj_val, diag, *q);
+        return 0;
+    });
+}
+
+int proxsdp_host_round_directions(int64_t seed, int32_t r, int32_t trials, double* g) {
+    return guarded([&]() -> int {
+        if (!g) throw std::invalid_argument("proxsdp_host_round_directions: g is NULL");
+        proxsdp::check_round_shape(r, trials);
+        if (r > proxsdp::ROUND_MAX_SIDE) throw std::invalid_argument("proxsdp_host_round_directions: r must be 1 .. 46340");
+        for (int64_t k = 0; k < r; ++k)
+            for (int64_t t = 0; t < trials; ++t) g[k * trials + t] = proxsdp::round_direction((uint64_t)seed, r, k, t);
+        return 0;
+    });
+}
+
 int proxsdp_hip_model_solve(proxsdp_model* mdl, const proxsdp_options* run_opt, proxsdp_result* res,
                             const proxsdp_start* start, const proxsdp_device_vectors* start_dev,
                             proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev) {

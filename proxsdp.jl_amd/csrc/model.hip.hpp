@@ -10,11 +10,13 @@
 // rows    = inequality rows added and dropped (model_rows.hip.hpp): a second RowState (solver.hip.hpp: every buffer sized by Q,
 //           nnz or the pattern) built for the new shape, filled from the live one through the plan's source maps, and exchanged
 //           with it; everything sized by n or a cone side stays
+// round   = a +-1 vector from a cone's factors against the current c (rounding.hip.hpp): reads the exit path's c, writes nothing
 // The entry points (argument checks, error codes) are in capi.hip.
 #pragma once
 #include "exit_device.hip.hpp"
 #include "model_update.hip.hpp"
 #include "model_rows.hip.hpp"
+#include "rounding.hip.hpp"
 
 struct proxsdp_model {
     std::atomic<long long> bytes{0};            // live device bytes (DevAccount); first member: outlives every buffer below
@@ -311,6 +313,17 @@ struct proxsdp_model {
         if (ch.kept) std::copy(pl.kept.begin(), pl.kept.end(), ch.kept);
         ch.bytes_allocated = allocated;
         ch.seconds = now_s() - t0;
+    }
+
+    // q: validated on the host against the cone (check_rounding_struct, check_rounding_factors).  The objective is the exit
+    // path's unscaled c, where the cone's entries are contiguous; nothing of the handle is written, the scratch is the call's
+    void round(proxsdp_rounding& q) {
+        using namespace proxsdp;
+        Solver& s = *S;
+        const BlockInfo& B = s.P.blocks[q.cone];
+        PX_HIP(hipSetDevice(opt0.device_id));
+        s.restore_cert_data();                              // (a certificate search of the last solve zeroed c or [b; h])
+        device_round(s.stream, s.xd.c.p + B.off, B.n, q.cone, q);
     }
 
     void info(proxsdp_model_info& out) const {

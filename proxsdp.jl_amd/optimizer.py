@@ -161,6 +161,17 @@ class Optimizer:
             raise ValueError("inactive_rows() needs optimize(..., keep_model=True) first")
         return self.model.inactive_rows(self.sol if result is None else result, **kw)
 
+    def round(self, result=None, **kw):
+        """After optimize(..., keep_model=True, factors=...): a +-1 vector from the factors of `result` (default: the last
+        solution) and the kept model's current objective -- binding.Model.round.  Its .objective is
+        problem.user_objective(value) when the cone holds every variable of the model, None otherwise."""
+        if getattr(self, "model", None) is None:
+            raise ValueError("round() needs optimize(..., keep_model=True) first")
+        out = self.model.round(self.sol if result is None else result, **kw)
+        if len(self.problem.psd[kw.get("cone", 0)]) == self.problem.n:
+            out.objective = self.problem.user_objective(out.value)
+        return out
+
     def _follow_rows(self, ch, add_rows):
         """self.problem with the rows of the kept model: G' = [kept rows; new rows], h' likewise (host copies)"""
         import dataclasses
