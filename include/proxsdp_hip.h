@@ -84,7 +84,9 @@ extern "C" {
  * later: proxsdp_hip_model_round (randomised hyperplane rounding of a PSD cone's factors to +-1 vectors and a one-flip local
  * search against the handle's current objective, on the device) with its host restatement proxsdp_host_round and the
  * direction generator proxsdp_host_round_directions, with the new struct proxsdp_rounding: functions and one new struct, no
- * existing struct changed: the version stays */
+ * existing struct changed: the version stays;
+ * later: the test entry proxsdp_hip_lanczos_cycles (every cycle of a thick-restart Lanczos run, as the driver leaves it) with
+ * the new struct proxsdp_lanczos_cycles: one function and one new struct, no existing struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -1361,6 +1363,50 @@ typedef struct {
     double* respart;                             /* 2 x wgs */
 } proxsdp_tail_copy;
 int proxsdp_hip_tail_copy(proxsdp_tail_copy* t);
+
+/* Every cycle of ONE thick-restart Lanczos run on a packed block, as the production driver Solver::lanczos leaves it: the
+ * entry installs the driver's per-cycle observer (called between the read-back of a cycle's record and the restart logic, the
+ * basis final and not yet rotated), sets the run's maxiter to max_cycles and calls Solver::lanczos -- the engine lz_plan
+ * chooses, the split cycle with the host or device merge, the speculated first mat-vec and the one-workgroup kernel's deferred
+ * rotation run as in a solve.  opt (NULL: the defaults) passes through: eigsolver_min_lanczos, lanczos_cycle_kernel,
+ * lanczos_wide_krylov, host_eig_merge, device_eig_merge, eigsolver, krylovkit_tol, ...; krylovkit_max_iter / arpack_max_iter
+ * are overwritten with max_cycles.  resid: the start vector (n entries, normalised by the library), NULL: the library's own.
+ * krylovdim = max(2 nev + 1, eigsolver_min_lanczos); the caller states cols = krylovdim + 1 and ldv = 64 ceil(n / 64) and
+ * allocates, per cycle c < max_cycles: info + PROXSDP_LZ_INFO c, V + c cols ldv, alphas / betas / D / f + c cols.  All are prefilled with the
+ * sentinel (info: -1).  For each cycle the driver ran (`cycles` of them):
+ *   info[0] kfirst (the kept columns; 0 in the first cycle), info[1] Kend (krylovdim, or kstop when the stop flag is set),
+ *   info[2] the stop flag, info[3] the engine (PROXSDP_LZ_ENGINE_*), info[4] 1 when the cycle was a split cycle,
+ *   info[5] 1 when its first mat-vec had been speculated by the cycle before, info[6] 1 when the preceding restart's merge ran
+ *   on the device, info[7] 1 when the first phase of the split eigensolve succeeded for this cycle, info[8] 1 when the kept
+ *   columns were compared with what the cycle was handed -- after a restart on the step or wide engine the entry repeats the
+ *   restart rotation (Solver::rotate_launch on the previous basis and the coefficients still on the device) into a buffer of
+ *   its own -- and info[9] the number of entries of the columns 0 .. kfirst, padding rows included, whose bits differ from it
+ *   (the one-workgroup kernel rotates in its own prologue: info[8] = 0 there), info[10 .. 11] reserved;
+ *   V: ALL cols columns of the basis buffer at stride ldv, padding rows included -- columns 0 .. Kend are the cycle's basis
+ *   (column Kend is not written by a cycle that stopped), the columns behind hold what earlier cycles or the zeroed
+ *   workspace left there; alphas[kfirst .. Kend), betas[kfirst .. Kend) from the cycle's record;
+ *   D[0 .. kfirst), f[0 .. kfirst): the arrow part the cycle ran with (Ritz values and couplings of the kept columns).
+ * Refused with PROXSDP_E_INVALID before a device is touched: nev < 1 or > n, max_cycles < 1, cols / ldv not as stated above,
+ * krylovdim > 255 without opt->lanczos_wide_krylov = 1 or > 511 with it (beyond the workspace), krylovkit_eager (another driver). */
+#define PROXSDP_LZ_ENGINE_STEP   0
+#define PROXSDP_LZ_ENGINE_BLOCK1 1
+#define PROXSDP_LZ_ENGINE_WIDE   2
+#define PROXSDP_LZ_INFO          12
+typedef struct {
+    int64_t struct_size;
+    /* in */
+    int32_t n, nev, max_cycles, cols, ldv, reserved;
+    const double* packed;                        /* n (n + 1) / 2 */
+    const proxsdp_options* opt;
+    const double* resid;                         /* n, or NULL */
+    double sentinel;
+    /* out */
+    int32_t* info;                               /* max_cycles x PROXSDP_LZ_INFO */
+    double* V;                                   /* max_cycles x cols x ldv */
+    double* alphas; double* betas; double* D; double* f;   /* max_cycles x cols each */
+    int32_t npad, krylovdim, cycles, reserved2;
+} proxsdp_lanczos_cycles;
+int proxsdp_hip_lanczos_cycles(proxsdp_lanczos_cycles* t);
 
 /* The "Init" section (pdhg.jl:54-142) of a solve with a dense A (prob->M_dense), nothing more: E (p + m) and D (n), the
  * equilibration diagonals -- ones when equilibration is off or switched itself off, *equilibrated says which --, frob =

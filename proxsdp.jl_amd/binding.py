@@ -356,6 +356,7 @@ def lib():
     L.proxsdp_hip_reconstruct_fused.argtypes = [C.POINTER(ReconstructFusedIO)]
     L.proxsdp_hip_rotate.argtypes = [C.POINTER(RotationIO)]
     L.proxsdp_hip_tail_copy.argtypes = [C.POINTER(TailCopyIO)]
+    L.proxsdp_hip_lanczos_cycles.argtypes = [C.POINTER(LanczosCyclesIO)]
     L.proxsdp_hip_solve_sharded.argtypes = [C.POINTER(Problem), C.POINTER(Options), i32, C.POINTER(i32), C.POINTER(i32),
                                             C.POINTER(i32), C.POINTER(i32), C.POINTER(Result), C.POINTER(Stats)]
     L.proxsdp_host_split_shard.argtypes = [C.POINTER(Problem), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32,
@@ -2003,6 +2004,52 @@ def tail_copy(xin, start, mask, wgs, sentinel=SYM_SENTINEL):
     t.xin, t.mask, t.mask_words, t.xout, t.respart = _p(xi), _p(mk, pu32), len(mk), _p(xout), _p(resp)
     _check(lib().proxsdp_hip_tail_copy(C.byref(t)))
     return xout, resp.reshape(2, -1).copy()
+
+
+LZ_ENGINES = {0: "step", 1: "block1", 2: "wide"}                          # PROXSDP_LZ_ENGINE_*
+LZ_INFO = 12                                                              # PROXSDP_LZ_INFO
+pi32 = C.POINTER(i32)
+
+
+class LanczosCyclesIO(C.Structure):
+    """proxsdp_lanczos_cycles (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64),
+                ("n", i32), ("nev", i32), ("max_cycles", i32), ("cols", i32), ("ldv", i32), ("reserved", i32),
+                ("packed", pf64), ("opt", C.POINTER(Options)), ("resid", pf64), ("sentinel", f64),
+                ("info", pi32), ("V", pf64), ("alphas", pf64), ("betas", pf64), ("D", pf64), ("f", pf64),
+                ("npad", i32), ("krylovdim", i32), ("cycles", i32), ("reserved2", i32)]
+
+
+def lanczos_cycles(packed, n, nev, max_cycles, options=None, resid=None, sentinel=SYM_SENTINEL):
+    """proxsdp_hip_lanczos_cycles: every cycle of one run of Solver::lanczos, ended by the driver after max_cycles.  Returns a
+    dict: npad, krylovdim, and `cycles`, one dict per cycle the driver ran: kfirst, K (Kend), stop, engine ("step" / "block1" /
+    "wide"), split, speculated, merge_on_device, split_ready, kept_compared / kept_differ (the kept columns against a repeat of
+    the restart rotation: entries whose bits differ), V (npad, krylovdim + 1: the whole basis buffer), alphas, betas,
+    D, f (krylovdim + 1 each; what the cycle did not write holds `sentinel`)."""
+    x = _f(packed)
+    assert len(x) == n * (n + 1) // 2
+    o = options if options is not None else default_options()
+    kd = max(2 * int(nev) + 1, int(get_option(o, "eigsolver_min_lanczos")))
+    cols, npad, mc = kd + 1, 64 * ((n + 63) // 64), max(int(max_cycles), 1)
+    t = LanczosCyclesIO()
+    t.struct_size = C.sizeof(LanczosCyclesIO)
+    t.n, t.nev, t.max_cycles, t.cols, t.ldv = int(n), int(nev), int(max_cycles), cols, npad
+    t.packed, t.opt, t.sentinel = _p(x), C.pointer(o), float(sentinel)
+    r = _f(resid) if resid is not None else None
+    if r is not None:
+        assert len(r) == n
+        t.resid = _p(r)
+    info = np.zeros((mc, LZ_INFO), dtype=np.int32)
+    V = np.zeros((mc, cols, npad))
+    al, be, D, f = (np.zeros((mc, cols)) for _ in range(4))
+    t.info, t.V, t.alphas, t.betas, t.D, t.f = _p(info, pi32), _p(V), _p(al), _p(be), _p(D), _p(f)
+    _check(lib().proxsdp_hip_lanczos_cycles(C.byref(t)))
+    assert t.npad == npad and t.krylovdim == kd
+    cyc = [dict(kfirst=int(info[c, 0]), K=int(info[c, 1]), stop=int(info[c, 2]), engine=LZ_ENGINES[int(info[c, 3])],
+                split=bool(info[c, 4]), speculated=bool(info[c, 5]), merge_on_device=bool(info[c, 6]),
+                split_ready=bool(info[c, 7]), kept_compared=bool(info[c, 8]), kept_differ=int(info[c, 9]), V=V[c].T, alphas=al[c], betas=be[c], D=D[c], f=f[c])
+           for c in range(t.cycles)]
+    return dict(npad=npad, krylovdim=kd, cycles=cyc, untouched=dict(info=info[t.cycles:], V=V[t.cycles:], alphas=al[t.cycles:]))
 
 
 def dense_scaling(prob, options=None):

@@ -1173,6 +1173,40 @@ int proxsdp_hip_tail_copy(proxsdp_tail_copy* t) {
     });
 }
 
+int proxsdp_hip_lanczos_cycles(proxsdp_lanczos_cycles* t) {
+    return guarded([&]() -> int {
+        if (!t) throw std::invalid_argument("NULL argument");
+        if (t->struct_size != (int64_t)sizeof(proxsdp_lanczos_cycles)) throw std::invalid_argument("lanczos cycles: struct_size mismatch");
+        if (t->n < 1 || t->n > 46340) throw std::invalid_argument("lanczos cycles: n out of range");
+        if (t->nev < 1 || t->nev > t->n) throw std::invalid_argument("lanczos cycles: nev must be 1 .. n");
+        if (t->max_cycles < 1) throw std::invalid_argument("lanczos cycles: max_cycles < 1");
+        if (!t->packed || !t->info || !t->V || !t->alphas || !t->betas || !t->D || !t->f) throw std::invalid_argument("lanczos cycles: NULL buffer");
+        proxsdp_options o = checked_options(t->opt);
+        if (o.lanczos_wide_krylov != 0 && o.lanczos_wide_krylov != 1) throw std::invalid_argument("lanczos_wide_krylov must be 0 or 1");
+        if (o.krylovkit_eager && o.eigsolver != 1) throw std::invalid_argument("lanczos cycles: krylovkit_eager runs another driver");
+        const int kd = std::max(2 * t->nev + 1, (int)o.eigsolver_min_lanczos);
+        if (kd > proxsdp::dev::LZ_KMAX && o.lanczos_wide_krylov != 1)
+            throw std::invalid_argument("lanczos cycles: a Krylov dimension > 255 needs the wide workspace (lanczos_wide_krylov = 1)");
+        if (kd > proxsdp::dev::LZW_MAXK - 1) throw std::invalid_argument("lanczos cycles: Krylov dimension beyond the workspace");
+        if (t->cols != kd + 1 || t->ldv != proxsdp::ceil_div(t->n, proxsdp::dev::TILE) * proxsdp::dev::TILE)
+            throw std::invalid_argument("lanczos cycles: cols must be krylovdim + 1, ldv 64 ceil(n / 64)");
+        o.krylovkit_max_iter = t->max_cycles; o.arpack_max_iter = t->max_cycles;   // the driver ends the run itself
+        // the caller's arrays hold the sentinel wherever the run writes nothing
+        const size_t nc = (size_t)t->max_cycles * t->cols;
+        std::fill(t->info, t->info + (size_t)t->max_cycles * PROXSDP_LZ_INFO, -1);
+        std::fill(t->V, t->V + nc * t->ldv, t->sentinel);
+        for (double* a : {t->alphas, t->betas, t->D, t->f}) std::fill(a, a + nc, t->sentinel);
+        t->npad = t->ldv; t->krylovdim = kd; t->cycles = 0;
+        Engine E(&o, t->n, t->nev);
+        E.set_resid(t->resid);
+        const int64_t N = (int64_t)t->n * (t->n + 1) / 2;
+        proxsdp::DevBuf<double> x(N);
+        x.upload(t->packed, N, E.S.stream);
+        E.S.test_lanczos_cycles(*t, x.p);
+        return 0;
+    });
+}
+
 int proxsdp_hip_sign_unpack(const double* packed, int64_t n, double sentinel, double* A, double* sc) {
     return guarded([&]() -> int {
         if (!packed || !A || !sc || n < 1 || n > 4096) throw std::invalid_argument("invalid argument");

@@ -366,7 +366,7 @@ inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     R.T.assign((size_t)R.ld * R.ld, 0.0); R.D.assign(R.ld, 0.0); R.f.assign(R.ld, 0.0);
     R.al.assign(R.ld, 0.0); R.be.assign(R.ld, 0.0);
     R.howmany = nev; R.numiter = 1; R.converged = 0; R.K = 0; R.kfirst = 0; R.pos_count = -1;
-    R.pos_fail = false; R.presymv = false; R.betaK = 0.0;
+    R.pos_fail = false; R.presymv = R.first_speculated = false; R.betaK = 0.0;
     R.split_ready = false; R.merge_active = false;
     R.split_cycle = R.dev_staged = R.merge_on_device = false;
     return true;
@@ -609,7 +609,7 @@ inline void Solver::lz_restart(EigWork& W, LzRun& R, int keep, bool speculated) 
         R.T[(size_t)keep * ld + j] = f[j];
     }
     R.kfirst = keep;
-    R.presymv = speculated;
+    R.presymv = R.first_speculated = speculated;
     ++R.numiter;
     W.lst.lanczos_restarts++;
 }
@@ -780,6 +780,7 @@ inline void Solver::lanczos(EigWork& W, const double* xp, int nev, bool positive
         lz_enqueue_cycle(W, R, xp);
         const bool speculated = lz_speculate(W, R, xp);
         lz_read_back(W, R);
+        if (lz_observer) (*lz_observer)(W, R);
         const double t1 = debug ? now_s() : 0.0;
         const bool go_on = lz_after_cycle(W, R, speculated);
         if (debug) dbg_lz.after_cycle += now_s() - t1;

@@ -276,6 +276,7 @@ struct LzRun {
     std::vector<double> T, Tw, D, U, f, al, be, Qa, da, ea;
     int howmany = 0, numiter = 1, converged = 0, K = 0, kfirst = 0, pos_count = -1, m_arrow = 0;
     bool pos_fail = false, presymv = false;
+    bool first_speculated = false;    // the first mat-vec of the cycle in progress was speculated by the cycle before (lz_restart; read by the observer only)
     double betaK = 0.0;
     int k1 = 0;                       // split + rank-one merge (EigWork::split): the cycle in progress is split at step k1 ...
     bool split_cycle = false, split_ready = false;   // ... if at all, and split.first() succeeded for it
@@ -670,6 +671,9 @@ public:
     bool lz_speculate(EigWork& W, LzRun& R, const double* xp);
     void lz_read_back(EigWork& W, LzRun& R);
     void lanczos(EigWork& W, const double* xp, int nev, bool positive_part = false);
+    // test seam of lanczos() (test_hooks.hip.hpp test_lanczos_cycles): called once per cycle between lz_read_back and
+    // lz_after_cycle -- the basis final, the record's pinned mirror valid, V and Z not yet swapped.  Null in every solve.
+    const std::function<void(EigWork&, LzRun&)>* lz_observer = nullptr;
     void lanczos_eager(EigWork& W, const double* xp, int nev);
     bool lanczos_certificate(EigWork& W, const double* xp, int npos, int msteps, double& theta_max, double& scale);
     void lanczos_batch(const std::vector<int>& blocks, const double* xbase, const std::vector<int>& nevs, int ctx_slot = 0);
@@ -699,6 +703,7 @@ public:
     void test_reconstruct_fused(proxsdp_reconstruct_fused& t);
     void test_rotate(proxsdp_rotation& t);
     void test_tail_copy(proxsdp_tail_copy& t);
+    void test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double* xp);
     void launch_tail_copy(const double* xin, double* xout);
     void test_sign_unpack(const double* packed, double sentinel, double* A, double* sc);
 

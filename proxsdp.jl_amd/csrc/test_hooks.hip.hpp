@@ -2,6 +2,7 @@
 // solver's own launch code on it and copies the outputs back.
 #pragma once
 #include "solver.hip.hpp"
+#include "lanczos.hip.hpp"
 
 namespace proxsdp {
 
@@ -285,6 +286,64 @@ inline void Solver::test_rotate(proxsdp_rotation& t) {
     t.npad = npad;
     t.form = W.rot_form;
     t.launches = W.rot_launches;
+}
+
+// Every cycle of ONE run of Solver::lanczos on the packed block xp (include/proxsdp_hip.h proxsdp_lanczos_cycles): the driver's
+// observer copies out what the cycle left -- the whole basis buffer, the record's coefficients, the arrow part in R.T and what
+// the plan and the restart before it decided -- and the driver itself ends the run after max_cycles (the options' maxiter).
+// eig[0] was sized for the run's Krylov dimension; the capi entry prefilled the caller's arrays.
+inline void Solver::test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double* xp) {
+    EigWork& W0 = eig[0];
+    const int cols = t.cols, npad = W0.npad;
+    if (npad != t.ldv || cols > W0.cap || krylov_dim(t.nev) + 1 != cols) throw std::logic_error("lanczos cycles: the workspace is not the one asked for");
+    int c = 0;
+    DevBuf<double> again;
+    std::vector<double> again_h;
+    const std::function<void(EigWork&, LzRun&)> observe = [&](EigWork& W, LzRun& R) {
+        if (c >= t.max_cycles) throw std::logic_error("lanczos cycles: the driver ran past max_cycles");
+        if (R.krylovdim + 1 != cols) throw std::logic_error("lanczos cycles: the run's Krylov dimension is not the one asked for");
+        const LzRecord rec(R.plan.rec.host, R.plan.rec.ld);
+        const int kfirst = R.kfirst, Kend = rec.ctl.stop ? rec.ctl.kstop : R.krylovdim;
+        if (Kend < kfirst || Kend > R.krylovdim) throw std::logic_error("lanczos cycles: kstop outside the cycle");
+        int32_t* info = t.info + (size_t)PROXSDP_LZ_INFO * c;
+        info[0] = kfirst; info[1] = Kend; info[2] = rec.ctl.stop;
+        info[3] = R.plan.engine == LzEngine::wide ? PROXSDP_LZ_ENGINE_WIDE
+                : R.plan.engine == LzEngine::block1 ? PROXSDP_LZ_ENGINE_BLOCK1 : PROXSDP_LZ_ENGINE_STEP;
+        info[4] = R.split_cycle ? 1 : 0; info[5] = R.first_speculated ? 1 : 0; info[6] = R.merge_on_device ? 1 : 0;
+        info[7] = R.split_ready ? 1 : 0;
+        const size_t row = (size_t)c * cols;
+        for (int k = kfirst; k < Kend; ++k) { t.alphas[row + k] = rec.al[k]; t.betas[row + k] = rec.be[k]; }
+        for (int j = 0; j < kfirst; ++j) { t.D[row + j] = R.T[(size_t)j * R.ld + j]; t.f[row + j] = R.T[(size_t)j * R.ld + kfirst]; }
+        PX_HIP(hipMemcpyAsync(t.V + row * npad, W.V.p, (size_t)cols * npad * sizeof(double), hipMemcpyDeviceToHost, stream));
+        PX_HIP(hipStreamSynchronize(stream));
+        info[8] = 0; info[9] = 0;
+        if (kfirst > 0 && R.plan.engine != LzEngine::block1) {
+            // What the cycle was handed: the restart rotation once more, through rotate_launch, from what it read -- the basis
+            // of the cycle before (in W.Z: lz_restart swapped the buffers) and its coefficients, still on the device
+            // (DeviceMerge::Uall after a device merge, else W.U behind rotate()'s upload) -- into a buffer of its own.  The
+            // cycle's columns 0 .. kfirst must still be these bits.  (k_lz_block1 rotates in its own prologue: not repeated.)
+            filled(again, (size_t)cols * npad, t.sentinel, stream);          // (the whole of a basis buffer's columns, as W.Z has them)
+            const double* Ud = R.merge_on_device ? W.dmerge.Uall.p : W.U.p;
+            const int form = W.rot_form, launches = W.rot_launches;
+            std::swap(W.V.p, W.Z.p);
+            rotate_launch(W, R.K, Ud, kfirst, again.p, R.K, kfirst);
+            std::swap(W.V.p, W.Z.p);
+            W.rot_form = form; W.rot_launches = launches;
+            again_h.resize((size_t)(kfirst + 1) * npad);
+            again.download(again_h.data(), again_h.size(), stream);
+            PX_HIP(hipStreamSynchronize(stream));
+            const double* snap = t.V + row * npad;
+            int differ = 0;
+            for (size_t q = 0; q < again_h.size(); ++q) differ += std::memcmp(&again_h[q], &snap[q], sizeof(double)) != 0;
+            info[8] = 1; info[9] = differ;
+        }
+        t.cycles = ++c;
+    };
+    lz_observer = &observe;
+    try { lanczos(W0, xp, t.nev); } catch (...) { lz_observer = nullptr; throw; }
+    lz_observer = nullptr;
+    PX_HIP(hipStreamSynchronize(stream));
+    PX_HIP(hipGetLastError());
 }
 
 // The support path's copy of the non-PSD tail x[start .. N) (include/proxsdp_hip.h proxsdp_tail_copy) through launch_tail_copy,
