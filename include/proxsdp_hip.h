@@ -86,7 +86,10 @@ extern "C" {
  * direction generator proxsdp_host_round_directions, with the new struct proxsdp_rounding: functions and one new struct, no
  * existing struct changed: the version stays;
  * later: the test entry proxsdp_hip_lanczos_cycles (every cycle of a thick-restart Lanczos run, as the driver leaves it) with
- * the new struct proxsdp_lanczos_cycles: one function and one new struct, no existing struct changed: the version stays */
+ * the new struct proxsdp_lanczos_cycles: one function and one new struct, no existing struct changed: the version stays;
+ * later: proxsdp_hip_model_cliques (pentagonal and heptagonal odd-clique inequalities of a PSD cone of a model handle, grown
+ * from triangles or pentagons on the device) with its host restatement proxsdp_host_clique_cuts and the new struct
+ * proxsdp_clique_cuts: two functions and one new struct, no existing struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -987,6 +990,88 @@ typedef struct proxsdp_inactive_rows {
     int64_t n_rows;           /* out */
 } proxsdp_inactive_rows;
 int  proxsdp_hip_model_inactive_rows(proxsdp_model* mdl, proxsdp_inactive_rows* q);
+/* ------------------------------------------- separation on a model handle: pentagonal and heptagonal cuts
+ * Where the triangle rows stop biting, the odd-clique inequalities of the next sizes go on: for a +-1 vector x and signs
+ * sigma on an odd set Q of k nodes the sum of sigma_a x_a is odd, its square at least 1, so
+ *     sum over a < b in Q of  -sigma_a sigma_b X_ab  <=  (k - 1) / 2            (k = 3: the triangle rows above).
+ * There are 16 C(s, 5) pentagonal rows: they are not enumerated.  The call GROWS given bases -- triangles (base_size q = 3)
+ * into pentagons, pentagons (q = 5) into heptagons -- by the best pair of further nodes and their signs.  The reference has
+ * no counterpart.
+ * IN.   cone, primal, on_device: as in proxsdp_triangle_cuts (X is the same matrix).  n_base bases (1 .. 65536):
+ *       base_nodes (n_base x q int64, 0-based nodes of the cone, strictly ascending inside a base) and base_sign (n_base x q
+ *       int8, each +-1, the first of every base +1), both HOST arrays whatever on_device says.  rhs: finite ((q + 1) / 2, that
+ *       is 2 and 3, for unit-diagonal models).  min_violation: finite, >= 0.
+ * VALUE.  For a base with nodes a_0 < ... < a_{q-1} and signs sigma, two nodes l < m outside the base and tau_l, tau_m in
+ *       {+1, -1}, in fp64, left to right exactly as written, no contraction (a product with +-1 is exact):
+ *           B   = the sum over the pairs (u < w) of the base, in lexicographic order, of (-sigma_u sigma_w) * X[a_u, a_w],
+ *                 starting from the first term
+ *           t_l = ((sigma_0 * X[a_0, l] + sigma_1 * X[a_1, l]) + ...) + sigma_{q-1} * X[a_{q-1}, l]
+ *           v   = (((B - tau_l * t_l) - tau_m * t_m) - (tau_l tau_m) * X[l, m]) - rhs
+ * BEST.   The extension of a base is the (l, m, code) with the greatest v, equal v by the smallest (l, m, code); code = 0
+ *       (+,+), 1 (+,-), 2 (-,+), 3 (-,-) for (tau_l, tau_m).  The base yields a row when that v > min_violation.
+ * ROW.    The k = q + 2 nodes sorted ascending, the signs multiplied by the sign of the smallest node (one normal form per
+ *       inequality).  Bases that yield the same (nodes, signs) are merged into the member with the greatest v, then the lowest
+ *       base number.  Rows are ordered by v descending, then by that base number ascending.  At most n_base rows come back.
+ * OUT (HOST arrays, caller-allocated for n_base rows; entries past n_rows are not written).  Per row: nodes (k), signs (k),
+ *       violation, from_base, add_col / add_val (k (k - 1) / 2 = 10 or 21 entries in the lexicographic order of the pairs
+ *       (u < w): the variable of X[n_u, n_w] in the caller's numbering and the index base of create, and -sigma'_u sigma'_w),
+ *       add_h (= rhs): with add_ptr = 0, 10, 20, ... (or steps of 21) a proxsdp_model_rows change as they stand.  Per call:
+ *       n_rows, violated_bases (bases that yielded a row, before merging), scanned = n_base 4 C(s - q, 2), bytes_allocated,
+ *       seconds, sweep_seconds (the sweep kernels alone, between device events, summed over the batches).
+ * The result is a pure function of the inputs: the same rows, order and bits on every run, whatever grid and batch are.  The
+ * handle's data is not touched.  Scratch (the dense X of 8 s^2 bytes, 8 s min(n_base, batch) bytes of t rounded up to whole
+ * waves of 64 bases, the bases, 16 bytes per (workgroup column, base) of partial results) is allocated in the call, released
+ * before it returns and reported in bytes_allocated only.
+ * How: k_tri_gather builds X; per batch of bases k_clique_rows writes t[l][base] (NaN at the base's own nodes: every later
+ * comparison fails there) and B; k_clique_sweep gives a wave 64 bases, one per lane, and tiles of 64 x 64 pairs (l, m) of the
+ * strict upper triangle -- X[l, m] is wave-uniform and read from LDS as a broadcast, t_m from LDS laid out [m][lane], t_l is
+ * hoisted per l, the four codes are evaluated in order and each lane keeps its best (v, l, m, code) in registers; a workgroup
+ * writes one partial best per (its range of tiles, base) and k_clique_best reduces them under the same total order, whose
+ * maximum does not depend on how the tiles were split.  Merging, normal form, sort and the rows are the host's.
+ * Test knobs (0 = the library's choice; the result does not depend on either): grid = workgroup columns of the sweep (each
+ * owns a range of tiles), batch = bases per launch (rounded up to a multiple of 64; default 1024).
+ * PROXSDP_E_INVALID, decided on the host before any device call, the message naming the field: a NULL struct, handle or
+ * array; a wrong struct_size; on_device other than 0 or 1; base_size not 3 or 5; n_base outside 1 .. 65536; a cone outside
+ * the model; a cone of side < q + 2; a base node out of range or not strictly ascending; a sign that is not +-1 or a first
+ * sign of -1; a non-finite rhs; a negative or non-finite min_violation; a negative knob.  A non-finite entry of the cone's
+ * part of primal: a host primal is checked by a host loop, a device primal by the reduction the triangle entry uses; the
+ * message names the cone. */
+typedef struct proxsdp_clique_cuts {
+    int64_t struct_size;      /* = sizeof(proxsdp_clique_cuts) */
+    int32_t on_device;        /* where primal lives: 0 host, 1 DEVICE pointer on the model's device (proxsdp_host_clique_cuts
+                               * ignores it) */
+    int32_t cone;             /* PSD cone of the model, 0-based in cone order (proxsdp_host_clique_cuts ignores it) */
+    int32_t base_size;        /* q: 3 or 5 */
+    int32_t grid, batch;      /* test knobs, 0 = default */
+    int32_t reserved;
+    int64_t n_base;           /* 1 .. 65536 */
+    double  rhs;
+    double  min_violation;    /* >= 0 */
+    const double*  primal;    /* n doubles (proxsdp_host_clique_cuts ignores it: it is given X) */
+    const int64_t* base_nodes;/* HOST, n_base x q */
+    const int8_t*  base_sign; /* HOST, n_base x q */
+    /* out: caller-allocated HOST arrays for n_base rows; k = q + 2 */
+    int64_t* nodes;           /* k per row, ascending */
+    int8_t*  signs;           /* k per row, the first +1 */
+    double*  violation;
+    int64_t* from_base;
+    int64_t* add_col;         /* k (k - 1) / 2 per row */
+    double*  add_val;         /* k (k - 1) / 2 per row */
+    double*  add_h;
+    int64_t n_rows;
+    int64_t violated_bases;   /* bases whose best extension has v > min_violation, before merging */
+    int64_t scanned;          /* n_base 4 C(s - q, 2) */
+    int64_t bytes_allocated;  /* device bytes this call allocated (and released); 0 on the host */
+    double  seconds;          /* wall time of the call */
+    double  sweep_seconds;    /* the sweep kernels alone, between device events (0 on the host) */
+} proxsdp_clique_cuts;
+int  proxsdp_hip_model_cliques(proxsdp_model* mdl, proxsdp_clique_cuts* q);
+/* The same contract with no device and no handle: a serial loop over the bases, the pairs in ascending order and the four
+ * codes, keeping the first maximum.  X, cone_idx, index_base: as in proxsdp_host_triangle_cuts (only i < j of X is read).
+ * PROXSDP_E_INVALID: as above where it applies; NULL X; side < q + 2 or > 46340; index_base other than 0 or 1; a non-finite
+ * X_ij, i < j. */
+int  proxsdp_host_clique_cuts(const double* X, int64_t side, const int64_t* cone_idx, int32_t index_base,
+                              proxsdp_clique_cuts* q);
 /* ------------------------------------------- rounding on a model handle: a +-1 vector from a PSD cone's factors
  * The verbs above tighten the relaxation's bound; this one produces a feasible point of a +-1 model (Max-Cut and its kin):
  * randomised hyperplane rounding (Goemans-Williamson) of the factors a solve hands out (proxsdp_psd_factors) to `trials`

@@ -243,6 +243,17 @@ class TriangleCutsIO(C.Structure):
                 ("bytes_allocated", i64), ("seconds", f64), ("sweep_seconds", f64)]
 
 
+class CliqueCutsIO(C.Structure):
+    """proxsdp_clique_cuts (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("on_device", i32), ("cone", i32), ("base_size", i32), ("grid", i32), ("batch", i32),
+                ("reserved", i32), ("n_base", i64), ("rhs", f64), ("min_violation", f64),
+                ("primal", pf64), ("base_nodes", pi64), ("base_sign", C.POINTER(C.c_int8)),
+                ("nodes", pi64), ("signs", C.POINTER(C.c_int8)), ("violation", pf64), ("from_base", pi64),
+                ("add_col", pi64), ("add_val", pf64), ("add_h", pf64),
+                ("n_rows", i64), ("violated_bases", i64), ("scanned", i64), ("bytes_allocated", i64),
+                ("seconds", f64), ("sweep_seconds", f64)]
+
+
 class InactiveRowsIO(C.Structure):
     """proxsdp_inactive_rows (include/proxsdp_hip.h)"""
     _fields_ = [("struct_size", i64), ("on_device", i32), ("reserved", i32), ("dual_in", pf64), ("slack_in", pf64),
@@ -332,6 +343,8 @@ def lib():
     L.proxsdp_hip_model_triangles.argtypes = [C.c_void_p, C.POINTER(TriangleCutsIO)]
     L.proxsdp_host_triangle_cuts.argtypes = [pf64, i64, pi64, i32, C.POINTER(TriangleCutsIO)]
     L.proxsdp_hip_model_inactive_rows.argtypes = [C.c_void_p, C.POINTER(InactiveRowsIO)]
+    L.proxsdp_hip_model_cliques.argtypes = [C.c_void_p, C.POINTER(CliqueCutsIO)]
+    L.proxsdp_host_clique_cuts.argtypes = [pf64, i64, pi64, i32, C.POINTER(CliqueCutsIO)]
     L.proxsdp_hip_model_round.argtypes = [C.c_void_p, C.POINTER(RoundingIO)]
     L.proxsdp_host_round.argtypes = [i64, pi64, pi64, pf64, pf64, C.POINTER(RoundingIO)]
     L.proxsdp_host_round_directions.argtypes = [i64, i32, i32, pf64]
@@ -1121,6 +1134,106 @@ def host_triangle_cuts(X, count=1000, min_violation=1e-3, rhs=1.0, cone_idx=None
     return TriangleCuts(T, arr, index_base)
 
 
+TRIANGLE_PATTERN_SIGNS = np.array([[1, 1, 1], [1, 1, -1], [1, -1, 1], [1, -1, -1]], dtype=np.int8)
+
+
+class CliqueCuts:
+    """What a pentagonal / heptagonal separation returned (proxsdp_clique_cuts): nodes (rows x k, ascending, k = base size + 2),
+    signs (rows x k int8, the first +1), violations (descending; equal ones by from_base), from_base (the base a row grew
+    from; of merged bases the one with the greatest violation, then the lowest number), violated_bases (before merging),
+    scanned, seconds, sweep_seconds, bytes_allocated, and add = ((rowptr, cols, values), h) with 0-based cols: what
+    Model.change_rows(add=...) and Optimizer.reoptimize(add_rows=...) take.  raw: add_col / add_val / add_h as the library
+    wrote them (add_col in the index base of the model); arrays: every output array at its full length of n_base rows, and the bases as they were passed.  A
+    CliqueCuts of size 5 is itself a set of bases for the next call."""
+
+    def __init__(self, Q, arr, index_base):
+        n, k = int(Q.n_rows), int(Q.base_size) + 2
+        npair = k * (k - 1) // 2
+        self.arrays = arr
+        self.size = k
+        self.nodes = arr["nodes"].reshape(-1, k)[:n].copy()
+        self.signs = arr["signs"].reshape(-1, k)[:n].copy()
+        self.violations = arr["violation"][:n].copy()
+        self.from_base = arr["from_base"][:n].copy()
+        self.violated_bases, self.scanned = int(Q.violated_bases), int(Q.scanned)
+        self.seconds, self.sweep_seconds = float(Q.seconds), float(Q.sweep_seconds)
+        self.bytes_allocated = int(Q.bytes_allocated)
+        self.raw = dict(add_col=arr["add_col"][:npair * n].copy(), add_val=arr["add_val"][:npair * n].copy(),
+                        add_h=arr["add_h"][:n].copy())
+        self.add = ((npair * np.arange(n + 1, dtype=np.int64), self.raw["add_col"] - index_base, self.raw["add_val"]),
+                    self.raw["add_h"])
+
+    def __len__(self):
+        return len(self.violations)
+
+
+def _clique_bases(bases):
+    """(nodes, signs) as contiguous n_base x q int64 / int8 arrays from a TriangleCuts (patterns 0: (+,+,+), 1: (+,+,-),
+    2: (+,-,+), 3: (+,-,-): the triangle rows' own signs in the normal form of a base), a CliqueCuts or a pair"""
+    if isinstance(bases, TriangleCuts):
+        nodes, signs = bases.triples, TRIANGLE_PATTERN_SIGNS[bases.patterns]
+    elif isinstance(bases, CliqueCuts):
+        nodes, signs = bases.nodes, bases.signs
+    else:
+        nodes, signs = bases
+    nodes = np.ascontiguousarray(nodes, dtype=np.int64)
+    signs = np.ascontiguousarray(signs, dtype=np.int8)
+    if nodes.ndim != 2 or nodes.shape != signs.shape:
+        raise ValueError("separate_cliques: bases must be n_base x q nodes and as many signs")
+    return nodes, signs
+
+
+def _clique_struct(nodes, signs, min_violation, rhs, knobs=None, sentinel=None):
+    """proxsdp_clique_cuts for those bases with output arrays for n_base rows (prefilled with `sentinel` when given), and the
+    arrays.  rhs None: (q + 1) / 2.  knobs: {grid: workgroup columns of the sweep, batch: bases per launch}"""
+    nb, q = nodes.shape
+    n, k = max(nb, 1), q + 2
+    npair = k * (k - 1) // 2
+    arr = dict(nodes=np.zeros(k * n, dtype=np.int64), signs=np.zeros(k * n, dtype=np.int8), violation=np.zeros(n),
+               from_base=np.zeros(n, dtype=np.int64), add_col=np.zeros(npair * n, dtype=np.int64),
+               add_val=np.zeros(npair * n), add_h=np.zeros(n))
+    if sentinel is not None:
+        for a in arr.values():
+            a[:] = sentinel
+    Q = CliqueCutsIO()
+    Q.struct_size = C.sizeof(CliqueCutsIO)
+    Q.base_size, Q.n_base = int(q), int(nb)
+    Q.rhs = float((q + 1) / 2 if rhs is None else rhs)
+    Q.min_violation = float(min_violation)
+    for name, v in dict(knobs or {}).items():
+        if name not in ("grid", "batch"):
+            raise ValueError(f"separate_cliques: no knob {name}")
+        setattr(Q, name, int(v))
+    # (the bases travel with the output arrays, so that they live as long as the struct points at them; no base: any
+    # non-NULL address, n_base = 0 is the library's to refuse)
+    arr["base_nodes"] = nodes if nodes.size else np.zeros(1, dtype=np.int64)
+    arr["base_sign"] = signs if signs.size else np.zeros(1, dtype=np.int8)
+    Q.base_nodes = _p(arr["base_nodes"], pi64)
+    Q.base_sign = arr["base_sign"].ctypes.data_as(C.POINTER(C.c_int8))
+    Q.nodes, Q.from_base, Q.add_col = _p(arr["nodes"], pi64), _p(arr["from_base"], pi64), _p(arr["add_col"], pi64)
+    Q.signs = arr["signs"].ctypes.data_as(C.POINTER(C.c_int8))
+    Q.violation, Q.add_val, Q.add_h = _p(arr["violation"]), _p(arr["add_val"]), _p(arr["add_h"])
+    return Q, arr
+
+
+def host_clique_cuts(X, bases, min_violation=1e-3, rhs=None, cone_idx=None, index_base=0, sentinel=None):
+    """proxsdp_host_clique_cuts: the separation of Model.separate_cliques on the host, serially (no device, no handle).  X: the
+    symmetric side x side matrix; bases: as Model.separate_cliques takes them; cone_idx: the cone's variable list as add_col
+    shall report it (None: tri_index + index_base).  Returns a CliqueCuts; its `arrays` are the output arrays at full length
+    (entries past the rows returned keep `sentinel`)."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != X.shape[1]:
+        raise ValueError("host_clique_cuts: X must be square")
+    nodes, signs = _clique_bases(bases)
+    Q, arr = _clique_struct(nodes, signs, min_violation, rhs, None, sentinel)
+    idx = None if cone_idx is None else _i(cone_idx)
+    if idx is not None and len(idx) != X.shape[0] * (X.shape[0] + 1) // 2:
+        raise ValueError("host_clique_cuts: cone_idx must list the upper triangle")
+    _check(lib().proxsdp_host_clique_cuts(_p(X if X.size else np.zeros(1)), X.shape[0], None if idx is None else _p(idx, pi64),
+                                          int(index_base), C.byref(Q)))
+    return CliqueCuts(Q, arr, index_base)
+
+
 class Rounding:
     """What a rounding returned (proxsdp_rounding): signs (int8, +-1, one per node of the cone), value (of `signs`, the
     cone's part of c'x in the units and the minimisation form of the model's c), value_rounded (the smallest value before the
@@ -1365,6 +1478,35 @@ class Model:
         _check(lib().proxsdp_hip_model_triangles(self._handle(), C.byref(T)))
         del keep
         return TriangleCuts(T, arr, getattr(self, "_index_base", 0))
+
+    def separate_cliques(self, primal, bases, cone=0, min_violation=1e-3, rhs=None, knobs=None):
+        """proxsdp_hip_model_cliques: every base grown by its most violated pair of further nodes and signs of PSD cone `cone`
+        at `primal` (as separate_triangles takes it) -- pentagonal rows from triangles, heptagonal rows from pentagons.  bases:
+        a TriangleCuts, a CliqueCuts of size 5, or (nodes, signs) as n_base x q arrays (q = 3 or 5; nodes 0-based and ascending,
+        signs +-1 with the first +1).  rhs None: (q + 1) / 2.  knobs: test knobs (_clique_struct).  Returns a CliqueCuts;
+        change_rows(add=cuts.add) appends the rows.  The model is not touched."""
+        if isinstance(primal, SolveResult):
+            primal = primal.primal
+        if primal is None:
+            raise ValueError("Model.separate_cliques: the result holds no primal (solve(primal=True))")
+        nodes, signs = _clique_bases(bases)
+        Q, arr = _clique_struct(nodes, signs, min_violation, rhs, knobs)
+        Q.cone = int(cone)
+        if _is_tensor(primal) and primal.is_cuda:
+            import torch
+            dev_id = int(self._options.device_id)
+            Q.on_device = 1
+            Q.primal = _device_ptr(primal, self.n, dev_id, "primal")
+            keep = primal
+            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
+        else:
+            keep = _f(primal.numpy() if _is_tensor(primal) else primal).ravel()
+            if len(keep) != self.n:
+                raise ValueError(f"Model.separate_cliques: primal must have {self.n} entries")
+            Q.primal = _p(keep if len(keep) else np.zeros(1))
+        _check(lib().proxsdp_hip_model_cliques(self._handle(), C.byref(Q)))
+        del keep
+        return CliqueCuts(Q, arr, getattr(self, "_index_base", 0))
 
     def inactive_rows(self, result_or_pair, dual_tol=0.0, slack_tol=1e-6):
         """proxsdp_hip_model_inactive_rows: the inequality rows r with |dual_in[r]| <= dual_tol and slack_in[r] < -slack_tol

@@ -15,6 +15,7 @@
 #include "shard_split.hpp"
 #include "model.hip.hpp"
 #include "triangle_cuts.hip.hpp"
+#include "clique_cuts.hip.hpp"
 
 namespace {
 thread_local std::string g_last_error;
@@ -451,6 +452,35 @@ int proxsdp_host_triangle_cuts(const double* X, int64_t side, const int64_t* con
         if (side < 3 || side > 46340) throw std::invalid_argument("proxsdp_host_triangle_cuts: side must be 3 .. 46340");
         if (index_base != 0 && index_base != 1) throw std::invalid_argument("index_base must be 0 or 1");
         proxsdp::host_triangle_cuts(X, side, cone_idx, index_base, *tc);
+        return 0;
+    });
+}
+
+int proxsdp_hip_model_cliques(proxsdp_model* mdl, proxsdp_clique_cuts* q) {
+    return guarded([&]() -> int {
+        proxsdp::check_clique_struct(q, true);
+        if (!mdl) throw std::invalid_argument("NULL handle");
+        const proxsdp::Prep& P = mdl->S->P;
+        if (q->cone < 0 || q->cone >= (int64_t)P.blocks.size()) throw std::invalid_argument("proxsdp_clique_cuts.cone is outside the model's PSD cones");
+        const proxsdp::BlockInfo& B = P.blocks[q->cone];
+        if (B.n < q->base_size + 2)
+            throw std::invalid_argument("proxsdp_clique_cuts: cone " + std::to_string(q->cone) + " has side < base_size + 2");
+        proxsdp::check_clique_bases(*q, B.n);
+        PX_HIP(hipSetDevice(mdl->opt0.device_id));
+        proxsdp::device_clique_cuts(mdl->S->stream, P.ord.data() + B.off, mdl->ord_d.p + B.off, B.n, mdl->index_base, q->cone, *q);
+        return 0;
+    });
+}
+
+int proxsdp_host_clique_cuts(const double* X, int64_t side, const int64_t* cone_idx, int32_t index_base, proxsdp_clique_cuts* q) {
+    return guarded([&]() -> int {
+        proxsdp::check_clique_struct(q, false);
+        if (!X) throw std::invalid_argument("proxsdp_host_clique_cuts: X is NULL");
+        if (side < q->base_size + 2 || side > proxsdp::CLQ_MAX_SIDE)
+            throw std::invalid_argument("proxsdp_host_clique_cuts: side must be base_size + 2 .. 46340");
+        if (index_base != 0 && index_base != 1) throw std::invalid_argument("index_base must be 0 or 1");
+        proxsdp::check_clique_bases(*q, side);
+        proxsdp::host_clique_cuts(X, side, cone_idx, index_base, *q);
         return 0;
     });
 }

@@ -154,6 +154,16 @@ class Optimizer:
             raise ValueError("separate_triangles() needs optimize(..., keep_model=True) first")
         return self.model.separate_triangles(self.sol if result is None else result, **kw)
 
+    def separate_cliques(self, result=None, bases=None, **kw):
+        """After optimize(..., keep_model=True): the bases (a TriangleCuts, a CliqueCuts of size 5 or (nodes, signs)) grown
+        into pentagonal / heptagonal rows at `result` (default: the last solution) -- binding.Model.separate_cliques.
+        reoptimize(add_rows=cuts.add) appends them."""
+        if getattr(self, "model", None) is None:
+            raise ValueError("separate_cliques() needs optimize(..., keep_model=True) first")
+        if bases is None:
+            raise ValueError("separate_cliques() needs bases")
+        return self.model.separate_cliques(self.sol if result is None else result, bases, **kw)
+
     def inactive_rows(self, result=None, **kw):
         """After optimize(..., keep_model=True): the inequality rows that went slack at `result` (default: the last
         solution) -- binding.Model.inactive_rows; a drop_rows list for reoptimize()."""
