@@ -89,7 +89,11 @@ extern "C" {
  * the new struct proxsdp_lanczos_cycles: one function and one new struct, no existing struct changed: the version stays;
  * later: proxsdp_hip_model_cliques (pentagonal and heptagonal odd-clique inequalities of a PSD cone of a model handle, grown
  * from triangles or pentagons on the device) with its host restatement proxsdp_host_clique_cuts and the new struct
- * proxsdp_clique_cuts: two functions and one new struct, no existing struct changed: the version stays */
+ * proxsdp_clique_cuts: two functions and one new struct, no existing struct changed: the version stays
+ * later: proxsdp_hip_model_bound (a certified lower bound of a model handle's optimum from any dual point: the proof is a
+ * completed fp64 Cholesky factorisation on the device with its backward-error bound) with its host restatement
+ * proxsdp_host_dual_bound, the test entries proxsdp_hip_cholesky / proxsdp_host_cholesky and the new struct
+ * proxsdp_dual_bound: four functions and one new struct, no existing struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -1164,6 +1168,105 @@ int  proxsdp_host_round(int64_t side, const int64_t* adj_ptr, const int64_t* adj
 /* g (r x trials doubles, row k contiguous) = the directions above.  PROXSDP_E_INVALID: NULL g, r < 1 or > 46340, trials as
  * above. */
 int  proxsdp_host_round_directions(int64_t seed, int32_t r, int32_t trials, double* g);
+/* ------------------------------------------- a certified dual bound of a model handle: a device Cholesky test
+ * objval and dual_objval of a solve are estimates: the dual point is infeasible by dual_feasibility, and the lambda_min behind
+ * that figure is a Lanczos Ritz value, which lies ABOVE the true eigenvalue -- the unsafe side.  This call returns a number
+ * that IS a lower bound of the handle's optimum, whatever the dual point handed in.  It rests on no Lanczos run, no iterative
+ * eigenvalue estimate and no tolerance of the solver: the proof is a COMPLETED floating-point Cholesky factorisation together
+ * with its backward-error bound.  The reference has no counterpart.
+ * THE BOUND.  The problem is min c'x, A x = b, G x <= h, x in its cones.  For any y_eq, any y_in and y_in+ = max(y_in, 0), with
+ *       T_k >= tr X_k for every feasible x and Z_k = smat of cone k's part of c + A'y_eq + G'y_in+ (off-diagonals halved),
+ *           c'x  >=  -b'y_eq - h'y_in+ + sum_k T_k min(0, lambda_min(Z_k))        for every feasible x,
+ *       for a feasible y and for an infeasible one.  The call evaluates this with every rounding error pushed to the safe side.
+ * SERVED.  Models whose variables all lie in PSD cones (side >= 1).  PROXSDP_E_UNSUPP, the message naming the reason: a
+ *       second-order cone; a variable outside every cone; an equilibrated model.  (A handle never holds M_dense.)
+ * IN.   dual_eq (p) and dual_in (m): both host or both device (on_device; device pointers are borrowed and trusted as
+ *       proxsdp_model_data's are), in the units of a result.  trace_cap: HOST, one double per PSD cone (T_k), or NULL: T_k is
+ *       then derived on the host from the model's CURRENT rows (create's, or the last proxsdp_hip_model_rows'): every diagonal
+ *       variable of the cone must be the only stored entry of some equality row a X_ii = b with a != 0 and b / a >= 0; its cap
+ *       is the smallest nextafter(b / a, +inf) over such rows, T_k the sum of the caps in order, each partial sum followed by
+ *       nextafter(., +inf).  A cone with an uncovered diagonal returns PROXSDP_E_INVALID and names the cone.
+ * 1. DUAL MATRIX AND RADIUS.  k_bound_dual_cone, one thread per column k of the model's unscaled [A; G] (cnt_k entries),
+ *       contraction off: acc = 0; acc += val_q y_row(q) over the column in storage order; dc[k] = c[k] + acc -- the bits
+ *       k_exit_dual_cone forms, with y_in+ in place of y_in -- and rad[k] = gamma(cnt_k + 2) (|c[k]| + sum |val_q| |y_row(q)|);
+ *       both halved where k is an off-diagonal entry.  gamma(j) = j u / (1 - j u), u = 2^-53.  rho_k = the largest row sum of
+ *       rad over the cone's matrix, every addition rounded up: it bounds ||Z_exact - Z~||_2.
+ * 2. DUAL OBJECTIVE.  d = -sum_r bh_r y_r and D = sum_r |bh_r y_r| in one fixed-order reduction; d_safe = d - gamma(Q + 2) D.
+ * 3. CERTIFIED lambda_min, per cone of side s >= 2 (side 1: l = dc - rad, rounded down).  Z~ is gathered into a dense s x s
+ *       array (as k_tri_gather maps a cone's packed entries); nu = its largest absolute row sum.  For a shift sigma >= 0,
+ *       A(sigma) = Z~ with fl(z_ii + sigma) on the diagonal.  The factorisation of A(sigma) either COMPLETES with every pivot
+ *       above 2^-500 nu or reports its first failing column in a device flag; a non-positive or NaN pivot is a result, never
+ *       an assert, a trap or a fault.  If it completes,
+ *           lambda_min(Z~) >= -(sigma + delta),   delta = gamma(s + 3) / (1 - gamma(s + 3)) tr+(A) + u max_i |a_ii|,
+ *       tr+ the diagonal sum rounded up.  First term: for a completed Cholesky factorisation in floating point
+ *       |R~'R~ - A|_ij <= gamma(s + 1) (1 - gamma(s + 1))^-1 sqrt(a_ii a_jj) (Higham, Accuracy and Stability of Numerical
+ *       Algorithms, 2nd ed., section 10.1, Theorem 10.3 and (10.7); Rump, Verification of positive definiteness, BIT 46 (2006));
+ *       the matrix of the right-hand sides has rank one and 2-norm tr A, and R~'R~ is positive semidefinite.  The theorem holds
+ *       for every order of summation and with fused multiply-adds, which is why the device may use MFMA and need not match
+ *       the host's bits.  Second term: the rounding of the shifted diagonal.  The constant is not to be loosened.
+ *       Shift search, decided only by completed / failed: sigma = 0; then sigma_j = nu 2^(-48 + 4 j), j = 0 .. 12, until one
+ *       completes; when that was at j >= 1, five bisection steps between the last failure and the first success, each at the
+ *       geometric mean (sqrt on the host); sigma* = the smallest completed shift.  At most 19 factorisations.  If sigma_12
+ *       fails, certified[k] = 0, the cone's lambda_lower and the bound are -inf, and the call still returns 0.  (nu is
+ *       rounded up, so sigma_12 >= ||Z~||_inf leaves positive pivots in exact arithmetic; what is not certified in practice
+ *       is a cone whose nu or rho overflows: no factorisation is tried then, factorisations[k] = 0.)
+ *       l_k = -(sigma* + delta(sigma*) + rho_k), the sums rounded up.
+ * 4. COMBINATION, on the host: bound = d_safe + sum_k T_k min(0, l_k), every product and sum followed by nextafter(., -inf).
+ * OUT.  bound, dual_objective (= d); per cone (HOST arrays, caller-allocated, n_psd entries): shift, lambda_lower, radius,
+ *       factorisations, certified, and -- optional, NULL when not wanted -- delta and trace_used (T_k); bytes_allocated,
+ *       seconds, factor_seconds (the factorisations with their flag read-backs).
+ * The handle's data is not touched: a solve after the call equals a solve before it bit for bit.  Scratch (y, dc, rad, two
+ * dense s x s arrays, row sums, the flag) is allocated in the call, released before it returns and reported in
+ * bytes_allocated only.
+ * How (csrc/dual_bound.hip.hpp): a right-looking blocked factorisation of the lower triangle with panels of 64 --
+ * k_chol_diag (one workgroup, the 64 x 64 diagonal block in LDS, IEEE sqrt and division, sets the flag at a bad pivot),
+ * k_chol_panel (the triangular solve of 64 rows per workgroup against the block in LDS), k_chol_update (A22 -= L21 L21' on
+ * the lower-triangle tiles by v_mfma_f64_16x16x4_f64) -- chained as plain dependent launches on the model's stream: no waits
+ * between workgroups, no atomics on doubles, every launch behind a set flag returns at once.  Each entry's accumulation order
+ * is fixed by the code: the same input gives the same factor and the same flag on every run.  Sides that are no multiple of
+ * 64 are handled by bounds in the kernels; the matrix is not padded.
+ * PROXSDP_E_INVALID, on the host: a NULL struct, handle or array that is needed; a wrong struct_size; on_device other than 0
+ * or 1; a non-finite host dual; a negative or non-finite cap.  Device duals are checked by a reduction on the device. */
+typedef struct proxsdp_dual_bound {
+    int64_t struct_size;      /* = sizeof(proxsdp_dual_bound) */
+    int32_t on_device;        /* where dual_eq and dual_in live: 0 host, 1 DEVICE pointers on the model's device
+                               * (proxsdp_host_dual_bound: must be 0) */
+    int32_t reserved;
+    const double* dual_eq;    /* p */
+    const double* dual_in;    /* m */
+    const double* trace_cap;  /* HOST, n_psd, or NULL = derive from the rows */
+    /* out: caller-allocated HOST arrays, n_psd entries each */
+    double*  shift;           /* sigma* (0 for side 1; +inf when not certified) */
+    double*  lambda_lower;    /* l_k */
+    double*  radius;          /* rho_k */
+    int32_t* factorisations;
+    int32_t* certified;
+    double*  delta;           /* optional: delta(sigma*) */
+    double*  trace_used;      /* optional: T_k */
+    double  bound;
+    double  dual_objective;   /* d */
+    int64_t bytes_allocated;  /* device bytes this call allocated (and released); 0 on the host */
+    double  seconds;          /* wall time of the call */
+    double  factor_seconds;
+} proxsdp_dual_bound;
+int  proxsdp_hip_model_bound(proxsdp_model* mdl, proxsdp_dual_bound* q);
+/* The same contract with no device and no handle: serial loops and the plain serial column Cholesky (column j: a_ij -= l_ik l_jk
+ * for k < j in order, then the pivot test, sqrt and division).  c (n), M = [A; G] ((p + m) x n, CSC with base index_base, the
+ * caller's variable order), bh = [b; h], and the PSD cone lists as proxsdp_problem holds them.  Sums run over a column in
+ * storage order, so dc equals the device's wherever the stored order agrees; d may differ from the device's in its last bits
+ * (another order), which D covers.  PROXSDP_E_INVALID: as above where it applies; a malformed matrix or cone list.
+ * PROXSDP_E_UNSUPP: a variable outside every cone. */
+int  proxsdp_host_dual_bound(int64_t n, int64_t p, int64_t m, const double* c, const proxsdp_csc* M, const double* bh,
+                             int64_t n_psd, const int64_t* psd_ptr, const int64_t* psd_idx, int32_t index_base,
+                             proxsdp_dual_bound* q);
+/* test entries: ONE factorisation of A + shift I, with no model.  A: s x s HOST doubles, symmetric (the entries A[j * s + i],
+ * i >= j, are read); 1 <= s <= 46340; the pivot floor is 2^-500 times the largest absolute row sum of A.  R_out (s x s,
+ * row-major, may be NULL): the upper-triangular factor R = L' with zeros below the diagonal, R'R ~ A + shift I (after a failure
+ * in the last panel of 64 columns the rows of R before fail_col hold the factor; otherwise only the rows of completed panels
+ * do, the rest is unspecified).  fail_col: -1 = completed, else the first failing column, 0-based.
+ * proxsdp_hip_cholesky runs the device kernels above; proxsdp_host_cholesky the plain serial column Cholesky of the host half. */
+int  proxsdp_hip_cholesky(const double* A, int64_t s, double shift, double* R_out, int64_t* fail_col);
+int  proxsdp_host_cholesky(const double* A, int64_t s, double shift, double* R_out, int64_t* fail_col);
 /* test entry: the model's current internal data, downloaded into caller-allocated host arrays.  The sizes (n, Q = p + m, nnz,
  * ns = length of the support list, 0 when the support path is off) and the four norms (||b||, ||h||, ||c||, ||M||_F) are always
  * written; an array is written when its pointer is not NULL (call once with every pointer NULL for the sizes, allocate, call

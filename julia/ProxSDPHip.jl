@@ -589,4 +589,53 @@ function model_round(mdl::Ptr{Cvoid}, values, V, side::Integer; cone::Integer = 
             flips = q.flips, values_rounded = vr, values_final = vf, seconds = q.seconds)
 end
 
+# ---- a certified dual bound of a kept model (include/proxsdp_hip.h, "a certified dual bound of a model handle")
+mutable struct DualBound         # proxsdp_dual_bound
+    struct_size::Int64
+    on_device::Int32
+    reserved::Int32
+    dual_eq::Ptr{Float64}
+    dual_in::Ptr{Float64}
+    trace_cap::Ptr{Float64}
+    shift::Ptr{Float64}
+    lambda_lower::Ptr{Float64}
+    radius::Ptr{Float64}
+    factorisations::Ptr{Int32}
+    certified::Ptr{Int32}
+    delta::Ptr{Float64}
+    trace_used::Ptr{Float64}
+    bound::Float64
+    dual_objective::Float64
+    bytes_allocated::Int64
+    seconds::Float64
+    factor_seconds::Float64
+end
+
+"""
+    model_bound(mdl, dual_eq, dual_in, n_psd; trace_cap = nothing, on_device = false)
+
+A certified LOWER bound of the optimum of the kept model `mdl` (minimisation form: a MAX model's bound is `-bound`, an upper
+bound) from any dual point: `dual_eq` / `dual_in` are `Vector{Float64}`s of a `Result`, or with `on_device = true` DEVICE
+pointers.  The proof is a completed fp64 Cholesky factorisation on the device with its backward-error bound; no eigenvalue
+estimate enters.  `trace_cap`: one number per PSD cone with `tr X_k <= cap` for every feasible x, or `nothing` = derived from
+equality rows `a X_ii = b`.  Returns a NamedTuple: `bound` (`-Inf` when a cone could not be certified), `dual_objective`, and
+per cone `shift`, `lambda_lower`, `radius`, `delta`, `trace`, `factorisations`, `certified`; `seconds`, `factor_seconds`.
+"""
+function model_bound(mdl::Ptr{Cvoid}, dual_eq, dual_in, n_psd::Integer; trace_cap = nothing, on_device::Bool = false)
+    k = max(n_psd, 1)
+    shift = zeros(k); lower = zeros(k); radius = zeros(k); delta = zeros(k); trace = zeros(k)
+    tries = zeros(Int32, k); cert = zeros(Int32, k)
+    cap = trace_cap === nothing ? Float64[] : Vector{Float64}(trace_cap)
+    hostptr(v) = (v === nothing || length(v) == 0) ? Ptr{Float64}(C_NULL) : pointer(v)
+    GC.@preserve dual_eq dual_in cap shift lower radius delta trace tries cert begin
+        q = DualBound(sizeof(DualBound), Int32(on_device), Int32(0),
+                      on_device ? Ptr{Float64}(dual_eq) : hostptr(dual_eq), on_device ? Ptr{Float64}(dual_in) : hostptr(dual_in),
+                      hostptr(cap), pointer(shift), pointer(lower), pointer(radius), pointer(tries), pointer(cert), pointer(delta),
+                      pointer(trace), 0.0, 0.0, 0, 0.0, 0.0)
+        _check_rc(ccall((:proxsdp_hip_model_bound, libproxsdp_hip), Cint, (Ptr{Cvoid}, Ref{DualBound}), mdl, q))
+    end
+    return (bound = q.bound, dual_objective = q.dual_objective, shift = shift, lambda_lower = lower, radius = radius, delta = delta,
+            trace = trace, factorisations = tries, certified = cert .!= 0, seconds = q.seconds, factor_seconds = q.factor_seconds)
+end
+
 end # module

@@ -272,6 +272,15 @@ class RoundingIO(C.Structure):
                 ("sweeps", i32), ("reserved", i32), ("bytes_allocated", i64), ("seconds", f64), ("search_seconds", f64)]
 
 
+class DualBoundIO(C.Structure):
+    """proxsdp_dual_bound (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64), ("on_device", i32), ("reserved", i32),
+                ("dual_eq", pf64), ("dual_in", pf64), ("trace_cap", pf64),
+                ("shift", pf64), ("lambda_lower", pf64), ("radius", pf64),
+                ("factorisations", C.POINTER(i32)), ("certified", C.POINTER(i32)), ("delta", pf64), ("trace_used", pf64),
+                ("bound", f64), ("dual_objective", f64), ("bytes_allocated", i64), ("seconds", f64), ("factor_seconds", f64)]
+
+
 MODEL_DUMP_ARRAYS = (("csc_val", "nnz"), ("csr_val", "nnz"), ("csc_val_orig", "nnz"), ("csr_val_orig", "nnz"),
                      ("c", "n"), ("c_orig", "n"), ("bh", "Q"), ("support", "ns"), ("cS", "ns"))
 MODEL_NORM_NAMES = ("norm_b", "norm_h", "norm_c", "frob")
@@ -348,6 +357,10 @@ def lib():
     L.proxsdp_hip_model_round.argtypes = [C.c_void_p, C.POINTER(RoundingIO)]
     L.proxsdp_host_round.argtypes = [i64, pi64, pi64, pf64, pf64, C.POINTER(RoundingIO)]
     L.proxsdp_host_round_directions.argtypes = [i64, i32, i32, pf64]
+    L.proxsdp_hip_model_bound.argtypes = [C.c_void_p, C.POINTER(DualBoundIO)]
+    L.proxsdp_host_dual_bound.argtypes = [i64, i64, i64, pf64, C.POINTER(CSC), pf64, i64, pi64, pi64, i32, C.POINTER(DualBoundIO)]
+    L.proxsdp_hip_cholesky.argtypes = [pf64, i64, f64, pf64, pi64]
+    L.proxsdp_host_cholesky.argtypes = [pf64, i64, f64, pf64, pi64]
     L.proxsdp_hip_factor_residual.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64]
     L.proxsdp_hip_factor_residual_kernel.argtypes = [pf64, i64, pf64, i64, pf64, i32, pf64, pf64, i32, pf64]
     L.proxsdp_hip_psd_project.argtypes = [pf64, i64, i32, i32, C.POINTER(Options), pf64, pf64,
@@ -1315,6 +1328,97 @@ def host_round(values, vectors, adjacency, trials=1024, seed=0, max_sweeps=50, s
     return Rounding(Q, arr)
 
 
+class DualBound:
+    """What a bound call returned (proxsdp_dual_bound): bound (a certified LOWER bound of min c'x in the units and the
+    minimisation form of the model's c; -inf when some cone could not be certified), dual_objective (d), and per PSD cone
+    shift (sigma*), lambda_lower (l_k), radius (rho_k), delta, trace (T_k), factorisations, certified; loss = sum_k
+    T_k (shift + delta + radius), what the certificate costs beside the ideal bound of the same duals; seconds,
+    factor_seconds, bytes_allocated.  objective: set by Optimizer.bound (the bound in the model's own sense)."""
+
+    def __init__(self, Q, arr):
+        self.arrays = arr
+        self.bound, self.dual_objective = float(Q.bound), float(Q.dual_objective)
+        for k in ("shift", "lambda_lower", "radius", "delta", "factorisations", "certified"):
+            setattr(self, k, arr[k].copy())
+        self.trace = arr["trace_used"].copy()
+        self.certified = self.certified.astype(bool)
+        with np.errstate(invalid="ignore"):
+            self.loss = float(np.sum(self.trace * (self.shift + self.delta + self.radius)))
+        self.seconds, self.factor_seconds = float(Q.seconds), float(Q.factor_seconds)
+        self.bytes_allocated = int(Q.bytes_allocated)
+        self.objective = None
+
+
+def _bound_struct(n_psd, trace_cap=None, sentinel=None):
+    """proxsdp_dual_bound with output arrays for n_psd cones (prefilled with `sentinel` when given), and the arrays"""
+    k = max(int(n_psd), 1)
+    arr = dict(shift=np.zeros(k), lambda_lower=np.zeros(k), radius=np.zeros(k), delta=np.zeros(k), trace_used=np.zeros(k),
+               factorisations=np.zeros(k, dtype=np.int32), certified=np.zeros(k, dtype=np.int32))
+    if sentinel is not None:
+        for a in arr.values():
+            a[:] = sentinel
+    Q = DualBoundIO()
+    Q.struct_size = C.sizeof(DualBoundIO)
+    for name in ("shift", "lambda_lower", "radius", "delta", "trace_used"):
+        setattr(Q, name, _p(arr[name]))
+    Q.factorisations, Q.certified = _p(arr["factorisations"], C.POINTER(i32)), _p(arr["certified"], C.POINTER(i32))
+    if trace_cap is not None:
+        cap = _f(trace_cap).ravel()
+        if len(cap) != int(n_psd):
+            raise ValueError(f"bound: trace_cap must have {n_psd} entries, one per PSD cone")
+        arr["trace_cap"] = cap
+        Q.trace_cap = _p(cap if len(cap) else np.zeros(1))
+    return Q, arr
+
+
+def host_dual_bound(prob, dual_eq, dual_in, trace_cap=None, index_base=0, sentinel=None):
+    """proxsdp_host_dual_bound: the certified bound of Model.bound on the host, serially (no device, no handle).  prob: a
+    problem (c, A, b, G, h, psd); dual_eq (p) and dual_in (m): any dual point.  Returns a DualBound."""
+    A, G = sp.csc_matrix(prob.A, dtype=np.float64), sp.csc_matrix(prob.G, dtype=np.float64)
+    p, m, n = A.shape[0], G.shape[0], int(prob.n)
+    M = sp.vstack([A, G], format="csc") if p + m else sp.csc_matrix((0, n))
+    M.sort_indices()
+    cp, rv, nz = _i(M.indptr) + index_base, _i(M.indices) + index_base, _f(M.data)
+    Mc = CSC(p + m, n, _p(cp, pi64), _p(rv if len(rv) else np.zeros(1, dtype=np.int64), pi64), _p(nz if len(nz) else np.zeros(1)))
+    bh = _f(np.concatenate([np.asarray(prob.b, float).ravel(), np.asarray(prob.h, float).ravel()]))
+    c = _f(prob.c).ravel()
+    lst = list(prob.psd)
+    ptr = np.zeros(len(lst) + 1, dtype=np.int64)
+    for k, v in enumerate(lst):
+        ptr[k + 1] = ptr[k] + len(v)
+    idx = (_i(np.concatenate(lst)) + index_base) if lst else np.zeros(1, dtype=np.int64)
+    ye, yi = _f(dual_eq).ravel(), _f(dual_in).ravel()
+    if len(ye) != p or len(yi) != m:
+        raise ValueError(f"host_dual_bound: dual_eq and dual_in must have {p} and {m} entries")
+    Q, arr = _bound_struct(len(lst), trace_cap, sentinel)
+    Q.dual_eq, Q.dual_in = _p(ye if p else np.zeros(1)), _p(yi if m else np.zeros(1))
+    _check(lib().proxsdp_host_dual_bound(n, p, m, _p(c if n else np.zeros(1)), C.byref(Mc), _p(bh if len(bh) else np.zeros(1)),
+                                         len(lst), _p(ptr, pi64), _p(idx, pi64), index_base, C.byref(Q)))
+    return DualBound(Q, arr)
+
+
+def _cholesky(entry, A, shift, want_factor):
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("cholesky: A must be square")
+    s = A.shape[0]
+    R = np.zeros((s, s)) if want_factor else None
+    fail = C.c_int64(-2)
+    _check(entry(_p(A if s else np.zeros(1)), s, float(shift), _p(R) if want_factor else None, C.byref(fail)))
+    return int(fail.value), R
+
+
+def cholesky(A, shift=0.0, want_factor=True):
+    """proxsdp_hip_cholesky: ONE factorisation of A + shift I by the device kernels of Model.bound (test entry).  Returns
+    (fail_col, R): fail_col = -1 when it completed, else the first failing column; R upper triangular, R'R ~ A + shift I."""
+    return _cholesky(lib().proxsdp_hip_cholesky, A, shift, want_factor)
+
+
+def host_cholesky(A, shift=0.0, want_factor=True):
+    """proxsdp_host_cholesky: the same by the plain serial column Cholesky of the host half (no device)"""
+    return _cholesky(lib().proxsdp_host_cholesky, A, shift, want_factor)
+
+
 def model_norm2(v, grid=0):
     """proxsdp_hip_model_norm2: ||v||_2 by the reduction a device-route Model.update uses, with `grid` workgroups"""
     v = _f(v).ravel()
@@ -1583,6 +1687,38 @@ class Model:
         _check(lib().proxsdp_hip_model_round(self._handle(), C.byref(Q)))
         del keep
         return Rounding(Q, arr)
+
+    # ---- a bound
+    def bound(self, duals, trace_cap=None):
+        """proxsdp_hip_model_bound: a certified LOWER bound of the model's optimum (minimisation form) from any dual point --
+        the proof is a completed fp64 Cholesky factorisation on the device with its backward-error bound, no eigenvalue
+        estimate.  duals: a SolveResult or (dual_eq, dual_in), both NumPy or both CUDA float64 tensors.  trace_cap: one number
+        per PSD cone with tr X_k <= cap for every feasible x, or None = derived from equality rows a X_ii = b.  Returns a
+        DualBound.  The model is not touched."""
+        if isinstance(duals, SolveResult):
+            duals = (duals.dual_eq, duals.dual_in)
+        ye, yi = duals
+        on_dev = [_is_tensor(v) and v.is_cuda for v in (ye, yi)]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("Model.bound: host arrays and CUDA tensors cannot be mixed in one call")
+        Q, arr = _bound_struct(len(self._sides), trace_cap)
+        if all(on_dev):
+            import torch
+            dev_id = int(self._options.device_id)
+            Q.on_device = 1
+            keep = [ye, yi]
+            Q.dual_eq = _device_ptr(ye, self.p, dev_id, "dual_eq") if self.p else _p(np.zeros(1))
+            Q.dual_in = _device_ptr(yi, self.m, dev_id, "dual_in") if self.m else _p(np.zeros(1))
+            torch.cuda.synchronize(dev_id)                          # the library runs on its own stream
+        else:
+            keep = [_f(v.numpy() if _is_tensor(v) else v).ravel() for v in (ye, yi)]
+            if len(keep[0]) != self.p or len(keep[1]) != self.m:
+                raise ValueError(f"Model.bound: dual_eq and dual_in must have {self.p} and {self.m} entries")
+            keep = [a if len(a) else np.zeros(1) for a in keep]
+            Q.dual_eq, Q.dual_in = _p(keep[0]), _p(keep[1])
+        _check(lib().proxsdp_hip_model_bound(self._handle(), C.byref(Q)))
+        del keep
+        return DualBound(Q, arr)
 
     # ---- solve
     def solve(self, start=None, factors=False, primal=True, device_out=False, trace_capacity=0, time_limit=None,

@@ -535,6 +535,77 @@ int proxsdp_host_round_directions(int64_t seed, int32_t r, int32_t trials, doubl
     });
 }
 
+int proxsdp_hip_model_bound(proxsdp_model* mdl, proxsdp_dual_bound* q) {
+    return guarded([&]() -> int {
+        if (!q) throw std::invalid_argument("NULL proxsdp_dual_bound");
+        if (q->struct_size != (int64_t)sizeof(proxsdp_dual_bound)) throw std::invalid_argument("proxsdp_dual_bound.struct_size mismatch");
+        if (!mdl) throw std::invalid_argument("NULL handle");
+        const proxsdp::Prep& P = mdl->S->P;
+        if (!P.socs.empty()) throw std::domain_error("proxsdp_hip_model_bound does not serve a model with a second-order cone");
+        if (P.conelen != P.n || P.blocks.empty())
+            throw std::domain_error("proxsdp_hip_model_bound serves models whose variables all lie in PSD cones: some variable is outside every cone");
+        if (P.dense()) throw std::domain_error("proxsdp_hip_model_bound does not serve a dense M_dense");
+        if (P.equilibrated) throw std::domain_error("proxsdp_hip_model_bound does not serve an equilibrated model: the duals of a result are rescaled");
+        proxsdp::check_bound_struct(q, P.p, P.m, (int64_t)P.blocks.size(), true);
+        mdl->bound(*q);
+        return 0;
+    });
+}
+
+int proxsdp_host_dual_bound(int64_t n, int64_t p, int64_t m, const double* c, const proxsdp_csc* M, const double* bh,
+                            int64_t n_psd, const int64_t* psd_ptr, const int64_t* psd_idx, int32_t index_base,
+                            proxsdp_dual_bound* q) {
+    return guarded([&]() -> int {
+        if (n < 1 || p < 0 || m < 0 || n_psd < 1) throw std::invalid_argument("proxsdp_host_dual_bound: n, n_psd must be >= 1 and p, m >= 0");
+        if (index_base != 0 && index_base != 1) throw std::invalid_argument("index_base must be 0 or 1");
+        if (!c || !M || (p + m > 0 && !bh) || !psd_ptr || !psd_idx) throw std::invalid_argument("proxsdp_host_dual_bound: a NULL argument");
+        proxsdp::check_bound_struct(q, p, m, n_psd, false);
+        proxsdp::check_csc(*M, p + m, n, index_base, "M");
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(c[i])) throw std::invalid_argument("proxsdp_host_dual_bound: non-finite entry in c");
+        for (int64_t r = 0; r < p + m; ++r)
+            if (!std::isfinite(bh[r])) throw std::invalid_argument("proxsdp_host_dual_bound: non-finite entry in bh");
+        for (int64_t e = 0; e < M->colptr[n] - index_base; ++e)
+            if (!std::isfinite(M->nzval[e])) throw std::invalid_argument("proxsdp_host_dual_bound: non-finite entry in M");
+        proxsdp::host_dual_bound(n, p, m, c, *M, bh, n_psd, psd_ptr, psd_idx, index_base, *q);
+        return 0;
+    });
+}
+
+static void check_cholesky_args(const double* A, int64_t s, double shift, const int64_t* fail_col) {
+    if (!A || !fail_col) throw std::invalid_argument("cholesky: A or fail_col is NULL");
+    if (s < 1 || s > proxsdp::BOUND_MAX_SIDE) throw std::invalid_argument("cholesky: s must be 1 .. 46340");
+    if (!(shift >= 0.0) || !std::isfinite(shift)) throw std::invalid_argument("cholesky: shift must be finite and >= 0");
+}
+
+int proxsdp_hip_cholesky(const double* A, int64_t s, double shift, double* R_out, int64_t* fail_col) {
+    return guarded([&]() -> int {
+        check_cholesky_args(A, s, shift, fail_col);
+        Engine E(nullptr, 2, 2);
+        *fail_col = proxsdp::device_cholesky(E.S.stream, A, s, shift, R_out);
+        return 0;
+    });
+}
+
+int proxsdp_host_cholesky(const double* A, int64_t s, double shift, double* R_out, int64_t* fail_col) {
+    return guarded([&]() -> int {
+        check_cholesky_args(A, s, shift, fail_col);
+        double nu = 0.0;
+        for (int64_t i = 0; i < s; ++i) {
+            double a = 0.0;
+            for (int64_t j = 0; j < s; ++j) a += std::fabs(A[i * s + j]);
+            nu = std::max(nu, a);
+        }
+        std::vector<double> W(A, A + s * s);
+        for (int64_t i = 0; i < s; ++i) W[(size_t)(i * s + i)] = A[i * s + i] + shift;
+        *fail_col = proxsdp::host_cholesky(W.data(), s, proxsdp::bound_pivot_floor(nu));
+        if (R_out)
+            for (int64_t c = 0; c < s; ++c)
+                for (int64_t r = 0; r < s; ++r) R_out[c * s + r] = r >= c ? W[(size_t)(c * s + r)] : 0.0;
+        return 0;
+    });
+}
+
 int proxsdp_hip_model_solve(proxsdp_model* mdl, const proxsdp_options* run_opt, proxsdp_result* res,
                             const proxsdp_start* start, const proxsdp_device_vectors* start_dev,
                             proxsdp_psd_factors* fac, proxsdp_device_vectors* out_dev) {

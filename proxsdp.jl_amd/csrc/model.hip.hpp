@@ -11,12 +11,15 @@
 //           nnz or the pattern) built for the new shape, filled from the live one through the plan's source maps, and exchanged
 //           with it; everything sized by n or a cone side stays
 // round   = a +-1 vector from a cone's factors against the current c (rounding.hip.hpp): reads the exit path's c, writes nothing
+// bound   = a certified lower bound of the optimum from any dual point (dual_bound.hip.hpp): reads the exit path's c, values
+//           and [b; h] and the host mirror of the rows, writes nothing
 // The entry points (argument checks, error codes) are in capi.hip.
 #pragma once
 #include "exit_device.hip.hpp"
 #include "model_update.hip.hpp"
 #include "model_rows.hip.hpp"
 #include "rounding.hip.hpp"
+#include "dual_bound.hip.hpp"
 
 struct proxsdp_model {
     std::atomic<long long> bytes{0};            // live device bytes (DevAccount); first member: outlives every buffer below
@@ -324,6 +327,17 @@ struct proxsdp_model {
         PX_HIP(hipSetDevice(opt0.device_id));
         s.restore_cert_data();                              // (a certificate search of the last solve zeroed c or [b; h])
         device_round(s.stream, s.xd.c.p + B.off, B.n, q.cone, q);
+    }
+
+    // q: validated on the host (check_bound_struct); the model is one the call serves.  Nothing of the handle is written, the
+    // scratch is the call's
+    void bound(proxsdp_dual_bound& q) {
+        using namespace proxsdp;
+        Solver& s = *S;
+        PX_HIP(hipSetDevice(opt0.device_id));
+        s.restore_cert_data();                              // (a certificate search of the last solve zeroed c or [b; h])
+        const BoundModel md{s.P, s.rs.csc_ptr.p, s.rs.csc_row.p, s.rs.exit.cval.p, s.rs.exit.bh.p, s.xd.c.p, s.offdiag_d.p};
+        device_dual_bound(s.stream, md, q);
     }
 
     void info(proxsdp_model_info& out) const {

@@ -180,7 +180,28 @@ class Optimizer:
         out = self.model.round(self.sol if result is None else result, **kw)
         if len(self.problem.psd[kw.get("cone", 0)]) == self.problem.n:
             out.objective = self.problem.user_objective(out.value)
+        self.last_round = out
         return out
+
+    def bound(self, result=None, trace_cap=None):
+        """After optimize(..., keep_model=True): a certified bound of the optimum from the duals of `result` (default: the
+        last solution) -- binding.Model.bound, a device Cholesky test, no eigenvalue estimate.  Returns the DualBound; its
+        .objective is the bound in the model's own sense, with the sign flip and the objective constant optimize() applies
+        to objval: a LOWER bound of a minimisation, an UPPER bound of a max_sense problem."""
+        if getattr(self, "model", None) is None:
+            raise ValueError("bound() needs optimize(..., keep_model=True) first")
+        out = self.model.bound(self.sol if result is None else result, trace_cap=trace_cap)
+        out.objective = self.problem.user_objective(out.bound)
+        self.last_bound = out
+        return out
+
+    def gap(self):
+        """(bound, value of the last round()) in the model's own sense, when both exist (else None): the optimum lies
+        between the two"""
+        b, r = getattr(self, "last_bound", None), getattr(self, "last_round", None)
+        if b is None or r is None or r.objective is None:
+            return None
+        return b.objective, r.objective
 
     def _follow_rows(self, ch, add_rows):
         """self.problem with the rows of the kept model: G' = [kept rows; new rows], h' likewise (host copies)"""
