@@ -93,7 +93,10 @@ extern "C" {
  * later: proxsdp_hip_model_bound (a certified lower bound of a model handle's optimum from any dual point: the proof is a
  * completed fp64 Cholesky factorisation on the device with its backward-error bound) with its host restatement
  * proxsdp_host_dual_bound, the test entries proxsdp_hip_cholesky / proxsdp_host_cholesky and the new struct
- * proxsdp_dual_bound: four functions and one new struct, no existing struct changed: the version stays */
+ * proxsdp_dual_bound: four functions and one new struct, no existing struct changed: the version stays;
+ * later: the test entry proxsdp_hip_project_cones (one PSD projection of a vector of mixed cones through the solver's own
+ * set-up and launch code) with the new struct proxsdp_project_cones: one function and one new struct, no existing struct
+ * changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -1439,6 +1442,27 @@ int proxsdp_hip_trial_batch(const proxsdp_csc* M, int32_t index_base, const doub
 int proxsdp_hip_cone_tail(const double* x, int64_t n, const int64_t* soc_off, const int32_t* soc_len, int32_t nsoc,
                           const int64_t* one_off, int32_t n_one, double* x_soc, double* gap_in, double* gap_out,
                           double* x_clamp, double* min_eig);
+
+/* ONE PSD projection of an n-vector through the solver's own phases, with no launch of its own: setup_device, classify_blocks
+ * (with the blocks' workspaces), setup_small_batch, setup_soc, an upload of x, psd_projection(x) at iteration 1, a stream
+ * synchronisation, harvest_small_ranks.  The problem is used for its cone layout only (PSD sides, 1x1 included, SOCs, free
+ * variables; it may have no rows); x is in the solver's internal order and scaling (cone variables first, in cone order,
+ * off-diagonal PSD entries times sqrt 2), as the vectors of proxsdp_state are.  The projection touches the PSD blocks only.
+ * Per PSD block: offset and side; block_class = 0 a 1x1 block (clamped), 1 one-launch Jacobi (k_small_psd_project), 2 one-launch
+ * sign function (k_small_sign_project), 3 large (an engine per block); rank = current_rank; min_eig (1x1 blocks: the clamped
+ * value the kernel recorded); sweeps = Jacobi sweeps run (class 1; -1 elsewhere).  Non-finite values in a block come back as
+ * PROXSDP_E_HIP with the message of the engine that met them. */
+typedef struct {
+    int64_t struct_size;
+    /* in */
+    const double* x;                     /* n */
+    /* out */
+    double* x_out;                       /* n */
+    int64_t* block_off; int32_t* block_side; int32_t* block_class;    /* n_psd each */
+    int64_t* rank; double* min_eig; int32_t* sweeps;                   /* n_psd each */
+    int64_t batched_small_eigs, full_eigs, full_eigs_sign, sign_short_pass, sign_short_fail;    /* proxsdp_stats of the call */
+} proxsdp_project_cones;
+int proxsdp_hip_project_cones(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_project_cones* t);
 
 /* ONE product of the sign-function projection (full_eig! without an eigendecomposition, prox_operators.jl:111-126) through the
  * solver's own launch code (Solver::sym_gemm), on host data: k_sym_gemm (tile = 64), k_sym_gemm32 (32) or k_sym_gemm48 (48).

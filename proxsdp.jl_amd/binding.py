@@ -377,6 +377,7 @@ def lib():
     L.proxsdp_host_preprocess.argtypes = [C.POINTER(Problem), pi64, pi64, pf64, pf64]
     L.proxsdp_hip_dense_scaling.argtypes = [C.POINTER(Problem), C.POINTER(Options), pf64, pf64, pf64, pf64, C.POINTER(i32)]
     L.proxsdp_host_equilibrate_rowsums.argtypes = [pf64, i64, i64, C.POINTER(Options), pf64, pf64]
+    L.proxsdp_hip_project_cones.argtypes = [C.POINTER(Problem), C.POINTER(Options), C.POINTER(ProjectConesIO)]
     L.proxsdp_hip_sym_product.argtypes = [C.POINTER(SymProductIO)]
     L.proxsdp_hip_sign_unpack.argtypes = [pf64, i64, f64, pf64, pf64]
     L.proxsdp_hip_reconstruct_fused.argtypes = [C.POINTER(ReconstructFusedIO)]
@@ -2098,6 +2099,44 @@ def cone_tail(x, soc_off, soc_len, one_off):
     _check(L.proxsdp_hip_cone_tail(_p(x), len(x), _p(so, pi64), _p(sl, C.POINTER(i32)), ns_, _p(oo, pi64), no_,
                                    _p(x_soc), _p(g0), _p(g1), _p(x_cl), _p(me)))
     return x_soc, g0[:ns_], g1[:ns_], x_cl, me[:no_]
+
+
+BLOCK_CLASSES = ("1x1", "small-jacobi", "small-sign", "large")       # proxsdp_project_cones.block_class
+
+
+class ProjectConesIO(C.Structure):
+    """proxsdp_project_cones (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64),
+                ("x", pf64), ("x_out", pf64),
+                ("block_off", pi64), ("block_side", C.POINTER(i32)), ("block_class", C.POINTER(i32)),
+                ("rank", pi64), ("min_eig", pf64), ("sweeps", C.POINTER(i32)),
+                ("batched_small_eigs", i64), ("full_eigs", i64), ("full_eigs_sign", i64),
+                ("sign_short_pass", i64), ("sign_short_fail", i64)]
+
+
+def project_cones(prob, x, options=None):
+    """proxsdp_hip_project_cones: ONE psd_projection of the n-vector x (solver order and scaling) through the solver's own set-up
+    and launch code; the problem gives the cone layout only.  Returns a dict: x (projected), and per PSD block offset, side,
+    cls (a name of BLOCK_CLASSES), rank, min_eig, sweeps (-1 where no Jacobi ran); stats (the five counters of the call)."""
+    M = _Marshalled(prob)
+    x = _f(x)
+    assert len(x) == M.P.n
+    nb = max(len(prob.psd), 1)
+    pi32 = C.POINTER(i32)
+    out = np.zeros_like(x)
+    off, rank = np.zeros(nb, dtype=np.int64), np.zeros(nb, dtype=np.int64)
+    side, cls, sweeps = (np.zeros(nb, dtype=np.int32) for _ in range(3))
+    me = np.zeros(nb)
+    t = ProjectConesIO()
+    t.struct_size = C.sizeof(ProjectConesIO)
+    t.x, t.x_out = _p(x), _p(out)
+    t.block_off, t.block_side, t.block_class = _p(off, pi64), _p(side, pi32), _p(cls, pi32)
+    t.rank, t.min_eig, t.sweeps = _p(rank, pi64), _p(me), _p(sweeps, pi32)
+    _check(lib().proxsdp_hip_project_cones(C.byref(M.P), C.byref(options) if options is not None else None, C.byref(t)))
+    k = len(prob.psd)
+    return dict(x=out, offset=off[:k], side=side[:k], cls=[BLOCK_CLASSES[c] for c in cls[:k]], rank=rank[:k], min_eig=me[:k],
+                sweeps=sweeps[:k],
+                stats={f: getattr(t, f) for f in ("batched_small_eigs", "full_eigs", "full_eigs_sign", "sign_short_pass", "sign_short_fail")})
 
 
 SYM_EPILOGUES = {"plain": 0, "poly": 1, "final": 2, "final_res": 3}    # proxsdp_sym_product.epilogue

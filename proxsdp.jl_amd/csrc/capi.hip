@@ -954,7 +954,7 @@ int proxsdp_hip_psd_project(const double* packed_in, int64_t n, int32_t target_r
                     PX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(proxsdp::dev::k_small_psd_project),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 hipLaunchKernelGGL(proxsdp::dev::k_small_psd_project, dim3(1), dim3(proxsdp::dev::TPB), lds, S.stream,
-                                   x.p, (const long long*)off.p, (const int*)side.p, o.tol_psd, rk.p, rk.p + 1, 2, 64);
+                                   x.p, (const long long*)off.p, (const int*)side.p, o.tol_psd, rk.p, rk.p + 1, 2, 64, (int*)nullptr);
             } else {
                 const size_t lds = proxsdp::dev::small_sign_lds_bytes((int)n);
                 if (lds > 48 * 1024)
@@ -1198,6 +1198,19 @@ int proxsdp_hip_cone_tail(const double* x, int64_t n, const int64_t* soc_off, co
             if (one_off[k] < 0 || one_off[k] >= n) throw std::invalid_argument("1x1 block outside x");
         Engine E(nullptr, 2, 2);
         E.S.test_cone_tail(x, n, soc_off, soc_len, nsoc, one_off, n_one, x_soc, gap_in, gap_out, x_clamp, min_eig);
+        return 0;
+    });
+}
+
+int proxsdp_hip_project_cones(const proxsdp_problem* prob, const proxsdp_options* opt, proxsdp_project_cones* t) {
+    return guarded([&]() -> int {
+        if (!prob || !t) throw std::invalid_argument("NULL argument");
+        if (t->struct_size != (int64_t)sizeof(proxsdp_project_cones)) throw std::invalid_argument("project cones: struct_size mismatch");
+        proxsdp_options o = checked_options(opt);
+        o.trace_capacity = 0;
+        proxsdp_result dummy{};
+        proxsdp::Solver S(*prob, o, dummy);
+        S.test_project_cones(*t);
         return 0;
     });
 }

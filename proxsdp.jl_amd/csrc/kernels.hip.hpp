@@ -1681,17 +1681,25 @@ k_lz_rotate_mfma(const double* __restrict__ V, int ldv, int K, const double* __r
 // calls a dense eigensolver per block per iteration -- on multi-block SDPLIB models (truss, control,
 // arch, qap: tens to hundreds of blocks of side 2..20) that is a serial chain of tiny LAPACK / rocSOLVER
 // calls.  Here: the block is unpacked into LDS, diagonalised by a parallel-order cyclic Jacobi
-// (n/2 disjoint rotations per round, round-robin schedule, eigenvectors accumulated; stops when
-// off(A)^2 <= 1e-32 |diag|^2), and X+ = sum over lambda_k > 0 of lambda_k v_k v_k' is written back in
-// packed form.  Jacobi's eigenpairs are accurate to a few ulp, as dsyevr's are.
-// out: rank[b] = #{lambda > tol_psd} (current_rank), npos[b] = #{lambda > 0}.
+// (n/2 disjoint rotations per round, round-robin schedule, eigenvectors accumulated), and
+// X+ = sum over lambda_k > 0 of lambda_k v_k v_k' is written back in packed form.  Jacobi's eigenpairs are accurate
+// to a few ulp, as dsyevr's are.
+// The sweeps stop when off(A)^2 <= 1e-32 |diag|^2, or -- that bound lies below the rounding floor of off^2 / diag^2 from side 5
+// on -- when off^2 <= 1e-28 diag^2 and a sweep has failed to reduce off^2 by a factor of 10 (far from convergence a sweep of
+// the cyclic method often gains less than that, so a stall counts only where what is left of off(A) can no longer move X+ by
+// 1e-13 of the scale).  A block whose largest |entry| is below 2^-400 or above 2^400 is scaled by an exact power of two for
+// the sweeps (the squares of the stopping test would underflow / overflow) and the result scaled back: the projection is
+// positively homogeneous.
+// out: rank[b] = #{lambda > tol_psd} (current_rank), npos[b] = #{lambda > 0}; both -1 when the block holds non-finite values
+// (it is left as it was; the host raises the error); sweeps[b] = sweeps run (optional).
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(TPB)
 k_small_psd_project(double* __restrict__ x, const long long* __restrict__ offs, const int* __restrict__ sides,
-                    double tol_psd, int* __restrict__ rank_out, int* __restrict__ npos_out, int nmin, int nmax) {
+                    double tol_psd, int* __restrict__ rank_out, int* __restrict__ npos_out, int nmin, int nmax,
+                    int* __restrict__ sweeps_out /* per block, or null */) {
     extern __shared__ __attribute__((aligned(16))) double sj_mem[];
     __shared__ double s_red[NWAVE];
-    __shared__ int s_cnt[2];
+    __shared__ int s_cnt[3];
     const int n = sides[blockIdx.x];
     if (n < nmin || n > nmax) return;                  // (sides outside the range belong to k_small_sign_project, small_sign.hip.hpp)
     double* __restrict__ xp = x + offs[blockIdx.x];
@@ -1701,16 +1709,31 @@ k_small_psd_project(double* __restrict__ x, const long long* __restrict__ offs, 
     double* cs = V + n * ld;                           // c[i], s[i] of the round's pairs (2 x 32)
     int* pq = (int*)(cs + 64);                         // p[i], q[i]
     const int tid = threadIdx.x;
+    double amax = 0.0;
     for (int t = tid; t < n * n; t += TPB) {
         const int i = t % n, j = t / n;
         const int lo = min(i, j), hi = max(i, j);
         const double v = xp[(long long)hi * (hi + 1) / 2 + lo];
         A[i * ld + j] = (i == j) ? v : v * INV_SQRT2;
         V[i * ld + j] = (i == j) ? 1.0 : 0.0;
+        amax = fmax(amax, fabs(v));
     }
+    amax = block_max(amax, s_red);
+    if (tid == 0) cs[0] = amax;
     __syncthreads();
+    amax = cs[0];
+    __syncthreads();
+    int sc_exp = 0;                                    // the sweeps run on A 2^-sc_exp (uniform over the workgroup)
+    if (amax > 0.0 && amax <= 1.7976931348623157e308 && (amax < 0x1p-400 || amax > 0x1p+400)) {
+        (void)frexp(amax, &sc_exp);
+        for (int t = tid; t < n * n; t += TPB) { const int i = t % n, j = t / n; A[i * ld + j] = ldexp(A[i * ld + j], -sc_exp); }
+        __syncthreads();
+    }
     const int m = n + (n & 1);                         // players of the round-robin (one dummy when n is odd)
     const int np = m / 2;
+    double off_prev = 0.0;
+    int sweeps = 0;
+    bool bad = false;                                  // non-finite input (the scaled squares cannot overflow)
     for (int sweep = 0; sweep < 40; ++sweep) {
         // convergence: off-diagonal mass against the diagonal
         double off = 0.0, dg = 0.0;
@@ -1725,7 +1748,12 @@ k_small_psd_project(double* __restrict__ x, const long long* __restrict__ offs, 
         const double dgs = block_sum(dg, s_red);
         if (tid == 0) cs[1] = dgs;
         __syncthreads();
-        if (cs[0] <= 1e-32 * cs[1] || cs[0] == 0.0) break;
+        const double off2 = cs[0], dg2 = cs[1];
+        bad = !(off2 + dg2 <= 1.7976931348623157e308);
+        if (bad || off2 <= 1e-32 * dg2 || off2 == 0.0) break;
+        if (sweep > 0 && off2 <= 1e-28 * dg2 && !(off2 <= 0.1 * off_prev)) break;
+        off_prev = off2;
+        ++sweeps;
         __syncthreads();
         for (int rd = 0; rd < m - 1; ++rd) {
             // the round's disjoint pairs and their rotations
@@ -1777,15 +1805,22 @@ k_small_psd_project(double* __restrict__ x, const long long* __restrict__ offs, 
         }
     }
     // eigenvalues on the diagonal; counts, then X+ in packed form
-    if (tid == 0) { s_cnt[0] = 0; s_cnt[1] = 0; }
+    __syncthreads();                                   // (the exit test's reads of cs precede the writes below)
+    if (tid == 0) { s_cnt[0] = 0; s_cnt[1] = 0; s_cnt[2] = bad ? 1 : 0; }
     __syncthreads();
     if (tid < n) {
-        const double lamk = A[tid * ld + tid];
+        const double lamk = ldexp(A[tid * ld + tid], sc_exp);
         cs[tid] = lamk > 0.0 ? lamk : 0.0;
         if (lamk > tol_psd) atomicAdd(&s_cnt[0], 1);
         if (lamk > 0.0) atomicAdd(&s_cnt[1], 1);
+        if (!(fabs(lamk) <= 1.7976931348623157e308)) atomicAdd(&s_cnt[2], 1);
     }
     __syncthreads();
+    if (tid == 0 && sweeps_out != nullptr) sweeps_out[blockIdx.x] = sweeps;
+    if (s_cnt[2] != 0) {                               // a non-finite eigenvalue: no projection to write
+        if (tid == 0) { rank_out[blockIdx.x] = -1; npos_out[blockIdx.x] = -1; }
+        return;
+    }
     const int N = n * (n + 1) / 2;
     for (int t = tid; t < N; t += TPB) {
         int j = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);

@@ -1413,9 +1413,9 @@ inline void Solver::setup_small_batch() {
     if (small_blocks.empty()) return;
     std::vector<long long> so; std::vector<int> ss;
     for (int idx : small_blocks) { so.push_back(P.blocks[idx].off); ss.push_back(P.blocks[idx].n); small_maxn = std::max(small_maxn, P.blocks[idx].n); }
-    small_off.alloc(so.size()); small_side.alloc(ss.size()); small_rank.alloc(3 * ss.size() + 2); small_rank.zero(stream);   // [rank | npos] per block, then the sign kernel's cumulative [pass, fail] counters
+    small_off.alloc(so.size()); small_side.alloc(ss.size()); small_rank.alloc(4 * ss.size() + 2); small_rank.zero(stream);   // [rank | npos | schedule-test outcome | Jacobi sweeps] per block
     small_off.upload(so.data(), so.size(), stream); small_side.upload(ss.data(), ss.size(), stream);
-    small_rank_host.alloc(2 * ss.size() + 2);      // (ints: rank | positive count | schedule-test outcome per block)
+    small_rank_host.alloc(2 * ss.size() + 2);      // (ints, two per slot: rank | positive count | schedule-test outcome | Jacobi sweeps per block)
     small_sign_maxn = 0;
     int jac_maxn = 0;
     for (int sd : ss) { if (sd > small_jacobi_max) small_sign_maxn = std::max(small_sign_maxn, sd); else jac_maxn = std::max(jac_maxn, sd); }

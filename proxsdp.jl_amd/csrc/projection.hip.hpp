@@ -25,12 +25,15 @@ inline void Solver::psd_projection(double* x) {
 inline void Solver::project_small_blocks(double* x) {
     harvest_small_ranks();
     const int nb = (int)small_blocks.size();
-    // ranks, positive counts and the schedule-test outcomes [nb each] go STRAIGHT into pinned host memory (no copy launch)
+    // ranks, positive counts, the schedule-test outcomes and the Jacobi sweep counts [nb each] go STRAIGHT into pinned host memory (no copy launch)
     // (small models only, as the scalars of the linesearch: zero_copy_small; otherwise through the device buffer and one copy)
     const bool zc = zero_copy_small();
     int* rk_host = zc ? reinterpret_cast<int*>(small_rank_host.p) : small_rank.p;
-    if (zc) for (int q = 0; q < nb; ++q) rk_host[2 * nb + q] = 0;          // (the previous launch's values were harvested above)
-    else PX_HIP(hipMemsetAsync(small_rank.p + 2 * nb, 0, (size_t)nb * sizeof(int), stream));
+    if (zc) for (int q = 0; q < nb; ++q) { rk_host[2 * nb + q] = 0; rk_host[3 * nb + q] = -1; }   // (the previous launch's values were harvested above)
+    else {
+        PX_HIP(hipMemsetAsync(small_rank.p + 2 * nb, 0, (size_t)nb * sizeof(int), stream));
+        PX_HIP(hipMemsetAsync(small_rank.p + 3 * nb, 0xFF, (size_t)nb * sizeof(int), stream));      // (-1: not a Jacobi block)
+    }
     bool any_jacobi = false;
     int jac_maxn = 0;
     for (int idx : small_blocks) if (P.blocks[idx].n <= small_jacobi_max) { any_jacobi = true; jac_maxn = std::max(jac_maxn, P.blocks[idx].n); }
@@ -39,7 +42,7 @@ inline void Solver::project_small_blocks(double* x) {
         const size_t lds = ((size_t)2 * jac_maxn * ld + 64) * sizeof(double) + 64 * sizeof(int);
         hipLaunchKernelGGL(dev::k_small_psd_project, dim3(nb), dim3(dev::TPB), lds, stream,
                            x, (const long long*)small_off.p, (const int*)small_side.p, opt.tol_psd, rk_host, rk_host + nb,
-                           2, small_jacobi_max);
+                           2, small_jacobi_max, rk_host + 3 * nb);
     }
     if (small_sign_maxn > 0) {
         // shortened, tested schedule as Solver::full_eig_by_sign: start at row 8 (sign_start_row overrides), fall back inside the kernel
@@ -52,7 +55,7 @@ inline void Solver::project_small_blocks(double* x) {
         st.full_eigs_sign += nb; st.sign_products += 57LL * nb;      // (counted per block below for the Jacobi ones)
         for (int idx : small_blocks) if (P.blocks[idx].n <= small_jacobi_max) { st.full_eigs_sign--; st.sign_products -= 57; }
     }
-    if (!zc) PX_HIP(hipMemcpyAsync(small_rank_host.p, small_rank.p, (size_t)3 * nb * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (!zc) PX_HIP(hipMemcpyAsync(small_rank_host.p, small_rank.p, (size_t)4 * nb * sizeof(int), hipMemcpyDeviceToHost, stream));
     small_pending = true;
     st.full_eigs += nb; st.batched_small_eigs += nb;
     for (int idx : small_blocks) { current_rank[idx] = 0; min_eig[idx] = 0.0; }
@@ -63,9 +66,10 @@ inline void Solver::harvest_small_ranks() {
     small_pending = false;
     const int* r = reinterpret_cast<const int*>(small_rank_host.p);
     for (size_t q = 0; q < small_blocks.size(); ++q) {
-        if (r[q] < 0) throw HipError("sign-function projection of a small block produced non-finite values");
+        if (r[q] < 0) throw HipError("projection of a small block (one-launch Jacobi or sign function) produced non-finite values");
         current_rank[small_blocks[q]] = r[q];
     }
+    small_sweeps.assign(r + 3 * small_blocks.size(), r + 4 * small_blocks.size());   // (Jacobi blocks: sweeps run; the others -1)
     // the shortened schedule's tests made inside k_small_sign_project (cumulative counters behind the ranks)
     const int* flag = r + 2 * small_blocks.size();            // per block: 1 = test passed, 2 = failed (fall-back rows ran), 0 = no test
     for (size_t q = 0; q < small_blocks.size(); ++q) { st.sign_short_pass += flag[q] == 1; st.sign_short_fail += flag[q] == 2; }

@@ -76,6 +76,21 @@ __device__ __forceinline__ double ss_sum(double v, double* __restrict__ s_red, d
     __syncthreads();
     return *s_out;
 }
+__device__ __forceinline__ double ss_max(double v, double* __restrict__ s_red, double* __restrict__ s_out) {
+    v = wave_max(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) s_red[w] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = s_red[0];
+#pragma unroll
+        for (int i = 1; i < SS_TPB / 64; ++i) r = fmax(r, s_red[i]);
+        *s_out = r;
+    }
+    __syncthreads();
+    return *s_out;
+}
 __device__ __forceinline__ double ss_fro2(const double* __restrict__ M, int np, int ld, double* __restrict__ s_red, double* __restrict__ s_out) {
     double s = 0.0;
     for (int t = threadIdx.x; t < np * np; t += SS_TPB) { const int i = t / np, j = t - i * np; const double v = M[i * ld + j]; s += v * v; }
@@ -120,17 +135,22 @@ k_small_sign_project(double* __restrict__ x, const long long* __restrict__ offs,
         A[i * ld + j] = (i == j) ? v : v * INV_SQRT2;
     }
     __syncthreads();
-    double f2 = ss_fro2(A, np, ld, s_red, &s_sc[0]);
-    const int N = n * (n + 1) / 2;
-    // a block of denormal-tiny entries (|A|_F^2 below ~1e-250: 1 / f2 would overflow): the projection is positively
+    // a block of tiny or huge entries (largest |entry| below 2^-400 or above 2^400: |A|_F^2 would underflow -- at 2^-600 to an
+    // exact 0, which reads as the zero matrix -- or 1 / f2 and the squares overflow): the projection is positively
     // homogeneous, so the block is scaled by an exact power of two for the iteration and the result scaled back
-    double unscale = 1.0;
-    if (f2 > 0.0 && f2 < 1e-250) {
-        for (int t = tid; t < np * ld; t += SS_TPB) A[t] *= 0x1p+500;
+    int sc_exp = 0;
+    {
+        double amax = 0.0;
+        for (int t = tid; t < np * ld; t += SS_TPB) amax = fmax(amax, fabs(A[t]));
+        amax = ss_max(amax, s_red, &s_sc[0]);
+        if (amax > 0.0 && amax <= 1.7976931348623157e308 && (amax < 0x1p-400 || amax > 0x1p+400)) {
+            (void)frexp(amax, &sc_exp);
+            for (int t = tid; t < np * ld; t += SS_TPB) A[t] = ldexp(A[t], -sc_exp);
+        }
         __syncthreads();
-        f2 = ss_fro2(A, np, ld, s_red, &s_sc[0]);
-        unscale = 0x1p-500;
     }
+    const double f2 = ss_fro2(A, np, ld, s_red, &s_sc[0]);
+    const int N = n * (n + 1) / 2;
     if (!(f2 > 0.0)) {                                       // the zero matrix (or non-finite input: left alone)
         if (f2 == 0.0) for (int t = tid; t < N; t += SS_TPB) xp[t] = 0.0;
         if (tid == 0) {
@@ -212,7 +232,7 @@ k_small_sign_project(double* __restrict__ x, const long long* __restrict__ offs,
         for (int reg = 0; reg < 4; ++reg) {
             const int r = 16 * tI + l4 + 4 * reg, c = 16 * tJ + l15;
             if (r <= c && c < n) {
-                const double v = 0.5 * (A[r * ld + c] + acc[reg]) * unscale;
+                const double v = ldexp(0.5 * (A[r * ld + c] + acc[reg]), sc_exp);
                 xp[(long long)c * (c + 1) / 2 + r] = (r == c) ? v : v * SQRT2;
             }
         }

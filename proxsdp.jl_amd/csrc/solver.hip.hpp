@@ -399,6 +399,7 @@ struct EigWork : EigSolveState {
     // the sign engine's verification (EigSolveState::sign) and the scratch for in-place calls
     DevBuf<double> sg_cmp;                         // max |difference|, max |value| of a verification
     DevBuf<double> sg_out;
+    DevBuf<double> sg_in;                          // the packed block times a power of two (sign_project_rescaled)
     // streams and events last: destroyed before the buffers above
     Stream stream;                                 // own stream (concurrent block projections)
     Event done;
@@ -696,6 +697,7 @@ public:
     double test_min_eig() const { return min_eig.empty() ? 0.0 : min_eig[0]; }
     void test_spmv(bool transpose, const double* in, double* out);
     void test_trial_batch(proxsdp_trial_batch& t);
+    void test_project_cones(proxsdp_project_cones& t);
     void test_cone_tail(const double* x, int64_t n, const int64_t* so, const int32_t* sl, int nsoc,
                         const int64_t* oo, int none, double* x_soc, double* gap_in, double* gap_out,
                         double* x_clamp, double* mineig);
@@ -785,6 +787,7 @@ private:
     int small_maxn = 0;
     int small_jacobi_max = 64;                 // small blocks up to this side: batched Jacobi; above: k_small_sign_project
     int small_sign_maxn = 0;                   // largest side served by k_small_sign_project (0: none)
+    std::vector<int> small_sweeps;             // per small block, from the last harvest: sweeps k_small_psd_project ran (-1: a sign block)
     int small_sign_cap = 0;                    // largest side whose dynamic LDS the device grants (setup_device; 64 on gfx950)
     // per-iteration read-backs written by the kernels straight into pinned host memory: only where the iteration leaves little
     // dirty data behind (a kernel that stores to host memory ends with a system-scope release)
@@ -857,6 +860,7 @@ private:
     void full_eig_project(int idx, const double* xp_in, double* xp_out, bool fuse);
     bool full_eig_by_lanczos(int idx, const double* xp_in, double* xp_out, bool fuse);
     bool full_eig_by_sign(int idx, const double* xp_in, double* xp_out, bool fuse, bool force = false);
+    bool sign_project_rescaled(int idx, double* xp_out, bool fused, bool force, const proxsdp_stats& before);
     void truncated_project_dense(int idx, const double* xp_in, double* xp_out, bool fuse, int nev);
     // acceptance threshold of the Lanczos-served full_eig! (options.full_eig_lanczos_posres, default 1e-6 of the spectral
     // scale), never looser than 1 % of the tightest tolerance the user asked for (a user at tolerance 1e-7
@@ -1162,11 +1166,20 @@ inline void Solver::full_eig_values(EigWork& W, const double* xp, double offscal
         W.A.alloc((size_t)n * n); W.D.alloc(n); W.E.alloc(n); W.info.alloc(1);
     }
     const int ntile = W.nt * (W.nt + 1) / 2;
+    // a block of tiny or huge entries (largest |entry| outside [2^-400, 2^400]): dsyevd's squares leave the fp64 range -- at
+    // 2^-600 it returned the diagonal, silently; at 2^520 it did not converge -- so such a block is scaled by an exact power of
+    // two on the way in and its eigenvalues scaled back, all on the device (no host round trip; nothing happens in range)
+    if (W.sg_cmp.n < 2) W.sg_cmp.alloc(2);
+    W.sg_cmp.zero(stream);
+    hipLaunchKernelGGL(dev::k_maxdiff, dim3(grid_for(W.N)), dim3(dev::TPB), 0, stream, xp, xp, (long long)W.N, W.sg_cmp.p);
     hipLaunchKernelGGL(dev::k_unpack_upper, dim3(ntile), dim3(dev::TPB), 0, stream, xp, n, W.A.p, n, offscale);
+    hipLaunchKernelGGL(dev::k_ldexp_range, dim3(grid_for((long long)n * n)), dim3(dev::TPB), 0, stream, W.A.p, (long long)n * n,
+                       (const double*)W.sg_cmp.p + 1, -1);
     std::lock_guard<std::mutex> lk(blas_mutex);          // one rocBLAS handle: dense fallbacks run one at a time
     PX_ROC(rocblas_set_stream(blas, (hipStream_t)stream));
     PX_ROC(rocsolver_dsyevd(blas, vectors ? rocblas_evect_original : rocblas_evect_none, rocblas_fill_upper,
                             n, W.A.p, n, W.D.p, W.E.p, W.info.p));
+    hipLaunchKernelGGL(dev::k_ldexp_range, dim3(1), dim3(dev::TPB), 0, stream, W.D.p, (long long)n, (const double*)W.sg_cmp.p + 1, 1);
     Dhost.resize(n);
     rocblas_int info = 0;
     W.D.download(Dhost.data(), n, stream);
@@ -1264,6 +1277,7 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
         // iteration): users who ask for tolerances near that floor get the LAPACK-accurate dense eigensolver
         if (opt.full_eig_sign < 0 && std::min({opt.tol_gap, opt.tol_feasibility, opt.tol_primal, opt.tol_dual}) < 1e-8) return false;
     }
+    const proxsdp_stats lst0 = W.lst;                        // (a projection that has to be scaled runs twice and counts once)
     const int ld = W.nt * dev::TILE;
     const int grid = sym_gemm_grid(W, true);
     if (W.sg_ld != ld) {
@@ -1398,6 +1412,10 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
         PX_HIP(hipMemcpyAsync(W.sg_host.p, sc, 16 * sizeof(double), hipMemcpyDeviceToHost, stream));
         wait_stream();
     }
+    // f = |A|_F came out 0 or non-finite: the zero matrix, non-finite input, or squares outside the fp64 range
+    if (const double f = W.sg_host.p[6]; (!(f > 0.0) || !std::isfinite(f)) && xp_in != W.sg_in.p) {   // (not the scaled pass itself)
+        if (sign_project_rescaled(idx, xp_out, fz, force, lst0)) return true;
+    }
     const double tr = W.sg_host.p[5], fro2 = W.sg_host.p[7];
     if (!std::isfinite(tr) || !std::isfinite(fro2)) throw HipError("sign-function projection produced non-finite values");
     const int npos = (int)std::llround(0.5 * (tr + fro2));
@@ -1405,6 +1423,34 @@ inline bool Solver::full_eig_by_sign(int idx, const double* xp_in, double* xp_ou
     current_rank[idx] = std::max(0, std::min(npos, n));
     min_eig[idx] = 0.0;                                      // prox_operators.jl:114
     W.xprev.last_npos = current_rank[idx];
+    return true;
+}
+
+// The sign-function projection of a block whose |A|_F^2 left the fp64 range (largest |entry| below ~1e-162: the sum of
+// squares underflows, at 2^-600 to an exact 0, and the iteration returned A / 2; or above ~1e+154: it overflows).  The
+// projection is positively homogeneous: the block is taken again from its unpacked copy sgA, scaled by an exact power of two
+// to a largest |entry| in [1/2, 1), projected, and the result scaled back.  False: nothing to do -- the zero matrix (what was
+// computed stands) or non-finite input (the caller raises the error).  `before`: the block's counters before the first pass.
+inline bool Solver::sign_project_rescaled(int idx, double* xp_out, bool fused, bool force, const proxsdp_stats& before) {
+    EigWork& W = eig[idx];
+    const int ld = W.nt * dev::TILE;
+    if (W.sg_cmp.n < 2) W.sg_cmp.alloc(2);
+    W.sg_cmp.zero(stream);
+    const long long sz = (long long)ld * ld;
+    hipLaunchKernelGGL(dev::k_maxdiff, dim3(grid_for(sz)), dim3(dev::TPB), 0, stream, (const double*)W.sgA.p, (const double*)W.sgA.p, sz, W.sg_cmp.p);
+    double h[2] = {0.0, 0.0};
+    W.sg_cmp.download(h, 2, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    const double amax = h[1];
+    if (amax == 0.0 || !std::isfinite(amax)) return false;
+    if (fused) throw HipError("sign-function projection: a block outside the fp64 range of its squares on the support path");
+    int e = 0;
+    (void)std::frexp(amax, &e);
+    if (W.sg_in.n < (size_t)W.N) W.sg_in.alloc(W.N);
+    hipLaunchKernelGGL(dev::k_pack_ldexp, dim3(grid_for(W.N)), dim3(dev::TPB), 0, stream, (const double*)W.sgA.p, ld, (long long)W.N, -e, W.sg_in.p);
+    W.lst = before;                                          // (the pass that ran on the unscaled block is not counted)
+    if (!full_eig_by_sign(idx, W.sg_in.p, xp_out, false, force)) return false;
+    hipLaunchKernelGGL(dev::k_ldexp, dim3(grid_for(W.N)), dim3(dev::TPB), 0, stream, xp_out, (long long)W.N, e);
     return true;
 }
 

@@ -138,6 +138,42 @@ inline void Solver::test_cone_tail(const double* x, int64_t n, const int64_t* so
     PX_HIP(hipStreamSynchronize(stream));
 }
 
+// one PSD projection of host data through the phases of setup() that the projection needs and psd_projection itself: the
+// block lists, the small-block batch with its rank record, the 1x1 offsets -- no launch of its own
+inline void Solver::test_project_cones(proxsdp_project_cones& t) {
+    if (P.n < 1) throw std::invalid_argument("project cones: the problem has no variables");
+    if (!t.x || !t.x_out || (!P.blocks.empty() && (!t.block_off || !t.block_side || !t.block_class || !t.rank || !t.min_eig || !t.sweeps)))
+        throw std::invalid_argument("project cones: NULL array");
+    init_parameters();
+    setup_device();
+    classify_blocks();
+    setup_small_batch();
+    setup_soc();
+    DevBuf<double> xd(P.n);
+    xd.upload(t.x, P.n, stream);
+    iter = 1;
+    psd_projection(xd.p);
+    xd.download(t.x_out, P.n, stream);
+    std::vector<double> ones(one_blocks.size());
+    if (!one_blocks.empty()) one_min.download(ones.data(), ones.size(), stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    harvest_small_ranks();
+    merge_block_stats();
+    for (size_t idx = 0; idx < P.blocks.size(); ++idx) {
+        t.block_off[idx] = P.blocks[idx].off; t.block_side[idx] = P.blocks[idx].n;
+        t.block_class[idx] = P.blocks[idx].n == 1 ? 0 : 3;
+        t.rank[idx] = current_rank[idx]; t.min_eig[idx] = min_eig[idx]; t.sweeps[idx] = -1;
+    }
+    for (size_t q = 0; q < one_blocks.size(); ++q) t.min_eig[one_blocks[q]] = ones[q];
+    for (size_t q = 0; q < small_blocks.size(); ++q) {
+        const int idx = small_blocks[q];
+        t.block_class[idx] = P.blocks[idx].n <= small_jacobi_max ? 1 : 2;
+        if (q < small_sweeps.size()) t.sweeps[idx] = small_sweeps[q];
+    }
+    t.batched_small_eigs = st.batched_small_eigs; t.full_eigs = st.full_eigs; t.full_eigs_sign = st.full_eigs_sign;
+    t.sign_short_pass = st.sign_short_pass; t.sign_short_fail = st.sign_short_fail;
+}
+
 // ONE product of the sign iteration on host data (include/proxsdp_hip.h proxsdp_sym_product), launched by sym_gemm itself on the
 // tile shape asked for.  eig[0] was sized for side t.n (alloc_eigwork); operands are zero-padded to ld as full_eig_by_sign
 // leaves its work matrices, every output buffer is prefilled with the sentinel.
