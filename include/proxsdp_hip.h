@@ -96,7 +96,11 @@ extern "C" {
  * proxsdp_dual_bound: four functions and one new struct, no existing struct changed: the version stays;
  * later: the test entry proxsdp_hip_project_cones (one PSD projection of a vector of mixed cones through the solver's own
  * set-up and launch code) with the new struct proxsdp_project_cones: one function and one new struct, no existing struct
- * changed: the version stays */
+ * changed: the version stays;
+ * later: the test entry proxsdp_hip_operator_cycles (every cycle of a Lanczos run on the operator form: the block given as a
+ * support list, its values and the previous projection's factors) with the new struct proxsdp_operator_cycles, and the host
+ * entry proxsdp_host_block1_lds_doubles (the LDS plan of the one-workgroup cycle kernel): two functions and one new struct, no
+ * existing struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -1619,6 +1623,56 @@ typedef struct {
     int32_t npad, krylovdim, cycles, reserved2;
 } proxsdp_lanczos_cycles;
 int proxsdp_hip_lanczos_cycles(proxsdp_lanczos_cycles* t);
+
+/* Every cycle of ONE thick-restart Lanczos run on the OPERATOR FORM, A v = F (lam o (F' v)) + E v: as proxsdp_hip_lanczos_cycles
+ * (the same observer, the same arrays per cycle, info[0 .. 9] as there), but the block of side n is given by its pieces and no
+ * packed block exists.  support: ns strictly ascending packed indices (column-major upper triangle, k = i + j (j + 1) / 2,
+ * i <= j) below n (n + 1) / 2; esv: the support-value array as the solver holds it, 2 ns values in svec units (an off-diagonal
+ * entry carries the sqrt(2)): [0, ns) is what the kernels read beside factors, [ns, 2 ns) what they read in the second form.
+ * F (n x rp, column-major) and lam (rp positive values), 0 <= rp <= 127, rp <= n: the previous projection's factors; they are
+ * put into the factor buffer from column f_first on (0 <= f_first <= 127), as a dsaupd-rule projection leaves them.
+ * no_factors = 1: the second form, x_prev has no factors (rp must be 0) and E takes the values esv + ns.  The ELL / overflow
+ * layout is built by the solver's own set-up code from the support list; a row of more than 32 entries needs
+ * opt->lanczos_operator = 1 below side 6000, as in a solve.  probe_v (n values, or NULL): before the run ONE mat-vec launch on
+ * the records form with v = probe_v: probe_ev (ldv) = E v, probe_tpart (ceil(n / 64) x 128) the per-row-block records of F' v
+ * (record g, column c at 128 g + c), probe_apart (ceil(n / 64)) the row blocks' shares of v' E v.
+ * Per cycle, beside info[0 .. 9]: info[10] the mat-vecs the cycle ran on the operator-form kernels, info[11] 1 on the owner
+ * form of F' v (0: the records form), info[12] the factor-column chunks of 64 the kernels were built for (1 or 2), info[13] the
+ * ELL width, info[14] the rows with overflow entries, info[15] for the one-workgroup kernel 1 when E sat in LDS, 0 when it
+ * was read through L2, -1 on the step kernels.  ell_w / overflow_rows: the same two numbers, known before the run.
+ * Refused with PROXSDP_E_INVALID before any launch: n outside 2 .. 46340, nev outside 1 .. n, max_cycles < 1, cols / ldv not
+ * krylovdim + 1 / 64 ceil(n / 64), a Krylov dimension above 255 (the operator form runs on the step kernels and the
+ * one-workgroup kernel only), krylovkit_eager, lanczos_operator = 0, rp or f_first out of range, no_factors with rp > 0, an
+ * index out of range or not ascending, a value of the active half of esv, of F, lam, resid or probe_v that is not finite,
+ * lam <= 0, a NULL array. */
+#define PROXSDP_OP_INFO          16
+typedef struct {
+    int64_t struct_size;
+    /* in */
+    int32_t n, nev, max_cycles, cols, ldv, rp;
+    int32_t f_first, no_factors;
+    int64_t ns;
+    const int32_t* support;                      /* ns */
+    const double* esv;                           /* 2 ns */
+    const double* F;                             /* n x rp */
+    const double* lam;                           /* rp */
+    const proxsdp_options* opt;
+    const double* resid;                         /* n, or NULL */
+    const double* probe_v;                       /* n, or NULL */
+    double sentinel;
+    /* out */
+    int32_t* info;                               /* max_cycles x PROXSDP_OP_INFO */
+    double* V;                                   /* max_cycles x cols x ldv */
+    double* alphas; double* betas; double* D; double* f;   /* max_cycles x cols each */
+    double* probe_ev; double* probe_tpart; double* probe_apart;   /* with probe_v */
+    int32_t npad, krylovdim, cycles, ell_w;
+    int32_t overflow_rows, reserved;
+} proxsdp_operator_cycles;
+int proxsdp_hip_operator_cycles(proxsdp_operator_cycles* t);
+/* host only: the doubles of dynamic LDS the one-workgroup cycle kernel asks for (b1_lds_plan) at nt = ceil(n / 64) row blocks
+ * -- fop = 0: the packed operator with a triangle of xN entries resident; fop = 1: the operator form with ell_w_lds ELL
+ * columns of E resident (0: E read through L2).  -1: nt outside 1 .. 8, or a negative size. */
+int64_t proxsdp_host_block1_lds_doubles(int32_t nt, int32_t fop, int64_t xN, int32_t ell_w_lds);
 
 /* The "Init" section (pdhg.jl:54-142) of a solve with a dense A (prob->M_dense), nothing more: E (p + m) and D (n), the
  * equilibration diagonals -- ones when equilibration is off or switched itself off, *equilibrated says which --, frob =

@@ -384,6 +384,9 @@ def lib():
     L.proxsdp_hip_rotate.argtypes = [C.POINTER(RotationIO)]
     L.proxsdp_hip_tail_copy.argtypes = [C.POINTER(TailCopyIO)]
     L.proxsdp_hip_lanczos_cycles.argtypes = [C.POINTER(LanczosCyclesIO)]
+    L.proxsdp_hip_operator_cycles.argtypes = [C.POINTER(OperatorCyclesIO)]
+    L.proxsdp_host_block1_lds_doubles.argtypes = [i32, i32, i64, i32]
+    L.proxsdp_host_block1_lds_doubles.restype = i64
     L.proxsdp_hip_solve_sharded.argtypes = [C.POINTER(Problem), C.POINTER(Options), i32, C.POINTER(i32), C.POINTER(i32),
                                             C.POINTER(i32), C.POINTER(i32), C.POINTER(Result), C.POINTER(Stats)]
     L.proxsdp_host_split_shard.argtypes = [C.POINTER(Problem), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32,
@@ -2367,6 +2370,92 @@ def lanczos_cycles(packed, n, nev, max_cycles, options=None, resid=None, sentine
                 split_ready=bool(info[c, 7]), kept_compared=bool(info[c, 8]), kept_differ=int(info[c, 9]), V=V[c].T, alphas=al[c], betas=be[c], D=D[c], f=f[c])
            for c in range(t.cycles)]
     return dict(npad=npad, krylovdim=kd, cycles=cyc, untouched=dict(info=info[t.cycles:], V=V[t.cycles:], alphas=al[t.cycles:]))
+
+
+OP_INFO = 16                                                              # PROXSDP_OP_INFO
+OP_RLD = 128                                                              # the stride of the records of F'v (probe_tpart)
+
+
+class OperatorCyclesIO(C.Structure):
+    """proxsdp_operator_cycles (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64),
+                ("n", i32), ("nev", i32), ("max_cycles", i32), ("cols", i32), ("ldv", i32), ("rp", i32),
+                ("f_first", i32), ("no_factors", i32), ("ns", i64),
+                ("support", pi32), ("esv", pf64), ("F", pf64), ("lam", pf64), ("opt", C.POINTER(Options)), ("resid", pf64),
+                ("probe_v", pf64), ("sentinel", f64),
+                ("info", pi32), ("V", pf64), ("alphas", pf64), ("betas", pf64), ("D", pf64), ("f", pf64),
+                ("probe_ev", pf64), ("probe_tpart", pf64), ("probe_apart", pf64),
+                ("npad", i32), ("krylovdim", i32), ("cycles", i32), ("ell_w", i32), ("overflow_rows", i32), ("reserved", i32)]
+
+
+def operator_cycles(n, support, values, F, lam, nev, max_cycles, options=None, resid=None, no_factors=False, f_first=0,
+                    other_half=None, probe_v=None, sentinel=SYM_SENTINEL):
+    """proxsdp_hip_operator_cycles: every cycle of one run of Solver::lanczos on the operator form A v = F (lam o F'v) + E v.
+    support: ascending packed indices of E's entries; values: theirs in svec units (off-diagonals carry the sqrt(2)); they go
+    into the half of the support-value array that the form reads (no_factors: the second), `other_half` (default NaN) into
+    the other.  F (n, rp), lam (rp).  Returns lanczos_cycles' dict; every cycle has besides: fop (the mat-vecs it ran on the
+    operator-form kernels), owner, nchp, ell_w, overflow_rows, ell_in_lds (None on the step kernels); the dict has ell_w,
+    overflow_rows and, with probe_v, probe = dict(ev (npad), tpart (nt, 128), apart (nt)) of one mat-vec launch."""
+    supp = np.ascontiguousarray(support, dtype=np.int32)
+    vals = _f(values)
+    ns = len(supp)
+    assert len(vals) == ns
+    oth = np.full(ns, np.nan) if other_half is None else _f(other_half)
+    assert len(oth) == ns
+    esv = np.ascontiguousarray(np.concatenate([oth, vals] if no_factors else [vals, oth]))
+    Fm = np.asfortranarray(np.asarray(F, dtype=np.float64).reshape(n, -1))
+    lm = _f(lam)
+    rp = Fm.shape[1]
+    assert len(lm) == rp
+    o = options if options is not None else default_options()
+    kd = max(2 * int(nev) + 1, int(get_option(o, "eigsolver_min_lanczos")))
+    cols, npad, mc = kd + 1, 64 * ((n + 63) // 64), max(int(max_cycles), 1)
+    nt = npad // 64
+    t = OperatorCyclesIO()
+    t.struct_size = C.sizeof(OperatorCyclesIO)
+    t.n, t.nev, t.max_cycles, t.cols, t.ldv, t.rp = int(n), int(nev), int(max_cycles), cols, npad, rp
+    t.f_first, t.no_factors, t.ns = int(f_first), int(bool(no_factors)), ns
+    Ff = Fm.ravel(order="F")
+    if ns > 0:
+        t.support, t.esv = _p(supp, pi32), _p(esv)
+    if rp > 0:
+        t.F, t.lam = _p(Ff), _p(lm)
+    t.opt, t.sentinel = C.pointer(o), float(sentinel)
+    r = _f(resid) if resid is not None else None
+    if r is not None:
+        assert len(r) == n
+        t.resid = _p(r)
+    pv = _f(probe_v) if probe_v is not None else None
+    pev, ptp, pap = np.zeros(npad), np.zeros((nt, OP_RLD)), np.zeros(nt)
+    if pv is not None:
+        assert len(pv) == n
+        t.probe_v, t.probe_ev, t.probe_tpart, t.probe_apart = _p(pv), _p(pev), _p(ptp), _p(pap)
+    info = np.zeros((mc, OP_INFO), dtype=np.int32)
+    V = np.zeros((mc, cols, npad))
+    al, be, D, f = (np.zeros((mc, cols)) for _ in range(4))
+    t.info, t.V, t.alphas, t.betas, t.D, t.f = _p(info, pi32), _p(V), _p(al), _p(be), _p(D), _p(f)
+    _check(lib().proxsdp_hip_operator_cycles(C.byref(t)))
+    assert t.npad == npad and t.krylovdim == kd
+    cyc = [dict(kfirst=int(info[c, 0]), K=int(info[c, 1]), stop=int(info[c, 2]), engine=LZ_ENGINES[int(info[c, 3])],
+                split=bool(info[c, 4]), speculated=bool(info[c, 5]), merge_on_device=bool(info[c, 6]),
+                split_ready=bool(info[c, 7]), kept_compared=bool(info[c, 8]), kept_differ=int(info[c, 9]),
+                fop=int(info[c, 10]), owner=bool(info[c, 11]), nchp=int(info[c, 12]), ell_w=int(info[c, 13]),
+                overflow_rows=int(info[c, 14]), ell_in_lds=None if info[c, 15] < 0 else bool(info[c, 15]),
+                V=V[c].T, alphas=al[c], betas=be[c], D=D[c], f=f[c])
+           for c in range(t.cycles)]
+    out = dict(npad=npad, krylovdim=kd, cycles=cyc, ell_w=int(t.ell_w), overflow_rows=int(t.overflow_rows),
+               untouched=dict(info=info[t.cycles:], V=V[t.cycles:], alphas=al[t.cycles:]))
+    if pv is not None:
+        out["probe"] = dict(ev=pev, tpart=ptp, apart=pap)
+    return out
+
+
+def block1_lds_doubles(nt, fop, xN=0, ell_w_lds=0):
+    """proxsdp_host_block1_lds_doubles: the doubles of dynamic LDS k_lz_block1 asks for (b1_lds_plan); host only"""
+    r = int(lib().proxsdp_host_block1_lds_doubles(int(nt), int(bool(fop)), int(xN), int(ell_w_lds)))
+    if r < 0:
+        raise ValueError("block1_lds_doubles: nt must be 1 .. 8, sizes non-negative, ell_w_lds <= 32")
+    return r
 
 
 def dense_scaling(prob, options=None):

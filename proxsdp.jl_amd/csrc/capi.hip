@@ -1321,6 +1321,56 @@ int proxsdp_hip_lanczos_cycles(proxsdp_lanczos_cycles* t) {
     });
 }
 
+int proxsdp_hip_operator_cycles(proxsdp_operator_cycles* t) {
+    return guarded([&]() -> int {
+        if (!t) throw std::invalid_argument("NULL argument");
+        if (t->struct_size != (int64_t)sizeof(proxsdp_operator_cycles)) throw std::invalid_argument("operator cycles: struct_size mismatch");
+        if (t->n < 2 || t->n > 46340) throw std::invalid_argument("operator cycles: n must be 2 .. 46340");
+        if (t->nev < 1 || t->nev > t->n) throw std::invalid_argument("operator cycles: nev must be 1 .. n");
+        if (t->max_cycles < 1) throw std::invalid_argument("operator cycles: max_cycles < 1");
+        if (t->rp < 0 || t->rp > proxsdp::dev::RLD - 1 || t->rp > t->n) throw std::invalid_argument("operator cycles: rp must be 0 .. min(127, n)");
+        if (t->f_first < 0 || t->f_first > proxsdp::dev::RLD - 1) throw std::invalid_argument("operator cycles: f_first must be 0 .. 127");
+        if (t->no_factors != 0 && t->no_factors != 1) throw std::invalid_argument("operator cycles: no_factors must be 0 or 1");
+        if (t->no_factors && t->rp != 0) throw std::invalid_argument("operator cycles: the second form has no factors (rp = 0)");
+        const int64_t N = (int64_t)t->n * (t->n + 1) / 2;
+        if (t->ns < 0 || t->ns > N) throw std::invalid_argument("operator cycles: ns must be 0 .. n (n + 1) / 2");
+        if (!t->info || !t->V || !t->alphas || !t->betas || !t->D || !t->f || (t->ns > 0 && (!t->support || !t->esv)) ||
+            (t->rp > 0 && (!t->F || !t->lam)) || (t->probe_v && (!t->probe_ev || !t->probe_tpart || !t->probe_apart)))
+            throw std::invalid_argument("operator cycles: NULL buffer");
+        for (int64_t s = 0; s < t->ns; ++s)
+            if (t->support[s] < 0 || t->support[s] >= N || (s > 0 && t->support[s] <= t->support[s - 1]))
+                throw std::invalid_argument("operator cycles: support indices must be strictly ascending and below n (n + 1) / 2");
+        auto finite = [](const double* a, size_t cnt) { for (size_t q = 0; q < cnt; ++q) if (!std::isfinite(a[q])) return false; return true; };
+        if (t->ns > 0 && !finite(t->esv + (t->no_factors ? t->ns : 0), (size_t)t->ns)) throw std::invalid_argument("operator cycles: a support value is not finite");
+        if (t->rp > 0 && (!finite(t->F, (size_t)t->n * t->rp) || !finite(t->lam, t->rp))) throw std::invalid_argument("operator cycles: a factor entry is not finite");
+        for (int c = 0; c < t->rp; ++c) if (!(t->lam[c] > 0.0)) throw std::invalid_argument("operator cycles: lam must be positive");
+        if ((t->resid && !finite(t->resid, t->n)) || (t->probe_v && !finite(t->probe_v, t->n))) throw std::invalid_argument("operator cycles: a vector entry is not finite");
+        proxsdp_options o = checked_options(t->opt);
+        if (o.lanczos_operator == 0) throw std::invalid_argument("operator cycles: lanczos_operator = 0 switches the operator form off");
+        if (o.krylovkit_eager && o.eigsolver != 1) throw std::invalid_argument("operator cycles: krylovkit_eager runs another driver");
+        const int kd = std::max(2 * t->nev + 1, (int)o.eigsolver_min_lanczos);
+        if (kd > proxsdp::dev::LZ_KMAX) throw std::invalid_argument("operator cycles: the operator form takes a Krylov dimension of at most 255");
+        if (t->cols != kd + 1 || t->ldv != proxsdp::ceil_div(t->n, proxsdp::dev::TILE) * proxsdp::dev::TILE)
+            throw std::invalid_argument("operator cycles: cols must be krylovdim + 1, ldv 64 ceil(n / 64)");
+        o.lanczos_wide_krylov = 0;
+        o.krylovkit_max_iter = t->max_cycles; o.arpack_max_iter = t->max_cycles;   // the driver ends the run itself
+        const size_t nc = (size_t)t->max_cycles * t->cols;
+        std::fill(t->info, t->info + (size_t)t->max_cycles * PROXSDP_OP_INFO, -1);
+        std::fill(t->V, t->V + nc * t->ldv, t->sentinel);
+        for (double* a : {t->alphas, t->betas, t->D, t->f}) std::fill(a, a + nc, t->sentinel);
+        t->npad = t->ldv; t->krylovdim = kd; t->cycles = 0; t->ell_w = 0; t->overflow_rows = 0;
+        Engine E(&o, t->n, t->nev);
+        E.set_resid(t->resid);
+        E.S.test_operator_cycles(*t);
+        return 0;
+    });
+}
+
+int64_t proxsdp_host_block1_lds_doubles(int32_t nt, int32_t fop, int64_t xN, int32_t ell_w_lds) {
+    if (nt < 1 || nt > proxsdp::dev::B1_MAXNT || xN < 0 || ell_w_lds < 0 || ell_w_lds > 32) return -1;
+    return proxsdp::dev::b1_lds_plan(nt, nt * proxsdp::dev::TILE, fop != 0, xN, ell_w_lds).total;
+}
+
 int proxsdp_hip_sign_unpack(const double* packed, int64_t n, double sentinel, double* A, double* sc) {
     return guarded([&]() -> int {
         if (!packed || !A || !sc || n < 1 || n > 4096) throw std::invalid_argument("invalid argument");

@@ -194,6 +194,7 @@ inline void Solver::launch_block1(EigWork& W, const double* xp, int kfirst, int 
         ell_lds = (size_t)Le.total * sizeof(double) <= (size_t)block1_lds_cap;
     }
     a.ell_in_lds = ell_lds ? 1 : 0;
+    W.b1_ell_in_lds = ell_lds;
     a.arrow = W.arrow_p;
     a.alphas = W.alphas_p; a.betas = W.betas_p; a.ctl = W.ctl_p;
     a.dbg = b1_dbg.p;

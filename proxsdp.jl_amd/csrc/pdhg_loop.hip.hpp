@@ -894,6 +894,76 @@ inline bool Solver::support_path_wanted(size_t ns) const {
     if (opt.support_path < 0 && (8 * (int64_t)ns > P.n || P.n < 4096)) return false;   // auto: only when it pays
     return true;
 }
+// One PSD block's share of setup_support: the support entries supp[s0 .. s1) that lie in block B as a symmetric sparse matrix in
+// ELL form (at most 32 entries a row, the rest of a hub row in the overflow list), and the operator form's workspaces.  W.fop_ok
+// says whether the block takes the operator form (not with hub rows under the auto rule below).  The entries' indices into the
+// support-value array are those of the whole list.
+inline void Solver::build_block_operator(EigWork& W, const BlockInfo& B, const std::vector<int>& supp, size_t s0, size_t s1) {
+    std::vector<int> cnt(W.npad, 0);
+    std::vector<std::array<int, 3>> ent;                 // row, col, s
+    ent.reserve(2 * (s1 - s0));
+    for (size_t sidx = s0; sidx < s1; ++sidx) {
+        const int64_t k = supp[sidx] - B.off;
+        int64_t j = (int64_t)((std::sqrt(8.0 * (double)k + 1.0) - 1.0) / 2.0);
+        while ((j + 1) * (j + 2) / 2 <= k) ++j;
+        while (j * (j + 1) / 2 > k) --j;
+        const int i = (int)(k - j * (j + 1) / 2);
+        ent.push_back({i, (int)j, (int)sidx}); cnt[i]++;
+        if (i != (int)j) { ent.push_back({(int)j, i, (int)sidx}); cnt[j]++; }
+    }
+    int wmax = 1;
+    for (int c : cnt) wmax = std::max(wmax, c);
+    // ELL part of at most 32 entries per row; the rest of a wider (hub) row goes to an
+    // overflow list that the row's workgroup reduces cooperatively
+    const int w = std::min(wmax, 32);
+    // measured (tools/gpurun_opcmp.py): below n ~ 2000 the two operators cost the same
+    // (latency-bound), and a hub row costs the operator form ~15 us per mat-vec at
+    // n = 1000 (maxG51) -- more than streaming a packed triangle of up to ~100 MB.  With
+    // hub rows the operator form is therefore only taken for large blocks.
+    if (wmax > w && B.n < 6000 && opt.lanczos_operator < 0) return;
+    std::vector<int> col((size_t)w * W.npad), sx((size_t)w * W.npad, -1);
+    for (int k = 0; k < w; ++k) for (int i = 0; i < W.npad; ++i) col[(size_t)k * W.npad + i] = i;
+    std::vector<std::vector<std::array<int, 2>>> over(W.npad);
+    std::fill(cnt.begin(), cnt.end(), 0);
+    for (const auto& e : ent) {
+        const int kk = cnt[e[0]]++;
+        if (kk < w) { const size_t at = (size_t)kk * W.npad + e[0]; col[at] = e[1]; sx[at] = e[2]; }
+        else over[e[0]].push_back({e[1], e[2]});
+    }
+    W.ell_w = w;
+    W.ell_col.alloc(col.size()); W.ell_sidx.alloc(sx.size());
+    W.ell_col.upload(col.data(), col.size(), stream); W.ell_sidx.upload(sx.data(), sx.size(), stream);
+    W.ov = dev::EllOverflow{};
+    if (wmax > w) {
+        std::vector<int> wptr(W.nt + 1, 0), wrow, wlo, whi, ocol, osx;
+        for (int g = 0; g < W.nt; ++g) {
+            for (int rl = 0; rl < dev::LZ_ROWS; ++rl) {
+                const int row = g * dev::LZ_ROWS + rl;
+                if (row >= W.npad || over[row].empty()) continue;
+                wrow.push_back(rl); wlo.push_back((int)ocol.size());
+                for (const auto& e : over[row]) { ocol.push_back(e[0]); osx.push_back(e[1]); }
+                whi.push_back((int)ocol.size());
+            }
+            wptr[g + 1] = (int)wrow.size();
+        }
+        W.wr_ptr.alloc(wptr.size()); W.wr_row.alloc(wrow.size()); W.wr_lo.alloc(wlo.size()); W.wr_hi.alloc(whi.size());
+        W.ov_col.alloc(ocol.size()); W.ov_sidx.alloc(osx.size());
+        W.wr_ptr.upload(wptr.data(), wptr.size(), stream); W.wr_row.upload(wrow.data(), wrow.size(), stream);
+        W.wr_lo.upload(wlo.data(), wlo.size(), stream); W.wr_hi.upload(whi.data(), whi.size(), stream);
+        W.ov_col.upload(ocol.data(), ocol.size(), stream); W.ov_sidx.upload(osx.data(), osx.size(), stream);
+        W.ov = dev::EllOverflow{W.wr_ptr.p, W.wr_row.p, W.wr_lo.p, W.wr_hi.p, W.ov_col.p, W.ov_sidx.p};
+        PX_HIP(hipStreamSynchronize(stream));             // host vectors go out of scope
+    }
+    W.F.alloc((size_t)W.npad * W.cap); W.F.zero(stream);
+    W.Flam.alloc(std::max(W.n, dev::MAXK)); W.Flam.zero(stream);
+    W.tpart.alloc((size_t)dev::MAXK * W.pld); W.tpart.zero(stream);
+    W.tred.alloc(dev::RLD); W.tred.zero(stream);
+    W.ebuf.alloc(W.npad); W.ebuf.zero(stream);
+    W.apartf.alloc(W.pld); W.apartf.zero(stream);
+    W.warm_part.alloc(ceil_div(W.npad, dev::TPB)); W.warm_part.zero(stream);
+    PX_HIP(hipStreamSynchronize(stream));                 // host vectors go out of scope
+    W.fop_ok = true;
+}
 inline void Solver::setup_support() {
     use_support = false;
     const std::vector<int> supp = support_list();
@@ -921,71 +991,8 @@ inline void Solver::setup_support() {
             size_t s1 = s0;
             while (s1 < supp.size() && supp[s1] < B.off + B.N) ++s1;     // supp is ascending
             if (B.n < 2 || W.npad == 0) { s0 = s1; continue; }
-            std::vector<int> cnt(W.npad, 0);
-            std::vector<std::array<int, 3>> ent;                 // row, col, s
-            ent.reserve(2 * (s1 - s0));
-            for (size_t sidx = s0; sidx < s1; ++sidx) {
-                const int64_t k = supp[sidx] - B.off;
-                int64_t j = (int64_t)((std::sqrt(8.0 * (double)k + 1.0) - 1.0) / 2.0);
-                while ((j + 1) * (j + 2) / 2 <= k) ++j;
-                while (j * (j + 1) / 2 > k) --j;
-                const int i = (int)(k - j * (j + 1) / 2);
-                ent.push_back({i, (int)j, (int)sidx}); cnt[i]++;
-                if (i != (int)j) { ent.push_back({(int)j, i, (int)sidx}); cnt[j]++; }
-            }
+            build_block_operator(W, B, supp, s0, s1);
             s0 = s1;
-            int wmax = 1;
-            for (int c : cnt) wmax = std::max(wmax, c);
-            // ELL part of at most 32 entries per row; the rest of a wider (hub) row goes to an
-            // overflow list that the row's workgroup reduces cooperatively
-            const int w = std::min(wmax, 32);
-            // measured (tools/gpurun_opcmp.py): below n ~ 2000 the two operators cost the same
-            // (latency-bound), and a hub row costs the operator form ~15 us per mat-vec at
-            // n = 1000 (maxG51) -- more than streaming a packed triangle of up to ~100 MB.  With
-            // hub rows the operator form is therefore only taken for large blocks.
-            if (wmax > w && B.n < 6000 && opt.lanczos_operator < 0) continue;
-            std::vector<int> col((size_t)w * W.npad), sx((size_t)w * W.npad, -1);
-            for (int k = 0; k < w; ++k) for (int i = 0; i < W.npad; ++i) col[(size_t)k * W.npad + i] = i;
-            std::vector<std::vector<std::array<int, 2>>> over(W.npad);
-            std::fill(cnt.begin(), cnt.end(), 0);
-            for (const auto& e : ent) {
-                const int kk = cnt[e[0]]++;
-                if (kk < w) { const size_t at = (size_t)kk * W.npad + e[0]; col[at] = e[1]; sx[at] = e[2]; }
-                else over[e[0]].push_back({e[1], e[2]});
-            }
-            W.ell_w = w;
-            W.ell_col.alloc(col.size()); W.ell_sidx.alloc(sx.size());
-            W.ell_col.upload(col.data(), col.size(), stream); W.ell_sidx.upload(sx.data(), sx.size(), stream);
-            W.ov = dev::EllOverflow{};
-            if (wmax > w) {
-                std::vector<int> wptr(W.nt + 1, 0), wrow, wlo, whi, ocol, osx;
-                for (int g = 0; g < W.nt; ++g) {
-                    for (int rl = 0; rl < dev::LZ_ROWS; ++rl) {
-                        const int row = g * dev::LZ_ROWS + rl;
-                        if (row >= W.npad || over[row].empty()) continue;
-                        wrow.push_back(rl); wlo.push_back((int)ocol.size());
-                        for (const auto& e : over[row]) { ocol.push_back(e[0]); osx.push_back(e[1]); }
-                        whi.push_back((int)ocol.size());
-                    }
-                    wptr[g + 1] = (int)wrow.size();
-                }
-                W.wr_ptr.alloc(wptr.size()); W.wr_row.alloc(wrow.size()); W.wr_lo.alloc(wlo.size()); W.wr_hi.alloc(whi.size());
-                W.ov_col.alloc(ocol.size()); W.ov_sidx.alloc(osx.size());
-                W.wr_ptr.upload(wptr.data(), wptr.size(), stream); W.wr_row.upload(wrow.data(), wrow.size(), stream);
-                W.wr_lo.upload(wlo.data(), wlo.size(), stream); W.wr_hi.upload(whi.data(), whi.size(), stream);
-                W.ov_col.upload(ocol.data(), ocol.size(), stream); W.ov_sidx.upload(osx.data(), osx.size(), stream);
-                W.ov = dev::EllOverflow{W.wr_ptr.p, W.wr_row.p, W.wr_lo.p, W.wr_hi.p, W.ov_col.p, W.ov_sidx.p};
-                PX_HIP(hipStreamSynchronize(stream));             // host vectors go out of scope
-            }
-            W.F.alloc((size_t)W.npad * W.cap); W.F.zero(stream);
-            W.Flam.alloc(std::max(W.n, dev::MAXK)); W.Flam.zero(stream);
-            W.tpart.alloc((size_t)dev::MAXK * W.pld); W.tpart.zero(stream);
-            W.tred.alloc(dev::RLD); W.tred.zero(stream);
-            W.ebuf.alloc(W.npad); W.ebuf.zero(stream);
-            W.apartf.alloc(W.pld); W.apartf.zero(stream);
-            W.warm_part.alloc(ceil_div(W.npad, dev::TPB)); W.warm_part.zero(stream);
-            PX_HIP(hipStreamSynchronize(stream));                 // host vectors go out of scope
-            W.fop_ok = true;
         }
     }
     PX_HIP(hipStreamSynchronize(stream));

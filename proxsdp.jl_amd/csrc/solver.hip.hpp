@@ -379,6 +379,7 @@ struct EigWork : EigSolveState {
     DevBuf<int> wr_ptr, wr_row, wr_lo, wr_hi, ov_col, ov_sidx;   // entries beyond the ELL width (hub rows)
     dev::EllOverflow ov{};
     int ell_w = 0;
+    bool b1_ell_in_lds = false;                    // the last k_lz_block1 launch on the operator form held E in LDS (launch_block1)
     bool fop_ok = false;                           // structures built (support path, narrow rows)
     // the previous projection's factors (valid while have_factors, or use_fop for the projection in progress)
     struct Factors { const double* V; const double* lam; int r; };
@@ -706,6 +707,8 @@ public:
     void test_rotate(proxsdp_rotation& t);
     void test_tail_copy(proxsdp_tail_copy& t);
     void test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double* xp);
+    void test_operator_cycles(proxsdp_operator_cycles& t);
+    void test_observed_run(const struct LzCycleSink& out, const double* xp);
     void launch_tail_copy(const double* xin, double* xout);
     void test_sign_unpack(const double* packed, double sentinel, double* A, double* sc);
 
@@ -825,6 +828,7 @@ private:
     void dense_pairs_to_block(int idx, const double* xp_in, double* xp_out, bool fuse, int npos);
     struct ShadowBookkeeping;
     bool matches_shadow(EigWork& W, const double* xo);
+    void build_block_operator(EigWork& W, const BlockInfo& B, const std::vector<int>& supp, size_t s0, size_t s1);
     void setup_support();
     void setup_dense();
     std::vector<int> support_list() const;

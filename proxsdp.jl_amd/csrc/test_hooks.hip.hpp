@@ -324,11 +324,21 @@ inline void Solver::test_rotate(proxsdp_rotation& t) {
     t.launches = W.rot_launches;
 }
 
-// Every cycle of ONE run of Solver::lanczos on the packed block xp (include/proxsdp_hip.h proxsdp_lanczos_cycles): the driver's
+// Where the per-cycle observer of a captured Lanczos run writes (the arrays of proxsdp_lanczos_cycles or proxsdp_operator_cycles,
+// prefilled by the capi entry), and `more`: what an entry reports on top of info[0 .. 9]
+struct LzCycleSink {
+    int nev, max_cycles, cols, ldv, info_ld;
+    double sentinel;
+    int32_t* info; double* V; double* alphas; double* betas; double* D; double* f;
+    int32_t* cycles;
+    std::function<void(EigWork&, LzRun&, int32_t*)> more;
+};
+
+// Every cycle of ONE run of Solver::lanczos (include/proxsdp_hip.h proxsdp_lanczos_cycles, proxsdp_operator_cycles): the driver's
 // observer copies out what the cycle left -- the whole basis buffer, the record's coefficients, the arrow part in R.T and what
 // the plan and the restart before it decided -- and the driver itself ends the run after max_cycles (the options' maxiter).
 // eig[0] was sized for the run's Krylov dimension; the capi entry prefilled the caller's arrays.
-inline void Solver::test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double* xp) {
+inline void Solver::test_observed_run(const LzCycleSink& t, const double* xp) {
     EigWork& W0 = eig[0];
     const int cols = t.cols, npad = W0.npad;
     if (npad != t.ldv || cols > W0.cap || krylov_dim(t.nev) + 1 != cols) throw std::logic_error("lanczos cycles: the workspace is not the one asked for");
@@ -341,7 +351,7 @@ inline void Solver::test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double*
         const LzRecord rec(R.plan.rec.host, R.plan.rec.ld);
         const int kfirst = R.kfirst, Kend = rec.ctl.stop ? rec.ctl.kstop : R.krylovdim;
         if (Kend < kfirst || Kend > R.krylovdim) throw std::logic_error("lanczos cycles: kstop outside the cycle");
-        int32_t* info = t.info + (size_t)PROXSDP_LZ_INFO * c;
+        int32_t* info = t.info + (size_t)t.info_ld * c;
         info[0] = kfirst; info[1] = Kend; info[2] = rec.ctl.stop;
         info[3] = R.plan.engine == LzEngine::wide ? PROXSDP_LZ_ENGINE_WIDE
                 : R.plan.engine == LzEngine::block1 ? PROXSDP_LZ_ENGINE_BLOCK1 : PROXSDP_LZ_ENGINE_STEP;
@@ -373,13 +383,81 @@ inline void Solver::test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double*
             for (size_t q = 0; q < again_h.size(); ++q) differ += std::memcmp(&again_h[q], &snap[q], sizeof(double)) != 0;
             info[8] = 1; info[9] = differ;
         }
-        t.cycles = ++c;
+        if (t.more) t.more(W, R, info);
+        *t.cycles = ++c;
     };
     lz_observer = &observe;
     try { lanczos(W0, xp, t.nev); } catch (...) { lz_observer = nullptr; throw; }
     lz_observer = nullptr;
     PX_HIP(hipStreamSynchronize(stream));
     PX_HIP(hipGetLastError());
+}
+inline void Solver::test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double* xp) {
+    test_observed_run(LzCycleSink{t.nev, t.max_cycles, t.cols, t.ldv, PROXSDP_LZ_INFO, t.sentinel, t.info, t.V, t.alphas, t.betas,
+                                  t.D, t.f, &t.cycles, nullptr}, xp);
+}
+
+// The same run on the OPERATOR FORM (include/proxsdp_hip.h proxsdp_operator_cycles): the block is never given densely.  The
+// support list goes through build_block_operator -- setup_support's own ELL / overflow construction --, its values into the
+// support-value array, the factors where ritz_pairs_to_block leaves them (W.F from column F_first on, W.Flam), and the block is
+// armed as project_block arms it.  The capi entry validated every index, rank and value.
+inline void Solver::test_operator_cycles(proxsdp_operator_cycles& t) {
+    EigWork& W = eig[0];
+    const int n = W.n, npad = W.npad, rp = t.rp;
+    ns = (int)t.ns;
+    const std::vector<int> supp(t.support, t.support + ns);
+    esv_d.alloc((size_t)2 * std::max(ns, 1)); esv_d.zero(stream);
+    if (ns > 0) esv_d.upload(t.esv, (size_t)2 * ns, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    P.blocks.assign(1, BlockInfo{n, W.N, 0});
+    use_support = true;
+    build_block_operator(W, P.blocks[0], supp, 0, supp.size());
+    if (!W.fop_ok) throw std::invalid_argument("operator cycles: a row wider than 32 entries needs lanczos_operator = 1 below side 6000");
+    t.ell_w = W.ell_w;
+    t.overflow_rows = W.ov.wr_ptr != nullptr ? (int32_t)W.wr_row.n : 0;
+    if (t.f_first + rp > W.cap) { W.F.alloc((size_t)npad * (t.f_first + rp)); W.F.zero(stream); }
+    if (rp > 0) {
+        std::vector<double> h((size_t)npad * rp, 0.0);
+        for (int j = 0; j < rp; ++j) std::copy(t.F + (size_t)j * n, t.F + (size_t)j * n + n, h.begin() + (size_t)j * npad);
+        PX_HIP(hipMemcpyAsync(W.F.p + (size_t)t.f_first * npad, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        W.Flam.upload(t.lam, rp, stream);
+        PX_HIP(hipStreamSynchronize(stream));                 // host vectors go out of scope
+    }
+    W.have_factors = t.no_factors == 0; W.xprev.sparse = t.no_factors != 0;
+    W.F_first = t.f_first; W.F_r = rp;
+    if (!fop_eligible(W, true)) throw std::logic_error("operator cycles: the block is not eligible for the operator form");
+    W.use_fop = true;
+    arm_fop(W);
+    if (t.probe_v) {
+        // ONE mat-vec launch on the records form, outside any run: E v, the records of Vp'v and the shares of v'Ev
+        std::vector<double> h(npad, 0.0);
+        std::copy(t.probe_v, t.probe_v + n, h.begin());
+        DevBuf<double> vd(npad);
+        vd.upload(h.data(), npad, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+        W.lzrun.plan.fop_owner = false;
+        launch_symv(W, nullptr, vd.p, false, nullptr);
+        PX_HIP(hipGetLastError());
+        W.ebuf.download(t.probe_ev, npad, stream);
+        W.tpart.download(t.probe_tpart, (size_t)W.nt * dev::RLD, stream);
+        W.apartf.download(t.probe_apart, W.nt, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+    }
+    long long launches = W.lst.symv_launches;
+    LzCycleSink out{t.nev, t.max_cycles, t.cols, t.ldv, PROXSDP_OP_INFO, t.sentinel, t.info, t.V, t.alphas, t.betas, t.D, t.f, &t.cycles, nullptr};
+    out.more = [&](EigWork& Wc, LzRun& R, int32_t* info) {
+        // (the mat-vecs counted for this cycle, a speculated one where it is used: each is a k_fop / k_fop_finish launch or a
+        // step of k_lz_block1<., true> while use_fop is set)
+        info[10] = Wc.use_fop ? (int32_t)(Wc.lst.symv_launches - launches) : 0;
+        launches = Wc.lst.symv_launches;
+        info[11] = lz_fop_owner(Wc) ? 1 : 0;
+        info[12] = !Wc.use_fop ? 0 : Wc.F_r <= 64 ? 1 : 2;
+        info[13] = Wc.ell_w;
+        info[14] = t.overflow_rows;
+        info[15] = R.plan.engine == LzEngine::block1 ? (Wc.b1_ell_in_lds ? 1 : 0) : -1;
+    };
+    try { test_observed_run(out, nullptr); } catch (...) { W.use_fop = false; throw; }
+    W.use_fop = false;
 }
 
 // The support path's copy of the non-PSD tail x[start .. N) (include/proxsdp_hip.h proxsdp_tail_copy) through launch_tail_copy,

@@ -9,7 +9,10 @@ Gram-Schmidt passes they predict, these must form a Krylov-Schur decomposition
 
 with V orthonormal and the coefficients the Rayleigh quotients of their columns.  `quantities` measures that in long double;
 `reference_cycle` is the textbook fp64 form (two measured classical Gram-Schmidt passes per step) whose own values, for the
-same inputs, are the yardstick: bound = MARGIN x max(reference, 2^-52)."""
+same inputs, are the yardstick: bound = MARGIN x max(reference, 2^-52).
+
+Where these take a dense A they also take an OPERATOR (operator_cycle_cases.Operator: a matrix known by its pieces, so that
+n > 4096 needs no dense matrix): an object with `shape`, `A @ v` in plain fp64 and `times_ld(V)` = A V in long double."""
 import functools
 import math
 
@@ -215,7 +218,9 @@ def times_a(A, V, reuse=None, chunk=512):
         same = [j for j in range(min(K, Vo.shape[1], AVo.shape[1])) if np.array_equal(V[:, j], Vo[:, j])]
         out[:, same] = AVo[:, same]
         todo = [j for j in range(K) if j not in set(same)]
-    if todo:
+    if todo and hasattr(A, "times_ld"):
+        out[:, todo] = A.times_ld(V[:, todo])
+    elif todo:
         Vl = V[:, todo].astype(LD)
         for r0 in range(0, n, chunk):
             out[r0:r0 + chunk, todo] = A[r0:r0 + chunk].astype(LD) @ Vl

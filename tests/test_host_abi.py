@@ -24,7 +24,8 @@ from kat_problems import KATS, sdp_wiki
 def test_library_loads_and_exports_every_declared_symbol():
     L = B.lib()
     names = B.header_symbols()
-    assert len(names) >= 35 and {"proxsdp_hip_sym_product", "proxsdp_hip_sign_unpack", "proxsdp_hip_project_cones"} <= set(names)
+    assert len(names) >= 35 and {"proxsdp_hip_sym_product", "proxsdp_hip_sign_unpack", "proxsdp_hip_project_cones",
+                                 "proxsdp_hip_operator_cycles", "proxsdp_host_block1_lds_doubles"} <= set(names)
     for name in names:
         assert hasattr(L, name), f"{name} declared in include/proxsdp_hip.h but not exported"
     assert L.proxsdp_hip_abi_version() == 10

@@ -12,8 +12,8 @@ fp64 reference (two measured Gram-Schmidt passes, lanczos_cycle_cases.reference_
 with the floor 8 x 2^-52.  Exact hand-over checks:
 padding rows, the start column, v_kfirst = the previous cycle's v_K bit for bit, the kept columns inside the previous span.
 
-Out of scope: lanczos_eager, lanczos_batch and the operator form (k_fop*, k_lz_orth<., 1 | 2>): bit-for-bit tests tie the
-batched path to the per-block one, and the operator form needs a support layout, i.e. a hook of its own.
+Out of scope: lanczos_eager and lanczos_batch: bit-for-bit tests tie the batched path to the per-block one.  The operator form
+(k_fop*, k_lz_orth<., 1 | 2>, k_lz_block1<., true>) has a hook of its own, held to the same rule: test_operator_cycles.py.
 
 The kept columns: after a restart on the step or wide engine the entry repeats the restart rotation (Solver::rotate_launch on
 the previous basis and the coefficients still on the device) into a buffer of its own and counts the entries of the columns
