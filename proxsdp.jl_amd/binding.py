@@ -1018,9 +1018,10 @@ def _rows_arguments(add, drop, n, index_base=0):
     return d, _host_index(ptr), _host_index(cols) + index_base, vals, h_new
 
 
-def _rows_struct(d, ptr, cols, vals, h_new, keep):
-    """proxsdp_model_rows over HOST arrays (vals, h_new float64 NumPy or None); keep collects what it points to"""
-    R = ModelRows()
+def _rows_struct(d, ptr, cols, vals, h_new, keep, R=None):
+    """proxsdp_model_rows over HOST arrays (vals, h_new float64 NumPy, or None: R holds them already); keep collects what it
+    points to"""
+    R = ModelRows() if R is None else R
     R.struct_size = C.sizeof(ModelRows)
     if d is not None and len(d):
         keep.append(d)
@@ -1117,14 +1118,30 @@ class TriangleCuts:
         return len(self.patterns)
 
 
-def _triangle_struct(count, min_violation, rhs, cand_cap, sentinel=None):
-    """proxsdp_triangle_cuts with output arrays for `count` rows (prefilled with `sentinel` when given), and the arrays"""
-    n = max(int(count), 1) if -(1 << 40) < int(count) < (1 << 24) else 1      # (an absurd count is the library's to refuse)
-    arr = dict(tri=np.zeros(3 * n, dtype=np.int64), pattern=np.zeros(n, dtype=np.int32), violation=np.zeros(n),
-               add_col=np.zeros(3 * n, dtype=np.int64), add_val=np.zeros(3 * n), add_h=np.zeros(n))
+def _prefilled(arr, sentinel):
+    """the output arrays of a tool call, every entry `sentinel` when one is given: what the library leaves alone shows"""
     if sentinel is not None:
         for a in arr.values():
             a[:] = sentinel
+    return arr
+
+
+def _dense_cone_arguments(who, X, cone_idx):
+    """(X, idx) of a host separation: the square float64 matrix and the cone's variable list (None: the library's own)"""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != X.shape[1]:
+        raise ValueError(f"{who}: X must be square")
+    idx = None if cone_idx is None else _i(cone_idx)
+    if idx is not None and len(idx) != X.shape[0] * (X.shape[0] + 1) // 2:
+        raise ValueError(f"{who}: cone_idx must list the upper triangle")
+    return X, idx
+
+
+def _triangle_struct(count, min_violation, rhs, cand_cap, sentinel=None):
+    """proxsdp_triangle_cuts with output arrays for `count` rows (prefilled with `sentinel` when given), and the arrays"""
+    n = max(int(count), 1) if -(1 << 40) < int(count) < (1 << 24) else 1      # (an absurd count is the library's to refuse)
+    arr = _prefilled(dict(tri=np.zeros(3 * n, dtype=np.int64), pattern=np.zeros(n, dtype=np.int32), violation=np.zeros(n),
+                          add_col=np.zeros(3 * n, dtype=np.int64), add_val=np.zeros(3 * n), add_h=np.zeros(n)), sentinel)
     T = TriangleCutsIO()
     T.struct_size = C.sizeof(TriangleCutsIO)
     T.count, T.min_violation, T.rhs, T.cand_cap = int(count), float(min_violation), float(rhs), int(cand_cap)
@@ -1139,13 +1156,8 @@ def host_triangle_cuts(X, count=1000, min_violation=1e-3, rhs=1.0, cone_idx=None
     X: the symmetric side x side matrix; cone_idx: the cone's variable list as add_col shall report it (None: tri_index +
     index_base).  Returns a TriangleCuts; its `arrays` are the output arrays at full length (entries past the rows returned
     keep `sentinel`)."""
-    X = np.ascontiguousarray(X, dtype=np.float64)
-    if X.ndim != 2 or X.shape[0] != X.shape[1]:
-        raise ValueError("host_triangle_cuts: X must be square")
+    X, idx = _dense_cone_arguments("host_triangle_cuts", X, cone_idx)
     T, arr = _triangle_struct(count, min_violation, rhs, 0, sentinel)
-    idx = None if cone_idx is None else _i(cone_idx)
-    if idx is not None and len(idx) != X.shape[0] * (X.shape[0] + 1) // 2:
-        raise ValueError("host_triangle_cuts: cone_idx must list the upper triangle")
     _check(lib().proxsdp_host_triangle_cuts(_p(X if X.size else np.zeros(1)), X.shape[0], None if idx is None else _p(idx, pi64),
                                             int(index_base), C.byref(T)))
     return TriangleCuts(T, arr, index_base)
@@ -1206,12 +1218,9 @@ def _clique_struct(nodes, signs, min_violation, rhs, knobs=None, sentinel=None):
     nb, q = nodes.shape
     n, k = max(nb, 1), q + 2
     npair = k * (k - 1) // 2
-    arr = dict(nodes=np.zeros(k * n, dtype=np.int64), signs=np.zeros(k * n, dtype=np.int8), violation=np.zeros(n),
-               from_base=np.zeros(n, dtype=np.int64), add_col=np.zeros(npair * n, dtype=np.int64),
-               add_val=np.zeros(npair * n), add_h=np.zeros(n))
-    if sentinel is not None:
-        for a in arr.values():
-            a[:] = sentinel
+    arr = _prefilled(dict(nodes=np.zeros(k * n, dtype=np.int64), signs=np.zeros(k * n, dtype=np.int8), violation=np.zeros(n),
+                          from_base=np.zeros(n, dtype=np.int64), add_col=np.zeros(npair * n, dtype=np.int64),
+                          add_val=np.zeros(npair * n), add_h=np.zeros(n)), sentinel)
     Q = CliqueCutsIO()
     Q.struct_size = C.sizeof(CliqueCutsIO)
     Q.base_size, Q.n_base = int(q), int(nb)
@@ -1238,14 +1247,9 @@ def host_clique_cuts(X, bases, min_violation=1e-3, rhs=None, cone_idx=None, inde
     symmetric side x side matrix; bases: as Model.separate_cliques takes them; cone_idx: the cone's variable list as add_col
     shall report it (None: tri_index + index_base).  Returns a CliqueCuts; its `arrays` are the output arrays at full length
     (entries past the rows returned keep `sentinel`)."""
-    X = np.ascontiguousarray(X, dtype=np.float64)
-    if X.ndim != 2 or X.shape[0] != X.shape[1]:
-        raise ValueError("host_clique_cuts: X must be square")
+    X, idx = _dense_cone_arguments("host_clique_cuts", X, cone_idx)
     nodes, signs = _clique_bases(bases)
     Q, arr = _clique_struct(nodes, signs, min_violation, rhs, None, sentinel)
-    idx = None if cone_idx is None else _i(cone_idx)
-    if idx is not None and len(idx) != X.shape[0] * (X.shape[0] + 1) // 2:
-        raise ValueError("host_clique_cuts: cone_idx must list the upper triangle")
     _check(lib().proxsdp_host_clique_cuts(_p(X if X.size else np.zeros(1)), X.shape[0], None if idx is None else _p(idx, pi64),
                                           int(index_base), C.byref(Q)))
     return CliqueCuts(Q, arr, index_base)
@@ -1284,9 +1288,7 @@ def _rounding_struct(side, r, trials, seed, max_sweeps, knobs=None, adj_cap=None
         cap = max(int(adj_cap), 1)
         arr.update(adj_ptr=np.zeros(s + 1, dtype=np.int64), adj_col=np.zeros(cap, dtype=np.int64), adj_val=np.zeros(cap),
                    diag=np.zeros(s))
-    if sentinel is not None:
-        for a in arr.values():
-            a[:] = sentinel
+    _prefilled(arr, sentinel)
     Q = RoundingIO()
     Q.struct_size = C.sizeof(RoundingIO)
     Q.r, Q.trials, Q.seed, Q.max_sweeps = int(r), int(trials), int(seed), int(max_sweeps)
@@ -1356,11 +1358,8 @@ class DualBound:
 def _bound_struct(n_psd, trace_cap=None, sentinel=None):
     """proxsdp_dual_bound with output arrays for n_psd cones (prefilled with `sentinel` when given), and the arrays"""
     k = max(int(n_psd), 1)
-    arr = dict(shift=np.zeros(k), lambda_lower=np.zeros(k), radius=np.zeros(k), delta=np.zeros(k), trace_used=np.zeros(k),
-               factorisations=np.zeros(k, dtype=np.int32), certified=np.zeros(k, dtype=np.int32))
-    if sentinel is not None:
-        for a in arr.values():
-            a[:] = sentinel
+    arr = _prefilled(dict(shift=np.zeros(k), lambda_lower=np.zeros(k), radius=np.zeros(k), delta=np.zeros(k), trace_used=np.zeros(k),
+                          factorisations=np.zeros(k, dtype=np.int32), certified=np.zeros(k, dtype=np.int32)), sentinel)
     Q = DualBoundIO()
     Q.struct_size = C.sizeof(DualBoundIO)
     for name in ("shift", "lambda_lower", "radius", "delta", "trace_used"):
@@ -1479,42 +1478,51 @@ class Model:
             raise ValueError("the model is closed")
         return self._h
 
+    def _route(self, who, S, fields, short=None):
+        """The host-or-device marshalling of a call.  fields: {field of the struct S: (value, entries, label)}, each value a
+        NumPy array (a CPU tensor counts as one) or a CUDA float64 tensor.  All CUDA tensors: the device route -- S.on_device
+        = 1, the tensors' own addresses, one synchronize (the library runs on its own stream).  Otherwise the host route:
+        contiguous float64 arrays, one zero in place of an empty one (any non-NULL address).  A mixture is a ValueError, and
+        so is a wrong length (`short`: the text of that refusal where the call names its fields together).  Returns
+        (on_device, keep); keep holds what S points to and has to outlive the call."""
+        on_dev = [_is_tensor(v) and v.is_cuda for v, _, _ in fields.values()]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError(f"{who}: host arrays and CUDA tensors cannot be mixed in one call")
+        if fields and all(on_dev):
+            import torch
+            dev_id = int(self._options.device_id)
+            S.on_device = 1
+            for k, (v, ln, what) in fields.items():
+                setattr(S, k, _device_ptr(v, ln, dev_id, what))
+            torch.cuda.synchronize(dev_id)
+            return True, [v for v, _, _ in fields.values()]
+        keep = []
+        for k, (v, ln, what) in fields.items():
+            a = _f(v.numpy() if _is_tensor(v) else v).ravel()
+            if len(a) != ln:
+                raise ValueError(f"{who}: " + (short or f"{what} must have {ln} entries"))
+            keep.append(a if len(a) else np.zeros(1))
+            setattr(S, k, _p(keep[-1]))
+        return False, keep
+
     # ---- data
     def update(self, c=None, b=None, h=None, A_values=None, G_values=None):
         """Replace data of the same shape: c (n), b (p), h (m) in the caller's order; A_values / G_values = the stored entries
         of A / G in sorted CSC order (scipy's .data after sort_indices), or a sparse matrix with the pattern the model was
         built with.  NumPy arrays go the host route, CUDA float64 tensors the device route (proxsdp_model_data.on_device);
         mixing the two in one call is a ValueError."""
-        given = dict(c=(c, self.n), b=(b, self.p), h=(h, self.m), A_nzval=(A_values, self._nnz[0]),
-                     G_nzval=(G_values, self._nnz[1]))
-        given = {k: v for k, v in given.items() if v[0] is not None}
-        on_dev = [_is_tensor(v) and v.is_cuda for v, _ in given.values()]
-        if any(on_dev) and not all(on_dev):
-            raise ValueError("Model.update: host arrays and CUDA tensors cannot be mixed in one call")
+        fields = {}
+        for k, v, ln in (("c", c, self.n), ("b", b, self.p), ("h", h, self.m), ("A_nzval", A_values, self._nnz[0]),
+                         ("G_nzval", G_values, self._nnz[1])):
+            if sp.issparse(v):
+                v = sp.csc_matrix(v, dtype=np.float64)
+                v.sort_indices()
+                v = v.data
+            if v is not None:
+                fields[k] = (v, ln, k)
         D = ModelData()
         D.struct_size = C.sizeof(ModelData)
-        keep = []
-        if given and all(on_dev):
-            import torch
-            dev_id = int(self._options.device_id)
-            D.on_device = 1
-            for k, (v, ln) in given.items():
-                setattr(D, k, _device_ptr(v, ln, dev_id, k))
-            keep = [v for v, _ in given.values()]
-            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
-        else:
-            for k, (v, ln) in given.items():
-                if _is_tensor(v):
-                    v = v.numpy()
-                if sp.issparse(v):
-                    v = sp.csc_matrix(v, dtype=np.float64)
-                    v.sort_indices()
-                    v = v.data
-                a = _f(v).ravel()
-                if len(a) != ln:
-                    raise ValueError(f"Model.update: {k} must have {ln} entries")
-                keep.append(a if len(a) else np.zeros(1))
-                setattr(D, k, _p(keep[-1]))
+        _, keep = self._route("Model.update", D, fields)
         _check(lib().proxsdp_hip_model_update(self._handle(), C.byref(D)))
         del keep
 
@@ -1526,32 +1534,13 @@ class Model:
         values / h_new as CUDA float64 tensors take the device route, NumPy arrays the host route; mixing the two is a
         ValueError.  Index arrays that arrive as tensors are copied to the host.  Returns a RowsChange; carry(prev) of it
         re-indexes a previous result's dual_in for start=."""
-        d, ptr, cols, vals, h_new = _rows_arguments(add, drop, self.n, getattr(self, "_index_base", 0))
-        k = 0 if ptr is None else len(ptr) - 1
-        on_dev = [_is_tensor(v) and v.is_cuda for v in (vals, h_new) if v is not None]
-        if any(on_dev) and not all(on_dev):
-            raise ValueError("Model.change_rows: host arrays and CUDA tensors cannot be mixed in one call")
-        keep = []
-        if k > 0 and all(on_dev):
-            import torch
-            dev_id = int(self._options.device_id)
-            R = _rows_struct(d, ptr, cols, None, None, keep)
-            R.on_device = 1
-            R.add_val = _device_ptr(vals, int(ptr[-1]), dev_id, "values")
-            R.add_h = _device_ptr(h_new, k, dev_id, "h_new")
-            keep += [vals, h_new]
-            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
-        else:
-            host = []
-            for v, ln, what in ((vals, 0 if ptr is None else int(ptr[-1]), "values"), (h_new, k, "h_new")):
-                if v is None:
-                    host.append(None)
-                    continue
-                a = _f(v.numpy() if _is_tensor(v) else v).ravel()
-                if len(a) != ln:
-                    raise ValueError(f"Model.change_rows: {what} must have {ln} entries")
-                host.append(a if len(a) else np.zeros(1))
-            R = _rows_struct(d, ptr, cols, host[0], host[1], keep)
+        d, ptr, cols, vals, h_new = _rows_arguments(add, drop, self.n)
+        fields = {}
+        if ptr is not None:
+            fields = dict(add_val=(vals, int(ptr[-1]), "values"), add_h=(h_new, len(ptr) - 1, "h_new"))
+        R = ModelRows()                                      # (the values first: what they are refused for needs no index array)
+        _, keep = self._route("Model.change_rows", R, fields)
+        _rows_struct(d, ptr, None if cols is None else cols + self._index_base, None, None, keep, R)
         kept = np.zeros(max(self.m - int(R.n_drop) + int(R.n_add), 1), dtype=np.int64)
         R.kept = _p(kept, pi64)
         _check(lib().proxsdp_hip_model_rows(self._handle(), C.byref(R)))
@@ -1571,21 +1560,10 @@ class Model:
             raise ValueError("Model.separate_triangles: the result holds no primal (solve(primal=True))")
         T, arr = _triangle_struct(count, min_violation, rhs, cand_cap)
         T.cone = int(cone)
-        if _is_tensor(primal) and primal.is_cuda:
-            import torch
-            dev_id = int(self._options.device_id)
-            T.on_device = 1
-            T.primal = _device_ptr(primal, self.n, dev_id, "primal")
-            keep = primal
-            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
-        else:
-            keep = _f(primal.numpy() if _is_tensor(primal) else primal).ravel()
-            if len(keep) != self.n:
-                raise ValueError(f"Model.separate_triangles: primal must have {self.n} entries")
-            T.primal = _p(keep if len(keep) else np.zeros(1))
+        _, keep = self._route("Model.separate_triangles", T, dict(primal=(primal, self.n, "primal")))
         _check(lib().proxsdp_hip_model_triangles(self._handle(), C.byref(T)))
         del keep
-        return TriangleCuts(T, arr, getattr(self, "_index_base", 0))
+        return TriangleCuts(T, arr, self._index_base)
 
     def separate_cliques(self, primal, bases, cone=0, min_violation=1e-3, rhs=None, knobs=None):
         """proxsdp_hip_model_cliques: every base grown by its most violated pair of further nodes and signs of PSD cone `cone`
@@ -1600,21 +1578,10 @@ class Model:
         nodes, signs = _clique_bases(bases)
         Q, arr = _clique_struct(nodes, signs, min_violation, rhs, knobs)
         Q.cone = int(cone)
-        if _is_tensor(primal) and primal.is_cuda:
-            import torch
-            dev_id = int(self._options.device_id)
-            Q.on_device = 1
-            Q.primal = _device_ptr(primal, self.n, dev_id, "primal")
-            keep = primal
-            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
-        else:
-            keep = _f(primal.numpy() if _is_tensor(primal) else primal).ravel()
-            if len(keep) != self.n:
-                raise ValueError(f"Model.separate_cliques: primal must have {self.n} entries")
-            Q.primal = _p(keep if len(keep) else np.zeros(1))
+        _, keep = self._route("Model.separate_cliques", Q, dict(primal=(primal, self.n, "primal")))
         _check(lib().proxsdp_hip_model_cliques(self._handle(), C.byref(Q)))
         del keep
-        return CliqueCuts(Q, arr, getattr(self, "_index_base", 0))
+        return CliqueCuts(Q, arr, self._index_base)
 
     def inactive_rows(self, result_or_pair, dual_tol=0.0, slack_tol=1e-6):
         """proxsdp_hip_model_inactive_rows: the inequality rows r with |dual_in[r]| <= dual_tol and slack_in[r] < -slack_tol
@@ -1624,30 +1591,16 @@ class Model:
             dual, slack = result_or_pair.dual_in, result_or_pair.slack_in
         else:
             dual, slack = result_or_pair
-        on_dev = [_is_tensor(v) and v.is_cuda for v in (dual, slack)]
-        if any(on_dev) and not all(on_dev):
-            raise ValueError("Model.inactive_rows: host arrays and CUDA tensors cannot be mixed in one call")
         Q = InactiveRowsIO()
         Q.struct_size = C.sizeof(InactiveRowsIO)
         Q.dual_tol, Q.slack_tol = float(dual_tol), float(slack_tol)
         rows = np.zeros(max(self.m, 1), dtype=np.int64)
         Q.rows = _p(rows, pi64)
-        if all(on_dev):
-            import torch
-            dev_id = int(self._options.device_id)
-            Q.on_device = 1
-            keep = [dual, slack]
-            if self.m:
-                Q.dual_in, Q.slack_in = _device_ptr(dual, self.m, dev_id, "dual_in"), _device_ptr(slack, self.m, dev_id, "slack_in")
-            else:                                            # (no row: any non-NULL address, never read)
-                Q.dual_in = Q.slack_in = _p(np.zeros(1))
-            torch.cuda.synchronize(dev_id)                   # the library runs on its own stream
-        else:
-            keep = [_f(v.numpy() if _is_tensor(v) else v).ravel() for v in (dual, slack)]
-            if any(len(a) != self.m for a in keep):
-                raise ValueError(f"Model.inactive_rows: dual_in and slack_in must have {self.m} entries")
-            keep = [a if len(a) else np.zeros(1) for a in keep]
-            Q.dual_in, Q.slack_in = _p(keep[0]), _p(keep[1])
+        on_dev, keep = self._route("Model.inactive_rows", Q, dict(dual_in=(dual, self.m, "dual_in"), slack_in=(slack, self.m, "slack_in")),
+                                   short=f"dual_in and slack_in must have {self.m} entries")
+        if on_dev and not self.m:                            # (no row: any non-NULL address, never read)
+            keep.append(np.zeros(1))
+            Q.dual_in = Q.slack_in = _p(keep[-1])
         _check(lib().proxsdp_hip_model_inactive_rows(self._handle(), C.byref(Q)))
         del keep
         return rows[:int(Q.n_rows)].copy()
@@ -1666,28 +1619,13 @@ class Model:
                 raise ValueError("Model.round: the result carries no factors (solve(factors=True))")
             factors = fl[cone][:2]
         vals, V = factors[0], factors[1]
-        on_dev = [_is_tensor(v) and v.is_cuda for v in (vals, V)]
-        if any(on_dev) and not all(on_dev):
-            raise ValueError("Model.round: host arrays and CUDA tensors cannot be mixed in one call")
         side = self._sides[cone] if 0 <= int(cone) < len(self._sides) else 1
         if len(V.shape) != 2 or V.shape[1] != len(vals) or (0 <= int(cone) < len(self._sides) and V.shape[0] != side):
-            raise ValueError("Model.round: vectors must be side x len(values)")
+            raise ValueError(f"Model.round: vectors must be side x len(values) = {side} x {len(vals)}")
         Q, arr = _rounding_struct(side, len(vals), trials, seed, max_sweeps, knobs, side * (side - 1) if adjacency else None)
         Q.cone = int(cone)
-        if all(on_dev):
-            import torch
-            dev_id = int(self._options.device_id)
-            Q.on_device = 1
-            Vt = V.t().contiguous()                                 # column-major, ld = side
-            keep = [Vt, vals]
-            Q.V = _device_ptr(Vt, Vt.numel(), dev_id, "vectors")
-            Q.values = _device_ptr(vals, len(vals), dev_id, "values")
-            torch.cuda.synchronize(dev_id)                          # the library runs on its own stream
-        else:
-            to_np = lambda v: v.numpy() if _is_tensor(v) else v
-            keep = [np.ascontiguousarray(np.asarray(to_np(V), dtype=np.float64).T).ravel(), _f(to_np(vals)).ravel()]
-            keep = [a if a.size else np.zeros(1) for a in keep]
-            Q.V, Q.values = _p(keep[0]), _p(keep[1])
+        Vt = V.t().contiguous() if _is_tensor(V) else np.asarray(V, dtype=np.float64).T     # column-major, ld = side
+        _, keep = self._route("Model.round", Q, dict(V=(Vt, V.shape[0] * V.shape[1], "vectors"), values=(vals, len(vals), "values")))
         _check(lib().proxsdp_hip_model_round(self._handle(), C.byref(Q)))
         del keep
         return Rounding(Q, arr)
@@ -1702,24 +1640,13 @@ class Model:
         if isinstance(duals, SolveResult):
             duals = (duals.dual_eq, duals.dual_in)
         ye, yi = duals
-        on_dev = [_is_tensor(v) and v.is_cuda for v in (ye, yi)]
-        if any(on_dev) and not all(on_dev):
-            raise ValueError("Model.bound: host arrays and CUDA tensors cannot be mixed in one call")
         Q, arr = _bound_struct(len(self._sides), trace_cap)
-        if all(on_dev):
-            import torch
-            dev_id = int(self._options.device_id)
-            Q.on_device = 1
-            keep = [ye, yi]
-            Q.dual_eq = _device_ptr(ye, self.p, dev_id, "dual_eq") if self.p else _p(np.zeros(1))
-            Q.dual_in = _device_ptr(yi, self.m, dev_id, "dual_in") if self.m else _p(np.zeros(1))
-            torch.cuda.synchronize(dev_id)                          # the library runs on its own stream
-        else:
-            keep = [_f(v.numpy() if _is_tensor(v) else v).ravel() for v in (ye, yi)]
-            if len(keep[0]) != self.p or len(keep[1]) != self.m:
-                raise ValueError(f"Model.bound: dual_eq and dual_in must have {self.p} and {self.m} entries")
-            keep = [a if len(a) else np.zeros(1) for a in keep]
-            Q.dual_eq, Q.dual_in = _p(keep[0]), _p(keep[1])
+        fields = dict(dual_eq=(ye, self.p, "dual_eq"), dual_in=(yi, self.m, "dual_in"))
+        on_dev, keep = self._route("Model.bound", Q, fields, short=f"dual_eq and dual_in must have {self.p} and {self.m} entries")
+        for k, (_, ln, _) in fields.items():
+            if on_dev and not ln:                            # (no row: any non-NULL address, never read)
+                keep.append(np.zeros(1))
+                setattr(Q, k, _p(keep[-1]))
         _check(lib().proxsdp_hip_model_bound(self._handle(), C.byref(Q)))
         del keep
         return DualBound(Q, arr)

@@ -14,8 +14,6 @@
 #include "test_hooks.hip.hpp"
 #include "shard_split.hpp"
 #include "model.hip.hpp"
-#include "triangle_cuts.hip.hpp"
-#include "clique_cuts.hip.hpp"
 
 namespace {
 thread_local std::string g_last_error;
@@ -379,7 +377,7 @@ int proxsdp_hip_model_destroy(proxsdp_model* mdl) {
 int proxsdp_hip_model_info(const proxsdp_model* mdl, proxsdp_model_info* info) {
     return guarded([&]() -> int {
         if (!info) throw std::invalid_argument("NULL info");
-        if (info->struct_size != (int64_t)sizeof(proxsdp_model_info)) throw std::invalid_argument("proxsdp_model_info.struct_size mismatch");
+        proxsdp::check_struct_size(info, "proxsdp_model_info");
         if (!mdl) throw std::invalid_argument("NULL handle");
         mdl->info(*info);
         return 0;
@@ -389,7 +387,7 @@ int proxsdp_hip_model_info(const proxsdp_model* mdl, proxsdp_model_info* info) {
 int proxsdp_hip_model_dump(proxsdp_model* mdl, proxsdp_model_dump* out) {
     return guarded([&]() -> int {
         if (!out) throw std::invalid_argument("NULL dump");
-        if (out->struct_size != (int64_t)sizeof(proxsdp_model_dump)) throw std::invalid_argument("proxsdp_model_dump.struct_size mismatch");
+        proxsdp::check_struct_size(out, "proxsdp_model_dump");
         if (!mdl) throw std::invalid_argument("NULL handle");
         mdl->dump(*out);
         return 0;
@@ -399,7 +397,7 @@ int proxsdp_hip_model_dump(proxsdp_model* mdl, proxsdp_model_dump* out) {
 int proxsdp_hip_model_update(proxsdp_model* mdl, const proxsdp_model_data* upd) {
     return guarded([&]() -> int {
         if (!upd) throw std::invalid_argument("NULL data");
-        if (upd->struct_size != (int64_t)sizeof(proxsdp_model_data)) throw std::invalid_argument("proxsdp_model_data.struct_size mismatch");
+        proxsdp::check_struct_size(upd, "proxsdp_model_data");
         if (upd->on_device != 0 && upd->on_device != 1) throw std::invalid_argument("proxsdp_model_data.on_device must be 0 or 1");
         if (!upd->c && !upd->b && !upd->h && !upd->A_nzval && !upd->G_nzval) throw std::invalid_argument("proxsdp_model_data: every pointer is NULL");
         if (!mdl) throw std::invalid_argument("NULL handle");
@@ -435,12 +433,9 @@ int proxsdp_hip_model_triangles(proxsdp_model* mdl, proxsdp_triangle_cuts* tc) {
     return guarded([&]() -> int {
         proxsdp::check_triangle_struct(tc, true);
         if (!mdl) throw std::invalid_argument("NULL handle");
-        const proxsdp::Prep& P = mdl->S->P;
-        if (tc->cone < 0 || tc->cone >= (int64_t)P.blocks.size()) throw std::invalid_argument("proxsdp_triangle_cuts.cone is outside the model's PSD cones");
-        const proxsdp::BlockInfo& B = P.blocks[tc->cone];
-        if (B.n < 3) throw std::invalid_argument("proxsdp_triangle_cuts: cone " + std::to_string(tc->cone) + " has side < 3");
-        PX_HIP(hipSetDevice(mdl->opt0.device_id));
-        proxsdp::device_triangle_cuts(mdl->S->stream, P.ord.data() + B.off, mdl->ord_d.p + B.off, B.n, mdl->index_base, tc->cone, *tc);
+        if (mdl->cone(tc->cone, "proxsdp_triangle_cuts").n < 3)
+            throw std::invalid_argument("proxsdp_triangle_cuts: cone " + std::to_string(tc->cone) + " has side < 3");
+        mdl->triangles(*tc);
         return 0;
     });
 }
@@ -460,14 +455,11 @@ int proxsdp_hip_model_cliques(proxsdp_model* mdl, proxsdp_clique_cuts* q) {
     return guarded([&]() -> int {
         proxsdp::check_clique_struct(q, true);
         if (!mdl) throw std::invalid_argument("NULL handle");
-        const proxsdp::Prep& P = mdl->S->P;
-        if (q->cone < 0 || q->cone >= (int64_t)P.blocks.size()) throw std::invalid_argument("proxsdp_clique_cuts.cone is outside the model's PSD cones");
-        const proxsdp::BlockInfo& B = P.blocks[q->cone];
-        if (B.n < q->base_size + 2)
+        const int64_t side = mdl->cone(q->cone, "proxsdp_clique_cuts").n;
+        if (side < q->base_size + 2)
             throw std::invalid_argument("proxsdp_clique_cuts: cone " + std::to_string(q->cone) + " has side < base_size + 2");
-        proxsdp::check_clique_bases(*q, B.n);
-        PX_HIP(hipSetDevice(mdl->opt0.device_id));
-        proxsdp::device_clique_cuts(mdl->S->stream, P.ord.data() + B.off, mdl->ord_d.p + B.off, B.n, mdl->index_base, q->cone, *q);
+        proxsdp::check_clique_bases(*q, side);
+        mdl->cliques(*q);
         return 0;
     });
 }
@@ -489,8 +481,7 @@ int proxsdp_hip_model_inactive_rows(proxsdp_model* mdl, proxsdp_inactive_rows* q
     return guarded([&]() -> int {
         proxsdp::check_inactive_struct(q);
         if (!mdl) throw std::invalid_argument("NULL handle");
-        if (q->on_device) PX_HIP(hipSetDevice(mdl->opt0.device_id));
-        proxsdp::inactive_rows(mdl->S->stream, mdl->S->P.m, *q);
+        mdl->inactive_rows(*q);
         return 0;
     });
 }
@@ -499,13 +490,10 @@ int proxsdp_hip_model_round(proxsdp_model* mdl, proxsdp_rounding* q) {
     return guarded([&]() -> int {
         proxsdp::check_rounding_struct(q, true);
         if (!mdl) throw std::invalid_argument("NULL handle");
-        proxsdp::Solver& s = *mdl->S;
-        const proxsdp::Prep& P = s.P;
-        if (q->cone < 0 || q->cone >= (int64_t)P.blocks.size()) throw std::invalid_argument("proxsdp_rounding.cone is outside the model's PSD cones");
-        const proxsdp::BlockInfo& B = P.blocks[q->cone];
+        const proxsdp::BlockInfo& B = mdl->cone(q->cone, "proxsdp_rounding");
         proxsdp::check_rounding_factors(*q, B.n, q->on_device == 0);
         // (the host mirror of the exit path's c is what the device holds: create and every update leave the two equal)
-        if (q->adj_ptr && proxsdp::round_adjacency_count(P.c_orig.data() + B.off, B.n) > q->adj_cap)
+        if (q->adj_ptr && proxsdp::round_adjacency_count(mdl->S->P.c_orig.data() + B.off, B.n) > q->adj_cap)
             throw std::invalid_argument("proxsdp_rounding.adj_cap is smaller than the adjacency");
         mdl->round(*q);
         return 0;
@@ -538,7 +526,7 @@ int proxsdp_host_round_directions(int64_t seed, int32_t r, int32_t trials, doubl
 int proxsdp_hip_model_bound(proxsdp_model* mdl, proxsdp_dual_bound* q) {
     return guarded([&]() -> int {
         if (!q) throw std::invalid_argument("NULL proxsdp_dual_bound");
-        if (q->struct_size != (int64_t)sizeof(proxsdp_dual_bound)) throw std::invalid_argument("proxsdp_dual_bound.struct_size mismatch");
+        proxsdp::check_struct_size(q, "proxsdp_dual_bound");
         if (!mdl) throw std::invalid_argument("NULL handle");
         const proxsdp::Prep& P = mdl->S->P;
         if (!P.socs.empty()) throw std::domain_error("proxsdp_hip_model_bound does not serve a model with a second-order cone");
@@ -1612,7 +1600,7 @@ int proxsdp_host_model_prepare(const proxsdp_problem* prob, proxsdp_model_dump* 
                                int32_t* csr_pos) {
     return guarded([&]() -> int {
         if (!prob || !out) throw std::invalid_argument("NULL problem or dump");
-        if (out->struct_size != (int64_t)sizeof(proxsdp_model_dump)) throw std::invalid_argument("proxsdp_model_dump.struct_size mismatch");
+        proxsdp::check_struct_size(out, "proxsdp_model_dump");
         if (is_shard(prob) || prob->M_dense) throw std::domain_error("proxsdp_host_model_prepare does not serve a shard of a block-sharded solve or M_dense");
         const proxsdp::Prep R = proxsdp::prepare(*prob, nullptr, false, true);
         std::vector<int32_t> supp;
@@ -1648,7 +1636,7 @@ int proxsdp_host_model_rows_plan(const proxsdp_problem* prob, proxsdp_model_rows
         proxsdp::check_rows_struct(ch);
         if (ch->on_device != 0) throw std::invalid_argument("proxsdp_host_model_rows_plan takes host values (on_device = 0)");
         if (!prob || !out) throw std::invalid_argument("NULL problem or dump");
-        if (out->struct_size != (int64_t)sizeof(proxsdp_model_dump)) throw std::invalid_argument("proxsdp_model_dump.struct_size mismatch");
+        proxsdp::check_struct_size(out, "proxsdp_model_dump");
         if (is_shard(prob) || prob->M_dense) throw std::domain_error("proxsdp_host_model_rows_plan does not serve a shard of a block-sharded solve or M_dense");
         const proxsdp::Prep P = proxsdp::prepare(*prob, nullptr, false, true);
         proxsdp::RowsPlan pl = proxsdp::plan_rows(P, prob->index_base, *ch);

@@ -8,7 +8,7 @@
 // the total order (v descending, then (l, m, code) ascending): clique_better of clique_cuts_host.hpp, with (l, m, code) as
 // the one number key = (l s + m) 4 + code.
 //
-// Device.  k_tri_gather builds the dense X.  Bases go through in batches of CLQ_WAVE-multiples so that t stays bounded:
+// Device.  dense_cone_matrix (model_call.hip.hpp) builds the dense X.  Bases go through in batches of CLQ_WAVE-multiples so that t stays bounded:
 // k_clique_rows writes t[l][b] (the base is the fast index; NaN at a base's own nodes, and in the columns that pad a batch to
 // whole waves, so that no comparison passes there and the sweep needs no membership test) and B[b].  k_clique_sweep: a
 // workgroup of 4 waves owns 64 bases, one per lane, and a range of 64 x 64 tiles of (l, m) pairs of the strict upper triangle;
@@ -20,7 +20,7 @@
 // a base.  The maximum under a total order does not depend on how the pairs were split: grid and batch are invisible.
 // The host half -- checks, order, serial restatement, normal form, merge, sort, rows -- is clique_cuts_host.hpp.
 #pragma once
-#include "triangle_cuts.hip.hpp"
+#include "model_call.hip.hpp"
 #include "clique_cuts_host.hpp"
 
 namespace proxsdp {
@@ -178,35 +178,10 @@ k_clique_best(const CliqueBest* __restrict__ part, int gx, int bp, CliqueBest* _
 inline void device_clique_cuts(hipStream_t st, const int64_t* ord_h, const long long* ord_d, int64_t s, int base, int cone,
                                proxsdp_clique_cuts& q) {
     const double t0 = now_s();
-    long long allocated = 0;
-    struct Count {
-        long long* prev;
-        explicit Count(long long* c) : prev(DevAccount::allocated) { DevAccount::allocated = c; }
-        ~Count() { DevAccount::allocated = prev; }
-    } counting(&allocated);
-    const int64_t N = s * (s + 1) / 2;
+    AllocCount counting;
     const int bq = q.base_size;
-    const std::string where = "proxsdp_clique_cuts: non-finite entry of primal in cone " + std::to_string(cone);
-    DevBuf<double> X((size_t)(s * s));
-    if (q.on_device) {
-        DevBuf<int> flag(1);
-        hipLaunchKernelGGL(dev::k_tri_gather, dim3(grid_for(s * s)), dim3(dev::TPB), 0, st, q.primal, ord_d, (int)s, X.p);
-        flag.zero(st);
-        hipLaunchKernelGGL(dev::k_exit_nonfinite, dim3(grid_for(s * s)), dim3(dev::TPB), 0, st, (const double*)X.p, (long long)(s * s), flag.p);
-        PX_HIP(hipGetLastError());
-        int bad = 0;
-        flag.download(&bad, 1, st);
-        PX_HIP(hipStreamSynchronize(st));
-        if (bad) throw std::invalid_argument(where);
-    } else {                                                        // the dense matrix formed on the host
-        for (int64_t e = 0; e < N; ++e)
-            if (!std::isfinite(q.primal[ord_h[e]])) throw std::invalid_argument(where);
-        std::vector<double> Xh((size_t)(s * s));
-        for (int64_t j = 0; j < s; ++j)
-            for (int64_t i = 0; i <= j; ++i) Xh[i * s + j] = Xh[j * s + i] = q.primal[ord_h[j * (j + 1) / 2 + i]];
-        X.upload(Xh.data(), Xh.size(), st);
-        PX_HIP(hipStreamSynchronize(st));
-    }
+    const DevBuf<double> X = dense_cone_matrix(st, q.primal, q.on_device != 0, ord_h, ord_d, s,
+                                               "proxsdp_clique_cuts: non-finite entry of primal in cone " + std::to_string(cone));
     // the launch: bp bases per batch in whole waves, gx workgroup columns over the NT tiles
     const int64_t want = q.batch > 0 ? q.batch : CLQ_DEFAULT_BATCH;
     const int bp = (int)((std::min<int64_t>(want, q.n_base) + CLQ_WAVE - 1) / CLQ_WAVE * CLQ_WAVE);
@@ -220,9 +195,7 @@ inline void device_clique_cuts(hipStream_t st, const int64_t* ord_h, const long 
     DevBuf<CliqueBest> part((size_t)gx * (size_t)bp), best_d((size_t)bp);
     std::vector<CliqueBest> best((size_t)q.n_base);
     std::vector<int> nodes_h((size_t)bp * (size_t)bq);
-    Event ev0, ev1;
-    ev0.create(); ev1.create();
-    double sweep_ms = 0.0;
+    StreamTimer sweeps(st);
     for (int64_t b0 = 0; b0 < q.n_base; b0 += bp) {
         const int nb = (int)std::min<int64_t>(bp, q.n_base - b0);
         for (int64_t e = 0; e < (int64_t)nb * bq; ++e) nodes_h[(size_t)e] = (int)q.base_nodes[b0 * bq + e];
@@ -236,23 +209,20 @@ inline void device_clique_cuts(hipStream_t st, const int64_t* ord_h, const long 
             hipLaunchKernelGGL(dev::k_clique_rows<5>, grid_rows, dim3(dev::TPB), 0, st, (const double*)X.p, (int)s,
                                (const int*)nodes_d.p, (const signed char*)sign_d.p, nb, bp, t.p, Bv.p);
         PX_HIP(hipGetLastError());
-        PX_HIP(hipEventRecord(ev0, st));
+        sweeps.start();
         hipLaunchKernelGGL(dev::k_clique_sweep, dim3((unsigned)gx, (unsigned)groups), dim3(dev::TPB), 0, st, (const double*)X.p,
                            (int)s, nt, (const double*)t.p, (const double*)Bv.p, bp, q.rhs, part.p);
         PX_HIP(hipGetLastError());
-        PX_HIP(hipEventRecord(ev1, st));
+        sweeps.stop();
         hipLaunchKernelGGL(dev::k_clique_best, dim3((unsigned)ceil_div(bp, dev::TPB)), dim3(dev::TPB), 0, st,
                            (const CliqueBest*)part.p, gx, bp, best_d.p);
         PX_HIP(hipGetLastError());
         best_d.download(best.data() + b0, (size_t)nb, st);
         PX_HIP(hipStreamSynchronize(st));                           // (the next batch overwrites the bases and t)
-        float ms = 0.f;
-        PX_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-        sweep_ms += (double)ms;
     }
     clique_write_rows(best, s, q, [&](int64_t i, int64_t j) { return ord_h[j * (j + 1) / 2 + i] + base; });
-    q.sweep_seconds = sweep_ms * 1e-3;
-    q.bytes_allocated = allocated;
+    q.sweep_seconds = sweeps.seconds();
+    q.bytes_allocated = counting.bytes;
     q.seconds = now_s() - t0;
 }
 

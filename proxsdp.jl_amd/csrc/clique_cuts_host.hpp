@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/proxsdp_hip.h"
+#include "struct_check.hpp"
 
 namespace proxsdp {
 
@@ -43,7 +44,7 @@ inline double clq_now_s() {
 // ---- what is decided on the host before a handle or a device is looked at
 inline void check_clique_struct(const proxsdp_clique_cuts* q, bool model_entry) {
     if (!q) throw std::invalid_argument("NULL proxsdp_clique_cuts");
-    if (q->struct_size != (int64_t)sizeof(proxsdp_clique_cuts)) throw std::invalid_argument("proxsdp_clique_cuts.struct_size mismatch");
+    check_struct_size(q, "proxsdp_clique_cuts");
     if (model_entry && q->on_device != 0 && q->on_device != 1) throw std::invalid_argument("proxsdp_clique_cuts.on_device must be 0 or 1");
     if (q->base_size != 3 && q->base_size != 5) throw std::invalid_argument("proxsdp_clique_cuts.base_size must be 3 or 5");
     if (q->n_base < 1 || q->n_base > CLQ_MAX_BASES) throw std::invalid_argument("proxsdp_clique_cuts.n_base must be 1 .. 65536");

@@ -21,7 +21,7 @@
 // The certificate's theorem (Higham, ASNA 2nd ed., Theorem 10.3) holds for any summation order and with fused multiply-adds:
 // contraction stays on in the factorisation and off where the header fixes bits (k_bound_dual_cone).
 #pragma once
-#include "exit_device.hip.hpp"
+#include "model_call.hip.hpp"
 #include "dual_bound_host.hpp"
 
 namespace proxsdp {
@@ -274,12 +274,7 @@ struct BoundModel {
 // variable in a PSD cone, not equilibrated).  Nothing of the handle is written.
 inline void device_dual_bound(hipStream_t st, const BoundModel& Md, proxsdp_dual_bound& q) {
     const double t0 = now_s();
-    long long allocated = 0;
-    struct Count {
-        long long* prev;
-        explicit Count(long long* c) : prev(DevAccount::allocated) { DevAccount::allocated = c; }
-        ~Count() { DevAccount::allocated = prev; }
-    } counting(&allocated);
+    AllocCount counting;
     const Prep& P = Md.P;
     const int64_t nb = (int64_t)P.blocks.size();
     // ---- the trace caps, from the host mirror of the current rows
@@ -378,7 +373,7 @@ inline void device_dual_bound(hipStream_t st, const BoundModel& Md, proxsdp_dual
     // ---- 4. the combination
     q.dual_objective = dD[0];
     q.bound = bound_combine(dD[0], dD[1], P.Q, nb, T.data(), q.lambda_lower, q.certified);
-    q.bytes_allocated = allocated;
+    q.bytes_allocated = counting.bytes;
     q.factor_seconds = factor_seconds;
     q.seconds = now_s() - t0;
 }

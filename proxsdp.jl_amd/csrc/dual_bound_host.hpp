@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 #include "prep.hpp"
+#include "struct_check.hpp"
 
 namespace proxsdp {
 
@@ -168,7 +169,7 @@ double bound_trace_cap(int64_t s, DiagCol&& diagcol, const Ptr* colptr, const Ro
 // what is decided on the host about the struct alone (p, m, n_psd: the model's); host duals and caps are checked here
 inline void check_bound_struct(const proxsdp_dual_bound* q, int64_t p, int64_t m, int64_t n_psd, bool handle) {
     if (!q) throw std::invalid_argument("NULL proxsdp_dual_bound");
-    if (q->struct_size != (int64_t)sizeof(proxsdp_dual_bound)) throw std::invalid_argument("proxsdp_dual_bound.struct_size mismatch");
+    check_struct_size(q, "proxsdp_dual_bound");
     if (q->on_device != 0 && q->on_device != 1) throw std::invalid_argument("proxsdp_dual_bound.on_device must be 0 or 1");
     if (!handle && q->on_device != 0) throw std::invalid_argument("proxsdp_host_dual_bound: on_device must be 0");
     if ((p > 0 && !q->dual_eq) || (m > 0 && !q->dual_in)) throw std::invalid_argument("proxsdp_dual_bound: dual_eq or dual_in is NULL");

@@ -128,9 +128,8 @@ k_exit_feas_fin(const double* __restrict__ part, int nwg, double* __restrict__ o
 }  // namespace dev
 
 // The finite check of data the caller holds on the device, before anything is written: one reduction per array src[q] of len[q]
-// doubles (null or empty: skipped) into flag[q] (cnt ints at least), read back together; throws by the first bad array's name
-inline void require_finite_device(hipStream_t st, DevBuf<int>& flag, int cnt, const double* const* src, const int64_t* len,
-                                  const char* const* name, const char* what) {
+// doubles (null or empty: skipped) into flag[q] (cnt ints at least), read back together.  Returns the first bad array, or -1
+inline int first_nonfinite_device(hipStream_t st, DevBuf<int>& flag, int cnt, const double* const* src, const int64_t* len) {
     flag.zero(st);
     for (int q = 0; q < cnt; ++q)
         if (src[q] && len[q] > 0)
@@ -140,7 +139,18 @@ inline void require_finite_device(hipStream_t st, DevBuf<int>& flag, int cnt, co
     flag.download(h.data(), (size_t)cnt, st);
     PX_HIP(hipStreamSynchronize(st));
     for (int q = 0; q < cnt; ++q)
-        if (h[q]) throw std::invalid_argument(std::string(what) + ": non-finite entry in " + name[q]);
+        if (h[q]) return q;
+    return -1;
+}
+// throws by the first bad array's name
+inline void require_finite_device(hipStream_t st, DevBuf<int>& flag, int cnt, const double* const* src, const int64_t* len,
+                                  const char* const* name, const char* what) {
+    const int q = first_nonfinite_device(st, flag, cnt, src, len);
+    if (q >= 0) throw std::invalid_argument(std::string(what) + ": non-finite entry in " + name[q]);
+}
+// one array, the whole message the caller's
+inline void require_finite_device(hipStream_t st, DevBuf<int>& flag, const double* v, int64_t len, const std::string& message) {
+    if (first_nonfinite_device(st, flag, 1, &v, &len) >= 0) throw std::invalid_argument(message);
 }
 
 // the in-place quirks of cache_solution (pdhg.jl:749-755): fix_diag_scaling on pair.x, then x = D x, y = E y

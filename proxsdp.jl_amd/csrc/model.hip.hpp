@@ -10,14 +10,20 @@
 // rows    = inequality rows added and dropped (model_rows.hip.hpp): a second RowState (solver.hip.hpp: every buffer sized by Q,
 //           nnz or the pattern) built for the new shape, filled from the live one through the plan's source maps, and exchanged
 //           with it; everything sized by n or a cone side stays
-// round   = a +-1 vector from a cone's factors against the current c (rounding.hip.hpp): reads the exit path's c, writes nothing
+// The tools read the handle and write nothing of it; their scratch is the call's own (bytes_allocated, not device_bytes):
+// triangles, cliques = the violated triangle rows of a cone, and given bases grown by two nodes (triangle_cuts.hip.hpp,
+//           clique_cuts.hip.hpp): read the cone's variable list
+// inactive_rows = the inequality rows that went slack (triangle_cuts.hip.hpp): reads m
+// round   = a +-1 vector from a cone's factors against the current c (rounding.hip.hpp): reads the exit path's c
 // bound   = a certified lower bound of the optimum from any dual point (dual_bound.hip.hpp): reads the exit path's c, values
-//           and [b; h] and the host mirror of the rows, writes nothing
-// The entry points (argument checks, error codes) are in capi.hip.
+//           and [b; h] and the host mirror of the rows
+// The entry points (argument checks, error codes) are in capi.hip; what a call needs round its kernels is model_call.hip.hpp.
 #pragma once
-#include "exit_device.hip.hpp"
+#include "model_call.hip.hpp"
 #include "model_update.hip.hpp"
 #include "model_rows.hip.hpp"
+#include "triangle_cuts.hip.hpp"
+#include "clique_cuts.hip.hpp"
 #include "rounding.hip.hpp"
 #include "dual_bound.hip.hpp"
 
@@ -233,12 +239,7 @@ struct proxsdp_model {
         RowsPlan pl = plan_rows(P, index_base, ch);
         PX_HIP(hipSetDevice(opt0.device_id));
         Accounting acct(*this);
-        long long allocated = 0;
-        struct Count {
-            long long* prev;
-            explicit Count(long long* c) : prev(DevAccount::allocated) { DevAccount::allocated = c; }
-            ~Count() { DevAccount::allocated = prev; }
-        } count(&allocated);
+        AllocCount counting;
         hipStream_t st = s.stream;
         const bool on_dev = ch.on_device != 0;
         const int64_t na = ch.n_add, nnz_add = pl.nnz_add;
@@ -314,30 +315,50 @@ struct proxsdp_model {
         PX_HIP(hipStreamSynchronize(st));
         ch.m_new = P.m; ch.nnz_new = P.nnz;
         if (ch.kept) std::copy(pl.kept.begin(), pl.kept.end(), ch.kept);
-        ch.bytes_allocated = allocated;
+        ch.bytes_allocated = counting.bytes;
         ch.seconds = now_s() - t0;
     }
 
-    // q: validated on the host against the cone (check_rounding_struct, check_rounding_factors).  The objective is the exit
-    // path's unscaled c, where the cone's entries are contiguous; nothing of the handle is written, the scratch is the call's
-    void round(proxsdp_rounding& q) {
-        using namespace proxsdp;
-        Solver& s = *S;
-        const BlockInfo& B = s.P.blocks[q.cone];
+    // ---- the tools.  The entry has refused what the host can decide; a method makes the handle's device current, takes the
+    // stream and the cone, and calls the tool's driver.  No Accounting: a tool's scratch is the call's.
+
+    // the PSD cone a struct names, or the refusal under the struct's name
+    const proxsdp::BlockInfo& cone(int64_t k, const char* who) const {
+        const std::vector<proxsdp::BlockInfo>& blocks = S->P.blocks;
+        if (k < 0 || k >= (int64_t)blocks.size()) throw std::invalid_argument(std::string(who) + ".cone is outside the model's PSD cones");
+        return blocks[(size_t)k];
+    }
+    hipStream_t enter() {
         PX_HIP(hipSetDevice(opt0.device_id));
-        s.restore_cert_data();                              // (a certificate search of the last solve zeroed c or [b; h])
-        device_round(s.stream, s.xd.c.p + B.off, B.n, q.cone, q);
+        return S->stream;
     }
 
-    // q: validated on the host (check_bound_struct); the model is one the call serves.  Nothing of the handle is written, the
-    // scratch is the call's
+    // the cone's variable list (0-based caller numbers) on the host and on the device: what the cut tools read
+    void triangles(proxsdp_triangle_cuts& tc) {
+        const proxsdp::BlockInfo& B = cone(tc.cone, "proxsdp_triangle_cuts");
+        proxsdp::device_triangle_cuts(enter(), S->P.ord.data() + B.off, ord_d.p + B.off, B.n, index_base, tc.cone, tc);
+    }
+    void cliques(proxsdp_clique_cuts& q) {
+        const proxsdp::BlockInfo& B = cone(q.cone, "proxsdp_clique_cuts");
+        proxsdp::device_clique_cuts(enter(), S->P.ord.data() + B.off, ord_d.p + B.off, B.n, index_base, q.cone, q);
+    }
+    void inactive_rows(proxsdp_inactive_rows& q) { proxsdp::inactive_rows(enter(), S->P.m, q); }
+
+    // The objective is the exit path's unscaled c, where the cone's entries are contiguous
+    void round(proxsdp_rounding& q) {
+        const proxsdp::BlockInfo& B = cone(q.cone, "proxsdp_rounding");
+        hipStream_t st = enter();
+        S->restore_cert_data();                             // (a certificate search of the last solve zeroed c or [b; h])
+        proxsdp::device_round(st, S->xd.c.p + B.off, B.n, q.cone, q);
+    }
+
+    // the model is one the call serves (the entry's refusals)
     void bound(proxsdp_dual_bound& q) {
-        using namespace proxsdp;
-        Solver& s = *S;
-        PX_HIP(hipSetDevice(opt0.device_id));
+        proxsdp::Solver& s = *S;
+        hipStream_t st = enter();
         s.restore_cert_data();                              // (a certificate search of the last solve zeroed c or [b; h])
-        const BoundModel md{s.P, s.rs.csc_ptr.p, s.rs.csc_row.p, s.rs.exit.cval.p, s.rs.exit.bh.p, s.xd.c.p, s.offdiag_d.p};
-        device_dual_bound(s.stream, md, q);
+        const proxsdp::BoundModel md{s.P, s.rs.csc_ptr.p, s.rs.csc_row.p, s.rs.exit.cval.p, s.rs.exit.bh.p, s.xd.c.p, s.offdiag_d.p};
+        proxsdp::device_dual_bound(st, md, q);
     }
 
     void info(proxsdp_model_info& out) const {

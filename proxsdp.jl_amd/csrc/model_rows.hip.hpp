@@ -18,6 +18,7 @@
 // arrays follow the map.
 #pragma once
 #include "model_update.hip.hpp"
+#include "struct_check.hpp"
 
 namespace proxsdp {
 namespace dev {
@@ -62,7 +63,7 @@ k_rows_bh(const int* __restrict__ src, long long Q, const double* __restrict__ o
 // ---- the checks of a change that need no model (capi.hip runs them before it looks at the handle)
 inline void check_rows_struct(const proxsdp_model_rows* ch) {
     if (!ch) throw std::invalid_argument("NULL change");
-    if (ch->struct_size != (int64_t)sizeof(proxsdp_model_rows)) throw std::invalid_argument("proxsdp_model_rows.struct_size mismatch");
+    check_struct_size(ch, "proxsdp_model_rows");
     if (ch->on_device != 0 && ch->on_device != 1) throw std::invalid_argument("proxsdp_model_rows.on_device must be 0 or 1");
     if (ch->n_drop < 0 || ch->n_add < 0) throw std::invalid_argument("proxsdp_model_rows: negative n_drop or n_add");
     if (ch->n_drop == 0 && ch->n_add == 0) throw std::invalid_argument("proxsdp_model_rows: n_drop and n_add are both 0");

@@ -26,7 +26,7 @@
 // Every kernel grid-strides over its work items, and nothing is accumulated across items: the result does not depend on
 // the launch.  The host half -- checks, weights, generator, best trial, serial restatement -- is rounding_host.hpp.
 #pragma once
-#include "solver.hip.hpp"
+#include "model_call.hip.hpp"
 #include "rounding_host.hpp"
 
 namespace proxsdp {
@@ -261,28 +261,16 @@ k_round_search(const unsigned long long* __restrict__ words, int s, int nwords, 
 // entries); q: checked by check_rounding_struct / check_rounding_factors; cone: for the messages
 inline void device_round(hipStream_t st, const double* cc_d, int64_t s, int cone, proxsdp_rounding& q) {
     const double t0 = now_s();
-    long long allocated = 0;
-    struct Count {
-        long long* prev;
-        explicit Count(long long* c) : prev(DevAccount::allocated) { DevAccount::allocated = c; }
-        ~Count() { DevAccount::allocated = prev; }
-    } counting(&allocated);
+    AllocCount counting;
     const int r = q.r, T = q.trials, nwords = T / 64;
-    const std::string where = " (proxsdp_rounding, cone " + std::to_string(cone) + ")";
     // ---- the factors: V on the device, the weights from host values
     DevBuf<double> Vbuf, w_d((size_t)r);
     const double* V_d = q.V;
     std::vector<double> vals((size_t)r);
     if (q.on_device) {
-        DevBuf<int> flag(1);
-        flag.zero(st);
-        hipLaunchKernelGGL(dev::k_exit_nonfinite, dim3(grid_for(s * r)), dim3(dev::TPB), 0, st, q.V, (long long)(s * r), flag.p);
-        PX_HIP(hipGetLastError());
-        int bad = 0;
-        flag.download(&bad, 1, st);
+        DevBuf<int> flag(1);                                        // (the check's wait brings the values too)
         PX_HIP(hipMemcpyAsync(vals.data(), q.values, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, st));
-        PX_HIP(hipStreamSynchronize(st));
-        if (bad) throw std::invalid_argument("proxsdp_rounding: non-finite entry in V" + where);
+        require_finite_device(st, flag, q.V, s * r, "proxsdp_rounding: non-finite entry in V (proxsdp_rounding, cone " + std::to_string(cone) + ")");
     } else {
         std::copy(q.values, q.values + r, vals.begin());
         Vbuf.alloc((size_t)(s * r));
@@ -326,9 +314,8 @@ inline void device_round(hipStream_t st, const double* cc_d, int64_t s, int cone
     const int lds_side = q.lds_side < 0 ? 0 : std::min(q.lds_side > 0 ? q.lds_side : ROUND_LDS_SIDE, ROUND_LDS_SIDE_MAX);
     const bool in_lds = s <= lds_side;
     const int gq = q.grid_search > 0 ? std::min(q.grid_search, nwords) : nwords;
-    Event ev0, ev1;
-    ev0.create(); ev1.create();
-    PX_HIP(hipEventRecord(ev0, st));
+    StreamTimer search(st);
+    search.start();
     if (in_lds)
         hipLaunchKernelGGL(dev::k_round_search<true>, dim3(gq), dim3(dev::WAVE), (size_t)s * sizeof(unsigned long long), st,
                            (const unsigned long long*)words.p, (int)s, nwords, nnz, (const long long*)ptr_d.p, (const int*)acol.p,
@@ -338,7 +325,7 @@ inline void device_round(hipStream_t st, const double* cc_d, int64_t s, int cone
                            (const unsigned long long*)words.p, (int)s, nwords, nnz, (const long long*)ptr_d.p, (const int*)acol.p,
                            (const double*)aval.p, (const double*)diag_d.p, (int)q.max_sweeps, cols.p, vr.p, vf.p, wsweeps.p, wflips.p);
     PX_HIP(hipGetLastError());
-    PX_HIP(hipEventRecord(ev1, st));
+    search.stop();
     // ---- the best trial on the host, its column, the optional outputs
     std::vector<double> vr_h((size_t)T), vf_h((size_t)T);
     std::vector<int> sw_h((size_t)nwords);
@@ -371,10 +358,8 @@ inline void device_round(hipStream_t st, const double* cc_d, int64_t s, int cone
     q.best_trial = best; q.value = vf_h[(size_t)best]; q.value_rounded = vr_h[(size_t)round_best(vr_h.data(), T)];
     q.flips = 0; q.sweeps = 0;
     for (int tw = 0; tw < nwords; ++tw) { q.flips += fl_h[(size_t)tw]; q.sweeps = std::max<int32_t>(q.sweeps, sw_h[(size_t)tw]); }
-    float ms = 0.f;
-    PX_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-    q.search_seconds = (double)ms * 1e-3;
-    q.bytes_allocated = allocated;
+    q.search_seconds = search.seconds();
+    q.bytes_allocated = counting.bytes;
     q.seconds = now_s() - t0;
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/proxsdp_hip.h"
+#include "struct_check.hpp"
 
 namespace proxsdp {
 
@@ -54,7 +55,7 @@ inline void check_round_shape(int64_t r, int64_t trials) {
 // ---- what is decided on the host before a handle or a device is looked at
 inline void check_rounding_struct(const proxsdp_rounding* q, bool model_entry) {
     if (!q) throw std::invalid_argument("NULL proxsdp_rounding");
-    if (q->struct_size != (int64_t)sizeof(proxsdp_rounding)) throw std::invalid_argument("proxsdp_rounding.struct_size mismatch");
+    check_struct_size(q, "proxsdp_rounding");
     if (model_entry && q->on_device != 0 && q->on_device != 1) throw std::invalid_argument("proxsdp_rounding.on_device must be 0 or 1");
     if (!q->V || !q->values || !q->signs) throw std::invalid_argument("proxsdp_rounding: V, values or signs is NULL");
     check_round_shape(q->r, q->trials);

@@ -10,7 +10,7 @@
 // (< 2^50 for every side a cone may have), and v > min_violation >= 0 makes the bit image of v monotone, so the order is the
 // descending order of ONE 128-bit key:  K = bits(v) : (2^50 - 1 - lin) << 14.
 //
-// Device.  k_tri_gather builds the dense symmetric X from the primal vector through the cone's variable list.  k_tri_sweep
+// Device.  dense_cone_matrix (model_call.hip.hpp) builds the dense symmetric X from the primal vector.  k_tri_sweep
 // visits every triple: a workgroup owns a 64 x 64 tile of (i, j) pairs (tiles with block row <= block column, pairs with
 // i >= j masked) and up to TRI_KG chunks of 64 values of k from the tile's j-block upward; the rows X[k, I] and X[k, J] of a
 // chunk are staged in LDS (X is symmetric: the tile [k][row] is read from global memory along `row`, contiguously, and read
@@ -27,7 +27,7 @@
 // The host half -- argument checks, the order, the decoding of a row, the serial restatement, the gate -- is
 // triangle_cuts_host.hpp, which needs no HIP.
 #pragma once
-#include "solver.hip.hpp"
+#include "model_call.hip.hpp"
 #include "triangle_cuts_host.hpp"
 
 namespace proxsdp {
@@ -42,17 +42,6 @@ __host__ __device__ inline unsigned long long tri_key_lo(unsigned long long lin)
 }
 
 namespace dev {
-
-// X[i, j] = X[j, i] = primal[ord[tri_index(min, max)]]: ord = the cone's variable list (upper triangle, column by column)
-__global__ void __launch_bounds__(TPB)
-k_tri_gather(const double* __restrict__ primal, const long long* __restrict__ ord, int s, double* __restrict__ X) {
-    const long long total = (long long)s * s, stride = (long long)gridDim.x * TPB;
-    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total; e += stride) {
-        const long long i = e / s, j = e - i * s;
-        const long long lo = i < j ? i : j, hi = i < j ? j : i;
-        X[e] = primal[ord[hi * (hi + 1) / 2 + lo]];
-    }
-}
 
 // one row past the gate.  MODE 0: its digit is counted when the higher digits equal P, the digit lying inside the bits of v
 // (shift >= 64: lin is not needed and never formed); MODE 2: the same for any digit; MODE 1: the row is appended when its
@@ -214,50 +203,22 @@ k_inactive_rows(const double* __restrict__ dual, const double* __restrict__ slac
 inline void device_triangle_cuts(hipStream_t st, const int64_t* ord_h, const long long* ord_d, int64_t s, int base, int cone,
                                  proxsdp_triangle_cuts& tc) {
     const double t0 = now_s();
-    long long allocated = 0;
-    struct Count {
-        long long* prev;
-        explicit Count(long long* c) : prev(DevAccount::allocated) { DevAccount::allocated = c; }
-        ~Count() { DevAccount::allocated = prev; }
-    } counting(&allocated);
-    const int64_t N = s * (s + 1) / 2;
-    const std::string where = "proxsdp_triangle_cuts: non-finite entry of primal in cone " + std::to_string(cone);
+    AllocCount counting;
     const unsigned cap = (unsigned)std::max<int64_t>(tc.cand_cap > 0 ? tc.cand_cap : std::max<int64_t>(4 * tc.count, 65536), tc.count);
-    DevBuf<double> X((size_t)(s * s));
+    const DevBuf<double> X = dense_cone_matrix(st, tc.primal, tc.on_device != 0, ord_h, ord_d, s,
+                                               "proxsdp_triangle_cuts: non-finite entry of primal in cone " + std::to_string(cone));
     DevBuf<unsigned long long> hist((size_t)TRI_BINS), cand((size_t)2 * cap);
     DevBuf<unsigned> cursor(1);
-    DevBuf<int> flag(1);
-    if (tc.on_device) {
-        hipLaunchKernelGGL(dev::k_tri_gather, dim3(grid_for(s * s)), dim3(dev::TPB), 0, st, tc.primal, ord_d, (int)s, X.p);
-    } else {                                                        // the dense matrix formed on the host: no other scratch
-        for (int64_t q = 0; q < N; ++q)
-            if (!std::isfinite(tc.primal[ord_h[q]])) throw std::invalid_argument(where);
-        std::vector<double> Xh((size_t)(s * s));
-        for (int64_t j = 0; j < s; ++j)
-            for (int64_t i = 0; i <= j; ++i) Xh[i * s + j] = Xh[j * s + i] = tc.primal[ord_h[j * (j + 1) / 2 + i]];
-        X.upload(Xh.data(), Xh.size(), st);
-        PX_HIP(hipStreamSynchronize(st));
-    }
-    if (tc.on_device) {
-        flag.zero(st);
-        hipLaunchKernelGGL(dev::k_exit_nonfinite, dim3(grid_for(s * s)), dim3(dev::TPB), 0, st, (const double*)X.p, (long long)(s * s), flag.p);
-        PX_HIP(hipGetLastError());
-        int bad = 0;
-        flag.download(&bad, 1, st);
-        PX_HIP(hipStreamSynchronize(st));
-        if (bad) throw std::invalid_argument(where);
-    }
     const int nt = (int)((s + TRI_TILE - 1) / TRI_TILE);
     const dim3 grid((unsigned)(nt * (nt + 1) / 2), (unsigned)((nt + TRI_KG - 1) / TRI_KG));
-    Event ev0, ev1;
-    ev0.create(); ev1.create();
+    StreamTimer first_pass(st);
     int passes = 0;
     // mode 0: histogram, 1: emit; P holds 128 - shift bits (hist: less the digit's)
     auto sweep = [&](int mode, int shift, tri_u128 P) {
         const unsigned long long hi = (unsigned long long)(P >> 64), lo = (unsigned long long)P;
         const int pbits = 128 - shift - (mode == 0 ? TRI_DIGIT_BITS : 0);
         const double gate = tri_gate(tc.min_violation, P, pbits);
-        if (passes == 0) PX_HIP(hipEventRecord(ev0, st));
+        if (passes == 0) first_pass.start();
         if (mode == 0) {
             hist.zero(st);
             if (shift >= 64)
@@ -272,7 +233,7 @@ inline void device_triangle_cuts(hipStream_t st, const int64_t* ord_h, const lon
                                tc.rhs, shift, hi, lo, hist.p, cand.p, cursor.p, cap);
         }
         PX_HIP(hipGetLastError());
-        if (passes == 0) PX_HIP(hipEventRecord(ev1, st));
+        if (passes == 0) first_pass.stop();
         ++passes;
     };
     std::vector<unsigned long long> h((size_t)TRI_BINS);
@@ -312,12 +273,10 @@ inline void device_triangle_cuts(hipStream_t st, const int64_t* ord_h, const lon
     } else if (violated != 0) {
         throw std::logic_error("proxsdp_triangle_cuts: the radix select did not end");
     }
-    float ms = 0.f;
-    PX_HIP(hipEventElapsedTime(&ms, ev0, ev1));
     tri_write_rows(rows, s, tc, [&](int64_t i, int64_t j) { return ord_h[j * (j + 1) / 2 + i] + base; });
     tc.violated = (int64_t)violated; tc.scanned = tri_scanned(s); tc.passes = passes;
-    tc.sweep_seconds = (double)ms * 1e-3;
-    tc.bytes_allocated = allocated;
+    tc.sweep_seconds = first_pass.seconds();
+    tc.bytes_allocated = counting.bytes;
     tc.seconds = now_s() - t0;
 }
 

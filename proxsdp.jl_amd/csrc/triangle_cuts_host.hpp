@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/proxsdp_hip.h"
+#include "struct_check.hpp"
 
 namespace proxsdp {
 
@@ -30,7 +31,7 @@ typedef unsigned __int128 tri_u128;
 // ---- what is decided on the host before a handle or a device is looked at
 inline void check_triangle_struct(const proxsdp_triangle_cuts* tc, bool model_entry) {
     if (!tc) throw std::invalid_argument("NULL proxsdp_triangle_cuts");
-    if (tc->struct_size != (int64_t)sizeof(proxsdp_triangle_cuts)) throw std::invalid_argument("proxsdp_triangle_cuts.struct_size mismatch");
+    check_struct_size(tc, "proxsdp_triangle_cuts");
     if (model_entry && tc->on_device != 0 && tc->on_device != 1) throw std::invalid_argument("proxsdp_triangle_cuts.on_device must be 0 or 1");
     if (tc->count < 1 || tc->count > TRI_MAX_COUNT) throw std::invalid_argument("proxsdp_triangle_cuts.count must be 1 .. 2^20");
     if (!std::isfinite(tc->min_violation) || tc->min_violation < 0.0)
@@ -130,7 +131,7 @@ inline double tri_gate(double min_violation, tri_u128 P, int pbits) {
 // ---- rows that went slack
 inline void check_inactive_struct(const proxsdp_inactive_rows* q) {
     if (!q) throw std::invalid_argument("NULL proxsdp_inactive_rows");
-    if (q->struct_size != (int64_t)sizeof(proxsdp_inactive_rows)) throw std::invalid_argument("proxsdp_inactive_rows.struct_size mismatch");
+    check_struct_size(q, "proxsdp_inactive_rows");
     if (q->on_device != 0 && q->on_device != 1) throw std::invalid_argument("proxsdp_inactive_rows.on_device must be 0 or 1");
     if (!q->dual_in || !q->slack_in || !q->rows) throw std::invalid_argument("proxsdp_inactive_rows: NULL array");
     if (!std::isfinite(q->dual_tol) || q->dual_tol < 0.0 || !std::isfinite(q->slack_tol) || q->slack_tol < 0.0)
