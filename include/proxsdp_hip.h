@@ -100,7 +100,10 @@ extern "C" {
  * later: the test entry proxsdp_hip_operator_cycles (every cycle of a Lanczos run on the operator form: the block given as a
  * support list, its values and the previous projection's factors) with the new struct proxsdp_operator_cycles, and the host
  * entry proxsdp_host_block1_lds_doubles (the LDS plan of the one-workgroup cycle kernel): two functions and one new struct, no
- * existing struct changed: the version stays */
+ * existing struct changed: the version stays;
+ * later: the test entry proxsdp_hip_positive_part (one positive-part run of the Lanczos engine through the same observer, and
+ * its per-call certificate on the run's or on given locked pairs) with the new struct proxsdp_positive_part: one function and
+ * one new struct, no existing struct changed: the version stays */
 #define PROXSDP_HIP_ABI_VERSION 10
 
 /* error codes (negative return values) */
@@ -1669,6 +1672,60 @@ typedef struct {
     int32_t overflow_rows, reserved;
 } proxsdp_operator_cycles;
 int proxsdp_hip_operator_cycles(proxsdp_operator_cycles* t);
+
+/* ONE positive-part run of the Lanczos engine (full_eig! served by it: Solver::lanczos(W, xp, nev, true)) and its per-call
+ * certificate (Solver::lanczos_certificate), as Solver::full_eig_by_lanczos runs them one after the other.  The block, the
+ * options, the start vector and the per-cycle arrays are those of ONE of the two entries above: packed_run or operator_run, the
+ * other NULL; the struct pointed to is validated, prefilled and filled per cycle exactly as by its own entry, with two
+ * differences: the run is the positive-part run, and the workspace is sized for ws_rank pairs, cap = min(max(2 min(max(ws_rank,
+ * 2), n) + 1, eigsolver_min_lanczos), 255) + 1 columns (lanczos_wide_krylov is read as 0).  The caller states cap, and in the
+ * wrapped struct cols = krylovdim + 1 of the positive-part run: krylovdim = min(min(cap, 256) - 1, max(max(2 nev + 1,
+ * eigsolver_min_lanczos), nev kdim10 / 10 + 8)), kdim10 = full_eig_lanczos_kdim10 (30 when not positive) -- a small ws_rank
+ * gives the clipped dimension krylovdim = cap - 1.
+ * run = 1: the run.  converged / count / numiter: what it returned; vals[0 .. count); Z: its Ritz vectors, count columns at
+ * stride ldv, padding rows included; warm = 1 when lz_start_basis took the warm path (k_lz_warm_sum / k_lz_warm_scale).  vals
+ * and Z hold `sentinel` (the wrapped struct's) where nothing was written.  run = 0: no run; the wrapped struct's per-cycle arrays
+ * stay prefilled, cycles = 0, and the run's parameters and plan are set by lz_init / lz_plan alone.
+ * cert_steps >= 2: then the certificate.  It locks the run's own result (npos_in = -1, needs run = 1; skipped with cert_ran = 0
+ * when the run did not converge) or the caller's set: locked (n x npos_in, column-major, orthonormal), locked_vals (npos_in,
+ * descending as a run leaves them), npos_in >= 0, put where lz_finish_run leaves a run's result (columns 0 .. npos_in of the
+ * Ritz-vector buffer with zero padding rows, and the workspace's values).  Before the call the columns from npos on of that
+ * buffer are filled with the sentinel, padding rows included, and the columns 0 .. npos and the values are kept aside.
+ *   cert_ran: the function's return value (0 as well when npos + cert_steps + 1 > cap: nothing is written then);
+ *   npos: the locked pairs; theta_max, scale: its results; posres: the factor of the caller's test theta_max <= posres scale
+ *   (Solver::lanczos_posres); steps: the steps that formed the tridiagonal (after the cut at kstop), stop / kstop: the control
+ *   block; cert_alphas / cert_betas (cap each): [npos .. npos + cert_steps) from the record, the sentinel elsewhere;
+ *   basis (cap x ldv): the whole Ritz-vector buffer after the call; resid2 (ldv): the second start vector; differ: the number
+ *   of doubles of the columns 0 .. npos, padding rows included, and of the values whose bits are no longer those kept aside;
+ *   matvecs: the mat-vecs the certificate counted.
+ * Refused with PROXSDP_E_INVALID before a device is touched and before an output array is written: whatever the wrapped entry
+ * refuses but a Krylov-branch dimension max(2 nev + 1, eigsolver_min_lanczos) above 255 (the run's is clipped), both or neither of the two
+ * pointers, cap or cols not as stated, ws_rank < 1, run / cert_steps / npos_in out of range, run = 0 without a locked set,
+ * npos_in > n, a locked entry or value that is not finite, a NULL array. */
+typedef struct {
+    int64_t struct_size;
+    /* in */
+    proxsdp_lanczos_cycles* packed_run;          /* one of the two */
+    proxsdp_operator_cycles* operator_run;
+    int32_t ws_rank, cap, run, cert_steps;
+    int32_t npos_in, reserved;
+    const double* locked;                        /* n x npos_in */
+    const double* locked_vals;                   /* npos_in */
+    /* out: the run */
+    int32_t converged, count, numiter, warm;
+    double* vals;                                /* cap */
+    double* Z;                                   /* cap x ldv */
+    /* out: the certificate */
+    int32_t cert_ran, npos, steps, stop;
+    int32_t kstop, reserved2;
+    int64_t differ, matvecs;
+    double theta_max, scale, posres;
+    double* cert_alphas; double* cert_betas;     /* cap each */
+    double* basis;                               /* cap x ldv */
+    double* resid2;                              /* ldv */
+} proxsdp_positive_part;
+int proxsdp_hip_positive_part(proxsdp_positive_part* t);
+
 /* host only: the doubles of dynamic LDS the one-workgroup cycle kernel asks for (b1_lds_plan) at nt = ceil(n / 64) row blocks
  * -- fop = 0: the packed operator with a triangle of xN entries resident; fop = 1: the operator form with ell_w_lds ELL
  * columns of E resident (0: E read through L2).  -1: nt outside 1 .. 8, or a negative size. */

@@ -2267,16 +2267,15 @@ class LanczosCyclesIO(C.Structure):
                 ("npad", i32), ("krylovdim", i32), ("cycles", i32), ("reserved2", i32)]
 
 
-def lanczos_cycles(packed, n, nev, max_cycles, options=None, resid=None, sentinel=SYM_SENTINEL):
-    """proxsdp_hip_lanczos_cycles: every cycle of one run of Solver::lanczos, ended by the driver after max_cycles.  Returns a
-    dict: npad, krylovdim, and `cycles`, one dict per cycle the driver ran: kfirst, K (Kend), stop, engine ("step" / "block1" /
-    "wide"), split, speculated, merge_on_device, split_ready, kept_compared / kept_differ (the kept columns against a repeat of
-    the restart rotation: entries whose bits differ), V (npad, krylovdim + 1: the whole basis buffer), alphas, betas,
-    D, f (krylovdim + 1 each; what the cycle did not write holds `sentinel`)."""
+def _krylov_dim(o, nev):
+    return max(2 * int(nev) + 1, int(get_option(o, "eigsolver_min_lanczos")))
+
+
+def _lanczos_cycles_io(packed, n, nev, max_cycles, o, resid, sentinel, kd):
+    """proxsdp_lanczos_cycles for a run of Krylov dimension kd, filled in, and the function that decodes it after the call
+    (it keeps the arrays alive)"""
     x = _f(packed)
     assert len(x) == n * (n + 1) // 2
-    o = options if options is not None else default_options()
-    kd = max(2 * int(nev) + 1, int(get_option(o, "eigsolver_min_lanczos")))
     cols, npad, mc = kd + 1, 64 * ((n + 63) // 64), max(int(max_cycles), 1)
     t = LanczosCyclesIO()
     t.struct_size = C.sizeof(LanczosCyclesIO)
@@ -2290,13 +2289,28 @@ def lanczos_cycles(packed, n, nev, max_cycles, options=None, resid=None, sentine
     V = np.zeros((mc, cols, npad))
     al, be, D, f = (np.zeros((mc, cols)) for _ in range(4))
     t.info, t.V, t.alphas, t.betas, t.D, t.f = _p(info, pi32), _p(V), _p(al), _p(be), _p(D), _p(f)
+    keep = (x, o, r)
+
+    def decode():
+        assert t.npad == npad and t.krylovdim == kd and keep is not None
+        cyc = [dict(kfirst=int(info[c, 0]), K=int(info[c, 1]), stop=int(info[c, 2]), engine=LZ_ENGINES[int(info[c, 3])],
+                    split=bool(info[c, 4]), speculated=bool(info[c, 5]), merge_on_device=bool(info[c, 6]),
+                    split_ready=bool(info[c, 7]), kept_compared=bool(info[c, 8]), kept_differ=int(info[c, 9]), V=V[c].T, alphas=al[c], betas=be[c], D=D[c], f=f[c])
+               for c in range(t.cycles)]
+        return dict(npad=npad, krylovdim=kd, cycles=cyc, untouched=dict(info=info[t.cycles:], V=V[t.cycles:], alphas=al[t.cycles:]))
+    return t, decode
+
+
+def lanczos_cycles(packed, n, nev, max_cycles, options=None, resid=None, sentinel=SYM_SENTINEL):
+    """proxsdp_hip_lanczos_cycles: every cycle of one run of Solver::lanczos, ended by the driver after max_cycles.  Returns a
+    dict: npad, krylovdim, and `cycles`, one dict per cycle the driver ran: kfirst, K (Kend), stop, engine ("step" / "block1" /
+    "wide"), split, speculated, merge_on_device, split_ready, kept_compared / kept_differ (the kept columns against a repeat of
+    the restart rotation: entries whose bits differ), V (npad, krylovdim + 1: the whole basis buffer), alphas, betas,
+    D, f (krylovdim + 1 each; what the cycle did not write holds `sentinel`)."""
+    o = options if options is not None else default_options()
+    t, decode = _lanczos_cycles_io(packed, n, nev, max_cycles, o, resid, sentinel, _krylov_dim(o, nev))
     _check(lib().proxsdp_hip_lanczos_cycles(C.byref(t)))
-    assert t.npad == npad and t.krylovdim == kd
-    cyc = [dict(kfirst=int(info[c, 0]), K=int(info[c, 1]), stop=int(info[c, 2]), engine=LZ_ENGINES[int(info[c, 3])],
-                split=bool(info[c, 4]), speculated=bool(info[c, 5]), merge_on_device=bool(info[c, 6]),
-                split_ready=bool(info[c, 7]), kept_compared=bool(info[c, 8]), kept_differ=int(info[c, 9]), V=V[c].T, alphas=al[c], betas=be[c], D=D[c], f=f[c])
-           for c in range(t.cycles)]
-    return dict(npad=npad, krylovdim=kd, cycles=cyc, untouched=dict(info=info[t.cycles:], V=V[t.cycles:], alphas=al[t.cycles:]))
+    return decode()
 
 
 OP_INFO = 16                                                              # PROXSDP_OP_INFO
@@ -2315,14 +2329,9 @@ class OperatorCyclesIO(C.Structure):
                 ("npad", i32), ("krylovdim", i32), ("cycles", i32), ("ell_w", i32), ("overflow_rows", i32), ("reserved", i32)]
 
 
-def operator_cycles(n, support, values, F, lam, nev, max_cycles, options=None, resid=None, no_factors=False, f_first=0,
-                    other_half=None, probe_v=None, sentinel=SYM_SENTINEL):
-    """proxsdp_hip_operator_cycles: every cycle of one run of Solver::lanczos on the operator form A v = F (lam o F'v) + E v.
-    support: ascending packed indices of E's entries; values: theirs in svec units (off-diagonals carry the sqrt(2)); they go
-    into the half of the support-value array that the form reads (no_factors: the second), `other_half` (default NaN) into
-    the other.  F (n, rp), lam (rp).  Returns lanczos_cycles' dict; every cycle has besides: fop (the mat-vecs it ran on the
-    operator-form kernels), owner, nchp, ell_w, overflow_rows, ell_in_lds (None on the step kernels); the dict has ell_w,
-    overflow_rows and, with probe_v, probe = dict(ev (npad), tpart (nt, 128), apart (nt)) of one mat-vec launch."""
+def _operator_cycles_io(n, support, values, F, lam, nev, max_cycles, o, resid, no_factors, f_first, other_half, probe_v, sentinel, kd):
+    """proxsdp_operator_cycles for a run of Krylov dimension kd, filled in, and the function that decodes it after the call
+    (it keeps the arrays alive)"""
     supp = np.ascontiguousarray(support, dtype=np.int32)
     vals = _f(values)
     ns = len(supp)
@@ -2334,8 +2343,6 @@ def operator_cycles(n, support, values, F, lam, nev, max_cycles, options=None, r
     lm = _f(lam)
     rp = Fm.shape[1]
     assert len(lm) == rp
-    o = options if options is not None else default_options()
-    kd = max(2 * int(nev) + 1, int(get_option(o, "eigsolver_min_lanczos")))
     cols, npad, mc = kd + 1, 64 * ((n + 63) // 64), max(int(max_cycles), 1)
     nt = npad // 64
     t = OperatorCyclesIO()
@@ -2361,19 +2368,105 @@ def operator_cycles(n, support, values, F, lam, nev, max_cycles, options=None, r
     V = np.zeros((mc, cols, npad))
     al, be, D, f = (np.zeros((mc, cols)) for _ in range(4))
     t.info, t.V, t.alphas, t.betas, t.D, t.f = _p(info, pi32), _p(V), _p(al), _p(be), _p(D), _p(f)
+    keep = (supp, esv, Ff, lm, o, r, pv)
+
+    def decode():
+        assert keep is not None
+        assert t.npad == npad and t.krylovdim == kd
+        cyc = [dict(kfirst=int(info[c, 0]), K=int(info[c, 1]), stop=int(info[c, 2]), engine=LZ_ENGINES[int(info[c, 3])],
+                    split=bool(info[c, 4]), speculated=bool(info[c, 5]), merge_on_device=bool(info[c, 6]),
+                    split_ready=bool(info[c, 7]), kept_compared=bool(info[c, 8]), kept_differ=int(info[c, 9]),
+                    fop=int(info[c, 10]), owner=bool(info[c, 11]), nchp=int(info[c, 12]), ell_w=int(info[c, 13]),
+                    overflow_rows=int(info[c, 14]), ell_in_lds=None if info[c, 15] < 0 else bool(info[c, 15]),
+                    V=V[c].T, alphas=al[c], betas=be[c], D=D[c], f=f[c])
+               for c in range(t.cycles)]
+        out = dict(npad=npad, krylovdim=kd, cycles=cyc, ell_w=int(t.ell_w), overflow_rows=int(t.overflow_rows),
+                   untouched=dict(info=info[t.cycles:], V=V[t.cycles:], alphas=al[t.cycles:]))
+        if pv is not None:
+            out["probe"] = dict(ev=pev, tpart=ptp, apart=pap)
+        return out
+    return t, decode
+
+
+def operator_cycles(n, support, values, F, lam, nev, max_cycles, options=None, resid=None, no_factors=False, f_first=0,
+                    other_half=None, probe_v=None, sentinel=SYM_SENTINEL):
+    """proxsdp_hip_operator_cycles: every cycle of one run of Solver::lanczos on the operator form A v = F (lam o F'v) + E v.
+    support: ascending packed indices of E's entries; values: theirs in svec units (off-diagonals carry the sqrt(2)); they go
+    into the half of the support-value array that the form reads (no_factors: the second), `other_half` (default NaN) into
+    the other.  F (n, rp), lam (rp).  Returns lanczos_cycles' dict; every cycle has besides: fop (the mat-vecs it ran on the
+    operator-form kernels), owner, nchp, ell_w, overflow_rows, ell_in_lds (None on the step kernels); the dict has ell_w,
+    overflow_rows and, with probe_v, probe = dict(ev (npad), tpart (nt, 128), apart (nt)) of one mat-vec launch."""
+    o = options if options is not None else default_options()
+    t, decode = _operator_cycles_io(n, support, values, F, lam, nev, max_cycles, o, resid, no_factors, f_first, other_half, probe_v,
+                                    sentinel, _krylov_dim(o, nev))
     _check(lib().proxsdp_hip_operator_cycles(C.byref(t)))
-    assert t.npad == npad and t.krylovdim == kd
-    cyc = [dict(kfirst=int(info[c, 0]), K=int(info[c, 1]), stop=int(info[c, 2]), engine=LZ_ENGINES[int(info[c, 3])],
-                split=bool(info[c, 4]), speculated=bool(info[c, 5]), merge_on_device=bool(info[c, 6]),
-                split_ready=bool(info[c, 7]), kept_compared=bool(info[c, 8]), kept_differ=int(info[c, 9]),
-                fop=int(info[c, 10]), owner=bool(info[c, 11]), nchp=int(info[c, 12]), ell_w=int(info[c, 13]),
-                overflow_rows=int(info[c, 14]), ell_in_lds=None if info[c, 15] < 0 else bool(info[c, 15]),
-                V=V[c].T, alphas=al[c], betas=be[c], D=D[c], f=f[c])
-           for c in range(t.cycles)]
-    out = dict(npad=npad, krylovdim=kd, cycles=cyc, ell_w=int(t.ell_w), overflow_rows=int(t.overflow_rows),
-               untouched=dict(info=info[t.cycles:], V=V[t.cycles:], alphas=al[t.cycles:]))
-    if pv is not None:
-        out["probe"] = dict(ev=pev, tpart=ptp, apart=pap)
+    return decode()
+
+
+class PositivePartIO(C.Structure):
+    """proxsdp_positive_part (include/proxsdp_hip.h)"""
+    _fields_ = [("struct_size", i64),
+                ("packed_run", C.POINTER(LanczosCyclesIO)), ("operator_run", C.POINTER(OperatorCyclesIO)),
+                ("ws_rank", i32), ("cap", i32), ("run", i32), ("cert_steps", i32), ("npos_in", i32), ("reserved", i32),
+                ("locked", pf64), ("locked_vals", pf64),
+                ("converged", i32), ("count", i32), ("numiter", i32), ("warm", i32), ("vals", pf64), ("Z", pf64),
+                ("cert_ran", i32), ("npos", i32), ("steps", i32), ("stop", i32), ("kstop", i32), ("reserved2", i32),
+                ("differ", i64), ("matvecs", i64), ("theta_max", f64), ("scale", f64), ("posres", f64),
+                ("cert_alphas", pf64), ("cert_betas", pf64), ("basis", pf64), ("resid2", pf64)]
+
+
+def positive_part_dims(n, nev, ws_rank, options=None):
+    """(cap, krylovdim) of a positive-part run for nev pairs in a workspace sized for ws_rank pairs, as the header states them"""
+    o = options if options is not None else default_options()
+    kmin = int(get_option(o, "eigsolver_min_lanczos"))
+    k10 = int(get_option(o, "full_eig_lanczos_kdim10"))
+    cap = min(max(2 * min(max(int(ws_rank), 2), int(n)) + 1, kmin), 255) + 1
+    return cap, min(min(cap, 256) - 1, max(max(2 * int(nev) + 1, kmin), int(nev) * (k10 if k10 > 0 else 30) // 10 + 8))
+
+
+def positive_part(n, nev, ws_rank, max_cycles=1, packed=None, operator=None, options=None, resid=None, run=True, cert_steps=0,
+                  locked=None, locked_vals=None, sentinel=SYM_SENTINEL):
+    """proxsdp_hip_positive_part: one positive-part run of Solver::lanczos through the per-cycle observer, then
+    Solver::lanczos_certificate.  The block: `packed` (lanczos_cycles' argument) or `operator`, a dict of operator_cycles'
+    arguments (support, values, F, lam; no_factors, f_first, other_half).  locked (n, npos) / locked_vals: the pairs the
+    certificate locks in place of the run's.  Returns the wrapped entry's dict and: cap; with run: converged, count, numiter,
+    warm, vals (count), Z (npad, count); with cert_steps >= 2, cert = dict(ran, npos, steps, stop, kstop, theta_max, scale,
+    posres, differ, matvecs, alphas, betas (cap each), basis (npad, cap), resid2 (npad))."""
+    o = options if options is not None else default_options()
+    cap, kd = positive_part_dims(n, nev, ws_rank, o)
+    npad = 64 * ((n + 63) // 64)
+    p = PositivePartIO()
+    p.struct_size = C.sizeof(PositivePartIO)
+    p.ws_rank, p.cap, p.run, p.cert_steps, p.npos_in = int(ws_rank), cap, int(bool(run)), int(cert_steps), -1
+    if locked is not None:
+        Lk = np.asfortranarray(np.asarray(locked, dtype=np.float64).reshape(n, -1))
+        lv = _f(locked_vals)
+        assert len(lv) == Lk.shape[1]
+        Lf = Lk.ravel(order="F")
+        p.npos_in = Lk.shape[1]
+        if p.npos_in > 0:
+            p.locked, p.locked_vals = _p(Lf), _p(lv)
+    vals, al, be = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+    Z, basis, r2 = np.zeros((cap, npad)), np.zeros((cap, npad)), np.zeros(npad)
+    p.vals, p.Z, p.cert_alphas, p.cert_betas, p.basis, p.resid2 = _p(vals), _p(Z), _p(al), _p(be), _p(basis), _p(r2)
+
+    if packed is not None:
+        t, decode = _lanczos_cycles_io(packed, n, nev, max_cycles, o, resid, sentinel, kd)
+        p.packed_run = C.pointer(t)
+    else:
+        op = dict(operator)
+        t, decode = _operator_cycles_io(n, op["support"], op["values"], op["F"], op["lam"], nev, max_cycles, o, resid,
+                                        op.get("no_factors", False), op.get("f_first", 0), op.get("other_half"), op.get("probe_v"),
+                                        sentinel, kd)
+        p.operator_run = C.pointer(t)
+    _check(lib().proxsdp_hip_positive_part(C.byref(p)))
+    out = decode()
+    out.update(cap=cap, converged=bool(p.converged), count=int(p.count), numiter=int(p.numiter), warm=bool(p.warm),
+               vals=vals[:p.count].copy(), Z=Z[:p.count].T.copy())
+    if cert_steps >= 2:
+        out["cert"] = dict(ran=bool(p.cert_ran), npos=int(p.npos), steps=int(p.steps), stop=int(p.stop), kstop=int(p.kstop),
+                           theta_max=float(p.theta_max), scale=float(p.scale), posres=float(p.posres), differ=int(p.differ),
+                           matvecs=int(p.matvecs), alphas=al, betas=be, basis=basis.T, resid2=r2)
     return out
 
 

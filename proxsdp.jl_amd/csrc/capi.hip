@@ -1275,81 +1275,144 @@ int proxsdp_hip_tail_copy(proxsdp_tail_copy* t) {
     });
 }
 
-int proxsdp_hip_lanczos_cycles(proxsdp_lanczos_cycles* t) {
-    return guarded([&]() -> int {
-        if (!t) throw std::invalid_argument("NULL argument");
-        if (t->struct_size != (int64_t)sizeof(proxsdp_lanczos_cycles)) throw std::invalid_argument("lanczos cycles: struct_size mismatch");
-        if (t->n < 1 || t->n > 46340) throw std::invalid_argument("lanczos cycles: n out of range");
-        if (t->nev < 1 || t->nev > t->n) throw std::invalid_argument("lanczos cycles: nev must be 1 .. n");
-        if (t->max_cycles < 1) throw std::invalid_argument("lanczos cycles: max_cycles < 1");
-        if (!t->packed || !t->info || !t->V || !t->alphas || !t->betas || !t->D || !t->f) throw std::invalid_argument("lanczos cycles: NULL buffer");
-        proxsdp_options o = checked_options(t->opt);
-        if (o.lanczos_wide_krylov != 0 && o.lanczos_wide_krylov != 1) throw std::invalid_argument("lanczos_wide_krylov must be 0 or 1");
-        if (o.krylovkit_eager && o.eigsolver != 1) throw std::invalid_argument("lanczos cycles: krylovkit_eager runs another driver");
-        const int kd = std::max(2 * t->nev + 1, (int)o.eigsolver_min_lanczos);
-        if (kd > proxsdp::dev::LZ_KMAX && o.lanczos_wide_krylov != 1)
-            throw std::invalid_argument("lanczos cycles: a Krylov dimension > 255 needs the wide workspace (lanczos_wide_krylov = 1)");
-        if (kd > proxsdp::dev::LZW_MAXK - 1) throw std::invalid_argument("lanczos cycles: Krylov dimension beyond the workspace");
-        if (t->cols != kd + 1 || t->ldv != proxsdp::ceil_div(t->n, proxsdp::dev::TILE) * proxsdp::dev::TILE)
-            throw std::invalid_argument("lanczos cycles: cols must be krylovdim + 1, ldv 64 ceil(n / 64)");
-        o.krylovkit_max_iter = t->max_cycles; o.arpack_max_iter = t->max_cycles;   // the driver ends the run itself
-        // the caller's arrays hold the sentinel wherever the run writes nothing
-        const size_t nc = (size_t)t->max_cycles * t->cols;
-        std::fill(t->info, t->info + (size_t)t->max_cycles * PROXSDP_LZ_INFO, -1);
-        std::fill(t->V, t->V + nc * t->ldv, t->sentinel);
-        for (double* a : {t->alphas, t->betas, t->D, t->f}) std::fill(a, a + nc, t->sentinel);
-        t->npad = t->ldv; t->krylovdim = kd; t->cycles = 0;
-        Engine E(&o, t->n, t->nev);
-        E.set_resid(t->resid);
-        const int64_t N = (int64_t)t->n * (t->n + 1) / 2;
-        proxsdp::DevBuf<double> x(N);
-        x.upload(t->packed, N, E.S.stream);
-        E.S.test_lanczos_cycles(*t, x.p);
-        return 0;
-    });
+// columns of the workspace Engine(&o, n, ws_rank) allocates (Solver::alloc_eigwork without the wide records)
+static int engine_cap(const proxsdp_options& o, int64_t n, int ws_rank) {
+    const int wsr = std::min<int>(std::max(ws_rank, 2), (int)n);
+    return std::min(std::max(2 * wsr + 1, (int)o.eigsolver_min_lanczos), proxsdp::dev::LZ_KMAX) + 1;
+}
+// The positive-part entry's own arguments (the wrapped struct's n is valid) and the Krylov dimension of its run in place of the
+// Krylov branch's kd (o.lanczos_wide_krylov is 0): checked before a device is touched and before an output array is written
+static int checked_positive_part_dim(const proxsdp_options& o, int64_t n, int nev, int kd, const proxsdp_positive_part& pp) {
+    if (pp.ws_rank < 1) throw std::invalid_argument("positive part: ws_rank < 1");
+    if (pp.run != 0 && pp.run != 1) throw std::invalid_argument("positive part: run must be 0 or 1");
+    if (pp.cert_steps < 0 || pp.cert_steps > proxsdp::dev::KLD) throw std::invalid_argument("positive part: cert_steps out of range");
+    if (pp.npos_in < -1 || pp.npos_in > n) throw std::invalid_argument("positive part: npos_in must be -1 .. n");
+    if (!pp.run && pp.npos_in < 0) throw std::invalid_argument("positive part: no run needs a locked set (npos_in >= 0)");
+    if (pp.npos_in > 0 && (!pp.locked || !pp.locked_vals)) throw std::invalid_argument("positive part: NULL locked set");
+    if (!pp.vals || !pp.Z || !pp.cert_alphas || !pp.cert_betas || !pp.basis || !pp.resid2) throw std::invalid_argument("positive part: NULL buffer");
+    for (int64_t q = 0; q < (int64_t)std::max(pp.npos_in, 0) * n; ++q)
+        if (!std::isfinite(pp.locked[q])) throw std::invalid_argument("positive part: a locked entry is not finite");
+    for (int32_t q = 0; q < pp.npos_in; ++q)
+        if (!std::isfinite(pp.locked_vals[q])) throw std::invalid_argument("positive part: a locked value is not finite");
+    if (o.eigsolver == 1) throw std::invalid_argument("positive part: eigsolver = 1 never takes the positive-part run");
+    const int cap = engine_cap(o, n, pp.ws_rank);
+    if (pp.cap != cap) throw std::invalid_argument("positive part: cap must be min(max(2 min(max(ws_rank, 2), n) + 1, eigsolver_min_lanczos), 255) + 1");
+    return proxsdp::lz_positive_part_dim(cap, kd, nev, (int)o.full_eig_lanczos_kdim10);
 }
 
+// the caller's arrays of a positive-part call hold the sentinel wherever nothing is written (after every argument check)
+static void prefill_positive_part(proxsdp_positive_part& t, int32_t ldv, double sentinel) {
+    const size_t cap = (size_t)t.cap;
+    for (double* a : {t.vals, t.cert_alphas, t.cert_betas}) std::fill(a, a + cap, sentinel);
+    std::fill(t.Z, t.Z + cap * ldv, sentinel);
+    std::fill(t.basis, t.basis + cap * ldv, sentinel);
+    std::fill(t.resid2, t.resid2 + ldv, sentinel);
+    t.converged = t.count = t.numiter = t.warm = 0;
+    t.cert_ran = t.npos = t.steps = t.stop = t.kstop = 0;
+    t.differ = t.matvecs = 0;
+    t.theta_max = t.scale = t.posres = 0.0;
+}
+
+// proxsdp_hip_lanczos_cycles; pp: the same block and arrays under proxsdp_hip_positive_part
+static void run_lanczos_cycles(proxsdp_lanczos_cycles* t, proxsdp_positive_part* pp) {
+    if (!t) throw std::invalid_argument("NULL argument");
+    if (t->struct_size != (int64_t)sizeof(proxsdp_lanczos_cycles)) throw std::invalid_argument("lanczos cycles: struct_size mismatch");
+    if (t->n < 1 || t->n > 46340) throw std::invalid_argument("lanczos cycles: n out of range");
+    if (t->nev < 1 || t->nev > t->n) throw std::invalid_argument("lanczos cycles: nev must be 1 .. n");
+    if (t->max_cycles < 1) throw std::invalid_argument("lanczos cycles: max_cycles < 1");
+    if (!t->packed || !t->info || !t->V || !t->alphas || !t->betas || !t->D || !t->f) throw std::invalid_argument("lanczos cycles: NULL buffer");
+    proxsdp_options o = checked_options(t->opt);
+    if (o.lanczos_wide_krylov != 0 && o.lanczos_wide_krylov != 1) throw std::invalid_argument("lanczos_wide_krylov must be 0 or 1");
+    if (o.krylovkit_eager && o.eigsolver != 1) throw std::invalid_argument("lanczos cycles: krylovkit_eager runs another driver");
+    if (pp) o.lanczos_wide_krylov = 0;               // (a positive-part run keeps the step kernels' columns)
+    const int kd = std::max(2 * t->nev + 1, (int)o.eigsolver_min_lanczos);
+    // (a positive-part run clips its dimension to the workspace: the Krylov branch's two refusals are not its own)
+    if (!pp && kd > proxsdp::dev::LZ_KMAX && o.lanczos_wide_krylov != 1)
+        throw std::invalid_argument("lanczos cycles: a Krylov dimension > 255 needs the wide workspace (lanczos_wide_krylov = 1)");
+    if (!pp && kd > proxsdp::dev::LZW_MAXK - 1) throw std::invalid_argument("lanczos cycles: Krylov dimension beyond the workspace");
+    const int kdr = pp ? checked_positive_part_dim(o, t->n, t->nev, kd, *pp) : kd;       // the run's
+    if (t->cols != kdr + 1 || t->ldv != proxsdp::ceil_div(t->n, proxsdp::dev::TILE) * proxsdp::dev::TILE)
+        throw std::invalid_argument("lanczos cycles: cols must be krylovdim + 1, ldv 64 ceil(n / 64)");
+    o.krylovkit_max_iter = t->max_cycles; o.arpack_max_iter = t->max_cycles;   // the driver ends the run itself
+    // the caller's arrays hold the sentinel wherever the run writes nothing
+    const size_t nc = (size_t)t->max_cycles * t->cols;
+    std::fill(t->info, t->info + (size_t)t->max_cycles * PROXSDP_LZ_INFO, -1);
+    std::fill(t->V, t->V + nc * t->ldv, t->sentinel);
+    for (double* a : {t->alphas, t->betas, t->D, t->f}) std::fill(a, a + nc, t->sentinel);
+    if (pp) prefill_positive_part(*pp, t->ldv, t->sentinel);
+    t->npad = t->ldv; t->krylovdim = kdr; t->cycles = 0;
+    Engine E(&o, t->n, pp ? pp->ws_rank : t->nev);
+    E.set_resid(t->resid);
+    const int64_t N = (int64_t)t->n * (t->n + 1) / 2;
+    proxsdp::DevBuf<double> x(N);
+    x.upload(t->packed, N, E.S.stream);
+    E.S.test_lanczos_cycles(*t, x.p, pp);
+}
+int proxsdp_hip_lanczos_cycles(proxsdp_lanczos_cycles* t) {
+    return guarded([&]() -> int { run_lanczos_cycles(t, nullptr); return 0; });
+}
+
+// proxsdp_hip_operator_cycles; pp: the same block and arrays under proxsdp_hip_positive_part
+static void run_operator_cycles(proxsdp_operator_cycles* t, proxsdp_positive_part* pp) {
+    if (!t) throw std::invalid_argument("NULL argument");
+    if (t->struct_size != (int64_t)sizeof(proxsdp_operator_cycles)) throw std::invalid_argument("operator cycles: struct_size mismatch");
+    if (t->n < 2 || t->n > 46340) throw std::invalid_argument("operator cycles: n must be 2 .. 46340");
+    if (t->nev < 1 || t->nev > t->n) throw std::invalid_argument("operator cycles: nev must be 1 .. n");
+    if (t->max_cycles < 1) throw std::invalid_argument("operator cycles: max_cycles < 1");
+    if (t->rp < 0 || t->rp > proxsdp::dev::RLD - 1 || t->rp > t->n) throw std::invalid_argument("operator cycles: rp must be 0 .. min(127, n)");
+    if (t->f_first < 0 || t->f_first > proxsdp::dev::RLD - 1) throw std::invalid_argument("operator cycles: f_first must be 0 .. 127");
+    if (t->no_factors != 0 && t->no_factors != 1) throw std::invalid_argument("operator cycles: no_factors must be 0 or 1");
+    if (t->no_factors && t->rp != 0) throw std::invalid_argument("operator cycles: the second form has no factors (rp = 0)");
+    const int64_t N = (int64_t)t->n * (t->n + 1) / 2;
+    if (t->ns < 0 || t->ns > N) throw std::invalid_argument("operator cycles: ns must be 0 .. n (n + 1) / 2");
+    if (!t->info || !t->V || !t->alphas || !t->betas || !t->D || !t->f || (t->ns > 0 && (!t->support || !t->esv)) ||
+        (t->rp > 0 && (!t->F || !t->lam)) || (t->probe_v && (!t->probe_ev || !t->probe_tpart || !t->probe_apart)))
+        throw std::invalid_argument("operator cycles: NULL buffer");
+    for (int64_t s = 0; s < t->ns; ++s)
+        if (t->support[s] < 0 || t->support[s] >= N || (s > 0 && t->support[s] <= t->support[s - 1]))
+            throw std::invalid_argument("operator cycles: support indices must be strictly ascending and below n (n + 1) / 2");
+    auto finite = [](const double* a, size_t cnt) { for (size_t q = 0; q < cnt; ++q) if (!std::isfinite(a[q])) return false; return true; };
+    if (t->ns > 0 && !finite(t->esv + (t->no_factors ? t->ns : 0), (size_t)t->ns)) throw std::invalid_argument("operator cycles: a support value is not finite");
+    if (t->rp > 0 && (!finite(t->F, (size_t)t->n * t->rp) || !finite(t->lam, t->rp))) throw std::invalid_argument("operator cycles: a factor entry is not finite");
+    for (int c = 0; c < t->rp; ++c) if (!(t->lam[c] > 0.0)) throw std::invalid_argument("operator cycles: lam must be positive");
+    if ((t->resid && !finite(t->resid, t->n)) || (t->probe_v && !finite(t->probe_v, t->n))) throw std::invalid_argument("operator cycles: a vector entry is not finite");
+    proxsdp_options o = checked_options(t->opt);
+    if (o.lanczos_operator == 0) throw std::invalid_argument("operator cycles: lanczos_operator = 0 switches the operator form off");
+    if (o.krylovkit_eager && o.eigsolver != 1) throw std::invalid_argument("operator cycles: krylovkit_eager runs another driver");
+    const int kd = std::max(2 * t->nev + 1, (int)o.eigsolver_min_lanczos);
+    if (!pp && kd > proxsdp::dev::LZ_KMAX) throw std::invalid_argument("operator cycles: the operator form takes a Krylov dimension of at most 255");
+    o.lanczos_wide_krylov = 0;
+    const int kdr = pp ? checked_positive_part_dim(o, t->n, t->nev, kd, *pp) : kd;       // the run's (clipped to the workspace)
+    if (t->cols != kdr + 1 || t->ldv != proxsdp::ceil_div(t->n, proxsdp::dev::TILE) * proxsdp::dev::TILE)
+        throw std::invalid_argument("operator cycles: cols must be krylovdim + 1, ldv 64 ceil(n / 64)");
+    o.krylovkit_max_iter = t->max_cycles; o.arpack_max_iter = t->max_cycles;   // the driver ends the run itself
+    const size_t nc = (size_t)t->max_cycles * t->cols;
+    std::fill(t->info, t->info + (size_t)t->max_cycles * PROXSDP_OP_INFO, -1);
+    std::fill(t->V, t->V + nc * t->ldv, t->sentinel);
+    for (double* a : {t->alphas, t->betas, t->D, t->f}) std::fill(a, a + nc, t->sentinel);
+    if (pp) prefill_positive_part(*pp, t->ldv, t->sentinel);
+    t->npad = t->ldv; t->krylovdim = kdr; t->cycles = 0; t->ell_w = 0; t->overflow_rows = 0;
+    Engine E(&o, t->n, pp ? pp->ws_rank : t->nev);
+    E.set_resid(t->resid);
+    E.S.test_operator_cycles(*t, pp);
+}
 int proxsdp_hip_operator_cycles(proxsdp_operator_cycles* t) {
+    return guarded([&]() -> int { run_operator_cycles(t, nullptr); return 0; });
+}
+
+static_assert(sizeof(proxsdp_positive_part) == 192 && offsetof(proxsdp_positive_part, locked) == 48 &&
+              offsetof(proxsdp_positive_part, cert_ran) == 96 && offsetof(proxsdp_positive_part, differ) == 120 &&
+              offsetof(proxsdp_positive_part, resid2) == 184, "proxsdp_positive_part: the layout tests/test_host_abi.py states");
+int proxsdp_hip_positive_part(proxsdp_positive_part* t) {
     return guarded([&]() -> int {
         if (!t) throw std::invalid_argument("NULL argument");
-        if (t->struct_size != (int64_t)sizeof(proxsdp_operator_cycles)) throw std::invalid_argument("operator cycles: struct_size mismatch");
-        if (t->n < 2 || t->n > 46340) throw std::invalid_argument("operator cycles: n must be 2 .. 46340");
-        if (t->nev < 1 || t->nev > t->n) throw std::invalid_argument("operator cycles: nev must be 1 .. n");
-        if (t->max_cycles < 1) throw std::invalid_argument("operator cycles: max_cycles < 1");
-        if (t->rp < 0 || t->rp > proxsdp::dev::RLD - 1 || t->rp > t->n) throw std::invalid_argument("operator cycles: rp must be 0 .. min(127, n)");
-        if (t->f_first < 0 || t->f_first > proxsdp::dev::RLD - 1) throw std::invalid_argument("operator cycles: f_first must be 0 .. 127");
-        if (t->no_factors != 0 && t->no_factors != 1) throw std::invalid_argument("operator cycles: no_factors must be 0 or 1");
-        if (t->no_factors && t->rp != 0) throw std::invalid_argument("operator cycles: the second form has no factors (rp = 0)");
-        const int64_t N = (int64_t)t->n * (t->n + 1) / 2;
-        if (t->ns < 0 || t->ns > N) throw std::invalid_argument("operator cycles: ns must be 0 .. n (n + 1) / 2");
-        if (!t->info || !t->V || !t->alphas || !t->betas || !t->D || !t->f || (t->ns > 0 && (!t->support || !t->esv)) ||
-            (t->rp > 0 && (!t->F || !t->lam)) || (t->probe_v && (!t->probe_ev || !t->probe_tpart || !t->probe_apart)))
-            throw std::invalid_argument("operator cycles: NULL buffer");
-        for (int64_t s = 0; s < t->ns; ++s)
-            if (t->support[s] < 0 || t->support[s] >= N || (s > 0 && t->support[s] <= t->support[s - 1]))
-                throw std::invalid_argument("operator cycles: support indices must be strictly ascending and below n (n + 1) / 2");
-        auto finite = [](const double* a, size_t cnt) { for (size_t q = 0; q < cnt; ++q) if (!std::isfinite(a[q])) return false; return true; };
-        if (t->ns > 0 && !finite(t->esv + (t->no_factors ? t->ns : 0), (size_t)t->ns)) throw std::invalid_argument("operator cycles: a support value is not finite");
-        if (t->rp > 0 && (!finite(t->F, (size_t)t->n * t->rp) || !finite(t->lam, t->rp))) throw std::invalid_argument("operator cycles: a factor entry is not finite");
-        for (int c = 0; c < t->rp; ++c) if (!(t->lam[c] > 0.0)) throw std::invalid_argument("operator cycles: lam must be positive");
-        if ((t->resid && !finite(t->resid, t->n)) || (t->probe_v && !finite(t->probe_v, t->n))) throw std::invalid_argument("operator cycles: a vector entry is not finite");
-        proxsdp_options o = checked_options(t->opt);
-        if (o.lanczos_operator == 0) throw std::invalid_argument("operator cycles: lanczos_operator = 0 switches the operator form off");
-        if (o.krylovkit_eager && o.eigsolver != 1) throw std::invalid_argument("operator cycles: krylovkit_eager runs another driver");
-        const int kd = std::max(2 * t->nev + 1, (int)o.eigsolver_min_lanczos);
-        if (kd > proxsdp::dev::LZ_KMAX) throw std::invalid_argument("operator cycles: the operator form takes a Krylov dimension of at most 255");
-        if (t->cols != kd + 1 || t->ldv != proxsdp::ceil_div(t->n, proxsdp::dev::TILE) * proxsdp::dev::TILE)
-            throw std::invalid_argument("operator cycles: cols must be krylovdim + 1, ldv 64 ceil(n / 64)");
-        o.lanczos_wide_krylov = 0;
-        o.krylovkit_max_iter = t->max_cycles; o.arpack_max_iter = t->max_cycles;   // the driver ends the run itself
-        const size_t nc = (size_t)t->max_cycles * t->cols;
-        std::fill(t->info, t->info + (size_t)t->max_cycles * PROXSDP_OP_INFO, -1);
-        std::fill(t->V, t->V + nc * t->ldv, t->sentinel);
-        for (double* a : {t->alphas, t->betas, t->D, t->f}) std::fill(a, a + nc, t->sentinel);
-        t->npad = t->ldv; t->krylovdim = kd; t->cycles = 0; t->ell_w = 0; t->overflow_rows = 0;
-        Engine E(&o, t->n, t->nev);
-        E.set_resid(t->resid);
-        E.S.test_operator_cycles(*t);
+        if (t->struct_size != (int64_t)sizeof(proxsdp_positive_part)) throw std::invalid_argument("positive part: struct_size mismatch");
+        if ((t->packed_run != nullptr) == (t->operator_run != nullptr)) throw std::invalid_argument("positive part: one of packed_run and operator_run");
+        // (the wrapped struct's own entry code checks its struct_size before a field of it is read; this entry's arguments are
+        // checked and its arrays prefilled there too, behind the wrapped struct's)
+        if (t->cap < 2 || t->cap > proxsdp::dev::KLD) throw std::invalid_argument("positive part: cap out of range");
+        if (t->packed_run) run_lanczos_cycles(t->packed_run, t);
+        else run_operator_cycles(t->operator_run, t);
         return 0;
     });
 }

@@ -324,6 +324,13 @@ inline void Solver::flush_rotations(RotSink& S, BatchCtx& C) {
 }
 
 // ------------------------------------------------------------------ Lanczos (KrylovKit eigsolve)
+// Krylov dimension of a positive-part run for nev pairs in a workspace of `cap` columns, krylovdim = krylov_dim(nev)
+// (the engine keeps the step kernels' 255 columns in a wide workspace too)
+static inline int lz_positive_part_dim(int cap, int krylovdim, int nev, int kdim10) {
+    const int mult10 = kdim10 > 0 ? kdim10 : 30;
+    return std::min(std::min(cap, dev::MAXK - 4) - 1, std::max(krylovdim, nev * mult10 / 10 + 8));
+}
+
 // eigsolver.jl:798-823 -> KrylovKit.eigsolve(A, resid, nev, :LR, Lanczos(orth, krylovdim, maxiter, tol))
 // with A = Symmetric(smat(xp)).  eigsolver == 1 selects ARPACK's acceptance rule
 // (dsaupd: |resid_i| <= tol*max(eps^(2/3), |theta_i|) for all nev wanted values,
@@ -348,11 +355,7 @@ inline bool Solver::lz_init(EigWork& W, LzRun& R, int nev, bool positive_part) {
     int krylovdim = krylov_dim(nev);
     // positive-part mode is the library's own algorithm (not KrylovKit's call): a larger Krylov space
     // resolves the bulk-edge pairs that decide it with fewer restarts (options.full_eig_lanczos_kdim10)
-    if (positive_part) {
-        const int mult10 = opt.full_eig_lanczos_kdim10 > 0 ? opt.full_eig_lanczos_kdim10 : 30;
-        // (the engine keeps the step kernels' 255 columns in a wide workspace too)
-        krylovdim = std::min(std::min(W.cap, dev::MAXK - 4) - 1, std::max(krylovdim, nev * mult10 / 10 + 8));
-    }
+    if (positive_part) krylovdim = lz_positive_part_dim(W.cap, krylovdim, nev, (int)opt.full_eig_lanczos_kdim10);
     if (krylovdim + 1 > W.cap) throw std::invalid_argument("Lanczos workspace too small for the requested rank");
     R.krylovdim = krylovdim;
     if (krylovdim > dev::LZ_KMAX && !W.wide) throw std::logic_error("wide Lanczos: workspace has no wide records");
@@ -863,6 +866,11 @@ inline void Solver::lanczos_eager(EigWork& W, const double* xp, int nev) {
 // must be <= 0; the largest Ritz value of the msteps x msteps tridiagonal is a LOWER bound of the largest remaining
 // eigenvalue and converges to an isolated one within a few steps.  Returns false when the check could not run (workspace
 // too small, non-finite coefficients); theta_max / scale are what the caller tests.
+// What ten steps of the plain fp64 recurrence give (NumPy, tests/positive_part_cases.py certificate_reference; sides 130, 257,
+// 520, 0 .. 100 locked pairs 9 .. 1, the rest in [-3, -0.5], 5 seeds): theta_max in [-0.61, -0.50] when nothing positive is left;
+// 7.000 to four digits with one eigenvalue 7 outside the locked pairs; anywhere in [-0.11, 1e-3] with one at 1e-3 -- ten steps do
+// not promise to find a small isolated positive value (the device's values: profiles/positive_part.md; the kernels of this
+// function against that recurrence: tests/test_positive_part.py).
 inline bool Solver::lanczos_certificate(EigWork& W, const double* xp, int npos, int msteps, double& theta_max, double& scale) {
     if (npos + msteps + 1 > W.cap || npos + msteps + 1 > dev::KLD || msteps < 2) return false;
     if (W.resid2.n == 0) {

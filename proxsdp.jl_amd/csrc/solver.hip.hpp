@@ -706,8 +706,9 @@ public:
     void test_reconstruct_fused(proxsdp_reconstruct_fused& t);
     void test_rotate(proxsdp_rotation& t);
     void test_tail_copy(proxsdp_tail_copy& t);
-    void test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double* xp);
-    void test_operator_cycles(proxsdp_operator_cycles& t);
+    void test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double* xp, proxsdp_positive_part* pp = nullptr);
+    void test_operator_cycles(proxsdp_operator_cycles& t, proxsdp_positive_part* pp = nullptr);
+    void test_positive_part(proxsdp_positive_part& t, const struct LzCycleSink& out, const double* xp, int n);
     void test_observed_run(const struct LzCycleSink& out, const double* xp);
     void launch_tail_copy(const double* xin, double* xout);
     void test_sign_unpack(const double* packed, double sentinel, double* A, double* sc);

@@ -332,6 +332,7 @@ struct LzCycleSink {
     int32_t* info; double* V; double* alphas; double* betas; double* D; double* f;
     int32_t* cycles;
     std::function<void(EigWork&, LzRun&, int32_t*)> more;
+    bool positive_part = false;                  // the run is lanczos(W, xp, nev, true) (proxsdp_hip_positive_part)
 };
 
 // Every cycle of ONE run of Solver::lanczos (include/proxsdp_hip.h proxsdp_lanczos_cycles, proxsdp_operator_cycles): the driver's
@@ -341,7 +342,8 @@ struct LzCycleSink {
 inline void Solver::test_observed_run(const LzCycleSink& t, const double* xp) {
     EigWork& W0 = eig[0];
     const int cols = t.cols, npad = W0.npad;
-    if (npad != t.ldv || cols > W0.cap || krylov_dim(t.nev) + 1 != cols) throw std::logic_error("lanczos cycles: the workspace is not the one asked for");
+    const int kd = t.positive_part ? lz_positive_part_dim(W0.cap, krylov_dim(t.nev), t.nev, (int)opt.full_eig_lanczos_kdim10) : krylov_dim(t.nev);
+    if (npad != t.ldv || cols > W0.cap || kd + 1 != cols) throw std::logic_error("lanczos cycles: the workspace is not the one asked for");
     int c = 0;
     DevBuf<double> again;
     std::vector<double> again_h;
@@ -387,21 +389,23 @@ inline void Solver::test_observed_run(const LzCycleSink& t, const double* xp) {
         *t.cycles = ++c;
     };
     lz_observer = &observe;
-    try { lanczos(W0, xp, t.nev); } catch (...) { lz_observer = nullptr; throw; }
+    try { lanczos(W0, xp, t.nev, t.positive_part); } catch (...) { lz_observer = nullptr; throw; }
     lz_observer = nullptr;
     PX_HIP(hipStreamSynchronize(stream));
     PX_HIP(hipGetLastError());
 }
-inline void Solver::test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double* xp) {
-    test_observed_run(LzCycleSink{t.nev, t.max_cycles, t.cols, t.ldv, PROXSDP_LZ_INFO, t.sentinel, t.info, t.V, t.alphas, t.betas,
-                                  t.D, t.f, &t.cycles, nullptr}, xp);
+inline void Solver::test_lanczos_cycles(proxsdp_lanczos_cycles& t, const double* xp, proxsdp_positive_part* pp) {
+    const LzCycleSink out{t.nev, t.max_cycles, t.cols, t.ldv, PROXSDP_LZ_INFO, t.sentinel, t.info, t.V, t.alphas, t.betas,
+                          t.D, t.f, &t.cycles, nullptr, pp != nullptr};
+    if (pp) test_positive_part(*pp, out, xp, t.n);
+    else test_observed_run(out, xp);
 }
 
 // The same run on the OPERATOR FORM (include/proxsdp_hip.h proxsdp_operator_cycles): the block is never given densely.  The
 // support list goes through build_block_operator -- setup_support's own ELL / overflow construction --, its values into the
 // support-value array, the factors where ritz_pairs_to_block leaves them (W.F from column F_first on, W.Flam), and the block is
 // armed as project_block arms it.  The capi entry validated every index, rank and value.
-inline void Solver::test_operator_cycles(proxsdp_operator_cycles& t) {
+inline void Solver::test_operator_cycles(proxsdp_operator_cycles& t, proxsdp_positive_part* pp) {
     EigWork& W = eig[0];
     const int n = W.n, npad = W.npad, rp = t.rp;
     ns = (int)t.ns;
@@ -456,8 +460,82 @@ inline void Solver::test_operator_cycles(proxsdp_operator_cycles& t) {
         info[14] = t.overflow_rows;
         info[15] = R.plan.engine == LzEngine::block1 ? (Wc.b1_ell_in_lds ? 1 : 0) : -1;
     };
-    try { test_observed_run(out, nullptr); } catch (...) { W.use_fop = false; throw; }
+    out.positive_part = pp != nullptr;
+    // (a positive-part run's certificate runs while use_fop is still set, as in full_eig_by_lanczos)
+    try {
+        if (pp) test_positive_part(*pp, out, nullptr, t.n);
+        else test_observed_run(out, nullptr);
+    } catch (...) { W.use_fop = false; throw; }
     W.use_fop = false;
+}
+
+// ONE positive-part run through the observed driver and its per-call certificate (include/proxsdp_hip.h proxsdp_positive_part),
+// in full_eig_by_lanczos's order: lanczos(W, xp, nev, true), then lanczos_certificate on the pairs the run left in W.Z / W.vals
+// -- or on the caller's, put there.  `out` is the wrapped entry's sink (positive_part set), eig[0] was sized for t.ws_rank
+// pairs; the capi entry validated every argument and prefilled the caller's arrays.
+inline void Solver::test_positive_part(proxsdp_positive_part& t, const LzCycleSink& out, const double* xp, int n) {
+    EigWork& W = eig[0];
+    const int npad = W.npad, cap = W.cap;
+    if (cap != t.cap || npad != out.ldv) throw std::logic_error("positive part: the workspace is not the one asked for");
+    if (t.run) {
+        const long long warm0 = W.lst.warm_starts;
+        test_observed_run(out, xp);
+        t.warm = W.lst.warm_starts > warm0 ? 1 : 0;
+        t.converged = W.converged ? 1 : 0; t.count = W.count; t.numiter = (int32_t)W.numiter;
+        std::copy(W.vals.begin(), W.vals.begin() + W.count, t.vals);
+        if (W.count > 0) W.Z.download(t.Z, (size_t)npad * W.count, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+    } else {
+        // no run: its parameters and its plan alone (the certificate launches under the plan of the run it certifies)
+        lz_init(W, W.lzrun, out.nev, true);
+        lz_plan(W, W.lzrun, true);
+    }
+    if (t.cert_steps < 2) return;
+    if (t.npos_in < 0 && !W.converged) return;             // (full_eig_by_lanczos certifies a converged run only)
+    const int npos = t.npos_in >= 0 ? t.npos_in : W.count;
+    t.npos = npos;
+    t.posres = lanczos_posres();
+    const bool fits = npos + t.cert_steps + 1 <= cap;
+    std::vector<double> h, before;
+    if (t.npos_in >= 0) {
+        W.vals.assign(t.locked_vals, t.locked_vals + npos);
+        W.count = npos;
+        if (fits && npos > 0) {
+            h.assign((size_t)npad * npos, 0.0);
+            for (int j = 0; j < npos; ++j) std::copy(t.locked + (size_t)j * n, t.locked + (size_t)j * n + n, h.begin() + (size_t)j * npad);
+            W.Z.upload(h.data(), h.size(), stream);
+            PX_HIP(hipStreamSynchronize(stream));
+        }
+    }
+    if (fits) {
+        h.assign((size_t)npad * (cap - npos), out.sentinel);
+        PX_HIP(hipMemcpyAsync(W.Z.p + (size_t)npos * npad, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        before.resize((size_t)npad * std::max(npos, 1));
+        if (npos > 0) W.Z.download(before.data(), (size_t)npad * npos, stream);
+        PX_HIP(hipStreamSynchronize(stream));
+    }
+    const std::vector<double> vals0 = W.vals;
+    const long long mv0 = W.lst.cert_matvecs;
+    double theta = 0.0, scale = 0.0;
+    t.cert_ran = lanczos_certificate(W, xp, npos, t.cert_steps, theta, scale) ? 1 : 0;
+    PX_HIP(hipStreamSynchronize(stream));
+    PX_HIP(hipGetLastError());
+    t.matvecs = W.lst.cert_matvecs - mv0;
+    if (!fits) return;                                      // (refused by the function before its first launch)
+    t.theta_max = theta; t.scale = scale;
+    const LzRecBuf narrow = W.record(false);
+    const LzRecord rec(narrow.host, narrow.ld);
+    t.stop = rec.ctl.stop; t.kstop = rec.ctl.kstop;
+    t.steps = rec.ctl.stop ? std::max(0, std::min(t.cert_steps, rec.ctl.kstop - npos)) : t.cert_steps;
+    for (int k = npos; k < npos + t.cert_steps; ++k) { t.cert_alphas[k] = rec.al[k]; t.cert_betas[k] = rec.be[k]; }
+    W.Z.download(t.basis, (size_t)npad * cap, stream);
+    W.resid2.download(t.resid2, npad, stream);
+    PX_HIP(hipStreamSynchronize(stream));
+    int64_t differ = 0;
+    for (size_t q = 0; q < (size_t)npad * npos; ++q) differ += std::memcmp(&before[q], &t.basis[q], sizeof(double)) != 0;
+    if (W.vals.size() != vals0.size()) differ += (int64_t)std::max(W.vals.size(), vals0.size());
+    else for (size_t q = 0; q < vals0.size(); ++q) differ += std::memcmp(&vals0[q], &W.vals[q], sizeof(double)) != 0;
+    t.differ = differ;
 }
 
 // The support path's copy of the non-PSD tail x[start .. N) (include/proxsdp_hip.h proxsdp_tail_copy) through launch_tail_copy,

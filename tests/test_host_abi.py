@@ -31,6 +31,20 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert L.proxsdp_hip_abi_version() == 10
 
 
+def test_positive_part_struct_size_and_offsets():
+    """proxsdp_positive_part beside the two structs it points to (their sizes: test_lanczos_cycles_host.py,
+    test_operator_cycles_host.py): every member is 4 or 8 bytes wide and the 4-byte ones come in pairs, so there is no padding"""
+    S = B.PositivePartIO
+    assert "proxsdp_hip_positive_part" in B.header_symbols()
+    assert ctypes.sizeof(S) == 8 + 8 * 2 + 4 * 6 + 8 * 2 + 4 * 4 + 8 * 2 + 4 * 6 + 8 * 2 + 8 * 3 + 8 * 4 == 192
+    want = dict(struct_size=0, packed_run=8, operator_run=16, ws_rank=24, cap=28, run=32, cert_steps=36, npos_in=40, locked=48,
+                locked_vals=56, converged=64, count=68, numiter=72, warm=76, vals=80, Z=88, cert_ran=96, npos=100, steps=104,
+                stop=108, kstop=112, differ=120, matvecs=128, theta_max=136, scale=144, posres=152, cert_alphas=160,
+                cert_betas=168, basis=176, resid2=184)
+    assert {k: getattr(S, k).offset for k in want} == want
+    assert ctypes.sizeof(B.LanczosCyclesIO) == 128 and ctypes.sizeof(B.OperatorCyclesIO) == 208
+
+
 def test_options_struct_layout_and_defaults_match_reference_options():
     o = B.default_options()
     assert o.struct_size == ctypes.sizeof(B.Options)

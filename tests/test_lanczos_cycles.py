@@ -14,6 +14,8 @@ padding rows, the start column, v_kfirst = the previous cycle's v_K bit for bit,
 
 Out of scope: lanczos_eager and lanczos_batch: bit-for-bit tests tie the batched path to the per-block one.  The operator form
 (k_fop*, k_lz_orth<., 1 | 2>, k_lz_block1<., true>) has a hook of its own, held to the same rule: test_operator_cycles.py.
+The positive-part run (full_eig! served by this engine: another Krylov dimension, acceptance rule and start) and its certificate
+(k_lz_measure, the step kernels from kfirst = npos) have theirs, held to the same rule too: test_positive_part.py.
 
 The kept columns: after a restart on the step or wide engine the entry repeats the restart rotation (Solver::rotate_launch on
 the previous basis and the coefficients still on the device) into a buffer of its own and counts the entries of the columns

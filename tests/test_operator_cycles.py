@@ -18,7 +18,8 @@ ELL width, the overflow rows, for block1 whether E sat in LDS.
 block1 against step: test_lanczos_cycles.py ties the two engines by nothing but the rule above (profiles/lanczos_cycles.md shows
 equal digits, no test asserts equal bits), so here too each engine stands on its own checks.
 
-Not reached: the lam-power weights of k_lz_warm_sum (positive-part runs only; the entry runs the Krylov branch's lanczos())."""
+Not reached here: the lam-power weights of k_lz_warm_sum (positive-part runs only; the entry runs the Krylov branch's lanczos()).
+They, the positive-part run and its certificate on the operator form are test_positive_part.py's."""
 from fractions import Fraction
 
 import numpy as np
